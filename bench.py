@@ -9,7 +9,12 @@ block arg-max) -> k_argmax_final, then (G > 1) ONE RCCL all-gather of the 16-byt
 record per GPU and the same reduction kernel on every GPU -- both inside libbohip, on the handle's stream;
 the 16-byte result lands in pinned host memory and is read after the stream synchronisation.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the side figures (model update and
+Cholesky, host-buffer entry point, default searches, Thompson, N = 10^4, measured HBM traffic, CPU baseline, R = 32768
+beside a weak-scaling run).  --dump-outputs DIR writes the last timed step's result record as DIR/best_value.npy and
+DIR/best_index.npy (float64); the inputs are seeded, so two builds can be compared output for output.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
              N = 1: one handle.  N > 1 without a launcher: ONE process drives N devices through the
              in-library multi-GPU entry points (bohip_mgp_*: ncclCommInitAll, worker thread per device).
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -32,6 +37,9 @@ sys.path.insert(0, ROOT)
 N_OBS, DIM, R_PER_GPU = 3000, 8, 4096
 SPIN_S = float(os.environ.get("BOHIP_BENCH_SPIN_S", "4"))   # untimed repetition of the step for an outside activity sampler (reported as untimed_spin_s)
 STRONG_R_TOTAL = 32768   # --strong: BASELINE configs[2] (R = 32768 restarts in total) at every --gpus
+UNTIMED_MIN = 40         # untimed steps (the W warm-up steps included) before the bracket: the device reaches its working clocks
+#                          (one GPU, 30 timed steps: 2110-2120 MHz under k_trigemm_sq and +10 % per step after W = 5 alone,
+#                          2290-2300 MHz and the figure the side legs used to leave behind after 40)
 FP64_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix = vector peak (256 CU x 4 SIMD x 2.4 GHz x 32 FLOP/clk); the
 #                          MICROARCH guide lists no FP64 row; tools/ubench_fp64b.hip measures 73 TF/s sustained.
 
@@ -303,7 +311,7 @@ def report(args, world, elapsed, stage_sum, info_ms, fit_ms, val, idx, X, y, Xs_
     achieved = flops_per_launch / (tg_ms * 1e-3) / 1e12
     traffic, traffic_source = (None, "not measured on this rank")
     if world == 1 and not args.strong:
-        traffic, traffic_source = measure_traffic()
+        traffic, traffic_source = measure_traffic() if args.full else (None, "measured only under --full")
     if traffic is None:
         tpath = os.path.join(ROOT, "profiles", "traffic_trigemm_sq.json")
         why = traffic_source
@@ -339,14 +347,15 @@ def report(args, world, elapsed, stage_sum, info_ms, fit_ms, val, idx, X, y, Xs_
                          "profiles/ agrees).  Every other stage: event brackets of the warm-up steps with ALL stages bracketed -- a bracket adds "
                          "the launch gap and two event records (~10-12 us) to a short kernel: `kstar` reads ~40 us here where the kernel trace "
                          "says 28 us for k_kstar itself (2.5 vs 3.6 TB/s of K*' written); the trace is the kernel, the bracket is the stage",
-        "model_update_ms": fit_ms.get("model_update_ms", fit_ms),
-        "cholesky": ({"N": N_OBS, "gflops": fit_ms["cholesky_alone_tflops"] * 1e3,
-                      "sample": "median of 7 full refits with the executor's inverse queues off (factorisation alone)",
-                      **{k: v for k, v in fit_ms.items() if k != "model_update_ms"}} if "model_update_ms" in fit_ms else
-                     {"N": N_OBS, "note": "sharded run: stage times of one replica as shipped (factorisation + inverse are one stage "
-                                          "when the executor form runs); the one-GPU line carries the factorisation-alone figure"}),
         "best": {"value": val, "index": idx},
     }
+    if fit_ms:      # (a plain one-GPU run times no model update: refit_figures runs under --full)
+        out["model_update_ms"] = fit_ms.get("model_update_ms", fit_ms)
+        out["cholesky"] = ({"N": N_OBS, "gflops": fit_ms["cholesky_alone_tflops"] * 1e3,
+                            "sample": "median of 7 full refits with the executor's inverse queues off (factorisation alone)",
+                            **{k: v for k, v in fit_ms.items() if k != "model_update_ms"}} if "model_update_ms" in fit_ms else
+                           {"N": N_OBS, "note": "sharded run: stage times of one replica as shipped (factorisation + inverse are one stage "
+                                                "when the executor form runs); the one-GPU line carries the factorisation-alone figure"})
     if n_devices is not None and n_devices != world:
         # TEST mode (BOHIP_LOGICAL_SHARDS=1): `world` logical shards on n_devices GPU(s) -- NOT a multi-GPU measurement
         out["logical_shards"] = world
@@ -355,9 +364,19 @@ def report(args, world, elapsed, stage_sum, info_ms, fit_ms, val, idx, X, y, Xs_
         out["exchange_us"] = info_ms["exchange"] * 1e3
     if extra:
         out.update(extra)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(X, y, Xs_all, tau)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, val, idx)
     emit(json.dumps(out))
+
+
+def dump_outputs(path, val, idx):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the 16-byte (value, global index) record
+    of the arg-max -- as float64 arrays (the index is exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "best_value.npy"), np.array([val], dtype=np.float64))
+    np.save(os.path.join(path, "best_index.npy"), np.array([idx], dtype=np.float64))
 
 
 def timed(args, step, sync, barrier=None, barrier_after=True):
@@ -406,7 +425,7 @@ def main_single_process(args):
         model.enable_timing(True)
         model.append_(X.T, y)
         model.fit_()
-        fit_ms = refit_figures(model, N_OBS, 7)
+        fit_ms = refit_figures(model, N_OBS, 7) if args.full else {}
         dev = torch.device("cuda", 0)
         dXs = torch.from_numpy(np.ascontiguousarray(Xs_all)).to(dev)  # [R][d] = d x R column-major, resident in HBM
         # the 16-byte result record is written by the arg-max kernel straight into pinned host memory and read after
@@ -426,20 +445,24 @@ def main_single_process(args):
         for _ in range(args.warmup):
             step()
             info_ms = dict(model.timing())      # every stage bracketed by events: for the report only
-        # first the same call through the host-pointer entry point (H2D of the 256 KB of candidates inside the call): a
-        # reported side figure, never `value`
+        if args.full:
+            # first the same call through the host-pointer entry point (H2D of the 256 KB of candidates inside the call): a
+            # reported side figure, never `value`
+            model.enable_timing(0)
+            Xs_host = np.ascontiguousarray(Xs_all)
+            bestrec = _lib.Best()
+            xp = Xs_host.ctypes.data_as(C.POINTER(C.c_double))
+
+            def hstep():
+                _lib.check(lib.bohip_gp_score(model._h, _lib.ACQ["EI"], params, xp, R_GPU, None, C.byref(bestrec)))
+                return bestrec.val, bestrec.idx
+
+            for _ in range(3):
+                hstep()
+            el_h, (hv, hi) = timed(args, hstep, torch.cuda.synchronize)
         model.enable_timing(0)
-        Xs_host = np.ascontiguousarray(Xs_all)
-        bestrec = _lib.Best()
-        xp = Xs_host.ctypes.data_as(C.POINTER(C.c_double))
-
-        def hstep():
-            _lib.check(lib.bohip_gp_score(model._h, _lib.ACQ["EI"], params, xp, R_GPU, None, C.byref(bestrec)))
-            return bestrec.val, bestrec.idx
-
-        for _ in range(3):
-            hstep()
-        el_h, (hv, hi) = timed(args, hstep, torch.cuda.synchronize)
+        for _ in range(max(0, UNTIMED_MIN - args.warmup)):
+            step()
         # timed region: only the dominant kernel carries events (2 records per step), and they are READ after the loop
         # (mode 3): bracketing all stages costs ~25 us per step, reading the pair inside the loop another ~2 us
         model.enable_timing(3)
@@ -450,29 +473,31 @@ def main_single_process(args):
         for name, ms in model.timing(4096):
             stage_sum[name] = stage_sum.get(name, 0.0) + ms
         clock_mhz = model.info(_lib.INFO_KERNEL_CLOCK_MHZ)   # core clock under k_trigemm_sq over the timed region (sampled workgroups)
-        # UNTIMED: a few more seconds of the same step, so that a coarse GPU-activity sampler around this process (one sample every 5 s)
-        # sees the device busy (the timed region is ~20 ms of a run whose remainder is side figures and the CPU baseline); the JSON says
-        # so (untimed_spin_s).  BOHIP_BENCH_SPIN_S overrides.
-        model.enable_timing(0)
-        t_spin = time.perf_counter()
-        while time.perf_counter() - t_spin < SPIN_S:
-            step()
         n_launch = C.c_int64(0)
         _lib.check(lib.bohip_gp_info(model._h, _lib.INFO_SCORE_LAUNCHES, C.byref(n_launch)))
-        extra = {"_launches": int(n_launch.value), "_clock_mhz": clock_mhz, "value_host_buffers": R_total * args.steps / el_h, "ms_per_step_host_buffers": el_h / args.steps * 1e3,
-                 "host_buffers_note": "same workload through bohip_gp_score: host X* in (pageable, 256 KB H2D inside the "
-                                      "call), 16-byte record out; `value` is the HBM-resident rate",
-                 "host_buffers_same_winner": bool(hv == val and hi == idx)}
-        extra["untimed_spin_s"] = SPIN_S   # (gpu_busy of an outside sampler reflects this untimed repetition of the step, not the timed region)
-        extra["default_usage"] = default_usage(model, tau)
-        extra["default_usage_ei"] = default_usage(model, tau, "EI")
-        extra["thompson_default"] = thompson_default(model)
-        extra["thompson_c5"] = thompson_c5(model)
-        # (last user of `model`: the call changes the hyper-parameters' staleness, nothing after it looks at the model)
-        extra["mll_grad_ms"] = {"N=3000": mll_grad_ms(model)}      # value + gradient of the marginal likelihood (optimizemodel!)
-        if not args.no_c4:
-            extra["cholesky_c4"] = cholesky_c4(bohip)
-            extra["mll_grad_ms"]["N=10000"] = extra["cholesky_c4"].pop("_mll_grad_ms")
+        extra = {"_launches": int(n_launch.value), "_clock_mhz": clock_mhz}
+        if args.full:
+            # UNTIMED: a few more seconds of the same step, so that a coarse GPU-activity sampler around this process (one sample every 5 s)
+            # sees the device busy (the timed region is ~20 ms of a run whose remainder is side figures and the CPU baseline); the JSON says
+            # so (untimed_spin_s).  BOHIP_BENCH_SPIN_S overrides.
+            model.enable_timing(0)
+            t_spin = time.perf_counter()
+            while time.perf_counter() - t_spin < SPIN_S:
+                step()
+            extra.update({"value_host_buffers": R_total * args.steps / el_h, "ms_per_step_host_buffers": el_h / args.steps * 1e3,
+                          "host_buffers_note": "same workload through bohip_gp_score: host X* in (pageable, 256 KB H2D inside the "
+                                               "call), 16-byte record out; `value` is the HBM-resident rate",
+                          "host_buffers_same_winner": bool(hv == val and hi == idx)})
+            extra["untimed_spin_s"] = SPIN_S   # (gpu_busy of an outside sampler reflects this untimed repetition of the step, not the timed region)
+            extra["default_usage"] = default_usage(model, tau)
+            extra["default_usage_ei"] = default_usage(model, tau, "EI")
+            extra["thompson_default"] = thompson_default(model)
+            extra["thompson_c5"] = thompson_c5(model)
+            # (last user of `model`: the call changes the hyper-parameters' staleness, nothing after it looks at the model)
+            extra["mll_grad_ms"] = {"N=3000": mll_grad_ms(model)}      # value + gradient of the marginal likelihood (optimizemodel!)
+            if not args.no_c4:
+                extra["cholesky_c4"] = cholesky_c4(bohip)
+                extra["mll_grad_ms"]["N=10000"] = extra["cholesky_c4"].pop("_mll_grad_ms")
         report(args, 1, elapsed, stage_sum, info_ms, fit_ms, val, idx, X, y, Xs_all, tau, "one handle", extra)
         return
     # ---- N > 1 in one process: bohip_mgp_* -------------------------------------------------------------------
@@ -492,7 +517,7 @@ def main_single_process(args):
         return [(names[i].decode(), msb[i]) for i in range(min(n, 4096))]
 
     fit_ms = dict(timing0())
-    for _ in range(4):          # (best of five refits: the first one carries the allocations)
+    for _ in range(4 if args.full else 0):      # (best of five refits: the first one carries the allocations)
         model._push_hyper()     # marks the factor stale on every replica
         model.fit_()
         for k_, v_ in timing0():
@@ -510,6 +535,9 @@ def main_single_process(args):
         info_ms = {}
         for k, v in timing0(True):              # spd > 1: several shards on device 0 -> sum per stage
             info_ms[k] = info_ms.get(k, 0.0) + v
+    lib.bohip_gp_enable_timing(g0, 0)
+    for _ in range(max(0, UNTIMED_MIN - args.warmup)):
+        step()
     lib.bohip_gp_enable_timing(g0, 3)
     step()
     timing0()
@@ -529,7 +557,7 @@ def main_single_process(args):
     extra = {"_launches": int(n_launch.value), "_shards_per_device": spd,
              "rccl": {"nranks": int(nranks), "version": int(model.info(_lib.MGP_INFO_RCCL_VERSION)),
                       "allgathers_per_step": (ex1 - ex0) / float(args.steps), "read_from": "ncclCommCount / ncclGetVersion / the library's exchange counter"}}
-    if not args.strong and STRONG_R_TOTAL % G == 0:
+    if args.full and not args.strong and STRONG_R_TOTAL % G == 0:
         # BASELINE configs[2] beside the weak-scaling line: R = 32768 in total over the same devices
         Xs_s = lhs(STRONG_R_TOTAL, seed=1)
         model.set_candidates(Xs_s.T)
@@ -704,13 +732,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also every side figure (see the module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result record to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--strong", action="store_true", help="strong scaling: R = 32768 candidates in total (BASELINE configs[2]) at every --gpus")
-    ap.add_argument("--no-c4", action="store_true", help="skip the N=10000 model-update figure (cholesky_c4)")
+    ap.add_argument("--no-c4", action="store_true", help="(--full) skip the N=10000 model-update figure (cholesky_c4)")
     ap.add_argument("--traffic-child", action="store_true", help="(internal) the child process of measure_traffic()")
     args = ap.parse_args()
     if args.traffic_child:
         return traffic_child()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.strong and STRONG_R_TOTAL % args.gpus:
         raise SystemExit("--strong needs --gpus to divide 32768")
     quiet_stdout()
@@ -825,7 +857,7 @@ def main():
     # 30 steps right behind it against 0.663 over 200).  So: rendezvous first, then the W warm-up steps plus enough further
     # untimed steps to have the device at its working clocks (the single-process run does 33 host-buffer steps at this
     # point), then the bracket with a collective step as its barrier.
-    for _ in range(max(0, 40 - args.warmup)):
+    for _ in range(max(0, UNTIMED_MIN - args.warmup)):
         step()
     model.timing(4096)
 
@@ -851,7 +883,7 @@ def main():
         extra["rccl"] = {"nranks": int(nranks), "version": int(model.info(_lib.INFO_COMM_RCCL_VERSION)),
                          "allgathers_per_step": (ex1 - ex0 - 1) / float(args.steps),   # (- 1: the collective step that serves as the opening barrier)
                          "read_from": "ncclCommCount / the handle's exchange counter"}
-    if not args.strong and STRONG_R_TOTAL % world == 0:
+    if args.full and not args.strong and STRONG_R_TOTAL % world == 0:
         # BASELINE configs[2] beside the weak-scaling line: R = 32768 in total, this rank's contiguous shard
         R_s = STRONG_R_TOTAL // world
         Xs_s = lhs(STRONG_R_TOTAL, seed=1)

@@ -163,13 +163,13 @@ def _run_bench(cmd, env=None):
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
 
 
-def test_bench_launches_the_way_the_driver_does(bohip):
+def test_bench_launches_the_way_the_driver_does(bohip, tmp_path):
     """`python bench.py --gpus N` must run by itself (N = 1: one handle; N > 1: in-library multi-GPU path -- here with
     logical shards, the box has one GPU), and under torch.distributed.run the exchange is the in-library RCCL one."""
     sys.path.insert(0, ROOT)
     import bench
 
-    one = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    one = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                       "--no-cpu-baseline"])
     assert one["n_gpus"] == 1 and one["value_host_buffers"] > 0 and one["host_buffers_same_winner"] is True
     two = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
@@ -184,7 +184,12 @@ def test_bench_launches_the_way_the_driver_does(bohip):
                      "--warmup", "1", "--no-cpu-baseline"])
     assert "bohip_gp_score_sharded_dev" in tr["config"]["parallelism"] and tr["best"] == one["best"]
     strong = _run_bench([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--strong",
-                         "--no-cpu-baseline", "--no-c4"])
+                         "--no-cpu-baseline", "--no-c4", "--dump-outputs", str(tmp_path / "dump")])
+    # a plain run carries no side figure (they are --full's); --dump-outputs holds the record the line reports
+    assert "default_usage" not in strong and "configs2_strong" not in two and "configs2_strong" not in tr
+    dv, di = np.load(tmp_path / "dump" / "best_value.npy"), np.load(tmp_path / "dump" / "best_index.npy")
+    assert dv.dtype == di.dtype == np.float64 and dv.shape == di.shape == (1,)
+    assert (dv[0], int(di[0])) == (strong["best"]["value"], strong["best"]["index"])
     assert strong["scaling"] == "strong" and strong["config"]["R_total"] == 32768 and strong["roofline"]["launches_per_step"] == 4   # 4 x 8192: equal chunks of about 256 MB, counted by the library
     assert "cholesky_c4" in one and one["cholesky_c4"]["N"] == 10000
     X, y = bench.synth(0)

@@ -6,10 +6,10 @@ bash tools/prof.sh $TAG > $out/prof_stdout.txt 2>&1
 cp gpurun_out/prof_$TAG/summary.txt $out/rocprof_bench_summary.txt 2>/dev/null
 cp gpurun_out/prof_$TAG/traffic_trigemm_sq.json $out/traffic_trigemm_sq.json 2>/dev/null
 rm -rf gpurun_out/prof_$TAG/kt gpurun_out/prof_$TAG/pmc_*   # (raw traces: tens of MB; gpurun merges at most 64 MiB back)
-python bench.py > $out/bench_line_default.json 2> $out/bench.err
+python bench.py --full > $out/bench_line_default.json 2> $out/bench.err
 python bench.py --strong --no-cpu-baseline --no-c4 > $out/bench_line_strong_1gpu.json 2>> $out/bench.err
-BOHIP_LOGICAL_SHARDS=1 python bench.py --gpus 8 --no-cpu-baseline > $out/bench_line_8_logical_shards_1gpu.json 2>> $out/bench.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 1 --no-cpu-baseline --no-c4 > $out/bench_line_torchrun_1gpu.json 2>> $out/bench.err
+BOHIP_LOGICAL_SHARDS=1 python bench.py --gpus 8 --full --no-cpu-baseline > $out/bench_line_8_logical_shards_1gpu.json 2>> $out/bench.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 1 --full --no-cpu-baseline --no-c4 > $out/bench_line_torchrun_1gpu.json 2>> $out/bench.err
 python tools/bench_configs.py > $out/bench_configs.jsonl 2>> $out/bench.err
 {
 echo "# the factorisation ALONE (tools/chol_sizes.py switches the executor's inverse queues off), one process"

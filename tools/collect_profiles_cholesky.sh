@@ -1,5 +1,5 @@
 out=gpurun_out/r06b; mkdir -p $out
-python bench.py > $out/bench_line_default.json 2> $out/bench.err
+python bench.py --full > $out/bench_line_default.json 2> $out/bench.err
 {
 echo "# the factorisation ALONE (tools/chol_sizes.py switches the executor's inverse queues off), one process"
 python tools/chol_sizes.py 1000 2000 3000 4000 6000 8000 10000 12000 2>&1 | grep -v amdgpu
