@@ -115,6 +115,13 @@ struct bohip_gp {
     Best* dfz_best = nullptr;      // [tiles] per-tile arg-max records
     int64_t fz_cap = 0;
     bool fz_dirty = false;         // a fused call failed between its launches: clear the counters before the next one
+    // pruned arg-max (pruned_pass): ONE allocation [packed K*' rows | q2 | mu2 | bounds | lists, ranks | counters, record | pieces]
+    char* dpr = nullptr;
+    size_t pr_bytes = 0;
+    std::vector<int> hpr_pieces;
+    int* pr_pieces_at = nullptr;
+    unsigned* hprune_stat = nullptr;   // pinned: round 2's list length of the last pruned call (prune_wanted)
+    int prune_skip = 0;                // value-only calls left on the full pass before pruning is tried again
     double* dgrad = nullptr;   // d x R gradient staging of the host-pointer entry point
     double asc_ftol_abs = 0.0, asc_xtol_rel = 0.0, asc_stopval = INFINITY;   // bohip_gp_set_ascent_stop (NLopt's ftol_abs / xtol_rel / stopval)
     double asc_maxtime = 0.0;    // bohip_gp_set_maxtime: wall-clock budget of one acquire_max call in seconds (NLopt maxtime), 0 = none
@@ -361,6 +368,7 @@ static int g_append_alpha_inc = 1;   // incremental alpha on append (BOHIP_APPEN
 static int g_fuse_finish = 1;  // sigma^2 + acquisition + arg-max in k_trigemm_sq's epilogue (BOHIP_FUSE_FINISH=0: k_score + k_argmax_final)
 static int64_t g_chunk_rows_forced = 0;   // BOHIP_CHUNK_ROWS: candidates per K*' chunk (tools: chunk-size sweeps), 0 = the rule in chunk_rows
 static int g_halve_lo = -1, g_halve_hi = -1;   // BOHIP_TRIGEMM_HALVE (see trigemm_pieces)
+static int g_prune_m = -1;  // pruned arg-max: row tiles of the bounding prefix (BOHIP_PRUNE_M; 0: off, -1: the rule in prune_tiles)
 static int g_ks8 = 1;  // 8-wave k_trigemm_sq (contraction index split inside the workgroup); BOHIP_KS8=0 selects the 4-wave loop
 static int launch_gemm_nt(bohip_gp* g, const GemmNTParams& p, int batch = 1, hipStream_t st = nullptr, bool hi = false) {
     if (p.mt <= 0 || p.nt64 <= 0 || p.kc <= 0 || batch <= 0) return 0;
@@ -386,7 +394,7 @@ static void read_dev_knobs() {
         {"BOHIP_CHOL_EXEC_INV_PAIRS", &g_chol_exec_inv_pairs, 0, 1}, {"BOHIP_CHOL_EXEC_WGS", &g_chol_exec_wgs, 1, 1 << 20}, {"BOHIP_KS8", &g_ks8, 0, 1},
         {"BOHIP_CHOL_EXEC_BULK_EDF", &g_chol_exec_bulk_edf, 0, 1}, {"BOHIP_CHOL_EXEC_FAST", &g_chol_exec_fast, -1, 1 << 20},
         {"BOHIP_CHOL_EXEC_SECOND", &g_chol_exec_second, 0, 1}, {"BOHIP_CHOL_EXEC_EARLY_SPLIT", &g_chol_exec_early_split, 0, 2}, {"BOHIP_CHOL_EXEC_EARLY_TAIL", &g_chol_exec_early_tail, 0, 1 << 20}, {"BOHIP_SMALL_ZERO_COPY", &g_small_zero_copy, 0, 1}, {"BOHIP_CHOL_EXEC_EXCL", &g_chol_exec_excl, 0, 1}, {"BOHIP_CHOL_EXEC_NBU", &g_chol_exec_nbu, 0, 16}, {"BOHIP_CHUNK_ROWS", &chunk_rows, 0, 1 << 30},
-        {"BOHIP_TRIGEMM_HALVE_LO", &g_halve_lo, 0, 1 << 20}, {"BOHIP_TRIGEMM_HALVE_HI", &g_halve_hi, 0, 1 << 20}, {"BOHIP_FUSE_FINISH", &g_fuse_finish, 0, 1},
+        {"BOHIP_TRIGEMM_HALVE_LO", &g_halve_lo, 0, 1 << 20}, {"BOHIP_TRIGEMM_HALVE_HI", &g_halve_hi, 0, 1 << 20}, {"BOHIP_FUSE_FINISH", &g_fuse_finish, 0, 1}, {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16},
         {"BOHIP_APPEND_ALPHA_INC", &g_append_alpha_inc, 0, 1}, {"BOHIP_BULK_PIECES", &g_bulk_pieces, 0, 8}, {"BOHIP_SPLIT", &g_split, 0, 1},
         {"BOHIP_SMALL_R", &g_small_r, 0, SMALL_MAX}, {"BOHIP_SMALL_M", &g_small_m, 0, 1 << 20}, {"BOHIP_CHOL_DF_DUMP", &dump, 0, 1},
     };
@@ -2249,6 +2257,148 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
     return 0;
 }
 
+// ---- pruned arg-max: value-only calls (kernels_score.hip, "pruned arg-max") ---------------------------------------------------
+constexpr int PRUNE_K1 = 64;          // candidates scored exactly in round 1 (one candidate tile)
+constexpr int64_t PRUNE_R_MAX = 8192; // k_prune_rank is quadratic in the batch; larger batches keep the full pass
+// row tiles of the bounding prefix: a function of T only (never of the batch): the smallest m >= 2 whose triangle holds >= 2 % of
+// the contraction's, 0 (no pruning) when that leaves no row tile after it
+static int prune_tiles(int T) {
+    if (g_prune_m >= 0) return g_prune_m < T ? g_prune_m : 0;
+    int m = 2;
+    while ((double)m * (m + 1) < 0.02 * T * (T + 1)) ++m;
+    return m < T ? m : 0;
+}
+static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, int NP, int CT, double* q, int64_t ldq, double* mu_raw,
+                             FuseParams fz) {
+    const int n_local = (CT + 7) / 8;
+    if (NP <= 0 || CT <= 0) return 0;
+    if (g->timing && g->dclk) fz.clk = g->dclk;
+    if (g_ks8)
+        hipLaunchKernelGGL(k_trigemm_sq<2>, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW,
+                           g->ld, KsT, g->ld, pieces, NP, CT, g->n, q, ldq, mu_raw, (int64_t)0, nullptr, g->ld, fz);
+    else
+        hipLaunchKernelGGL(k_trigemm_sq<1>, dim3(8 * n_local * NP), dim3(GEMM_THREADS), glds3_lds_bytes<4>(), g->stream, g->dW,
+                           g->ld, KsT, g->ld, pieces, NP, CT, g->n, q, ldq, mu_raw, (int64_t)0, nullptr, g->ld, fz);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// One chunk, value-only: phase A (row tiles < m, every candidate) -> bounds -> round 1 (the 64 highest bounds, row tiles >= m, exact
+// finish: L) -> round 2 (every other candidate whose bound is not below L) -> the record.  No host round trip: the lists and their
+// lengths stay on the device, round 2's launches are sized for the worst case and the surplus workgroups leave at once.
+// ub_host (tests, bohip_debug_prune_bounds): stop after the bounds and copy them out.
+static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
+                       double* ub_host = nullptr) {
+    CHK(one_time_kernel_setup());
+    if (!g->hprune_stat) {
+        HIPCHK(hipHostMalloc((void**)&g->hprune_stat, 64, hipHostMallocDefault));
+        g->hprune_stat[0] = 0u;
+    }
+    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
+    const int T = (int)(Npad / TILE);
+    CHK(ensure_pieces(g, T, N));
+    std::vector<int> pa, pb;   // the full pass's row pieces (same modes, same order), split at row tile m
+    for (int c : g->hpieces) ((c & 0xffff) < m ? pa : pb).push_back(c);
+    // layout (bytes, every part 256-aligned)
+    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
+                 o_ub = o_mu2 + al((size_t)Rpad * 8), o_l1 = o_ub + al((size_t)Rpad * 8), o_l2 = o_l1 + al((size_t)PRUNE_K1 * 4),
+                 o_rank = o_l2 + al((size_t)Rpad * 4), o_cnt = o_rank + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
+                 o_pc = o_rec + 256, total = o_pc + al(g->hpieces.size() * 4);
+    bool fresh = false;
+    if (g->pr_bytes < total) {
+        fresh = true;
+        if (g->dpr) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dpr)); g->dpr = nullptr; g->pr_bytes = 0; }
+        HIPCHK(hipMalloc(&g->dpr, total));
+        g->pr_bytes = total;
+    }
+    char* b = g->dpr;
+    double *ks2 = (double*)(b + o_ks), *q2 = (double*)(b + o_q2), *mu2 = (double*)(b + o_mu2), *ub = (double*)(b + o_ub);
+    int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *rank = (int*)(b + o_rank), *pcs = (int*)(b + o_pc);
+    unsigned* cnt = (unsigned*)(b + o_cnt);
+    Best* rec = (Best*)(b + o_rec);
+    std::vector<int> both = pa;
+    both.insert(both.end(), pb.begin(), pb.end());
+    if (fresh || g->hpr_pieces != both || g->pr_pieces_at != pcs) {   // (the table's offset moves with the batch)
+        g->pr_pieces_at = pcs;
+        g->hpr_pieces = both;   // (kept alive until the stream has consumed the copy)
+        HIPCHK(hipMemcpyAsync(pcs, g->hpr_pieces.data(), both.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
+    }
+    if (g->timing && !g->dclk) {
+        HIPCHK(hipMalloc(&g->dclk, 2 * sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
+    }
+    g->q_tiles = T;
+    g->score_launches = 1;
+    const KernelHyper hp = make_hyper(g);
+    const double sigma2 = std::exp(2.0 * g->logsig);
+    const int k1 = (int)std::min<int64_t>(PRUNE_K1, R);
+    t_begin(g, "kstar");
+    CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp));
+    t_end(g);
+    // ONE bracket from phase A to the record, under the dense pass's label: what bench.py's roofline divides by
+    t_begin(g, "trigemm_sq");
+    FuseParams fz{};
+    fz.T = T;
+    CHK(launch_trigemm_on(g, g->dKsT, pcs, (int)pa.size(), (int)((R + CTILE - 1) / CTILE), g->dq, Rpad, g->dmu_raw, fz));
+    PruneBound bd{};
+    bd.KsT = g->dKsT; bd.ldk = ld; bd.Npad = Npad; bd.walpha = g->dW + N * ld; bd.q = g->dq; bd.ldq = Rpad; bd.R = R; bd.m = m;
+    bd.sigma2 = sigma2; bd.beta = g->beta; bd.ap = ap; bd.ub = ub; bd.rank = rank;
+    hipLaunchKernelGGL(k_prune_bound, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, g->stream, bd);
+    if (ub_host) {
+        t_end(g);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ub_host, ub, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        return 0;
+    }
+    const unsigned nb = (unsigned)((R + 255) / 256);
+    hipLaunchKernelGGL(k_prune_rank, dim3(nb, nb), dim3(256), 0, g->stream, (const double*)ub, R, rank);
+    hipLaunchKernelGGL(k_prune_pick, dim3(nb), dim3(256), 0, g->stream, (const int*)rank, R, k1, l1, cnt, rec);
+    HIPCHK(hipGetLastError());
+    PruneFinish pf{};
+    pf.q = g->dq; pf.ldq = Rpad; pf.q2 = q2; pf.ldq2 = Rpad; pf.mu2 = mu2; pf.m = m; pf.T = T; pf.sigma2 = sigma2; pf.beta = g->beta;
+    pf.ap = ap; pf.rec = rec;
+    for (int round = 0; round < 2; ++round) {
+        const int* list = round == 0 ? l1 : l2;
+        const unsigned* c = cnt + round;
+        const int64_t cap = round == 0 ? k1 : R - k1;   // worst case of the list's length
+        if (round == 1)
+            hipLaunchKernelGGL(k_prune_compact, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, (const double*)ub,
+                               (const int*)rank, R, k1, (const Best*)rec, l2, cnt + 1);
+        if (cap > 0) {
+            hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, list, c, (const double*)g->dKsT, ld, Npad, ks2);
+            fz.live = c;
+            CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
+        }
+        pf.list = list; pf.cnt = c;
+        pf.best_out = round == 1 ? d_best : nullptr; pf.best_off = (long long)best_off;
+        pf.stat = round == 1 ? g->hprune_stat : nullptr;
+        hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
+        HIPCHK(hipGetLastError());
+    }
+    t_end(g);
+    return 0;
+}
+
+// Path choice for value-only calls that qualify.  Pruning pays when few candidates outside round 1 survive; when many do, round 1's
+// latency (one lone whole-K job, ~0.2 ms at N = 3000) comes on top of the full contraction.  The last pruned call of the handle left
+// the length of its round-2 list in pinned memory (read without a wait: an older call's figure is as good a guide).  When more than an
+// eighth of the batch survived, the next PRUNE_BACKOFF calls take the full pass, then one call tries pruning again.  Either path gives
+// the same record bit for bit, so the choice moves only time.
+constexpr int PRUNE_BACKOFF = 31;
+static bool prune_wanted(bohip_gp* g, int64_t R) {
+    if (g->prune_skip > 0) { --g->prune_skip; return false; }
+    if (g->hprune_stat) {
+        const unsigned n2 = __atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
+        if ((int64_t)n2 > R / 8) {
+            __atomic_store_n(g->hprune_stat, 0u, __ATOMIC_RELAXED);
+            g->prune_skip = PRUNE_BACKOFF - 1;
+            return false;
+        }
+    }
+    return true;
+}
+
 // best_off: added to the winner's index (a shard of a larger candidate set reports GLOBAL columns)
 static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const double* dXs, int64_t R, double* d_mu,
                       double* d_var, double* d_score, Best* d_best, int64_t best_off = 0) {
@@ -2269,6 +2419,12 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
     const SplitPlan sp = split_plan(g, R);
     if (sp.nsl > 0) {
         CHK(split_posterior(g, dXs, R, sp, false));
+    } else if (int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
+               m > 0 && g_fuse_finish && d_best && !d_mu && !d_var && !d_score && R <= PRUNE_R_MAX && R <= g->chunk_now &&
+               g->batch_hint == 0 && prune_wanted(g, R)) {
+        // value-only: only the winner leaves the call -- candidates that provably cannot win are not contracted past m row tiles.
+        // Not for shards of a larger set (batch_hint: the sharded entry points and bohip_gp_set_batch_hint): see DESIGN.md 6d.
+        return pruned_pass(g, dXs, R, m, ap, d_best, best_off);
     } else if (g_fuse_finish) {
         // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
         // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
@@ -2481,6 +2637,8 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->dbest) hipFree(g->dbest);
     if (g->dfz_cnt) hipFree(g->dfz_cnt);
     if (g->dfz_best) hipFree(g->dfz_best);
+    if (g->dpr) hipFree(g->dpr);
+    if (g->hprune_stat) hipHostFree(g->hprune_stat);
     if (g->dpieces) hipFree(g->dpieces);
     if (g->dclk) hipFree(g->dclk);
     if (g->dgrad) hipFree(g->dgrad);
@@ -3419,6 +3577,24 @@ int bohip_debug_trigemm_pieces(int T, int64_t alpha_row, int* out, int cap) {
 }
 // tools and bench.py: switch the executor's inverse queues at run time (returns the previous chunk size; 0 = off: the factorisation
 // alone can then be timed against its own flop count)
+// tests only (tests/test_prune_gpu.py): the pruned pass's upper bounds of the scores of R host candidates (layout of bohip_gp_score);
+// BOHIP_E_UNSUPPORTED where a value-only call of this size would not prune
+int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* ub) {
+    if (!g || R <= 0 || !Xs || !ub || acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(g->device));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(ensure_fresh(g));
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    AcqParams ap{acq_id, 0.0, 0.0};
+    if (acq_params && acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
+    if (acq_params && acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
+    const int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
+    if (m == 0 || R > PRUNE_R_MAX || R > g->chunk_now || (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) || split_plan(g, R).nsl > 0)
+        return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    return pruned_pass(g, g->dXs, R, m, ap, nullptr, 0, ub);
+}
 int bohip_debug_set_chol_inv_g(int g_new) {
     return g_chol_inv_g.exchange(std::min(64, std::max(0, g_new)));   // (atomic; a refit in flight on another thread may see either value)
 }

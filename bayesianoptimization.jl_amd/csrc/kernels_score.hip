@@ -126,6 +126,8 @@ struct FuseParams {
     Best* best_out;          // nullable: the batch's arg-max record
     long long best_off;      // added to the winner's index (sharded scoring)
     unsigned long long* clk; // nullable: [2] core-clock and 100 MHz wall-clock ticks summed over a sample of workgroups (timing runs)
+    const unsigned* live;    // nullable: candidates of the chunk that exist, counted on the device (pruned scoring: the grid is sized
+                             // for the worst case, candidate tiles at or past the count leave at once)
 };
 __device__ void trigemm_fused_finish(const FuseParams& fz, int tile_g, int T, const double* q_part, int64_t ldq,
                                      const double* mu_raw);
@@ -247,6 +249,7 @@ __global__ __launch_bounds__(KS * GEMM_THREADS, 2 * KS) void k_trigemm_sq(const 
     const int n_local = (CT + 7) >> 3;
     const int ct = xcd + 8 * (slot % n_local);
     if (ct >= CT) return;
+    if (fz.live != nullptr && ct * CTILE >= (int)*fz.live) return;
     const int piece = __builtin_amdgcn_readfirstlane(pieces[slot / n_local]);   // (uniform: a scalar load)
     // timing runs (bohip_gp_enable_timing): every 33rd workgroup reports how many core-clock cycles and 100 MHz ticks it lived --
     // their ratio is the clock the chip sustained UNDER THIS KERNEL (MI355X clocks to its power budget: ~2.0 of 2.4 GHz here)
@@ -507,6 +510,191 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
         if (better(in[i].val, in[i].idx, v, idx)) { v = in[i].val; idx = in[i].idx; }
     block_argmax(v, idx, sh);
     if (threadIdx.x == 0) { out->val = idx >= 0 ? v : -INFINITY; out->idx = idx >= 0 ? idx + idx_off : -1; }
+}
+
+// ---- pruned arg-max (value-only calls, bohip.hip pruned_pass) ---------------------------------------------------------------
+// A call that returns only the winner need not contract the rows of candidates that provably cannot win.  After the first m row
+// tiles (phase A: k_trigemm_sq over the row pieces with rt < m, all candidates) every candidate gets an UPPER BOUND of the score
+// the full pass would compute for it (k_prune_bound).  Round 1 scores the 64 candidates of highest bound exactly; its best value
+// L is an exactly computed score.  Round 2 scores exactly every other candidate whose bound is not below L.  A dropped candidate
+// has score <= bound < L, so it can neither win nor tie: the record equals the full pass's bit for bit (the exact rounds run the
+// same row pieces on the same K*' rows -- gathered, a column of the contraction depends on its own K*' row only -- and add the
+// partial sums in the fused finish's order).
+//
+// The bound, per candidate (u = 2^-53, n = Npad + 64 >= the number of terms of any summation of the alpha row):
+//   s2_up = max(s_f^2 - sum_{t < m} (q[2t] + q[2t+1]), 0): every partial sum is >= 0 and rounded addition is monotone, so the prefix
+//           done in the finish's order never exceeds the full q -- an upper bound of the computed sigma^2 with no margin.
+//   mu_up = beta + up(mu~ + 4 gamma_n S) (rounded up by >= 1 ulp), mu~ = sum_j alpha_j K*'_j, S = sum_j |alpha_j K*'_j| (any order): the computed
+//           mu_raw and mu~ both lie within gamma_n S(1 + gamma_n) of the exact dot product; beta + . is monotone.
+//   functor f at (mu_up, s2_b), plus a slack for its evaluation where its operations are not exactly monotone:
+//     EI  (the reference's D Phi(D/s) + phi(D/s)): in s it rises up to s = 1 and falls after; at s <= 1 it rises in D for D <= 0, at
+//         s = 1 for every D.  So s2_b = min(s2_up, 1) when D_up <= 0, else 1 (a computed sigma^2 of 0 gives max(D, 0) <= both).
+//         Slack 2^-38 (1 + s_f + max(D_up, 0) + |f|): erf / exp and the cancellation in 1 + erf err by ~1e-15 absolute in Phi
+//         and relative in phi, times |D| <= 8 s_f where Phi is not negligible (Mills' ratio covers the rest) -- ~100x head-room.
+//     PI  D_up >= 0: 1; else f(mu_up, s2_up) + 2^-38.
+//     UCB, MI: s2_b = s2_up for p0 >= 0, 0 for p0 < 0; slack 2^-38 (|mu_up| + |p0| (sqrt terms)) for the square roots.
+//     MaxMean: mu_up (one rounded addition: exact).
+// A NaN bound is never below L: such a candidate is always scored.
+struct PruneBound {
+    const double* KsT;       // chunk [R][ldk]
+    int64_t ldk, Npad;
+    const double* walpha;    // the alpha row of W (zero past N)
+    const double* q;         // k_trigemm_sq's partial sums [2 t + h][ldq], t < m filled by phase A
+    int64_t ldq, R;
+    int m;
+    double sigma2, beta;
+    AcqParams ap;
+    double* ub;              // [R]
+    int* rank;               // [R] zeroed here for k_prune_rank
+};
+__global__ __launch_bounds__(256) void k_prune_bound(PruneBound pb) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= pb.R) return;
+    if (lane == 0) pb.rank[r] = 0;
+    const double* k = pb.KsT + r * pb.ldk;
+    double mu = 0.0, sa = 0.0;
+    for (int64_t j = lane; j < pb.Npad; j += 64) {
+        const double p = pb.walpha[j] * k[j];
+        mu += p;
+        sa += fabs(p);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mu += __shfl_xor(mu, o);
+        sa += __shfl_xor(sa, o);
+    }
+    if (lane != 0) return;
+    double qp = 0.0;
+    for (int t = 0; t < pb.m; ++t) qp += pb.q[(int64_t)(2 * t) * pb.ldq + r] + pb.q[(int64_t)(2 * t + 1) * pb.ldq + r];
+    double s2 = pb.sigma2 - qp;
+    if (s2 < 0.0) s2 = 0.0;
+    const double n = (double)(pb.Npad + 64), un = n * 0x1p-53, gam = un / (1.0 - un);
+    double y = mu + (4.0 * gam * sa + 0x1p-1000);
+    y += fabs(y) * 0x1p-52 + 0x1p-1000;   // at least one ulp up: y >= the exact mu~ + margin
+    const double mu_up = pb.beta + y;
+    const AcqParams& ap = pb.ap;
+    double ub;
+    switch (ap.acq) {
+        case ACQ_EI: {
+            const double D = mu_up - ap.p0;
+            const double f = acq_eval(ap, mu_up, D <= 0.0 ? fmin(s2, 1.0) : 1.0);
+            ub = f + 0x1p-38 * (1.0 + sqrt(pb.sigma2) + fmax(D, 0.0) + fabs(f));
+            break;
+        }
+        case ACQ_PI:
+            ub = (mu_up - ap.p0 >= 0.0 ? 1.0 : acq_eval(ap, mu_up, s2)) + 0x1p-38;
+            break;
+        case ACQ_UCB:
+        case ACQ_MI: {
+            const double sb = ap.p0 >= 0.0 ? s2 : 0.0;
+            const double f = acq_eval(ap, mu_up, sb);
+            const double roots = ap.acq == ACQ_UCB ? sqrt(sb) : sqrt(sb + fabs(ap.p1)) + sqrt(fabs(ap.p1));
+            ub = f + 0x1p-38 * (fabs(mu_up) + fabs(ap.p0) * roots + 0x1p-1000);
+            break;
+        }
+        default:
+            ub = mu_up;
+    }
+    pb.ub[r] = ub;
+}
+
+// rank of every candidate in (bound desc, index asc), a NaN bound counting as +inf.  Workgroup (x, y): its 256 candidates against
+// the 256 bounds of block y, counts added into rank[] (zeroed by k_prune_bound); k_prune_pick then lists the first k1 ranks.
+__device__ __forceinline__ double prune_key(double v) { return v != v ? INFINITY : v; }
+__global__ __launch_bounds__(256) void k_prune_rank(const double* __restrict__ ub, int64_t R, int* __restrict__ rank) {
+    __shared__ double sk[256];
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x, base = (int64_t)blockIdx.y * 256;
+    const int64_t s = base + threadIdx.x;
+    sk[threadIdx.x] = s < R ? prune_key(ub[s]) : -INFINITY;
+    __syncthreads();
+    if (r >= R) return;
+    const double kr = prune_key(ub[r]);
+    const int n = (int)min((int64_t)256, R - base);
+    int above = 0;
+    for (int i = 0; i < n; ++i) {
+        const double v = sk[i];
+        above += (v > kr) || (v == kr && base + i < r);
+    }
+    if (above) atomicAdd(rank + r, above);
+}
+// round 1's list (position = rank); readies the counters and the running record of the call
+__global__ __launch_bounds__(256) void k_prune_pick(const int* __restrict__ rank, int64_t R, int k1, int* __restrict__ list1,
+                                                    unsigned* __restrict__ cnt, Best* __restrict__ rec) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < R && rank[r] < k1) list1[rank[r]] = (int)r;
+    if (r == 0) {
+        cnt[0] = (unsigned)min((int64_t)k1, R);
+        cnt[1] = 0u;
+        rec->val = -INFINITY;
+        rec->idx = -1;
+    }
+}
+
+// round 2's list: candidates outside round 1 whose bound is not below round 1's exact best (order is immaterial: every listed
+// candidate is scored on its own and the record is reduced by `better`)
+__global__ __launch_bounds__(256) void k_prune_compact(const double* __restrict__ ub, const int* __restrict__ rank, int64_t R, int k1,
+                                                       const Best* __restrict__ rec, int* __restrict__ list2, unsigned* __restrict__ cnt2) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R || rank[r] < k1) return;
+    if (ub[r] < rec->val) return;
+    list2[atomicAdd(cnt2, 1u)] = (int)r;
+}
+
+// K*' rows of the listed candidates, packed (workgroup i: row list[i]; the grid is sized for the worst case)
+__global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ list, const unsigned* __restrict__ cnt,
+                                                      const double* __restrict__ src, int64_t ld, int64_t ncols, double* __restrict__ dst) {
+    const int i = blockIdx.x;
+    if (i >= (int)*cnt) return;
+    const d2* s = reinterpret_cast<const d2*>(src + (int64_t)list[i] * ld);
+    d2* d = reinterpret_cast<d2*>(dst + (int64_t)i * ld);
+    for (int64_t j = threadIdx.x; j < ncols / 2; j += 256) d[j] = s[j];
+}
+
+// exact scores of the listed candidates: q in the fused finish's order (t < m from phase A at the candidate's index, t >= m from
+// the round's own launch at its list position), mu from the round; the round's best is merged into the call's record.
+struct PruneFinish {
+    const int* list;
+    const unsigned* cnt;
+    const double *q, *q2, *mu2;
+    int64_t ldq, ldq2;
+    int m, T;
+    double sigma2, beta;
+    AcqParams ap;
+    Best* rec;
+    Best* best_out;       // nullable: the call's result (last round)
+    long long best_off;
+    unsigned* stat;       // nullable (pinned host word): the round's list length, read by the host's path choice of a later call
+};
+__global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
+#pragma clang fp contract(off)
+    __shared__ Best sh[4];
+    const int n = (int)*pf.cnt;
+    double v = -INFINITY;
+    long long idx = -1;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int64_t r = pf.list[i];
+        double q = 0.0;
+        for (int t = 0; t < pf.m; ++t) q += pf.q[(int64_t)(2 * t) * pf.ldq + r] + pf.q[(int64_t)(2 * t + 1) * pf.ldq + r];
+        for (int t = pf.m; t < pf.T; ++t) q += pf.q2[(int64_t)(2 * t) * pf.ldq2 + i] + pf.q2[(int64_t)(2 * t + 1) * pf.ldq2 + i];
+        double s2 = pf.sigma2 - q;
+        if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
+        const double mu = pf.beta + pf.mu2[i];
+        const double f = acq_eval(pf.ap, mu, s2);
+        if (better(f, r, v, idx)) { v = f; idx = r; }
+    }
+    block_argmax(v, idx, sh);
+    if (threadIdx.x == 0) {
+        const Best b = *pf.rec;
+        if (better(b.val, b.idx, v, idx)) { v = b.val; idx = b.idx; }
+        pf.rec->val = idx >= 0 ? v : -INFINITY;
+        pf.rec->idx = idx;
+        if (pf.best_out) {
+            pf.best_out->val = idx >= 0 ? v : -INFINITY;
+            pf.best_out->idx = idx >= 0 ? idx + pf.best_off : -1;
+        }
+        if (pf.stat) *pf.stat = (unsigned)n;
+    }
 }
 
 // The exchange step of sharded scoring: `all` holds nrec records per draw-slot layout [rec][S] gathered
