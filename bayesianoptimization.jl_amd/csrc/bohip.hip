@@ -416,6 +416,7 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<1>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<2>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_rows, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_chol_chain, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_inv128, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_pair, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
@@ -2259,6 +2260,7 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
 
 // ---- pruned arg-max: value-only calls (kernels_score.hip, "pruned arg-max") ---------------------------------------------------
 constexpr int PRUNE_K1 = 64;          // candidates scored exactly in round 1 (one candidate tile)
+constexpr int PRUNE_ROWS_CAP = 256;   // round 2 on k_trigemm_rows up to this many candidates, on gathered rows + k_trigemm_sq beyond
 constexpr int64_t PRUNE_R_MAX = 8192; // k_prune_rank is quadratic in the batch; larger batches keep the full pass
 // row tiles of the bounding prefix: a function of T only (never of the batch): the smallest m >= 2 whose triangle holds >= 2 % of
 // the contraction's, 0 (no pruning) when that leaves no row tile after it
@@ -2267,6 +2269,38 @@ static int prune_tiles(int T) {
     int m = 2;
     while ((double)m * (m + 1) < 0.02 * T * (T + 1)) ++m;
     return m < T ? m : 0;
+}
+// k_trigemm_rows's job table: the 64-row halves of the row pieces, heaviest (most chunks) first -- rt | hh << 16 | solo << 17.  The
+// weight falls with rt, so the halves of the row tiles >= t0 are the table's first rows_halves_from(t0) entries.  Empty when a
+// piece is not one k_trigemm_rows reproduces (the measurement knobs: halved tiles, the 4-wave loop).
+static std::vector<int> rows_halves(const std::vector<int>& pieces) {
+    std::vector<int> out;
+    if (!g_ks8) return out;
+    for (int c : pieces) {
+        const int rt = c & 0xffff, mode = c >> 16;
+        if (mode == PIECE_UPPER_SOLO) out.push_back(rt | 1 << 17);
+        else if (mode == PIECE_WHOLE) { out.push_back(rt | 1 << 16); out.push_back(rt); }
+        else return {};
+    }
+    std::stable_sort(out.begin(), out.end(), [](int a, int b) {   // chunks: 8 rt + 8 (lower half), 8 rt + 4 (upper, solo)
+        return 8 * (a & 0xffff) + ((a >> 16) & 1) * 4 > 8 * (b & 0xffff) + ((b >> 16) & 1) * 4;
+    });
+    return out;
+}
+static int rows_halves_from(const std::vector<int>& hv, int t0) {
+    int n = 0;
+    while (n < (int)hv.size() && (hv[n] & 0xffff) >= t0) ++n;
+    return n;
+}
+static int launch_trigemm_rows(bohip_gp* g, const double* KsT, const int* halves, int NH, const int* list, const unsigned* cnt,
+                               int cnt_max, double* q, int64_t ldq, double* mu) {
+    if (NH <= 0 || cnt_max <= 0) return 0;
+    RowsParams rp{};
+    rp.W = g->dW; rp.ldw = g->ld; rp.KsT = KsT; rp.ldk = g->ld; rp.list = list; rp.cnt = cnt; rp.cnt_max = cnt_max;
+    rp.halves = halves; rp.NH = NH; rp.G = (cnt_max + RS_COLS - 1) / RS_COLS; rp.alpha_row = g->n; rp.q = q; rp.ldq = ldq; rp.mu = mu;
+    hipLaunchKernelGGL(k_trigemm_rows, dim3((unsigned)(8 * ((NH + 7) / 8) * rp.G)), dim3(RS_THREADS), RS_LDS_BYTES, g->stream, rp);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, int NP, int CT, double* q, int64_t ldq, double* mu_raw,
                              FuseParams fz) {
@@ -2283,7 +2317,9 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
     return 0;
 }
 // One chunk, value-only: phase A (row tiles < m, every candidate) -> bounds -> round 1 (the 64 highest bounds, row tiles >= m, exact
-// finish: L) -> round 2 (every other candidate whose bound is not below L) -> the record.  No host round trip: the lists and their
+// finish: L) -> round 2 (every other candidate whose bound is not below L) -> the record.  The rounds run on k_trigemm_rows (round 2
+// up to PRUNE_ROWS_CAP candidates; past that on gathered rows and k_trigemm_sq); under the measurement knobs that change the row
+// pieces or the loop (rows_halves empty) both keep k_trigemm_sq.  No host round trip: the lists and their
 // lengths stay on the device, round 2's launches are sized for the worst case and the surplus workgroups leave at once.
 // ub_host (tests, bohip_debug_prune_bounds): stop after the bounds and copy them out.
 static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
@@ -2303,7 +2339,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
                  o_ub = o_mu2 + al((size_t)Rpad * 8), o_l1 = o_ub + al((size_t)Rpad * 8), o_l2 = o_l1 + al((size_t)PRUNE_K1 * 4),
                  o_rank = o_l2 + al((size_t)Rpad * 4), o_cnt = o_rank + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
-                 o_pc = o_rec + 256, total = o_pc + al(g->hpieces.size() * 4);
+                 o_pc = o_rec + 256, total = o_pc + al((3 * g->hpieces.size() + 8) * 4);
     bool fresh = false;
     if (g->pr_bytes < total) {
         fresh = true;
@@ -2316,8 +2352,11 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *rank = (int*)(b + o_rank), *pcs = (int*)(b + o_pc);
     unsigned* cnt = (unsigned*)(b + o_cnt);
     Best* rec = (Best*)(b + o_rec);
+    const std::vector<int> hv = rows_halves(g->hpieces);   // (after the pieces in the table; empty: the rounds keep k_trigemm_sq)
+    const int nh = rows_halves_from(hv, m);
     std::vector<int> both = pa;
     both.insert(both.end(), pb.begin(), pb.end());
+    both.insert(both.end(), hv.begin(), hv.end());
     if (fresh || g->hpr_pieces != both || g->pr_pieces_at != pcs) {   // (the table's offset moves with the batch)
         g->pr_pieces_at = pcs;
         g->hpr_pieces = both;   // (kept alive until the stream has consumed the copy)
@@ -2358,6 +2397,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     PruneFinish pf{};
     pf.q = g->dq; pf.ldq = Rpad; pf.q2 = q2; pf.ldq2 = Rpad; pf.mu2 = mu2; pf.m = m; pf.T = T; pf.sigma2 = sigma2; pf.beta = g->beta;
     pf.ap = ap; pf.rec = rec;
+    const int* hvd = pcs + pa.size() + pb.size();
     for (int round = 0; round < 2; ++round) {
         const int* list = round == 0 ? l1 : l2;
         const unsigned* c = cnt + round;
@@ -2365,10 +2405,17 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         if (round == 1)
             hipLaunchKernelGGL(k_prune_compact, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, (const double*)ub,
                                (const int*)rank, R, k1, (const Best*)rec, l2, cnt + 1);
-        if (cap > 0) {
-            hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, list, c, (const double*)g->dKsT, ld, Npad, ks2);
-            fz.live = c;
+        if (cap > 0 && nh > 0 && cap <= PRUNE_ROWS_CAP) {   // (round 1: always)
+            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, list, c, (int)cap, q2, Rpad, mu2));
+        } else if (cap > 0) {
+            // the row-split kernel takes lists of up to PRUNE_ROWS_CAP candidates, the gathered rows and k_trigemm_sq the longer ones:
+            // both launches are enqueued and the device-side count picks (cnt[2]: k_trigemm_sq's count, 0 when the list is short)
+            const int sq_min = nh > 0 ? PRUNE_ROWS_CAP : -1;
+            hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, list, c, (const double*)g->dKsT, ld, Npad, ks2,
+                               sq_min, cnt + 2);
+            fz.live = cnt + 2;
             CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
+            if (nh > 0) CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, list, c, PRUNE_ROWS_CAP, q2, Rpad, mu2));
         }
         pf.list = list; pf.cnt = c;
         pf.best_out = round == 1 ? d_best : nullptr; pf.best_off = (long long)best_off;
@@ -2380,8 +2427,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     return 0;
 }
 
-// Path choice for value-only calls that qualify.  Pruning pays when few candidates outside round 1 survive; when many do, round 1's
-// latency (one lone whole-K job, ~0.2 ms at N = 3000) comes on top of the full contraction.  The last pruned call of the handle left
+// Path choice for value-only calls that qualify.  Pruning pays when few candidates outside round 1 survive; when many do, phase A,
+// the bounds and round 1 (k_trigemm_rows, ~60 us at N = 3000) come on top of the full contraction.  The last pruned call of the handle left
 // the length of its round-2 list in pinned memory (read without a wait: an older call's figure is as good a guide).  When more than an
 // eighth of the batch survived, the next PRUNE_BACKOFF calls take the full pass, then one call tries pruning again.  Either path gives
 // the same record bit for bit, so the choice moves only time.
@@ -3594,6 +3641,62 @@ int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, 
         return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     return pruned_pass(g, g->dXs, R, m, ap, nullptr, 0, ub);
+}
+// tests only (tests/test_prune_rows_gpu.py): the partial sums q[2T][R] and mu_raw[R] of R host candidates from the full pass's
+// k_trigemm_sq (path 0) or from k_trigemm_rows over every row tile, the candidates listed in reverse order (path 1)
+int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int path, double* q_out, double* mu_out) {
+    if (!g || R <= 0 || !Xs || !q_out || !mu_out || (path != 0 && path != 1)) return fail(BOHIP_E_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(g->device));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(ensure_fresh(g));
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    if (R > g->chunk_now) return fail(BOHIP_E_UNSUPPORTED, "more than one K*' chunk");
+    CHK(one_time_kernel_setup());
+    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE);
+    const int T = (int)(Npad / TILE);
+    CHK(ensure_pieces(g, T, N));
+    const std::vector<int> hv = rows_halves(g->hpieces);
+    if (path == 1 && hv.empty()) return fail(BOHIP_E_UNSUPPORTED, "row pieces k_trigemm_rows does not reproduce");
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(launch_kstar_any(g, g->dXs, 0, R, Npad, make_hyper(g)));
+    std::vector<double> q((size_t)2 * T * Rpad), mu((size_t)Rpad);
+    if (path == 0) {
+        CHK(launch_trigemm_on(g, g->dKsT, g->dpieces, g->n_pieces, (int)((R + CTILE - 1) / CTILE), g->dq, Rpad, g->dmu_raw, FuseParams{}));
+        HIPCHK(hipMemcpyAsync(q.data(), g->dq, q.size() * 8, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(mu.data(), g->dmu_raw, mu.size() * 8, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        for (int t = 0; t < 2 * T; ++t) std::memcpy(q_out + (size_t)t * R, q.data() + (size_t)t * Rpad, (size_t)R * 8);
+        std::memcpy(mu_out, mu.data(), (size_t)R * 8);
+        return 0;
+    }
+    std::vector<int> list((size_t)R);
+    for (int64_t i = 0; i < R; ++i) list[i] = (int)(R - 1 - i);
+    const unsigned n = (unsigned)R;
+    char* d = nullptr;
+    const size_t o_q = 0, o_mu = o_q + q.size() * 8, o_l = o_mu + mu.size() * 8, o_h = o_l + list.size() * 4, o_c = o_h + hv.size() * 4;
+    HIPCHK(hipMalloc(&d, o_c + 16));
+    int rc = 0;
+    hipMemcpyAsync(d + o_l, list.data(), list.size() * 4, hipMemcpyHostToDevice, g->stream);
+    hipMemcpyAsync(d + o_h, hv.data(), hv.size() * 4, hipMemcpyHostToDevice, g->stream);
+    hipMemcpyAsync(d + o_c, &n, 4, hipMemcpyHostToDevice, g->stream);
+    rc = launch_trigemm_rows(g, g->dKsT, (const int*)(d + o_h), (int)hv.size(), (const int*)(d + o_l), (const unsigned*)(d + o_c), (int)R,
+                             (double*)(d + o_q), Rpad, (double*)(d + o_mu));
+    hipMemcpyAsync(q.data(), d + o_q, q.size() * 8, hipMemcpyDeviceToHost, g->stream);
+    hipMemcpyAsync(mu.data(), d + o_mu, mu.size() * 8, hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e = hipStreamSynchronize(g->stream);
+    hipFree(d);
+    if (rc != 0) return rc;
+    if (e != hipSuccess) return fail(BOHIP_E_HIP, hipGetErrorString(e));
+    for (int t = 0; t < 2 * T; ++t)
+        for (int64_t i = 0; i < R; ++i) q_out[(size_t)t * R + list[i]] = q[(size_t)t * Rpad + i];
+    for (int64_t i = 0; i < R; ++i) mu_out[list[i]] = mu[i];
+    return 0;
+}
+// tests only: round 2's list length of the handle's last pruned call (the pinned word prune_wanted reads; 0 after a backoff), -1: none yet
+int64_t bohip_debug_prune_stat(bohip_gp* g) {
+    if (!g || !g->hprune_stat) return -1;
+    return (int64_t)__atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
 }
 int bohip_debug_set_chol_inv_g(int g_new) {
     return g_chol_inv_g.exchange(std::min(64, std::max(0, g_new)));   // (atomic; a refit in flight on another thread may see either value)

@@ -152,6 +152,18 @@ __device__ unsigned long long g_trace[6 * 8192];   // per workgroup: wall start,
 // by tile -- for a whole-tile job exactly the sum it used to store, so a list without halves reproduces the old bits.
 constexpr int PIECE_WHOLE = 0, PIECE_UPPER = 1, PIECE_LOWER = 2, PIECE_UPPER_SOLO = 3;
 
+// The sum of squares of one 64-row half of V for one candidate, shared by k_trigemm_sq and k_trigemm_rows so that the two cannot
+// differ in a bit (operand order, contraction of v * v + s): the lane of k = lane >> 4, b1 = (lane >> 3) & 1 adds the squares of
+// rows 8 mi + 4 b1 + k of the half over mi = 0..7 in sequence (sq_step; the alpha row left out), then the butterflies over b1 and
+// k (sq_tree) give every lane the half's sum.
+__device__ __forceinline__ double sq_step(double s, double v) { return s + v * v; }
+__device__ __forceinline__ double sq_tree(double s) {
+    s += __shfl_xor(s, 8);
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    return s;
+}
+
 // one job: row piece (rt, mode) of W against candidate tile ct of the chunk (all arguments wave-uniform)
 template <int KS>
 __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const double* __restrict__ W, int64_t ldw,
@@ -191,14 +203,12 @@ __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const doub
             if (grow == alpha_row && rows_mine) {
                 __hip_atomic_store(mu_raw + r_off + (int64_t)ct * CW + acc_col<NJ>(lane, wc, nj), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-                s += v * v;
+                s = sq_step(s, v);
             }
             if (VT != nullptr && grow < alpha_row && rows_mine)
                 VT[((int64_t)ct * CW + acc_col<NJ>(lane, wc, nj)) * ldv + grow] = v;
         }
-        s += __shfl_xor(s, 8);
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
+        s = sq_tree(s);
         if (lane < 8) red[wr * CW + wc * 8 * NJ + 8 * nj + lane] = s;
     }
     }
@@ -517,9 +527,9 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 // tiles (phase A: k_trigemm_sq over the row pieces with rt < m, all candidates) every candidate gets an UPPER BOUND of the score
 // the full pass would compute for it (k_prune_bound).  Round 1 scores the 64 candidates of highest bound exactly; its best value
 // L is an exactly computed score.  Round 2 scores exactly every other candidate whose bound is not below L.  A dropped candidate
-// has score <= bound < L, so it can neither win nor tie: the record equals the full pass's bit for bit (the exact rounds run the
-// same row pieces on the same K*' rows -- gathered, a column of the contraction depends on its own K*' row only -- and add the
-// partial sums in the fused finish's order).
+// has score <= bound < L, so it can neither win nor tie: the record equals the full pass's bit for bit (the exact rounds compute
+// every element of V with k_trigemm_sq's MFMA chain -- k_trigemm_rows, or k_trigemm_sq itself on gathered K*' rows: a column of
+// the contraction depends on its own K*' row only -- and add the partial sums in the fused finish's order).
 //
 // The bound, per candidate (u = 2^-53, n = Npad + 64 >= the number of terms of any summation of the alpha row):
 //   s2_up = max(s_f^2 - sum_{t < m} (q[2t] + q[2t+1]), 0): every partial sum is >= 0 and rounded addition is monotone, so the prefix
@@ -642,13 +652,185 @@ __global__ __launch_bounds__(256) void k_prune_compact(const double* __restrict_
 }
 
 // K*' rows of the listed candidates, packed (workgroup i: row list[i]; the grid is sized for the worst case)
+// sq_min >= 0: a list of at most sq_min candidates is k_trigemm_rows's -- nothing is gathered and live_out (k_trigemm_sq's count) is 0
 __global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ list, const unsigned* __restrict__ cnt,
-                                                      const double* __restrict__ src, int64_t ld, int64_t ncols, double* __restrict__ dst) {
-    const int i = blockIdx.x;
-    if (i >= (int)*cnt) return;
+                                                      const double* __restrict__ src, int64_t ld, int64_t ncols, double* __restrict__ dst,
+                                                      int sq_min, unsigned* __restrict__ live_out) {
+    const int i = blockIdx.x, n = (int)*cnt;
+    if (i == 0 && threadIdx.x == 0) *live_out = n > sq_min ? (unsigned)n : 0u;
+    if (i >= n || n <= sq_min) return;
     const d2* s = reinterpret_cast<const d2*>(src + (int64_t)list[i] * ld);
     d2* d = reinterpret_cast<d2*>(dst + (int64_t)i * ld);
     for (int64_t j = threadIdx.x; j < ncols / 2; j += 256) d[j] = s[j];
+}
+
+// ---- the exact rounds, row-split: k_trigemm_rows ------------------------------------------------------------------------------
+// k_trigemm_sq runs a row piece against a 64-wide candidate tile as ONE job: for round 1 (64 candidates) that is one workgroup per
+// row tile, and the job of the last tiles (K = N: ~190 chunks of 16) runs alone on one CU for ~0.2 ms.  Here a workgroup owns one
+// 64-row HALF of a row tile against RS_COLS listed candidates and walks the half's whole contraction extent, so a round spreads over
+// (halves x candidate groups) workgroups.  Every element of V comes out bit for bit as in k_trigemm_sq<2>: an element of an
+// MFMA's result depends on its own A row and B column only, so what changes is which rows and columns share an instruction, never an element's
+// chain:
+//   * v_mfma_f64_4x4x4 k-slot k of chunk kc carries contraction index 16 kc + 8 h + 2 k (the pair's even member), the next
+//     instruction the odd one into the same accumulator (mma_row); h is the contraction half of the wave (khalf there);
+//   * PIECE_WHOLE: kc < 8 (rt + 1), one chain per h, v = a0 + a1 (the loop's LDS fold).  The upper half stops at kc = 8 rt + 4: from
+//     there on every row group of it is skipped there as well;
+//   * PIECE_UPPER_SOLO (the loop's half mode): kc < 8 rt + 4, chains e_h (even members) and o_h (odd), v = (e0 + e1) + (o0 + o1);
+//   * an 8-row group G of the tile skips chunk kc >= tri_kc = 8 rt when G < 2 (kc - tri_kc) + h (chunk_mma's skip);
+//   * q of the half: sq_step over the rows of a lane in k_trigemm_sq's accumulator layout, then sq_tree (shared helpers).
+// Only the product build's pieces (whole tiles, the solo last half) and the 8-wave loop are reproduced: under the measurement
+// knobs (halved tiles, BOHIP_KS8=0) the pruned pass keeps k_trigemm_sq for its rounds.
+// Sizing: a workgroup is 4 waves (h x two 32-row quarters), 8 accumulator chains of 8 x 8 per wave, 16 MFMAs per wave and chunk
+// (~0.1 us).  The operands come by LDS-DMA as whole 128-B rows, RS_DEPTH chunks deep, one barrier per chunk.  Measured on MI355X
+// (round 1 at N = 3000, 64 candidates, 188 chunks in the longest half): the same loop with its operands loaded straight into VGPRs
+// (16-B fragments, each fetched by two lanes and every 128-B row by two waves) took 129 us and 170 us with 8 waves of 16 rows and
+// more loads in flight (bench step 0.28 against 0.32 ms) -- the per-CU fetch of scattered fragments bound it, not the latency;
+// whole rows by DMA: 60 us.  The column groups of a half run on one XCD: W's rows come from the Infinity Cache once per XCD.
+constexpr int RS_COLS = 16, RS_WAVES = 4, RS_THREADS = 64 * RS_WAVES, RS_DEPTH = 6;
+constexpr int RS_RG = 16 / RS_WAVES;   // 8-row groups per wave
+constexpr int RS_BUF = (64 + RS_COLS) * KC;                  // doubles of one chunk's operands in LDS
+constexpr int RS_LDS_BYTES = RS_DEPTH * RS_BUF * 8;          // dynamic LDS of k_trigemm_rows
+struct RowsParams {
+    const double* W;
+    int64_t ldw;
+    const double* KsT;       // chunk [R][ldk]; column i of the round is row list[i]
+    int64_t ldk;
+    const int* list;
+    const unsigned* cnt;     // the list's length (device)
+    int cnt_max;             // the launch's worst case: a longer list is not this launch's (k_trigemm_sq takes it), every workgroup leaves
+    const int* halves;       // rt | hh << 16 | solo << 17, heaviest first (host: rows_halves)
+    int NH, G;               // halves in the table, candidate groups of RS_COLS
+    int64_t alpha_row;
+    double* q;               // [2 rt + hh][ldq] at the list position
+    int64_t ldq;
+    double* mu;              // [list position]
+};
+__global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
+    __shared__ double xch[2 * 64 * 16];          // the h = 1 waves' chains
+    __shared__ double vb[64 * RS_COLS];          // v of the half [row][column]
+    // an XCD owns the halves x, x + 8, ... (block b runs on XCD b % 8) with all their candidate groups: W's rows are fetched once
+    // per XCD, and the heaviest halves start first
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int hi = xcd + 8 * (slot / rp.G), grp = slot % rp.G;
+    const int n = (int)*rp.cnt;
+    if (hi >= rp.NH || n > rp.cnt_max || grp * RS_COLS >= n) return;
+    const int code = __builtin_amdgcn_readfirstlane(rp.halves[hi]);
+    const int rt = code & 0xffff, hh = (code >> 16) & 1;
+    const bool solo = (code >> 17) & 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = __builtin_amdgcn_readfirstlane(wave / (RS_WAVES / 2)), wq = __builtin_amdgcn_readfirstlane(wave % (RS_WAVES / 2));
+    const int k = lane >> 4, b = (lane >> 2) & 3;
+    const int tri_kc = 8 * rt, kc_end = tri_kc + (hh == 0 ? 4 : 8);
+    const int g0 = 8 * hh + RS_RG * wq;          // row group (8 rows) of the tile behind this wave's acc[0]
+    // operands: LDS-DMA (global_load_lds, 16 B per lane) of whole 128-B rows, RS_DEPTH chunks deep.  Per chunk 8 pieces of 8 rows of
+    // W and 2 of K*' (rows through the list): wave w issues W pieces w, w + 4 and K*' piece w & 1 (waves 2, 3 repeat the pieces of
+    // waves 0, 1 -- the same bytes to the same place -- so that every wave counts three loads per chunk).  LDS row r holds the row's
+    // 16-B segment s at slot s ^ (r & 7) (gemm_core.h's swizzle).  Fragments as the loop's: lane (k, b, t) reads A rows 4 (b >> 1) + t
+    // of each row group and B column 4 (b & 1) + t of each column group, segment 4 h + k = the pair 16 kc + 8 h + 2 k.
+    extern __shared__ __attribute__((aligned(16))) double rs_ring[];   // [RS_DEPTH][64 + RS_COLS rows][16]
+    const int prow = lane >> 3, sseg = (lane & 7) ^ prow;
+    const double* a_src0 = rp.W + ((int64_t)rt * TILE + 64 * hh + 8 * wave + prow) * rp.ldw + 2 * sseg;
+    const double* a_src1 = a_src0 + (int64_t)32 * rp.ldw;
+    const int ib = grp * RS_COLS + 8 * (wave & 1) + prow;
+    const double* b_src = rp.KsT + (int64_t)(ib < n ? rp.list[ib] : rp.list[0]) * rp.ldk + 2 * sseg;
+    auto issue = [&](int kc, int buf) {
+        kc = min(kc, kc_end - 1);   // (past the end: a harmless re-read into a free buffer that keeps the wait counts straight)
+        double* d = rs_ring + buf * RS_BUF;
+        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(a_src0 + (int64_t)kc * KC), (lds_void_ptr)(d + 8 * wave * KC), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(a_src1 + (int64_t)kc * KC), (lds_void_ptr)(d + (8 * wave + 32) * KC), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(b_src + (int64_t)kc * KC), (lds_void_ptr)(d + (64 + 8 * (wave & 1)) * KC), 16, 0, 0);
+    };
+    const int rr = 4 * (b >> 1) + (lane & 3), cc = 4 * (b & 1) + (lane & 3), S = 4 * h + k;
+    const uint32_t ring0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const double*)rs_ring;
+    const uint32_t fa = ring0 + (uint32_t)(((8 * RS_RG * wq + rr) * KC + 2 * (S ^ rr)) * 8);
+    const uint32_t fb = ring0 + (uint32_t)(((64 + cc) * KC + 2 * (S ^ cc)) * 8);
+    double acc[RS_RG][2], acc2[RS_RG][2];   // WHOLE: acc (both members); SOLO: acc the even members, acc2 the odd ones
+    auto run = [&](auto solo_tag) {
+        constexpr bool SOLO = decltype(solo_tag)::value;
+#pragma unroll
+        for (int i = 0; i < RS_RG; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = acc2[i][j] = 0.0;
+#pragma unroll
+        for (int p = 0; p < RS_DEPTH - 1; ++p) issue(p, p);
+        int cur = 0;
+        for (int kc = 0; kc < kc_end; ++kc) {
+            // chunk kc has landed (the RS_DEPTH - 2 later ones stay in flight); after the barrier every wave's pieces of it are in LDS
+            // and every wave is done reading the buffer of chunk kc - 1, which the next issue refills
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (RS_DEPTH - 2)) : "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            issue(kc + RS_DEPTH - 1, cur == 0 ? RS_DEPTH - 1 : cur - 1);
+            const uint32_t off = (uint32_t)(cur * RS_BUF * 8);
+            d2 a0 = ds_read128<0>(fa + off), a1 = ds_read128<1024>(fa + off), a2 = ds_read128<2048>(fa + off),
+               a3 = ds_read128<3072>(fa + off), b0 = ds_read128<0>(fb + off), b1 = ds_read128<1024>(fb + off);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1));
+            const d2 av[4] = {a0, a1, a2, a3}, bv[2] = {b0, b1};
+            const int skip = kc >= tri_kc ? 2 * (kc - tri_kc) + h - g0 : 0;   // row groups g0 + i, i < skip: all-zero in the block
+#pragma unroll
+            for (int i = 0; i < RS_RG; ++i) {
+                if (skip > i) continue;
+                if constexpr (SOLO) {
+                    mma_row<2, 1>(av[i], bv, acc[i]);
+                    mma_row<2, 2>(av[i], bv, acc2[i]);
+                } else {
+                    mma_row<2, 0>(av[i], bv, acc[i]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            cur = cur + 1 == RS_DEPTH ? 0 : cur + 1;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    if (solo) run(std::true_type{});
+    else run(std::false_type{});
+    // fold the contraction halves in the loop's order, then v into vb in the rows' order
+    if (h == 1) {
+#pragma unroll
+        for (int i = 0; i < RS_RG; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                xch[((wq * RS_RG + i) * 2 + j) * 64 + lane] = acc[i][j];
+                xch[64 * 16 + ((wq * RS_RG + i) * 2 + j) * 64 + lane] = acc2[i][j];
+            }
+    }
+    __syncthreads();
+    if (h == 0) {
+#pragma unroll
+        for (int i = 0; i < RS_RG; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const double a1 = xch[((wq * RS_RG + i) * 2 + j) * 64 + lane];
+                double v = acc[i][j] + a1;
+                if (solo) {
+                    const double o1 = xch[64 * 16 + ((wq * RS_RG + i) * 2 + j) * 64 + lane];
+                    v = v + (acc2[i][j] + o1);
+                }
+                const int row = 8 * (RS_RG * wq + i) + 4 * (b >> 1) + k, col = 8 * j + 4 * (b & 1) + (lane & 3);
+                vb[row * RS_COLS + col] = v;
+            }
+    }
+    __syncthreads();
+    if (wave >= 2) return;
+    // wave w: candidate columns 8 w .. 8 w + 7 in k_trigemm_sq's accumulator layout (lane (k, b, t): column 4 (b & 1) + t)
+    const int col = 8 * wave + 4 * (b & 1) + (lane & 3), i_list = grp * RS_COLS + col;
+    const int64_t row_base = (int64_t)rt * TILE + 64 * hh;
+    double s = 0.0;
+#pragma unroll
+    for (int mi = 0; mi < 8; ++mi) {
+        const int row = 8 * mi + 4 * (b >> 1) + k;
+        const double v = vb[row * RS_COLS + col];
+        if (row_base + row == rp.alpha_row) {
+            if (i_list < n) rp.mu[i_list] = v;
+        } else {
+            s = sq_step(s, v);
+        }
+    }
+    s = sq_tree(s);
+    if (lane < 8 && i_list < n) {
+        rp.q[(int64_t)(2 * rt + hh) * rp.ldq + i_list] = s;
+        if (solo) rp.q[(int64_t)(2 * rt + 1) * rp.ldq + i_list] = 0.0;   // no sibling half: its slot is zero
+    }
 }
 
 // exact scores of the listed candidates: q in the fused finish's order (t < m from phase A at the candidate's index, t >= m from
