@@ -6,7 +6,8 @@ libbohip.so (HIP, gfx950).  See DESIGN.md / INTEGRATION.md.
 """
 from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
-from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, mean_var, myrand, dims, maxy, update_)
+from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
+                    mean_var, myrand, dims, maxy, update_)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
@@ -22,4 +23,5 @@ __all__ = ["BOpt", "ExpectedImprovement", "ProbabilityOfImprovement", "UpperConf
            "MutualInformation", "boptimize_", "MAPGPOptimizer", "NoModelOptimizer", "Min", "Max", "BrochuBetaScaling",
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
            "maxduration_", "maxiterations_", "optimize",
-           "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard"]
+           "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
+           "Mat32Iso", "Mat12Ard", "Mat12Iso"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BOHIP_LIB") or os.path.join(_HERE, "csrc", "libbohip.so")   # BOHIP_LIB: measurement builds (csrc/abl)
 
 OK, E_ARG, E_NOTPD, E_HIP, E_NODEVICE, E_STATE, E_UNSUPPORTED, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
-KERN = {"SEArd": 0, "SEIso": 1, "Mat52Ard": 2}
+KERN = {"SEArd": 0, "SEIso": 1, "Mat52Ard": 2, "Mat32Ard": 3, "Mat12Ard": 4, "Mat52Iso": 5, "Mat32Iso": 6, "Mat12Iso": 7}
 ACQ = {"EI": 0, "PI": 1, "UCB": 2, "MI": 3, "MaxMean": 4, "ThompsonDraw": 5}   # (5: bohip_gp_direct_max only)
 INFO_PIVOT, INFO_CAPACITY, INFO_REFITS, INFO_APPENDS = 0, 1, 2, 3
 INFO_CHOL_FORM, INFO_CHOL_FALLBACKS, INFO_CHOL_ABORT_TILES, INFO_JITTER_STEPS = 4, 5, 6, 7

@@ -192,13 +192,30 @@ struct bohip_gp {
     std::vector<double> tms;
 };
 
+// ABI kernel id -> the family the device kernels branch on, and whether the kernel has one length-scale (iso)
+static int kern_family(int id) {
+    switch (id) {
+        case KERN_MAT52ARD: case KERN_MAT52ISO: return FAM_M52;
+        case KERN_MAT32ARD: case KERN_MAT32ISO: return FAM_M32;
+        case KERN_MAT12ARD: case KERN_MAT12ISO: return FAM_M12;
+        default: return FAM_SE;
+    }
+}
+static bool kern_iso(int id) { return id == KERN_SEISO || id == KERN_MAT52ISO || id == KERN_MAT32ISO || id == KERN_MAT12ISO; }
+
+// The kernels that evaluate k are instantiated twice (template argument LOW): the Matérn 1/2 and 3/2 families run their own
+// instantiation, so the SE / Matérn 5/2 one compiles to the code it had before those families existed.
+static bool fam_low(const KernelHyper& h) { return h.fam == FAM_M12 || h.fam == FAM_M32; }
+#define LAUNCH_FAM(lo, k_low, k_std, ...) \
+    do { if (lo) hipLaunchKernelGGL(k_low, __VA_ARGS__); else hipLaunchKernelGGL(k_std, __VA_ARGS__); } while (0)
+
 static KernelHyper make_hyper(const bohip_gp* g) {
     KernelHyper h;
-    h.kern = g->kern;
+    h.fam = kern_family(g->kern);
     h.d = g->d;
     h.sigma2 = std::exp(2.0 * g->logsig);
     for (int k = 0; k < DMAX; ++k) h.il2[k] = 0.0;
-    for (int k = 0; k < g->d; ++k) h.il2[k] = std::exp(-2.0 * g->loglen[g->kern == KERN_SEISO ? 0 : k]);
+    for (int k = 0; k < g->d; ++k) h.il2[k] = std::exp(-2.0 * g->loglen[kern_iso(g->kern) ? 0 : k]);
     return h;
 }
 
@@ -1499,7 +1516,9 @@ static int refit_once(bohip_gp* g, double jitter) {
     {
         const int rpb = 32;
         dim3 grid((Npad + 255) / 256, (Npad + rpb - 1) / rpb);
-#define BC(DTV) hipLaunchKernelGGL(k_build_cov<DTV>, grid, dim3(256), 0, g->stream, g->dX, N, Npad, hp, noise, g->dL, ld, rpb)
+        const bool lo = fam_low(hp);
+#define BC(DTV) LAUNCH_FAM(lo, (k_build_cov<DTV, true>), (k_build_cov<DTV, false>), grid, dim3(256), 0, g->stream, g->dX, N, Npad, hp, \
+                           noise, g->dL, ld, rpb)
         if (g->d <= 2) BC(2); else if (g->d <= 4) BC(4); else if (g->d <= 8) BC(8); else if (g->d <= 16) BC(16);
         else if (g->d <= 32) BC(32); else BC(64);
 #undef BC
@@ -1792,8 +1811,8 @@ static int append_incremental(bohip_gp* g, int64_t N0, int64_t p, int* defer_inf
     const double noise = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;
     HIPCHK(hipMemsetAsync(g->dinfo, 0, sizeof(int), g->stream));
     t_begin(g, "append_cov_rows");
-    hipLaunchKernelGGL(k_cov_rows, dim3((Npad1 + 255) / 256, Npad1 - N0), dim3(256), 0, g->stream, g->dX, N0, N1, Npad1,
-                       hp, noise, g->dL, g->dW, g->dWT, ld);
+    LAUNCH_FAM(fam_low(hp), k_cov_rows<true>, k_cov_rows<false>, dim3((Npad1 + 255) / 256, Npad1 - N0), dim3(256), 0, g->stream, g->dX,
+               N0, N1, Npad1, hp, noise, g->dL, g->dW, g->dWT, ld);
     HIPCHK(hipGetLastError());
     t_end(g);
     t_begin(g, "append_L21");
@@ -1940,7 +1959,8 @@ static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1,
     // two per block (ten in a row on 12 workgroups were a serial chain of ten `exp`s per thread)
     const int rb = r1 - r0 <= 32 ? 2 : 16;
     dim3 grid((Npad + 255) / 256, (r1 - r0 + rb - 1) / rb);
-    hipLaunchKernelGGL(k_kstar<DT>, grid, dim3(256), 0, g->stream, g->dX, g->n, Npad, dXs, r0, r1, hp, g->dKsT, g->ld, rb);
+    LAUNCH_FAM(fam_low(hp), (k_kstar<DT, true>), (k_kstar<DT, false>), grid, dim3(256), 0, g->stream, g->dX, g->n, Npad, dXs, r0, r1, hp,
+               g->dKsT, g->ld, rb);
 }
 
 // The row pieces of k_trigemm_sq (kernels_score.hip), heaviest first: which row tiles go as two 64-row halves is a function
@@ -2058,8 +2078,12 @@ extern "C" int bohip_debug_small_trace_read(unsigned long long* out) {   // meas
 template <int DT, int G>
 static void launch_small_pass(bohip_gp* g, const SmallCommon& sc, const SmallCommon& scu, const SmallV& sv, const SmallU* su, const KernelHyper& hp,
                               int npass) {
-    hipLaunchKernelGGL((k_small_v<DT, G>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0, g->stream, sc, sv, hp);
-    if (su) hipLaunchKernelGGL((k_small_u<DT, G>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0, g->stream, scu, *su, hp);
+    const bool lo = fam_low(hp);
+    LAUNCH_FAM(lo, (k_small_v<DT, G, true>), (k_small_v<DT, G, false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
+               g->stream, sc, sv, hp);
+    if (su)
+        LAUNCH_FAM(lo, (k_small_u<DT, G, true>), (k_small_u<DT, G, false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
+                   g->stream, scu, *su, hp);
 }
 template <int DT>
 static void launch_small_pass_g(bohip_gp* g, int G, const SmallCommon& sc, const SmallCommon& scu, const SmallV& sv, const SmallU* su,
@@ -2508,13 +2532,13 @@ static void launch_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, 
                         double* d_grad, const double* UT, int S, const GradQ& gq) {
     if constexpr (DT <= 16) {   // large batches: 4 candidates per workgroup share the observation stream
         if (r1 - r0 > SMALL_MAX) {
-            hipLaunchKernelGGL(k_grad_finish_tiled<DT>, dim3((unsigned)((r1 - r0 + GC - 1) / GC)), dim3(256), 0, g->stream, g->dX, g->n,
-                               dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad);
+            LAUNCH_FAM(fam_low(hp), (k_grad_finish_tiled<DT, true>), (k_grad_finish_tiled<DT, false>), dim3((unsigned)((r1 - r0 + GC - 1) / GC)),
+                       dim3(256), 0, g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad);
             return;
         }
     }
-    hipLaunchKernelGGL(k_grad_finish<DT>, dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0, g->stream, g->dX, g->n, dXs, r0, r1,
-                       hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad, g->dgparts, g->dgcount, gq);
+    LAUNCH_FAM(fam_low(hp), (k_grad_finish<DT, true>), (k_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
+               g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad, g->dgparts, g->dgcount, gq);
 }
 static int launch_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, const AcqParams& ap,
                            double* d_grad, const double* UT, const GradQ& gq = GradQ{}) {
@@ -2628,7 +2652,7 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
     *out = nullptr;
     if (d < 1 || d > DMAX) return fail(BOHIP_E_ARG, "d must be in [1, 64]");
     if (capacity < 1) capacity = 1;
-    if (kernel_id < 0 || kernel_id > 2) return fail(BOHIP_E_ARG, "unknown kernel_id");
+    if (kernel_id < 0 || kernel_id >= KERN_COUNT) return fail(BOHIP_E_ARG, "unknown kernel_id");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(BOHIP_E_NODEVICE, "no HIP device visible; libbohip has no CPU fallback");
@@ -2724,9 +2748,9 @@ void bohip_gp_destroy(bohip_gp* g) {
 
 int bohip_gp_set_hyper(bohip_gp* g, const double* loglen, double logsig, double lognoise, double mean_const) {
     if (!g || !loglen) return fail(BOHIP_E_ARG, "null argument");
-    const int nl = g->kern == KERN_SEISO ? 1 : g->d;
+    const int nl = kern_iso(g->kern) ? 1 : g->d;
     for (int k = 0; k < nl; ++k) g->loglen[k] = loglen[k];
-    if (g->kern == KERN_SEISO)
+    if (kern_iso(g->kern))
         for (int k = 1; k < g->d; ++k) g->loglen[k] = loglen[0];
     g->logsig = logsig;
     g->lognoise = lognoise;
@@ -2856,7 +2880,7 @@ int bohip_gp_mll(bohip_gp* g, double* mll) {
 int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_mean, double* d_kern) {
     if (!g || !mll || !d_lognoise || !d_mean || !d_kern) return fail(BOHIP_E_ARG, "null argument");
     HIPCHK(hipSetDevice(g->device));
-    const int iso = g->kern == KERN_SEISO, nl = iso ? 1 : g->d;
+    const int iso = kern_iso(g->kern), nl = iso ? 1 : g->d;
     if (g->n == 0) {
         *mll = 0.0; *d_lognoise = 0.0; *d_mean = 0.0;
         for (int k = 0; k <= nl; ++k) d_kern[k] = 0.0;
@@ -2887,8 +2911,9 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     }
     const KernelHyper hp = make_hyper(g);
     const double noise_var = std::exp(2.0 * g->lognoise);
-#define DM(DTV) hipLaunchKernelGGL(k_dmll_parts<DTV>, grid, dim3(256), 0, g->stream, g->dX, N, hp, noise_var, g->dS, ld, \
-                                   g->dalpha, rpb, g->ddmll_parts)
+    const bool lo = fam_low(hp);
+#define DM(DTV) LAUNCH_FAM(lo, (k_dmll_parts<DTV, true>), (k_dmll_parts<DTV, false>), grid, dim3(256), 0, g->stream, g->dX, N, hp, \
+                           noise_var, g->dS, ld, g->dalpha, rpb, g->ddmll_parts)
     if (g->d <= 2) DM(2); else if (g->d <= 4) DM(4); else if (g->d <= 8) DM(8); else if (g->d <= 16) DM(16);
     else if (g->d <= 32) DM(32); else DM(64);
 #undef DM
@@ -3009,7 +3034,9 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, T, g->dmu_raw, R,
                        std::exp(2.0 * g->logsig), g->beta, ap, g->dmu, g->dvar, (double*)nullptr, (Best*)nullptr);
     dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
-#define PC(DTV) hipLaunchKernelGGL(k_post_cov<DTV>, grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV, g->cov_cap, g->dcov, R)
+    const bool lo = fam_low(hp);
+#define PC(DTV) LAUNCH_FAM(lo, (k_post_cov<DTV, true>), (k_post_cov<DTV, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV, \
+                           g->cov_cap, g->dcov, R)
     if (g->d <= 2) PC(2); else if (g->d <= 4) PC(4); else if (g->d <= 8) PC(8); else if (g->d <= 16) PC(16);
     else if (g->d <= 32) PC(32); else PC(64);
 #undef PC
@@ -3198,10 +3225,13 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
         pw.max_ticks = g->asc_maxtime > 0.0 ? (unsigned long long)(g->asc_maxtime * 1e8) : 0ull;
         pw.passes = st.accepted;
         t_begin(g, "ascent_wg");
-        if (d <= 2) hipLaunchKernelGGL(k_ascent_wg<2>, dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-        else if (d <= 4) hipLaunchKernelGGL(k_ascent_wg<4>, dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-        else if (d <= 8) hipLaunchKernelGGL(k_ascent_wg<8>, dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-        else hipLaunchKernelGGL(k_ascent_wg<16>, dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
+        const bool lo = fam_low(pw.hp);
+#define AW(DTV) LAUNCH_FAM(lo, (k_ascent_wg<DTV, true>), (k_ascent_wg<DTV, false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw)
+        if (d <= 2) AW(2);
+        else if (d <= 4) AW(4);
+        else if (d <= 8) AW(8);
+        else AW(16);
+#undef AW
         HIPCHK(hipGetLastError());
         t_end(g);
         // the packed result goes straight into the pinned host block (second half: the first holds the inputs): ~100 doubles written by one

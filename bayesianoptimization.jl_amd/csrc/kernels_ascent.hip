@@ -532,7 +532,7 @@ struct AscWgParams {
     unsigned long long max_ticks;       // maxtime in wall_clock64 ticks (0: none)
     int* passes;                        // [R] evaluation passes start r needed
 };
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
 #pragma clang fp contract(off)
     __shared__ double ks[AWG_NMAX + 1], V[AWG_NMAX + 1], U[AWG_NMAX];
@@ -582,7 +582,7 @@ __global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
                 const double t = ((k < d && j < N) ? p.X[j * d + k] : 0.0) - xs[k];
                 rr += s_il2[k] * (t * t);
             }
-            ks[j] = j < N ? cov_from_r_fast(p.hp.kern, p.hp.sigma2, rr) : 0.0;
+            ks[j] = j < N ? cov_from_r_fast<LOW>(p.hp.fam, p.hp.sigma2, rr) : 0.0;
         }
         __syncthreads();
         // V[i] = sum_{k <= i} W[i][k] k*[k]   (row N: alpha).  A wave takes FOUR of its rows at a time (rows i, i + 8, i + 16, i + 24):
@@ -665,7 +665,9 @@ __global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
                     rr += s_il2[k] * (t * t);
                 }
             double fac;
-            if (p.hp.kern == KERN_MAT52ARD) {
+            if constexpr (LOW) {
+                fac = matern_lo_fx(p.hp.fam, p.hp.sigma2, rr);
+            } else if (p.hp.fam == FAM_M52) {
                 const double sq = sqrt(5.0) * sqrt(rr);
                 fac = -(5.0 / 3.0) * p.hp.sigma2 * (1.0 + sq) * exp(-sq);
             } else {

@@ -1,5 +1,5 @@
 // kernels_linalg.hip -- model-update kernels (rows A1-A3 of SURVEY.md section 8):
-//   k_build_cov      SEArd/SEIso/Mat52Ard kernel-matrix assembly, lower 128-tiles (HBM-write bound)
+//   k_build_cov      SE / Matérn 1/2, 3/2, 5/2 kernel-matrix assembly, lower 128-tiles (HBM-write bound)
 //   k_potf2_inv      128x128 diagonal block: Cholesky + triangular inverse in LDS (latency bound)
 //   k_gemm_nt        FP64 MFMA contraction C = alpha*A*B' + beta*C, both operands K-major (panel solve,
 //                    trailing updates, recursive triangular inverse W = L^-1, U' = V'W of the gradient path)
@@ -20,15 +20,22 @@ namespace bohip {
 // X is [N][d] row-major (= Julia's d x N column-major).  64 x 64 outputs per workgroup.
 // Written with contraction off so entries are bit-identical to the oracle's up to exp().
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double cov_from_r(int kern, double sigma2, double r) {
-    if (kern == KERN_MAT52ARD) {
-        const double R = sqrt(r), s = sqrt(5.0) * R;
-        return sigma2 * (1.0 + s + 5.0 / 3.0 * r) * exp(-s);
+// LOW (a template argument of every kernel that evaluates k): the Matérn 1/2 and 3/2 families (common.h).  The SE / Matérn 5/2
+// instantiations (LOW = false) compile to the code they had before those families existed.
+template <bool LOW>
+__device__ __forceinline__ double cov_from_r(int fam, double sigma2, double r) {
+    if constexpr (LOW) {
+        return matern_lo_k(fam, sigma2, r);
+    } else {
+        if (fam == FAM_M52) {
+            const double R = sqrt(r), s = sqrt(5.0) * R;
+            return sigma2 * (1.0 + s + 5.0 / 3.0 * r) * exp(-s);
+        }
+        return sigma2 * exp(-0.5 * r);
     }
-    return sigma2 * exp(-0.5 * r);
 }
 
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_build_cov(const double* __restrict__ X, int64_t N, int64_t Npad,
                                                    KernelHyper hp, double noise, double* __restrict__ K,
                                                    int64_t ld, int rows_per_block) {
@@ -66,7 +73,7 @@ __global__ __launch_bounds__(256) void k_build_cov(const double* __restrict__ X,
                 const double t = xi_l[c * DT + k] - xj[k];
                 r += w[k] * (t * t);
             }
-            v = cov_from_r(hp.kern, hp.sigma2, r);
+            v = cov_from_r<LOW>(hp.fam, hp.sigma2, r);
             if (i == j) v += noise;
         } else {
             v = (i == j) ? 1.0 : 0.0;
@@ -946,7 +953,7 @@ __global__ __launch_bounds__(256) void k_mll(const double* __restrict__ L, int64
 // entries of K and dK/dll_k are recomputed from X (cheaper than a second N x N buffer).  Per-block partial sums
 // [block][NP], NP = d + 3: {logNoise, beta, ll_0..ll_{d-1}, logsig}; k_dmll_final adds them in a fixed order.
 // ------------------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_dmll_parts(const double* __restrict__ X, int64_t N, KernelHyper hp,
                                                     double noise_var, const double* __restrict__ Kinv, int64_t ld,
                                                     const double* __restrict__ alpha, int rows_per_block,
@@ -979,7 +986,10 @@ __global__ __launch_bounds__(256) void k_dmll_parts(const double* __restrict__ X
             r += t[k];
         }
         double Kij, fac;
-        if (hp.kern == KERN_MAT52ARD) {
+        if constexpr (LOW) {
+            Kij = matern_lo_k(hp.fam, hp.sigma2, r);
+            fac = -matern_lo_fx(hp.fam, hp.sigma2, r);   // 0 on the diagonal for M12, whose limit there is 0
+        } else if (hp.fam == FAM_M52) {
             const double sq = sqrt(5.0) * sqrt(r), e = exp(-sq);
             Kij = hp.sigma2 * (1.0 + sq + 5.0 / 3.0 * r) * e;
             fac = 5.0 / 3.0 * hp.sigma2 * (1.0 + sq) * e;
@@ -1015,7 +1025,7 @@ __global__ __launch_bounds__(256) void k_dmll_parts(const double* __restrict__ X
     __syncthreads();
     for (int k = threadIdx.x; k < NP; k += 256) out[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
 }
-// out[k] = sum over blocks of parts[b][k] in a fixed strided order + tree; SEIso folds the d length entries into one.
+// out[k] = sum over blocks of parts[b][k] in a fixed strided order + tree; an iso kernel folds the d length entries into one.
 // One workgroup per output parameter.
 __global__ __launch_bounds__(256) void k_dmll_final(const double* __restrict__ parts, int64_t nblocks, int NP, int d,
                                                     int iso, double* __restrict__ out) {
@@ -1052,6 +1062,7 @@ constexpr int APPEND_PMAX = 32;   // larger batches take the full refit
 constexpr int APPEND_CHUNK = 8;   // right-hand sides per pass over W
 
 // New rows [N0, Npad1) of cK into L (cols 0..i) and identity padding rows into L and W.
+template <bool LOW>
 __global__ __launch_bounds__(256) void k_cov_rows(const double* __restrict__ X, int64_t N0, int64_t N1, int64_t Npad1,
                                                   KernelHyper hp, double noise, double* __restrict__ L,
                                                   double* __restrict__ W, double* __restrict__ WT, int64_t ld) {
@@ -1067,7 +1078,7 @@ __global__ __launch_bounds__(256) void k_cov_rows(const double* __restrict__ X, 
             const double t = X[i * d + k] - X[j * d + k];
             r += hp.il2[k] * (t * t);
         }
-        double v = cov_from_r(hp.kern, hp.sigma2, r);
+        double v = cov_from_r<LOW>(hp.fam, hp.sigma2, r);
         if (i == j) v += noise;
         L[i * ld + j] = v;
     } else {  // identity padding (also clears a stale alpha row)

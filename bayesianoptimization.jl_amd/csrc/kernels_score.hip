@@ -12,12 +12,18 @@
 
 namespace bohip {
 
-__device__ __forceinline__ double cov_from_r_fast(int kern, double sigma2, double r) {
-    if (kern == KERN_MAT52ARD) {
-        const double R = sqrt(r), s = sqrt(5.0) * R;
-        return sigma2 * (1.0 + s + 5.0 / 3.0 * r) * exp(-s);
+// LOW: the Matérn 1/2 and 3/2 families, a compile-time choice as in kernels_linalg.hip's cov_from_r
+template <bool LOW>
+__device__ __forceinline__ double cov_from_r_fast(int fam, double sigma2, double r) {
+    if constexpr (LOW) {
+        return matern_lo_k(fam, sigma2, r);
+    } else {
+        if (fam == FAM_M52) {
+            const double R = sqrt(r), s = sqrt(5.0) * R;
+            return sigma2 * (1.0 + s + 5.0 / 3.0 * r) * exp(-s);
+        }
+        return sigma2 * exp(-0.5 * r);
     }
-    return sigma2 * exp(-0.5 * r);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -25,7 +31,7 @@ __device__ __forceinline__ double cov_from_r_fast(int kern, double sigma2, doubl
 // candidates whose coordinates are wave-uniform (scalar loads).  Stores are coalesced along j.
 // KsT[r][j] = k(x_j, x*_r) for j < N, 0 for N <= j < Npad.  Xs is [R][d] (d contiguous).
 // ------------------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int64_t N, int64_t Npad,
                                                const double* __restrict__ Xs, int64_t r_begin, int64_t r_end,
                                                KernelHyper hp, double* __restrict__ KsT, int64_t ldk, int rb) {
@@ -57,7 +63,7 @@ __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int
             const double t = xj[k] - xs_l[c * DT + k];
             rr += w[k] * (t * t);
         }
-        const double v = (j < N) ? cov_from_r_fast(hp.kern, hp.sigma2, rr) : 0.0;
+        const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
         KsT[(r0 + c - r_begin) * ldk + j] = v;   // plain stores: non-temporal ones evict K*' from L2/MALL and k_trigemm_sq
                                                    // then runs at 0.70 instead of 0.635 ms (measured)
     }
@@ -69,7 +75,7 @@ __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int
 // VV holds the LOWER triangle of V'V (k_gemm_nt on the stored V'); both halves of cov are written from it so the
 // result is exactly symmetric.  Thread = column s, block walks 16 rows.
 // ------------------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_post_cov(const double* __restrict__ Xs, int64_t R, KernelHyper hp,
                                                   const double* __restrict__ VV, int64_t ldv,
                                                   double* __restrict__ cov, int64_t ldc) {
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(256) void k_post_cov(const double* __restrict__ Xs,
                 rr += hp.il2[k] * (t * t);
             }
         const double vv = (r >= s) ? VV[r * ldv + s] : VV[s * ldv + r];
-        cov[r * ldc + s] = cov_from_r_fast(hp.kern, hp.sigma2, rr) - vv;
+        cov[r * ldc + s] = cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) - vv;
     }
 }
 
@@ -958,7 +964,7 @@ struct GradQ {
     double *mu_out, *var_out, *score_out;
     const unsigned* go;   // not null: return at once when the word is 0 (free-running ascent, see AscentState::ticket)
 };
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ X, int64_t N,
                                                      const double* __restrict__ Xs, int64_t r_begin, int64_t r_end,
                                                      KernelHyper hp, const double* __restrict__ alpha,
@@ -996,7 +1002,9 @@ __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ 
                 rr += hp.il2[k] * (t[k] * t[k]);
             }
         double fac;
-        if (hp.kern == KERN_MAT52ARD) {
+        if constexpr (LOW) {
+            fac = matern_lo_fx(hp.fam, hp.sigma2, rr);
+        } else if (hp.fam == FAM_M52) {
             const double s = sqrt(5.0) * sqrt(rr);
             fac = -(5.0 / 3.0) * hp.sigma2 * (1.0 + s) * exp(-s);
         } else {
@@ -1076,7 +1084,7 @@ __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ 
 // whole observation block X and alpha through L2 (R x 216 KB = 0.9 GB at R = 4096, N = 3000: 180 us); two candidates
 // share each X row and alpha element in registers (0.11 ms).  Same per-candidate summation order as k_grad_finish with one split.
 constexpr int GC = 2;   // 4 needs 259 VGPRs (320 with the coordinates in LDS) and is slower: 0.16 vs 0.11 ms at R = 4096
-template <int DT>
+template <int DT, bool LOW>
 __global__ __launch_bounds__(256) void k_grad_finish_tiled(const double* __restrict__ X, int64_t N,
                                                            const double* __restrict__ Xs, int64_t r_begin, int64_t r_end,
                                                            KernelHyper hp, const double* __restrict__ alpha,
@@ -1113,7 +1121,9 @@ __global__ __launch_bounds__(256) void k_grad_finish_tiled(const double* __restr
                 rr += w[k] * (t[k] * t[k]);
             }
             double fac;
-            if (hp.kern == KERN_MAT52ARD) {
+            if constexpr (LOW) {
+                fac = matern_lo_fx(hp.fam, hp.sigma2, rr);
+            } else if (hp.fam == FAM_M52) {
                 const double s = sqrt(5.0) * sqrt(rr);
                 fac = -(5.0 / 3.0) * hp.sigma2 * (1.0 + s) * exp(-s);
             } else {

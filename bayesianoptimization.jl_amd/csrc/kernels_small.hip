@@ -354,7 +354,7 @@ struct SmallLds {
     __shared__ int sl_flag_;                                                              \
     SmallLds<DT_> L_{sl_lbuf_, sl_xs_, sl_xc_, sl_al_, sl_small_, sl_shb_, &sl_flag_}
 
-template <int DT, int G>
+template <int DT, int G, bool LOW>
 __device__ __forceinline__ void small_v_body(const SmallCommon& sc, unsigned gow, const SmallV& sv, const KernelHyper& hp, int tile, const SmallLds<DT>& L) {
     double* const lbuf = L.lbuf;
     double* const rt2 = lbuf;             // 2 x [128][16] right-hand-side tiles
@@ -403,7 +403,7 @@ __device__ __forceinline__ void small_v_body(const SmallCommon& sc, unsigned gow
                 const double t = xr.x[kk] - xs_l[r * DT + kk];
                 rr += (kk < d ? hp.il2[kk] : 0.0) * (t * t);
             }
-            v[g] = (k < N && pass * 16 + r < sc.P) ? cov_from_r_fast(hp.kern, hp.sigma2, rr) : 0.0;
+            v[g] = (k < N && pass * 16 + r < sc.P) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
         }
         *(d2*)(rt_ + kl * 16 + 4 * i) = d2{v[0], v[1]};
         *(d2*)(rt_ + kl * 16 + 4 * i + 2) = d2{v[2], v[3]};
@@ -487,11 +487,11 @@ __device__ __forceinline__ void small_v_body(const SmallCommon& sc, unsigned gow
     SM_MARK(sc, 0, 10);
     if (tid == 0) { sv.best_out->val = idx >= 0 ? f_best : -INFINITY; sv.best_out->idx = idx >= 0 ? idx + sv.idx_off : -1; }
 }
-template <int DT, int G>
+template <int DT, int G, bool LOW>
 __global__ __launch_bounds__(SP_THREADS) void k_small_v(SmallCommon sc, SmallV sv, KernelHyper hp) {
     const unsigned gow = sc.go ? *sc.go : 1u;
     SMALL_LDS_DECL(DT, L);
-    small_v_body<DT, G>(sc, gow, sv, hp, blockIdx.x, L);
+    small_v_body<DT, G, LOW>(sc, gow, sv, hp, blockIdx.x, L);
 }
 
 // ---- U pass ---------------------------------------------------------------------------------------------------------------------------
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_small_v(SmallCommon sc, SmallV s
 // 10 us contraction, profiles/r05_small_pass_trace_*.txt.)  For the SE kernels d k*_j / d x_k = -k*_j (x_k - X_jk) / l_k^2 with k*_j taken
 // from the V pass's own K*' record (no second exponential).
 struct SmallVPair { d2 a, b; };
-template <int DT, int G>
+template <int DT, int G, bool LOW>
 __device__ __forceinline__ void small_u_body(const SmallCommon& sc, unsigned gow, const SmallU& su, const KernelHyper& hp, int tile, const SmallLds<DT>& L) {
     double* const lbuf = L.lbuf;
     double* const rt2 = lbuf;
@@ -565,7 +565,13 @@ __device__ __forceinline__ void small_u_body(const SmallCommon& sc, unsigned gow
         for (int g = 0; g < 4; ++g) {
             fac[e][g] = 0.0;
             if (g < G && j < N && pass * 16 + 4 * g + q < sc.P) {
-                if (hp.kern == KERN_MAT52ARD) {
+                if constexpr (LOW) {
+                    double rr = 0.0;
+#pragma unroll
+                    for (int k = 0; k < DT; ++k)
+                        if (k < d) { const double t = xs_l[(4 * g + q) * DT + k] - xc_l[cl * d + k]; rr += hp.il2[k] * (t * t); }
+                    fac[e][g] = matern_lo_fx(hp.fam, hp.sigma2, rr);
+                } else if (hp.fam == FAM_M52) {
                     double rr = 0.0;
 #pragma unroll
                     for (int k = 0; k < DT; ++k)
@@ -826,11 +832,11 @@ __device__ __forceinline__ void small_u_body(const SmallCommon& sc, unsigned gow
     }
     SM_MARK(sc, 1, 11);
 }
-template <int DT, int G>
+template <int DT, int G, bool LOW>
 __global__ __launch_bounds__(SP_THREADS) void k_small_u(SmallCommon sc, SmallU su, KernelHyper hp) {
     const unsigned gow = sc.go ? *sc.go : 1u;
     SMALL_LDS_DECL(DT, L);
-    small_u_body<DT, G>(sc, gow, su, hp, blockIdx.x, L);
+    small_u_body<DT, G, LOW>(sc, gow, su, hp, blockIdx.x, L);
 }
 
 }  // namespace bohip

@@ -44,6 +44,7 @@ class MeanConst:
 
 class _Kernel:
     kern = "SEArd"
+    iso = False    # one length-scale (ll has 1 entry) instead of d
 
     def __init__(self, ll, lsigma):
         self.ll = np.atleast_1d(np.asarray(ll, dtype=np.float64)).copy()
@@ -58,11 +59,41 @@ class SEArd(_Kernel):
 class SEIso(_Kernel):
     """SEIso(ll, lσ)  (test/acquisition.jl:2)."""
     kern = "SEIso"
+    iso = True
 
 
 class Mat52Ard(_Kernel):
     """Mat52Ard(ll::Vector, lσ)  (default model, src/BayesianOptimization.jl:259-262)."""
     kern = "Mat52Ard"
+
+
+class Mat52Iso(_Kernel):
+    """Mat52Iso(ll, lσ): k = exp(2lσ) (1 + √5ρ + 5ρ²/3) exp(-√5ρ), ρ = |x-y|/exp(ll)."""
+    kern = "Mat52Iso"
+    iso = True
+
+
+class Mat32Ard(_Kernel):
+    """Mat32Ard(ll::Vector, lσ): k = exp(2lσ) (1 + √3ρ) exp(-√3ρ), ρ² = Σ (x-y)²/exp(2 ll_k)."""
+    kern = "Mat32Ard"
+
+
+class Mat32Iso(_Kernel):
+    """Mat32Iso(ll, lσ): Mat32Ard with one length-scale."""
+    kern = "Mat32Iso"
+    iso = True
+
+
+class Mat12Ard(_Kernel):
+    """Mat12Ard(ll::Vector, lσ): k = exp(2lσ) exp(-ρ), ρ² = Σ (x-y)²/exp(2 ll_k).  Not differentiable where a point meets
+    an observation (ρ = 0): gradients take the minimum-norm subgradient there, that observation contributes 0."""
+    kern = "Mat12Ard"
+
+
+class Mat12Iso(_Kernel):
+    """Mat12Iso(ll, lσ): Mat12Ard with one length-scale (same rule at ρ = 0)."""
+    kern = "Mat12Iso"
+    iso = True
 
 
 class ElasticGPE:
@@ -113,7 +144,7 @@ class ElasticGPE:
     # -- hyper-parameters (GP.set_params!) ---------------------------------------------------------
     def _push_hyper(self):
         ll = self.kernel.ll
-        if self.kernel.kern != "SEIso" and ll.size != self.dim:
+        if not self.kernel.iso and ll.size != self.dim:
             raise ValueError("kernel length-scale vector must have d entries")
         ll = np.ascontiguousarray(np.broadcast_to(ll, (self.dim,)) if ll.size == 1 else ll)
         check(self._lib.bohip_gp_set_hyper(self._h, _ptr(ll), self.kernel.lsigma, self.logNoise, self.mean.beta))
@@ -167,7 +198,7 @@ class ElasticGPE:
     def mll_grad(self):
         """(mll, dlogNoise, dmean, dkern) -- gp.target / gp.dtarget after update_target_and_dtarget!
         (reference src/models/gp.jl:61-63); dkern = [dll..., dlsigma] in the kernel's parameter order."""
-        nk = (1 if isinstance(self.kernel, SEIso) else self.dim) + 1
+        nk = (1 if self.kernel.iso else self.dim) + 1
         m, dn, dm = C.c_double(), C.c_double(), C.c_double()
         dk = np.empty(nk)
         check(self._lib.bohip_gp_mll_grad(self._h, C.byref(m), C.byref(dn), C.byref(dm), _ptr(dk)))

@@ -37,11 +37,22 @@ typedef struct bohip_gp bohip_gp;
 #define BOHIP_E_UNSUPPORTED (-6)
 #define BOHIP_E_COMM (-7)     /* RCCL error, or the devices disagree after the exchange (multi-GPU entry points) */
 
-/* kernel_id: GaussianProcesses.jl kernels the reference's tests/defaults construct
- * (README.md:24, test/acquisition.jl:2, src/BayesianOptimization.jl:259-262) */
+/* kernel_id: GaussianProcesses.jl kernels.  0-2 are the ones the reference's tests/defaults construct (README.md:24,
+ * test/acquisition.jl:2, src/BayesianOptimization.jl:259-262); 3-7 are the other Matérn kernels of that package.
+ * With r = sum_k (x_k - y_k)^2 exp(-2 ll_k), rho = sqrt(r), sigma2 = exp(2 lsigma):
+ *   SE    sigma2 exp(-r/2)                       Matérn 3/2  sigma2 (1 + sqrt3 rho) exp(-sqrt3 rho)
+ *   Matérn 1/2  sigma2 exp(-rho)                 Matérn 5/2  sigma2 (1 + sqrt5 rho + 5r/3) exp(-sqrt5 rho)
+ * ARD kernels take d log length-scales, iso kernels one (loglen[0]).  Matérn 1/2 is not differentiable where a point
+ * coincides with an observation (rho = 0): every gradient (bohip_gp_score_grad, the ascent, bohip_gp_mll_grad) takes
+ * the minimum-norm subgradient there, i.e. that observation contributes 0.                                           */
 #define BOHIP_KERN_SEARD 0
 #define BOHIP_KERN_SEISO 1
 #define BOHIP_KERN_MAT52ARD 2
+#define BOHIP_KERN_MAT32ARD 3
+#define BOHIP_KERN_MAT12ARD 4
+#define BOHIP_KERN_MAT52ISO 5
+#define BOHIP_KERN_MAT32ISO 6
+#define BOHIP_KERN_MAT12ISO 7
 
 /* acq_id + acq_params: the functors of reference src/acquisitionfunctions.jl
  *   EI  :47-50  params {tau}          PI :24-27 params {tau}
@@ -67,7 +78,7 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
 void bohip_gp_destroy(bohip_gp *gp);
 
 /* ---- hyper-parameters (GP.set_params! at reference src/models/gp.jl:60) ------------------
- * loglen: d log length-scales (SEIso: loglen[0] only), logsig: log signal std, lognoise:
+ * loglen: d log length-scales (iso kernels: loglen[0] only), logsig: log signal std, lognoise:
  * logNoise, mean_const: MeanConst beta (0 for MeanZero).  Marks the factor stale; the next
  * append/refit/predict rebuilds K, its Cholesky factor and alpha from the stored x, y.     */
 int bohip_gp_set_hyper(bohip_gp *gp, const double *loglen, double logsig, double lognoise, double mean_const);
@@ -79,7 +90,7 @@ int bohip_gp_set_hyper(bohip_gp *gp, const double *loglen, double logsig, double
 int bohip_gp_append(bohip_gp *gp, const double *X, const double *y, int64_t p);
 
 /* ---- GP.fit! / update_target! role (reference src/models/gp.jl:14-16,61): full rebuild of
- * K (SEArd assembly), its Cholesky factor and alpha from the stored observations.          */
+ * K (kernel-matrix assembly), its Cholesky factor and alpha from the stored observations.          */
 int bohip_gp_refit(bohip_gp *gp);
 
 /* ---- dims(model) :9, maxy(model) :10, model.x / model.y field reads ---------------------- */
@@ -91,7 +102,7 @@ int bohip_gp_get_xy(const bohip_gp *gp, double *X /* d x n, nullable */, double 
 int bohip_gp_mll(bohip_gp *gp, double *mll);
 /* mll and its analytic gradient w.r.t. the log hyper-parameters, in the reference's get_params order
  * [logNoise; mean; kernel (loglen..., logsig)] -- the role of GP.update_target_and_dtarget! + gp.dtarget in
- * optimizemodel! (reference src/models/gp.jl:59-64).  d_kern has d + 1 entries (SEArd, Mat52Ard) or 2 (SEIso).
+ * optimizemodel! (reference src/models/gp.jl:59-64).  d_kern has d + 1 entries (ARD kernels) or 2 (iso kernels).
  * d mll/d theta = 1/2 tr((alpha alpha' - cK^-1) dcK/dtheta); cK^-1 = W'W is formed on the device.          */
 int bohip_gp_mll_grad(bohip_gp *gp, double *mll, double *d_lognoise, double *d_mean, double *d_kern);
 
@@ -110,7 +121,7 @@ int bohip_gp_score(bohip_gp *gp, int acq_id, const double *acq_params, const dou
                    double *score /* R, nullable */, bohip_best *best);
 
 /* ---- wrap_gradient role (reference src/acquisition.jl:11-17): score and d(score)/dx, the
- * latter d x R column-major.  SEArd / SEIso kernels.                                        */
+ * latter d x R column-major.  Every kernel id.                                              */
 int bohip_gp_score_grad(bohip_gp *gp, int acq_id, const double *acq_params, const double *Xs, int64_t R,
                         double *score, double *grad);
 

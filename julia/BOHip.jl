@@ -135,7 +135,10 @@ end
 # Model types.  Field names follow what the reference READS: model.x (d x n), model.y
 # (src/BayesianOptimization.jl:117-119, src/acquisitionfunctions.jl:136, test/warmstart.jl:26-27).
 # =====================================================================================================================
-const KERN = Dict(:SEArd => 0, :SEIso => 1, :Mat52Ard => 2)
+const KERN = Dict(:SEArd => 0, :SEIso => 1, :Mat52Ard => 2, :Mat32Ard => 3, :Mat12Ard => 4, :Mat52Iso => 5, :Mat32Iso => 6,
+                  :Mat12Iso => 7)
+"iso kernels take one log length-scale, ARD kernels d"
+_isokernel(k::Symbol) = k in (:SEIso, :Mat52Iso, :Mat32Iso, :Mat12Iso)
 abstract type AbstractBOHipModel end
 
 "Device-resident elastic GP on ONE MI355X: drop-in for `ElasticGPE(d; mean, kernel, logNoise, capacity)` (README.md:22-27)."
@@ -147,7 +150,7 @@ mutable struct BOHipGPE <: AbstractBOHipModel
     kernel::Symbol
     meanconst::Bool             # MeanConst(beta) (a parameter) or MeanZero()
     mean::Float64
-    loglen::Vector{Float64}     # d entries (SEIso: 1)
+    loglen::Vector{Float64}     # d entries (iso kernels: 1)
     logsig::Float64
     logNoise::Float64
 end
@@ -169,11 +172,12 @@ end
 function _hyper_args(kernel, d, mean, loglen)
     haskey(KERN, kernel) || throw(ArgumentError("kernel must be one of $(collect(keys(KERN)))"))
     ll = Float64.(collect(loglen))
-    length(ll) == (kernel == :SEIso ? 1 : d) || throw(ArgumentError("loglen has the wrong length for $kernel"))
+    length(ll) == (_isokernel(kernel) ? 1 : d) || throw(ArgumentError("loglen has the wrong length for $kernel"))
     mean === nothing ? (false, 0.0, ll) : (true, Float64(mean), ll)
 end
-"`BOHipGPE(d; mean = nothing (MeanZero) | beta (MeanConst), kernel = :SEArd | :SEIso | :Mat52Ard, loglen, logsig, logNoise, capacity, device)`"
-function BOHipGPE(d::Integer; mean = nothing, kernel::Symbol = :SEArd, loglen = zeros(kernel == :SEIso ? 1 : d),
+"`BOHipGPE(d; mean = nothing (MeanZero) | beta (MeanConst), kernel = :SEArd | :SEIso | :Mat52Ard | :Mat52Iso | :Mat32Ard | :Mat32Iso |
+:Mat12Ard | :Mat12Iso, loglen (d entries; iso kernels: 1), logsig, logNoise, capacity, device)`"
+function BOHipGPE(d::Integer; mean = nothing, kernel::Symbol = :SEArd, loglen = zeros(_isokernel(kernel) ? 1 : d),
                   logsig = 0.0, logNoise = -2.0, capacity = 3000, device = 0)
     mc, beta, ll = _hyper_args(kernel, d, mean, loglen)
     h = Ref{Ptr{Cvoid}}(C_NULL)
@@ -184,7 +188,7 @@ function BOHipGPE(d::Integer; mean = nothing, kernel::Symbol = :SEArd, loglen = 
     m
 end
 function BOHipMultiGPE(d::Integer; devices = collect(0:c_device_count()-1), shards_per_device = 1, mean = nothing,
-                       kernel::Symbol = :SEArd, loglen = zeros(kernel == :SEIso ? 1 : d), logsig = 0.0, logNoise = -2.0,
+                       kernel::Symbol = :SEArd, loglen = zeros(_isokernel(kernel) ? 1 : d), logsig = 0.0, logNoise = -2.0,
                        capacity = 3000)
     mc, beta, ll = _hyper_args(kernel, d, mean, loglen)
     devs = Cint.(collect(devices))
@@ -201,7 +205,7 @@ function BOHipGPE(x::AbstractMatrix, y::AbstractVector; kwargs...)
     update!(m, x, y)
 end
 
-_ll_full(m::AbstractBOHipModel) = m.kernel == :SEIso ? fill(m.loglen[1], m.dim) : m.loglen
+_ll_full(m::AbstractBOHipModel) = _isokernel(m.kernel) ? fill(m.loglen[1], m.dim) : m.loglen
 push_hyper!(m::BOHipGPE) = check(c_gp_set_hyper(m.handle, _ll_full(m), m.logsig, m.logNoise, m.mean))
 push_hyper!(m::BOHipMultiGPE) = check(c_mgp_set_hyper(m.handle, _ll_full(m), m.logsig, m.logNoise, m.mean))
 "the replica whose scalar queries (predict, mll, ...) answer for the whole model"
