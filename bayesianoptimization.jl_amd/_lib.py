@@ -22,6 +22,7 @@ INFO_SCORE_LAUNCHES, INFO_SCORE_CHUNK, INFO_KERNEL_CLOCK_MHZ = 8, 9, 10
 INFO_COMM_NRANKS, INFO_COMM_EXCHANGES, INFO_COMM_RCCL_VERSION, INFO_CHOL_LOCK_SKIPS = 11, 12, 13, 14
 MGP_INFO_DEVICES, MGP_INFO_SHARDS, MGP_INFO_EXCHANGES, MGP_INFO_RCCL_VERSION, MGP_INFO_COMM_NRANKS = 0, 1, 2, 3, 4
 UNIQUE_ID_BYTES = 128
+FANTASY_BELIEVER, FANTASY_CONST, BATCH_RAISE_TAU = 0, 1, 1   # bohip_gp_select_batch
 
 
 class Best(C.Structure):
@@ -65,6 +66,8 @@ SIGNATURES = {
     "bohip_gp_set_jitter": (C.c_int, [_gp, C.c_double, C.c_int]),
     "bohip_gp_predict": (C.c_int, [_gp, _dp, C.c_int64, _dp, _dp]),
     "bohip_gp_score": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, _dp, C.POINTER(Best)]),
+    "bohip_gp_select_batch": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int, _i64p, _dp, _dp,
+                                       _dp]),
     "bohip_gp_score_grad": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, _dp, _dp]),
     "bohip_gp_thompson": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.POINTER(Best)]),
     "bohip_thompson_normal": (C.c_double, [C.c_uint64, C.c_int64, C.c_int64]),

@@ -486,5 +486,58 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     return maxf, maxx
 
 
+_BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau"}
+_BATCH_FANTASIES = ("believer", "liar_max", "liar_min", "liar_mean")
+
+
+def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None, setparams=True):
+    """q points to evaluate in parallel -- an extension: the reference's iteration is one acquire_max and `repetitions`
+    evaluations of ONE point (src/BayesianOptimization.jl:185-196).  Greedy arg-max over a candidate set under the posterior
+    conditioned on the fantasised observations of the earlier picks (model.select_batch; the model itself is not changed).
+    options: "candidates" Latin-hypercube points (default 4096) or an explicit d x R "xs"; "fantasy" in {"believer" (y_f = mu),
+    "liar_max", "liar_min", "liar_mean" (a constant taken from model.y)}; "raise_tau" (EI / PI: the incumbent follows the
+    fantasies).  Returns (values[q'], X d x q') with q' <= q: picks that could not win (no finite score left) are dropped."""
+    lb = np.asarray(lowerbounds, dtype=np.float64)
+    ub = np.asarray(upperbounds, dtype=np.float64)
+    opts = dict(options or {})
+    for k in opts:
+        if k not in _BATCH_OPTS:
+            raise ValueError(f"unknown batch option {k!r} (known: {sorted(_BATCH_OPTS)})")
+    q = int(q)
+    if q < 1:
+        raise ValueError(f"batch size q = {q} < 1")
+    if lb.size != ub.size:
+        raise ValueError("length of lowerbounds does not match length of upperbounds")
+    fantasy = opts.get("fantasy", "believer")
+    if fantasy not in _BATCH_FANTASIES:
+        raise ValueError(f"fantasy must be one of {_BATCH_FANTASIES}, got {fantasy!r}")
+    if isinstance(a, ThompsonSamplingSimple):
+        raise ValueError("acquire_batch needs a deterministic acquisition (ThompsonSamplingSimple draws its own batch: model.thompson)")
+    if not hasattr(model, "select_batch"):
+        raise NotImplementedError(f"{type(model).__name__} has no select_batch")
+    if "xs" in opts and opts["xs"] is not None:
+        xs = np.asarray(opts["xs"], dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[0] != lb.size:
+            raise ValueError(f"options['xs'] must be {lb.size} x R (one point per column), got shape {xs.shape}")
+    else:
+        ncand = int(opts.get("candidates", 4096))
+        if ncand < 1:
+            raise ValueError(f"options['candidates'] = {ncand} < 1")
+        xs = latin_hypercube_sampling(lb, ub, ncand, rng)
+    if q > xs.shape[1]:
+        raise ValueError(f"batch size q = {q} exceeds the {xs.shape[1]} candidates")
+    if model.nobs == 0:
+        raise RuntimeError("acquire_batch on an empty model")
+    if setparams:
+        setparams_(a, model)
+    y = np.asarray(model.y)
+    fv = {"believer": "believer", "liar_max": float(y.max()), "liar_min": float(y.min()), "liar_mean": float(y.mean())}[fantasy]
+    idx, val, _, _ = model.select_batch(a.acq_id, a.params(), xs, q, fantasy=fv, raise_tau=bool(opts.get("raise_tau", False)))
+    keep = idx >= 0
+    if not keep.all():
+        warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a finite score")
+    return val[keep], np.asfortranarray(xs[:, idx[keep]])
+
+
 def acquire_model_max(o, options=None):                           # :45-47
     return acquire_max(MaxMean(), o.model, o.lowerbounds, o.upperbounds, options or o.acquisitionoptions, o.rng)

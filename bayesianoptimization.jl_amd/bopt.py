@@ -9,7 +9,8 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, acquire_max, defaultoptions, setparams_)
+from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, acquire_batch, acquire_max, defaultoptions,
+                          setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ElasticGPE, Mat52Ard, MeanConst, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, step_)
@@ -125,7 +126,9 @@ class BOpt:
 
     def __init__(self, func, model, acquisition, modeloptimizer, lowerbounds, upperbounds, *, sense=Max,
                  maxiterations=10 ** 4, maxduration=math.inf, acquisitionoptions=None, repetitions=1,
-                 verbosity=Progress, initializer_iterations=None, initializer=None, rng=None):
+                 verbosity=Progress, initializer_iterations=None, initializer=None, rng=None, batchsize=1, batchoptions=None):
+        # batchsize > 1 (an extension, the reference evaluates one point per iteration): an iteration proposes `batchsize` points
+        # with acquire_batch(..., batchoptions) and appends all their evaluations in ONE model update
         now = time.time()
         lowerbounds = np.asarray(lowerbounds, dtype=np.float64)
         upperbounds = np.asarray(upperbounds, dtype=np.float64)
@@ -142,6 +145,10 @@ class BOpt:
             raise ValueError("maxduration < 0")
         if len(lowerbounds) != len(upperbounds):
             raise ValueError("length of lowerbounds does not match length of upperbounds")
+        if int(batchsize) != batchsize or batchsize < 1:
+            raise ValueError(f"batchsize = {batchsize!r} is not a positive integer")
+        if batchsize == 1 and batchoptions:
+            raise ValueError("batchoptions given with batchsize = 1")
         if not np.all(lowerbounds <= upperbounds):
             raise ValueError("lowerbounds are not pointwise less than or eqal to upperbounds, they were possibly "
                              "passed in the wrong order")
@@ -157,6 +164,7 @@ class BOpt:
         self.duration = DurationCounter(now, maxduration, now, now + maxduration)
         self.verbosity, self.initializer, self.repetitions = Verbosity(verbosity), initializer, repetitions
         self.rng = rng if rng is not None else np.random.default_rng()
+        self.batchsize, self.batchoptions = int(batchsize), dict(batchoptions or {})
         self.timeroutput = {}
         setparams_(acquisition, model)                                          # nlopt_setup :30 (ctor :134)
 
@@ -211,6 +219,27 @@ def initialise_model_(o):                                                       
         optimizemodel_(o.modeloptimizer, o.model)
 
 
+def _batch_iteration(o):
+    """One iteration with batchsize > 1: ONE acquire_batch, `repetitions` evaluations of each of its points, ONE model update
+    with all columns, one step of the iteration counter."""
+    with _timeit(o, "acquisition"):
+        _, X = acquire_batch(o.acquisition, o.model, o.lowerbounds, o.upperbounds, o.batchsize, o.batchoptions, o.rng,
+                             setparams=False)
+    step_(o.iterations)
+    xs, ys = [], []
+    for j in range(X.shape[1]):
+        x = np.array(X[:, j])
+        for _ in range(o.repetitions):
+            ys.append(_evaluate_function(o, x))
+            xs.append(x)
+    if not xs:                                                                   # (no candidate had a finite score: acquire_batch has warned)
+        return
+    with _timeit(o, "model update"):
+        update_(o.model, np.stack(xs, axis=1), np.array(ys))
+    with _timeit(o, "model hyperparameter optimization"):
+        optimizemodel_(o.modeloptimizer, o.model)
+
+
 def boptimize_(o):
     """boptimize!(o) :176-207.  Re-calling resumes: init! zeroes the per-call counter but keeps the cumulative one."""
     init_(o.duration)
@@ -222,6 +251,9 @@ def boptimize_(o):
         if o.verbosity >= Progress:
             print(f"{time.strftime('%Y-%m-%dT%H:%M:%S')}\titeration: {o.iterations.i}\tcurrent optimum: {o.observed_optimum}")
         setparams_(o.acquisition, o.model)                                       # :184
+        if o.batchsize > 1:
+            _batch_iteration(o)
+            continue
         with _timeit(o, "acquisition"):
             f, x = acquire_max(o.acquisition, o.model, o.lowerbounds, o.upperbounds, o.acquisitionoptions, o.rng,
                                setparams=False)                                  # :185 (4-argument method: no second setparams!)
@@ -248,7 +280,7 @@ def boptimize_(o):
 def merge_with_defaults(f, lowerbounds, upperbounds, optkwargs):                # :238-289
     args_keys = ("model", "acquisition", "modeloptimizer")
     kwargs_keys = ("sense", "maxiterations", "maxduration", "acquisitionoptions", "repetitions", "verbosity",
-                   "initializer_iterations", "initializer")
+                   "initializer_iterations", "initializer", "batchsize", "batchoptions")
     if not set(optkwargs) <= set(args_keys) | set(kwargs_keys):
         raise ValueError("use of unsupported keyword arguments")                 # ArgumentError :250-251
     if len(lowerbounds) != len(upperbounds):

@@ -19,6 +19,7 @@
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
+#include "kernels_batch.hip"   // (after the scoring kernels: shares their functors and arg-max order)
 #include "kernels_ascent.hip"
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
 #include "direct_l.h"          // host bookkeeping of :GN_DIRECT_L (ask / tell)
@@ -122,6 +123,11 @@ struct bohip_gp {
     int* pr_pieces_at = nullptr;
     unsigned* hprune_stat = nullptr;   // pinned: round 2's list length of the last pruned call (prune_wanted)
     int prune_skip = 0;                // value-only calls left on the full pass before pruning is tried again
+    // batch selection (bohip_gp_select_batch): V' of ALL candidates, and ONE block [u_i q x ldu | records | scalars | workgroup records | picked]
+    double* dBV = nullptr;
+    int64_t bv_rows = 0, bv_ld = 0;
+    char* dbatch = nullptr;
+    size_t batch_bytes = 0;
     double* dgrad = nullptr;   // d x R gradient staging of the host-pointer entry point
     double asc_ftol_abs = 0.0, asc_xtol_rel = 0.0, asc_stopval = INFINITY;   // bohip_gp_set_ascent_stop (NLopt's ftol_abs / xtol_rel / stopval)
     double asc_maxtime = 0.0;    // bohip_gp_set_maxtime: wall-clock budget of one acquire_max call in seconds (NLopt maxtime), 0 = none
@@ -281,9 +287,9 @@ static size_t chol_abort_word(int T);
 static int alloc_model(bohip_gp* g, int64_t cap) {
     free_model(g);
     // chunk buffers are sized by ld: drop them, they are re-made on demand
-    for (double** p : {&g->dKsT, &g->dVT, &g->dUT, &g->dq})
+    for (double** p : {&g->dKsT, &g->dVT, &g->dUT, &g->dq, &g->dBV})
         if (*p) { hipFree(*p); *p = nullptr; }
-    g->kst_rows = g->vt_rows = g->q_cap = 0;
+    g->kst_rows = g->vt_rows = g->q_cap = g->bv_rows = 0;
     g->cap = cap;
     // +16 doubles: row stride is an ODD multiple of 128 B, so the 128 rows of a tile spread over the L2/HBM
     // channels instead of camping on one (a power-of-two stride sends every row of a tile to the same channel).
@@ -434,6 +440,8 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<1>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<2>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_rows, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
+    HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)k_chol_chain, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_inv128, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_pair, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
@@ -2713,6 +2721,8 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->dpieces) hipFree(g->dpieces);
     if (g->dclk) hipFree(g->dclk);
     if (g->dgrad) hipFree(g->dgrad);
+    if (g->dBV) hipFree(g->dBV);
+    if (g->dbatch) hipFree(g->dbatch);
     if (g->dgparts) hipFree(g->dgparts);
     if (g->dsplit) hipFree(g->dsplit);
     if (g->dgcount) hipFree(g->dgcount);
@@ -3078,6 +3088,131 @@ int bohip_gp_score(bohip_gp* g, int acq_id, const double* acq_params, const doub
     if (score) HIPCHK(hipMemcpyAsync(score, g->dscore, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (best) HIPCHK(hipMemcpyAsync(best, g->dbest, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+// ---- greedy batch selection (an extension: the reference proposes ONE point per iteration, src/BayesianOptimization.jl:185-196) ----
+// q picks from one contraction: V' of all R candidates is kept (dBV), every further pick is k_batch_cond + k_batch_final
+// (kernels_batch.hip).  All rounds are enqueued without a synchronisation; the model is not touched.
+static constexpr size_t BATCH_VT_CAP_BYTES = (size_t)8 << 30;   // V' of one call (R = 32768 at N = 10^4: 2.7 GB)
+static int ensure_batch(bohip_gp* g, int64_t R, int64_t q) {
+    const int64_t rows = round_up(R, TILE) + TILE;
+    if (g->dBV == nullptr || g->bv_rows < rows || g->bv_ld != g->ld) {
+        if (g->dBV) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dBV)); }
+        g->dBV = nullptr; g->bv_rows = 0;
+        const size_t bytes = (size_t)rows * g->ld * 8;
+        HIPCHK(hipMalloc(&g->dBV, bytes));
+        HIPCHK(hipMemsetAsync(g->dBV, 0, bytes, g->stream));   // padding columns (>= N) stay zero
+        g->bv_rows = rows; g->bv_ld = g->ld;
+    }
+    const size_t need = (size_t)q * rows * 8 + (size_t)q * sizeof(BatchRec) + sizeof(BatchScal) + BATCH_WG_MAX * sizeof(Best) +
+                        (size_t)rows * sizeof(int);
+    if (g->batch_bytes < need) {
+        if (g->dbatch) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dbatch)); }
+        g->dbatch = nullptr; g->batch_bytes = 0;
+        HIPCHK(hipMalloc(&g->dbatch, need));
+        g->batch_bytes = need;
+    }
+    return 0;
+}
+
+int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t q, int fantasy,
+                          double fantasy_value, int flags, int64_t* idx, double* val, double* mu, double* var) {
+    if (!g || !Xs || !idx || !val || R < 1) return fail(BOHIP_E_ARG, "bad arguments");
+    if (acq_id == BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, "select_batch: a posterior draw has no conditioned score");
+    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    if (q < 1 || q > R) return fail(BOHIP_E_ARG, "select_batch: q must lie in 1..R (q = " + std::to_string(q) + ", R = " + std::to_string(R) + ")");
+    if (fantasy != BOHIP_FANTASY_BELIEVER && fantasy != BOHIP_FANTASY_CONST)
+        return fail(BOHIP_E_ARG, "select_batch: unknown fantasy " + std::to_string(fantasy));
+    if (fantasy == BOHIP_FANTASY_CONST && !std::isfinite(fantasy_value)) return fail(BOHIP_E_ARG, "select_batch: fantasy_value is not finite");
+    if (flags & ~BOHIP_BATCH_RAISE_TAU) return fail(BOHIP_E_ARG, "select_batch: unknown flags");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    if (q == 1) {   // one pick is the plain arg-max: bohip_gp_score's record (and its pruned pass)
+        bohip_best b{-INFINITY, -1};
+        CHK(bohip_gp_score(g, acq_id, acq_params, Xs, R, nullptr, &b));
+        idx[0] = b.idx; val[0] = b.val;
+        double m = NAN, v = NAN;
+        if ((mu || var) && b.idx >= 0) CHK(bohip_gp_predict(g, Xs + b.idx * g->d, 1, &m, &v));
+        if (mu) mu[0] = m;
+        if (var) var[0] = v;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    const int64_t rows = round_up(R, TILE) + TILE;
+    if ((size_t)rows * (g->ld + q) * 8 > BATCH_VT_CAP_BYTES)   // V' [rows][ld] and the q rows of u_i
+        return fail(BOHIP_E_UNSUPPORTED, "select_batch: V' of " + std::to_string(R) + " candidates needs " +
+                                             std::to_string((size_t)rows * (g->ld + q) * 8) + " bytes, above the cap of " +
+                                             std::to_string(BATCH_VT_CAP_BYTES) + " (at this model size R <= " +
+                                             std::to_string((int64_t)(BATCH_VT_CAP_BYTES / ((size_t)(g->ld + q) * 8)) - 2 * TILE) + ")");
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    CHK(one_time_kernel_setup());
+    CHK(ensure_batch(g, R, q));
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    AcqParams ap{acq_id, 0.0, 0.0};
+    if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
+    if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
+    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
+    const int T = (int)(Npad / TILE);
+    const KernelHyper hp = make_hyper(g);
+    double* U = reinterpret_cast<double*>(g->dbatch);
+    BatchRec* rec = reinterpret_cast<BatchRec*>(U + q * rows);
+    BatchScal* scal = reinterpret_cast<BatchScal*>(rec + q);
+    Best* wg_best = reinterpret_cast<Best*>(scal + 1);
+    int* picked = reinterpret_cast<int*>(wg_best + BATCH_WG_MAX);
+    HIPCHK(hipMemsetAsync(picked, 0, (size_t)rows * sizeof(int), g->stream));
+    // round 0: the batched pass (K*' chunk -> k_trigemm_sq with V' stored), whatever R is: the other paths do not leave V' in this layout
+    g->q_tiles = T;
+    g->score_launches = 0;
+    const int64_t rc = g->chunk_now;
+    for (int64_t r0 = 0; r0 < R; r0 += rc) {
+        const int64_t r1 = std::min(R, r0 + rc);
+        ++g->score_launches;
+        t_begin(g, "kstar");
+        CHK(launch_kstar_any(g, g->dXs, r0, r1, Npad, hp));
+        t_end(g);
+        t_begin(g, "trigemm_sq+V");
+        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, g->dBV + r0 * ld));
+        t_end(g);
+    }
+    t_begin(g, "batch_rounds");
+    const int nb = (int)((R + 255) / 256);
+    hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, T, g->dmu_raw, R, hp.sigma2, g->beta, ap, g->dmu, g->dvar,
+                       (double*)nullptr, g->dblock_best);
+    BatchFinal bf{};
+    bf.mu = g->dmu; bf.var = g->dvar; bf.picked = picked; bf.rec = rec; bf.scal = scal; bf.fantasy = fantasy;
+    bf.fantasy_value = fantasy_value; bf.tau0 = ap.p0;
+    bf.noise = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
+    bf.raise_tau = (flags & BOHIP_BATCH_RAISE_TAU) && (acq_id == BOHIP_ACQ_EI || acq_id == BOHIP_ACQ_PI);
+    bf.in = g->dblock_best; bf.n = nb; bf.t = 0;
+    hipLaunchKernelGGL(k_batch_final, dim3(1), dim3(256), 0, g->stream, bf);
+    BatchCond bc{};
+    bc.VT = g->dBV; bc.ldv = ld; bc.N = N; bc.Xs = g->dXs; bc.R = R; bc.mu = g->dmu; bc.var = g->dvar; bc.U = U; bc.ldu = rows;
+    bc.picked = picked; bc.rec = rec; bc.scal = scal; bc.ap = ap; bc.block_best = wg_best;
+    const size_t lds = (size_t)(N / 2) * 16;
+    bc.use_lds = lds <= (size_t)BATCH_LDS_MAX;
+    const int nwg = (int)std::min<int64_t>((R + BATCH_WAVES - 1) / BATCH_WAVES, BATCH_WG_MAX);
+    bf.in = wg_best; bf.n = nwg;
+    for (int64_t t = 0; t + 1 < q; ++t) {
+        bc.t = (int)t;
+        LAUNCH_FAM(fam_low(hp), k_batch_cond<true>, k_batch_cond<false>, dim3(nwg), dim3(64 * BATCH_WAVES), bc.use_lds ? lds : 0, g->stream, bc, hp);
+        bf.t = (int)t + 1;
+        hipLaunchKernelGGL(k_batch_final, dim3(1), dim3(256), 0, g->stream, bf);
+    }
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    std::vector<BatchRec> h((size_t)q);
+    HIPCHK(hipMemcpyAsync(h.data(), rec, (size_t)q * sizeof(BatchRec), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    for (int64_t t = 0; t < q; ++t) {
+        idx[t] = h[t].idx; val[t] = h[t].val;
+        if (mu) mu[t] = h[t].mu;
+        if (var) var[t] = h[t].var;
+    }
     t_collect(g);
     return 0;
 }

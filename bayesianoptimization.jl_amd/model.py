@@ -235,6 +235,31 @@ class ElasticGPE:
                                        _ptr(sc) if want_scores else None, C.byref(best)))
         return sc, best.val, best.idx
 
+    def select_batch(self, acq, params, xs, q, fantasy="believer", raise_tau=False):
+        """q candidates to evaluate in parallel (bohip_gp_select_batch; an extension, the reference proposes one point per
+        iteration): greedy arg-max under the posterior conditioned on the fantasised observations of the earlier picks.
+        fantasy: "believer" (y_f = mu(x_s)) or a number (constant liar).  raise_tau: EI / PI incumbent follows the fantasies.
+        The model is not changed.  Returns (idx[q] int64, val[q], mu[q], var[q]); idx = -1, val = -Inf where nothing could win."""
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        q = int(q)
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+        if p.size < 2:
+            p = np.concatenate([p, np.zeros(2 - p.size)])
+        if isinstance(fantasy, str):
+            if fantasy != "believer":
+                raise ValueError(f"fantasy must be 'believer' or a number, got {fantasy!r}")
+            mode, fv = _lib.FANTASY_BELIEVER, 0.0
+        else:
+            mode, fv = _lib.FANTASY_CONST, float(fantasy)
+        n = max(q, 1)
+        idx = np.full(n, -1, dtype=np.int64)
+        val, mu, var = np.empty(n), np.empty(n), np.empty(n)
+        check(self._lib.bohip_gp_select_batch(self._h, _lib.ACQ[acq], _ptr(p), _ptr(xs), R, q, mode, fv,
+                                              _lib.BATCH_RAISE_TAU if raise_tau else 0,
+                                              idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(val), _ptr(mu), _ptr(var)))
+        return idx, val, mu, var
+
     def score_grad(self, acq, params, xs):
         xs = _cols(xs, self.dim)
         R = xs.shape[1]

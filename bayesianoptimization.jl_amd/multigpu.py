@@ -102,6 +102,11 @@ class MultiGPE:
                                         C.byref(best)))
         return sc, best.val, best.idx
 
+    def select_batch(self, acq, params, xs, q, fantasy="believer", raise_tau=False):
+        """Not implemented for a device list: every shard of V' would need the picked candidate's row v_s broadcast per round
+        (DESIGN.md 10).  Use ElasticGPE.select_batch on one device."""
+        raise NotImplementedError("MultiGPE.select_batch: batch selection runs on one device (ElasticGPE.select_batch)")
+
     def set_candidates(self, xs):
         xs = _cols(xs, self.dim)
         check(self._lib.bohip_mgp_set_candidates(self._h, _ptr(xs), xs.shape[1]))

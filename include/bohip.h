@@ -120,6 +120,27 @@ int bohip_gp_predict_cov(bohip_gp *gp, const double *Xs, int64_t R, double *mu, 
 int bohip_gp_score(bohip_gp *gp, int acq_id, const double *acq_params, const double *Xs, int64_t R,
                    double *score /* R, nullable */, bohip_best *best);
 
+/* ---- greedy batch selection: q candidates to evaluate in parallel.  AN EXTENSION: the reference has no batch -- an iteration
+ * is one acquire_max followed by `repetitions` evaluations of ONE point (src/BayesianOptimization.jl:185-196).
+ * Round j scores the candidates not yet picked under the posterior conditioned on the fantasised observations (x_s, y_f) of the
+ * earlier picks and takes the arg-max (value desc, index asc; NaN / -Inf never win) -- exactly "append (x_s, y_f), score again",
+ * hyper-parameters fixed (Kriging believer / constant liar), computed as rank-one updates over the candidate set from ONE
+ * contraction V = W K*.  The model (n, L, W, alpha) is NOT changed by the call.
+ *   fantasy   BOHIP_FANTASY_BELIEVER  y_f = mu(x_s): the mean stays, the variance shrinks
+ *             BOHIP_FANTASY_CONST     y_f = fantasy_value (constant liar: max / min / mean of y)
+ *   flags     BOHIP_BATCH_RAISE_TAU   EI / PI: tau <- max(tau, y_f) after every pick (what setparams! would do after a real
+ *                                     append); every other acquisition parameter stays as passed
+ * idx, val (q): the picks in order; mu, var (q, nullable): the conditioned posterior at each pick before its own fantasy.
+ * When fewer than q candidates can win, the rest are idx = -1, val = -Inf (mu = var = NaN).  q = 1 is bohip_gp_score's record
+ * bit for bit.  BOHIP_E_ARG: q < 1, q > R, unknown fantasy / flags, a non-finite fantasy_value, BOHIP_ACQ_THOMPSON_DRAW; BOHIP_E_STATE: no observations;
+ * BOHIP_E_UNSUPPORTED: V' of the candidates ([round_up(R,128)+128][ld] doubles) and the q update vectors exceed 8 GiB.        */
+#define BOHIP_FANTASY_BELIEVER 0
+#define BOHIP_FANTASY_CONST 1
+#define BOHIP_BATCH_RAISE_TAU 1
+int bohip_gp_select_batch(bohip_gp *gp, int acq_id, const double *acq_params, const double *Xs, int64_t R, int64_t q,
+                          int fantasy, double fantasy_value, int flags, int64_t *idx /* q */, double *val /* q */,
+                          double *mu /* q, nullable */, double *var /* q, nullable */);
+
 /* ---- wrap_gradient role (reference src/acquisition.jl:11-17): score and d(score)/dx, the
  * latter d x R column-major.  Every kernel id.                                              */
 int bohip_gp_score_grad(bohip_gp *gp, int acq_id, const double *acq_params, const double *Xs, int64_t R,

@@ -67,6 +67,7 @@ c_gp_mll_grad(h, mll, dn, dm, dk) = ccall((:bohip_gp_mll_grad, libbohip), Cint, 
 c_gp_predict(h, Xs, R, mu, var) = ccall((:bohip_gp_predict, libbohip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}), h, Xs, R, mu, var)
 c_gp_predict_cov(h, Xs, R, mu, cov) = ccall((:bohip_gp_predict_cov, libbohip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}), h, Xs, R, mu, cov)
 c_gp_score(h, acq, p, Xs, R, sc, best) = ccall((:bohip_gp_score, libbohip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Best}), h, acq, p, Xs, R, sc, best)
+c_gp_select_batch(h, acq, p, Xs, R, q, fantasy, fv, flags, idx, val, mu, var) = ccall((:bohip_gp_select_batch, libbohip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Cint, Float64, Cint, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h, acq, p, Xs, R, q, fantasy, fv, flags, idx, val, mu, var)
 c_gp_score_grad(h, acq, p, Xs, R, sc, g) = ccall((:bohip_gp_score_grad, libbohip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}), h, acq, p, Xs, R, sc, g)
 c_gp_acquire_max(h, acq, p, lb, ub, st, R, maxeval, ftol, xtol, xo, fo, best, bx, ev) = ccall((:bohip_gp_acquire_max, libbohip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Best}, Ptr{Float64}, Ptr{Int64}), h, acq, p, lb, ub, st, R, maxeval, ftol, xtol, xo, fo, best, bx, ev)
 c_direct_create(d, lb, ub, maxeval, stopval, maxtime, out) = ccall((:bohip_direct_create, libbohip), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Float64, Ptr{Ptr{Cvoid}}), d, lb, ub, maxeval, stopval, maxtime, out)
@@ -305,6 +306,23 @@ function score(m::AbstractBOHipModel, a::AbstractAcquisition, X::AbstractMatrix;
                                c_gp_score(m.handle, acqid(a), p, Xc, R, scores ? sc : C_NULL, best)
     check(rc)
     sc, best[].val, Int(best[].idx) + 1
+end
+"""
+    acquire_batch(m, a, X, q; fantasy = :believer, raise_tau = false) -> (values, 1-based columns, mu, var)
+
+q columns of X to evaluate in parallel (bohip_gp_select_batch) -- an extension: the reference's iteration is one acquire_max and
+`repetitions` evaluations of ONE point (src/BayesianOptimization.jl:185-196).  Greedy arg-max under the posterior conditioned on
+the fantasised observations of the earlier picks; `fantasy` is `:believer` (y_f = mu) or a number (constant liar).  The model is
+not changed.  A column of 0 (value -Inf) means no candidate was left that could win.
+"""
+function acquire_batch(m::BOHipGPE, a::AbstractAcquisition, X::AbstractMatrix, q::Integer; fantasy = :believer, raise_tau::Bool = false)
+    Xc = _cols(m, X); R = size(Xc, 2)
+    fantasy === :believer || fantasy isa Real || throw(ArgumentError("fantasy must be :believer or a number"))
+    idx = Vector{Int64}(undef, max(q, 1)); val = Vector{Float64}(undef, max(q, 1))
+    mu = similar(val); var = similar(val)
+    check(c_gp_select_batch(m.handle, acqid(a), acqparams(a), Xc, R, q, fantasy === :believer ? Cint(0) : Cint(1),
+                            fantasy === :believer ? 0.0 : Float64(fantasy), raise_tau ? Cint(1) : Cint(0), idx, val, mu, var))
+    val, idx .+ 1, mu, var
 end
 "value and gradient (d x R) of the acquisition at the columns of X: the role of wrap_gradient (src/acquisition.jl:11-17)"
 function score_grad(m::AbstractBOHipModel, a::AbstractAcquisition, X::AbstractMatrix)
