@@ -11,7 +11,7 @@ from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
-                          acquire_max, acquire_batch, acquire_model_max, defaultoptions)
+                          acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, NoModelOptimizer, optimizemodel_,
                    Min, Max, Silent, Timings, Progress, isdone)
 from .utils import (ScaledSobolIterator, ScaledLHSIterator, latin_hypercube_sampling, maxduration_, maxiterations_,
@@ -22,6 +22,6 @@ GPE = ElasticGPE.from_data
 __all__ = ["BOpt", "ExpectedImprovement", "ProbabilityOfImprovement", "UpperConfidenceBound", "ThompsonSamplingSimple",
            "MutualInformation", "boptimize_", "MAPGPOptimizer", "NoModelOptimizer", "Min", "Max", "BrochuBetaScaling",
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
-           "maxduration_", "maxiterations_", "optimize", "acquire_batch",
+           "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
            "Mat32Iso", "Mat12Ard", "Mat12Iso"]

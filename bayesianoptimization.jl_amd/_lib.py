@@ -71,6 +71,8 @@ SIGNATURES = {
     "bohip_gp_score_grad": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, _dp, _dp]),
     "bohip_gp_thompson": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.POINTER(Best)]),
     "bohip_thompson_normal": (C.c_double, [C.c_uint64, C.c_int64, C.c_int64]),
+    "bohip_gp_sample_joint": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_int, _dp, _dp, _dp,
+                                       C.POINTER(Best), _dp, _ip]),
     "bohip_direct_create": (C.c_int, [C.c_int64, _dp, _dp, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "bohip_direct_destroy": (None, [C.c_void_p]),
     "bohip_direct_ask": (C.c_int, [C.c_void_p, _dp, C.c_int64, _i64p]),

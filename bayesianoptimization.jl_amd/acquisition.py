@@ -372,7 +372,9 @@ def _warn_not_a_local_search(method):
                   "scored in one device batch instead (use :LD_LBFGS or :GN_DIRECT_L for a search)", stacklevel=3)
 
 
-_OPTS_USED = {"method", "restarts", "maxeval", "maxtime", "ftol_rel", "xtol_abs", "ftol_abs", "xtol_rel", "stopval"}
+# "joint" is this package's own option (not an NLopt property): ThompsonSamplingSimple over a candidate set takes ONE JOINT draw
+# of the posterior (model.sample_joint) instead of independent per-candidate draws (model.thompson).  Default False.
+_OPTS_USED = {"method", "restarts", "maxeval", "maxtime", "ftol_rel", "xtol_abs", "ftol_abs", "xtol_rel", "stopval", "joint"}
 _OPTS_NLOPT_ONLY = {"initial_step", "population", "vector_storage", "seed", "local_optimizer", "default_initial_step"}
 
 
@@ -438,12 +440,19 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return maxf, maxx
     if isinstance(a, ThompsonSamplingSimple):
         _warn_not_a_local_search(method)
-        # one joint draw of the posterior at `maxeval` candidates per restart, arg-max on the device
+        # `maxeval` candidates per restart, arg-max on the device.  Default: model.thompson, every candidate drawn INDEPENDENTLY
+        # from its own marginal (mu_j + sigma_j z_j).  "joint": True: model.sample_joint, ONE JOINT draw of the posterior over the
+        # candidates (mu + chol(Sigma) z, the reference's myrand(model, X::Matrix)), whose arg-max is a draw of the maximiser.
         n = max(maxeval, 1)
+        joint = bool(opts.get("joint", False))
         for _ in range(restarts):
             starts = latin_hypercube_sampling(lb, ub, n, rng)
             seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
-            bv, bi = model.thompson(starts, 1, seed=seed)
+            if joint:
+                js = model.sample_joint(starts, 1, seed, want_samples=False)
+                bv, bi = js.best_val, js.best_idx
+            else:
+                bv, bi = model.thompson(starts, 1, seed=seed)
             if bi[0] >= 0 and bv[0] > maxf:
                 maxf, maxx = float(bv[0]), starts[:, int(bi[0])].copy()
         return maxf, maxx
@@ -537,6 +546,65 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
     if not keep.all():
         warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a finite score")
     return val[keep], np.asfortranarray(xs[:, idx[keep]])
+
+
+def _distinct_picks(samples):
+    """Greedy distinct arg-max over the rows of an S x R sample matrix: draw s takes its best candidate not already taken by draws
+    0..s-1 (strict '>' from -Inf, ties -> smallest index, NaN never wins).  -1 where no candidate is left that could win."""
+    F = np.asarray(samples, dtype=np.float64)
+    taken = np.zeros(F.shape[1], dtype=bool)
+    out = np.full(F.shape[0], -1, dtype=np.int64)
+    for s in range(F.shape[0]):
+        f = np.where(taken | np.isnan(F[s]), -math.inf, F[s])
+        j = int(np.argmax(f)) if f.size else -1               # (argmax: the first maximum)
+        if j >= 0 and f[j] > -math.inf:
+            out[s] = j
+            taken[j] = True
+    return out
+
+
+_THOMPSON_BATCH_OPTS = {"candidates", "xs"}
+
+
+def acquire_thompson_batch(model, lowerbounds, upperbounds, q, options=None, rng=None):
+    """q points to evaluate in parallel by Thompson sampling -- an extension, as acquire_batch is.  ONE model.sample_joint call
+    with S = q joint posterior draws over a candidate set ("candidates" Latin-hypercube points, default 4096, or an explicit
+    d x R "xs"); draw s takes its best candidate not already taken by draws 0..s-1 (_distinct_picks).  The draws' seed comes from
+    `rng`.  Returns (values[q'], X d x q'), q' <= q (a draw with no finite value left is dropped)."""
+    lb = np.asarray(lowerbounds, dtype=np.float64)
+    ub = np.asarray(upperbounds, dtype=np.float64)
+    opts = dict(options or {})
+    for k in opts:
+        if k not in _THOMPSON_BATCH_OPTS:
+            raise ValueError(f"unknown Thompson batch option {k!r} (known: {sorted(_THOMPSON_BATCH_OPTS)})")
+    q = int(q)
+    if q < 1:
+        raise ValueError(f"batch size q = {q} < 1")
+    if lb.size != ub.size:
+        raise ValueError("length of lowerbounds does not match length of upperbounds")
+    if not hasattr(model, "sample_joint"):
+        raise NotImplementedError(f"{type(model).__name__} has no sample_joint")
+    if "xs" in opts and opts["xs"] is not None:
+        xs = np.asarray(opts["xs"], dtype=np.float64)
+        if xs.ndim != 2 or xs.shape[0] != lb.size:
+            raise ValueError(f"options['xs'] must be {lb.size} x R (one point per column), got shape {xs.shape}")
+    else:
+        ncand = int(opts.get("candidates", 4096))
+        if ncand < 1:
+            raise ValueError(f"options['candidates'] = {ncand} < 1")
+        xs = latin_hypercube_sampling(lb, ub, ncand, rng)
+    if q > xs.shape[1]:
+        raise ValueError(f"batch size q = {q} exceeds the {xs.shape[1]} candidates")
+    if model.nobs == 0:
+        raise RuntimeError("acquire_thompson_batch on an empty model")
+    seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
+    F = model.sample_joint(xs, q, seed).samples
+    idx = _distinct_picks(F)
+    keep = idx >= 0
+    if not keep.all():
+        warnings.warn(f"acquire_thompson_batch: only {int(keep.sum())} of {q} draws had a finite value left")
+    rows = np.flatnonzero(keep)
+    return F[rows, idx[rows]], np.asfortranarray(xs[:, idx[rows]])
 
 
 def acquire_model_max(o, options=None):                           # :45-47

@@ -9,8 +9,8 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, acquire_batch, acquire_max, defaultoptions,
-                          setparams_)
+from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, ThompsonSamplingSimple, acquire_batch, acquire_max,
+                          acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ElasticGPE, Mat52Ard, MeanConst, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, step_)
@@ -220,11 +220,14 @@ def initialise_model_(o):                                                       
 
 
 def _batch_iteration(o):
-    """One iteration with batchsize > 1: ONE acquire_batch, `repetitions` evaluations of each of its points, ONE model update
+    """One iteration with batchsize > 1: ONE acquire_batch (ThompsonSamplingSimple: ONE acquire_thompson_batch), `repetitions` evaluations of each of its points, ONE model update
     with all columns, one step of the iteration counter."""
     with _timeit(o, "acquisition"):
-        _, X = acquire_batch(o.acquisition, o.model, o.lowerbounds, o.upperbounds, o.batchsize, o.batchoptions, o.rng,
-                             setparams=False)
+        if isinstance(o.acquisition, ThompsonSamplingSimple):                    # `batchsize` joint posterior draws, distinct winners
+            _, X = acquire_thompson_batch(o.model, o.lowerbounds, o.upperbounds, o.batchsize, o.batchoptions, o.rng)
+        else:
+            _, X = acquire_batch(o.acquisition, o.model, o.lowerbounds, o.upperbounds, o.batchsize, o.batchoptions, o.rng,
+                                 setparams=False)
     step_(o.iterations)
     xs, ys = [], []
     for j in range(X.shape[1]):

@@ -20,6 +20,7 @@
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
 #include "kernels_batch.hip"   // (after the scoring kernels: shares their functors and arg-max order)
+#include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
 #include "kernels_ascent.hip"
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
 #include "direct_l.h"          // host bookkeeping of :GN_DIRECT_L (ask / tell)
@@ -164,6 +165,13 @@ struct bohip_gp {
     double* ddmll_parts = nullptr;  // per-block partial sums of the marginal-likelihood gradient
     double *dVV = nullptr, *dcov = nullptr;  // [Rp][Rp] V'V (lower tiles) and the full posterior covariance
     int64_t cov_cap = 0;
+    // joint sampler (bohip_gp_sample_joint): a factor workspace the model does not own -- matrix, panel scratch, the 128 x 128
+    // diagonal inverses -- plus [max diag | pivot word], the S x R draws (only when asked for) and the per-tile arg-max records
+    double *sjL = nullptr, *sjS = nullptr, *sjW = nullptr, *sjWT = nullptr, *sjF = nullptr, *sj_scal = nullptr;
+    int* sj_info = nullptr;
+    Best* sj_part = nullptr;
+    int64_t sj_cap = 0;           // rows (a multiple of 128) the workspace holds; its leading dimension is sj_cap + 16
+    size_t sjF_cap = 0, sj_part_cap = 0;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -328,6 +336,8 @@ static int g_inv_overlap = 0;  // BOHIP_INV_OVERLAP=1: grow W = L^-1 block by bl
                                // Measured: refit 3.67 -> 3.56 ms (N=3000), 21.4 -> 19.9 ms (N=10000), but the factorisation itself slows
                                // down under the competition (2.90 -> 3.08 ms, 13.9 -> 17.7 ms), so it stays opt-in.
 static int g_bulk_pieces = 4;   // gated pieces of the side-stream bulk update per outer block (BOHIP_BULK_PIECES; 0/1: one launch)
+static int g_sample_mfma_min = 200;  // BOHIP_SAMPLE_MFMA_MIN: draws from which bohip_gp_sample_joint takes k_sample_mfma instead of k_sample_rows
+                                     // (measured at R = 4096: the two cross between 192 and 256 draws, kernels_sample.hip)
 static int g_split = 1;   // split-K path for batches of a few hundred candidates (BOHIP_SPLIT=0 disables)
 static int g_asc_wg_nmax = 256;  // BOHIP_ASC_WG_NMAX: models up to this many observations run acquire_max as ONE launch, one workgroup per start point
                                  // (kernels_ascent.hip k_ascent_wg); 0: never
@@ -463,6 +473,7 @@ static int one_time_kernel_setup() {
     if (const char* e = getenv("BOHIP_ASC_WG_NMAX")) g_asc_wg_nmax = std::max(0, atoi(e));
     if (const char* e = getenv("BOHIP_ASC_LOCKSTEP")) { g_asc_lockstep = atoi(e) == 1; g_asc_fold = atoi(e) != 2; }
     if (const char* e = getenv("BOHIP_SMALL_MFMA")) g_small_mfma = atoi(e);
+    if (const char* e = getenv("BOHIP_SAMPLE_MFMA_MIN")) g_sample_mfma_min = std::max(1, atoi(e));
     g_chol_df_strict = getenv("BOHIP_CHOL_DF_STRICT") != nullptr;
     read_dev_knobs();
     done = true;
@@ -1481,6 +1492,128 @@ static int device_cus() {
     if (c == 0 && hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) c = 0;
     return c;
 }
+// The launch-chained factorisation as a stage of its own: the matrix, its scratch and the 128 x 128 diagonal inverses are a workspace,
+// so that the same code factorises the model's cK (refit_once) and a matrix the model does not own (the joint sampler's Sigma).
+// Streams and events are the handle's.  grow_inverse: W = L^-1 is grown beside the factorisation (the model's dW / dWT only).
+struct FactorWs {
+    double *L, *S, *W, *WT;     // ld x ld matrix (lower tiles) and panel scratch; diagonal inverses W_kk at W + k wstep, W_kk' at WT + k wstep
+    int64_t ld, ldw, wstep;
+    int* info;
+};
+static FactorWs model_factor_ws(bohip_gp* g) {
+    return FactorWs{g->dL, g->dS, g->dW, g->dWT, g->ld, g->ld, (int64_t)TILE * (g->ld + 1), g->dinfo};
+}
+static int factor_launch_chain(bohip_gp* g, const FactorWs& ws, int T, bool grow_inverse) {
+    const int64_t ld = ws.ld;
+    // Right-looking on 128-column panels, with the trailing update applied in two tiers: inside an outer block
+    // of OB panels only the block's own remaining columns are updated after every panel (K = 128); everything to
+    // the right of the outer block is updated ONCE per outer block with K = 128 * OB.  The C tiles of the bulk
+    // are therefore read-modified-written T/OB times instead of T times and the bulk contraction is OB x deeper.
+    const int OB = 4;
+    bool side_pending = false;
+    // The bulk update of the columns right of the NEXT block runs on the side stream.  Run as one launch it shares the chip
+    // with the next block's whole diagonal chain and slows the chain's small GEMMs 3-6x (N = 10^4: 90-120 us instead of
+    // 15-25 us each).  So it is cut into pieces of equal area, and piece j is released by an event recorded just before the
+    // j-th diagonal-block kernel of the next block starts: the pieces fill the ~70 us during which that single-workgroup
+    // kernel leaves the chip idle and are (mostly) gone when the chain's GEMMs arrive.
+    struct Pending { int ob = 0, oe = 0, c0 = 0, rest = 0, next = 0, pieces = 0; int cut[9] = {0}; } pend;
+    auto bulk_params = [&](int pob, int poe, int r0t, int c0t, int mt, int nct) {
+        GemmNTParams b{};  // A[i, j] -= L[i, pob:poe] L[j, pob:poe]'  on rows >= r0t, columns [c0t, c0t + nct)
+        b.A = ws.S + (int64_t)r0t * TILE * ld + (int64_t)pob * TILE; b.lda = ld;
+        b.B = ws.S + (int64_t)c0t * TILE * ld + (int64_t)pob * TILE; b.ldb = ld;
+        b.C = ws.L + (int64_t)r0t * TILE * ld + (int64_t)c0t * TILE; b.ldc = ld;
+        b.mt = mt; b.nt64 = 2 * nct; b.kc = (poe - pob) * (TILE / KC); b.alpha = -1.0; b.beta = 1.0;
+        b.diag_skip = 1; b.row0 = (int64_t)r0t * TILE; b.col0 = (int64_t)c0t * TILE;
+        return b;
+    };
+    auto release_piece = [&](bool gated) -> int {   // next piece of the pending bulk update -> side stream
+        if (pend.next >= pend.pieces) return 0;
+        if (gated) {
+            HIPCHK(hipEventRecord(g->ev_gate, g->stream));
+            HIPCHK(hipStreamWaitEvent(g->side_stream, g->ev_gate, 0));
+        }
+        const int a = pend.cut[pend.next], b = pend.cut[pend.next + 1];
+        ++pend.next;
+        if (b > a)   // columns [c0 + a, c0 + b) of the pending region, rows from the first of them down
+            CHK(launch_gemm_nt(g, bulk_params(pend.ob, pend.oe, pend.c0 + a, pend.c0 + a, pend.rest - a, b - a), 1, g->side_stream));
+        if (pend.next == pend.pieces) HIPCHK(hipEventRecord(g->ev_bulk, g->side_stream));
+        return 0;
+    };
+    for (int ob = 0; ob < T; ob += OB) {
+        const int oe = std::min(T, ob + OB);
+        for (int kb = ob; kb < oe; ++kb) {
+            double* Lkk = ws.L + (int64_t)kb * TILE * (ld + 1);
+            double* Wkk = ws.W + (int64_t)kb * ws.wstep;
+            CHK(release_piece(true));
+            hipLaunchKernelGGL(k_potf2_inv, dim3(1), dim3(PF_THREADS), POTF2_LDS_BYTES, g->stream, Lkk, ld, Wkk,
+                               ws.WT + (int64_t)kb * ws.wstep, ws.ldw, ws.info, kb * TILE);
+            HIPCHK(hipGetLastError());
+            const int rem = T - kb - 1;
+            if (rem == 0) break;
+            const int64_t poff = (int64_t)(kb + 1) * TILE * ld + (int64_t)kb * TILE;
+            double* panel = ws.S + poff;  // solved panel L[kb+1:, kb] lives in the scratch matrix until the final copy
+            GemmNTParams p{};  // panel solve L[i,kb] = A[i,kb] * inv(L_kk)'   (out of place: dL -> dS)
+            p.A = ws.L + poff; p.lda = ld; p.B = Wkk; p.ldb = ws.ldw; p.C = panel; p.ldc = ld;
+            p.mt = rem; p.nt64 = 2; p.kc = TILE / KC; p.alpha = 1.0; p.beta = 0.0;
+            CHK(launch_gemm_nt(g, p));
+            const int inner_cols = oe - kb - 1;  // remaining panels of this outer block
+            if (inner_cols > 0) {
+                GemmNTParams u{};  // A[i, j] -= L[i,kb] L[j,kb]'  for j in (kb, oe), i >= j
+                u.A = panel; u.lda = ld; u.B = panel; u.ldb = ld;
+                u.C = ws.L + (int64_t)(kb + 1) * TILE * (ld + 1); u.ldc = ld;
+                u.mt = rem; u.nt64 = 2 * inner_cols; u.kc = TILE / KC; u.alpha = -1.0; u.beta = 1.0;
+                u.diag_skip = 1; u.row0 = (int64_t)(kb + 1) * TILE; u.col0 = (int64_t)(kb + 1) * TILE;
+                CHK(launch_gemm_nt(g, u));
+            }
+        }
+        while (pend.next < pend.pieces) CHK(release_piece(false));   // a short last block: whatever is left goes now
+        if (grow_inverse && g_inv_overlap) {
+            // The block's panels are final: invert its diagonal region and join it to the leading inverse on the inverse
+            // stream, beside the next blocks' diagonal chain (which leaves most CUs idle).  Reads dS panels of columns
+            // < oe (final), W/W' of tiles < oe; writes W/W' rows/columns of THIS block and the upper-right part of dS.
+            HIPCHK(hipEventRecord(g->ev_blk, g->stream));
+            HIPCHK(hipStreamWaitEvent(g->inv_stream, g->ev_blk, 0));
+            for (int h = 1; h < oe - ob; h *= 2) CHK(inverse_level(g, g->inv_stream, ob, oe - ob, h));
+            CHK(inverse_join(g, g->inv_stream, ob, oe - ob));
+        }
+        const int rem = T - oe;
+        if (rem > 0) {
+            // Bulk update with the OB solved panels: the columns of the NEXT outer block on the critical stream, everything
+            // to their right in gated pieces on the side stream.  Hazards: (1) the side stream needs the panels -> ev_panels;
+            // (2) the next block's columns were last written by the previous block's pieces -> ev_bulk (after the last one).
+            const int nxt = std::min(OB, rem), rest = rem - nxt;
+            if (rest > 0) {
+                HIPCHK(hipEventRecord(g->ev_panels, g->stream));
+                HIPCHK(hipStreamWaitEvent(g->side_stream, g->ev_panels, 0));
+            }
+            if (side_pending) HIPCHK(hipStreamWaitEvent(g->stream, g->ev_bulk, 0));
+            CHK(launch_gemm_nt(g, bulk_params(ob, oe, oe, oe, rem, nxt)));
+            if (rest > 0) {
+                pend = Pending{};
+                pend.ob = ob; pend.oe = oe; pend.c0 = oe + nxt; pend.rest = rest; pend.next = 0;
+                pend.pieces = g_bulk_pieces > 0 ? std::min({g_bulk_pieces, nxt, rest}) : 1;
+                // equal-area cuts of the lower-triangular region: the area left of column c is c rest - c (c - 1) / 2
+                const double total = 0.5 * rest * (rest + 1.0);
+                for (int q = 0, c = 0; q <= pend.pieces; ++q) {
+                    const double want = total * q / pend.pieces;
+                    while (c < rest && c * (double)rest - 0.5 * c * (c - 1.0) < want - 1e-9) ++c;
+                    pend.cut[q] = q == pend.pieces ? rest : c;
+                }
+                if (pend.pieces == 1) CHK(release_piece(false));   // ungated single launch (small problems, BOHIP_BULK_PIECES=0)
+                side_pending = true;
+            } else {
+                side_pending = false;
+            }
+        }
+    }
+    if (side_pending) HIPCHK(hipStreamWaitEvent(g->stream, g->ev_bulk, 0));
+    if (T > 1) {
+        hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, ws.S, ws.L, ld, T);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
 static int refit_once(bohip_gp* g, double jitter);
 // Full rebuild.  A factorisation that fails (BOHIP_E_NOTPD) is reported as such unless jitter escalation was asked for
 // (bohip_gp_set_jitter / BOHIP_JITTER): then the diagonal gets jitter_rel x mean(diag) more, x10 per further try -- the shape
@@ -1670,112 +1803,7 @@ static int refit_once(bohip_gp* g, double jitter) {
         return 0;
     }
     g->chol_form_last = 0;
-    // Right-looking on 128-column panels, with the trailing update applied in two tiers: inside an outer block
-    // of OB panels only the block's own remaining columns are updated after every panel (K = 128); everything to
-    // the right of the outer block is updated ONCE per outer block with K = 128 * OB.  The C tiles of the bulk
-    // are therefore read-modified-written T/OB times instead of T times and the bulk contraction is OB x deeper.
-    const int OB = 4;
-    bool side_pending = false;
-    // The bulk update of the columns right of the NEXT block runs on the side stream.  Run as one launch it shares the chip
-    // with the next block's whole diagonal chain and slows the chain's small GEMMs 3-6x (N = 10^4: 90-120 us instead of
-    // 15-25 us each).  So it is cut into pieces of equal area, and piece j is released by an event recorded just before the
-    // j-th diagonal-block kernel of the next block starts: the pieces fill the ~70 us during which that single-workgroup
-    // kernel leaves the chip idle and are (mostly) gone when the chain's GEMMs arrive.
-    struct Pending { int ob = 0, oe = 0, c0 = 0, rest = 0, next = 0, pieces = 0; int cut[9] = {0}; } pend;
-    auto bulk_params = [&](int pob, int poe, int r0t, int c0t, int mt, int nct) {
-        GemmNTParams b{};  // A[i, j] -= L[i, pob:poe] L[j, pob:poe]'  on rows >= r0t, columns [c0t, c0t + nct)
-        b.A = g->dS + (int64_t)r0t * TILE * ld + (int64_t)pob * TILE; b.lda = ld;
-        b.B = g->dS + (int64_t)c0t * TILE * ld + (int64_t)pob * TILE; b.ldb = ld;
-        b.C = g->dL + (int64_t)r0t * TILE * ld + (int64_t)c0t * TILE; b.ldc = ld;
-        b.mt = mt; b.nt64 = 2 * nct; b.kc = (poe - pob) * (TILE / KC); b.alpha = -1.0; b.beta = 1.0;
-        b.diag_skip = 1; b.row0 = (int64_t)r0t * TILE; b.col0 = (int64_t)c0t * TILE;
-        return b;
-    };
-    auto release_piece = [&](bool gated) -> int {   // next piece of the pending bulk update -> side stream
-        if (pend.next >= pend.pieces) return 0;
-        if (gated) {
-            HIPCHK(hipEventRecord(g->ev_gate, g->stream));
-            HIPCHK(hipStreamWaitEvent(g->side_stream, g->ev_gate, 0));
-        }
-        const int a = pend.cut[pend.next], b = pend.cut[pend.next + 1];
-        ++pend.next;
-        if (b > a)   // columns [c0 + a, c0 + b) of the pending region, rows from the first of them down
-            CHK(launch_gemm_nt(g, bulk_params(pend.ob, pend.oe, pend.c0 + a, pend.c0 + a, pend.rest - a, b - a), 1, g->side_stream));
-        if (pend.next == pend.pieces) HIPCHK(hipEventRecord(g->ev_bulk, g->side_stream));
-        return 0;
-    };
-    for (int ob = 0; ob < T; ob += OB) {
-        const int oe = std::min(T, ob + OB);
-        for (int kb = ob; kb < oe; ++kb) {
-            double* Lkk = g->dL + (int64_t)kb * TILE * (ld + 1);
-            double* Wkk = g->dW + (int64_t)kb * TILE * (ld + 1);
-            CHK(release_piece(true));
-            hipLaunchKernelGGL(k_potf2_inv, dim3(1), dim3(PF_THREADS), POTF2_LDS_BYTES, g->stream, Lkk, ld, Wkk,
-                               g->dWT + (int64_t)kb * TILE * (ld + 1), ld, g->dinfo, kb * TILE);
-            HIPCHK(hipGetLastError());
-            const int rem = T - kb - 1;
-            if (rem == 0) break;
-            const int64_t poff = (int64_t)(kb + 1) * TILE * ld + (int64_t)kb * TILE;
-            double* panel = g->dS + poff;  // solved panel L[kb+1:, kb] lives in the scratch matrix until the final copy
-            GemmNTParams p{};  // panel solve L[i,kb] = A[i,kb] * inv(L_kk)'   (out of place: dL -> dS)
-            p.A = g->dL + poff; p.lda = ld; p.B = Wkk; p.ldb = ld; p.C = panel; p.ldc = ld;
-            p.mt = rem; p.nt64 = 2; p.kc = TILE / KC; p.alpha = 1.0; p.beta = 0.0;
-            CHK(launch_gemm_nt(g, p));
-            const int inner_cols = oe - kb - 1;  // remaining panels of this outer block
-            if (inner_cols > 0) {
-                GemmNTParams u{};  // A[i, j] -= L[i,kb] L[j,kb]'  for j in (kb, oe), i >= j
-                u.A = panel; u.lda = ld; u.B = panel; u.ldb = ld;
-                u.C = g->dL + (int64_t)(kb + 1) * TILE * (ld + 1); u.ldc = ld;
-                u.mt = rem; u.nt64 = 2 * inner_cols; u.kc = TILE / KC; u.alpha = -1.0; u.beta = 1.0;
-                u.diag_skip = 1; u.row0 = (int64_t)(kb + 1) * TILE; u.col0 = (int64_t)(kb + 1) * TILE;
-                CHK(launch_gemm_nt(g, u));
-            }
-        }
-        while (pend.next < pend.pieces) CHK(release_piece(false));   // a short last block: whatever is left goes now
-        if (g_inv_overlap) {
-            // The block's panels are final: invert its diagonal region and join it to the leading inverse on the inverse
-            // stream, beside the next blocks' diagonal chain (which leaves most CUs idle).  Reads dS panels of columns
-            // < oe (final), W/W' of tiles < oe; writes W/W' rows/columns of THIS block and the upper-right part of dS.
-            HIPCHK(hipEventRecord(g->ev_blk, g->stream));
-            HIPCHK(hipStreamWaitEvent(g->inv_stream, g->ev_blk, 0));
-            for (int h = 1; h < oe - ob; h *= 2) CHK(inverse_level(g, g->inv_stream, ob, oe - ob, h));
-            CHK(inverse_join(g, g->inv_stream, ob, oe - ob));
-        }
-        const int rem = T - oe;
-        if (rem > 0) {
-            // Bulk update with the OB solved panels: the columns of the NEXT outer block on the critical stream, everything
-            // to their right in gated pieces on the side stream.  Hazards: (1) the side stream needs the panels -> ev_panels;
-            // (2) the next block's columns were last written by the previous block's pieces -> ev_bulk (after the last one).
-            const int nxt = std::min(OB, rem), rest = rem - nxt;
-            if (rest > 0) {
-                HIPCHK(hipEventRecord(g->ev_panels, g->stream));
-                HIPCHK(hipStreamWaitEvent(g->side_stream, g->ev_panels, 0));
-            }
-            if (side_pending) HIPCHK(hipStreamWaitEvent(g->stream, g->ev_bulk, 0));
-            CHK(launch_gemm_nt(g, bulk_params(ob, oe, oe, oe, rem, nxt)));
-            if (rest > 0) {
-                pend = Pending{};
-                pend.ob = ob; pend.oe = oe; pend.c0 = oe + nxt; pend.rest = rest; pend.next = 0;
-                pend.pieces = g_bulk_pieces > 0 ? std::min({g_bulk_pieces, nxt, rest}) : 1;
-                // equal-area cuts of the lower-triangular region: the area left of column c is c rest - c (c - 1) / 2
-                const double total = 0.5 * rest * (rest + 1.0);
-                for (int q = 0, c = 0; q <= pend.pieces; ++q) {
-                    const double want = total * q / pend.pieces;
-                    while (c < rest && c * (double)rest - 0.5 * c * (c - 1.0) < want - 1e-9) ++c;
-                    pend.cut[q] = q == pend.pieces ? rest : c;
-                }
-                if (pend.pieces == 1) CHK(release_piece(false));   // ungated single launch (small problems, BOHIP_BULK_PIECES=0)
-                side_pending = true;
-            } else {
-                side_pending = false;
-            }
-        }
-    }
-    if (side_pending) HIPCHK(hipStreamWaitEvent(g->stream, g->ev_bulk, 0));
-    if (T > 1) {
-        hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-        HIPCHK(hipGetLastError());
-    }
+    CHK(factor_launch_chain(g, model_factor_ws(g), T, true));
     t_end(g);
     t_begin(g, "tri_inverse");
     if (g_inv_overlap) {   // only the tail of the last block's join is still running
@@ -2741,6 +2769,10 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->ddmll_parts) hipFree(g->ddmll_parts);
     if (g->dVV) hipFree(g->dVV);
     if (g->dcov) hipFree(g->dcov);
+    for (double** p : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT, &g->sjF, &g->sj_scal})
+        if (*p) hipFree(*p);
+    if (g->sj_info) hipFree(g->sj_info);
+    if (g->sj_part) hipFree(g->sj_part);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -3001,9 +3033,9 @@ int bohip_gp_predict(bohip_gp* g, const double* Xs, int64_t R, double* mu, doubl
     return 0;
 }
 
-int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, double* cov) {
-    if (!g || R < 0 || (R > 0 && (!Xs || !mu || !cov))) return fail(BOHIP_E_ARG, "bad arguments");
-    if (R == 0) return 0;
+// Stages shared by bohip_gp_predict_cov and bohip_gp_sample_joint: K*', V' = K*'W' (stored), V'V on the MFMA engine (lower
+// 128-tiles of dVV, leading dimension cov_cap).  `who` names the caller in the message of the one-chunk limit.
+static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* who) {
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
@@ -3011,7 +3043,7 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
     if (R > g->chunk_now)
-        return fail(BOHIP_E_UNSUPPORTED, "predict_cov: R exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + ")");
+        return fail(BOHIP_E_UNSUPPORTED, std::string(who) + ": R exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + ")");
     CHK(ensure_grad_scratch(g));
     CHK(one_time_kernel_setup());
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, Rp = round_up(R, TILE);
@@ -3039,10 +3071,25 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     p.mt = CT; p.nt64 = 2 * CT; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.diag_skip = 1;
     CHK(launch_gemm_nt(g, p));
     t_end(g);
-    t_begin(g, "post_cov");
+    return 0;
+}
+// the latent mean of the candidates of posterior_vv -> dmu (dvar: the clamped variance, unused by the joint forms)
+static int posterior_mean(bohip_gp* g, int64_t R) {
+    const int64_t Rpad = round_up(R, TILE) + TILE;
     AcqParams ap{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
-    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, T, g->dmu_raw, R,
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, g->q_tiles, g->dmu_raw, R,
                        std::exp(2.0 * g->logsig), g->beta, ap, g->dmu, g->dvar, (double*)nullptr, (Best*)nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, double* cov) {
+    if (!g || R < 0 || (R > 0 && (!Xs || !mu || !cov))) return fail(BOHIP_E_ARG, "bad arguments");
+    if (R == 0) return 0;
+    CHK(posterior_vv(g, Xs, R, "predict_cov"));
+    const KernelHyper hp = make_hyper(g);
+    t_begin(g, "post_cov");
+    CHK(posterior_mean(g, R));
     dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
     const bool lo = fam_low(hp);
 #define PC(DTV) LAUNCH_FAM(lo, (k_post_cov<DTV, true>), (k_post_cov<DTV, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV, \
@@ -3055,6 +3102,141 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipMemcpyAsync(cov, g->dcov, (size_t)R * R * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+// ---- joint posterior draws over a candidate set (kernels_sample.hip; reference myrand(model, X::Matrix), src/models/gp.jl:7) ----
+static int ensure_sample(bohip_gp* g, int64_t Rp, int64_t R, int64_t S, bool want_samples, size_t part_recs) {
+    if (g->sj_cap < Rp) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        for (double** p : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT})
+            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+        const int64_t cap = std::max<int64_t>(Rp, round_up(g->sj_cap + g->sj_cap / 2, TILE)), ld = cap + 16;
+        g->sj_cap = 0;
+        const size_t mat = (size_t)ld * ld * 8, inv = (size_t)cap * TILE * 8;
+        HIPCHK(hipMalloc(&g->sjL, mat));
+        HIPCHK(hipMalloc(&g->sjS, mat));
+        HIPCHK(hipMalloc(&g->sjW, inv));
+        HIPCHK(hipMalloc(&g->sjWT, inv));
+        // tiles above the diagonal tiles of the matrix, and the far triangles of the diagonal inverses, are never written: zero once
+        HIPCHK(hipMemsetAsync(g->sjL, 0, mat, g->stream));
+        HIPCHK(hipMemsetAsync(g->sjS, 0, mat, g->stream));
+        HIPCHK(hipMemsetAsync(g->sjW, 0, inv, g->stream));
+        HIPCHK(hipMemsetAsync(g->sjWT, 0, inv, g->stream));
+        g->sj_cap = cap;
+    }
+    if (!g->sj_scal) HIPCHK(hipMalloc(&g->sj_scal, 8));
+    if (!g->sj_info) HIPCHK(hipMalloc(&g->sj_info, sizeof(int)));
+    const size_t fneed = want_samples ? (size_t)S * R : 0;
+    if (g->sjF_cap < fneed) {
+        if (g->sjF) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sjF)); g->sjF = nullptr; }
+        const size_t cap = std::max(fneed, g->sjF_cap + g->sjF_cap / 2);
+        g->sjF_cap = 0;
+        HIPCHK(hipMalloc(&g->sjF, cap * 8));
+        g->sjF_cap = cap;
+    }
+    if (g->sj_part_cap < part_recs) {
+        if (g->sj_part) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sj_part)); g->sj_part = nullptr; }
+        const size_t cap = std::max(part_recs, g->sj_part_cap + g->sj_part_cap / 2);
+        g->sj_part_cap = 0;
+        HIPCHK(hipMalloc(&g->sj_part, cap * sizeof(Best)));
+        g->sj_part_cap = cap;
+    }
+    if (g->thompson_cap < S) {
+        if (g->dthompson) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dthompson)); }
+        g->dthompson = nullptr; g->thompson_cap = 0;
+        HIPCHK(hipMalloc(&g->dthompson, (size_t)S * sizeof(Best)));
+        g->thompson_cap = S;
+    }
+    return 0;
+}
+
+int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel, int max_tries,
+                          double* mu, double* chol, double* samples, bohip_best* best, double* jitter_used, int* tries_used) {
+    if (!g || !Xs || R < 1 || S < 1) return fail(BOHIP_E_ARG, "sample_joint: bad arguments (R and S must be at least 1)");
+    if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return fail(BOHIP_E_ARG, "sample_joint: jitter_rel must be finite and not negative");
+    if (max_tries < 0) return fail(BOHIP_E_ARG, "sample_joint: max_tries must not be negative");
+    CHK(posterior_vv(g, Xs, R, "sample_joint"));
+    const int64_t Rp = round_up(R, TILE);
+    const int CT = (int)(Rp / TILE);
+    const bool mfma = S >= g_sample_mfma_min;
+    const int ntiles = (int)((R + (mfma ? SM_ROWS : SROWS) - 1) / (mfma ? SM_ROWS : SROWS));
+    CHK(ensure_sample(g, Rp, R, S, samples != nullptr, (size_t)S * ntiles));
+    const int64_t ld = g->sj_cap + 16;
+    const FactorWs ws{g->sjL, g->sjS, g->sjW, g->sjWT, ld, TILE, (int64_t)TILE * TILE, g->sj_info};
+    const KernelHyper hp = make_hyper(g);
+    const dim3 cgrid((unsigned)((Rp + 255) / 256), (unsigned)(Rp / 16));
+    t_begin(g, "post_cov+jitter");
+    CHK(posterior_mean(g, R));
+    {
+        const bool lo = fam_low(hp);
+#define SC(DTV) LAUNCH_FAM(lo, (k_sample_cov<DTV, true>), (k_sample_cov<DTV, false>), cgrid, dim3(256), 0, g->stream, g->dXs, R, Rp, hp, \
+                           g->dVV, g->cov_cap, g->dcov, g->cov_cap, ws.L, ld)
+        if (g->d <= 2) SC(2); else if (g->d <= 4) SC(4); else if (g->d <= 8) SC(8); else if (g->d <= 16) SC(16);
+        else if (g->d <= 32) SC(32); else SC(64);
+#undef SC
+    }
+    hipLaunchKernelGGL(k_sample_diagmax, dim3(1), dim3(256), 0, g->stream, g->dcov, g->cov_cap, R, g->sj_scal);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    double jit = 0.0;
+    int tries = 0;
+    for (;;) {
+        HIPCHK(hipMemsetAsync(g->sj_info, 0, sizeof(int), g->stream));
+        if (tries > 0) {   // Sigma is kept (dcov): the workspace again, with the jitter on the diagonal
+            t_begin(g, "post_cov+jitter");
+            hipLaunchKernelGGL(k_sample_rejit, cgrid, dim3(256), 0, g->stream, g->dcov, g->cov_cap, R, Rp, jit, ws.L, ld);
+            HIPCHK(hipGetLastError());
+            t_end(g);
+        }
+        // the launch-chained form, without the inverse queues: only the diagonal inverses the panel solves use.  It touches
+        // nothing of the model (no flag block, no refit lock: it has no persistent workgroups).
+        t_begin(g, "sample_cholesky");
+        CHK(factor_launch_chain(g, ws, CT, false));
+        t_end(g);
+        t_begin(g, "sample_draw");
+        double* const dF = samples ? g->sjF : nullptr;
+        if (mfma) {
+            hipLaunchKernelGGL(k_sample_mfma, dim3((unsigned)ntiles, (unsigned)((S + SM_DRAWS - 1) / SM_DRAWS)), dim3(256), 0, g->stream,
+                               ws.L, ld, R, S, seed, g->dmu, dF, g->sj_part, ntiles);
+        } else if (S == 1) {
+            hipLaunchKernelGGL(k_sample_rows<1>, dim3((unsigned)ntiles, 1), dim3(256), 0, g->stream, ws.L, ld, R, S, seed, g->dmu, dF,
+                               g->sj_part, ntiles);
+        } else {
+            hipLaunchKernelGGL(k_sample_rows<4>, dim3((unsigned)ntiles, (unsigned)((S + 3) / 4)), dim3(256), 0, g->stream, ws.L, ld, R, S,
+                               seed, g->dmu, dF, g->sj_part, ntiles);
+        }
+        hipLaunchKernelGGL(k_sample_best, dim3((unsigned)S), dim3(64), 0, g->stream, g->sj_part, ntiles, g->dthompson);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        // everything the caller asked for is copied behind the kernels, so a call that needs no jitter synchronises once
+        int info = 0;
+        double scale = 0.0;
+        HIPCHK(hipMemcpyAsync(&info, g->sj_info, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(&scale, g->sj_scal, 8, hipMemcpyDeviceToHost, g->stream));
+        if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+        if (best) HIPCHK(hipMemcpyAsync(best, g->dthompson, (size_t)S * sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+        if (samples) HIPCHK(hipMemcpyAsync(samples, g->sjF, (size_t)S * R * 8, hipMemcpyDeviceToHost, g->stream));
+        if (chol) {   // dVV is free once Sigma exists
+            hipLaunchKernelGGL(k_sample_pack, dim3((unsigned)((R + 255) / 256), (unsigned)R), dim3(256), 0, g->stream, ws.L, ld, R, g->dVV);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(chol, g->dVV, (size_t)R * R * 8, hipMemcpyDeviceToHost, g->stream));
+        }
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (info == 0) break;
+        const double next = std::max(10.0 * jit, jitter_rel * scale);
+        if (tries >= max_tries || !(next > jit)) {
+            g->pivot = info;
+            t_collect(g);
+            return fail(BOHIP_E_NOTPD, "sample_joint: posterior covariance not positive definite at pivot " + std::to_string(info) +
+                                           " (jitter " + std::to_string(jit) + " after " + std::to_string(tries) + " tries)");
+        }
+        jit = next;
+        ++tries;
+    }
+    if (jitter_used) *jitter_used = jit;
+    if (tries_used) *tries_used = tries;
     t_collect(g);
     return 0;
 }

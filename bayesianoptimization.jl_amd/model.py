@@ -359,6 +359,13 @@ class ElasticGPE:
         check(self._lib.bohip_gp_thompson(self._h, _ptr(xs), xs.shape[1], S, seed, j0, out))
         return np.array([b.val for b in out]), np.array([b.idx for b in out], dtype=np.int64)
 
+    def sample_joint(self, xs, S=1, seed=0, jitter=1e-12, max_tries=40, want_samples=True, want_factor=False):
+        """S JOINT draws of the posterior over the columns of xs on the device (bohip_gp_sample_joint; reference
+        myrand(model, X::Matrix), src/models/gp.jl:7): f_s = mu + C z_s, C C' = Sigma + jitter I, z from the library's counter-based
+        generator keyed (seed, s, j).  `thompson` draws every candidate independently; this is the draw whose arg-max is a draw of
+        the maximiser.  Only what is asked for crosses to the host.  Returns a JointSample."""
+        return _sample_joint(self._lib, self._h, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
+
     # -- introspection ------------------------------------------------------------------------------
     def factor(self):
         n = self.nobs
@@ -396,6 +403,35 @@ class ElasticGPE:
                 f"logNoise={self.logNoise}) [device-resident, libbohip]")
 
 
+class JointSample:
+    """Result of sample_joint: samples (S x R, or None), best_val[S] / best_idx[S] (arg-max of every draw: strict '>', ties to the
+    smallest index), mu[R], jitter (what was added to the diagonal), tries (failed factorisations before the one that went through),
+    factor (R x R lower triangular, or None)."""
+    __slots__ = ("samples", "best_val", "best_idx", "mu", "jitter", "tries", "factor")
+
+    def __init__(self, samples, best_val, best_idx, mu, jitter, tries, factor):
+        self.samples, self.best_val, self.best_idx, self.mu = samples, best_val, best_idx, mu
+        self.jitter, self.tries, self.factor = jitter, tries, factor
+
+    def __iter__(self):
+        return iter((self.samples, self.best_val, self.best_idx, self.mu, self.jitter, self.tries, self.factor))
+
+
+def _sample_joint(lib, handle, xs, S, seed, jitter, max_tries, want_samples, want_factor):
+    R, S = xs.shape[1], int(S)
+    mu = np.empty(R)
+    samples = np.empty((S, R)) if want_samples and S > 0 else None
+    factor = np.empty((R, R)) if want_factor else None
+    out = (Best * max(S, 1))()
+    jit, tries = C.c_double(0.0), C.c_int(0)
+    check(lib.bohip_gp_sample_joint(handle, _ptr(xs), R, S, int(seed), float(jitter), int(max_tries), _ptr(mu),
+                                    _ptr(factor) if factor is not None else None,
+                                    _ptr(samples) if samples is not None else None, out, C.byref(jit), C.byref(tries)))
+    vals = np.array([out[i].val for i in range(S)])
+    idx = np.array([out[i].idx for i in range(S)], dtype=np.int64)
+    return JointSample(samples, vals, idx, mu, jit.value, tries.value, factor)
+
+
 # ---- the generic functions of reference src/models/gp.jl ----------------------------------------
 def mean_var(model, x):
     """gp.jl:2-5 (vector -> scalars) and :8 (d x R matrix -> vectors)."""
@@ -406,12 +442,16 @@ def mean_var(model, x):
     return mu, var
 
 
-def myrand(model, x, rng=None):
+def myrand(model, x, rng=None, *, seed=None):
     """gp.jl:6-7.  Vector: one draw from N(mu, sigma^2).  Matrix: ONE JOINT draw from N(mu, Sigma_post) over the columns
     (rand(gp, X) = mu + chol(Sigma)·z with jitter added until the factorisation succeeds -- GaussianProcesses.jl
-    make_posdef!, UPSTREAM-UNVERIFIED; only the length is pinned by test/acquisitionfunctions.jl:8)."""
-    rng = rng if rng is not None else np.random.default_rng()
+    make_posdef!, UPSTREAM-UNVERIFIED; only the length is pinned by test/acquisitionfunctions.jl:8).
+    seed given (matrix x, a model with sample_joint): the same draw made on the device, z from the library's generator keyed by
+    `seed` (model.sample_joint, S = 1); without it the covariance is factorised on the host with z from `rng`."""
     x = np.asarray(x, dtype=np.float64)
+    if seed is not None and x.ndim == 2 and hasattr(model, "sample_joint"):
+        return model.sample_joint(x, 1, int(seed)).samples[0]
+    rng = rng if rng is not None else np.random.default_rng()
     if x.ndim == 1:
         mu, var = model.predict_f(x)
         return float(mu[0] + math.sqrt(var[0]) * rng.standard_normal())

@@ -168,6 +168,14 @@ class MultiGPE:
                                             float(maxtime or 0.0), int(seed), C.byref(bf), _ptr(bx), C.byref(ev), C.byref(dc)))
         return float(bf.value), bx, int(ev.value), int(dc.value)
 
+    def sample_joint(self, xs, S=1, seed=0, jitter=1e-12, max_tries=40, want_samples=True, want_factor=False):
+        """Joint posterior draws (ElasticGPE.sample_joint, bohip_gp_sample_joint) on the FIRST replica: Sigma couples all candidates,
+        so there is nothing to shard -- every device holds the whole model."""
+        from .model import _sample_joint
+
+        g = self._lib.bohip_mgp_handle(self._h, 0)
+        return _sample_joint(self._lib, g, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
+
     def replica_factor(self, i):
         """Cholesky factor held by the i-th device (tests: every replica is the same model)."""
         g = self._lib.bohip_mgp_handle(self._h, i)

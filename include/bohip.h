@@ -184,6 +184,26 @@ int bohip_gp_thompson(bohip_gp *gp, const double *Xs, int64_t R, int64_t S, uint
 /* the generator itself, exposed so tests and other shards can reproduce z (host side) */
 double bohip_thompson_normal(uint64_t seed, int64_t s, int64_t j);
 
+/* ---- myrand(model, X::Matrix) = rand(gp, X) (reference src/models/gp.jl:7): JOINT posterior draws over the R candidates, S at
+ * once, everything on the device.  (bohip_gp_thompson's draws are independent per candidate; the arg-max of a joint draw is a
+ * draw from the posterior of the maximiser over the candidate set, the arg-max of independent draws is not.)
+ *   Sigma = K** - V'V                      exactly bohip_gp_predict_cov's matrix (latent f, diagonal NOT clamped)
+ *   C C'  = Sigma + jitter I               C lower triangular, candidates in the order given
+ *   f_s   = mu + C z_s,  z_sj = bohip_thompson_normal(seed, s, j)          s = 0..S-1, j = 0..R-1
+ *   best[s] = arg-max_j f_sj               strict '>' from -Inf, ties -> smallest j, NaN never wins (bohip_gp_score's rule)
+ * jitter: the first try adds 0.  A factorisation that fails is repeated with jitter = max(10 * jitter, jitter_rel * scale),
+ * scale = max(max_j Sigma_jj, DBL_MIN), at most max_tries times (max_tries = 0: BOHIP_E_NOTPD at once, BOHIP_INFO_PIVOT names
+ * the pivot).  jitter_rel = 1e-12, max_tries = 40 is the rule of the host myrand in model.py.  A retry repeats no contraction:
+ * Sigma is kept on the device.
+ * Outputs, each nullable: mu (R), chol (R x R row-major, strict upper triangle zero), samples (S x R row-major: draw s at
+ * samples[s*R + j]), best (S records), jitter_used, tries_used.  Only what is asked for is copied to the host.  The model is
+ * not changed.  One host synchronisation per call, plus one per retry.
+ * BOHIP_E_ARG: R < 1, S < 1, jitter_rel < 0 or not finite, max_tries < 0; BOHIP_E_STATE: no observations;
+ * BOHIP_E_UNSUPPORTED: R exceeds one candidate chunk (the limit of bohip_gp_predict_cov).                               */
+int bohip_gp_sample_joint(bohip_gp *gp, const double *Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel,
+                          int max_tries, double *mu, double *chol, double *samples, bohip_best *best,
+                          double *jitter_used, int *tries_used);
+
 /* ---- :GN_DIRECT_L, the reference's default search for ThompsonSamplingSimple (reference src/acquisition.jl:7-9: restarts 1,
  * maxeval 2000; nlopt_setup :20-38 hands the acquisition to NLopt) and for any acquisition the caller selects it for.
  * NLopt is not vendored in the reference; csrc/direct_l.h restates DIRECT-L with the rules of NLopt's cdirect.c for this variant

@@ -91,6 +91,7 @@ c_gp_set_ascent_stop(h, fa, xr, sv) = ccall((:bohip_gp_set_ascent_stop, libbohip
 c_debug_set_chol_inv_g(blocks) = ccall((:bohip_debug_set_chol_inv_g, libbohip), Cint, (Cint,), blocks)
 c_gp_set_jitter(h, rel, tries) = ccall((:bohip_gp_set_jitter, libbohip), Cint, (Ptr{Cvoid}, Float64, Cint), h, rel, tries)
 c_gp_thompson(h, Xs, R, S, seed, j0, best) = ccall((:bohip_gp_thompson, libbohip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, UInt64, Int64, Ptr{Best}), h, Xs, R, S, seed, j0, best)
+c_gp_sample_joint(h, Xs, R, S, seed, jrel, tries, mu, chol, samples, best, jused, tused) = ccall((:bohip_gp_sample_joint, libbohip), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, UInt64, Float64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Best}, Ptr{Float64}, Ptr{Cint}), h, Xs, R, S, seed, jrel, tries, mu, chol, samples, best, jused, tused)
 c_thompson_normal(seed, s, j) = ccall((:bohip_thompson_normal, libbohip), Float64, (UInt64, Int64, Int64), seed, s, j)
 c_gp_score_dev(h, acq, p, dXs, R, dsc, dbest) = ccall((:bohip_gp_score_dev, libbohip), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), h, acq, p, dXs, R, dsc, dbest)
 c_gp_predict_dev(h, dXs, R, dmu, dvar) = ccall((:bohip_gp_predict_dev, libbohip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), h, dXs, R, dmu, dvar)
@@ -323,6 +324,45 @@ function acquire_batch(m::BOHipGPE, a::AbstractAcquisition, X::AbstractMatrix, q
     check(c_gp_select_batch(m.handle, acqid(a), acqparams(a), Xc, R, q, fantasy === :believer ? Cint(0) : Cint(1),
                             fantasy === :believer ? 0.0 : Float64(fantasy), raise_tau ? Cint(1) : Cint(0), idx, val, mu, var))
     val, idx .+ 1, mu, var
+end
+"""
+    sample_joint(m, X, S; seed = 0, jitter = 1e-12, max_tries = 40, samples = true, factor = false)
+        -> (samples R x S or nothing, best values, 1-based best columns, mu, jitter, tries, factor or nothing)
+
+S JOINT posterior draws over the columns of X on the device (bohip_gp_sample_joint): column s of `samples` is mu + C z_s with
+C C' = Sigma + jitter I and z from the library's counter-based generator keyed (seed, s - 1, j - 1).  `myrand(m, X)` is the same
+draw made on the host with Julia's RNG; `thompson` draws every candidate independently.  On a device list the first replica runs it.
+"""
+function sample_joint(m::AbstractBOHipModel, X::AbstractMatrix, S::Integer; seed::Integer = 0, jitter::Real = 1e-12,
+                      max_tries::Integer = 40, samples::Bool = true, factor::Bool = false)
+    Xc = _cols(m, X); R = size(Xc, 2)
+    μ = Vector{Float64}(undef, R)
+    F = samples ? Matrix{Float64}(undef, R, S) : nothing          # the library's S x R row-major = R x S column-major
+    Ct = factor ? Matrix{Float64}(undef, R, R) : nothing          # row-major lower factor = its transpose, column-major
+    best = Vector{Best}(undef, max(S, 1)); jused = Ref(0.0); tused = Ref(Cint(0))
+    check(c_gp_sample_joint(gp_handle(m), Xc, R, S, UInt64(seed), Float64(jitter), Cint(max_tries), μ, factor ? Ct : C_NULL,
+                            samples ? F : C_NULL, best, jused, tused))
+    F, map(b -> b.val, first(best, S)), map(b -> Int(b.idx) + 1, first(best, S)), μ, jused[], Int(tused[]), factor ? permutedims(Ct) : nothing
+end
+"""
+    acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
+
+q columns of X to evaluate in parallel by Thompson sampling: ONE `sample_joint` call with q joint draws; draw s takes its best
+column not already taken by draws 1..s-1 (ties -> the smallest index).  An extension, as `acquire_batch` is.
+"""
+function acquire_thompson_batch(m::AbstractBOHipModel, X::AbstractMatrix, q::Integer; seed::Integer = rand(UInt64) >> 1)
+    1 <= q <= size(X, 2) || throw(ArgumentError("q must lie in 1..$(size(X, 2))"))
+    F = sample_joint(m, X, q; seed = seed)[1]
+    taken = falses(size(F, 1)); vals = Float64[]; cols = Int[]
+    for s in 1:q
+        bv = -Inf; bj = 0
+        for j in 1:size(F, 1)
+            (!taken[j] && F[j, s] > bv) && ((bv, bj) = (F[j, s], j))
+        end
+        bj == 0 && continue
+        taken[bj] = true; push!(vals, bv); push!(cols, bj)
+    end
+    vals, cols
 end
 "value and gradient (d x R) of the acquisition at the columns of X: the role of wrap_gradient (src/acquisition.jl:11-17)"
 function score_grad(m::AbstractBOHipModel, a::AbstractAcquisition, X::AbstractMatrix)
