@@ -7,7 +7,7 @@ libbohip.so (HIP, gfx950).  See DESIGN.md / INTEGRATION.md.
 from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
-                    mean_var, myrand, dims, maxy, update_)
+                    mean_var, myrand, dims, maxy, update_, PosteriorPaths)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,

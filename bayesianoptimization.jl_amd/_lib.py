@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -23,6 +23,7 @@ INFO_COMM_NRANKS, INFO_COMM_EXCHANGES, INFO_COMM_RCCL_VERSION, INFO_CHOL_LOCK_SK
 MGP_INFO_DEVICES, MGP_INFO_SHARDS, MGP_INFO_EXCHANGES, MGP_INFO_RCCL_VERSION, MGP_INFO_COMM_NRANKS = 0, 1, 2, 3, 4
 UNIQUE_ID_BYTES = 128
 FANTASY_BELIEVER, FANTASY_CONST, BATCH_RAISE_TAU = 0, 1, 1   # bohip_gp_select_batch
+PATHS_S_MAX, PATHS_M_MAX = 4096, 16384                       # bohip_gp_paths_draw
 
 
 class Best(C.Structure):
@@ -120,6 +121,17 @@ SIGNATURES = {
     "bohip_device_count": (C.c_int, []),
 }
 
+# every symbol include/bohip_paths.h declares (the posterior sample paths, an object of its own beside the model's ABI)
+_paths = C.c_void_p
+PATHS_SIGNATURES = {
+    "bohip_gp_paths_draw": (C.c_int, [_gp, C.c_int64, C.c_int64, C.c_uint64, C.POINTER(_paths)]),
+    "bohip_paths_destroy": (None, [_paths]),
+    "bohip_paths_dims": (C.c_int, [_paths, _i64p, _i64p, _i64p, _i64p]),
+    "bohip_paths_eval": (C.c_int, [_paths, _dp, C.c_int64, _dp, C.POINTER(Best)]),
+    "bohip_paths_eval_grad": (C.c_int, [_paths, _dp, C.c_int64, _i64p, _dp, _dp]),
+    "bohip_paths_coef": (C.c_int, [_paths, C.c_int64, _dp, _dp, _dp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -166,7 +178,7 @@ def _one_hip_runtime():
 
 
 def load():
-    """dlopen libbohip.so and bind every declared symbol.  Raises if the library was not built."""
+    """dlopen libbohip.so and bind every declared symbol (both headers).  Raises if the library was not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -174,7 +186,7 @@ def load():
         raise BohipError(E_NODEVICE, f"{LIB_PATH} not built (run __graft_entry__.build()); there is no CPU fallback")
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

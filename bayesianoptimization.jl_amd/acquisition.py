@@ -374,7 +374,10 @@ def _warn_not_a_local_search(method):
 
 # "joint" is this package's own option (not an NLopt property): ThompsonSamplingSimple over a candidate set takes ONE JOINT draw
 # of the posterior (model.sample_joint) instead of independent per-candidate draws (model.thompson).  Default False.
-_OPTS_USED = {"method", "restarts", "maxeval", "maxtime", "ftol_rel", "xtol_abs", "ftol_abs", "xtol_rel", "stopval", "joint"}
+# "pathwise" (with "features" = M, default 2048) is this package's own too: ThompsonSamplingSimple searches ONE posterior sample
+# path per restart (model.draw_paths), a function that keeps its value wherever it is evaluated again.  Default False.
+_OPTS_USED = {"method", "restarts", "maxeval", "maxtime", "ftol_rel", "xtol_abs", "ftol_abs", "xtol_rel", "stopval", "joint",
+              "pathwise", "features"}
 _OPTS_NLOPT_ONLY = {"initial_step", "population", "vector_storage", "seed", "local_optimizer", "default_initial_step"}
 
 
@@ -387,6 +390,54 @@ def _check_options(opts):
         else:
             raise ValueError(f"unknown acquisition option {k!r} (the reference forwards every key to NLopt.Opt, "
                              "which rejects unknown properties)")
+
+
+def _acquire_max_pathwise(model, lb, ub, method, restarts, maxeval, maxtime, opts, rng):
+    """ThompsonSamplingSimple with "pathwise": True.  Every restart draws ONE posterior sample path (model.draw_paths, S = 1, seed
+    from `rng`) and maximises that function:
+      :GN_DIRECT*  direct_l_search over x -> path(x): every point of the search sees the same draw (the reference's objective
+                   x -> myrand(model, x) returns an unrelated draw per evaluation);
+      otherwise    `maxeval` Latin-hypercube points scored on the path, arg-max on the device; with an :LD_* method the best
+                   `restarts` of them are then refined by the batched L-BFGS ascent on the path's analytic gradient.
+    The first maximum over the restarts wins (strict '>')."""
+    if not hasattr(model, "draw_paths"):
+        raise NotImplementedError(f"{type(model).__name__} has no draw_paths")
+    M = int(opts.get("features", 2048))
+    gen = rng or np.random.default_rng()
+    sval = float(opts.get("stopval", math.inf))
+    direct = "DIRECT" in method.upper()
+    ascend = method.upper().startswith("LD")
+    if not direct and not ascend:
+        _warn_not_a_local_search(method)
+    maxf, maxx = -math.inf, lb.copy()
+    for _ in range(restarts):
+        seed = int(gen.integers(0, 2 ** 63 - 1))
+        with model.draw_paths(1, M, seed) as path:
+            if direct:
+                def path_batch(X):
+                    return path.eval(X)[0][0]
+
+                f, x, _ = direct_l_search(path_batch, lb, ub, max(1, maxeval), sval, maxtime)
+            else:
+                starts = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+                vals, bv, bi = path.eval(starts, want_values=ascend)
+                if bi[0] < 0:
+                    continue
+                f, x = float(bv[0]), starts[:, int(bi[0])].copy()
+                if ascend:
+                    order = np.argsort(-np.where(np.isnan(vals[0]), -math.inf, vals[0]), kind="stable")[:max(1, restarts)]
+                    fa, Xa = _batched_lbfgs_ascent(path.eval_grad, np.asfortranarray(starts[:, order]), lb, ub, max(2, maxeval),
+                                                   ftol_rel=float(opts.get("ftol_rel", 1e-10)), xtol_abs=float(opts.get("xtol_abs", 1e-10)),
+                                                   ftol_abs=float(opts.get("ftol_abs", 0.0)), xtol_rel=float(opts.get("xtol_rel", 0.0)),
+                                                   stopval=sval)
+                    j = int(np.argmax(np.where(np.isnan(fa), -math.inf, fa)))
+                    if fa[j] > f:
+                        f, x = float(fa[j]), Xa[:, j].copy()
+        if f > maxf:                                              # :62 strict '>'
+            maxf, maxx = f, x
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
 
 
 def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
@@ -409,6 +460,10 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     if model.nobs == 0 or restarts <= 0:
         return maxf, maxx
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31
+    if bool(opts.get("pathwise", False)):
+        if not isinstance(a, ThompsonSamplingSimple):
+            raise ValueError("option 'pathwise' applies to ThompsonSamplingSimple only")
+        return _acquire_max_pathwise(model, lb, ub, method, restarts, maxeval, maxtime, opts, rng)
     if "DIRECT" in method.upper() and not derivative:
         # :GN_DIRECT_L (the reference's default for ThompsonSamplingSimple, src/acquisition.jl:7-9) and its siblings: dividing
         # rectangles with every iteration's new points in one device call.  DIRECT ignores the start point, so `restarts` runs are
@@ -563,14 +618,19 @@ def _distinct_picks(samples):
     return out
 
 
-_THOMPSON_BATCH_OPTS = {"candidates", "xs"}
+_THOMPSON_BATCH_OPTS = {"candidates", "xs", "pathwise", "features", "refine", "maxeval"}
 
 
 def acquire_thompson_batch(model, lowerbounds, upperbounds, q, options=None, rng=None):
     """q points to evaluate in parallel by Thompson sampling -- an extension, as acquire_batch is.  ONE model.sample_joint call
     with S = q joint posterior draws over a candidate set ("candidates" Latin-hypercube points, default 4096, or an explicit
     d x R "xs"); draw s takes its best candidate not already taken by draws 0..s-1 (_distinct_picks).  The draws' seed comes from
-    `rng`.  Returns (values[q'], X d x q'), q' <= q (a draw with no finite value left is dropped)."""
+    `rng`.  Returns (values[q'], X d x q'), q' <= q (a draw with no finite value left is dropped).
+    "pathwise": True (default False): the q draws are posterior sample PATHS (model.draw_paths, S = q, "features" = M random
+    features, default 2048) evaluated over the candidates in one call -- no R x R factorisation, so "candidates" may exceed one
+    chunk -- and, with "refine" (default True), every pick is then ascended on ITS OWN path (eval_grad with path_of; at most
+    "maxeval" passes, default 200) inside the box; a refined point replaces its pick only where its path value is higher and the
+    point is not already in the batch (two paths may climb to the same corner of the box)."""
     lb = np.asarray(lowerbounds, dtype=np.float64)
     ub = np.asarray(upperbounds, dtype=np.float64)
     opts = dict(options or {})
@@ -582,8 +642,11 @@ def acquire_thompson_batch(model, lowerbounds, upperbounds, q, options=None, rng
         raise ValueError(f"batch size q = {q} < 1")
     if lb.size != ub.size:
         raise ValueError("length of lowerbounds does not match length of upperbounds")
-    if not hasattr(model, "sample_joint"):
-        raise NotImplementedError(f"{type(model).__name__} has no sample_joint")
+    pathwise = bool(opts.get("pathwise", False))
+    if not pathwise and any(k in opts for k in ("features", "refine", "maxeval")):
+        raise ValueError("Thompson batch options 'features', 'refine' and 'maxeval' need 'pathwise': True")
+    if not hasattr(model, "draw_paths" if pathwise else "sample_joint"):
+        raise NotImplementedError(f"{type(model).__name__} has no {'draw_paths' if pathwise else 'sample_joint'}")
     if "xs" in opts and opts["xs"] is not None:
         xs = np.asarray(opts["xs"], dtype=np.float64)
         if xs.ndim != 2 or xs.shape[0] != lb.size:
@@ -598,6 +661,22 @@ def acquire_thompson_batch(model, lowerbounds, upperbounds, q, options=None, rng
     if model.nobs == 0:
         raise RuntimeError("acquire_thompson_batch on an empty model")
     seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
+    if pathwise:
+        with model.draw_paths(q, int(opts.get("features", 2048)), seed) as paths:
+            F, _, _ = paths.eval(xs)
+            idx = _distinct_picks(F)
+            keep = idx >= 0
+            if not keep.all():
+                warnings.warn(f"acquire_thompson_batch: only {int(keep.sum())} of {q} draws had a finite value left")
+            rows = np.flatnonzero(keep)
+            vals, X = F[rows, idx[rows]].copy(), np.asfortranarray(xs[:, idx[rows]])
+            if bool(opts.get("refine", True)) and rows.size:
+                fa, Xa = _batched_lbfgs_ascent(lambda Z: paths.eval_grad(Z, rows), X, lb, ub, max(2, int(opts.get("maxeval", 200))))
+                for s in np.flatnonzero(fa > vals):               # (two paths may climb to the same point, e.g. a corner of the box:
+                    others = np.delete(X, s, axis=1)              #  the batch stays distinct, the later one keeps its pick)
+                    if not np.any(np.all(others == Xa[:, [s]], axis=0)):
+                        X[:, s], vals[s] = Xa[:, s], fa[s]
+        return vals, X
     F = model.sample_joint(xs, q, seed).samples
     idx = _distinct_picks(F)
     keep = idx >= 0

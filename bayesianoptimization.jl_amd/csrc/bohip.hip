@@ -15,12 +15,14 @@
 // There is NO CPU fallback: every entry point that computes fails with BOHIP_E_NODEVICE / BOHIP_E_HIP
 // when the GPU is unavailable.
 #include "../../include/bohip.h"
+#include "../../include/bohip_paths.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
 #include "kernels_batch.hip"   // (after the scoring kernels: shares their functors and arg-max order)
 #include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
+#include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_ascent.hip"
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
 #include "direct_l.h"          // host bookkeeping of :GN_DIRECT_L (ask / tell)
@@ -338,6 +340,10 @@ static int g_inv_overlap = 0;  // BOHIP_INV_OVERLAP=1: grow W = L^-1 block by bl
 static int g_bulk_pieces = 4;   // gated pieces of the side-stream bulk update per outer block (BOHIP_BULK_PIECES; 0/1: one launch)
 static int g_sample_mfma_min = 200;  // BOHIP_SAMPLE_MFMA_MIN: draws from which bohip_gp_sample_joint takes k_sample_mfma instead of k_sample_rows
                                      // (measured at R = 4096: the two cross between 192 and 256 draws, kernels_sample.hip)
+static int g_path_mfma_min = 24;     // BOHIP_PATH_MFMA_MIN: paths from which bohip_paths_eval takes k_path_mfma instead of k_path_rows (read at every
+                                     // bohip_gp_paths_draw and kept by the object).  The forms cross at ~130 paths at R = 4096 and at ~15 at R = 65536
+                                     // (the MFMA form is flat at 1.13 ms until its grid fills the chip, the row form is linear in S); the switch is on S
+                                     // alone so that a path's bits do not depend on R, and 24 favours large candidate sets
 static int g_split = 1;   // split-K path for batches of a few hundred candidates (BOHIP_SPLIT=0 disables)
 static int g_asc_wg_nmax = 256;  // BOHIP_ASC_WG_NMAX: models up to this many observations run acquire_max as ONE launch, one workgroup per start point
                                  // (kernels_ascent.hip k_ascent_wg); 0: never
@@ -459,6 +465,8 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_quad, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_chol_exec, hipFuncAttributeMaxDynamicSharedMemorySize, std::max<size_t>(glds3_lds_bytes<4>(), 84 * 1024)));
     HIPCHK(hipFuncSetAttribute((const void*)k_trimv_stream<TRIMV_D>, hipFuncAttributeMaxDynamicSharedMemorySize, trimv_lds_bytes(TRIMV_D)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
     // The library's switches (README "Environment"): the forms of the factorisation the tests select, the bound of its
     // waits, the ascent drivers, the small-batch pass.  Everything else that used to be read here is a constant now; the
     // sweeps under tools/ that vary those constants run against csrc/abl/libbohip_dev.so (read_dev_knobs below).
@@ -3237,6 +3245,276 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
     }
     if (jitter_used) *jitter_used = jit;
     if (tries_used) *tries_used = tries;
+    t_collect(g);
+    return 0;
+}
+
+// ---- posterior sample paths (kernels_path.hip): pathwise conditioning with a random-feature prior ----------------
+// The object owns copies of everything an evaluation reads (X, Omega, Cf, the hyper-parameters), so the model may change or be
+// refitted afterwards; it borrows the handle's device and stream.
+struct bohip_paths {
+    bohip_gp* g = nullptr;
+    int64_t S = 0, M = 0, N = 0, Npad = 0, ldc = 0;
+    int d = 0, F = 0, mfma_min = 0;
+    double amp = 0.0, beta = 0.0;
+    KernelHyper hp;
+    double *dX = nullptr, *dOm = nullptr, *dCf = nullptr;
+    // evaluation scratch: one chunk of candidates, its S x chunk values, its tile records, the S running records, the gradient staging
+    double *dXs = nullptr, *dV = nullptr, *df = nullptr, *dg = nullptr;
+    int64_t* dpath_of = nullptr;
+    Best *dpart = nullptr, *dbest = nullptr;
+    int64_t xs_cap = 0, g_cap = 0;
+    size_t v_cap = 0, part_cap = 0;
+};
+static constexpr int64_t PATHS_CHUNK = 32768;       // candidates per launch of an evaluation (a multiple of PM_ROWS and PR_CAND)
+static constexpr int64_t PATHS_GRAD_CHUNK = 4096;   // points per launch of bohip_paths_eval_grad
+static_assert(BOHIP_PATHS_S_MAX <= 65535 && PATHS_CHUNK % PM_ROWS == 0 && PATHS_CHUNK % PR_CAND == 0, "grid.y holds the path tiles");
+
+static void paths_free(bohip_paths* p) {
+    for (double** q : {&p->dX, &p->dOm, &p->dCf, &p->dXs, &p->dV, &p->df, &p->dg})
+        if (*q) { hipFree(*q); *q = nullptr; }
+    if (p->dpath_of) hipFree(p->dpath_of);
+    if (p->dpart) hipFree(p->dpart);
+    if (p->dbest) hipFree(p->dbest);
+    delete p;
+}
+static PathArgs paths_args(const bohip_paths* p) {
+    return PathArgs{p->dX, p->dOm, p->dCf, p->N, p->Npad, p->ldc, p->S, p->F, p->amp, p->beta};
+}
+static bool paths_use_mfma(const bohip_paths* p) { return p->S >= p->mfma_min; }
+static int64_t paths_tile(bool mfma) { return mfma ? PM_ROWS : PR_CAND; }
+
+// One launch over Rc candidates already on the device: values (nullable, leading dimension ldv) and, with dbest, the fold of the
+// chunk's tile records onto dbest (carry: onto what the earlier chunks left there).
+static int paths_eval_launch(bohip_paths* p, const double* dXs, int64_t Rc, int64_t j_off, double* dV, int64_t ldv, Best* dbest,
+                             bool carry, bool feat_only, bool mfma) {
+    hipStream_t st = p->g->stream;
+    const PathArgs a = paths_args(p);
+    const bool lo = fam_low(p->hp);
+    const int ntiles = (int)((Rc + paths_tile(mfma) - 1) / paths_tile(mfma));
+    Best* part = dbest ? p->dpart : nullptr;
+    if (mfma) {
+        const dim3 grid((unsigned)ntiles, (unsigned)((p->S + PM_PATHS - 1) / PM_PATHS));
+        LAUNCH_FAM(lo, k_path_mfma<true>, k_path_mfma<false>, grid, dim3(256), path_mfma_lds_bytes(p->d), st, a, p->hp, dXs, Rc, j_off,
+                   dV, ldv, part, ntiles, feat_only ? 1 : 0);
+    } else if (p->S == 1) {
+        LAUNCH_FAM(lo, (k_path_rows<1, true>), (k_path_rows<1, false>), dim3((unsigned)ntiles, 1), dim3(256), 0, st, a, p->hp, dXs, Rc,
+                   j_off, dV, ldv, part, ntiles, feat_only ? 1 : 0);
+    } else {
+        LAUNCH_FAM(lo, (k_path_rows<4, true>), (k_path_rows<4, false>), dim3((unsigned)ntiles, (unsigned)((p->S + 3) / 4)), dim3(256), 0,
+                   st, a, p->hp, dXs, Rc, j_off, dV, ldv, part, ntiles, feat_only ? 1 : 0);
+    }
+    if (dbest) hipLaunchKernelGGL(k_path_best, dim3((unsigned)p->S), dim3(64), 0, st, p->dpart, ntiles, dbest, carry ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int paths_draw_fill(bohip_paths* p, uint64_t seed) {
+    bohip_gp* g = p->g;
+    hipStream_t st = g->stream;
+    const int64_t N = p->N, S = p->S, M = p->M;
+    const int d = p->d;
+    HIPCHK(hipMalloc(&p->dX, (size_t)N * d * 8));
+    HIPCHK(hipMalloc(&p->dOm, (size_t)p->F * d * 8));
+    HIPCHK(hipMalloc(&p->dCf, (size_t)S * p->ldc * 8));
+    HIPCHK(hipMalloc(&p->dbest, (size_t)S * sizeof(Best)));
+    // right-hand sides and the two triangular products: [S][ldr] twice (k_trimv_stream reads whole chunks of 256 columns, masked by index)
+    const int64_t ldr = round_up(N, 256) + 256;
+    double *T0 = nullptr, *T1 = nullptr;
+    HIPCHK(hipMalloc(&T0, (size_t)S * ldr * 8));
+    if (hipMalloc(&T1, (size_t)S * ldr * 8) != hipSuccess) { hipFree(T0); return fail(BOHIP_E_HIP, "paths_draw: out of device memory"); }
+    int rc = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(p->dX, g->dX, (size_t)N * d * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(p->dCf, 0, (size_t)S * p->ldc * 8, st));
+        HIPCHK(hipMemsetAsync(T0, 0, (size_t)S * ldr * 8, st));
+        HIPCHK(hipMemsetAsync(T1, 0, (size_t)S * ldr * 8, st));
+        t_begin(g, "path_basis");
+        PathLen len;
+        for (int k = 0; k < DMAX; ++k) len.inv[k] = k < d ? std::exp(-g->loglen[kern_iso(g->kern) ? 0 : k]) : 0.0;
+        hipLaunchKernelGGL(k_path_omega, dim3((unsigned)((p->F + 255) / 256)), dim3(256), 0, st, seed, p->F, d, path_family_dof(p->hp.fam), len,
+                           p->dOm);
+        hipLaunchKernelGGL(k_path_w, dim3((unsigned)((M + 255) / 256), (unsigned)S), dim3(256), 0, st, seed, M, p->dCf, p->ldc, p->Npad);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        // r_s = Phi(X) w_s at the observations: the evaluation kernel itself, prior term only.  ALWAYS the MFMA form, so that the
+        // coefficients of path s do not depend on how many paths were drawn.
+        t_begin(g, "path_prior_at_X");
+        for (int64_t j0 = 0; j0 < N; j0 += PATHS_CHUNK) {
+            const int64_t Rc = std::min<int64_t>(PATHS_CHUNK, N - j0);
+            CHK(paths_eval_launch(p, p->dX + j0 * d, Rc, j0, T0 + j0, ldr, nullptr, false, true, true));
+        }
+        const double noise = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;
+        hipLaunchKernelGGL(k_path_rhs, dim3((unsigned)((N + 255) / 256), (unsigned)S), dim3(256), 0, st, seed, M, N, g->dy, g->beta,
+                           std::sqrt(noise), T0, ldr);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        // u_s = W'(W rhs_s): the streaming triangular products, 16 right-hand sides per pass over W
+        t_begin(g, "path_solve");
+        const int64_t nblk = (N + 7) / 8;
+        const unsigned wgs = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::max(device_cus(), 1), nblk));
+        const dim3 tg(wgs, (unsigned)((S + 15) / 16));
+        hipLaunchKernelGGL(k_trimv_stream<TRIMV_D>, tg, dim3(TRIMV_THREADS), trimv_lds_bytes(TRIMV_D), st, g->dW, g->ld, N, T0, ldr, (int)S,
+                           T1, ldr, 0, (const unsigned*)nullptr);
+        hipLaunchKernelGGL(k_trimv_stream<TRIMV_D>, tg, dim3(TRIMV_THREADS), trimv_lds_bytes(TRIMV_D), st, g->dWT, g->ld, N, T1, ldr, (int)S,
+                           T0, ldr, 1, (const unsigned*)nullptr);
+        hipLaunchKernelGGL(k_path_pack, dim3((unsigned)((N + 255) / 256), (unsigned)S), dim3(256), 0, st, T0, ldr, N, p->dCf, p->ldc);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }();
+    hipFree(T0);
+    hipFree(T1);
+    return rc;
+}
+
+int bohip_gp_paths_draw(bohip_gp* g, int64_t S, int64_t M, uint64_t seed, bohip_paths** out) {
+    auto done = [](int rc) { return rc; };
+    if (!out) return fail(BOHIP_E_ARG, "paths_draw: null output pointer");
+    *out = nullptr;
+    if (!g) return done(fail(BOHIP_E_ARG, "paths_draw: null handle"));
+    if (S < 1) return done(fail(BOHIP_E_ARG, "paths_draw: S must be at least 1"));
+    if (M < 2 || (M & 1) || M % 16 != 0) return done(fail(BOHIP_E_ARG, "paths_draw: M must be a positive multiple of 16"));
+    if (S > BOHIP_PATHS_S_MAX) return done(fail(BOHIP_E_UNSUPPORTED, "paths_draw: at most " + std::to_string(BOHIP_PATHS_S_MAX) + " paths per object"));
+    if (M > BOHIP_PATHS_M_MAX) return done(fail(BOHIP_E_UNSUPPORTED, "paths_draw: at most " + std::to_string(BOHIP_PATHS_M_MAX) + " features"));
+    if (g->n < 1) return done(fail(BOHIP_E_STATE, "paths_draw: the model has no observations"));
+    if (hipSetDevice(g->device) != hipSuccess) return done(fail(BOHIP_E_HIP, "paths_draw: hipSetDevice failed"));
+    t_reset(g);
+    int rc = one_time_kernel_setup();
+    if (rc == 0) rc = ensure_fresh(g);
+    if (rc != 0) return done(rc);
+    bohip_paths* p = new bohip_paths;
+    p->g = g;
+    p->S = S; p->M = M; p->F = (int)(M / 2); p->N = g->n; p->d = g->d;
+    p->Npad = round_up(p->N, KC);
+    p->ldc = p->Npad + M;                         // a multiple of 16 doubles = 128 B ...
+    if ((p->ldc / 16) % 2 == 0) p->ldc += 16;     // ... made an odd one (alloc_model's reason)
+    p->hp = make_hyper(g);
+    p->beta = g->beta;
+    p->amp = std::sqrt(p->hp.sigma2 / (double)p->F);
+    p->mfma_min = g_path_mfma_min;
+    if (const char* e = getenv("BOHIP_PATH_MFMA_MIN")) p->mfma_min = std::max(1, atoi(e));
+    rc = paths_draw_fill(p, seed);
+    t_collect(g);
+    if (rc != 0) { paths_free(p); return done(rc); }
+    *out = p;
+    return 0;
+}
+
+void bohip_paths_destroy(bohip_paths* p) {
+    if (!p) return;
+    hipSetDevice(p->g->device);
+    hipStreamSynchronize(p->g->stream);
+    paths_free(p);
+}
+
+int bohip_paths_dims(const bohip_paths* p, int64_t* S, int64_t* M, int64_t* N, int64_t* d) {
+    if (!p) return fail(BOHIP_E_ARG, "paths_dims: null object");
+    if (S) *S = p->S;
+    if (M) *M = p->M;
+    if (N) *N = p->N;
+    if (d) *d = p->d;
+    return 0;
+}
+
+int bohip_paths_coef(const bohip_paths* p, int64_t s, double* omega, double* w, double* u) {
+    if (!p) return fail(BOHIP_E_ARG, "paths_coef: null object");
+    if (s < 0 || s >= p->S) return fail(BOHIP_E_ARG, "paths_coef: no such path");
+    HIPCHK(hipSetDevice(p->g->device));
+    hipStream_t st = p->g->stream;
+    if (omega) HIPCHK(hipMemcpyAsync(omega, p->dOm, (size_t)p->F * p->d * 8, hipMemcpyDeviceToHost, st));
+    if (w) HIPCHK(hipMemcpyAsync(w, p->dCf + s * p->ldc + p->Npad, (size_t)p->M * 8, hipMemcpyDeviceToHost, st));
+    if (u) HIPCHK(hipMemcpyAsync(u, p->dCf + s * p->ldc, (size_t)p->N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int bohip_paths_eval(bohip_paths* p, const double* Xs, int64_t R, double* values, bohip_best* best) {
+    if (!p || !Xs) return fail(BOHIP_E_ARG, "paths_eval: null argument");
+    if (R < 1) return fail(BOHIP_E_ARG, "paths_eval: R must be at least 1");
+    bohip_gp* g = p->g;
+    HIPCHK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    const bool mfma = paths_use_mfma(p);
+    // with values the chunk also bounds the S x chunk staging block (128 MiB)
+    int64_t chunk = PATHS_CHUNK;
+    if (values) chunk = std::max<int64_t>(PM_ROWS, std::min<int64_t>(PATHS_CHUNK, ((int64_t)1 << 24) / p->S / PM_ROWS * PM_ROWS));
+    chunk = std::min<int64_t>(chunk, round_up(R, PM_ROWS));
+    if (p->xs_cap < chunk) {
+        if (p->dXs) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dXs)); p->dXs = nullptr; p->xs_cap = 0; }
+        HIPCHK(hipMalloc(&p->dXs, (size_t)chunk * p->d * 8));
+        p->xs_cap = chunk;
+    }
+    const size_t vneed = values ? (size_t)p->S * chunk : 0;
+    if (p->v_cap < vneed) {
+        if (p->dV) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dV)); p->dV = nullptr; p->v_cap = 0; }
+        HIPCHK(hipMalloc(&p->dV, vneed * 8));
+        p->v_cap = vneed;
+    }
+    const size_t pneed = best ? (size_t)p->S * ((chunk + paths_tile(mfma) - 1) / paths_tile(mfma)) : 0;
+    if (p->part_cap < pneed) {
+        if (p->dpart) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dpart)); p->dpart = nullptr; p->part_cap = 0; }
+        HIPCHK(hipMalloc(&p->dpart, pneed * sizeof(Best)));
+        p->part_cap = pneed;
+    }
+    t_reset(g);
+    t_begin(g, "path_eval");
+    for (int64_t j0 = 0; j0 < R; j0 += chunk) {
+        const int64_t Rc = std::min<int64_t>(chunk, R - j0);
+        HIPCHK(hipMemcpyAsync(p->dXs, Xs + j0 * p->d, (size_t)Rc * p->d * 8, hipMemcpyHostToDevice, st));
+        CHK(paths_eval_launch(p, p->dXs, Rc, j0, values ? p->dV : nullptr, chunk, best ? p->dbest : nullptr, j0 > 0, false, mfma));
+        if (values)
+            HIPCHK(hipMemcpy2DAsync(values + j0, (size_t)R * 8, p->dV, (size_t)chunk * 8, (size_t)Rc * 8, (size_t)p->S, hipMemcpyDeviceToHost, st));
+    }
+    t_end(g);
+    if (best) HIPCHK(hipMemcpyAsync(best, p->dbest, (size_t)p->S * sizeof(Best), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_paths_eval_grad(bohip_paths* p, const double* Xs, int64_t R, const int64_t* path_of, double* f, double* grad) {
+    if (!p || !Xs || !f || !grad) return fail(BOHIP_E_ARG, "paths_eval_grad: null argument");
+    if (R < 1) return fail(BOHIP_E_ARG, "paths_eval_grad: R must be at least 1");
+    if (path_of)
+        for (int64_t j = 0; j < R; ++j)
+            if (path_of[j] < 0 || path_of[j] >= p->S) return fail(BOHIP_E_ARG, "paths_eval_grad: path_of[" + std::to_string(j) + "] names no path");
+    bohip_gp* g = p->g;
+    HIPCHK(hipSetDevice(g->device));
+    hipStream_t st = g->stream;
+    const int64_t chunk = std::min<int64_t>(PATHS_GRAD_CHUNK, R);
+    if (p->g_cap < chunk) {
+        HIPCHK(hipStreamSynchronize(st));
+        for (double** q : {&p->df, &p->dg})
+            if (*q) { HIPCHK(hipFree(*q)); *q = nullptr; }
+        if (p->dpath_of) { HIPCHK(hipFree(p->dpath_of)); p->dpath_of = nullptr; }
+        p->g_cap = 0;
+        HIPCHK(hipMalloc(&p->df, (size_t)chunk * 8));
+        HIPCHK(hipMalloc(&p->dg, (size_t)chunk * p->d * 8));
+        HIPCHK(hipMalloc(&p->dpath_of, (size_t)chunk * 8));
+        p->g_cap = chunk;
+    }
+    if (p->xs_cap < chunk) {
+        if (p->dXs) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dXs)); p->dXs = nullptr; p->xs_cap = 0; }
+        HIPCHK(hipMalloc(&p->dXs, (size_t)chunk * p->d * 8));
+        p->xs_cap = chunk;
+    }
+    const PathArgs a = paths_args(p);
+    const bool lo = fam_low(p->hp);
+    t_reset(g);
+    t_begin(g, "path_grad");
+    for (int64_t j0 = 0; j0 < R; j0 += chunk) {
+        const int64_t Rc = std::min<int64_t>(chunk, R - j0);
+        HIPCHK(hipMemcpyAsync(p->dXs, Xs + j0 * p->d, (size_t)Rc * p->d * 8, hipMemcpyHostToDevice, st));
+        if (path_of) HIPCHK(hipMemcpyAsync(p->dpath_of, path_of + j0, (size_t)Rc * 8, hipMemcpyHostToDevice, st));
+        LAUNCH_FAM(lo, k_path_grad<true>, k_path_grad<false>, dim3((unsigned)Rc), dim3(256), 0, st, a, p->hp, p->dXs, Rc,
+                   path_of ? p->dpath_of : (const int64_t*)nullptr, p->df, p->dg);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(f + j0, p->df, (size_t)Rc * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(grad + j0 * p->d, p->dg, (size_t)Rc * p->d * 8, hipMemcpyDeviceToHost, st));
+    }
+    t_end(g);
+    HIPCHK(hipStreamSynchronize(st));
     t_collect(g);
     return 0;
 }

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 
 import numpy as np
 
@@ -122,6 +123,8 @@ class ElasticGPE:
     def close(self):
         """Release the device model now (idempotent; also run for every live model at interpreter exit)."""
         h, self._h = getattr(self, "_h", None), None
+        for p in list(getattr(self, "_paths", ())):               # paths objects borrow the handle's stream: they go first
+            p.close()
         if h:
             self._lib.bohip_gp_destroy(h)
 
@@ -366,6 +369,17 @@ class ElasticGPE:
         the maximiser.  Only what is asked for crosses to the host.  Returns a JointSample."""
         return _sample_joint(self._lib, self._h, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
 
+    def draw_paths(self, S=1, M=2048, seed=0):
+        """S posterior SAMPLE PATHS (bohip_gp_paths_draw): draws that are functions, f_s(x) = beta + sum_m w_sm phi_m(x) +
+        sum_j u_sj k(x, X_j) with M random features for the prior term and the exact data term (pathwise conditioning).  The result
+        can be evaluated and differentiated anywhere afterwards and does not follow later changes of the model.  Close it (or use it
+        as a context manager) before the model is closed.  Returns a PosteriorPaths."""
+        p = PosteriorPaths(self._lib, self._h, self.dim, S, M, seed)
+        if not hasattr(self, "_paths"):
+            self._paths = weakref.WeakSet()
+        self._paths.add(p)
+        return p
+
     # -- introspection ------------------------------------------------------------------------------
     def factor(self):
         n = self.nobs
@@ -430,6 +444,76 @@ def _sample_joint(lib, handle, xs, S, seed, jitter, max_tries, want_samples, wan
     vals = np.array([out[i].val for i in range(S)])
     idx = np.array([out[i].idx for i in range(S)], dtype=np.int64)
     return JointSample(samples, vals, idx, mu, jit.value, tries.value, factor)
+
+
+class PosteriorPaths:
+    """S sample paths of one model's posterior on the device (bohip_paths, include/bohip_paths.h).  Self-contained: it holds its own copy
+    of the observations, hyper-parameters, frequencies and coefficients.
+      eval(xs, want_values=True) -> (values S x R or None, best_val[S], best_idx[S])   arg-max per path under score's rule
+      eval_grad(xs, path_of=None) -> (f[R], grad d x R)   point j on path path_of[j] (None: path 0)
+      coef(s) -> (omega F x d, w[M], u[N])"""
+
+    def __init__(self, lib, handle, dim, S, M, seed):
+        self._lib, self.dim, self._p = lib, int(dim), None
+        p = C.c_void_p()
+        check(lib.bohip_gp_paths_draw(handle, int(S), int(M), int(seed), C.byref(p)))
+        self._p = p
+        s, m, n, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib.bohip_paths_dims(self._p, C.byref(s), C.byref(m), C.byref(n), C.byref(d)))
+        self.S, self.M, self.N = s.value, m.value, n.value
+        _lib.register(self)
+
+    def _handle(self):
+        if not self._p:
+            raise _lib.BohipError(_lib.E_STATE, "the paths object is closed")
+        return self._p
+
+    def close(self):
+        """Release the device object now (idempotent)."""
+        p, self._p = getattr(self, "_p", None), None
+        if p:
+            self._lib.bohip_paths_destroy(p)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def eval(self, xs, want_values=True):
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        vals = np.empty((self.S, R)) if want_values else None
+        out = (Best * self.S)()
+        check(self._lib.bohip_paths_eval(self._handle(), _ptr(xs), R, _ptr(vals) if want_values else None, out))
+        rec = np.frombuffer(out, dtype=[("val", "f8"), ("idx", "i8")])
+        return vals, rec["val"].copy(), rec["idx"].copy()
+
+    def eval_grad(self, xs, path_of=None):
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        f = np.empty(R)
+        grad = np.empty((self.dim, R), order="F")
+        po = None
+        if path_of is not None:
+            po = np.ascontiguousarray(np.broadcast_to(np.asarray(path_of, dtype=np.int64), (R,)))
+        check(self._lib.bohip_paths_eval_grad(self._handle(), _ptr(xs), R,
+                                              po.ctypes.data_as(C.POINTER(C.c_int64)) if po is not None else None, _ptr(f), _ptr(grad)))
+        return f, grad
+
+    def coef(self, s):
+        om = np.empty((self.M // 2, self.dim))
+        w = np.empty(self.M)
+        u = np.empty(self.N)
+        check(self._lib.bohip_paths_coef(self._handle(), int(s), _ptr(om), _ptr(w), _ptr(u)))
+        return om, w, u
 
 
 # ---- the generic functions of reference src/models/gp.jl ----------------------------------------

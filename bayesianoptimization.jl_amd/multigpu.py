@@ -49,6 +49,8 @@ class MultiGPE:
     def close(self):
         """Release every replica, the communicators and the worker threads now (idempotent; run at interpreter exit too)."""
         h, self._h = getattr(self, "_h", None), None
+        for p in list(getattr(self, "_paths", ())):               # paths objects borrow a replica's stream: they go first
+            p.close()
         if h:
             self._lib.bohip_mgp_destroy(h)
 
@@ -175,6 +177,19 @@ class MultiGPE:
 
         g = self._lib.bohip_mgp_handle(self._h, 0)
         return _sample_joint(self._lib, g, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
+
+    def draw_paths(self, S=1, M=2048, seed=0):
+        """Posterior sample paths (ElasticGPE.draw_paths, bohip_gp_paths_draw) on the FIRST replica, as sample_joint: the object is
+        self-contained and lives on that device.  Close it before the model."""
+        import weakref
+
+        from .model import PosteriorPaths
+
+        p = PosteriorPaths(self._lib, self._lib.bohip_mgp_handle(self._h, 0), self.dim, S, M, seed)
+        if not hasattr(self, "_paths"):
+            self._paths = weakref.WeakSet()
+        self._paths.add(p)
+        return p
 
     def replica_factor(self, i):
         """Cholesky factor held by the i-th device (tests: every replica is the same model)."""

@@ -204,6 +204,9 @@ int bohip_gp_sample_joint(bohip_gp *gp, const double *Xs, int64_t R, int64_t S, 
                           int max_tries, double *mu, double *chol, double *samples, bohip_best *best,
                           double *jitter_used, int *tries_used);
 
+/* ---- posterior SAMPLE PATHS (draws of the posterior that are functions, evaluated anywhere after the draw): a separate object
+ * with its own header, include/bohip_paths.h (bohip_paths, bohip_gp_paths_draw, bohip_paths_eval ...), in the same library.   */
+
 /* ---- :GN_DIRECT_L, the reference's default search for ThompsonSamplingSimple (reference src/acquisition.jl:7-9: restarts 1,
  * maxeval 2000; nlopt_setup :20-38 hands the acquisition to NLopt) and for any acquisition the caller selects it for.
  * NLopt is not vendored in the reference; csrc/direct_l.h restates DIRECT-L with the rules of NLopt's cdirect.c for this variant
