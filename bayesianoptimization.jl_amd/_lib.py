@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -24,6 +24,7 @@ MGP_INFO_DEVICES, MGP_INFO_SHARDS, MGP_INFO_EXCHANGES, MGP_INFO_RCCL_VERSION, MG
 UNIQUE_ID_BYTES = 128
 FANTASY_BELIEVER, FANTASY_CONST, BATCH_RAISE_TAU = 0, 1, 1   # bohip_gp_select_batch
 PATHS_S_MAX, PATHS_M_MAX = 4096, 16384                       # bohip_gp_paths_draw
+FIT_NMAX = 512                                               # bohip_gp_mll_grad_batch
 
 
 class Best(C.Structure):
@@ -132,6 +133,12 @@ PATHS_SIGNATURES = {
     "bohip_paths_coef": (C.c_int, [_paths, C.c_int64, _dp, _dp, _dp]),
 }
 
+# every symbol include/bohip_fit.h declares (the marginal likelihood and its gradient at H settings in one launch)
+FIT_SIGNATURES = {
+    "bohip_gp_mll_batch_dims": (C.c_int, [_gp, _i64p, _i64p]),
+    "bohip_gp_mll_grad_batch": (C.c_int, [_gp, C.c_int64, _dp, _dp, _dp, _i64p]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -178,7 +185,7 @@ def _one_hip_runtime():
 
 
 def load():
-    """dlopen libbohip.so and bind every declared symbol (both headers).  Raises if the library was not built."""
+    """dlopen libbohip.so and bind every declared symbol (all headers).  Raises if the library was not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -186,7 +193,7 @@ def load():
         raise BohipError(E_NODEVICE, f"{LIB_PATH} not built (run __graft_entry__.build()); there is no CPU fallback")
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

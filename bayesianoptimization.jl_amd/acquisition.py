@@ -203,7 +203,9 @@ def _batched_lbfgs_ascent(fg, X0, lb, ub, maxeval, ftol_rel=1e-10, xtol_abs=1e-1
         if S:
             step = np.ones(R)
         else:                                                     # the FIRST step (kernels_ascent.hip asc_direction_one): L-BFGS-B's unit step to P(x + g),
-            step = np.maximum(1.0, 0.1 * np.min(ub - lb + 1e-300) / np.maximum(np.sqrt(np.einsum("dr,dr->r", D, D)), 1e-12))   # but never shorter than a tenth of the box
+            span = (ub - lb)[np.isfinite(ub - lb)]                # (a box without a finite side -- the MAP fit's log-parameters -- keeps the unit step)
+            box = np.min(span + 1e-300) if span.size else 0.0
+            step = np.maximum(1.0, 0.1 * box / np.maximum(np.sqrt(np.einsum("dr,dr->r", D, D)), 1e-12))   # but never shorter than a tenth of the box
         step = np.where(active & (slope > 0), step, 0.0)
         accepted = ~active | ~(slope > 0)
         Xn, fn, Gn = X.copy(), f.copy(), G.copy()

@@ -9,11 +9,11 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, ThompsonSamplingSimple, acquire_batch, acquire_max,
-                          acquire_thompson_batch, defaultoptions, setparams_)
+from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
+                          acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ElasticGPE, Mat52Ard, MeanConst, update_
-from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, step_)
+from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
 
 
 class Sense(enum.IntEnum):                                    # :56
@@ -43,7 +43,12 @@ class MAPGPOptimizer(ModelOptimizer):
     """src/models/gp.jl:20-52: MAP hyper-parameter fit every ``every`` calls.  Each objective evaluation is a
     full device rebuild (kernel matrix + Cholesky + alpha) plus the analytic gradient 1/2 tr((aa' - cK^-1) dcK)
     formed on the device (bohip_gp_mll_grad); the bounded L-BFGS search itself stays on the host, like the
-    reference's NLopt :LD_LBFGS driving GP.update_target_and_dtarget!."""
+    reference's NLopt :LD_LBFGS driving GP.update_target_and_dtarget!.
+
+    ``restarts = k > 1`` (an extension: the reference runs ONE search from the current parameters) starts k searches -- the current
+    parameters and k - 1 Latin-hypercube points of the bounds, a side without a finite bound replaced by current -/+ ``startwidth``
+    (log-parameters) -- and advances them in lock-step, one batched device evaluation of all k per step (bohip_gp_mll_grad_batch);
+    ``maxeval`` then counts lock-step evaluations, i.e. per start.  ``seed`` seeds the starts.  The best end point wins, the first on ties."""
 
     def __init__(self, every=10, **kwargs):
         self.i = 0
@@ -53,7 +58,7 @@ class MAPGPOptimizer(ModelOptimizer):
     @staticmethod
     def defaultoptions():                                     # :48-52
         return dict(domean=True, kern=True, noise=True, lik=True, meanbounds=None, kernbounds=None, noisebounds=None,
-                    likbounds=None, method="LD_LBFGS", maxeval=500)
+                    likbounds=None, method="LD_LBFGS", maxeval=500, restarts=1, startwidth=3.0, seed=None)
 
 
 def optimizemodel_(o, model):                                 # :42-47 and NoModelOptimizer :49
@@ -113,12 +118,80 @@ def _map_fit(model, opt):                                     # :54-77
             g += dk.tolist()
         return -m, -np.asarray(g, dtype=float)
 
+    if int(opt.get("restarts", 1)) > 1:
+        fg = _fit_objective(model, opt, nk, apply, x0.size, int(opt["restarts"]))
+        val, best, _ = _multistart_map(fg, x0, np.asarray(lo, float), np.asarray(hi, float), int(opt["restarts"]), int(opt["maxeval"]),
+                                       np.random.default_rng(opt.get("seed")), float(opt.get("startwidth", 3.0)))
+        apply(best if np.isfinite(val) else x0)
+        model.fit_()
+        return val, best
     res = minimize(negmll, x0, jac=True, method="L-BFGS-B", bounds=list(zip(lo, hi)),
                    options=dict(maxfun=int(opt["maxeval"])))
     best = res.x if np.isfinite(res.fun) and res.fun < 1e299 else x0
     apply(best)
     model.fit_()
     return -res.fun, best
+
+
+def _multistart_map(fg_batch, x0, lo, hi, restarts, maxeval, rng, startwidth=3.0):
+    """``restarts`` bounded L-BFGS ascents of the log marginal likelihood in lock-step.  fg_batch(X[p, R]) -> (mll[R], G[p, R]) is ONE
+    evaluation of all columns (a failed one: -inf, from which the ascent backtracks).  Start 0 is x0 clipped to the bounds, the others
+    a Latin hypercube of the bounds (an infinite side: x0 -/+ startwidth).  Returns (best mll, its x, the end value of every start)."""
+    x0 = np.clip(np.asarray(x0, float), lo, hi)
+    slo = np.where(np.isfinite(lo), lo, x0 - startwidth)
+    shi = np.where(np.isfinite(hi), hi, x0 + startwidth)
+    starts = np.concatenate([x0.reshape(-1, 1), latin_hypercube_sampling(slo, shi, restarts - 1, rng)], axis=1)
+    f, X = _batched_lbfgs_ascent(fg_batch, starts, lo, hi, maxeval)
+    f = np.where(np.isfinite(f), f, -np.inf)
+    w = int(np.argmax(f))                                     # the first of equal bests
+    return float(f[w]), X[:, w].copy(), f
+
+
+# When the batched call runs (n observations, H settings): H at least the entry of the first row with n <= its size.
+# PROVISIONAL: not from a measured table yet (DESIGN.md 6i) -- one mll_grad costs 0.27 ... 0.39 ms up to N = 500 (DESIGN.md 8), the kernel
+# is estimated at ~0.3 ms at N = 256 and ~2 ms at N = 512 whatever H.  tools/time_mll_batch.py measures both; its table replaces this.
+_FIT_BATCH_MIN_H = ((64, 2), (128, 2), (256, 2), (512, 8))
+
+
+def _fit_batched(n, H, nmax):
+    if n > nmax:
+        return False
+    for size, hmin in _FIT_BATCH_MIN_H:
+        if n <= size:
+            return H >= hmin
+    return False
+
+
+def _fit_objective(model, opt, nk, apply, p, H):
+    """fg_batch of _multistart_map for a model: the free parameters of the fit sit in the optimisation vector, the fixed ones are
+    constants of Theta's rows.  A device model of a size the batched call takes, and wins at, evaluates all columns in one launch;
+    otherwise (or for a model without the call) every column is a set_params_ + mll_grad, at any N."""
+    mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
+    base = np.concatenate([[model.logNoise, model.mean.beta if isinstance(model.mean, MeanConst) else 0.0], model.kernel.ll,
+                           [model.kernel.lsigma]])
+    idx = ([0] if opt["noise"] else []) + ([1] if mean_free else []) + (list(range(2, 2 + nk)) if opt["kern"] else [])
+    assert len(idx) == p
+    batched = hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
+
+    def fg_batched(X):
+        Theta = np.tile(base, (X.shape[1], 1))
+        Theta[:, idx] = X.T
+        mll, G, piv = model.mll_grad_batch(Theta)
+        return np.where(piv == 0, mll, -np.inf), np.ascontiguousarray(G[:, idx].T)
+
+    def fg_loop(X):
+        f, G = np.full(X.shape[1], -np.inf), np.zeros(X.shape)
+        for r in range(X.shape[1]):
+            apply(X[:, r])
+            try:
+                m, dn, dm, dk = model.mll_grad()
+            except NotPositiveDefinite:
+                continue
+            full = np.concatenate([[dn, dm], dk])
+            f[r], G[:, r] = m, full[idx]
+        return f, G
+
+    return fg_batched if batched else fg_loop
 
 
 class BOpt:

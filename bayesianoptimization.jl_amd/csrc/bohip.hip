@@ -16,6 +16,7 @@
 // when the GPU is unavailable.
 #include "../../include/bohip.h"
 #include "../../include/bohip_paths.h"
+#include "../../include/bohip_fit.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -24,6 +25,7 @@
 #include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_ascent.hip"
+#include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
 #include "direct_l.h"          // host bookkeeping of :GN_DIRECT_L (ask / tell)
 
@@ -165,6 +167,10 @@ struct bohip_gp {
     int64_t grad_cap = 0;
     Best* dthompson = nullptr; // S arg-max records
     double* ddmll_parts = nullptr;  // per-block partial sums of the marginal-likelihood gradient
+    // batched marginal likelihood (bohip_gp_mll_grad_batch): the slabs of the settings of one launch, and [theta | mll | grad | pivot | stamps]
+    double* fit_ws = nullptr;
+    char* fit_io = nullptr;
+    size_t fit_ws_bytes = 0, fit_io_bytes = 0;
     double *dVV = nullptr, *dcov = nullptr;  // [Rp][Rp] V'V (lower tiles) and the full posterior covariance
     int64_t cov_cap = 0;
     // joint sampler (bohip_gp_sample_joint): a factor workspace the model does not own -- matrix, panel scratch, the 128 x 128
@@ -2775,6 +2781,8 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->asc_best) hipFree(g->asc_best);
     if (g->dthompson) hipFree(g->dthompson);
     if (g->ddmll_parts) hipFree(g->ddmll_parts);
+    if (g->fit_ws) hipFree(g->fit_ws);
+    if (g->fit_io) hipFree(g->fit_io);
     if (g->dVV) hipFree(g->dVV);
     if (g->dcov) hipFree(g->dcov);
     for (double** p : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT, &g->sjF, &g->sj_scal})
@@ -2977,6 +2985,105 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = h[0]; *d_lognoise = h[1]; *d_mean = h[2];
     for (int k = 0; k <= nl; ++k) d_kern[k] = h[3 + k];
+    return 0;
+}
+
+// ---- batched marginal likelihood (include/bohip_fit.h, kernels_fit.hip) ---------------------------------------------------------
+static constexpr size_t FIT_WS_CAP_BYTES = (size_t)1 << 30;
+extern "C++" {
+template <int DT>
+static int fit_launch(bohip_gp* g, const FitArgs& a, int64_t Hc, bool lo) {
+    const size_t lds = fit_lds_bytes(a.M, DT);
+    // the > 64 KB dynamic-LDS opt-in is a per-device function attribute
+    static bool done_dev[64] = {false};
+    if (!done_dev[g->device & 63]) {
+        const int most = (int)fit_lds_bytes(BOHIP_FIT_NMAX, DT);
+        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        done_dev[g->device & 63] = true;
+    }
+    LAUNCH_FAM(lo, (k_mll_batch<DT, true>), (k_mll_batch<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), lds, g->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}   // extern "C++"
+
+int bohip_gp_mll_batch_dims(bohip_gp* g, int64_t* P, int64_t* nmax) {
+    if (!g) return fail(BOHIP_E_ARG, "null handle");
+    if (P) *P = 2 + (kern_iso(g->kern) ? 2 : g->d + 1);
+    if (nmax) *nmax = BOHIP_FIT_NMAX;
+    return 0;
+}
+
+int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double* mll, double* grad, int64_t* pivot) {
+    if (!g || !theta || !mll) return fail(BOHIP_E_ARG, "null argument");
+    if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "no observations");
+    if (g->n > BOHIP_FIT_NMAX)
+        return fail(BOHIP_E_UNSUPPORTED, "the batched marginal likelihood takes at most " + std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " +
+                                             std::to_string(g->n) + " (bohip_gp_mll_grad has no limit)");
+    HIPCHK(hipSetDevice(g->device));
+    // the observations as the device holds them: the call reads dX / dy and nothing else of the model, and never refits
+    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
+    if (g->mirror_dirty) {
+        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        g->mirror_dirty = false;
+    }
+    const int iso = kern_iso(g->kern), P = 2 + (iso ? 2 : g->d + 1);
+    const int M = (int)round_up(g->n, FIT_NB), ld = M + 8;
+    const size_t slab = (size_t)(2 * M + 1) * ld;
+    size_t cap = FIT_WS_CAP_BYTES;
+    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
+    const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(H, (int64_t)(cap / (slab * 8))));
+    if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {
+        if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
+        g->fit_ws = nullptr; g->fit_ws_bytes = 0;
+        HIPCHK(hipMalloc(&g->fit_ws, (size_t)Hc * slab * 8));
+        g->fit_ws_bytes = (size_t)Hc * slab * 8;
+    }
+    const size_t io_bytes = (size_t)H * (2 * P + 2) * 8 + FIT_STAGES * 8;
+    if (g->fit_io_bytes < io_bytes) {
+        if (g->fit_io) HIPCHK(hipFree(g->fit_io));
+        g->fit_io = nullptr; g->fit_io_bytes = 0;
+        HIPCHK(hipMalloc(&g->fit_io, io_bytes));
+        g->fit_io_bytes = io_bytes;
+    }
+    double* d_theta = reinterpret_cast<double*>(g->fit_io);
+    double* d_mll = d_theta + (size_t)H * P;
+    double* d_grad = d_mll + H;
+    long long* d_pivot = reinterpret_cast<long long*>(d_grad + (size_t)H * P);
+    unsigned long long* d_stamps = reinterpret_cast<unsigned long long*>(d_pivot + H);
+    const bool trace = getenv("BOHIP_FIT_TRACE") != nullptr;   // tools: the stage times of the first workgroup on stderr
+    HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
+    const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
+    for (int64_t h0 = 0; h0 < H; h0 += Hc) {
+        FitArgs a{};
+        a.X = g->dX; a.y = g->dy; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.mll = d_mll + h0;
+        a.grad = grad ? d_grad + (size_t)h0 * P : nullptr; a.pivot = d_pivot + h0;
+        a.stamps = (trace && h0 == 0) ? d_stamps : nullptr;
+        a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = g->d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
+        const int64_t hc = std::min(Hc, H - h0);
+        if (g->d <= 2) CHK(fit_launch<2>(g, a, hc, lo)); else if (g->d <= 4) CHK(fit_launch<4>(g, a, hc, lo));
+        else if (g->d <= 8) CHK(fit_launch<8>(g, a, hc, lo)); else if (g->d <= 16) CHK(fit_launch<16>(g, a, hc, lo));
+        else if (g->d <= 32) CHK(fit_launch<32>(g, a, hc, lo)); else CHK(fit_launch<64>(g, a, hc, lo));
+    }
+    std::vector<long long> hpiv;
+    HIPCHK(hipMemcpyAsync(mll, d_mll, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
+    if (grad) HIPCHK(hipMemcpyAsync(grad, d_grad, (size_t)H * P * 8, hipMemcpyDeviceToHost, g->stream));
+    if (pivot) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "pivot words");
+        HIPCHK(hipMemcpyAsync(pivot, d_pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
+    }
+    unsigned long long st[FIT_STAGES] = {0};
+    if (trace) HIPCHK(hipMemcpyAsync(st, d_stamps, sizeof(st), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (trace) {   // wall_clock64 ticks at 100 MHz; a stage that did not run (value only, failed row) keeps its old stamp
+        auto us = [&](int i) { return st[i] >= st[i - 1] ? (double)(st[i] - st[i - 1]) * 0.01 : 0.0; };
+        std::fprintf(stderr, "bohip fit stages N=%lld d=%d H=%lld us: build %.1f chol %.1f value %.1f inverse %.1f grad %.1f\n", (long long)g->n, g->d,
+                     (long long)H, us(1), us(2), us(3), grad ? us(4) : 0.0, grad ? us(5) : 0.0);
+    }
     return 0;
 }
 

@@ -207,6 +207,19 @@ class ElasticGPE:
         check(self._lib.bohip_gp_mll_grad(self._h, C.byref(m), C.byref(dn), C.byref(dm), _ptr(dk)))
         return m.value, dn.value, dm.value, dk
 
+    def mll_batch_dims(self):
+        """(P, nmax): the row length of mll_grad_batch's Theta and the largest model its batched form takes."""
+        P, nmax = C.c_int64(), C.c_int64()
+        check(self._lib.bohip_gp_mll_batch_dims(self._h, C.byref(P), C.byref(nmax)))
+        return int(P.value), int(nmax.value)
+
+    def mll_grad_batch(self, Theta, want_grad=True):
+        """The log marginal likelihood, and its gradient, at the H rows of Theta in ONE launch (bohip_gp_mll_grad_batch):
+        row = [logNoise, mean, ll..., lsigma], GP.get_params order.  Returns (mll[H], G[H, P] or None, pivot[H]); a row whose
+        factorisation fails has pivot > 0, mll = -inf and a zero gradient.  The model itself is neither read (beyond its
+        observations) nor changed."""
+        return _mll_grad_batch(self._lib, self._h, Theta, want_grad)
+
     # -- predict_f / scoring ------------------------------------------------------------------------
     def predict_f(self, xs):
         xs = _cols(xs, self.dim)
@@ -415,6 +428,21 @@ class ElasticGPE:
         return (f"ElasticGPE(dim={self.dim}, nobs={self.nobs}, kernel={self.kernel.kern}"
                 f"(ll={self.kernel.ll.tolist()}, lσ={self.kernel.lsigma}), mean β={self.mean.beta}, "
                 f"logNoise={self.logNoise}) [device-resident, libbohip]")
+
+
+def _mll_grad_batch(lib, h, Theta, want_grad):
+    P, nmax = C.c_int64(), C.c_int64()
+    check(lib.bohip_gp_mll_batch_dims(h, C.byref(P), C.byref(nmax)))
+    Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
+    if Theta.shape[1] != P.value:
+        raise ValueError(f"Theta must have {P.value} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
+    H = Theta.shape[0]
+    mll = np.empty(H)
+    G = np.empty((H, P.value)) if want_grad else None
+    pivot = np.zeros(H, dtype=np.int64)
+    check(lib.bohip_gp_mll_grad_batch(h, H, _ptr(Theta), _ptr(mll), _ptr(G) if want_grad else None,
+                                      pivot.ctypes.data_as(C.POINTER(C.c_int64))))
+    return mll, G, pivot
 
 
 class JointSample:

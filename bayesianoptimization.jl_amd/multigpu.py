@@ -178,6 +178,17 @@ class MultiGPE:
         g = self._lib.bohip_mgp_handle(self._h, 0)
         return _sample_joint(self._lib, g, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
 
+    def mll_batch_dims(self):
+        P, nmax = C.c_int64(), C.c_int64()
+        check(self._lib.bohip_gp_mll_batch_dims(self._lib.bohip_mgp_handle(self._h, 0), C.byref(P), C.byref(nmax)))
+        return int(P.value), int(nmax.value)
+
+    def mll_grad_batch(self, Theta, want_grad=True):
+        """ElasticGPE.mll_grad_batch on the FIRST replica, as draw_paths: every device holds the whole model."""
+        from .model import _mll_grad_batch
+
+        return _mll_grad_batch(self._lib, self._lib.bohip_mgp_handle(self._h, 0), Theta, want_grad)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """Posterior sample paths (ElasticGPE.draw_paths, bohip_gp_paths_draw) on the FIRST replica, as sample_joint: the object is
         self-contained and lives on that device.  Close it before the model."""

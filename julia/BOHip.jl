@@ -345,6 +345,7 @@ function sample_joint(m::AbstractBOHipModel, X::AbstractMatrix, S::Integer; seed
     F, map(b -> b.val, first(best, S)), map(b -> Int(b.idx) + 1, first(best, S)), μ, jused[], Int(tused[]), factor ? permutedims(Ct) : nothing
 end
 include("BOHipPaths.jl")   # posterior sample paths (include/bohip_paths.h): draw_paths, paths_eval, paths_eval_grad, paths_coef
+include("BOHipFit.jl")     # batched marginal likelihood (include/bohip_fit.h): mll_batch_dims, mll_grad_batch
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
