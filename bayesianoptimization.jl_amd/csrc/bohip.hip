@@ -121,7 +121,7 @@ struct bohip_gp {
     Best* dfz_best = nullptr;      // [tiles] per-tile arg-max records
     int64_t fz_cap = 0;
     bool fz_dirty = false;         // a fused call failed between its launches: clear the counters before the next one
-    // pruned arg-max (pruned_pass): ONE allocation [packed K*' rows | q2 | mu2 | bounds | lists, ranks | counters, record | pieces]
+    // pruned arg-max (pruned_pass): ONE allocation [packed K*' rows | q2 | mu2 | bounds | lists, marks | counters, record | k_kstar's partials | pieces]
     char* dpr = nullptr;
     size_t pr_bytes = 0;
     std::vector<int> hpr_pieces;
@@ -2003,14 +2003,20 @@ static int ensure_xs(bohip_gp* g, int64_t R) {
     return 0;
 }
 
+// kp (the pruned pass): the kernel also leaves the per-wave partial sums of alpha_j K*'_j and of its absolute value (always 16
+// candidates per block: the halving reduction is written for 16)
 template <int DT>
-static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp) {
+static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp, const KstarParts* kp) {
     // 16 candidates per block: N/256 x R/16 blocks keep >= 8 waves per SIMD in flight (latency-bound loop); a handful of candidates:
     // two per block (ten in a row on 12 workgroups were a serial chain of ten `exp`s per thread)
-    const int rb = r1 - r0 <= 32 ? 2 : 16;
+    const int rb = r1 - r0 <= 32 && !kp ? 2 : 16;
     dim3 grid((Npad + 255) / 256, (r1 - r0 + rb - 1) / rb);
-    LAUNCH_FAM(fam_low(hp), (k_kstar<DT, true>), (k_kstar<DT, false>), grid, dim3(256), 0, g->stream, g->dX, g->n, Npad, dXs, r0, r1, hp,
-               g->dKsT, g->ld, rb);
+    if (kp)
+        LAUNCH_FAM(fam_low(hp), (k_kstar<DT, true, true>), (k_kstar<DT, false, true>), grid, dim3(256), 0, g->stream, g->dX, g->n, Npad, dXs,
+                   r0, r1, hp, g->dKsT, g->ld, rb, *kp);
+    else
+        LAUNCH_FAM(fam_low(hp), (k_kstar<DT, true>), (k_kstar<DT, false>), grid, dim3(256), 0, g->stream, g->dX, g->n, Npad, dXs, r0, r1, hp,
+                   g->dKsT, g->ld, rb, KstarParts{});
 }
 
 // The row pieces of k_trigemm_sq (kernels_score.hip), heaviest first: which row tiles go as two 64-row halves is a function
@@ -2084,14 +2090,15 @@ static int launch_trigemm(bohip_gp* g, int T, int64_t ncand, int64_t N, int64_t 
 
 // posterior pass over all R candidates: fills dq (partials) and dmu_raw.  VT optional (chunk-local).
 template <int DT>
-static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp);
-static int launch_kstar_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp) {
-    if (g->d <= 2) launch_kstar<2>(g, dXs, r0, r1, Npad, hp);
-    else if (g->d <= 4) launch_kstar<4>(g, dXs, r0, r1, Npad, hp);
-    else if (g->d <= 8) launch_kstar<8>(g, dXs, r0, r1, Npad, hp);
-    else if (g->d <= 16) launch_kstar<16>(g, dXs, r0, r1, Npad, hp);
-    else if (g->d <= 32) launch_kstar<32>(g, dXs, r0, r1, Npad, hp);
-    else launch_kstar<64>(g, dXs, r0, r1, Npad, hp);
+static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp, const KstarParts* kp);
+static int launch_kstar_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp,
+                            const KstarParts* kp = nullptr) {
+    if (g->d <= 2) launch_kstar<2>(g, dXs, r0, r1, Npad, hp, kp);
+    else if (g->d <= 4) launch_kstar<4>(g, dXs, r0, r1, Npad, hp, kp);
+    else if (g->d <= 8) launch_kstar<8>(g, dXs, r0, r1, Npad, hp, kp);
+    else if (g->d <= 16) launch_kstar<16>(g, dXs, r0, r1, Npad, hp, kp);
+    else if (g->d <= 32) launch_kstar<32>(g, dXs, r0, r1, Npad, hp, kp);
+    else launch_kstar<64>(g, dXs, r0, r1, Npad, hp, kp);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2335,7 +2342,7 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
 // ---- pruned arg-max: value-only calls (kernels_score.hip, "pruned arg-max") ---------------------------------------------------
 constexpr int PRUNE_K1 = 64;          // candidates scored exactly in round 1 (one candidate tile)
 constexpr int PRUNE_ROWS_CAP = 256;   // round 2 on k_trigemm_rows up to this many candidates, on gathered rows + k_trigemm_sq beyond
-constexpr int64_t PRUNE_R_MAX = 8192; // k_prune_rank is quadratic in the batch; larger batches keep the full pass
+constexpr int64_t PRUNE_R_MAX = 8192; // k_prune_select is one workgroup holding 8 keys a thread; larger batches keep the full pass
 // row tiles of the bounding prefix: a function of T only (never of the batch): the smallest m >= 2 whose triangle holds >= 2 % of
 // the contraction's, 0 (no pruning) when that leaves no row tile after it
 static int prune_tiles(int T) {
@@ -2390,8 +2397,9 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
     HIPCHK(hipGetLastError());
     return 0;
 }
-// One chunk, value-only: phase A (row tiles < m, every candidate) -> bounds -> round 1 (the 64 highest bounds, row tiles >= m, exact
-// finish: L) -> round 2 (every other candidate whose bound is not below L) -> the record.  The rounds run on k_trigemm_rows (round 2
+// One chunk, value-only: K*' with the partial sums of the alpha row's product -> phase A (row tiles < m, every candidate) -> bounds ->
+// select (the 64 highest bounds) -> round 1 (row tiles >= m, exact finish: L; the finish lists round 2: every other candidate
+// whose bound is not below L) -> round 2 -> the record.  The rounds run on k_trigemm_rows (round 2
 // up to PRUNE_ROWS_CAP candidates; past that on gathered rows and k_trigemm_sq); under the measurement knobs that change the row
 // pieces or the loop (rows_halves empty) both keep k_trigemm_sq.  No host round trip: the lists and their
 // lengths stay on the device, round 2's launches are sized for the worst case and the surplus workgroups leave at once.
@@ -2405,6 +2413,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     }
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
     const int T = (int)(Npad / TILE);
+    const int64_t P = Npad / 64;   // k_kstar's partial sums: one per wave of observations
     CHK(ensure_pieces(g, T, N));
     std::vector<int> pa, pb;   // the full pass's row pieces (same modes, same order), split at row tile m
     for (int c : g->hpieces) ((c & 0xffff) < m ? pa : pb).push_back(c);
@@ -2412,8 +2421,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
                  o_ub = o_mu2 + al((size_t)Rpad * 8), o_l1 = o_ub + al((size_t)Rpad * 8), o_l2 = o_l1 + al((size_t)PRUNE_K1 * 4),
-                 o_rank = o_l2 + al((size_t)Rpad * 4), o_cnt = o_rank + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
-                 o_pc = o_rec + 256, total = o_pc + al((3 * g->hpieces.size() + 8) * 4);
+                 o_mark = o_l2 + al((size_t)Rpad * 4), o_cnt = o_mark + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
+                 o_parts = o_rec + 256, o_pc = o_parts + al((size_t)2 * P * Rpad * 8), total = o_pc + al((3 * g->hpieces.size() + 8) * 4);
     bool fresh = false;
     if (g->pr_bytes < total) {
         fresh = true;
@@ -2423,7 +2432,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     }
     char* b = g->dpr;
     double *ks2 = (double*)(b + o_ks), *q2 = (double*)(b + o_q2), *mu2 = (double*)(b + o_mu2), *ub = (double*)(b + o_ub);
-    int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *rank = (int*)(b + o_rank), *pcs = (int*)(b + o_pc);
+    int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *mark = (int*)(b + o_mark), *pcs = (int*)(b + o_pc);
+    const KstarParts kp{g->dW + N * ld, (double*)(b + o_parts), Rpad};
     unsigned* cnt = (unsigned*)(b + o_cnt);
     Best* rec = (Best*)(b + o_rec);
     const std::vector<int> hv = rows_halves(g->hpieces);   // (after the pieces in the table; empty: the rounds keep k_trigemm_sq)
@@ -2446,7 +2456,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     const double sigma2 = std::exp(2.0 * g->logsig);
     const int k1 = (int)std::min<int64_t>(PRUNE_K1, R);
     t_begin(g, "kstar");
-    CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp));
+    CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp, &kp));
     t_end(g);
     // ONE bracket from phase A to the record, under the dense pass's label: what bench.py's roofline divides by
     t_begin(g, "trigemm_sq");
@@ -2454,9 +2464,9 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     fz.T = T;
     CHK(launch_trigemm_on(g, g->dKsT, pcs, (int)pa.size(), (int)((R + CTILE - 1) / CTILE), g->dq, Rpad, g->dmu_raw, fz));
     PruneBound bd{};
-    bd.KsT = g->dKsT; bd.ldk = ld; bd.Npad = Npad; bd.walpha = g->dW + N * ld; bd.q = g->dq; bd.ldq = Rpad; bd.R = R; bd.m = m;
-    bd.sigma2 = sigma2; bd.beta = g->beta; bd.ap = ap; bd.ub = ub; bd.rank = rank;
-    hipLaunchKernelGGL(k_prune_bound, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, g->stream, bd);
+    bd.parts = kp.parts; bd.P = P; bd.ldp = Rpad; bd.Npad = Npad; bd.q = g->dq; bd.ldq = Rpad; bd.R = R; bd.m = m;
+    bd.sigma2 = sigma2; bd.beta = g->beta; bd.ap = ap; bd.ub = ub;
+    hipLaunchKernelGGL(k_prune_bound, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, g->stream, bd);
     if (ub_host) {
         t_end(g);
         HIPCHK(hipGetLastError());
@@ -2464,9 +2474,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         HIPCHK(hipStreamSynchronize(g->stream));
         return 0;
     }
-    const unsigned nb = (unsigned)((R + 255) / 256);
-    hipLaunchKernelGGL(k_prune_rank, dim3(nb, nb), dim3(256), 0, g->stream, (const double*)ub, R, rank);
-    hipLaunchKernelGGL(k_prune_pick, dim3(nb), dim3(256), 0, g->stream, (const int*)rank, R, k1, l1, cnt, rec);
+    static_assert(PRUNE_R_MAX <= (int64_t)SELECT_THREADS * SELECT_PER, "k_prune_select holds the whole batch in one workgroup");
+    hipLaunchKernelGGL(k_prune_select, dim3(1), dim3(SELECT_THREADS), 0, g->stream, (const double*)ub, R, k1, l1, mark, cnt, rec);
     HIPCHK(hipGetLastError());
     PruneFinish pf{};
     pf.q = g->dq; pf.ldq = Rpad; pf.q2 = q2; pf.ldq2 = Rpad; pf.mu2 = mu2; pf.m = m; pf.T = T; pf.sigma2 = sigma2; pf.beta = g->beta;
@@ -2476,9 +2485,6 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         const int* list = round == 0 ? l1 : l2;
         const unsigned* c = cnt + round;
         const int64_t cap = round == 0 ? k1 : R - k1;   // worst case of the list's length
-        if (round == 1)
-            hipLaunchKernelGGL(k_prune_compact, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, (const double*)ub,
-                               (const int*)rank, R, k1, (const Best*)rec, l2, cnt + 1);
         if (cap > 0 && nh > 0 && cap <= PRUNE_ROWS_CAP) {   // (round 1: always)
             CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, list, c, (int)cap, q2, Rpad, mu2));
         } else if (cap > 0) {
@@ -2494,6 +2500,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         pf.list = list; pf.cnt = c;
         pf.best_out = round == 1 ? d_best : nullptr; pf.best_off = (long long)best_off;
         pf.stat = round == 1 ? g->hprune_stat : nullptr;
+        // round 1's finish goes on to list round 2 (its tail); round 2's is the same kernel without it
+        pf.ub = ub; pf.mark = mark; pf.R = R; pf.list2 = round == 0 ? l2 : nullptr; pf.cnt2 = cnt + 1;
         hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
         HIPCHK(hipGetLastError());
     }

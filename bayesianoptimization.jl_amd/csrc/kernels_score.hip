@@ -31,10 +31,54 @@ __device__ __forceinline__ double cov_from_r_fast(int fam, double sigma2, double
 // candidates whose coordinates are wave-uniform (scalar loads).  Stores are coalesced along j.
 // KsT[r][j] = k(x_j, x*_r) for j < N, 0 for N <= j < Npad.  Xs is [R][d] (d contiguous).
 // ------------------------------------------------------------------------------------------------
-template <int DT, bool LOW>
+// PARTS (the pruned pass only, rb = 16): besides K*' the kernel leaves, per wave (64 observations) and candidate, the partial sums
+// of p_j = alpha_j K*'_j and of |p_j| that k_prune_bound adds up -- the bound kernel then need not read K*' again.
+//   parts[0][w][r] = sum of p over the observations 64 w .. 64 w + 63,  parts[1][w][r] = the same of |p|   (w < Npad / 64, r < ldp)
+// Every partial has one writer and a fixed summation order (no atomics): the bounds are the same from run to run.
+struct KstarParts {
+    const double* alpha;     // the alpha row of W (zero past N), read for j < Npad
+    double* parts;           // [2][Npad / 64][ldp]
+    int64_t ldp;
+};
+// Sum over the wave's 64 lanes of 16 values per lane (one per candidate) by halving: a lane gives away half of what it holds and
+// adds the other lane's half of the rest.  The candidates come four at a time (one group: their `exp`s overlap, and no more than
+// a group's values are live): lane ^ 32 and ^ 16 take a group's 4 values to 1, lane ^ 8 two groups' values to 1 as soon as
+// both are there, lane ^ 4 the two pairs' -- of candidate 8 b2 + 4 b3 + 2 b5 + b4 (b: the bits of the lane number), summed over the
+// 16 lanes that share its bits 0 and 1; two plain steps finish.  17 exchanges for 16 sums instead of 16 x 6, and the first 8 of
+// them move p itself: they serve the sum of p and the sum of |p| alike.
+__device__ __forceinline__ void swap32(double a, double b, double& x, double& y) {
+    // v_permlane32_swap: lanes 32-63 of the first operand change places with lanes 0-31 of the second.  Afterwards the lower half
+    // holds (own a, the upper half's a) and the upper half (the lower half's b, own b): x + y is the sum of a in the lower and of b
+    // in the upper half, |x| + |y| the same of the absolute values -- one exchange serves both.
+    const unsigned long long ua = (unsigned long long)__double_as_longlong(a), ub = (unsigned long long)__double_as_longlong(b);
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)ua, (unsigned)ub, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32), false, false);
+    x = __longlong_as_double((long long)((unsigned long long)hi[0] << 32 | lo[0]));
+    y = __longlong_as_double((long long)((unsigned long long)hi[1] << 32 | lo[1]));
+}
+template <int BIT>
+__device__ __forceinline__ double halve_sum(double a, double b, int lane) {   // a where the lane's BIT is clear, b where it is set
+    const bool up = lane & BIT;
+    return (up ? b : a) + __shfl_xor(up ? a : b, BIT);
+}
+// a group's 4 products p -> the lane's sums of p and |p| of candidate 2 b5 + b4 of the group, over the lanes that share its bits 0-3
+__device__ __forceinline__ void group_sum4(const double* p, int lane, double& sm, double& sa) {
+    double x0, y0, x1, y1;
+    swap32(p[0], p[2], x0, y0);
+    swap32(p[1], p[3], x1, y1);
+    sm = halve_sum<16>(x0 + y0, x1 + y1, lane);
+    sa = halve_sum<16>(fabs(x0) + fabs(y0), fabs(x1) + fabs(y1), lane);
+}
+__device__ __forceinline__ double wave_finish(double s) {
+    s += __shfl_xor(s, 2);
+    s += __shfl_xor(s, 1);
+    return s;
+}
+
+template <int DT, bool LOW, bool PARTS = false>
 __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int64_t N, int64_t Npad,
                                                const double* __restrict__ Xs, int64_t r_begin, int64_t r_end,
-                                               KernelHyper hp, double* __restrict__ KsT, int64_t ldk, int rb) {
+                                               KernelHyper hp, double* __restrict__ KsT, int64_t ldk, int rb, KstarParts kp) {
     // the block's rb (<= 16) candidates are staged in LDS by one coalesced load (see k_build_cov: per-dimension scalar
     // loads behind `if (k < d)` made this kernel latency-bound); dimensions d <= k < DT carry zero weight
     __shared__ double xs_l[16 * DT];
@@ -56,16 +100,61 @@ __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int
     __syncthreads();
     if (j >= Npad) return;
     const int nc = (int)(r1 - r0);
-    for (int c = 0; c < nc; ++c) {
-        double rr = 0.0;
+    if constexpr (PARTS) {
+        // (Npad is a multiple of 64: a wave is either whole or gone at the return above)
+        const double aj = kp.alpha[j];
+        const int lane = threadIdx.x & 63;
+        double um[2], ua[2], tm0 = 0.0, ta0 = 0.0;
 #pragma unroll
-        for (int k = 0; k < DT; ++k) {
-            const double t = xj[k] - xs_l[c * DT + k];
-            rr += w[k] * (t * t);
+        for (int g = 0; g < 4; ++g) {
+            double p[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = 4 * g + i;
+                p[i] = 0.0;
+                if (c < nc) {
+                    double rr = 0.0;
+#pragma unroll
+                    for (int k = 0; k < DT; ++k) {
+                        const double t = xj[k] - xs_l[c * DT + k];
+                        rr += w[k] * (t * t);
+                    }
+                    const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
+                    KsT[(r0 + c - r_begin) * ldk + j] = v;
+                    p[i] = aj * v;   // v exactly as stored
+                }
+            }
+            double tm, ta;
+            group_sum4(p, lane, tm, ta);
+            if (g & 1) {
+                um[g >> 1] = halve_sum<8>(tm0, tm, lane);
+                ua[g >> 1] = halve_sum<8>(ta0, ta, lane);
+            } else {
+                tm0 = tm;
+                ta0 = ta;
+            }
+            __builtin_amdgcn_sched_barrier(0);   // a group at a time: all 16 `exp`s scheduled together spill
         }
-        const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
-        KsT[(r0 + c - r_begin) * ldk + j] = v;   // plain stores: non-temporal ones evict K*' from L2/MALL and k_trigemm_sq
-                                                   // then runs at 0.70 instead of 0.635 ms (measured)
+        const double sm = wave_finish(halve_sum<4>(um[0], um[1], lane)), sa = wave_finish(halve_sum<4>(ua[0], ua[1], lane));
+        // of the four lanes that hold a candidate's sums, lane 4 q writes the sum of p and lane 4 q + 1 the sum of |p| (bit 1 clear:
+        // a writer; bit 0: which sum): 16 doubles of one 128-B line per quantity and wave
+        const int c = 8 * ((lane >> 2) & 1) + 4 * ((lane >> 3) & 1) + 2 * (lane >> 5) + ((lane >> 4) & 1);
+        if ((lane & 3) < 2 && c < nc) {
+            const int64_t P = Npad >> 6;
+            kp.parts[((int64_t)(lane & 1) * P + (j >> 6)) * kp.ldp + (r0 + c - r_begin)] = (lane & 1) ? sa : sm;
+        }
+    } else {
+        for (int c = 0; c < nc; ++c) {
+            double rr = 0.0;
+#pragma unroll
+            for (int k = 0; k < DT; ++k) {
+                const double t = xj[k] - xs_l[c * DT + k];
+                rr += w[k] * (t * t);
+            }
+            const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
+            KsT[(r0 + c - r_begin) * ldk + j] = v;   // plain stores: non-temporal ones evict K*' from L2/MALL and k_trigemm_sq
+                                                       // then runs at 0.70 instead of 0.635 ms (measured)
+        }
     }
 }
 
@@ -531,7 +620,8 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 // ---- pruned arg-max (value-only calls, bohip.hip pruned_pass) ---------------------------------------------------------------
 // A call that returns only the winner need not contract the rows of candidates that provably cannot win.  After the first m row
 // tiles (phase A: k_trigemm_sq over the row pieces with rt < m, all candidates) every candidate gets an UPPER BOUND of the score
-// the full pass would compute for it (k_prune_bound).  Round 1 scores the 64 candidates of highest bound exactly; its best value
+// the full pass would compute for it (k_prune_bound).  Round 1 scores the 64 candidates of highest bound exactly (k_prune_select:
+// the first 64 in (bound desc, index asc) -- of the candidates that share the 64th bound, the lowest indices); its best value
 // L is an exactly computed score.  Round 2 scores exactly every other candidate whose bound is not below L.  A dropped candidate
 // has score <= bound < L, so it can neither win nor tie: the record equals the full pass's bit for bit (the exact rounds compute
 // every element of V with k_trigemm_sq's MFMA chain -- k_trigemm_rows, or k_trigemm_sq itself on gathered K*' rows: a column of
@@ -542,6 +632,9 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 //           done in the finish's order never exceeds the full q -- an upper bound of the computed sigma^2 with no margin.
 //   mu_up = beta + up(mu~ + 4 gamma_n S) (rounded up by >= 1 ulp), mu~ = sum_j alpha_j K*'_j, S = sum_j |alpha_j K*'_j| (any order): the computed
 //           mu_raw and mu~ both lie within gamma_n S(1 + gamma_n) of the exact dot product; beta + . is monotone.
+//           mu~ and S are not summed over K*' here: k_kstar<.., PARTS> leaves the sums of every 64 observations (one wave; its
+//           halving tree) and k_prune_bound adds those Npad / 64 partials in index order.  A two-level sum of the same Npad <= n
+//           terms is one of the orders the argument covers (any summation of at most n terms lies within gamma_n S), so n stays.
 //   functor f at (mu_up, s2_b), plus a slack for its evaluation where its operations are not exactly monotone:
 //     EI  (the reference's D Phi(D/s) + phi(D/s)): in s it rises up to s = 1 and falls after; at s <= 1 it rises in D for D <= 0, at
 //         s = 1 for every D.  So s2_b = min(s2_up, 1) when D_up <= 0, else 1 (a computed sigma^2 of 0 gives max(D, 0) <= both).
@@ -552,35 +645,33 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 //     MaxMean: mu_up (one rounded addition: exact).
 // A NaN bound is never below L: such a candidate is always scored.
 struct PruneBound {
-    const double* KsT;       // chunk [R][ldk]
-    int64_t ldk, Npad;
-    const double* walpha;    // the alpha row of W (zero past N)
+    const double* parts;     // k_kstar's partial sums [2][P][ldp]: of alpha_j K*'_j and of its absolute value, per 64 observations
+    int64_t P, ldp, Npad;
     const double* q;         // k_trigemm_sq's partial sums [2 t + h][ldq], t < m filled by phase A
     int64_t ldq, R;
     int m;
     double sigma2, beta;
     AcqParams ap;
     double* ub;              // [R]
-    int* rank;               // [R] zeroed here for k_prune_rank
 };
-__global__ __launch_bounds__(256) void k_prune_bound(PruneBound pb) {
+// thread = candidate (the partials are contiguous in r: every load is coalesced)
+__global__ __launch_bounds__(64) void k_prune_bound(PruneBound pb) {
 #pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (r >= pb.R) return;
-    if (lane == 0) pb.rank[r] = 0;
-    const double* k = pb.KsT + r * pb.ldk;
     double mu = 0.0, sa = 0.0;
-    for (int64_t j = lane; j < pb.Npad; j += 64) {
-        const double p = pb.walpha[j] * k[j];
-        mu += p;
-        sa += fabs(p);
+    for (int64_t w0 = 0; w0 < pb.P; w0 += 16) {   // index order: a fixed two-level sum of the Npad terms; 32 loads in flight
+        double a[16], b[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int64_t w = min(w0 + i, pb.P - 1);
+            a[i] = pb.parts[w * pb.ldp + r];
+            b[i] = pb.parts[(pb.P + w) * pb.ldp + r];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (w0 + i < pb.P) { mu += a[i]; sa += b[i]; }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        mu += __shfl_xor(mu, o);
-        sa += __shfl_xor(sa, o);
-    }
-    if (lane != 0) return;
     double qp = 0.0;
     for (int t = 0; t < pb.m; ++t) qp += pb.q[(int64_t)(2 * t) * pb.ldq + r] + pb.q[(int64_t)(2 * t + 1) * pb.ldq + r];
     double s2 = pb.sigma2 - qp;
@@ -615,46 +706,116 @@ __global__ __launch_bounds__(256) void k_prune_bound(PruneBound pb) {
     pb.ub[r] = ub;
 }
 
-// rank of every candidate in (bound desc, index asc), a NaN bound counting as +inf.  Workgroup (x, y): its 256 candidates against
-// the 256 bounds of block y, counts added into rank[] (zeroed by k_prune_bound); k_prune_pick then lists the first k1 ranks.
+// Round 1's list: the k1 candidates of highest bound in (bound desc, index asc), a NaN bound counting as +inf -- ONE workgroup, for
+// R <= 8 x 1024.  A bound maps to a 64-bit key that orders as the doubles compare (-0 as +0); thread t holds the keys of the
+// candidates t per .. t per + per - 1 in registers.  The k1-th largest key comes from a radix select, 8 bits a pass from the top:
+//   * the leading bits that the largest and the smallest key share are skipped (bounds of one call share most of their exponent:
+//     without the skip the first passes would add every key into one LDS word);
+//   * a pass counts the digits of the keys that still agree with the threshold's known bits (integer LDS atomics), then EVERY wave
+//     adds the 256 counts up from the top by itself and finds the digit at which the sum reaches the rank looked for -- no result
+//     goes through LDS, and with three histograms in turn (the one of pass p + 2 is cleared during pass p) a pass has one barrier;
+//   * when the rank looked for takes ALL keys of that digit, the bits below need not be resolved: keys compare by their bits
+//     from that digit up.  Distinct bounds end there after about three passes; only ties at the threshold go down to bit 0.
+// Membership: a key above the threshold is in; of the candidates AT the threshold, the first in ascending index until the list
+// holds k1 -- the set the order above gives.  list1 holds the members in ascending index, mark[r] says whether r is one; the
+// counters and the running record of the call are readied.
 __device__ __forceinline__ double prune_key(double v) { return v != v ? INFINITY : v; }
-__global__ __launch_bounds__(256) void k_prune_rank(const double* __restrict__ ub, int64_t R, int* __restrict__ rank) {
-    __shared__ double sk[256];
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x, base = (int64_t)blockIdx.y * 256;
-    const int64_t s = base + threadIdx.x;
-    sk[threadIdx.x] = s < R ? prune_key(ub[s]) : -INFINITY;
-    __syncthreads();
-    if (r >= R) return;
-    const double kr = prune_key(ub[r]);
-    const int n = (int)min((int64_t)256, R - base);
-    int above = 0;
-    for (int i = 0; i < n; ++i) {
-        const double v = sk[i];
-        above += (v > kr) || (v == kr && base + i < r);
-    }
-    if (above) atomicAdd(rank + r, above);
+__device__ __forceinline__ unsigned long long prune_key_bits(double v) {
+    const double k = prune_key(v);
+    const unsigned long long b = k == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(k);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;   // > 0 for every double: 0 marks "no candidate"
 }
-// round 1's list (position = rank); readies the counters and the running record of the call
-__global__ __launch_bounds__(256) void k_prune_pick(const int* __restrict__ rank, int64_t R, int k1, int* __restrict__ list1,
-                                                    unsigned* __restrict__ cnt, Best* __restrict__ rec) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r < R && rank[r] < k1) list1[rank[r]] = (int)r;
-    if (r == 0) {
-        cnt[0] = (unsigned)min((int64_t)k1, R);
+constexpr int SELECT_THREADS = 1024, SELECT_PER = 8;
+__global__ __launch_bounds__(SELECT_THREADS) void k_prune_select(const double* __restrict__ ub, int64_t R, int k1, int* __restrict__ list1,
+                                                                 int* __restrict__ mark, unsigned* __restrict__ cnt, Best* __restrict__ rec) {
+    __shared__ uint4 hist[3][64];   // [.][l]: the counts of the digits 4 l .. 4 l + 3
+    __shared__ unsigned long long red[2 * SELECT_THREADS / 64];
+    __shared__ unsigned tot[SELECT_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int per = (int)((R + SELECT_THREADS - 1) / SELECT_THREADS);   // <= SELECT_PER
+    unsigned long long key[SELECT_PER];
+    unsigned long long kmax = 0ull, kmin = ~0ull;
+#pragma unroll
+    for (int i = 0; i < SELECT_PER; ++i) {
+        const int64_t r = (int64_t)t * per + i;
+        key[i] = (i < per && r < R) ? prune_key_bits(ub[r]) : 0ull;
+        if (key[i]) { kmax = max(kmax, key[i]); kmin = min(kmin, key[i]); }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        kmax = max(kmax, __shfl_xor(kmax, o));
+        kmin = min(kmin, __shfl_xor(kmin, o));
+    }
+    if (lane == 0) { red[2 * wave] = kmax; red[2 * wave + 1] = kmin; }
+    if (t < 128) (&hist[0][0])[t] = make_uint4(0u, 0u, 0u, 0u);   // (hist[0] and hist[1])
+    __syncthreads();
+    for (int w = 0; w < SELECT_THREADS / 64; ++w) { kmax = max(kmax, red[2 * w]); kmin = min(kmin, red[2 * w + 1]); }
+    // the threshold agrees with `prefix` from bit hb up; k: its rank among the keys that do.  All of it is uniform over the workgroup.
+    unsigned long long prefix = kmax;
+    int hb = kmax == kmin ? 0 : 64 - __clzll((long long)(kmax ^ kmin)), k = k1;
+    for (int pass = 0; hb > 0; ++pass) {
+        const int wd = hb < 8 ? hb : 8, shift = hb - wd;
+        unsigned* h = reinterpret_cast<unsigned*>(hist[pass % 3]);
+#pragma unroll
+        for (int i = 0; i < SELECT_PER; ++i)
+            if (key[i] && (hb == 64 || (key[i] >> hb) == (prefix >> hb))) atomicAdd(h + ((unsigned)(key[i] >> shift) & ((1u << wd) - 1u)), 1u);
+        __syncthreads();
+        if (t < 64) hist[(pass + 2) % 3][t] = make_uint4(0u, 0u, 0u, 0u);
+        // lane l: the digits 255 - 4 l down to 252 - 4 l; counts added from the top
+        const uint4 c4 = hist[pass % 3][63 - lane];
+        const unsigned c[4] = {c4.w, c4.z, c4.y, c4.x};
+        unsigned incl = c[0] + c[1] + c[2] + c[3];
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned u = __shfl_up(incl, o);
+            if (lane >= o) incl += u;
+        }
+        unsigned run = incl - (c[0] + c[1] + c[2] + c[3]);   // keys above this lane's digits
+        int found = -1, knew = 0, all = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (run < (unsigned)k && (unsigned)k <= run + c[i]) { found = 255 - 4 * lane - i; knew = k - (int)run; all = knew == (int)c[i]; }
+            run += c[i];
+        }
+        const unsigned long long who = __ballot(found >= 0);   // exactly one lane
+        const int src = __ffsll((long long)who) - 1;
+        const int digit = __shfl(found, src);
+        k = __shfl(knew, src);
+        all = __shfl(all, src);
+        const unsigned long long low = hb == 64 ? ~0ull : (1ull << hb) - 1ull;
+        prefix = (prefix & ~low) | (unsigned long long)digit << shift;
+        hb = shift;
+        if (all) break;   // every key of this digit is in: the bits below hb stay out of the comparison
+    }
+    // keys compare from bit hb up; the threshold is prefix >> hb, and k of the candidates that hold it are in (k >= 1)
+    const unsigned long long thr = prefix >> hb;
+    int ngt = 0, neq = 0;
+#pragma unroll
+    for (int i = 0; i < SELECT_PER; ++i) { ngt += key[i] && (key[i] >> hb) > thr; neq += key[i] && (key[i] >> hb) == thr; }
+    const unsigned mine = (unsigned)ngt | (unsigned)neq << 16;   // ngt < 64 and neq <= 8192 in total: no carry between the halves
+    unsigned incl = mine;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned u = __shfl_up(incl, o);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) tot[wave] = incl;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) incl += tot[w];
+    int g = (int)((incl - mine) & 0xffffu), e = (int)((incl - mine) >> 16);   // members above / ties at the threshold, before this thread
+#pragma unroll
+    for (int i = 0; i < SELECT_PER; ++i) {
+        if (!key[i]) continue;
+        const int64_t r = (int64_t)t * per + i;
+        const bool gt = (key[i] >> hb) > thr, eq = (key[i] >> hb) == thr, in = gt || (eq && e < k);
+        if (in) list1[g + min(e, k)] = (int)r;
+        mark[r] = in;
+        g += gt;
+        e += eq;
+    }
+    if (t == 0) {
+        cnt[0] = (unsigned)k1;
         cnt[1] = 0u;
         rec->val = -INFINITY;
         rec->idx = -1;
     }
-}
-
-// round 2's list: candidates outside round 1 whose bound is not below round 1's exact best (order is immaterial: every listed
-// candidate is scored on its own and the record is reduced by `better`)
-__global__ __launch_bounds__(256) void k_prune_compact(const double* __restrict__ ub, const int* __restrict__ rank, int64_t R, int k1,
-                                                       const Best* __restrict__ rec, int* __restrict__ list2, unsigned* __restrict__ cnt2) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= R || rank[r] < k1) return;
-    if (ub[r] < rec->val) return;
-    list2[atomicAdd(cnt2, 1u)] = (int)r;
 }
 
 // K*' rows of the listed candidates, packed (workgroup i: row list[i]; the grid is sized for the worst case)
@@ -853,18 +1014,38 @@ struct PruneFinish {
     Best* best_out;       // nullable: the call's result (last round)
     long long best_off;
     unsigned* stat;       // nullable (pinned host word): the round's list length, read by the host's path choice of a later call
+    // round 1 only (list2 != nullptr): the tail that lists round 2
+    const double* ub;     // [R] the bounds
+    const int* mark;      // [R] k_prune_select's "in round 1"
+    int64_t R;
+    int* list2;
+    unsigned* cnt2;
 };
 __global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
 #pragma clang fp contract(off)
     __shared__ Best sh[4];
+    __shared__ double tail_L;
+    __shared__ unsigned tail_n;
     const int n = (int)*pf.cnt;
     double v = -INFINITY;
     long long idx = -1;
     for (int i = threadIdx.x; i < n; i += 256) {
         const int64_t r = pf.list[i];
         double q = 0.0;
-        for (int t = 0; t < pf.m; ++t) q += pf.q[(int64_t)(2 * t) * pf.ldq + r] + pf.q[(int64_t)(2 * t + 1) * pf.ldq + r];
-        for (int t = pf.m; t < pf.T; ++t) q += pf.q2[(int64_t)(2 * t) * pf.ldq2 + i] + pf.q2[(int64_t)(2 * t + 1) * pf.ldq2 + i];
+        for (int t0 = 0; t0 < pf.T; t0 += 8) {   // the sum in its order, sixteen loads in flight (a pair at a time: 8 us for 24 pairs, profiles/prune_select_ab.txt)
+            double a[8], b[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int t = min(t0 + u, pf.T - 1);
+                const double* src = t < pf.m ? pf.q + r : pf.q2 + i;
+                const int64_t ld = t < pf.m ? pf.ldq : pf.ldq2;
+                a[u] = src[(int64_t)(2 * t) * ld];
+                b[u] = src[(int64_t)(2 * t + 1) * ld];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (t0 + u < pf.T) q += a[u] + b[u];
+        }
         double s2 = pf.sigma2 - q;
         if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
         const double mu = pf.beta + pf.mu2[i];
@@ -882,7 +1063,30 @@ __global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
             pf.best_out->idx = idx >= 0 ? idx + pf.best_off : -1;
         }
         if (pf.stat) *pf.stat = (unsigned)n;
+        tail_L = idx >= 0 ? v : -INFINITY;
+        tail_n = 0u;
     }
+    // round 2's list: candidates outside round 1 whose bound is not below round 1's exact best (order is immaterial: every listed
+    // candidate is scored on its own and the record is reduced by `better`).  The same workgroup, after its record: no other
+    // workgroup waits on it, the next launch reads the list.
+    if (!pf.list2) return;
+    __syncthreads();
+    const double L = tail_L;
+    for (int64_t r0 = threadIdx.x; r0 < pf.R; r0 += 8 * 256) {   // eight loads of each in flight
+        int mk[8];
+        double u[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int64_t r = min(r0 + 256 * i, pf.R - 1);
+            mk[i] = pf.mark[r];
+            u[i] = pf.ub[r];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (r0 + 256 * i < pf.R && !mk[i] && !(u[i] < L)) pf.list2[atomicAdd(&tail_n, 1u)] = (int)(r0 + 256 * i);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *pf.cnt2 = tail_n;
 }
 
 // The exchange step of sharded scoring: `all` holds nrec records per draw-slot layout [rec][S] gathered
