@@ -847,13 +847,23 @@ __global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ li
 //   * q of the half: sq_step over the rows of a lane in k_trigemm_sq's accumulator layout, then sq_tree (shared helpers).
 // Only the product build's pieces (whole tiles, the solo last half) and the 8-wave loop are reproduced: under the measurement
 // knobs (halved tiles, BOHIP_KS8=0) the pruned pass keeps k_trigemm_sq for its rounds.
-// Sizing: a workgroup is 4 waves (h x two 32-row quarters), 8 accumulator chains of 8 x 8 per wave, 16 MFMAs per wave and chunk
-// (~0.1 us).  The operands come by LDS-DMA as whole 128-B rows, RS_DEPTH chunks deep, one barrier per chunk.  Measured on MI355X
-// (round 1 at N = 3000, 64 candidates, 188 chunks in the longest half): the same loop with its operands loaded straight into VGPRs
-// (16-B fragments, each fetched by two lanes and every 128-B row by two waves) took 129 us and 170 us with 8 waves of 16 rows and
-// more loads in flight (bench step 0.28 against 0.32 ms) -- the per-CU fetch of scattered fragments bound it, not the latency;
-// whole rows by DMA: 60 us.  The column groups of a half run on one XCD: W's rows come from the Infinity Cache once per XCD.
-constexpr int RS_COLS = 16, RS_WAVES = 4, RS_THREADS = 64 * RS_WAVES, RS_DEPTH = 6;
+// Sizing: a workgroup is 8 waves (h x four 16-row quarters: two waves per SIMD) against RS_COLS = 8 candidates, 2 accumulator chains
+// of 8 x 8 per wave, 4 MFMAs per wave and chunk; round 1 of 64 candidates at T = 24 is 41 halves x 8 groups = 328 workgroups, two
+// to a CU (RS_DEPTH = 7 buffers of 9 KB).  The operands come by LDS-DMA as whole 128-B rows, RS_DEPTH chunks deep, one barrier per
+// chunk, and the fragment reads of chunk kc + 1 are issued before the MFMAs of chunk kc into a second register set, so the LDS
+// latency runs under the matrix pipe.  The buffer of chunk kc is free as soon as every wave holds the chunk in registers: RS_DEPTH
+// buffers keep RS_DEPTH - 1 chunks in flight.
+// Measured on MI355X (round 1 at N = 3000, 64 candidates, 188 chunks in the longest half; profiles/prune_rows_pipeline_ab.txt):
+//   operands loaded straight into VGPRs (16-B fragments, each fetched by two lanes, every 128-B row by two waves)   129 us
+//     ... with 8 waves of 16 rows and more loads in flight (the per-CU fetch of scattered fragments bound it)        170 us
+//   whole rows by DMA, loop serial per chunk (wait, barrier, DMA issue, six ds_read_b128, lgkmcnt(0), 16 MFMAs),
+//     16 columns x 4 waves x 6 buffers, K*' pieces issued twice to keep the waves' wait counts equal                60.4 us
+//     ... 9 / 12 buffers: 59.9 / 60.5 us (fetch latency is not on the path); without the DMA re-issue: 46.7 us
+//   this loop (reads one chunk ahead, K*' issued once), columns x waves x buffers:
+//     16 x 4 x 6: 51.8    16 x 4 x 12: 53.6    16 x 8 x 6: 49.2    16 x 8 x 12: 49.3
+//      8 x 4 x 7: 45.4     8 x 4 x 12: 44.8     8 x 8 x 12: 42.8 (one workgroup a CU)     8 x 8 x 7: 42.6 us  <- kept
+// The column groups of a half run on one XCD: W's rows come from the Infinity Cache once per XCD.
+constexpr int RS_COLS = 8, RS_WAVES = 8, RS_THREADS = 64 * RS_WAVES, RS_DEPTH = 7;
 constexpr int RS_RG = 16 / RS_WAVES;   // 8-row groups per wave
 constexpr int RS_BUF = (64 + RS_COLS) * KC;                  // doubles of one chunk's operands in LDS
 constexpr int RS_LDS_BYTES = RS_DEPTH * RS_BUF * 8;          // dynamic LDS of k_trigemm_rows
@@ -873,7 +883,7 @@ struct RowsParams {
     double* mu;              // [list position]
 };
 __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
-    __shared__ double xch[2 * 64 * 16];          // the h = 1 waves' chains
+    __shared__ double xch[2 * 64 * RS_COLS];     // the h = 1 waves' chains
     __shared__ double vb[64 * RS_COLS];          // v of the half [row][column]
     // an XCD owns the halves x, x + 8, ... (block b runs on XCD b % 8) with all their candidate groups: W's rows are fetched once
     // per XCD, and the heaviest halves start first
@@ -884,67 +894,102 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
     const int code = __builtin_amdgcn_readfirstlane(rp.halves[hi]);
     const int rt = code & 0xffff, hh = (code >> 16) & 1;
     const bool solo = (code >> 17) & 1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int h = __builtin_amdgcn_readfirstlane(wave / (RS_WAVES / 2)), wq = __builtin_amdgcn_readfirstlane(wave % (RS_WAVES / 2));
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = wave / (RS_WAVES / 2), wq = wave % (RS_WAVES / 2);
     const int k = lane >> 4, b = (lane >> 2) & 3;
-    const int tri_kc = 8 * rt, kc_end = tri_kc + (hh == 0 ? 4 : 8);
+    const int tri_kc = 8 * rt, kc_end = tri_kc + (hh == 0 ? 4 : 8);   // (even)
     const int g0 = 8 * hh + RS_RG * wq;          // row group (8 rows) of the tile behind this wave's acc[0]
     // operands: LDS-DMA (global_load_lds, 16 B per lane) of whole 128-B rows, RS_DEPTH chunks deep.  Per chunk 8 pieces of 8 rows of
-    // W and 2 of K*' (rows through the list): wave w issues W pieces w, w + 4 and K*' piece w & 1 (waves 2, 3 repeat the pieces of
-    // waves 0, 1 -- the same bytes to the same place -- so that every wave counts three loads per chunk).  LDS row r holds the row's
+    // W and one of K*' (rows through the list): wave w issues W piece w and wave 0 the K*' piece as well -- so a wave counts one
+    // load per chunk, wave 0 two (has_b picks the wait's count).  LDS row r holds the row's
     // 16-B segment s at slot s ^ (r & 7) (gemm_core.h's swizzle).  Fragments as the loop's: lane (k, b, t) reads A rows 4 (b >> 1) + t
-    // of each row group and B column 4 (b & 1) + t of each column group, segment 4 h + k = the pair 16 kc + 8 h + 2 k.
+    // of each row group and B column 4 (b & 1) + t, segment 4 h + k = the pair 16 kc + 8 h + 2 k.
     extern __shared__ __attribute__((aligned(16))) double rs_ring[];   // [RS_DEPTH][64 + RS_COLS rows][16]
     const int prow = lane >> 3, sseg = (lane & 7) ^ prow;
+    const bool has_b = wave == 0;
     const double* a_src0 = rp.W + ((int64_t)rt * TILE + 64 * hh + 8 * wave + prow) * rp.ldw + 2 * sseg;
-    const double* a_src1 = a_src0 + (int64_t)32 * rp.ldw;
-    const int ib = grp * RS_COLS + 8 * (wave & 1) + prow;
+    const int ib = grp * RS_COLS + prow;
     const double* b_src = rp.KsT + (int64_t)(ib < n ? rp.list[ib] : rp.list[0]) * rp.ldk + 2 * sseg;
     auto issue = [&](int kc, int buf) {
         kc = min(kc, kc_end - 1);   // (past the end: a harmless re-read into a free buffer that keeps the wait counts straight)
         double* d = rs_ring + buf * RS_BUF;
         __builtin_amdgcn_global_load_lds((gbl_void_ptr)(a_src0 + (int64_t)kc * KC), (lds_void_ptr)(d + 8 * wave * KC), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(a_src1 + (int64_t)kc * KC), (lds_void_ptr)(d + (8 * wave + 32) * KC), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gbl_void_ptr)(b_src + (int64_t)kc * KC), (lds_void_ptr)(d + (64 + 8 * (wave & 1)) * KC), 16, 0, 0);
+        if (has_b)
+            __builtin_amdgcn_global_load_lds((gbl_void_ptr)(b_src + (int64_t)kc * KC), (lds_void_ptr)(d + 64 * KC), 16, 0, 0);
+    };
+    // all but the `left` youngest chunks of this wave's loads have landed
+    auto wait_left = [&](auto left) {
+        constexpr int L = decltype(left)::value;
+        if (has_b) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * L) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L) : "memory");
     };
     const int rr = 4 * (b >> 1) + (lane & 3), cc = 4 * (b & 1) + (lane & 3), S = 4 * h + k;
     const uint32_t ring0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const double*)rs_ring;
     const uint32_t fa = ring0 + (uint32_t)(((8 * RS_RG * wq + rr) * KC + 2 * (S ^ rr)) * 8);
     const uint32_t fb = ring0 + (uint32_t)(((64 + cc) * KC + 2 * (S ^ cc)) * 8);
-    double acc[RS_RG][2], acc2[RS_RG][2];   // WHOLE: acc (both members); SOLO: acc the even members, acc2 the odd ones
+    // the fragment reads of a chunk are issued one chunk AHEAD of their MFMAs, into the register set the MFMAs of the chunk before
+    // last used: the LDS latency runs under the matrix pipe.  `landed` is the wait that ends the chunk.
+    // INVARIANT (the compiler does not know that the asm reads of `frags` complete later): between a set's `frags` and its `landed`
+    // no instruction may read, copy or spill a register of the set.  The source keeps it by touching the set in those two asm
+    // statements only, by ending every chunk with `landed` (no set is in flight across the loop's back edge or a phi) and by the
+    // sched_barriers around them.  To re-check after a compiler or flag change: in the gfx950 assembly of this kernel (hipcc -S or
+    // --save-temps), between each group of three ds_read_b128 and the next s_waitcnt lgkmcnt(0) there must be nothing but
+    // v_mfma_f64_4x4x4 on OTHER registers, scalar instructions and branches -- no v_mov / v_accvgpr / scratch_ of the three destinations;
+    // tests/test_prune_rows_gpu.py fails on a stale fragment (every element is compared bit for bit).
+    auto frags = [&](int buf, d2 (&av)[RS_RG], d2 (&bv)[1]) {
+        const uint32_t off = (uint32_t)(buf * RS_BUF * 8);
+        av[0] = ds_read128<0>(fa + off);
+        av[1] = ds_read128<1024>(fa + off);
+        bv[0] = ds_read128<0>(fb + off);
+    };
+    auto landed = [&](d2 (&av)[RS_RG], d2 (&bv)[1]) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[0]), "+v"(av[1]), "+v"(bv[0]));
+    };
+    double acc[RS_RG][1], acc2[RS_RG][1];   // WHOLE: acc (both members); SOLO: acc the even members, acc2 the odd ones
     auto run = [&](auto solo_tag) {
         constexpr bool SOLO = decltype(solo_tag)::value;
 #pragma unroll
         for (int i = 0; i < RS_RG; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = acc2[i][j] = 0.0;
-#pragma unroll
-        for (int p = 0; p < RS_DEPTH - 1; ++p) issue(p, p);
-        int cur = 0;
-        for (int kc = 0; kc < kc_end; ++kc) {
-            // chunk kc has landed (the RS_DEPTH - 2 later ones stay in flight); after the barrier every wave's pieces of it are in LDS
-            // and every wave is done reading the buffer of chunk kc - 1, which the next issue refills
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * (RS_DEPTH - 2)) : "memory");
+            for (int j = 0; j < 1; ++j) acc[i][j] = acc2[i][j] = 0.0;
+        // chunk kc: its operands (in the registers `av`, `bv`) against the accumulators, while chunk kc + 1's are read into `avn`, `bvn`
+        auto step = [&](int kc, int cur, const d2 (&av)[RS_RG], const d2 (&bv)[1], d2 (&avn)[RS_RG], d2 (&bvn)[1]) {
+            // chunk kc + 1 has landed (the RS_DEPTH - 2 later ones stay in flight); after the barrier every wave's pieces of it are in
+            // LDS and every wave holds chunk kc in registers (its `landed`), so the next issue refills the buffer of chunk kc
+            wait_left(std::integral_constant<int, RS_DEPTH - 2>{});
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            issue(kc + RS_DEPTH - 1, cur == 0 ? RS_DEPTH - 1 : cur - 1);
-            const uint32_t off = (uint32_t)(cur * RS_BUF * 8);
-            d2 a0 = ds_read128<0>(fa + off), a1 = ds_read128<1024>(fa + off), a2 = ds_read128<2048>(fa + off),
-               a3 = ds_read128<3072>(fa + off), b0 = ds_read128<0>(fb + off), b1 = ds_read128<1024>(fb + off);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1));
-            const d2 av[4] = {a0, a1, a2, a3}, bv[2] = {b0, b1};
+            issue(kc + RS_DEPTH, cur);
+            frags(cur + 1 == RS_DEPTH ? 0 : cur + 1, avn, bvn);
+            __builtin_amdgcn_sched_barrier(0);
             const int skip = kc >= tri_kc ? 2 * (kc - tri_kc) + h - g0 : 0;   // row groups g0 + i, i < skip: all-zero in the block
 #pragma unroll
             for (int i = 0; i < RS_RG; ++i) {
                 if (skip > i) continue;
                 if constexpr (SOLO) {
-                    mma_row<2, 1>(av[i], bv, acc[i]);
-                    mma_row<2, 2>(av[i], bv, acc2[i]);
+                    mma_row<1, 1>(av[i], bv, acc[i]);
+                    mma_row<1, 2>(av[i], bv, acc2[i]);
                 } else {
-                    mma_row<2, 0>(av[i], bv, acc[i]);
+                    mma_row<1, 0>(av[i], bv, acc[i]);
                 }
             }
+            landed(avn, bvn);
             __builtin_amdgcn_sched_barrier(0);
+        };
+#pragma unroll
+        for (int p = 0; p < RS_DEPTH; ++p) issue(p, p);
+        d2 av0[RS_RG], bv0[1], av1[RS_RG], bv1[1];
+        wait_left(std::integral_constant<int, RS_DEPTH - 1>{});
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        frags(0, av0, bv0);
+        landed(av0, bv0);
+        __builtin_amdgcn_sched_barrier(0);
+        int cur = 0;
+        for (int kc = 0; kc < kc_end; kc += 2) {   // (kc_end is even; the last step reads ahead into a buffer that holds a re-read)
+            step(kc, cur, av0, bv0, av1, bv1);
+            cur = cur + 1 == RS_DEPTH ? 0 : cur + 1;
+            step(kc + 1, cur, av1, bv1, av0, bv0);
             cur = cur + 1 == RS_DEPTH ? 0 : cur + 1;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -956,9 +1001,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
 #pragma unroll
         for (int i = 0; i < RS_RG; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                xch[((wq * RS_RG + i) * 2 + j) * 64 + lane] = acc[i][j];
-                xch[64 * 16 + ((wq * RS_RG + i) * 2 + j) * 64 + lane] = acc2[i][j];
+            for (int j = 0; j < 1; ++j) {
+                xch[((wq * RS_RG + i)  + j) * 64 + lane] = acc[i][j];
+                xch[64 * RS_COLS + ((wq * RS_RG + i)  + j) * 64 + lane] = acc2[i][j];
             }
     }
     __syncthreads();
@@ -966,11 +1011,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
 #pragma unroll
         for (int i = 0; i < RS_RG; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double a1 = xch[((wq * RS_RG + i) * 2 + j) * 64 + lane];
+            for (int j = 0; j < 1; ++j) {
+                const double a1 = xch[((wq * RS_RG + i)  + j) * 64 + lane];
                 double v = acc[i][j] + a1;
                 if (solo) {
-                    const double o1 = xch[64 * 16 + ((wq * RS_RG + i) * 2 + j) * 64 + lane];
+                    const double o1 = xch[64 * RS_COLS + ((wq * RS_RG + i)  + j) * 64 + lane];
                     v = v + (acc2[i][j] + o1);
                 }
                 const int row = 8 * (RS_RG * wq + i) + 4 * (b >> 1) + k, col = 8 * j + 4 * (b & 1) + (lane & 3);
@@ -978,8 +1023,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
             }
     }
     __syncthreads();
-    if (wave >= 2) return;
-    // wave w: candidate columns 8 w .. 8 w + 7 in k_trigemm_sq's accumulator layout (lane (k, b, t): column 4 (b & 1) + t)
+    if (wave >= 1) return;
+    // wave 0: the 8 candidate columns in k_trigemm_sq's accumulator layout (lane (k, b, t): column 4 (b & 1) + t)
     const int col = 8 * wave + 4 * (b & 1) + (lane & 3), i_list = grp * RS_COLS + col;
     const int64_t row_base = (int64_t)rt * TILE + 64 * hh;
     double s = 0.0;
