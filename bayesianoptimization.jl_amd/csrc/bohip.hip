@@ -127,6 +127,9 @@ struct bohip_gp {
     std::vector<int> hpr_pieces;
     int* pr_pieces_at = nullptr;
     unsigned* hprune_stat = nullptr;   // pinned: round 2's list length of the last pruned call (prune_wanted)
+    unsigned prune_seen = 0;           // the last figure prune_wanted read from it
+    bool prune_retry = false;          // the next pruned call is the retry after a back-off (prune_wanted cleared the word)
+    int prune_r2_form = -1;            // tests (bohip_debug_prune_round2_form): -1 the rule, 0 the steady form, 1 the long form
     int prune_skip = 0;                // value-only calls left on the full pass before pruning is tried again
     // batch selection (bohip_gp_select_batch): V' of ALL candidates, and ONE block [u_i q x ldu | records | scalars | workgroup records | picked]
     double* dBV = nullptr;
@@ -2341,7 +2344,8 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
 
 // ---- pruned arg-max: value-only calls (kernels_score.hip, "pruned arg-max") ---------------------------------------------------
 constexpr int PRUNE_K1 = 64;          // candidates scored exactly in round 1 (one candidate tile)
-constexpr int PRUNE_ROWS_CAP = 256;   // round 2 on k_trigemm_rows up to this many candidates, on gathered rows + k_trigemm_sq beyond
+constexpr int PRUNE_ROWS_CAP = 256;   // round 2's long form: k_trigemm_rows up to this many candidates, gathered rows + k_trigemm_sq beyond
+constexpr int PRUNE_R2_GROUPS = 8;    // round 2's steady form: column groups in the grid (a workgroup loops over g, g + 8, ...)
 constexpr int64_t PRUNE_R_MAX = 8192; // k_prune_select is one workgroup holding 8 keys a thread; larger batches keep the full pass
 // row tiles of the bounding prefix: a function of T only (never of the batch): the smallest m >= 2 whose triangle holds >= 2 % of
 // the contraction's, 0 (no pruning) when that leaves no row tile after it
@@ -2373,12 +2377,17 @@ static int rows_halves_from(const std::vector<int>& hv, int t0) {
     while (n < (int)hv.size() && (hv[n] & 0xffff) >= t0) ++n;
     return n;
 }
+// groups: column groups in the grid, 0: as many as cnt_max candidates need (no workgroup takes a second one); a list longer than
+// cnt_max is not this launch's.  pf, arrive: the round finishes in the launch (its last arriver); nullptr: the caller enqueues the finish.
 static int launch_trigemm_rows(bohip_gp* g, const double* KsT, const int* halves, int NH, const int* list, const unsigned* cnt,
-                               int cnt_max, double* q, int64_t ldq, double* mu) {
+                               int cnt_max, double* q, int64_t ldq, double* mu, int groups = 0, const PruneFinish* pf = nullptr,
+                               unsigned* arrive = nullptr) {
     if (NH <= 0 || cnt_max <= 0) return 0;
     RowsParams rp{};
     rp.W = g->dW; rp.ldw = g->ld; rp.KsT = KsT; rp.ldk = g->ld; rp.list = list; rp.cnt = cnt; rp.cnt_max = cnt_max;
-    rp.halves = halves; rp.NH = NH; rp.G = (cnt_max + RS_COLS - 1) / RS_COLS; rp.alpha_row = g->n; rp.q = q; rp.ldq = ldq; rp.mu = mu;
+    rp.halves = halves; rp.NH = NH; rp.G = groups > 0 ? groups : (cnt_max + RS_COLS - 1) / RS_COLS;
+    rp.alpha_row = g->n; rp.q = q; rp.ldq = ldq; rp.mu = mu;
+    if (pf) { rp.finish = 1; rp.arrive = arrive; rp.pf = *pf; }
     hipLaunchKernelGGL(k_trigemm_rows, dim3((unsigned)(8 * ((NH + 7) / 8) * rp.G)), dim3(RS_THREADS), RS_LDS_BYTES, g->stream, rp);
     HIPCHK(hipGetLastError());
     return 0;
@@ -2399,13 +2408,16 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
 }
 // One chunk, value-only: K*' with the partial sums of the alpha row's product -> phase A (row tiles < m, every candidate) -> bounds ->
 // select (the 64 highest bounds) -> round 1 (row tiles >= m, exact finish: L; the finish lists round 2: every other candidate
-// whose bound is not below L) -> round 2 -> the record.  The rounds run on k_trigemm_rows (round 2
-// up to PRUNE_ROWS_CAP candidates; past that on gathered rows and k_trigemm_sq); under the measurement knobs that change the row
-// pieces or the loop (rows_halves empty) both keep k_trigemm_sq.  No host round trip: the lists and their
-// lengths stay on the device, round 2's launches are sized for the worst case and the surplus workgroups leave at once.
+// whose bound is not below L) -> round 2 -> the record.  Six launches: a round is ONE k_trigemm_rows launch whose last workgroup to
+// arrive finishes it (scores, merges the record; round 1 lists round 2 and, when it lists nobody, writes the result).  Round 2's
+// steady form is a fixed grid whose workgroups loop over the column groups: right for a list of any length, slow for a long one.
+// long_form (the host expects a long list: score_core) is round 2 as four launches: gathered rows + k_trigemm_sq past PRUNE_ROWS_CAP
+// candidates, k_trigemm_rows up to it, k_prune_finish.  Under the measurement knobs that change the row pieces or the loop
+// (rows_halves empty) both rounds keep k_trigemm_sq and k_prune_finish.  No host round trip: the lists and their lengths stay on
+// the device and the surplus workgroups leave at once.
 // ub_host (tests, bohip_debug_prune_bounds): stop after the bounds and copy them out.
 static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
-                       double* ub_host = nullptr) {
+                       double* ub_host = nullptr, bool long_form = false) {
     CHK(one_time_kernel_setup());
     if (!g->hprune_stat) {
         HIPCHK(hipHostMalloc((void**)&g->hprune_stat, 64, hipHostMallocDefault));
@@ -2481,27 +2493,52 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     pf.q = g->dq; pf.ldq = Rpad; pf.q2 = q2; pf.ldq2 = Rpad; pf.mu2 = mu2; pf.m = m; pf.T = T; pf.sigma2 = sigma2; pf.beta = g->beta;
     pf.ap = ap; pf.rec = rec;
     const int* hvd = pcs + pa.size() + pb.size();
+    pf.ub = ub; pf.mark = mark; pf.R = R; pf.cnt2 = cnt + 1; pf.best_off = (long long)best_off;
+    if (nh > 0) {
+        // Round 1 finishes in its own launch: the last workgroup to arrive scores, merges and lists round 2 (the tail), and when it
+        // lists nobody it writes the call's result and the pinned word itself.
+        pf.list = l1; pf.cnt = cnt; pf.list2 = l2; pf.best_out = d_best; pf.stat = g->hprune_stat;
+        CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l1, cnt, k1, q2, Rpad, mu2, 0, &pf, cnt + PRUNE_ARRIVE));
+        const int64_t cap = R - k1;   // worst case of round 2's list
+        pf.list = l2; pf.cnt = cnt + 1; pf.list2 = nullptr;
+        if (cap > 0 && !long_form) {
+            // steady form, ONE launch for a list of any length: a fixed grid whose workgroups loop over the column groups; its last
+            // arriver finishes the round and writes the result.  An empty list: every workgroup leaves, round 1 has written it.
+            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, INT_MAX, q2, Rpad, mu2, PRUNE_R2_GROUPS, &pf, cnt + PRUNE_ARRIVE + 1));
+        } else if (cap > 0) {
+            // long form, when a long list is expected: the row-split kernel takes lists of up to PRUNE_ROWS_CAP candidates, the gathered
+            // rows and k_trigemm_sq the longer ones -- both are enqueued and the device-side count picks (cnt[2]: k_trigemm_sq's
+            // count, 0 when the list is short); the finish is a launch of its own
+            if (cap > PRUNE_ROWS_CAP) {
+                hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, (const int*)l2, (const unsigned*)(cnt + 1),
+                                   (const double*)g->dKsT, ld, Npad, ks2, PRUNE_ROWS_CAP, cnt + 2);
+                fz.live = cnt + 2;
+                CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
+            }
+            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, (int)std::min<int64_t>(cap, PRUNE_ROWS_CAP), q2, Rpad, mu2));
+            hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
+            HIPCHK(hipGetLastError());
+        }
+        t_end(g);
+        return 0;
+    }
+    // the measurement knobs that change the row pieces or the loop (rows_halves empty): both rounds keep k_trigemm_sq on gathered rows
+    // and k_prune_finish
     for (int round = 0; round < 2; ++round) {
         const int* list = round == 0 ? l1 : l2;
         const unsigned* c = cnt + round;
         const int64_t cap = round == 0 ? k1 : R - k1;   // worst case of the list's length
-        if (cap > 0 && nh > 0 && cap <= PRUNE_ROWS_CAP) {   // (round 1: always)
-            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, list, c, (int)cap, q2, Rpad, mu2));
-        } else if (cap > 0) {
-            // the row-split kernel takes lists of up to PRUNE_ROWS_CAP candidates, the gathered rows and k_trigemm_sq the longer ones:
-            // both launches are enqueued and the device-side count picks (cnt[2]: k_trigemm_sq's count, 0 when the list is short)
-            const int sq_min = nh > 0 ? PRUNE_ROWS_CAP : -1;
+        if (cap > 0) {
             hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, list, c, (const double*)g->dKsT, ld, Npad, ks2,
-                               sq_min, cnt + 2);
+                               -1, cnt + 2);
             fz.live = cnt + 2;
             CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
-            if (nh > 0) CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, list, c, PRUNE_ROWS_CAP, q2, Rpad, mu2));
         }
         pf.list = list; pf.cnt = c;
-        pf.best_out = round == 1 ? d_best : nullptr; pf.best_off = (long long)best_off;
+        pf.best_out = round == 1 ? d_best : nullptr;
         pf.stat = round == 1 ? g->hprune_stat : nullptr;
         // round 1's finish goes on to list round 2 (its tail); round 2's is the same kernel without it
-        pf.ub = ub; pf.mark = mark; pf.R = R; pf.list2 = round == 0 ? l2 : nullptr; pf.cnt2 = cnt + 1;
+        pf.list2 = round == 0 ? l2 : nullptr;
         hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
         HIPCHK(hipGetLastError());
     }
@@ -2517,11 +2554,14 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
 constexpr int PRUNE_BACKOFF = 31;
 static bool prune_wanted(bohip_gp* g, int64_t R) {
     if (g->prune_skip > 0) { --g->prune_skip; return false; }
+    g->prune_seen = 0u;
     if (g->hprune_stat) {
         const unsigned n2 = __atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
+        g->prune_seen = n2;
         if ((int64_t)n2 > R / 8) {
             __atomic_store_n(g->hprune_stat, 0u, __ATOMIC_RELAXED);
             g->prune_skip = PRUNE_BACKOFF - 1;
+            g->prune_retry = true;   // (the word no longer says why: the call after the back-off expects a long list)
             return false;
         }
     }
@@ -2553,7 +2593,10 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
                g->batch_hint == 0 && prune_wanted(g, R)) {
         // value-only: only the winner leaves the call -- candidates that provably cannot win are not contracted past m row tiles.
         // Not for shards of a larger set (batch_hint: the sharded entry points and bohip_gp_set_batch_hint): see DESIGN.md 6d.
-        return pruned_pass(g, dXs, R, m, ap, d_best, best_off);
+        // round 2's form (either gives the same record): the long one when the last figure read or a back-off announces a long list
+        const bool want_long = g->prune_retry || g->prune_seen > (unsigned)PRUNE_ROWS_CAP;
+        g->prune_retry = false;
+        return pruned_pass(g, dXs, R, m, ap, d_best, best_off, nullptr, g->prune_r2_form < 0 ? want_long : g->prune_r2_form == 1);
     } else if (g_fuse_finish) {
         // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
         // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
@@ -4383,9 +4426,10 @@ int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, 
     return pruned_pass(g, g->dXs, R, m, ap, nullptr, 0, ub);
 }
 // tests only (tests/test_prune_rows_gpu.py): the partial sums q[2T][R] and mu_raw[R] of R host candidates from the full pass's
-// k_trigemm_sq (path 0) or from k_trigemm_rows over every row tile, the candidates listed in reverse order (path 1)
+// k_trigemm_sq (path 0) or from k_trigemm_rows over every row tile, the candidates listed in reverse order (path 1; path 2: the
+// same with ONE column group in the grid, every further group from the kernel's loop)
 int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int path, double* q_out, double* mu_out) {
-    if (!g || R <= 0 || !Xs || !q_out || !mu_out || (path != 0 && path != 1)) return fail(BOHIP_E_ARG, "bad arguments");
+    if (!g || R <= 0 || !Xs || !q_out || !mu_out || path < 0 || path > 2) return fail(BOHIP_E_ARG, "bad arguments");
     HIPCHK(hipSetDevice(g->device));
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     CHK(ensure_fresh(g));
@@ -4397,7 +4441,7 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
     const int T = (int)(Npad / TILE);
     CHK(ensure_pieces(g, T, N));
     const std::vector<int> hv = rows_halves(g->hpieces);
-    if (path == 1 && hv.empty()) return fail(BOHIP_E_UNSUPPORTED, "row pieces k_trigemm_rows does not reproduce");
+    if (path != 0 && hv.empty()) return fail(BOHIP_E_UNSUPPORTED, "row pieces k_trigemm_rows does not reproduce");
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     CHK(launch_kstar_any(g, g->dXs, 0, R, Npad, make_hyper(g)));
     std::vector<double> q((size_t)2 * T * Rpad), mu((size_t)Rpad);
@@ -4421,7 +4465,7 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
     hipMemcpyAsync(d + o_h, hv.data(), hv.size() * 4, hipMemcpyHostToDevice, g->stream);
     hipMemcpyAsync(d + o_c, &n, 4, hipMemcpyHostToDevice, g->stream);
     rc = launch_trigemm_rows(g, g->dKsT, (const int*)(d + o_h), (int)hv.size(), (const int*)(d + o_l), (const unsigned*)(d + o_c), (int)R,
-                             (double*)(d + o_q), Rpad, (double*)(d + o_mu));
+                             (double*)(d + o_q), Rpad, (double*)(d + o_mu), path == 2 ? 1 : 0);
     hipMemcpyAsync(q.data(), d + o_q, q.size() * 8, hipMemcpyDeviceToHost, g->stream);
     hipMemcpyAsync(mu.data(), d + o_mu, mu.size() * 8, hipMemcpyDeviceToHost, g->stream);
     const hipError_t e = hipStreamSynchronize(g->stream);
@@ -4437,6 +4481,12 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
 int64_t bohip_debug_prune_stat(bohip_gp* g) {
     if (!g || !g->hprune_stat) return -1;
     return (int64_t)__atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
+}
+// tests only: round 2's form in the handle's pruned calls -- -1 the library's rule, 0 the steady form (one launch), 1 the long form
+int bohip_debug_prune_round2_form(bohip_gp* g, int form) {
+    if (!g || form < -1 || form > 1) return fail(BOHIP_E_ARG, "bad arguments");
+    g->prune_r2_form = form;
+    return 0;
 }
 int bohip_debug_set_chol_inv_g(int g_new) {
     return g_chol_inv_g.exchange(std::min(64, std::max(0, g_new)));   // (atomic; a refit in flight on another thread may see either value)

@@ -726,6 +726,7 @@ __device__ __forceinline__ unsigned long long prune_key_bits(double v) {
     return (b >> 63) ? ~b : b | 0x8000000000000000ull;   // > 0 for every double: 0 marks "no candidate"
 }
 constexpr int SELECT_THREADS = 1024, SELECT_PER = 8;
+constexpr int PRUNE_ARRIVE = 4;   // cnt[]: 0, 1 the rounds' list lengths, 2 k_trigemm_sq's count, 4, 5 the rounds' arrival counters
 __global__ __launch_bounds__(SELECT_THREADS) void k_prune_select(const double* __restrict__ ub, int64_t R, int k1, int* __restrict__ list1,
                                                                  int* __restrict__ mark, unsigned* __restrict__ cnt, Best* __restrict__ rec) {
     __shared__ uint4 hist[3][64];   // [.][l]: the counts of the digits 4 l .. 4 l + 3
@@ -813,6 +814,8 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_prune_select(const double* _
     if (t == 0) {
         cnt[0] = (unsigned)k1;
         cnt[1] = 0u;
+        cnt[PRUNE_ARRIVE] = 0u;       // the rounds' arrival counters (k_trigemm_rows): their last arrivers leave them at zero, but a
+        cnt[PRUNE_ARRIVE + 1] = 0u;   // call that died between two launches does not
         rec->val = -INFINITY;
         rec->idx = -1;
     }
@@ -829,6 +832,113 @@ __global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ li
     const d2* s = reinterpret_cast<const d2*>(src + (int64_t)list[i] * ld);
     d2* d = reinterpret_cast<d2*>(dst + (int64_t)i * ld);
     for (int64_t j = threadIdx.x; j < ncols / 2; j += 256) d[j] = s[j];
+}
+
+// exact scores of the listed candidates: q in the fused finish's order (t < m from phase A at the candidate's index, t >= m from
+// the round's own launch at its list position), mu from the round; the round's best is merged into the call's record.
+struct PruneFinish {
+    const int* list;
+    const unsigned* cnt;
+    const double *q, *q2, *mu2;
+    int64_t ldq, ldq2;
+    int m, T;
+    double sigma2, beta;
+    AcqParams ap;
+    Best* rec;
+    Best* best_out;       // nullable: the call's result.  The last round writes it; round 1 (list2 != nullptr) when it lists nobody for round 2
+    long long best_off;
+    unsigned* stat;       // nullable (pinned host word): round 2's list length, read by the host's path choice of a later call --
+                          // written with best_out (by round 1: the 0 of its empty list)
+    // round 1 only (list2 != nullptr): the tail that lists round 2
+    const double* ub;     // [R] the bounds
+    const int* mark;      // [R] k_prune_select's "in round 1"
+    int64_t R;
+    int* list2;
+    unsigned* cnt2;
+};
+// One workgroup of NT threads, all of them: k_prune_finish's, or the workgroup of k_trigemm_rows that arrived last in its round.  The
+// record is reduced by `better`, a total order, so it does not depend on NT.  sh: NT / 64 records, tail_L, tail_n: one word each (LDS).
+template <int NT>
+__device__ __forceinline__ void prune_finish_body(const PruneFinish& pf, Best* sh, double* tail_L, unsigned* tail_n) {
+#pragma clang fp contract(off)
+    const int n = (int)*pf.cnt;
+    double v = -INFINITY;
+    long long idx = -1;
+    for (int i = threadIdx.x; i < n; i += NT) {
+        const int64_t r = pf.list[i];
+        double q = 0.0;
+        for (int t0 = 0; t0 < pf.T; t0 += 8) {   // the sum in its order, sixteen loads in flight (a pair at a time: 8 us for 24 pairs, profiles/prune_select_ab.txt)
+            double a[8], b[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int t = min(t0 + u, pf.T - 1);
+                const double* src = t < pf.m ? pf.q + r : pf.q2 + i;
+                const int64_t ld = t < pf.m ? pf.ldq : pf.ldq2;
+                a[u] = src[(int64_t)(2 * t) * ld];
+                b[u] = src[(int64_t)(2 * t + 1) * ld];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (t0 + u < pf.T) q += a[u] + b[u];
+        }
+        double s2 = pf.sigma2 - q;
+        if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
+        const double mu = pf.beta + pf.mu2[i];
+        const double f = acq_eval(pf.ap, mu, s2);
+        if (better(f, r, v, idx)) { v = f; idx = r; }
+    }
+    block_argmax(v, idx, sh);
+    const bool last_round = !pf.list2;
+    if (threadIdx.x == 0) {
+        const Best b = *pf.rec;
+        if (better(b.val, b.idx, v, idx)) { v = b.val; idx = b.idx; }
+        pf.rec->val = idx >= 0 ? v : -INFINITY;
+        pf.rec->idx = idx;
+        if (pf.best_out && last_round) {
+            pf.best_out->val = idx >= 0 ? v : -INFINITY;
+            pf.best_out->idx = idx >= 0 ? idx + pf.best_off : -1;
+        }
+        if (pf.stat && last_round) *pf.stat = (unsigned)n;
+        *tail_L = idx >= 0 ? v : -INFINITY;
+        *tail_n = 0u;
+    }
+    // round 2's list: candidates outside round 1 whose bound is not below round 1's exact best (order is immaterial: every listed
+    // candidate is scored on its own and the record is reduced by `better`).  The same workgroup, after its record: no other
+    // workgroup waits on it, the next launch reads the list.
+    if (last_round) return;
+    __syncthreads();
+    const double L = *tail_L;
+    for (int64_t r0 = threadIdx.x; r0 < pf.R; r0 += 8 * NT) {   // eight loads of each in flight
+        int mk[8];
+        double u[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int64_t r = min(r0 + NT * i, pf.R - 1);
+            mk[i] = pf.mark[r];
+            u[i] = pf.ub[r];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (r0 + NT * i < pf.R && !mk[i] && !(u[i] < L)) pf.list2[atomicAdd(tail_n, 1u)] = (int)(r0 + NT * i);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned n2 = *tail_n;
+        *pf.cnt2 = n2;
+        if (n2 == 0u) {   // nobody for round 2: round 1's record is the call's (v, idx are still the merged record here)
+            if (pf.best_out) {
+                pf.best_out->val = idx >= 0 ? v : -INFINITY;
+                pf.best_out->idx = idx >= 0 ? idx + pf.best_off : -1;
+            }
+            if (pf.stat) *pf.stat = 0u;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
+    __shared__ Best sh[4];
+    __shared__ double tail_L;
+    __shared__ unsigned tail_n;
+    prune_finish_body<256>(pf, sh, &tail_L, &tail_n);
 }
 
 // ---- the exact rounds, row-split: k_trigemm_rows ------------------------------------------------------------------------------
@@ -849,10 +959,12 @@ __global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ li
 // knobs (halved tiles, BOHIP_KS8=0) the pruned pass keeps k_trigemm_sq for its rounds.
 // Sizing: a workgroup is 8 waves (h x four 16-row quarters: two waves per SIMD) against RS_COLS = 8 candidates, 2 accumulator chains
 // of 8 x 8 per wave, 4 MFMAs per wave and chunk; round 1 of 64 candidates at T = 24 is 41 halves x 8 groups = 328 workgroups, two
-// to a CU (RS_DEPTH = 7 buffers of 9 KB).  The operands come by LDS-DMA as whole 128-B rows, RS_DEPTH chunks deep, one barrier per
-// chunk, and the fragment reads of chunk kc + 1 are issued before the MFMAs of chunk kc into a second register set, so the LDS
-// latency runs under the matrix pipe.  The buffer of chunk kc is free as soon as every wave holds the chunk in registers: RS_DEPTH
-// buffers keep RS_DEPTH - 1 chunks in flight.
+// to a CU with 7 buffers of 9 KB, one with the RS_DEPTH = 8 kept (72 KB beside 12 KB of static LDS).  The operands come by LDS-DMA
+// as whole 128-B rows, and the fragment reads of chunk kc + 1 are issued before the MFMAs of chunk kc into a second register set,
+// so the LDS latency runs under the matrix pipe.  One vmcnt wait, one barrier and the DMA issue of two chunks per PAIR of chunks:
+// at the pair (kc, kc + 1) chunks kc + 1 and kc + 2 have landed, every wave holds chunk kc in registers and is done with chunk
+// kc - 1, so those two buffers are refilled (chunks kc + RS_DEPTH - 1 and kc + RS_DEPTH); RS_DEPTH - 4 chunks stay in flight
+// under the pair's MFMAs.  RS_DEPTH is even: the ring turns in pairs.
 // Measured on MI355X (round 1 at N = 3000, 64 candidates, 188 chunks in the longest half; profiles/prune_rows_pipeline_ab.txt):
 //   operands loaded straight into VGPRs (16-B fragments, each fetched by two lanes, every 128-B row by two waves)   129 us
 //     ... with 8 waves of 16 rows and more loads in flight (the per-CU fetch of scattered fragments bound it)        170 us
@@ -861,9 +973,23 @@ __global__ __launch_bounds__(256) void k_prune_gather(const int* __restrict__ li
 //     ... 9 / 12 buffers: 59.9 / 60.5 us (fetch latency is not on the path); without the DMA re-issue: 46.7 us
 //   this loop (reads one chunk ahead, K*' issued once), columns x waves x buffers:
 //     16 x 4 x 6: 51.8    16 x 4 x 12: 53.6    16 x 8 x 6: 49.2    16 x 8 x 12: 49.3
-//      8 x 4 x 7: 45.4     8 x 4 x 12: 44.8     8 x 8 x 12: 42.8 (one workgroup a CU)     8 x 8 x 7: 42.6 us  <- kept
+//      8 x 4 x 7: 45.4     8 x 4 x 12: 44.8     8 x 8 x 12: 42.8 (one workgroup a CU)     8 x 8 x 7: 42.6 us  <- kept then
+//   with the round's finish in the launch (profiles/prune_round2_ab.txt; the parent's 8 x 8 x 7 kernel + its k_prune_finish launch
+//   are 41.4 + 8.6 = 50.1 us there), 8 columns x 8 waves:
+//     one barrier per chunk, 7 buffers                              54.9 us   (min 53.4, p90 56.3)
+//     one barrier per pair of chunks, 6 buffers (two workgroups a CU) 50.8 us
+//     one barrier per pair of chunks, 8 buffers (one workgroup a CU)  46.2 us  <- kept
 // The column groups of a half run on one XCD: W's rows come from the Infinity Cache once per XCD.
-constexpr int RS_COLS = 8, RS_WAVES = 8, RS_THREADS = 64 * RS_WAVES, RS_DEPTH = 7;
+// A workgroup takes the column groups grp0, grp0 + G, ... of its half until the list ends: round 1 (G = 8 for 64 candidates) and the
+// long form of round 2 (G sized for the launch's cap) run one group per workgroup, the steady form of round 2 is a fixed grid of
+// G = 8 groups for a list of any length (bohip.hip pruned_pass).  Between two groups the DMA is drained and a barrier stands before
+// the ring, xch and vb are reused.
+// The round finishes in the launch (RowsParams::finish): every workgroup that stored arrives at the round's counter, and the last
+// one runs prune_finish_body -- the code of k_prune_finish -- on data that is complete; nothing waits on another workgroup.  The
+// hand-over is the agent-scope release / acquire of the fused finish of k_trigemm_sq in its counter form (see the kernel's end).
+// The expected count comes from the list's length on the device.  The counter is left at zero by the last arriver and zeroed by
+// k_prune_select in every call (a call that died between two launches leaves it anywhere).
+constexpr int RS_COLS = 8, RS_WAVES = 8, RS_THREADS = 64 * RS_WAVES, RS_DEPTH = 8;
 constexpr int RS_RG = 16 / RS_WAVES;   // 8-row groups per wave
 constexpr int RS_BUF = (64 + RS_COLS) * KC;                  // doubles of one chunk's operands in LDS
 constexpr int RS_LDS_BYTES = RS_DEPTH * RS_BUF * 8;          // dynamic LDS of k_trigemm_rows
@@ -881,6 +1007,10 @@ struct RowsParams {
     double* q;               // [2 rt + hh][ldq] at the list position
     int64_t ldq;
     double* mu;              // [list position]
+    // the round finishes in this launch (finish != 0): a workgroup that has stored arrives at *arrive, the last one scores and reduces
+    int finish;
+    unsigned* arrive;        // zero before the launch (k_prune_select) and after it (the last arriver)
+    PruneFinish pf;
 };
 __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
     __shared__ double xch[2 * 64 * RS_COLS];     // the h = 1 waves' chains
@@ -888,9 +1018,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
     // an XCD owns the halves x, x + 8, ... (block b runs on XCD b % 8) with all their candidate groups: W's rows are fetched once
     // per XCD, and the heaviest halves start first
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int hi = xcd + 8 * (slot / rp.G), grp = slot % rp.G;
+    const int hi = xcd + 8 * (slot / rp.G), grp0 = slot % rp.G;
     const int n = (int)*rp.cnt;
-    if (hi >= rp.NH || n > rp.cnt_max || grp * RS_COLS >= n) return;
+    if (hi >= rp.NH || n > rp.cnt_max || grp0 * RS_COLS >= n) return;
     const int code = __builtin_amdgcn_readfirstlane(rp.halves[hi]);
     const int rt = code & 0xffff, hh = (code >> 16) & 1;
     const bool solo = (code >> 17) & 1;
@@ -908,8 +1038,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
     const int prow = lane >> 3, sseg = (lane & 7) ^ prow;
     const bool has_b = wave == 0;
     const double* a_src0 = rp.W + ((int64_t)rt * TILE + 64 * hh + 8 * wave + prow) * rp.ldw + 2 * sseg;
-    const int ib = grp * RS_COLS + prow;
-    const double* b_src = rp.KsT + (int64_t)(ib < n ? rp.list[ib] : rp.list[0]) * rp.ldk + 2 * sseg;
+    const double* b_src = nullptr;   // (per column group, below)
     auto issue = [&](int kc, int buf) {
         kc = min(kc, kc_end - 1);   // (past the end: a harmless re-read into a free buffer that keeps the wait counts straight)
         double* d = rs_ring + buf * RS_BUF;
@@ -928,7 +1057,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
     const uint32_t fa = ring0 + (uint32_t)(((8 * RS_RG * wq + rr) * KC + 2 * (S ^ rr)) * 8);
     const uint32_t fb = ring0 + (uint32_t)(((64 + cc) * KC + 2 * (S ^ cc)) * 8);
     // the fragment reads of a chunk are issued one chunk AHEAD of their MFMAs, into the register set the MFMAs of the chunk before
-    // last used: the LDS latency runs under the matrix pipe.  `landed` is the wait that ends the chunk.
+    // last used: the LDS latency runs under the matrix pipe.  `landed` is the wait that ends the chunk.  The vmcnt wait, the barrier
+    // and the DMA issue come once per PAIR of chunks.
     // INVARIANT (the compiler does not know that the asm reads of `frags` complete later): between a set's `frags` and its `landed`
     // no instruction may read, copy or spill a register of the set.  The source keeps it by touching the set in those two asm
     // statements only, by ending every chunk with `landed` (no set is in flight across the loop's back edge or a phi) and by the
@@ -952,16 +1082,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
         for (int i = 0; i < RS_RG; ++i)
 #pragma unroll
             for (int j = 0; j < 1; ++j) acc[i][j] = acc2[i][j] = 0.0;
-        // chunk kc: its operands (in the registers `av`, `bv`) against the accumulators, while chunk kc + 1's are read into `avn`, `bvn`
-        auto step = [&](int kc, int cur, const d2 (&av)[RS_RG], const d2 (&bv)[1], d2 (&avn)[RS_RG], d2 (&bvn)[1]) {
-            // chunk kc + 1 has landed (the RS_DEPTH - 2 later ones stay in flight); after the barrier every wave's pieces of it are in
-            // LDS and every wave holds chunk kc in registers (its `landed`), so the next issue refills the buffer of chunk kc
-            wait_left(std::integral_constant<int, RS_DEPTH - 2>{});
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-            issue(kc + RS_DEPTH, cur);
-            frags(cur + 1 == RS_DEPTH ? 0 : cur + 1, avn, bvn);
-            __builtin_amdgcn_sched_barrier(0);
+        // the MFMAs of chunk kc on the registers `av`, `bv`
+        auto mmas = [&](int kc, const d2 (&av)[RS_RG], const d2 (&bv)[1]) {
             const int skip = kc >= tri_kc ? 2 * (kc - tri_kc) + h - g0 : 0;   // row groups g0 + i, i < skip: all-zero in the block
 #pragma unroll
             for (int i = 0; i < RS_RG; ++i) {
@@ -973,27 +1095,46 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
                     mma_row<1, 0>(av[i], bv, acc[i]);
                 }
             }
-            landed(avn, bvn);
-            __builtin_amdgcn_sched_barrier(0);
         };
+        static_assert(RS_DEPTH % 2 == 0, "a pair of chunks per barrier: the ring turns in pairs");
 #pragma unroll
-        for (int p = 0; p < RS_DEPTH; ++p) issue(p, p);
+        for (int p = 0; p < RS_DEPTH - 1; ++p) issue(p, p);
         d2 av0[RS_RG], bv0[1], av1[RS_RG], bv1[1];
-        wait_left(std::integral_constant<int, RS_DEPTH - 1>{});
+        wait_left(std::integral_constant<int, RS_DEPTH - 2>{});
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         frags(0, av0, bv0);
         landed(av0, bv0);
         __builtin_amdgcn_sched_barrier(0);
-        int cur = 0;
-        for (int kc = 0; kc < kc_end; kc += 2) {   // (kc_end is even; the last step reads ahead into a buffer that holds a re-read)
-            step(kc, cur, av0, bv0, av1, bv1);
-            cur = cur + 1 == RS_DEPTH ? 0 : cur + 1;
-            step(kc + 1, cur, av1, bv1, av0, bv0);
-            cur = cur + 1 == RS_DEPTH ? 0 : cur + 1;
+        int cur = 0;   // buffer of chunk kc
+        for (int kc = 0; kc < kc_end; kc += 2) {   // (kc_end is even; the last pair reads ahead into a buffer that holds a re-read)
+            // ONE wait and ONE barrier per pair: chunks kc + 1 and kc + 2 have landed (the RS_DEPTH - 4 later ones stay in flight);
+            // after the barrier every wave's pieces of them are in LDS, every wave holds chunk kc in registers and is done with
+            // chunk kc - 1: the two issues refill those two buffers
+            wait_left(std::integral_constant<int, RS_DEPTH - 4>{});
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            const int prev = cur == 0 ? RS_DEPTH - 1 : cur - 1, b1 = cur + 1, b2 = cur + 2 == RS_DEPTH ? 0 : cur + 2;
+            issue(kc + RS_DEPTH - 1, prev);
+            issue(kc + RS_DEPTH, cur);
+            frags(b1, av1, bv1);
+            __builtin_amdgcn_sched_barrier(0);
+            mmas(kc, av0, bv0);
+            landed(av1, bv1);
+            __builtin_amdgcn_sched_barrier(0);
+            frags(b2, av0, bv0);
+            __builtin_amdgcn_sched_barrier(0);
+            mmas(kc + 1, av1, bv1);
+            landed(av0, bv0);
+            __builtin_amdgcn_sched_barrier(0);
+            cur = b2;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
+    // the column groups grp0, grp0 + G, ... of this half until the list ends (round 1 and the long form's launch: one group)
+    for (int grp = grp0; grp * RS_COLS < n; grp += rp.G) {
+    const int ib = grp * RS_COLS + prow;
+    b_src = rp.KsT + (int64_t)(ib < n ? rp.list[ib] : rp.list[0]) * rp.ldk + 2 * sseg;
     if (solo) run(std::true_type{});
     else run(std::false_type{});
     // fold the contraction halves in the loop's order, then v into vb in the rows' order
@@ -1023,7 +1164,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
             }
     }
     __syncthreads();
-    if (wave >= 1) return;
+    if (wave == 0) {
     // wave 0: the 8 candidate columns in k_trigemm_sq's accumulator layout (lane (k, b, t): column 4 (b & 1) + t)
     const int col = 8 * wave + 4 * (b & 1) + (lane & 3), i_list = grp * RS_COLS + col;
     const int64_t row_base = (int64_t)rt * TILE + 64 * hh;
@@ -1043,95 +1184,37 @@ __global__ __launch_bounds__(RS_THREADS) void k_trigemm_rows(RowsParams rp) {
         rp.q[(int64_t)(2 * rt + hh) * rp.ldq + i_list] = s;
         if (solo) rp.q[(int64_t)(2 * rt + 1) * rp.ldq + i_list] = 0.0;   // no sibling half: its slot is zero
     }
-}
-
-// exact scores of the listed candidates: q in the fused finish's order (t < m from phase A at the candidate's index, t >= m from
-// the round's own launch at its list position), mu from the round; the round's best is merged into the call's record.
-struct PruneFinish {
-    const int* list;
-    const unsigned* cnt;
-    const double *q, *q2, *mu2;
-    int64_t ldq, ldq2;
-    int m, T;
-    double sigma2, beta;
-    AcqParams ap;
-    Best* rec;
-    Best* best_out;       // nullable: the call's result (last round)
-    long long best_off;
-    unsigned* stat;       // nullable (pinned host word): the round's list length, read by the host's path choice of a later call
-    // round 1 only (list2 != nullptr): the tail that lists round 2
-    const double* ub;     // [R] the bounds
-    const int* mark;      // [R] k_prune_select's "in round 1"
-    int64_t R;
-    int* list2;
-    unsigned* cnt2;
-};
-__global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
-#pragma clang fp contract(off)
-    __shared__ Best sh[4];
-    __shared__ double tail_L;
-    __shared__ unsigned tail_n;
-    const int n = (int)*pf.cnt;
-    double v = -INFINITY;
-    long long idx = -1;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int64_t r = pf.list[i];
-        double q = 0.0;
-        for (int t0 = 0; t0 < pf.T; t0 += 8) {   // the sum in its order, sixteen loads in flight (a pair at a time: 8 us for 24 pairs, profiles/prune_select_ab.txt)
-            double a[8], b[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = min(t0 + u, pf.T - 1);
-                const double* src = t < pf.m ? pf.q + r : pf.q2 + i;
-                const int64_t ld = t < pf.m ? pf.ldq : pf.ldq2;
-                a[u] = src[(int64_t)(2 * t) * ld];
-                b[u] = src[(int64_t)(2 * t + 1) * ld];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (t0 + u < pf.T) q += a[u] + b[u];
-        }
-        double s2 = pf.sigma2 - q;
-        if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
-        const double mu = pf.beta + pf.mu2[i];
-        const double f = acq_eval(pf.ap, mu, s2);
-        if (better(f, r, v, idx)) { v = f; idx = r; }
+    // the storing wave drains its stores: before the next group's loads (the ring's waits count loads only) and before the arrival
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    block_argmax(v, idx, sh);
-    if (threadIdx.x == 0) {
-        const Best b = *pf.rec;
-        if (better(b.val, b.idx, v, idx)) { v = b.val; idx = b.idx; }
-        pf.rec->val = idx >= 0 ? v : -INFINITY;
-        pf.rec->idx = idx;
-        if (pf.best_out) {
-            pf.best_out->val = idx >= 0 ? v : -INFINITY;
-            pf.best_out->idx = idx >= 0 ? idx + pf.best_off : -1;
-        }
-        if (pf.stat) *pf.stat = (unsigned)n;
-        tail_L = idx >= 0 ? v : -INFINITY;
-        tail_n = 0u;
-    }
-    // round 2's list: candidates outside round 1 whose bound is not below round 1's exact best (order is immaterial: every listed
-    // candidate is scored on its own and the record is reduced by `better`).  The same workgroup, after its record: no other
-    // workgroup waits on it, the next launch reads the list.
-    if (!pf.list2) return;
+    // the next group reuses the ring, xch and vb: every wave's DMA has landed (run's last wait) and vb has been read
     __syncthreads();
-    const double L = tail_L;
-    for (int64_t r0 = threadIdx.x; r0 < pf.R; r0 += 8 * 256) {   // eight loads of each in flight
-        int mk[8];
-        double u[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int64_t r = min(r0 + 256 * i, pf.R - 1);
-            mk[i] = pf.mark[r];
-            u[i] = pf.ub[r];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (r0 + 256 * i < pf.R && !mk[i] && !(u[i] < L)) pf.list2[atomicAdd(&tail_n, 1u)] = (int)(r0 + 256 * i);
+    }
+    if (!rp.finish) return;
+    // The round's hand-over, agent-scope release / acquire: the stores above are drained and behind a barrier; one lane releases,
+    // waits, and adds to the round's counter.  The workgroup whose arrival completes the count (the halves in the table x the column
+    // groups that have work: padding workgroups and groups past the list never arrive) acquires and finishes the round -- it waits
+    // for nobody: everything it reads is complete.  The flag goes through xch (a further __shared__ object beside the DMA ring can
+    // make the compiler drain vmcnt before every fragment read); xch is free after the barrier that ends the last group.
+    unsigned* flag = reinterpret_cast<unsigned*>(xch + 64);
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned want = (unsigned)rp.NH * (unsigned)min(rp.G, (n + RS_COLS - 1) / RS_COLS);
+        const bool last = __hip_atomic_fetch_add(rp.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == want - 1u;
+        if (last) __hip_atomic_store(rp.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *flag = last;
     }
     __syncthreads();
-    if (threadIdx.x == 0) *pf.cnt2 = tail_n;
+    if (!*flag) return;
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    // (inlined: the kernel then has 101 VGPRs -- still 4 waves a SIMD -- and its SGPR spills lie outside the main loops; behind a
+    // noinline call the callee takes 248 VGPRs and the kernel drops to 2 waves a SIMD)
+    prune_finish_body<RS_THREADS>(rp.pf, reinterpret_cast<Best*>(xch), xch + 32, reinterpret_cast<unsigned*>(xch + 40));
 }
 
 // The exchange step of sharded scoring: `all` holds nrec records per draw-slot layout [rec][S] gathered
