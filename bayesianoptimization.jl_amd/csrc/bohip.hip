@@ -44,7 +44,6 @@
 #include <unistd.h>
 #include <string>
 #include <vector>
-#include <queue>
 
 using namespace bohip;
 
@@ -90,11 +89,8 @@ struct bohip_gp {
     hipStream_t side_stream = nullptr;            // bulk trailing updates of the factorisation run here (look-ahead)
     hipEvent_t ev_panels = nullptr, ev_bulk = nullptr;
     hipStream_t col_stream = nullptr;             // dataflow factorisation: bulk followers + column updates (high priority)
-    hipStream_t inv_stream = nullptr;             // W = L^-1 grows block by block beside the factorisation's diagonal chain
-    hipEvent_t ev_blk = nullptr, ev_inv = nullptr;
+    hipEvent_t ev_inv = nullptr;
     hipEvent_t ev_gate = nullptr;                 // a diagonal-block kernel is about to start: release one piece of the pending bulk update
-    std::vector<hipEvent_t> ev_tier;              // its cross-stream hand-overs (two per group of four blocks)
-    bool w_seeded = false;                        // the diagonal blocks of W were produced during the factorisation (k_chol_inverter)
     ExTask* dex_tasks = nullptr;                  // task records of the executor form (kernels_exec.hip), built once per (buffers, T)
     size_t ex_cap = 0;
     bool ex_bulk4_ok = false;   // the bulk queue may be claimed two tiles at a time (exec_bulk_stride_ok)
@@ -196,7 +192,7 @@ struct bohip_gp {
     int alpha_inc_run = 0;         // appends since alpha was last computed in full (compute_alpha); the incremental form re-synchronises every 256
     bool mirror_dirty = false;     // a staged append failed after the host mirrors advanced: the next refit uploads X and y again
     int64_t chol_lock_skips = 0;   // refits that took the launch-chained form because another process held the refit lock
-    int chol_form_last = 0;            // BOHIP_INFO_CHOL_FORM: 0 launch chain, 1 dataflow form 1, 2 form 2, 3 form 2 left-looking, 4 executor
+    int chol_form_last = 0;            // BOHIP_INFO_CHOL_FORM: 0 launch chain, 4 executor (1-3: retired forms, never reported)
     int64_t chol_fallbacks = 0;        // BOHIP_INFO_CHOL_FALLBACKS: refits of this handle that timed out on a dependency and were redone launch-chained
     int chol_abort_T = 0;              // BOHIP_INFO_CHOL_ABORT_TILES: row tiles of the last factorisation that timed out (0: never)
     // jitter escalation on a failed factorisation (GaussianProcesses.jl make_posdef!, UPSTREAM-UNVERIFIED: off by default)
@@ -343,9 +339,6 @@ static int alloc_model(bohip_gp* g, int64_t cap) {
 }
 
 // ---- GEMM launcher --------------------------------------------------------------------------------
-static int g_inv_overlap = 0;  // BOHIP_INV_OVERLAP=1: grow W = L^-1 block by block beside the factorisation instead of after it.
-                               // Measured: refit 3.67 -> 3.56 ms (N=3000), 21.4 -> 19.9 ms (N=10000), but the factorisation itself slows
-                               // down under the competition (2.90 -> 3.08 ms, 13.9 -> 17.7 ms), so it stays opt-in.
 static int g_bulk_pieces = 4;   // gated pieces of the side-stream bulk update per outer block (BOHIP_BULK_PIECES; 0/1: one launch)
 static int g_sample_mfma_min = 200;  // BOHIP_SAMPLE_MFMA_MIN: draws from which bohip_gp_sample_joint takes k_sample_mfma instead of k_sample_rows
                                      // (measured at R = 4096: the two cross between 192 and 256 draws, kernels_sample.hip)
@@ -366,16 +359,8 @@ static int g_small_r = -1;  // batches up to this size (<= 256) take the row-wis
                             // break-even with the MFMA path (N=500: > 256, N=3000: ~190, N=10000: ~110); BOHIP_SMALL_R overrides: below that
                             // candidates one 64-wide MFMA tile column leaves single workgroups walking the whole K extent
 static int g_inv_hi_h = 16;            // levels of the triangular inverse with half-size >= this many tiles run as throughput launches (BOHIP_INV_HI_H)
-static int g_chol_df2_ll = 1;          // left-looking window updates (cholesky_dataflow3) instead of cholesky_dataflow2's K = 128 ones: N=8000 7.46 vs
-                                       // 7.63 ms, N=10000 11.7 vs 11.9, N=12000 16.5 vs 18.9 (BOHIP_CHOL_DF2_LL=0: the latter)
-static int g_chol_df2_coal = 1;        // its K = 512 launches store through LDS in 16-byte pieces (BOHIP_CHOL_DF2_COAL=0: from the MFMA layout)
-static int g_chol_df2_hi = 1;          // its K = 512 launches with two workgroups per CU (BOHIP_CHOL_DF2_HI=0: one)
-static int g_chol_df2_win = 6;         // its window: block k's flagged update reaches column 4 (k / 4) + win (BOHIP_CHOL_DF2_WIN, 6..10; 6 is the least that keeps the chain's next tiles inside)
-static int g_chol_df2_min = 47;  // cholesky_dataflow2 (large-T form) from this many row tiles on (BOHIP_CHOL_DF2_MIN): N=6000 5.13 vs 5.3 ms, N=8000 7.8
-                                 // vs 8.65, N=10000 12.1 vs 13.06, N=11000 14.6 vs 15.4; below (N=5600) the first form is faster (4.58 vs 4.78)
-static int g_chol_df = 1;  // dataflow factorisation (kernels_chol.hip) for 3 <= T <= g_chol_df_tmax row tiles: N=3000 1.66 vs 2.71 ms, N=1000 0.57
-                            // vs 0.82 ms.  Far beyond that its one-tier K=128 bulk updates lose to the two-tier launch chain, below 3 there is
-                            // nothing to pipeline.  BOHIP_CHOL_DATAFLOW=0 disables, =2 forces it for every 2 <= T <= CHOL_DF_TCAP.
+static int g_chol_df = 1;  // dataflow factorisation (the executor form: kernels_chol.hip + kernels_exec.hip) for up to g_chol_df_tmax row tiles, see refit_once:
+                            // N=3000 1.66 vs 2.71 ms, N=1000 0.57 vs 0.82 ms against the launch chain.  BOHIP_CHOL_DATAFLOW=0 disables, any other value is on.
 static bool g_chol_df_strict = false;   // BOHIP_CHOL_DF_STRICT: a timed-out dependency is an error instead of a fall-back (tests, tools)
 static bool g_chol_df_dump = false;     // measurement builds: the flags of a timed-out factorisation on stderr
 static int g_chol_df_tmax = 96;   // = CHOL_DF_TCAP, N <= ~12200 (N=12000: 16.5 vs 18.5 ms for the launch chain)
@@ -383,11 +368,7 @@ static int g_chol_df_tmax = 96;   // = CHOL_DF_TCAP, N <= ~12200 (N=12000: 16.5 
 // switches the PROCESS to the launch chain -- for the next `skip` refits, not for good: the cause is usually transient, a
 // time-out costs one bounded wait (200 ms), and every further time-out doubles the pause (8, 24, 56, ... up to 1024 refits).
 static std::atomic<int> g_chol_df_skip{0}, g_chol_df_backoff{0};
-static unsigned long long g_chol_spin_ticks = CH_SPIN_TICKS_DEFAULT;   // BOHIP_CHOL_SPIN_US: bound of every in-kernel wait of the dataflow forms
-static int g_chol_exec = 1;       // executor form (kernels_exec.hip, cholesky_exec) from g_chol_exec_min row tiles on (BOHIP_CHOL_EXEC=0: the stream-based second form)
-static int g_chol_exec_min = -1;  // BOHIP_CHOL_EXEC_MIN, row tiles.  Default: 4 with the executor's inverse queues (factorisation + inverse: N=500 0.41 ms against
-                                  // 0.51 for the first dataflow form + the inverse behind it, N=1000 0.70 / 0.87, N=3000 2.02 / 2.49, N=4000 2.96 / 3.50), 32 without
-                                  // them (the factorisation alone: N=3000 1.75 against 1.67 for the first form, N=4000 2.42 / 2.49, N=5000 3.23 / 3.75)
+static unsigned long long g_chol_spin_ticks = CH_SPIN_TICKS_DEFAULT;   // BOHIP_CHOL_SPIN_US: bound of every in-kernel wait of the dataflow form
 static int g_chol_exec_patience_us = 1000;   // BOHIP_CHOL_EXEC_PATIENCE_US: how long a workgroup only polls a held record before it takes other work meanwhile
 static int g_chol_exec_fill_inv = 1;    // a workgroup waiting for the counters of a claimed task runs inverse-wave tasks meanwhile (BOHIP_CHOL_EXEC_FILL_INV)
 static int g_chol_exec_inv_pairs = 0;   // inverse queue claimed one record (0) or one tile = two records (1) at a time (BOHIP_CHOL_EXEC_INV_PAIRS)
@@ -396,19 +377,13 @@ static std::atomic<int> g_chol_inv_grp_min{28};   // row tiles from which the in
 static std::atomic<int> g_chol_inv_g{8};      // executor form: W = L^-1 is grown behind the chain by a fifth task queue, in pieces of this many 128-blocks
                                    // of contraction (BOHIP_CHOL_INV_G; 0 = off: the level-by-level inverse runs after the factorisation)
 static int g_chol_nsf = 3;         // solve-follower workgroups of the chain kernel in the executor form (BOHIP_CHOL_NSF, 1..6)
-static int g_chol_copy_early = 1;   // BOHIP_CHOL_COPY_EARLY=0: the copy S -> L behind the executor instead of behind the chain kernel (cholesky_exec)
 static int g_chol_exec_urgent = -1; // executor workgroups that serve the urgent queue only (BOHIP_CHOL_EXEC_URGENT); -1: 32, and 16 from 56 row tiles on
                                     // (N = 10^4: 14.0-14.2 against 14.3 ms; 8 starve the chain at N = 6000: 4.75 against 3.95; profiles/r04_inverse_group_form.txt)
-static int g_chol_exec_fill = 0;   // BOHIP_CHOL_EXEC_FILL=1/2: a workgroup that holds a claimed task whose counters are not in takes bulk work meanwhile (1: Early sums only, 2: also row solves / updates).  Measured without effect on the total (N=10^4: 9.6-9.9 ms in every mode): more workgroups are busy, but the factorisation is paced by the per-block row steps, not by throughput -- so the default stays the simple rule
 static int g_chol_exec_second = 1;   // BOHIP_CHOL_EXEC_SECOND=0: every executor workgroup serves every queue (until round 4).  1: the workgroups beyond one per CU take
                                      // throughput work only (early sums, bulk, waves) and leave when it is exhausted: N = 6000 4.60 -> 4.38 ms, N = 5000 3.27 -> 3.18
-static int g_chol_exec_excl = 0;   // measurement build: more than half a CU's LDS per executor workgroup where the rule says one per CU (no effect measured: the dispatcher places them so already)
 static int g_small_zero_copy = 1;          // small host calls: candidates read from the pinned block (0 in the measurement build: copied to HBM first)
-static int g_chol_exec_early_tail = 0;    // the factorisation ALONE beyond 56 row tiles: two-piece Early sums for the last this-many blocks (the chain-bound tail)
-static int g_chol_exec_early_split = 1;   // Early sums in two pieces (BOHIP_CHOL_EXEC_EARLY_SPLIT=0 in the measurement build: one piece, until round 6)
 static int g_chol_exec_nbu = 2;      // BOHIP_CHOL_EXEC_NBU: rows behind the solve followers whose row step (Solve, Late) sits in the urgent queue
 static int g_chol_exec_fast = -1;    // BOHIP_CHOL_EXEC_FAST: executor workgroups that never take bulk / wave tasks (-1: where CUs hold two executor workgroups and the chain paces, 33 ... 48 row tiles: up to 112)
-static int g_chol_exec_bulk_edf = 0;   // BOHIP_CHOL_EXEC_BULK_EDF=1: bulk queue in earliest-deadline order from a host-side simulation (round-4 experiment: same total, see exec_task_list)
 static int g_chol_exec_pairs = -1; // early sums and bulk updates are claimed two records (= both halves of a tile) at a time (BOHIP_CHOL_EXEC_PAIRS=1; 0: one); p >= 2: the bulk 2 p
                                     // records (p tiles) per claim.  -1: 1, and 2 from 72 row tiles on (N = 10^4 14.05 -> 13.8 ms, N = 12000 23.1 -> 22.6; N = 8000 the same, N = 6000 4.0 -> 4.25)
 static int g_chol_exec_wgs = -1;  // executor workgroups (BOHIP_CHOL_EXEC_WGS); -1: by size -- ONE per free CU up to 32 row tiles, two from 45 on (see cholesky_exec)
@@ -434,14 +409,13 @@ static void read_dev_knobs() {
     struct Knob { const char* name; int* v; int lo, hi; };
     static int chunk_rows = 0, dump = 0;
     const Knob knobs[] = {
-        {"BOHIP_CHOL_DF2_HI", &g_chol_df2_hi, 0, 1}, {"BOHIP_CHOL_DF2_COAL", &g_chol_df2_coal, 0, 1}, {"BOHIP_CHOL_DF2_WIN", &g_chol_df2_win, 6, 10},
-        {"BOHIP_CHOL_DF_TMAX", &g_chol_df_tmax, 0, CHOL_DF_TCAP}, {"BOHIP_INV_HI_H", &g_inv_hi_h, 0, 1 << 20}, {"BOHIP_INV_OVERLAP", &g_inv_overlap, 0, 1},
-        {"BOHIP_CHOL_EXEC_PAIRS", &g_chol_exec_pairs, -1, 64}, {"BOHIP_CHOL_EXEC_FILL", &g_chol_exec_fill, 0, 2}, {"BOHIP_CHOL_COPY_EARLY", &g_chol_copy_early, 0, 1},
+        {"BOHIP_CHOL_DF_TMAX", &g_chol_df_tmax, 0, CHOL_DF_TCAP}, {"BOHIP_INV_HI_H", &g_inv_hi_h, 0, 1 << 20},
+        {"BOHIP_CHOL_EXEC_PAIRS", &g_chol_exec_pairs, -1, 64},
         {"BOHIP_CHOL_EXEC_URGENT", &g_chol_exec_urgent, 1, 1 << 20}, {"BOHIP_CHOL_NSF", &g_chol_nsf, 1, CH_NSF_MAX},
         {"BOHIP_CHOL_EXEC_PATIENCE_US", &g_chol_exec_patience_us, 0, 1 << 30}, {"BOHIP_CHOL_EXEC_FILL_INV", &g_chol_exec_fill_inv, 0, 1},
         {"BOHIP_CHOL_EXEC_INV_PAIRS", &g_chol_exec_inv_pairs, 0, 1}, {"BOHIP_CHOL_EXEC_WGS", &g_chol_exec_wgs, 1, 1 << 20}, {"BOHIP_KS8", &g_ks8, 0, 1},
-        {"BOHIP_CHOL_EXEC_BULK_EDF", &g_chol_exec_bulk_edf, 0, 1}, {"BOHIP_CHOL_EXEC_FAST", &g_chol_exec_fast, -1, 1 << 20},
-        {"BOHIP_CHOL_EXEC_SECOND", &g_chol_exec_second, 0, 1}, {"BOHIP_CHOL_EXEC_EARLY_SPLIT", &g_chol_exec_early_split, 0, 2}, {"BOHIP_CHOL_EXEC_EARLY_TAIL", &g_chol_exec_early_tail, 0, 1 << 20}, {"BOHIP_SMALL_ZERO_COPY", &g_small_zero_copy, 0, 1}, {"BOHIP_CHOL_EXEC_EXCL", &g_chol_exec_excl, 0, 1}, {"BOHIP_CHOL_EXEC_NBU", &g_chol_exec_nbu, 0, 16}, {"BOHIP_CHUNK_ROWS", &chunk_rows, 0, 1 << 30},
+        {"BOHIP_CHOL_EXEC_FAST", &g_chol_exec_fast, -1, 1 << 20},
+        {"BOHIP_CHOL_EXEC_SECOND", &g_chol_exec_second, 0, 1}, {"BOHIP_SMALL_ZERO_COPY", &g_small_zero_copy, 0, 1}, {"BOHIP_CHOL_EXEC_NBU", &g_chol_exec_nbu, 0, 16}, {"BOHIP_CHUNK_ROWS", &chunk_rows, 0, 1 << 30},
         {"BOHIP_TRIGEMM_HALVE_LO", &g_halve_lo, 0, 1 << 20}, {"BOHIP_TRIGEMM_HALVE_HI", &g_halve_hi, 0, 1 << 20}, {"BOHIP_FUSE_FINISH", &g_fuse_finish, 0, 1}, {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16},
         {"BOHIP_APPEND_ALPHA_INC", &g_append_alpha_inc, 0, 1}, {"BOHIP_BULK_PIECES", &g_bulk_pieces, 0, 8}, {"BOHIP_SPLIT", &g_split, 0, 1},
         {"BOHIP_SMALL_R", &g_small_r, 0, SMALL_MAX}, {"BOHIP_SMALL_M", &g_small_m, 0, 1 << 20}, {"BOHIP_CHOL_DF_DUMP", &dump, 0, 1},
@@ -468,11 +442,8 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)k_chol_chain, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void*)k_inv128, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_pair, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_hi, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt_quad, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_chol_exec, hipFuncAttributeMaxDynamicSharedMemorySize, std::max<size_t>(glds3_lds_bytes<4>(), 84 * 1024)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_chol_exec, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trimv_stream<TRIMV_D>, hipFuncAttributeMaxDynamicSharedMemorySize, trimv_lds_bytes(TRIMV_D)));
     HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
     HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
@@ -480,11 +451,7 @@ static int one_time_kernel_setup() {
     // waits, the ascent drivers, the small-batch pass.  Everything else that used to be read here is a constant now; the
     // sweeps under tools/ that vary those constants run against csrc/abl/libbohip_dev.so (read_dev_knobs below).
     if (const char* e = getenv("BOHIP_CHOL_DATAFLOW")) g_chol_df = atoi(e);
-    if (const char* e = getenv("BOHIP_CHOL_DF2_MIN")) g_chol_df2_min = atoi(e);
-    if (const char* e = getenv("BOHIP_CHOL_DF2_LL")) g_chol_df2_ll = atoi(e);
     if (const char* e = getenv("BOHIP_CHOL_SPIN_US")) g_chol_spin_ticks = 100ull * (unsigned long long)std::max(1, atoi(e));
-    if (const char* e = getenv("BOHIP_CHOL_EXEC")) g_chol_exec = atoi(e);
-    if (const char* e = getenv("BOHIP_CHOL_EXEC_MIN")) g_chol_exec_min = atoi(e);
     if (const char* e = getenv("BOHIP_CHOL_INV_G")) g_chol_inv_g = std::min(64, std::max(0, atoi(e)));
     if (const char* e = getenv("BOHIP_CHOL_INV_GRP_MIN")) g_chol_inv_grp_min = std::max(0, atoi(e));
     if (const char* e = getenv("BOHIP_ASC_WG_NMAX")) g_asc_wg_nmax = std::max(0, atoi(e));
@@ -563,26 +530,12 @@ static int inverse_level(bohip_gp* g, hipStream_t st, int t0, int nt, int h) {
     CHK(launch_gemm_nt(g, b, pairs, st, big));
     return 0;
 }
-// inverse_join: the leading P tiles are inverted, so are the nb tiles behind them: fill W[P:P+nb, 0:P] (and its transpose).
-static int inverse_join(bohip_gp* g, hipStream_t st, int P, int nb) {
-    if (P <= 0 || nb <= 0) return 0;
-    const int64_t ld = g->ld;
-    const int64_t off21 = (int64_t)P * TILE * ld, off12 = (int64_t)P * TILE, off22 = (int64_t)P * TILE * (ld + 1);
-    GemmNTParams a{};
-    a.A = g->dWT; a.lda = ld; a.B = g->dS + off21; a.ldb = ld; a.C = g->dS + off12; a.ldc = ld;
-    a.mt = P; a.nt64 = 2 * nb; a.kc = P * (TILE / KC); a.alpha = 1.0; a.beta = 0.0; a.klo_from_m = 1;
-    CHK(launch_gemm_nt(g, a, 1, st));
-    GemmNTParams b{};
-    b.A = g->dW + off22; b.lda = ld; b.B = g->dS + off12; b.ldb = ld; b.C = g->dW + off21; b.ldc = ld;
-    b.CT = g->dWT + off12; b.ldct = ld;
-    b.mt = nb; b.nt64 = 2 * P; b.kc = nb * (TILE / KC); b.alpha = -1.0; b.beta = 0.0; b.khi_from_m = 1;
-    CHK(launch_gemm_nt(g, b, 1, st));
-    return 0;
-}
 
-// ---- A2, dataflow form (kernels_chol.hip): ONE persistent chain launch on the critical stream; the panel followers and the
-// flag-gated trailing updates of every block are enqueued up front on the side stream.  No host events inside the factorisation.
-static size_t chol_abort_word(int T) { return (size_t)T * (CH_PANELS + 7) + (size_t)T * T * (CH_PANELS + 1); }   // see the layout in cholesky_dataflow
+// ---- A2, the flag area of the dataflow factorisation (kernels_chol.hip, kernels_exec.hip), in words:
+//   panel[8 T] | solved[T] | crit[T] | rest[T] | col[T] | farall[T] | fol[T] | colall[T] | colr[T T] | xp[8 T T] | abort word |
+//   the executor's six queue cursors | one spare word | the inverse queues' counters [4 T T] | xp3[8 T] | pre3[4 T]
+// The executor's task records address words by this layout (exec_task_list); words nobody waits on any more stay allocated.
+static size_t chol_abort_word(int T) { return (size_t)T * (CH_PANELS + 7) + (size_t)T * T * (CH_PANELS + 1); }
 static size_t chol_inv_word(int T) { return chol_abort_word(T) + 8; }      // the inverse queue's counters: 4 words per tile (i, j)
 static size_t chol_xp3_word(int T) { return chol_inv_word(T) + (size_t)4 * T * T; }    // per-panel flags of S(k+3, k) (8 per block), then pre3 (4 per block)
 static size_t chol_flag_words(int T) { return chol_xp3_word(T) + (size_t)12 * T; }       // abort word + the executor's queue cursors + those
@@ -605,289 +558,10 @@ static CholFlags chol_flags_layout_at(unsigned* base, double* idl, int T) {
     fl.xp3 = base + chol_xp3_word(T);
     fl.pre3 = fl.xp3 + (size_t)T * CH_PANELS;
     fl.w16_g = idl;
-    fl.resident = fl.abort + 7;   // (the word between the executor's six queue cursors and the inverse queues' counters)
     fl.spin_ticks = g_chol_spin_ticks;
     fl.crit_want = 16u;   // the row-(k+2) update: 4 workgroups x 4 storing waves
     fl.panel_want = 3u;   // three publishing waves per panel
     return fl;
-}
-static int cholesky_dataflow(bohip_gp* g, int T) {
-    const int64_t ld = g->ld;
-    CholFlags fl = chol_flags_layout(g, T);
-    g->w_seeded = false;
-    HIPCHK(hipMemsetAsync(g->dchol_flags, 0, chol_flag_words(T) * sizeof(unsigned), g->stream));
-    HIPCHK(hipEventRecord(g->ev_panels, g->stream));           // K and the cleared flags are in place
-    // Four launches that live for the whole factorisation and talk through flags:
-    //   critical stream: the chain (row owners, critical followers of rows k+1 / k+2, gated update of row k+2)
-    //   two more       : one follower workgroup per row >= 3, two column-updater workgroups per row >= 3
-    hipLaunchKernelGGL(k_chol_chain, dim3(T > 1 ? 8 : 1), dim3(CH_THREADS), CH_LDS_BYTES, g->stream, g->dL, ld, g->dS, T, fl, g->dinfo, g->dW, g->dWT);
-    HIPCHK(hipGetLastError());
-    if (T > 3) {
-        HIPCHK(hipStreamWaitEvent(g->col_stream, g->ev_panels, 0));
-        HIPCHK(hipStreamWaitEvent(g->side_stream, g->ev_panels, 0));
-        HIPCHK(hipStreamWaitEvent(g->inv_stream, g->ev_panels, 0));
-        hipLaunchKernelGGL(k_chol_rows, dim3(T - 3), dim3(CH_THREADS), WK_LDS_DOUBLES * 8, g->col_stream, g->dL, ld, g->dS, T, fl);
-        hipLaunchKernelGGL(k_chol_cols, dim3(2 * (T - 3)), dim3(GEMM_THREADS), 0, g->side_stream, g->dL, ld, g->dS, T, fl);
-        HIPCHK(hipGetLastError());
-    }
-    if (T > 3) {   // the flagged launches below stay behind the persistent workgroups (k_chol_gate)
-        hipLaunchKernelGGL(k_chol_gate, dim3(1), dim3(64), 0, g->inv_stream, fl.resident, 8u + 3u * (unsigned)(T - 3), fl.abort, fl.spin_ticks);
-        HIPCHK(hipGetLastError());
-    }
-    for (int k = 0; k + 3 < T; ++k) {
-        // fourth stream: the rest of block k's update -- rows >= k+3, columns >= k+2 -- on the MFMA engine; each workgroup
-        // waits for the last panel of the two rows of L(:, k) it reads
-        GemmNTParams f{};
-        f.A = g->dS + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; f.lda = ld;
-        f.B = g->dS + (int64_t)(k + 2) * TILE * ld + (int64_t)k * TILE; f.ldb = ld;
-        f.C = g->dL + (int64_t)(k + 3) * TILE * ld + (int64_t)(k + 2) * TILE; f.ldc = ld;
-        f.mt = T - (k + 3); f.nt64 = 2 * (T - (k + 2)); f.kc = TILE / KC; f.alpha = -1.0; f.beta = 1.0;
-        f.diag_skip = 1; f.row0 = (int64_t)(k + 3) * TILE; f.col0 = (int64_t)(k + 2) * TILE;
-        f.wait_flag = fl.xp + ((size_t)k * T + (k + 3)) * CH_PANELS + (CH_PANELS - 1); f.wait_val = 1u; f.wait_stride_ti = CH_PANELS;
-        f.wait_flag2 = fl.xp + ((size_t)k * T + (k + 2)) * CH_PANELS + (CH_PANELS - 1); f.wait_val2 = 1u; f.wait_stride_tj2 = CH_PANELS;
-        f.signal = fl.colall + k;          // (selects the agent-scope stores; nobody waits for the whole launch)
-        f.signal_row0 = fl.rest + k;       // row k+3: what the gated update of block k+1 starts from
-        f.signal_col0 = fl.farall + k;     // column k+2: what block k+1's column updaters write next
-        f.first_row_col = 1; f.abort_flag = fl.abort; f.spin_ticks = g_chol_spin_ticks;
-        CHK(launch_gemm_nt(g, f, 1, g->inv_stream));
-    }
-    if (T > 3) {
-        HIPCHK(hipEventRecord(g->ev_bulk, g->col_stream));
-        HIPCHK(hipStreamWaitEvent(g->stream, g->ev_bulk, 0));
-        HIPCHK(hipEventRecord(g->ev_gate, g->side_stream));
-        HIPCHK(hipStreamWaitEvent(g->stream, g->ev_gate, 0));
-        HIPCHK(hipEventRecord(g->ev_inv, g->inv_stream));
-        HIPCHK(hipStreamWaitEvent(g->stream, g->ev_inv, 0));
-    }
-    if (T > 1) {
-        hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
-}
-
-// ---- A2, dataflow form for LARGE T.  The form above keeps T - 3 row followers and 2 (T - 3) column updaters resident for the
-// whole factorisation: at T = 63 they sit on ~180 of the 256 CUs and halve the rate of every GEMM beside them, and its far
-// updates are one K = 128 launch per block over the whole trailing matrix (~16 TF/s).  Here only the chain (8 workgroups)
-// and one inverter workgroup are persistent:
-//   rows >= k+3 of L(:, k)      one launch: product with W_kk' (k_chol_inverter raises solved[k] a few us after the pivot block)
-//   columns k+1 .. 4m+6, m=k/4  one flagged K = 128 launch (first row = what the chain reads next, counted in rest[k])
-//   columns 4m+7 .. 4m+10       K = 512, plain, once group m (four blocks) is solved; the next group's flagged update waits for it
-//   columns >= 4m+11            K = 512, plain, behind it on the same low-priority stream
-// Every launch with an in-kernel wait is on ONE in-order stream and waits only for the chain or for launches before it on that
-// stream; the plain launches are released by host events: no spinning workgroup can keep a producer off the chip.
-static int cholesky_dataflow2(bohip_gp* g, int T) {
-    const int64_t ld = g->ld;
-    // the handle's four streams and no more: a fifth and sixth stream ended up sharing a hardware queue on the first handle of a
-    // process (the long plain launches then sat in front of the flagged ones: 14.2 instead of 12.2 ms at N = 10000)
-    hipStream_t flagged_stream = g->col_stream, bulk_stream = g->side_stream;
-    CholFlags fl = chol_flags_layout(g, T);
-    const int win = g_chol_df2_win;
-    fl.mode2 = win;
-    HIPCHK(hipMemsetAsync(g->dchol_flags, 0, chol_flag_words(T) * sizeof(unsigned), g->stream));
-    HIPCHK(hipEventRecord(g->ev_panels, g->stream));           // K and the cleared flags are in place
-    hipLaunchKernelGGL(k_chol_chain, dim3(9), dim3(CH_THREADS), CH_LDS_BYTES, g->stream, g->dL, ld, g->dS, T, fl, g->dinfo, g->dW, g->dWT);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamWaitEvent(flagged_stream, g->ev_panels, 0));
-    HIPCHK(hipStreamWaitEvent(bulk_stream, g->ev_panels, 0));
-    while ((int)g->ev_tier.size() < 2 * (T / 4 + 1)) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        g->ev_tier.push_back(ev);
-    }
-    // ONE in-order stream of flagged launches.  Launch k carries Update(k) and Solve(k+1) in one grid (k_gemm_nt_pair), so that
-    // the row solve is already resident when the inverse of its diagonal block arrives:
-    //   Solve(k)   row i waits for solved[k] and for tile (i, k) from Update(k-1); counts S(i, k) into colr[k T + i] (16 = done)
-    //   Update(k)  tile (i, j) waits for S(i, k) and S(j, k) (rows k+1, k+2: the chain's last-panel flags); its column k+1
-    //              counts into xp[(k T + i) 8] (rows >= k+3 have no other use for that word), its first row into rest[k]
-    hipStream_t ss = flagged_stream;
-    auto solve_params = [&](int k) {
-        GemmNTParams sv{};   // S(i, k) = A(i, k) W_kk' for i >= k+3
-        sv.A = g->dL + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; sv.lda = ld;
-        sv.B = g->dW + (int64_t)k * TILE * (ld + 1); sv.ldb = ld;
-        sv.C = g->dS + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; sv.ldc = ld;
-        sv.mt = T - (k + 3); sv.nt64 = 2; sv.kc = TILE / KC; sv.alpha = 1.0; sv.beta = 0.0;
-        if (k == 0) {
-            sv.wait_flag = fl.solved + k; sv.wait_val = 1u; sv.wait_stride_ti = 0;
-        } else {
-            sv.wait_flag = fl.xp + ((size_t)(k - 1) * T + (k + 3)) * CH_PANELS; sv.wait_val = 16u; sv.wait_stride_ti = CH_PANELS;
-            sv.wait_flag2 = fl.solved + k; sv.wait_val2 = 1u; sv.wait_stride_tj2 = 0;
-        }
-        sv.abort_flag = fl.abort; sv.spin_ticks = g_chol_spin_ticks;
-        sv.signal = fl.farall + k;         // (selects the agent-scope stores: the update beside it reads these tiles)
-        sv.signal_rows = fl.colr + (size_t)k * T + (k + 3); sv.signal_rows_ntj = 2; sv.signal_rows_stride = 1;
-        return sv;
-    };
-    auto update_params = [&](int k) {
-        const int c_hi = near_last_col(T, k, win);
-        GemmNTParams f{};    // tiles (i, j), i >= k+3, k+1 <= j <= c_hi:  -= S(i, k) S(j, k)'
-        f.A = g->dS + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; f.lda = ld;
-        f.B = g->dS + (int64_t)(k + 1) * TILE * ld + (int64_t)k * TILE; f.ldb = ld;
-        f.C = g->dL + (int64_t)(k + 3) * TILE * ld + (int64_t)(k + 1) * TILE; f.ldc = ld;
-        f.mt = T - (k + 3); f.nt64 = 2 * (c_hi - k); f.kc = TILE / KC; f.alpha = -1.0; f.beta = 1.0;
-        f.diag_skip = 1; f.row0 = (int64_t)(k + 3) * TILE; f.col0 = (int64_t)(k + 1) * TILE;
-        f.wait_flag = fl.colr + (size_t)k * T + (k + 3); f.wait_val = 16u; f.wait_stride_ti = 1;
-        f.wait_flag2 = fl.xp + ((size_t)k * T + (k + 1)) * CH_PANELS + (CH_PANELS - 1); f.wait_val2 = 1u; f.wait_stride_tj2 = CH_PANELS;
-        f.wait2_tj2_max = 2; f.wait2_rows = 1;
-        f.signal = fl.colall + k;          // (selects the agent-scope stores; nobody waits for the whole launch)
-        f.signal_row0 = fl.rest + k;       // row k+3: what the chain's followers and gated updates of block k+1 start from
-        f.signal_rows = fl.xp + ((size_t)k * T + (k + 3)) * CH_PANELS; f.signal_rows_ntj = 2; f.signal_rows_stride = CH_PANELS;
-        f.first_row_col = 1; f.abort_flag = fl.abort; f.spin_ticks = g_chol_spin_ticks;
-        return f;
-    };
-    if (T > 3) CHK(launch_gemm_nt(g, solve_params(0), 1, ss, true));
-    for (int k = 0; k + 3 < T; ++k) {
-        const int m = k / 4;
-        if (k % 4 == 0 && m >= 1 && 4 * (m - 1) + win + 1 <= T - 1)   // columns 4m+3 .. 4m+6 carry group m-1 only after its first K = 512 launch
-            HIPCHK(hipStreamWaitEvent(ss, g->ev_tier[2 * (m - 1) + 1], 0));
-        const GemmNTParams f = update_params(k);
-        if (k + 4 < T) {
-            const GemmNTParams sv = solve_params(k + 1);
-            hipLaunchKernelGGL(k_gemm_nt_pair, dim3(f.mt * f.nt64 + sv.mt * sv.nt64), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), ss, f, sv,
-                               f.mt * f.nt64);
-            HIPCHK(hipGetLastError());
-        } else {
-            CHK(launch_gemm_nt(g, f, 1, ss, true));
-        }
-        if (k % 4 == 3 && 4 * m + win + 1 <= T - 1) {
-            // group m is solved for every row once this launch has finished (the update waited for every row of S(:, k))
-            HIPCHK(hipEventRecord(g->ev_tier[2 * m], ss));
-            HIPCHK(hipStreamWaitEvent(bulk_stream, g->ev_tier[2 * m], 0));
-            for (int part = 0; part < 2; ++part) {
-                const int c0 = part == 0 ? 4 * m + win + 1 : 4 * m + win + 5, c1 = part == 0 ? std::min(T - 1, 4 * m + win + 4) : T - 1;
-                if (c0 <= c1) {
-                    GemmNTParams q{};
-                    q.A = g->dS + (int64_t)c0 * TILE * ld + (int64_t)(4 * m) * TILE; q.lda = ld;
-                    q.B = q.A; q.ldb = ld;
-                    q.C = g->dL + (int64_t)c0 * TILE * (ld + 1); q.ldc = ld;
-                    q.mt = T - c0; q.nt64 = 2 * (c1 - c0 + 1); q.kc = 4 * (TILE / KC); q.alpha = -1.0; q.beta = 1.0;
-                    q.diag_skip = 1; q.row0 = (int64_t)c0 * TILE; q.col0 = (int64_t)c0 * TILE;
-                    q.coalesced = g_chol_df2_coal;
-                    CHK(launch_gemm_nt(g, q, 1, bulk_stream, g_chol_df2_hi != 0));
-                }
-                if (part == 0) HIPCHK(hipEventRecord(g->ev_tier[2 * m + 1], bulk_stream));
-            }
-        }
-    }
-    HIPCHK(hipEventRecord(g->ev_inv, ss));
-    HIPCHK(hipStreamWaitEvent(g->stream, g->ev_inv, 0));
-    HIPCHK(hipEventRecord(g->ev_blk, bulk_stream));
-    HIPCHK(hipStreamWaitEvent(g->stream, g->ev_blk, 0));
-    hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-    HIPCHK(hipGetLastError());
-    g->w_seeded = true;
-    return 0;
-}
-
-// ---- the same with LEFT-LOOKING window updates (BOHIP_CHOL_DF2_LL=1).  In cholesky_dataflow2 a quarter of the flops run as
-// K = 128 read-modify-writes of the window columns (~15 TF/s).  Here a column receives its updates just in time and all at once:
-//   bulk      group m (blocks 4m..4m+3), K = 512, goes to the columns >= 4m+8 only: Qa(m) = columns 4m+8..4m+11 (counted into
-//             col[m]: the flagged launches that touch those columns wait for it in-kernel), Qb(m) = the rest
-//   block k   column c = k+1, rows >= k+3:  -= S(i, ks..k) S(c, ks..k)'  with ks = first block of the group BEFORE c's -- K up to 1024,
-//             one read-modify-write per tile; the two tiles (k+3, k+2), (k+3, k+3) the chain reads next the same way; Solve(k+1)
-//             -- all four in one grid (k_gemm_nt_quad) on the one flagged stream.
-static int cholesky_dataflow3(bohip_gp* g, int T) {
-    const int64_t ld = g->ld;
-    hipStream_t ss = g->col_stream, bulk_stream = g->side_stream;
-    CholFlags fl = chol_flags_layout(g, T);
-    fl.mode2 = 100;
-    HIPCHK(hipMemsetAsync(g->dchol_flags, 0, chol_flag_words(T) * sizeof(unsigned), g->stream));
-    HIPCHK(hipEventRecord(g->ev_panels, g->stream));           // K and the cleared flags are in place
-    hipLaunchKernelGGL(k_chol_chain, dim3(9), dim3(CH_THREADS), CH_LDS_BYTES, g->stream, g->dL, ld, g->dS, T, fl, g->dinfo, g->dW, g->dWT);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamWaitEvent(ss, g->ev_panels, 0));
-    HIPCHK(hipStreamWaitEvent(bulk_stream, g->ev_panels, 0));
-    while ((int)g->ev_tier.size() < 2 * (T / 4 + 1)) {
-        hipEvent_t ev;
-        HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        g->ev_tier.push_back(ev);
-    }
-    unsigned* qa_cnt = fl.col;   // [T] words, one per group used
-    auto qa_dims = [&](int m, int& mt, int& nt64) {   // Qa(m): columns 4m+8 .. 4m+11, rows >= 4m+8
-        const int c0 = 4 * m + 8, c1 = std::min(T - 1, 4 * m + 11);
-        mt = T - c0; nt64 = 2 * (c1 - c0 + 1);
-    };
-    auto bulk_wait = [&](GemmNTParams& f, int c) {    // column c carries the groups <= c/4 - 2 once Qa(c/4 - 2) has stored
-        const int m = c / 4 - 2;
-        if (m < 0) return;
-        int mt, nt64; qa_dims(m, mt, nt64);
-        f.wait_flag3 = qa_cnt + m; f.wait_val3 = 8u * (unsigned)(mt * nt64);
-    };
-    auto solve_params = [&](int k) {
-        GemmNTParams sv{};   // S(i, k) = A(i, k) W_kk' for i >= k+3
-        sv.A = g->dL + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; sv.lda = ld;
-        sv.B = g->dW + (int64_t)k * TILE * (ld + 1); sv.ldb = ld;
-        sv.C = g->dS + (int64_t)(k + 3) * TILE * ld + (int64_t)k * TILE; sv.ldc = ld;
-        sv.mt = T - (k + 3); sv.nt64 = 2; sv.kc = TILE / KC; sv.alpha = 1.0; sv.beta = 0.0;
-        if (k == 0) {
-            sv.wait_flag = fl.solved + k; sv.wait_val = 1u; sv.wait_stride_ti = 0;
-        } else {
-            sv.wait_flag = fl.xp + ((size_t)(k - 1) * T + (k + 3)) * CH_PANELS; sv.wait_val = 16u; sv.wait_stride_ti = CH_PANELS;
-            sv.wait_flag2 = fl.solved + k; sv.wait_val2 = 1u; sv.wait_stride_tj2 = 0;
-        }
-        sv.abort_flag = fl.abort; sv.spin_ticks = g_chol_spin_ticks;
-        sv.signal = fl.farall + k;
-        sv.signal_rows = fl.colr + (size_t)k * T + (k + 3); sv.signal_rows_ntj = 2; sv.signal_rows_stride = 1;
-        return sv;
-    };
-    // tiles (i, c), i = r0 .. r0 + mt - 1, left-looking over the blocks ks .. k
-    auto ll_params = [&](int k, int c, int r0, int mt) {
-        const int ks = 4 * std::max(c / 4 - 1, 0), nb = k - ks + 1;
-        GemmNTParams f{};
-        f.A = g->dS + (int64_t)r0 * TILE * ld + (int64_t)ks * TILE; f.lda = ld;
-        f.B = g->dS + (int64_t)c * TILE * ld + (int64_t)ks * TILE; f.ldb = ld;
-        f.C = g->dL + (int64_t)r0 * TILE * ld + (int64_t)c * TILE; f.ldc = ld;
-        f.mt = mt; f.nt64 = 2; f.kc = nb * (TILE / KC); f.alpha = -1.0; f.beta = 1.0;
-        f.diag_skip = 1; f.row0 = (int64_t)r0 * TILE; f.col0 = (int64_t)c * TILE;
-        f.wait_flag = fl.colr + (size_t)k * T + r0; f.wait_val = 16u; f.wait_stride_ti = 1;   // S(i, k) from Solve(k)
-        if (c <= k + 2) {   // operand row c is one of the chain's two: its last-panel flag
-            f.wait_flag2 = fl.xp + ((size_t)k * T + c) * CH_PANELS + (CH_PANELS - 1); f.wait_val2 = 1u; f.wait_stride_tj2 = 0;
-        }
-        bulk_wait(f, c);
-        f.signal = fl.colall + k;          // (selects the agent-scope stores)
-        f.signal_row0 = fl.rest + k;       // only the launches whose FIRST row is row k+3 count there (all three per block do)
-        f.abort_flag = fl.abort; f.spin_ticks = g_chol_spin_ticks;
-        return f;
-    };
-    if (T > 3) CHK(launch_gemm_nt(g, solve_params(0), 1, ss, true));
-    for (int k = 0; k + 3 < T; ++k) {
-        const int m = k / 4;
-        GemmNTParams r2 = ll_params(k, k + 2, k + 3, 1), r3 = ll_params(k, k + 3, k + 3, 1);
-        GemmNTParams col = ll_params(k, k + 1, k + 3, T - (k + 3));
-        col.signal_rows = fl.xp + ((size_t)k * T + (k + 3)) * CH_PANELS; col.signal_rows_ntj = 2; col.signal_rows_stride = CH_PANELS;
-        GemmNTParams sv{};
-        int n3 = 0;
-        if (k + 4 < T) { sv = solve_params(k + 1); n3 = sv.mt * sv.nt64; }
-        const int n0 = r2.mt * r2.nt64, n1 = r3.mt * r3.nt64, n2 = col.mt * col.nt64;
-        hipLaunchKernelGGL(k_gemm_nt_quad, dim3(n0 + n1 + n2 + n3), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), ss, r2, r3, col, sv, n0, n1, n2);
-        HIPCHK(hipGetLastError());
-        if (k % 4 == 2 && 4 * m + 8 <= T - 1) {
-            // this grid held Solve(4m+3): group m is solved for every row, its K = 512 update of the columns >= 4m+8 can go
-            HIPCHK(hipEventRecord(g->ev_tier[2 * m], ss));
-            HIPCHK(hipStreamWaitEvent(bulk_stream, g->ev_tier[2 * m], 0));
-            for (int part = 0; part < 2; ++part) {
-                const int c0 = part == 0 ? 4 * m + 8 : 4 * m + 12, c1 = part == 0 ? std::min(T - 1, 4 * m + 11) : T - 1;
-                if (c0 > c1) continue;
-                GemmNTParams q{};
-                q.A = g->dS + (int64_t)c0 * TILE * ld + (int64_t)(4 * m) * TILE; q.lda = ld;
-                q.B = q.A; q.ldb = ld;
-                q.C = g->dL + (int64_t)c0 * TILE * (ld + 1); q.ldc = ld;
-                q.mt = T - c0; q.nt64 = 2 * (c1 - c0 + 1); q.kc = 4 * (TILE / KC); q.alpha = -1.0; q.beta = 1.0;
-                q.diag_skip = 1; q.row0 = (int64_t)c0 * TILE; q.col0 = (int64_t)c0 * TILE;
-                if (part == 0) q.signal = qa_cnt + m;   // agent-scope stores + the counter the flagged launches wait for
-                else q.coalesced = g_chol_df2_coal;
-                CHK(launch_gemm_nt(g, q, 1, bulk_stream, g_chol_df2_hi != 0));
-            }
-        }
-    }
-    HIPCHK(hipEventRecord(g->ev_inv, ss));
-    HIPCHK(hipStreamWaitEvent(g->stream, g->ev_inv, 0));
-    HIPCHK(hipEventRecord(g->ev_blk, bulk_stream));
-    HIPCHK(hipStreamWaitEvent(g->stream, g->ev_blk, 0));
-    hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-    HIPCHK(hipGetLastError());
-    g->w_seeded = true;
-    return 0;
 }
 
 // ---- A2, executor form (kernels_exec.hip): the chain + ONE persistent kernel that pulls tile tasks from six in-order queues
@@ -998,8 +672,7 @@ static void exec_task_list(double* dL, double* dS, double* dW, double* dWT, unsi
         auto early = [&](int i, int c) {
             if (i >= T || c >= T || ks(c) > kp) return;
             const int nbk = kp - ks(c) + 1;   // blocks in the sum: 1 ... 5, growing with c inside a group of four columns
-            if (((g_chol_exec_early_split == 1 && (T <= (inv_g == 0 ? 56 : 23) || (inv_g == 0 && T - kp <= g_chol_exec_early_tail))) ||
-                 g_chol_exec_early_split == 2) && nbk >= 2) {
+            if (T <= (inv_g == 0 ? 56 : 23) && nbk >= 2) {
                 // (round 6) TWO PIECES like Late: the blocks before kp need nothing of block kp, so the task starts a block earlier and waits for
                 // S(i, kp) / S(c, kp) inside, one K = 128 piece from its end.  In one piece it started only when the LAST block's rows were solved and
                 // then ran its whole window -- up to 50 us on the path S(i, kp) -> Early -> Late -> follower, growing over every group of four columns:
@@ -1025,101 +698,10 @@ static void exec_task_list(double* dL, double* dS, double* dW, double* dWT, unsi
         add(EX_QBULK, Sp(i, 4 * m), Sp(c, 4 * m), Ap(i, c), nullptr, 4 * CPB, 4 * CPB, i == c, 1,
             {{sver(i, 4 * m + 3), 16u}, {sver(c, 4 * m + 3), 16u}, {ver(i, c), 16u * (unsigned)m}}, ver(i, c), EX_NONE);
     };
-    if (!g_chol_exec_bulk_edf) {
-        // round 3: group after group, column-major inside a group
-        for (int m = 0; 4 * m + 8 <= T - 1; ++m)
-            for (int c = 4 * m + 8; c < T; ++c)
-                for (int i = c; i < T; ++i) add_bulk(m, c, i);
-    } else {
-        // Round-4 experiment (BOHIP_CHOL_EXEC_BULK_EDF=1, off by default): the bulk queue in EARLIEST-DEADLINE order.  A workgroup
-        // claims from a queue only when its HEAD is runnable, and group after group the head of group m -- the four columns the pivot
-        // chain reaches within the next blocks -- sits behind the far columns of group m-1, which nobody needs for another 50 blocks;
-        // the round-3 trace at N = 10^4 shows the chain stalling for up to 0.8 ms at group boundaries (gap between pivots: mean 64 us,
-        // median 18).  The deadline of a bulk tile is its COLUMN (the chain needs column c complete when it gets there), its release
-        // the moment its group's panels are solved.  The order here is produced by simulating the factorisation on the host: a chain
-        // that needs `period` per block and waits for its next column, `workers` workgroups that each take the released tile of the
-        // smallest column (rounds on one tile in group order), a group released `lag` behind its fourth pivot.  The counters the
-        // records wait for are the same, so any order is CORRECT (tests/test_exec_tasks.py replays this list too).
-        // MEASURED (profiles/r04_exec_bulk_edf.txt): the chain then advances evenly -- 3.3 blocks per 500 us from start to end, no stall
-        // above 100 us -- and the factorisation takes exactly as long: 9.75-9.83 ms against 9.80-9.86 at N = 10^4, 15.3 against 14.9 at
-        // N = 12000.  The executor is THROUGHPUT-bound, not order-bound: 350 of its 476 workgroups are busy whatever the order (bulk
-        // tasks lose 9 us of look + claim per 61 us of work, the row steps 45 us of waiting per 37 us), and an evenly paced chain only
-        // moves the idle time from the group boundaries to every block.
-        const int NG = std::max(0, (T - 1 - 8) / 4 + 1);
-        const double period = 76.0, lag = 90.0, tile_us = 125.0, col_lag = 140.0;   // us: pivot block; pivot -> S rows solved; one tile (two records); last bulk tile of a column -> its pivot can start
-        const int workers = 400;
-        struct Tile { int c, m, i; };
-        auto later = [](const Tile& a, const Tile& b) { return a.c != b.c ? a.c > b.c : (a.m != b.m ? a.m > b.m : a.i > b.i); };
-        std::priority_queue<Tile, std::vector<Tile>, decltype(later)> ready(later);
-        std::vector<int> left_in_col(T, 0);                 // bulk tiles of column c not yet finished
-        std::vector<double> col_done(T, 0.0), pivot_end(T, 0.0);
-        for (int m = 0; m < NG; ++m)
-            for (int c = 4 * m + 8; c < T; ++c) left_in_col[c] += T - c;
-        // (i, c) -> finish time of its last round, next round to run
-        std::vector<int> next_m((size_t)T * T, 0);
-        struct Run { double end; Tile t; };
-        auto run_later = [](const Run& a, const Run& b) { return a.end > b.end; };
-        std::priority_queue<Run, std::vector<Run>, decltype(run_later)> running(run_later);
-        int released = 0, pivots = 0;          // groups released, pivot blocks finished
-        double now = 0.0;
-        size_t emitted = 0, total = 0;
-        for (int c = 8; c < T; ++c) total += (size_t)left_in_col[c];
-        auto pivot_ready_at = [&](int k) {     // when can pivot block k start?  its column must be complete
-            double t = k == 0 ? 0.0 : pivot_end[k - 1];
-            if (k >= 8 && left_in_col[k] > 0) return 1e300;
-            if (k >= 8) t = std::max(t, col_done[k] + col_lag);
-            return t;
-        };
-        std::vector<char> busy((size_t)T * T, 0);   // a round of this tile is running
-        while (emitted < total) {
-            // advance the chain as far as it can go at `now`
-            while (pivots < T) {
-                const double st = pivot_ready_at(pivots);
-                if (st + period > now) break;
-                pivot_end[pivots] = st + period;
-                ++pivots;
-            }
-            // release the groups whose fourth pivot is `lag` old: the tiles whose earlier rounds are all done become ready now, the
-            // others when their running (or still queued) round finishes
-            while (released < NG && 4 * released + 3 < pivots && pivot_end[4 * released + 3] + lag <= now) {
-                const int m = released++;
-                for (int c = 4 * m + 8; c < T; ++c)
-                    for (int i = c; i < T; ++i)
-                        if (next_m[(size_t)i * T + c] == m && !busy[(size_t)i * T + c]) ready.push(Tile{c, m, i});
-            }
-            // start work on free workers, smallest column first
-            while ((int)running.size() < workers && !ready.empty()) {
-                const Tile t = ready.top(); ready.pop();
-                add_bulk(t.m, t.c, t.i);
-                ++emitted;
-                next_m[(size_t)t.i * T + t.c] = t.m + 1;
-                busy[(size_t)t.i * T + t.c] = 1;
-                running.push(Run{now + tile_us, t});
-            }
-            // next event: a tile finishes, a pivot ends, a group is released
-            double nxt = 1e300;
-            if (!running.empty()) nxt = std::min(nxt, running.top().end);
-            if (pivots < T) { const double st = pivot_ready_at(pivots); if (st < 1e299) nxt = std::min(nxt, st + period); }
-            if (released < NG && 4 * released + 3 < pivots) nxt = std::min(nxt, pivot_end[4 * released + 3] + lag);
-            if (nxt >= 1e299) break;       // (cannot happen: something is always in flight until everything is emitted)
-            now = std::max(now, nxt);
-            while (!running.empty() && running.top().end <= now) {
-                const Tile t = running.top().t;
-                const double e = running.top().end;
-                running.pop();
-                busy[(size_t)t.i * T + t.c] = 0;
-                if (--left_in_col[t.c] == 0) col_done[t.c] = e;
-                // the tile's next round, if its group is out already
-                if (t.m + 1 < released && 4 * (t.m + 1) + 8 <= t.c) ready.push(Tile{t.c, t.m + 1, t.i});
-            }
-        }
-        // safety net: whatever the simulation did not emit (it always emits everything; a change of the model must not lose tiles)
-        if (emitted < total)
-            for (int m = 0; m < NG; ++m)
-                for (int c = 4 * m + 8; c < T; ++c)
-                    for (int i = c; i < T; ++i)
-                        if (next_m[(size_t)i * T + c] <= m) { add_bulk(m, c, i); next_m[(size_t)i * T + c] = m + 1; }
-    }
+    // group after group, column-major inside a group
+    for (int m = 0; 4 * m + 8 <= T - 1; ++m)
+        for (int c = 4 * m + 8; c < T; ++c)
+            for (int i = c; i < T; ++i) add_bulk(m, c, i);
     // Queues 3 (EX_QROWS) and 5 (EX_QWAVE): W = L^-1 behind the chain (inv_g > 0: blocks per piece of the long contraction = chunk size G).
     //   Z(i, j) = -sum_{k=j}^{i-1} L(i, k) W(k, j)   accumulated in place at W(i, j), in k order, from three kinds of pieces:
     //       wave m     chunk m = blocks [G m, G (m+1)), pushed to EVERY row i >= G (m+1) + 1 as soon as the chunk's rows of W are
@@ -1433,7 +1015,6 @@ static int cholesky_exec(bohip_gp* g, int T) {
     const int64_t ld = g->ld;
     CHK(build_exec_tasks(g, T));
     CholFlags fl = chol_flags_layout(g, T);
-    fl.mode2 = 200;   // the chain's view: row k+3's three tiles carry block k (its own gated updates: rest[k] = 24), inverter workgroup on
     HIPCHK(hipMemsetAsync(g->dchol_flags, 0, chol_flag_words(T) * sizeof(unsigned), g->stream));
     HIPCHK(hipEventRecord(g->ev_panels, g->stream));           // K and the cleared flags are in place
     fl.nsf = g_chol_nsf;
@@ -1442,10 +1023,8 @@ static int cholesky_exec(bohip_gp* g, int T) {
     // The solved panels go home (S -> L) right behind the CHAIN kernel, not behind the executor: every S(i, k) feeds the diagonal tile of its
     // row, so all of them are final -- and the tiles of L they replace have been read for the last time -- when the last pivot is done, while the
     // executor still has the second half of W = L^-1 to grow (N = 10^4: 4.4 ms).  The copy runs beside that on the CUs the chain has left.
-    if (g_chol_copy_early) {
-        hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-        HIPCHK(hipGetLastError());
-    }
+    hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
+    HIPCHK(hipGetLastError());
     if (T > 3 || g->ex_qbeg[EX_NQ] > 0) {   // (T = 2, 3: no factorisation task, but the inverse's rows)
         ExQueues q{};
         q.tasks = g->dex_tasks;
@@ -1455,7 +1034,6 @@ static int cholesky_exec(bohip_gp* g, int T) {
         q.heads = q.abort + 1;
         q.ld = ld;
         q.spin_ticks = g_chol_spin_ticks;
-        q.fill = g_chol_exec_fill;
         // executor workgroups: two per CU that the chain kernel leaves free (a small partition must not fill its slots with the
         // urgent queue's own workgroups: nobody would serve the other queues until the time-out)
         const int cus_free = std::max(1, device_cus() - (9 + g_chol_nsf + 6));
@@ -1485,22 +1063,16 @@ static int cholesky_exec(bohip_gp* g, int T) {
         // the kernel then starts ~10 us behind them -- was built against the time-outs of refits that share the device with other host
         // threads' work: it cost 0.1 ms at N = 10^4 and the time-outs stayed.  What causes those is streams of several handles sharing a
         // hardware queue, where a kernel waits for the END of the one before it; the per-device lock in refit_once removed most of them.)
-        const size_t exec_lds = per_cu <= 1.0 && g_chol_exec_excl ? std::max<size_t>(glds3_lds_bytes<4>(), 84 * 1024) : glds3_lds_bytes<4>();
-        hipLaunchKernelGGL(k_chol_exec, dim3(exec_wgs), dim3(GEMM_THREADS_8), exec_lds, g->col_stream, q);
+        hipLaunchKernelGGL(k_chol_exec, dim3(exec_wgs), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->col_stream, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(g->ev_inv, g->col_stream));
         HIPCHK(hipStreamWaitEvent(g->stream, g->ev_inv, 0));
     }
-    if (!g_chol_copy_early) {
-        hipLaunchKernelGGL(k_copy_offdiag_tiles, dim3(T * (T - 1) / 2), dim3(256), 0, g->stream, g->dS, g->dL, ld, T);
-        HIPCHK(hipGetLastError());
-    }
-    g->w_seeded = true;
     g->w_done = g->ex_qbeg[EX_QROWS + 1] > g->ex_qbeg[EX_QROWS];
     return 0;
 }
 
-// multiprocessors of the current device (the dataflow forms need their persistent workgroups resident at the same time)
+// multiprocessors of the current device (the dataflow form needs its persistent workgroups resident at the same time)
 static int device_cus() {
     static int cus[64] = {0};
     int dev = 0;
@@ -1511,7 +1083,7 @@ static int device_cus() {
 }
 // The launch-chained factorisation as a stage of its own: the matrix, its scratch and the 128 x 128 diagonal inverses are a workspace,
 // so that the same code factorises the model's cK (refit_once) and a matrix the model does not own (the joint sampler's Sigma).
-// Streams and events are the handle's.  grow_inverse: W = L^-1 is grown beside the factorisation (the model's dW / dWT only).
+// Streams and events are the handle's.
 struct FactorWs {
     double *L, *S, *W, *WT;     // ld x ld matrix (lower tiles) and panel scratch; diagonal inverses W_kk at W + k wstep, W_kk' at WT + k wstep
     int64_t ld, ldw, wstep;
@@ -1520,7 +1092,7 @@ struct FactorWs {
 static FactorWs model_factor_ws(bohip_gp* g) {
     return FactorWs{g->dL, g->dS, g->dW, g->dWT, g->ld, g->ld, (int64_t)TILE * (g->ld + 1), g->dinfo};
 }
-static int factor_launch_chain(bohip_gp* g, const FactorWs& ws, int T, bool grow_inverse) {
+static int factor_launch_chain(bohip_gp* g, const FactorWs& ws, int T) {
     const int64_t ld = ws.ld;
     // Right-looking on 128-column panels, with the trailing update applied in two tiers: inside an outer block
     // of OB panels only the block's own remaining columns are updated after every panel (K = 128); everything to
@@ -1584,15 +1156,6 @@ static int factor_launch_chain(bohip_gp* g, const FactorWs& ws, int T, bool grow
             }
         }
         while (pend.next < pend.pieces) CHK(release_piece(false));   // a short last block: whatever is left goes now
-        if (grow_inverse && g_inv_overlap) {
-            // The block's panels are final: invert its diagonal region and join it to the leading inverse on the inverse
-            // stream, beside the next blocks' diagonal chain (which leaves most CUs idle).  Reads dS panels of columns
-            // < oe (final), W/W' of tiles < oe; writes W/W' rows/columns of THIS block and the upper-right part of dS.
-            HIPCHK(hipEventRecord(g->ev_blk, g->stream));
-            HIPCHK(hipStreamWaitEvent(g->inv_stream, g->ev_blk, 0));
-            for (int h = 1; h < oe - ob; h *= 2) CHK(inverse_level(g, g->inv_stream, ob, oe - ob, h));
-            CHK(inverse_join(g, g->inv_stream, ob, oe - ob));
-        }
         const int rem = T - oe;
         if (rem > 0) {
             // Bulk update with the OB solved panels: the columns of the NEXT outer block on the critical stream, everything
@@ -1683,29 +1246,26 @@ static int refit_once(bohip_gp* g, double jitter) {
     }
     HIPCHK(hipGetLastError());
     t_end(g);
-    // Which form.  The dataflow forms make progress only while their persistent workgroups are resident TOGETHER, one per CU
-    // (the chain's fill the LDS): the chain's 8-9 (+ solve followers), form 1's T - 3 row followers and 2 (T - 3) column
-    // updaters.  On a device (or partition: CPX mode exposes 32 CUs) that cannot hold them the launch chain is used.
+    // Which form.  The executor makes progress only while the chain kernel's workgroups (9 + solve followers + 6 gated updaters) are
+    // resident TOGETHER, one per CU (they fill the LDS), with CUs left over for the executor's own: on a device or partition that
+    // cannot hold them the launch chain is used.  T range: from TWO row tiles on with the inverse queues -- at T = 2, 3 the executor has
+    // no factorisation task at all (every tile is inside the chain kernel's window) but it grows W = L^-1 behind the chain: N = 200 0.15
+    // instead of 0.21 ms, N = 300 0.20 instead of 0.28 -- and from FOUR without them, the first T with a factorisation task.
     const int cus = device_cus();
-    const bool df_size = (g_chol_df == 1 && T >= 2 && T <= g_chol_df_tmax) || (g_chol_df == 2 && T >= 2 && T <= CHOL_DF_TCAP);
+    const bool exec_ok = T >= (g_chol_inv_g > 0 ? 2 : 4) && cus >= 9 + g_chol_nsf + 6 + 8;
+    const bool df_size = g_chol_df != 0 && exec_ok && T <= g_chol_df_tmax;
     bool paused = false;
     if (df_size)   // the pause after a time-out counts refits that WOULD have used a dataflow form, nothing else
         for (int sk = g_chol_df_skip.load(std::memory_order_relaxed); sk > 0;)
             if (g_chol_df_skip.compare_exchange_weak(sk, sk - 1, std::memory_order_relaxed)) { paused = true; break; }
     const bool want_df = !paused && df_size;
-    // (from TWO row tiles on with the inverse queues: at T = 2, 3 the executor has no factorisation task at all -- every tile is inside the
-    // chain kernel's window -- but it grows W = L^-1 behind the chain: N = 200 0.15 instead of 0.21 ms, N = 300 0.20 instead of 0.28)
-    const int exec_min = g_chol_exec_min >= 0 ? g_chol_exec_min : (g_chol_inv_g > 0 ? 2 : 24);   // (alone: 32 until round 6 -- since the chain's blocks run on the matrix pipe the first form's followers are what lags from 24 row tiles on: N=3000 1.15 against 1.18 ms, N=3500 1.37 / 1.51; N=2500 0.935 / 0.908)
-    const bool exec_ok = g_chol_exec && T >= std::max(g_chol_inv_g > 0 ? 2 : 4, exec_min) && cus >= 9 + g_chol_nsf + 6 + 8;
-    const bool form2_ok = T >= g_chol_df2_min && cus >= 9 + 32;
-    const bool form1_ok = T >= 3 && cus >= 8 + 3 * std::max(0, T - 3) + 8;
     // (stage name: with the executor's inverse queues the factorisation and W = L^-1 are ONE stage)
     // One dataflow refit per device at a time (see below): the host lock of this process and the file lock between processes, taken before
     // the stage begins.  Round 6: when ANOTHER PROCESS keeps the file lock for the whole wait this refit takes the launch-chained form instead
     // of going ahead unlocked (two processes' persistent kernels on one chip are what the 200 ms time-outs of profiles/r06_soak.txt are made of).
     std::unique_lock<std::mutex> df_lock;
     DfFileLock df_file;
-    bool df_go = want_df && (exec_ok || form2_ok || form1_ok);
+    bool df_go = want_df;
     if (df_go) {
         df_lock = std::unique_lock<std::mutex>(g_df_mutex[g->device & 63]);
         df_file.acquire(g->device, T);
@@ -1715,24 +1275,18 @@ static int refit_once(bohip_gp* g, double jitter) {
             g->chol_lock_skips++;
         }
     }
-    t_begin(g, df_go && exec_ok && g_chol_inv_g > 0 ? "cholesky+inverse" : "cholesky");
+    t_begin(g, df_go && g_chol_inv_g > 0 ? "cholesky+inverse" : "cholesky");
     if (df_go) {
         // One dataflow refit per device at a time: its persistent workgroups must be resident together, and two refits from two host threads
         // (several models on one GPU, the logical shards of bohip_mgp_*) take each other's CUs -- every other one then sat out its 200 ms
         // time-out and fell back (tools/w_stress.py: 6 time-outs in 64 refits on 8 threads).  The refit is synchronous anyway (the abort word is
         // read back below), so a host lock from the first launch to that read costs nothing a contended chip would not have cost.
         g->w_done = false;
-        if (exec_ok) { g->chol_form_last = 4; CHK(cholesky_exec(g, T)); }
-        else if (form2_ok && g_chol_df2_ll) { g->chol_form_last = 3; CHK(cholesky_dataflow3(g, T)); }
-        else if (form2_ok) { g->chol_form_last = 2; CHK(cholesky_dataflow2(g, T)); }
-        else { g->chol_form_last = 1; CHK(cholesky_dataflow(g, T)); }
+        g->chol_form_last = 4;
+        CHK(cholesky_exec(g, T));
         t_end(g);
-        if (!g->w_done) {
+        if (!g->w_done) {   // (without the inverse queues: the chain's inverter has left the diagonal blocks W_kk, the levels follow)
             t_begin(g, "tri_inverse");
-            if (!g->w_seeded) {
-                hipLaunchKernelGGL(k_inv128, dim3(T), dim3(PF_THREADS), POTF2_LDS_BYTES, g->stream, g->dL, ld, g->dW, g->dWT, ld);
-                HIPCHK(hipGetLastError());
-            }
             for (int h = 1; h < T; h *= 2) CHK(inverse_level(g, g->stream, 0, T, h));
             t_end(g);
         }
@@ -1760,9 +1314,8 @@ static int refit_once(bohip_gp* g, double jitter) {
             g->chol_fallbacks++;
             g->chol_abort_T = T;
             {
-                // the chain kernel's waits leave the word address of the flag that never arrived (bit 31 set); the executor's tasks and the
-                // flagged launches of the older forms leave 1
-                char which[96] = "counters of an executor task or a flagged launch";
+                // the chain kernel's waits leave the word address of the flag that never arrived (bit 31 set); the executor's tasks leave 1
+                char which[96] = "counters of an executor task";
                 if (aborted & 0x80000000u) {
                     const unsigned base_w = (unsigned)(reinterpret_cast<uintptr_t>(g->dchol_flags) >> 2) | 0x80000000u;
                     snprintf(which, sizeof which, "flag word %u of %zu", (aborted - base_w) & 0x7fffffffu, chol_flag_words(T));
@@ -1820,15 +1373,10 @@ static int refit_once(bohip_gp* g, double jitter) {
         return 0;
     }
     g->chol_form_last = 0;
-    CHK(factor_launch_chain(g, model_factor_ws(g), T, true));
+    CHK(factor_launch_chain(g, model_factor_ws(g), T));
     t_end(g);
     t_begin(g, "tri_inverse");
-    if (g_inv_overlap) {   // only the tail of the last block's join is still running
-        HIPCHK(hipEventRecord(g->ev_inv, g->inv_stream));
-        HIPCHK(hipStreamWaitEvent(g->stream, g->ev_inv, 0));
-    } else {               // recursive doubling over the whole matrix after the factorisation
-        for (int h = 1; h < T; h *= 2) CHK(inverse_level(g, g->stream, 0, T, h));
-    }
+    for (int h = 1; h < T; h *= 2) CHK(inverse_level(g, g->stream, 0, T, h));   // recursive doubling over the whole matrix after the factorisation
     t_end(g);
     t_begin(g, "alpha");
     CHK(compute_alpha(g));
@@ -2771,9 +2319,7 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&g->side_stream, hipStreamNonBlocking, prio_lo);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_panels, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_bulk, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&g->inv_stream, hipStreamNonBlocking, prio_lo);
     if (e == hipSuccess) e = hipStreamCreateWithPriority(&g->col_stream, hipStreamNonBlocking, prio_hi);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_blk, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_inv, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_gate, hipEventDisableTiming);
     if (e != hipSuccess) { delete g; return fail(BOHIP_E_HIP, hipGetErrorString(e)); }
@@ -2845,10 +2391,7 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
     if (g->ev_panels) hipEventDestroy(g->ev_panels);
     if (g->ev_bulk) hipEventDestroy(g->ev_bulk);
-    if (g->inv_stream) { hipStreamSynchronize(g->inv_stream); hipStreamDestroy(g->inv_stream); }
     if (g->col_stream) { hipStreamSynchronize(g->col_stream); hipStreamDestroy(g->col_stream); }
-    for (hipEvent_t ev : g->ev_tier) hipEventDestroy(ev);
-    if (g->ev_blk) hipEventDestroy(g->ev_blk);
     if (g->ev_inv) hipEventDestroy(g->ev_inv);
     if (g->ev_gate) hipEventDestroy(g->ev_gate);
     if (g->own_stream) hipStreamDestroy(g->own_stream);
@@ -3359,7 +2902,7 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
         // the launch-chained form, without the inverse queues: only the diagonal inverses the panel solves use.  It touches
         // nothing of the model (no flag block, no refit lock: it has no persistent workgroups).
         t_begin(g, "sample_cholesky");
-        CHK(factor_launch_chain(g, ws, CT, false));
+        CHK(factor_launch_chain(g, ws, CT));
         t_end(g);
         t_begin(g, "sample_draw");
         double* const dF = samples ? g->sjF : nullptr;
@@ -4533,7 +4076,6 @@ int bohip_debug_exec_throughput(bohip_gp* g, unsigned qmask, int hot, int wgs, d
     q.heads = q.abort + 1;
     q.ld = g->ld;
     q.spin_ticks = g_chol_spin_ticks;
-    q.fill = g_chol_exec_fill;
     const int exec_wgs = wgs > 0 ? wgs : std::max(2, std::min(g_chol_exec_wgs > 0 ? g_chol_exec_wgs : 1 << 20, 2 * std::max(1, device_cus() - (9 + g_chol_nsf + 6))));
     q.nurgent = std::max(1, std::min(exec_wgs / 8, g_chol_exec_urgent > 0 ? g_chol_exec_urgent : (T >= 56 ? 16 : 32)));
     const int pairs_ = g_chol_exec_pairs == 0 ? 0 : 1;

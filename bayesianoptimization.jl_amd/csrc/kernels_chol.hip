@@ -1,13 +1,14 @@
-// kernels_chol.hip -- the dataflow form of the blocked Cholesky factorisation (row A2 of SURVEY.md section 8; reference
+// kernels_chol.hip -- the persistent chain of the dataflow Cholesky factorisation (row A2 of SURVEY.md section 8; reference
 // call sites: update!/append!/fit! at src/models/gp.jl:11-18, i.e. the ElasticPDMats / LAPACK potrf behind them).
 //
 // Why.  The launch-chained form (k_potf2_inv -> panel solve -> in-block update, one round per 128-block) is bound by its
 // serial chain: ~66 us of single-workgroup diagonal-block work + two dependent launches (~2 x 20 us) per block, 24 blocks
 // at N = 3000 = 2.75 ms for 9 GF.  Only three things are intrinsically serial: the pivot chain inside a diagonal block,
-// the solve of the tile just below it, and the update of the NEXT diagonal block.  Here they are pipelined at 16-column
-// granularity and never leave the chip's registers / LDS:
+// the solve of the tiles just below it, and the update of the NEXT diagonal block.  Here they are pipelined at 16-column
+// granularity and never leave the chip's registers / LDS.  Everything else of the factorisation -- and the triangular inverse
+// W = L^-1 behind it -- is a tile task of the executor (kernels_exec.hip, k_chol_exec), which runs beside this kernel.
 //
-//   k_chol_chain   8 persistent workgroups, one per CU:
+//   k_chol_chain   9 + nsf + 6 persistent workgroups, one per CU:
 //                  2 row owners (rows alternate).  The owner of row r
 //                    during block r-1  holds the diagonal tile (r, r) [lower, registers] and gives it one rank-16 update per
 //                                      16-column panel of L(r, r-1) that row r's critical follower delivers through S;
@@ -19,14 +20,11 @@
 //                    remaining columns, their 16 new columns of L to S with a per-panel flag.
 //                  4 gated-update workgroups: the two tiles (k+2, k+1), (k+2, k+2) the chain needs next, as an MFMA tile
 //                    product whose contraction index arrives 16 columns at a time (gated_tile).
+//                  1 inverter: W_kk = L_kk^-1 row panel by row panel behind the pivot (inverter_role): what the executor's row
+//                    solves multiply with, and the seeds of the triangular inverse.
+//                  nsf solve followers: the tiles (k+3, k) .. (k+2+nsf, k), panel by panel like the critical followers.
+//                  6 gated-update workgroups for the three tiles of row k+3 (gated_worker3).
 //                  The chain per block is therefore the pivot time + one flag hand-over, not pivot + 2 launches + 2 GEMMs.
-//   k_chol_rows    one persistent workgroup per row i >= 3: the same panel follower for tile (i, k), k = 0 .. i-3.
-//   k_chol_cols    two persistent workgroups per row i >= 3: gated_tile on (i, k+1), the tile the row follows next.
-//   k_gemm_nt      (kernels_linalg.hip) the rest of block k's update -- rows >= k+3, columns >= k+2 -- on the MFMA engine,
-//                  one launch per block on its own stream, gated by flags instead of host events and counting into the
-//                  counters the persistent workgroups wait on.
-//   k_inv128       afterwards: the inverses W_kk of all diagonal blocks at once (no inverse is needed during the factorisation
-//                  any more), seeds of the triangular inverse W = L^-1.
 //
 // Cross-workgroup protocol.  The chip has 8 XCDs with one L2 each; an agent-scope fence (__threadfence) is correct but is a
 // whole-L2 write-back (release) / invalidate (acquire) of that XCD -- measured ~18 us per panel hand-over and it wrecks the
@@ -41,28 +39,17 @@
 
 namespace bohip {
 
-#ifndef BOHIP_PIVOT_W16GROW
-#define BOHIP_PIVOT_W16GROW 1   // 1 (round 6): W16 grown inside the pivot block's factorisation, the rows below solved as a PRODUCT with it on the matrix pipe; 0: round 5's substitutions
-#endif
 constexpr int CH_THREADS = 512;
 // Row stride of the owner's LDS image of the diagonal tile.  k_potf2_inv's 129 makes a thread-per-row walk conflict-free; the chain's pivot
 // block no longer has one: its operand fetches are MFMA fragments (8 rows x 4 consecutive entries per 32 lanes), which want
 // stride = 4 (mod 32): 132.  (With 129 the row-solve phase took 1.2 us of LDS conflicts per panel instead of 0.3.)
-constexpr int CH_LD = BOHIP_PIVOT_W16GROW ? TILE + 4 : PF_LD;
-constexpr int CH_WLS = BOHIP_PIVOT_W16GROW ? 20 : 16;   // row stride of the pivot block's inverse in LDS (20: see WK_S)
+constexpr int CH_LD = TILE + 4;
+constexpr int CH_WLS = 20;   // row stride of the pivot block's inverse in LDS (20: see WK_S)
 constexpr int CH_PANELS = TILE / 16;          // 8 panels of 16 columns per 128-block
-constexpr int WK_LPS = 16;                    // worker LDS: published panel LP[128][16]
-constexpr int WK_XS = 18;                     //             solved rows   XB[128][18]: rows 16-byte aligned (two entries per ds_read_b128), 16 consecutive rows on 16 different bank quads
-#ifndef BOHIP_FOLLOW_MFMA
-#define BOHIP_FOLLOW_MFMA 1   // 1 (round 6): the panel followers solve and update on the matrix pipe (follow_block below); 0: round 5's register-tiled VALU form
-#endif
+constexpr int WK_XS = 18;                     // the owner's panel rows XB[128][18]: rows 16-byte aligned (two entries per ds_read_b128), 16 consecutive rows on 16 different bank quads
 constexpr int WK_S = 20;                      // round 6, row stride of the follower's LDS arrays: 20 r + k (8-byte units) hits 32 different bank pairs for r < 8, k < 4 -- the
                                               // footprint of one MFMA operand fetch -- and keeps 16-byte alignment
-#if BOHIP_FOLLOW_MFMA
-constexpr int WK_LDS_DOUBLES = 2 * TILE * WK_S + 16 * WK_S + 2;   // Lp[128][20] | X[128][20] | W16[16][20] | next-panel-ready word: 43.5 KB (round 5: 55.5 -- a CU must still hold a column updater and a flagged launch's workgroup beside a follower)
-#else
-constexpr int WK_LDS_DOUBLES = 16 * (TILE + 2) + 2 * TILE * WK_XS + 256 + 2;   // LPt[16][130] | XB[128][18] | XS[128][18] | W16[16][16] | next-panel-ready word
-#endif
+constexpr int WK_LDS_DOUBLES = 2 * TILE * WK_S + 16 * WK_S + 2;   // Lp[128][20] | X[128][20] | W16[16][20] | next-panel-ready word: 43.5 KB
 constexpr int INV_LS = TILE - 16 + 4;           // row stride of the inverter's rows of L (116 = 20 mod 32: see WK_S)
 constexpr int INV_LDS_DOUBLES = (TILE - 16) * TILE + 16 * TILE + 16 * INV_LS + 16 * WK_S;   // the inverter workgroup's image (inverter_role): Wimg | Tl | Lrow | W16
 constexpr int CH_LDS_BYTES = (INV_LDS_DOUBLES > TILE * CH_LD + 2 * TILE + 2 * 16 * CH_WLS ? INV_LDS_DOUBLES : TILE * CH_LD + 2 * TILE + 2 * 16 * CH_WLS) * 8;   // the potf2 image + dl + idl + W16 scratch (the worker arrays alias its start), or the inverter's
@@ -70,7 +57,7 @@ static_assert(WK_LDS_DOUBLES * 8 <= CH_LDS_BYTES, "worker arrays must fit inside
 
 struct CholFlags {
     unsigned* panel;      // [T * 8]   panel p of block k is published (columns of L_kk in L, 1/diag in idl_g)
-    unsigned* solved;     // [T]       mode2: W_kk = L_kk^-1 is in W / W' (k_chol_inverter)
+    unsigned* solved;     // [T]       W_kk = L_kk^-1 is in W / W' (inverter_role)
     unsigned* crit;       // [T]       counter: waves of the update launch for row k+2 of block k that have finished
     unsigned* abort;      // [1]       set on a spin time-out: every wait returns at once
     double* w16_g;        // [T * 8][16][16] inverse of each 16 x 16 pivot block (lower, zeros above), published with its panel
@@ -82,16 +69,12 @@ struct CholFlags {
     unsigned* farall;     // [T]       storing waves of the first 128 columns (column k+2) of block k's far update
     unsigned* fol;        // [T]       bulk followers of block k that have finished
     unsigned* colall;     // [T]       (every storing wave of block k's column update; not waited on)
-    int mode2;            // > 0: large-T form, the value is the window `win` (6): block k's flagged update covers columns k+1 .. 4 (k / 4) + win -- (cholesky_dataflow2): no persistent followers beyond the chain -- rows >= k+3 are solved by
-                          // a launch against the inverse W_kk (k_chol_inverter raises solved[k]), block k's flagged update covers the
-                          // columns k+1 .. 4 (k / 4) + 6, the columns beyond get four blocks at a time from plain K = 512 launches
     unsigned crit_want;   // value of crit[k] when the whole row-(k+2) update launch of block k is in memory
     unsigned panel_want;  // value of panel[..] when every publishing wave has seen its stores land
     unsigned long long spin_ticks;   // bound of every in-kernel wait (wall_clock64 ticks), see flag_wait_ge
-    int nsf;              // executor form: solve-follower workgroups of the chain kernel (rows k+3 .. k+2+nsf of block k)
-    unsigned* xp3;        // [T * 8]   mode2 >= 200: panel p of S(k+3, k) is complete (solve follower 0): what the gated updates of row k+3 consume
-    unsigned* pre3;       // [T * 4]   mode2 >= 200: tile (k+3, k+1+j) carries every block before k (executor: 16 per tile): pre3[4 k + j]
-    unsigned* resident;   // [1]       persistent workgroups that have started (form 1: what k_chol_gate holds the flagged launches back for)
+    int nsf;              // solve-follower workgroups of the chain kernel (rows k+3 .. k+2+nsf of block k)
+    unsigned* xp3;        // [T * 8]   panel p of S(k+3, k) is complete (solve follower 0): what the gated updates of row k+3 consume
+    unsigned* pre3;       // [T * 4]   tile (k+3, k+1+j) carries every block before k (executor: 16 per tile): pre3[4 k + j]
 };
 
 // Bound of every in-kernel wait, in ticks of wall_clock64() (100 MHz constant clock): 200 ms by default.  The longest legitimate
@@ -155,24 +138,8 @@ __host__ __device__ constexpr int blk_bi(int idx) {
 }
 __host__ __device__ constexpr int blk_bj(int idx) { return idx - blk_bi(idx) * (blk_bi(idx) + 1) / 2; }
 
-// ------------------------------------------------------------------------------------------------------------------------
-// Panel follower.  Thread t: row rr = t & 127 of tile (i, k), column group q = t >> 7 (32 columns, wave-uniform).
-//   a[32]   this thread's piece of the tile row, in registers for the whole block
-//   D1 (owners only): tile (i, i) lower, 18 sub-block elements per thread (half H = t >> 8 takes sub-blocks 2s + H)
-// Per panel p: wait flag -> stage L_kk[:, 16p..16p+15] and 1/diag into LDS -> the threads that hold columns 16p..16p+15
-// solve  x L16' = a  by substitution (x = 16 new entries of L(i, k)), publish x in LDS and to S -> everybody applies
-// a[c'] -= x . L_kk[c'][16p..] to the columns still to come -> (owners) D1 -= x_i . x_j.
-// ------------------------------------------------------------------------------------------------------------------------
-// LDS of a follower: the published panel TRANSPOSED, LPt[m][i] = L_kk[i][16p + m], the panel rows XB[row][m] (first the
-// not-yet-solved tile entries, then the solution x), and 1 / diag of the pivot block.
-// Why this layout: an LDS read returns 64 lanes x its width whether or not the lanes share an address, so a thread that owns a
-// whole row piece and reads every L_kk entry as a broadcast (the first version) moved 256 KB per wave and panel and the update
-// took 10 us.  With an 8-row x 4-column register block per lane, a step of the update needs 8 + 4 operands for 32 FMAs.
-constexpr int WK_LS = TILE + 2;   // row stride of LPt (even: 16-B aligned rows; +2 spreads the staging writes over the banks)
-
-#if BOHIP_FOLLOW_MFMA
-// ---- round 6: the panel follower on the matrix pipe ------------------------------------------------------------------------------------
-// Round 5's follower (kept below, BOHIP_FOLLOW_MFMA=0) held 8 rows x 4 columns per lane and paid, per panel, 32 broadcast reads of 16 bytes
+// ---- the panel follower on the matrix pipe ----------------------------------------------------------------------------------------------
+// Round 5's follower (register-tiled VALU form) held 8 rows x 4 columns per lane and paid, per panel, 32 broadcast reads of 16 bytes
 // for the row solve (0.9 us of LDS time: an LDS read returns 64 lanes x its width whether or not the lanes share an address) and 96 per
 // updating wave for the rank-16 update (2.5 us with seven waves updating): 4.3-5 us per panel against a pivot that publishes one every
 // 4.3 us since the pivot block's own phases moved to the matrix pipe.  Here both are v_mfma_f64_4x4x4 products (2 x 2 blocks = 8 x 8 x 4 per
@@ -380,160 +347,6 @@ __device__ __forceinline__ void load_row_piece(const double* __restrict__ Lmat, 
         a[2 * rb + 1] = odd ? v[rb].y : got;
     }
 }
-#else
-// x L16' = r  <=>  x = r W16',  W16 = L16^-1 published by the pivot workgroup: 4 of the 16 entries per thread, all 512
-// threads, no dependent chain (the substitution by one thread per row -- 16 dependent steps behind two barriers -- took 4 us
-// of a 10 us panel).
-// Thread t of a follower: wave w = t >> 6 owns columns 16w..16w+15 of tile (i, k); lane (r16 = lane & 15, cg = lane >> 4)
-// holds rows r16 + 16 i (i < 8) x columns 16w + 4cg + e (e < 4):  a[4 i + e].
-template <int H>
-__device__ __forceinline__ void d1_rank16(const double* XB, double (&d)[18]);
-template <bool WITH_D1, int H>
-__device__ __forceinline__ void follow_block(const double* __restrict__ Lmat, int64_t ld, double* __restrict__ S,
-                                             int i_tile, int k_blk, const CholFlags& fl, double* wk, double (&a)[32],
-                                             double (&d)[18], unsigned* xf) {
-    // xf (rows k+1, k+2 only): raised per panel once its 16 columns of L(i, k) are in S -- the gated update of row k+2 consumes
-    // them chunk by chunk while the block is still being factored
-    const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6), r16 = lane & 15, cg = lane >> 4;
-    double* LPt = wk;                        // [16][WK_LS]
-    double* XB = wk + 16 * WK_LS;            // [128][18]  panel entries before the solve
-    double* XS = XB + TILE * WK_XS;          // [128][18]  x = the 16 new columns of L(i, k)
-    double* W16s = XS + TILE * WK_XS;        // [16][16]
-    const double* Lkk = Lmat + (int64_t)k_blk * TILE * (ld + 1);
-    const int ty = (t & 255) >> 4, tx = t & 15;
-    // A follower that is BEHIND the pivot (its tile arrived late) finds the next panel already published: its staging loads are then
-    // issued before this panel's arithmetic and land beside it -- one memory round trip per panel less while catching up (the
-    // pivot publishes a panel every ~7 us, a follower needed ~6 us per panel, so a late start was never made up)
-    int* nready = reinterpret_cast<int*>(W16s + 256);
-    double pv0 = 0.0, pv1 = 0.0, pv2 = 0.0, pv3 = 0.0, pw = 0.0;
-    bool have = false;
-    for (int p = 0; p < CH_PANELS; ++p) {
-        if (t == 0) {
-            if (WITH_D1 && k_blk == 1) CH_MARK(5912 + p);   // starts waiting (or finds the panel staged ahead)
-            if (!have) flag_wait_ge(fl.panel + k_blk * CH_PANELS + p, fl.panel_want, fl.abort, fl.spin_ticks);
-            if (WITH_D1) CH_MARK(1024 + k_blk * CH_PANELS + p);
-            *nready = (p + 1 < CH_PANELS && __hip_atomic_load(fl.panel + k_blk * CH_PANELS + p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= fl.panel_want) ? 1 : 0;
-        }
-        __syncthreads();
-        const bool nxt = *nready != 0;
-        {   // stage the published panel: rows 16p..127 of L_kk, columns 16p..16p+15 (4 threads per 128-B row segment)
-            const int i = t >> 2, mq = t & 3;
-            if (i >= 16 * p) {
-                double v0 = pv0, v1 = pv1, v2 = pv2, v3 = pv3;
-                if (!have) {
-                    const double* src = Lkk + (int64_t)i * ld + 16 * p + 4 * mq;
-                    d2 u0, u1;
-                    ld_agent_x2_issue(src, u0);
-                    ld_agent_x2_issue(src + 2, u1);
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(u0), "+v"(u1) : : "memory");
-                    v0 = u0.x; v1 = u0.y; v2 = u1.x; v3 = u1.y;
-                }
-                double* dst = LPt + (4 * mq) * WK_LS + i;
-                dst[0] = v0; dst[WK_LS] = v1; dst[2 * WK_LS] = v2; dst[3 * WK_LS] = v3;
-            }
-            if (have) {
-                if (t < 256) W16s[t] = pw;
-            } else if (t < 128) {
-                d2 u;
-                ld_agent_x2_issue(fl.w16_g + ((size_t)k_blk * CH_PANELS + p) * 256 + 2 * t, u);
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(u) : : "memory");
-                *reinterpret_cast<d2*>(W16s + 2 * t) = u;
-            }
-        }
-        if (nxt) {   // the next panel's staging loads: in flight during this panel's solve and update
-            const int i = t >> 2, mq = t & 3;
-            if (i >= 16 * (p + 1)) {
-                const double* src = Lkk + (int64_t)i * ld + 16 * (p + 1) + 4 * mq;
-                pv0 = ld_agent(src); pv1 = ld_agent(src + 1); pv2 = ld_agent(src + 2); pv3 = ld_agent(src + 3);   // (in flight across the panel's phases: loads the compiler tracks)
-            }
-            if (t < 256) pw = ld_agent(fl.w16_g + ((size_t)k_blk * CH_PANELS + p + 1) * 256 + t);
-        }
-        have = nxt;
-        if (w == p) {   // the wave that holds the panel's columns hands them to the row solvers
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) XB[(r16 + 16 * i) * WK_XS + 4 * cg + e] = a[4 * i + e];
-        }
-        __syncthreads();
-        {   // thread (row = t & 127, part = t >> 7): x[4 part .. 4 part + 3] = sum_k r[k] W16[c][k]
-            const int row = t & 127, part = t >> 7;
-            double r[16], x4[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int c = 0; c < 16; c += 2) {
-                const d2 rv = *reinterpret_cast<const d2*>(XB + row * WK_XS + c);
-                r[c] = rv.x; r[c + 1] = rv.y;
-            }
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-                const d2* wrow = reinterpret_cast<const d2*>(W16s + (4 * part + cc) * 16);
-#pragma unroll
-                for (int k2 = 0; k2 < 8; ++k2) {
-                    const d2 wv = wrow[k2];
-                    x4[cc] += r[2 * k2] * wv.x;
-                    x4[cc] += r[2 * k2 + 1] * wv.y;
-                }
-            }
-            double* Srow = S + ((int64_t)i_tile * TILE + row) * ld + (int64_t)k_blk * TILE + 16 * p + 4 * part;
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) XS[row * WK_XS + 4 * part + cc] = x4[cc];
-            st_agent2(Srow, x4[0], x4[1]);
-            st_agent2(Srow + 2, x4[2], x4[3]);
-        }
-        __syncthreads();
-        if (w > p) {   // wave-uniform: this wave's columns lie beyond the panel
-            const double* lp = LPt + 16 * w + 4 * cg;
-#pragma unroll 2
-            for (int m = 0; m < 16; m += 2) {   // two contraction indices per round of LDS reads (x as 16-byte pieces); per entry still m = 0, 1, 2, ...
-                d2 xv[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) xv[i] = *reinterpret_cast<const d2*>(XS + (r16 + 16 * i) * WK_XS + m);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const d2 l01 = *reinterpret_cast<const d2*>(lp + (m + h) * WK_LS), l23 = *reinterpret_cast<const d2*>(lp + (m + h) * WK_LS + 2);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double x = h == 0 ? xv[i].x : xv[i].y;
-                        a[4 * i + 0] -= x * l01.x;
-                        a[4 * i + 1] -= x * l01.y;
-                        a[4 * i + 2] -= x * l23.x;
-                        a[4 * i + 3] -= x * l23.y;
-                    }
-                }
-            }
-        }
-        if constexpr (WITH_D1) d1_rank16<H>(XS, d);
-        if (xf) release_wg();   // the S stores of this panel were issued two phases ago: they have landed by now
-        __syncthreads();   // LPt / XB are rewritten by the next panel
-        if (xf && t == 0) { flag_set(xf + p, 1u); if (!WITH_D1 && k_blk < 24 && i_tile - k_blk <= 2) CH_MARK(3648 + (k_blk * 2 + (i_tile - k_blk - 1)) * 9 + p); }
-        if (WITH_D1 && t == 0) CH_MARK(2048 + k_blk * CH_PANELS + p);
-    }
-}
-
-__device__ __forceinline__ void load_row_piece(const double* __restrict__ Lmat, int64_t ld, int i_tile, int k_blk,
-                                               double (&a)[32]) {
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, r16 = lane & 15, cg = lane >> 4;
-    const double* base = Lmat + ((int64_t)i_tile * TILE + r16) * ld + (int64_t)k_blk * TILE + 16 * w + 4 * cg;
-    d2 v[16];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        ld_agent_x2_issue(base + (int64_t)16 * i * ld, v[2 * i]);
-        ld_agent_x2_issue(base + (int64_t)16 * i * ld + 2, v[2 * i + 1]);
-    }
-    asm volatile("s_waitcnt vmcnt(0)"
-                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),
-                   "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 :
-                 : "memory");
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        a[2 * i] = v[i].x;
-        a[2 * i + 1] = v[i].y;
-    }
-}
-
-#endif
-
 // ------------------------------------------------------------------------------------------------------------------------
 // Pivot role: the Cholesky part of k_potf2_inv (same panels, same look-ahead of the next 16 x 16 pivot block beside the
 // trailing update) on the image `a` already in LDS, run by threads 0..255 of the 512-thread owner (the others only keep
@@ -558,97 +371,6 @@ __device__ __forceinline__ void publish_panel(double* __restrict__ Lblk, int64_t
     if (tid < 128) st_agent2(w16_out + 2 * tid, w16s[(tid >> 3) * CH_WLS + 2 * (tid & 7)], w16s[(tid >> 3) * CH_WLS + 2 * (tid & 7) + 1]);   // 256 entries, 16 bytes per store
 }
 
-// ---- forward substitution against a 16 x 16 pivot block on LPR lanes per row (used by pivot_block) ----------------------------------
-// Lane p of a group of LPR (= 2 or 4) neighbouring lanes holds the entries k = p + LPR j of its row.  The owner of entry C finishes it, a DPP
-// quad_perm move hands it to the group, everybody updates the entries it holds.
-#ifndef BOHIP_FSUB_LPR
-#define BOHIP_FSUB_LPR 4   // measured: 2 lanes per row (four waves, 150 registers of pivot-block entries per lane) 1.36 ms at N = 3000, 4 lanes (seven waves) 1.33-1.35;
-                          // since the owner keeps x in its slot the 2-lane form no longer fits 256 registers (it spills, and the chain kernel then times out)
-#endif
-constexpr int FSUB_LPR = BOHIP_FSUB_LPR, FSUB_NJ = 16 / FSUB_LPR;
-static_assert(FSUB_LPR == 4, "the two-lane form needs more than 256 registers (see above)");
-template <int S>
-__device__ __forceinline__ double group_bcast(double v) {   // the value lane S of this lane's group holds (DPP quad_perm: a VALU move, no LDS)
-    constexpr int ctrl = FSUB_LPR == 4 ? (S | (S << 2) | (S << 4) | (S << 6)) : (S | (S << 2) | ((2 + S) << 4) | ((2 + S) << 6));
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, ctrl, 0xf, 0xf, true);   // (old = the source itself: no zero to materialise; every lane has a source lane)
-    hi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-// The pivot block's entries a lane needs -- L16[p + LPR j][C] for the steps C that still reach slot j, and 1 / diag -- are ALL fetched before
-// the first step (one round of LDS reads): inside the steps nothing but the product, the group broadcast and the updates is left on the
-// dependent chain (fetched where they were used, every step waited for its own LDS round trip).
-struct GroupL16 {
-    double l[16][FSUB_NJ], id[16];
-};
-__device__ __forceinline__ void group_l16_load(const double* a, const double* idl, int P, int p, GroupL16& L) {
-#pragma unroll
-    for (int C = 0; C < 16; ++C) {
-        L.id[C] = idl[P + C];
-#pragma unroll
-        for (int j = 0; j < FSUB_NJ; ++j) L.l[C][j] = (FSUB_LPR * j + FSUB_LPR - 1 <= C) ? 0.0 : a[(P + C) * PF_LD + P + p + FSUB_LPR * j];
-    }
-}
-// one row below the pivot block:  x L16' = a[i][P .. P+15].
-// Step C: x_C = rw_C / L_CC (owner: lane C % LPR), written to the image as column P + C; then rw_k -= x_C L16[k][C] for every k > C.
-template <int C>
-__device__ __forceinline__ void group_fsub_row_step(double* a, int P, int i, bool on, int p, double (&rw)[FSUB_NJ], const GroupL16& L) {
-    const double x = group_bcast<(C % FSUB_LPR)>(rw[C / FSUB_LPR] * L.id[C]);
-    rw[C / FSUB_LPR] = (p == (C % FSUB_LPR)) ? x : rw[C / FSUB_LPR];   // the owner keeps x_C in the slot it no longer needs: written out after the last step
-#pragma unroll
-    for (int j = 0; j < FSUB_NJ; ++j) {
-        if (FSUB_LPR * j + FSUB_LPR - 1 <= C) continue;   // no lane holds an entry k > C in this slot
-        if (FSUB_LPR * j > C || p + FSUB_LPR * j > C) rw[j] -= x * L.l[C][j];
-    }
-    // (keep the steps apart: left to itself the scheduler sinks every update next to its consumer to save registers, and entry C then waits
-    // for a chain of C dependent FMAs -- the left-looking form's latency with the right-looking form's code)
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int... Cs>
-__device__ __forceinline__ void group_fsub_row_steps(double* a, int P, int i, bool on, int p, double (&rw)[FSUB_NJ], const GroupL16& L,
-                                                     std::integer_sequence<int, Cs...>) {
-    (group_fsub_row_step<Cs>(a, P, i, on, p, rw, L), ...);
-}
-__device__ __forceinline__ void group_fsub_rows(double* a, const double* idl, int P, int i, bool on, int p) {
-    double rw[FSUB_NJ];
-#pragma unroll
-    for (int j = 0; j < FSUB_NJ; ++j) rw[j] = on ? a[i * PF_LD + P + p + FSUB_LPR * j] : 0.0;
-    GroupL16 L;
-    group_l16_load(a, idl, P, p, L);
-    group_fsub_row_steps(a, P, i, on, p, rw, L, std::make_integer_sequence<int, 16>{});
-    if (on) {   // x_k for k = p + LPR j: column P + k of the image, row i
-#pragma unroll
-        for (int j = 0; j < FSUB_NJ; ++j) a[(P + p + FSUB_LPR * j) * PF_LD + i] = rw[j];
-    }
-}
-// column cc of W16 = L16^-1 (right-looking: w_k is final, every later partial sum takes its term at once).  Lane p holds the partial
-// sums of the rows i = p + LPR j.
-template <int K>
-__device__ __forceinline__ void group_fsub_w16_step(double* w16s, int cc, int p, double (&sacc)[FSUB_NJ], const GroupL16& L) {
-    const double w_own = (K < cc) ? 0.0 : (K == cc ? L.id[K] : -sacc[K / FSUB_LPR] * L.id[K]);   // (meaningful in the owner lane K % LPR)
-    const double wk = group_bcast<(K % FSUB_LPR)>(w_own);
-    if (p == (K % FSUB_LPR)) w16s[K * 16 + cc] = wk;
-#pragma unroll
-    for (int j = 0; j < FSUB_NJ; ++j) {
-        if (FSUB_LPR * j + FSUB_LPR - 1 <= K) continue;
-        if (FSUB_LPR * j > K || p + FSUB_LPR * j > K) sacc[j] += L.l[K][j] * wk;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int... Ks>
-__device__ __forceinline__ void group_fsub_w16_steps(double* w16s, int cc, int p, double (&sacc)[FSUB_NJ], const GroupL16& L, std::integer_sequence<int, Ks...>) {
-    (group_fsub_w16_step<Ks>(w16s, cc, p, sacc, L), ...);
-}
-__device__ __forceinline__ void group_fsub_w16(const double* a, const double* idl, double* w16s, int P, int cc, int p) {
-    double sacc[FSUB_NJ];
-#pragma unroll
-    for (int j = 0; j < FSUB_NJ; ++j) sacc[j] = 0.0;
-    GroupL16 L;
-    group_l16_load(a, idl, P, p, L);
-    group_fsub_w16_steps(w16s, cc, p, sacc, L, std::make_integer_sequence<int, 16>{});
-}
-
-#if BOHIP_PIVOT_W16GROW
 // Round 6.  Per panel the critical path was  factor16 (2.7 us) -> [16-step substitution of the rows below the pivot block (1.6 us) beside the
 // 16-step inverse W16 on wave 4 (2.1 us)] -> update of the next pivot block (0.5 us) -> factor16 ...: 5.2 us, 41 us per 128-block.  W16 now
 // comes out of factor16w itself (kernels_linalg.hip: the inverse's partial sums live in the triangle the Schur complement has left and take
@@ -749,85 +471,6 @@ __device__ __forceinline__ void pivot_block(double* a, double* dl, double* idl, 
         if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 2);
     }
 }
-#else
-__device__ __forceinline__ void pivot_block(double* a, double* dl, double* idl, double* __restrict__ Lblk, int64_t ld,
-                                            int k_blk, const CholFlags& fl, int* info, int row0) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool act = tid < PF_THREADS;
-    unsigned* pflag = fl.panel + k_blk * CH_PANELS;
-    double* w16s = idl + TILE;   // [16][16] inverse of the current pivot block
-    if (wave == 0) factor16(a, dl, idl, 0, lane, info, row0);
-    __syncthreads();
-    for (int jb = 0; jb < CH_PANELS; ++jb) {
-        const int P = 16 * jb;
-        const int base = P + 16, m = TILE - base;
-        // Phase A: W16 = inverse of the pivot block (for the followers) on wave 4 beside the row solves below the pivot block on the other
-        // waves -- LPR = 4 LANES per column of W16 / per row (group_fsub_*: lane p of a group holds the entries p, p + 4, ...; the
-        // owner of entry c finishes it, a DPP quad_perm move hands it to the group, everybody updates the entries it holds; two lanes per row
-        // were measured too: the same 1.9 us -- a step is ~22 wave instructions either way and issue-bound).  Until
-        // round 4 one thread per row / column walked all 16 steps with 136 broadcast LDS reads in its dependent chain: 2.4 us of a 6.15 us
-        // panel for a few hundred flops per thread.  Same operations in the same order per entry: the factor does not change by a bit.
-        if (wave == 4) {
-            if (lane < 16 * FSUB_LPR) group_fsub_w16(a, idl, w16s, P, lane / FSUB_LPR, lane % FSUB_LPR);
-            if (tid == PF_THREADS && k_blk == 1) CH_MARK(3584 + 8 * jb + 5);
-        } else {
-            const int t4 = wave < 4 ? tid : tid - 64, ri = t4 / FSUB_LPR;
-            if (t4 < FSUB_LPR * (TILE - 16)) group_fsub_rows(a, idl, P, base + ri, ri < m, t4 % FSUB_LPR);   // (whole waves in or out)
-            if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 6);
-        }
-        __syncthreads();
-        if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 0);
-        // Panel jb is final.  Two phases follow.  First the rank-16 update of the NEXT pivot block alone, on 256 threads (16 products per
-        // thread) -- until round 4 the publishing waves issued their stores in this phase too and everybody waited at its barrier for them:
-        // 1.4 us of every 7 us panel.  (The update on wave 0 alone, four elements per lane and no barrier, was measured as well: 2.0 us.)
-        // Then: waves 4, 6, 7 publish the panel (stores, the wait for them to land, +1 each on the panel's flag: followers wait for 3), wave 0
-        // factors the next pivot block, waves 1, 2, 3, 5 update the rest of the trailing matrix.
-        if (m > 0 && act) {
-            const int ty = tid >> 4, tx = tid & 15;
-            double acc = 0.0;
-#pragma unroll
-            for (int c = 0; c < 16; ++c) {
-                const double* col = a + (P + c) * PF_LD + base;
-                acc += col[ty] * col[tx];
-            }
-            if (tx <= ty) a[(base + ty) * PF_LD + base + tx] -= acc;
-        }
-        if (m > 0) __syncthreads();
-        if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 1);
-        // Who does what follows from where the waves sit: wave w runs on SIMD w % 4, so wave 4 shares its SIMD with wave 0.  The pivot
-        // chain (wave 0) gets the lightest neighbour: waves 4, 6, 7 publish (a few LDS reads and stores each), waves 1, 2, 3, 5 carry the
-        // trailing update.  (With the trailing update on waves 1-4, factor16 took 7.3 us instead of 2.9 beside the first, widest update
-        // of a block -- the "slow first panel" of rounds 2-3.)
-        if (wave == 4 || wave >= 6) {   // 192 threads walk the 256 publishing slots
-            const int pw = wave == 4 ? 0 : wave - 5;
-            for (int s_ = 64 * pw + lane; s_ < PF_THREADS; s_ += 192)
-                publish_panel(Lblk, ld, a, dl, w16s, fl.w16_g + ((size_t)k_blk * CH_PANELS + jb) * 256, P, s_);
-            if (lane == 0 && wave == 4 && k_blk == 1) CH_MARK(5904 + jb);   // wave 4 starts waiting for its stores
-            release_wg();   // s_waitcnt vmcnt(0): this wave's part of the panel has left the CU
-            if (lane == 0) {
-                atomicAdd(pflag + jb, 1u);
-                if (wave == 4) CH_MARK(k_blk * CH_PANELS + jb);
-                if (wave == 6 && k_blk == 1) CH_MARK(5888 + jb);
-                if (wave == 7 && k_blk == 1) CH_MARK(5896 + jb);
-            }
-        }
-        if (m == 0) break;
-        if (wave == 0) {
-            factor16(a, dl, idl, base, lane, info, row0);
-            if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 3);
-        } else if (wave <= 3 || wave == 5) {
-            // waves 1, 2, 3, 5: one (ty, tx) position of every live 16 x 16 sub-block per thread.  (k_potf2_inv has three waves for this
-            // and splits the fourth wave's rows three ways: four code variants per size, 28 in all, ~30 KB.)
-            const int u = 64 * (wave == 5 ? 3 : wave - 1) + lane;
-            trailing_dispatch<true, -1>(a, P, m >> 4, u >> 4, u & 15);
-            if (tid == 64 && k_blk == 1) CH_MARK(3584 + 8 * jb + 4);
-        }
-        __syncthreads();
-        if (tid == 0 && k_blk == 1) CH_MARK(3584 + 8 * jb + 2);
-    }
-}
-
-#endif
 // diagonal tile (r, r): HBM -> registers (owner, follower role) / registers -> LDS image (owner, pivot role)
 template <int H>
 __device__ __forceinline__ void d1_load(const double* __restrict__ Lmat, int64_t ld, int r, double (&d)[18]) {
@@ -942,15 +585,8 @@ __device__ __forceinline__ void chain_owner(double* __restrict__ Lmat, int64_t l
     }
 }
 
-// last column of block k's flagged update in mode2
-__host__ __device__ __forceinline__ int near_last_col(int T, int k, int win) { return min(T - 1, 4 * (k / 4) + win); }
-// waves of the first row tile (row k+3) of block k's flagged update: every workgroup of that row adds 8, with or without a tile
-// (host: nt64 = 2 (T - k - 2) columns k+2 ..; mode2: columns k+1 .. near_last_col)
-__device__ __forceinline__ unsigned rest_want(const CholFlags& fl, int k) {
-    if (fl.mode2 >= 200) return 24u;   // executor form: the six gated-update workgroups of row k+3 inside the chain kernel, four storing waves each
-    if (fl.mode2 >= 100) return 48u;   // left-looking form: three launches of two workgroups each hold row k+3's tiles
-    return fl.mode2 ? 8u * 2u * (unsigned)(near_last_col(fl.T, k, fl.mode2) - k) : 8u * 2u * (unsigned)(fl.T - k - 2);
-}
+// rest[k] when row k+3's three tiles carry block k: the six gated-update workgroups of that row (gated_worker3), four storing waves each
+constexpr unsigned rest_want = 24u;
 
 // ---- role 2 (workgroups 2, 3): critical followers.  Row r is followed twice -- as "row k+2" during block k = r-2 and as
 // "row k+1" during block k = r-1 -- always by the workgroup of its parity, so at any block the two rows next to the pivot
@@ -965,8 +601,7 @@ __device__ __forceinline__ void crit_follower(double* __restrict__ Lmat, int64_t
         if (k >= 1) {   // tile (r, k) must carry block k-1's update: row k+1 gets it from the gated update, row k+2 from the column launch
             if (tid == 0) {
                 if (r == k + 1) flag_wait_ge(fl.crit + (k - 1), fl.crit_want, fl.abort, fl.spin_ticks);
-                else if (fl.mode2) flag_wait_ge(fl.rest + (k - 1), rest_want(fl, k - 1), fl.abort, fl.spin_ticks);   // tile (k+2, k): first row of block k-1's launch
-                else flag_wait_ge(fl.colr + (size_t)(k - 1) * T + r, 8u, fl.abort, fl.spin_ticks);   // tile (k+2, k): its column updaters of block k-1
+                else flag_wait_ge(fl.rest + (k - 1), rest_want, fl.abort, fl.spin_ticks);   // tile (k+2, k): row k+2 of block k-1's gated updates
             }
             __syncthreads();
             if (tid == 0 && r == k + 2) CH_MARK(4352 + k);
@@ -1076,9 +711,6 @@ __device__ __forceinline__ void gated_tile(const double* __restrict__ A, const d
     __syncthreads();
 }
 
-// waves of the first 128 columns of block k's far update (host: mt = T - k - 3 row tiles x 2 column tiles; every workgroup adds 8)
-__device__ __forceinline__ unsigned farcol_want(int T, int k) { return 8u * 2u * (unsigned)(T - k - 3); }
-
 // ---- role 3 (workgroups 4..7): the update of row k+2 with block k's panel -- the two tiles (k+2, k+1), (k+2, k+2) the
 // chain needs next (the next owner waited 36 us per block for the launch-based form of this update).
 __device__ __forceinline__ void gated_worker(double* __restrict__ Lmat, int64_t ld, const double* __restrict__ S, int T,
@@ -1089,18 +721,18 @@ __device__ __forceinline__ void gated_worker(double* __restrict__ Lmat, int64_t 
         double* C = Lmat + (int64_t)(k + 2) * TILE * ld + (int64_t)(k + 1) * TILE + (int64_t)tj * CTILE;
         const unsigned* fa = xp_at(fl, k, k + 2);
         gated_tile(A, B, C, ld, (int64_t)(k + 2) * TILE, (int64_t)(k + 1) * TILE + (int64_t)tj * CTILE, fa,
-                   tj < 2 ? xp_at(fl, k, k + 1) : fa, k >= 1 ? fl.rest + (k - 1) : nullptr, k >= 1 ? rest_want(fl, k - 1) : 0u,
+                   tj < 2 ? xp_at(fl, k, k + 1) : fa, k >= 1 ? fl.rest + (k - 1) : nullptr, k >= 1 ? rest_want : 0u,
                    fl.crit + k, fl, sm);
         if (threadIdx.x == 0 && tj == 0) CH_MARK(3300 + 4 * k + 2);
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// mode2: one persistent workgroup of the chain kernel turns every finished diagonal block into its inverse W_kk (the inverse half of k_potf2_inv)
-// and raises solved[k]: the launch that solves the rows >= k+3 of L(:, k) as a product with W_kk' waits for it.  The same
-// blocks are the seeds of the triangular inverse W = L^-1, so k_inv128 is not needed afterwards.
+// One persistent workgroup of the chain kernel turns every finished diagonal block into its inverse W_kk (the inverse half of k_potf2_inv)
+// and raises solved[k]: the executor's tasks that solve the rows beyond the followers' as a product with W_kk' wait for it.  The same
+// blocks are the seeds of the triangular inverse W = L^-1.
 // ------------------------------------------------------------------------------------------------------------------------
-// ---- role 4 (workgroup 8, mode2 only; its upper four waves leave at once -- ended waves do not take part in barriers).
+// ---- role 4 (workgroup 8).
 // INCREMENTAL: the first version waited for the block's last panel and then ran the recursive-doubling inverse of k_potf2_inv
 // (25-30 us behind the pivot block -- on the critical path of every block: pivot -> inverse -> row solve -> update -> chain).
 // W = L^-1 can follow the pivot chain row panel by row panel instead:
@@ -1235,7 +867,7 @@ __device__ __forceinline__ void inverter_role(const double* __restrict__ Lmat, i
     }
 }
 
-// ---- role 5 (workgroups 9 .. 9 + nsf - 1, executor form only): the row solves of the tiles (k+3, k) .. (k+2+nsf, k), panel
+// ---- role 5 (workgroups 9 .. 9 + nsf - 1): the row solves of the tiles (k+3, k) .. (k+2+nsf, k), panel
 // by panel behind the pivot chain like the critical followers, so that S(k+3, k) -- the operand of the three tiles the chain
 // waits for next -- is complete ~3 us after the pivot block instead of one inverse (~20 us) + one solve task (~20-40 us) later.
 // Follower f needs tile (k+3+f, k) final, i.e. a row of the executor's Late(k-1), which in turn needs S(k+3+f, k-1): for all
@@ -1256,14 +888,14 @@ __device__ __forceinline__ void solve_follower(const double* __restrict__ Lmat, 
         }
         if (tid == 0 && f < 3) CH_MARK(7168 + 256 * f + k);
         load_row_piece(Lmat, ld, r, k, ar);
-        follow_block<false, 0>(Lmat, ld, S, r, k, fl, sm, ar, dd, (f == 0 && fl.mode2 >= 200) ? fl.xp3 + (size_t)k * CH_PANELS : nullptr);
+        follow_block<false, 0>(Lmat, ld, S, r, k, fl, sm, ar, dd, f == 0 ? fl.xp3 + (size_t)k * CH_PANELS : nullptr);
         release_wg();
         __syncthreads();
         if (tid == 0) { flag_set(fl.colr + (size_t)k * T + r, 16u); if (f == 0) CH_MARK(4608 + k); if (f < 3) CH_MARK(6144 + 256 * f + k); }   // sver(r, k)
     }
 }
 
-// ---- role 6 (workgroups 9 + nsf .. 9 + nsf + 5, executor form): the chunk-gated update of the three tiles of row k+3 --
+// ---- role 6 (workgroups 9 + nsf .. 9 + nsf + 5): the chunk-gated update of the three tiles of row k+3 --
 // (k+3, k+1), which row k+3's critical follower solves during block k+1, and (k+3, k+2), (k+3, k+3), which block k+1's gated
 // updates continue -- with block k, consumed 16 columns at a time as solve follower 0 publishes S(k+3, k): the chain's window
 // spans three rows.  As executor tasks (Late(k): blocks k-1 and k, started when S(k+3, k) was complete) these tiles reached the
@@ -1286,14 +918,13 @@ __device__ __forceinline__ void gated_worker3(double* __restrict__ Lmat, int64_t
     }
 }
 
-// The persistent chain: 8 workgroups of 512 threads, one per CU (the owners' LDS image fills it).
+// The persistent chain: 9 + nsf + 6 workgroups of 512 threads, one per CU (the owners' LDS image fills it).
 __global__ __launch_bounds__(CH_THREADS, 1) void k_chol_chain(double* __restrict__ Lmat, int64_t ld, double* __restrict__ S,
                                                            int T, CholFlags fl, int* __restrict__ info, double* __restrict__ W,
                                                            double* __restrict__ WT) {
     extern __shared__ double sm[];
     const int b = blockIdx.x;
-    if (threadIdx.x == 0) atomicAdd(fl.resident, 1u);
-    if (b >= 9 + fl.nsf && fl.mode2 >= 200) {
+    if (b >= 9 + fl.nsf) {
         gated_worker3(Lmat, ld, S, T, fl, sm, b - 9 - fl.nsf);
     } else if (b >= 9) {
         solve_follower(Lmat, ld, S, T, fl, sm, b - 9);
@@ -1307,83 +938,6 @@ __global__ __launch_bounds__(CH_THREADS, 1) void k_chol_chain(double* __restrict
     } else {
         gated_worker(Lmat, ld, S, T, fl, sm, b - 4);
     }
-}
-
-// Rows >= 3 before they reach the chain.  One PERSISTENT workgroup per row i follows blocks k = 0 .. i-3 (tile (i, k) each:
-// the same panel follower as the critical ones), and two persistent workgroups per row keep tile (i, k+1) -- the tile the
-// row follows NEXT -- updated chunk by chunk (gated_tile).  A row's work for block k+1 can therefore start a few
-// microseconds after its work for block k ends; with one launch per block for each of the two steps (the first version)
-// the cycle follower -> launch gap -> K = 128 update -> launch gap was 80 us against a 58 us pivot block and paced everything.
-__global__ __launch_bounds__(CH_THREADS, 1) void k_chol_rows(const double* __restrict__ Lmat, int64_t ld, double* __restrict__ S,
-                                                          int T, CholFlags fl) {
-    extern __shared__ double sm[];
-    const int i_tile = 3 + blockIdx.x;
-    if (threadIdx.x == 0) atomicAdd(fl.resident, 1u);
-    double ar[32], d[18];
-    for (int k = 0; k + 3 <= i_tile; ++k) {
-        if (k >= 1) {   // tile (i, k) carries block k-1's update once its two column updaters have stored
-            if (threadIdx.x == 0) flag_wait_ge(fl.colr + (size_t)(k - 1) * T + i_tile, 8u, fl.abort, fl.spin_ticks);
-            __syncthreads();
-        }
-        load_row_piece(Lmat, ld, i_tile, k, ar);
-        follow_block<false, 0>(Lmat, ld, S, i_tile, k, fl, sm, ar, d, xp_at(fl, k, i_tile));
-    }
-}
-__global__ __launch_bounds__(GEMM_THREADS) void k_chol_cols(double* __restrict__ Lmat, int64_t ld, const double* __restrict__ S,
-                                                         int T, CholFlags fl) {
-    __shared__ __attribute__((aligned(16))) double sm[(TILE + CTILE) * GL_ROW];
-    const int i_tile = 3 + (blockIdx.x >> 1), h = blockIdx.x & 1;
-    if (threadIdx.x == 0) atomicAdd(fl.resident, 1u);
-    for (int k = 0; k + 3 <= i_tile; ++k) {   // tile (i, k+1), columns [64 h, 64 h + 64): -= L(i, k) L(k+1, k)'
-        const double* A = S + (int64_t)i_tile * TILE * ld + (int64_t)k * TILE;
-        const double* B = S + ((int64_t)(k + 1) * TILE + (int64_t)h * CTILE) * ld + (int64_t)k * TILE;
-        double* C = Lmat + (int64_t)i_tile * TILE * ld + (int64_t)(k + 1) * TILE + (int64_t)h * CTILE;
-        // block k-1's far update wrote this tile too (column k+1 was its FIRST column, dispatched early, own counter)
-        gated_tile(A, B, C, ld, (int64_t)i_tile * TILE, (int64_t)(k + 1) * TILE + (int64_t)h * CTILE, xp_at(fl, k, i_tile),
-                   xp_at(fl, k, k + 1), k >= 1 ? fl.farall + (k - 1) : nullptr, k >= 1 ? farcol_want(T, k - 1) : 0u,
-                   fl.colr + (size_t)k * T + i_tile, fl, sm);
-    }
-}
-
-// Form 1's flagged launches (k_gemm_nt, one per block, hundreds of workgroups that spin inside the kernel) must not reach the chip before
-// every PERSISTENT workgroup is resident: a panel follower holds 2 x 213 of a SIMD's 512 vector registers since round 6 (round 5: 2 x 160)
-// and no longer fits beside even one k_gemm_nt workgroup, so when the first flagged launch was dispatched between the persistent
-// kernels -- they sit on four streams released by one event -- some follower found no CU, the spinning workgroups waited for its rows,
-// and the factorisation ended in the 200 ms time-out (4 of 8 fresh processes at 24 row tiles, none at 16).  One wave on the flagged
-// launches' stream, in front of them, waits until the persistent workgroups have counted themselves in.
-__global__ __launch_bounds__(64) void k_chol_gate(const unsigned* word, unsigned want, unsigned* abort, unsigned long long spin_ticks) {
-    if (threadIdx.x == 0) flag_wait_ge(word, want, abort, spin_ticks);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------
-// W_kk = L_kk^-1 for every diagonal block at once (the seeds of the recursive triangular inverse): the inverse half of
-// k_potf2_inv on an image rebuilt from the finished factor.  One workgroup per block.
-// ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PF_THREADS) void k_inv128(const double* __restrict__ Lmat, int64_t ld, double* __restrict__ W,
-                                                    double* __restrict__ WT, int64_t ldw) {
-    extern __shared__ double sm[];
-    double* a = sm;
-    double* idl = sm + TILE * PF_LD + TILE;
-    const int tid = threadIdx.x;
-    const int64_t off = (int64_t)blockIdx.x * TILE;
-    const double* Lblk = Lmat + off * (ld + 1);
-    {   // mirror image: a[c][r] = L[r][c] for c < r, the lower triangle is workspace for W
-        const int j = tid & 127, ih = tid >> 7;
-#pragma unroll 1
-        for (int i0 = 0; i0 < TILE; i0 += 32) {
-            double v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = Lblk[(int64_t)(i0 + 2 * u + ih) * ld + j];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int i = i0 + 2 * u + ih;
-                if (j < i) a[j * PF_LD + i] = v[u];
-                else if (j == i) idl[i] = 1.0 / v[u];
-            }
-        }
-    }
-    __syncthreads();
-    inverse_phase(a, idl, tid, W + off * (ldw + 1), WT + off * (ldw + 1), ldw);
 }
 
 }  // namespace bohip

@@ -1,9 +1,9 @@
 // kernels_exec.hip -- the tile-task executor of the blocked Cholesky factorisation AND of the triangular inverse W = L^-1 (row A2 of
 // SURVEY.md section 8; reference call sites: update!/fit! at src/models/gp.jl:11-18, i.e. the LAPACK potrf behind ElasticPDMats).
 //
-// Why.  The second dataflow form (cholesky_dataflow2/3 in bohip.hip) feeds the persistent chain (k_chol_chain) from ~4 launches
-// per 128-block on three streams: every flagged launch parks hundreds of workgroups that spin on flags inside the kernel (at
-// N = 10^4 about 300 of the chip's 512 workgroup slots, which is why the K = 512 bulk updates beside them ran at 37 TF/s), the
+// Why.  The stream-based forms this one replaced (retired) fed the persistent chain (k_chol_chain) from ~4
+// launches per 128-block on three streams: every flagged launch parked hundreds of workgroups that spun on flags inside the kernel
+// (at N = 10^4 about 300 of the chip's 512 workgroup slots, which is why the K = 512 bulk updates beside them ran at 37 TF/s), the
 // in-order streams put a 1 ms bulk launch in front of the 0.1 ms one the chain needs next, and the left-looking column update
 // (K up to 1024, one workgroup per tile) sat on the critical path of every block: 11.7 ms for 333 GF.
 //
@@ -93,10 +93,8 @@ struct ExQueues {
     int nfast;                  // the next nfast workgroups never take bulk or wave tasks: whatever the chain will need soon (queues 1-3) finds
                                 // one of them free.  Chain-paced sizes only: with every general workgroup inside a 60-100 us bulk / wave task
                                 // right after a group's release, the row steps waited that long and the pivot chain with them
-    int fill_inv;               // ... and inverse-wave work (1), see k_chol_exec
+    int fill_inv;               // 1: a workgroup that holds a claimed task whose counters are not in yet takes inverse-wave work meanwhile (k_chol_exec) ...
     unsigned patience_ticks;    // ... but only once the held record has been waited for this long (wall-clock ticks of 10 ns)
-    int fill;                   // a workgroup that holds a claimed task whose counters are not in yet takes bulk work meanwhile:
-                                // 1 = if the held task is an Early sum (queue 2: two blocks of slack), 2 = also for queue 1, 0 = never
     int stride[EX_NQ];          // records per claim: 1, or 2 = both halves of a tile run back to back by one workgroup (the look and
                                 // claim between two tasks cost ~12 us against ~70 us of work: queues 1 and 2 are claimed in pairs)
 };
@@ -435,7 +433,7 @@ __global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_chol_exec(ExQueues q) {
                 int tk = -3;
                 // which queues may this workgroup claim from right now?  one held record per slot: `pend` (queues 1, 2), `pend2`
                 // (bulk), `pend3` (inverse: rows or waves).  While `pend` is occupied only fill-in work is taken: inverse waves
-                // (nothing ever waits for those), bulk if asked for (q.fill).
+                // (nothing ever waits for those).
                 // A record that was claimed a little ahead of its counters is usually microseconds from runnable (its producers
                 // were claimed just before it): for `patience` the workgroup only polls -- picking up a 60-100 us task meanwhile
                 // made row-chain records and row steps start that much late on a mostly idle chip (N = 3000: the inverse's rows
@@ -451,7 +449,6 @@ __global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_chol_exec(ExQueues q) {
                     if (pend2 < 0) qmask |= 1u << EX_QBULK;
                     if (pend3 < 0 && pend2 < 0) qmask |= 1u << EX_QWAVE;
                 } else {
-                    if (pend2 < 0 && (q.fill >= 2 || (q.fill == 1 && queue_of(pend) == 2))) qmask |= 1u << EX_QBULK;
                     if (pend3 < 0 && q.fill_inv) qmask |= 1u << EX_QWAVE;
                 }
                 qmask &= lane_mask;

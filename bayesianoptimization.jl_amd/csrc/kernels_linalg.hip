@@ -8,9 +8,6 @@
 // update_cK! + ElasticPDMats Cholesky behind them).
 #include "gemm_core.h"
 #include <utility>
-#ifndef BOHIP_FACTOR16_ROWDPP
-#define BOHIP_FACTOR16_ROWDPP 1   // factor16: row J's entries reach the lanes of a 16-row by DPP row_newbcast (1) or ds_swizzle (0)
-#endif
 
 namespace bohip {
 
@@ -190,27 +187,13 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
 }
 // 1/sqrt(x) to ~1 ulp: hardware v_rsq_f64 seed + two Newton steps (the libm sqrt + divide pair is a
 // ~150-cycle dependent chain, and this sits on the critical path of every column).
-#ifndef BOHIP_RSQRT_NEWTON2
-#define BOHIP_RSQRT_NEWTON2 1   // 1 (default): two Newton steps; 0: one Halley step (round-4 experiment: same speed, different last bits)
-#endif
+// (One third-order Halley step instead was measured in round 4, profiles/r04_rsqrt_halley_ab.txt: inside the noise, different last bits.)
 __device__ __forceinline__ double fast_rsqrt(double x) {
     double y = __builtin_amdgcn_rsq(x);
-#if BOHIP_RSQRT_NEWTON2
     double h = 0.5 * x;
     y = y * (1.5 - h * y * y);
     y = y * (1.5 - h * y * y);
     return y;
-#else
-    // ONE third-order (Halley) step instead of two Newton steps: v_rsq_f64 is good to ~2^-24, its residual e = 1 - x y^2 cubed is below
-    // 2^-70, and the chain  x y -> e -> (t, y e) -> y + y e t  is four dependent operations instead of eight.  This function sits on the
-    // pivot chain of every 16 x 16 block (factor16_step: 16 times per block, nothing overlaps it).  MEASURED: refit 1.648 against 1.665 ms
-    // at N = 3000, 9.80 against 9.93 at N = 10^4 (profiles/r04_rsqrt_halley_ab.txt): inside the noise -- the depth of this chain is not
-    // what a pivot step waits for either.  Not the default (the factor's last bits would change for nothing).
-    const double xy = x * y;
-    const double e = __builtin_fma(-xy, y, 1.0);
-    const double t = __builtin_fma(0.375, e, 0.5);
-    return __builtin_fma(y * e, t, y);
-#endif
 }
 
 // A3 for a trailing size of NB 16-blocks: cyclic NB x NB register tile per thread (lower half only), FP64 VALU.
@@ -271,20 +254,13 @@ __device__ __forceinline__ void trailing_dispatch(double* a, int P, int nb, int 
 // memory and none on the reciprocal-square-root chain (they move the un-scaled entries; the scaling by 1/L_jj follows):
 //     a_jj            v_readlane from lane (j, j >> 2)                          (wave-uniform)
 //     a[r][j]         ds_bpermute from lane (r, j >> 2): the row's entry in column j
-//     a[j][4q + e]    ds_swizzle "lane j of my 16-row": row j's entries in my columns -- by symmetry these ARE the
+//     a[j][4q + e]    DPP row_newbcast "lane j of my 16-row": row j's entries in my columns -- by symmetry these ARE the
 //                     multipliers l_k of my columns, so no per-column broadcast is needed
 // The first version kept a row per lane (16 of 64 lanes busy) and fetched every l_k with its own v_readlane pair:
 // 240 pairs per block, 8.7 k cycles per block on the critical path of every panel.  Same arithmetic, same operation order:
 // the factor is bit-identical.  Finished columns go to the mirror position, the diagonal to dl / idl.
 template <int J>
-__device__ __forceinline__ double row_bcast16(double v) {   // value of lane J of this lane's row of 16
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_ds_swizzle(lo, (J << 5) | 0x10);
-    hi = __builtin_amdgcn_ds_swizzle(hi, (J << 5) | 0x10);
-    return __hiloint2double(hi, lo);
-}
-template <int J>
-__device__ __forceinline__ double row_bcast16_dpp(double v) {   // the same value by DPP row_newbcast: a VALU move, no trip through the LDS crossbar
+__device__ __forceinline__ double row_bcast16_dpp(double v) {   // value of lane J of this lane's row of 16 by DPP row_newbcast: a VALU move, no trip through the LDS crossbar
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(lo, lo, 0x150 + J, 0xf, 0xf, true);
     hi = __builtin_amdgcn_update_dpp(hi, hi, 0x150 + J, 0xf, 0xf, true);
@@ -296,32 +272,9 @@ __device__ __forceinline__ double lane_fetch(double v, int byte_addr) {
     hi = __builtin_amdgcn_ds_bpermute(byte_addr, hi);
     return __hiloint2double(hi, lo);
 }
-template <int J>
-__device__ __forceinline__ void factor16_step(double (&v)[4], int r, int q, double* dl, double* idl, int P, int lane, int* info,
-                                              int row0) {
-    constexpr int QJ = J >> 2, EJ = J & 3;
-    double ajj = readlane_f64(v[EJ], J + 16 * QJ);
-    const double arj = lane_fetch(v[EJ], 4 * (r + 16 * QJ));
-    double ajk[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ajk[e] = row_bcast16<J>(v[e]);
-    if (!(ajj > 0.0)) {
-        if (lane == 0) atomicCAS(info, 0, row0 + P + J + 1);
-        ajj = 1.0;
-    }
-    const double inv = fast_rsqrt(ajj);
-    const double lr = arj * inv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const double lk = ajk[e] * inv;
-        if (4 * q + e > J) v[e] -= lr * lk;
-    }
-    if (q == QJ) v[EJ] = lr;                       // column J is final: L[r][J] for r > J (rows <= J: dead entries)
-    if (lane == J + 16 * QJ) { dl[P + J] = ajj * inv; idl[P + J] = inv; }
-}
-// The same step with nothing but arithmetic and lane exchanges in it: the diagonal and its reciprocal (lane-uniform) stay in registers
-// until the block is done, a non-positive pivot is remembered and reported once at the end -- no divergent branch (two per step before:
-// `if (lane == ...)` around two LDS writes, `if (!(ajj > 0))` around the atomic) between a pivot and the next.
+// A step has nothing but arithmetic and lane exchanges in it: the diagonal and its reciprocal (lane-uniform) stay in registers
+// until the block is done, a non-positive pivot is remembered and reported once at the end -- no divergent branch between a pivot
+// and the next.
 template <int J>
 __device__ __forceinline__ void factor16_step_nb(double (&v)[4], int r, int q, double (&dj)[16], double (&ij)[16], int& bad) {
     constexpr int QJ = J >> 2, EJ = J & 3;
@@ -329,7 +282,7 @@ __device__ __forceinline__ void factor16_step_nb(double (&v)[4], int r, int q, d
     const double arj = lane_fetch(v[EJ], 4 * (r + 16 * QJ));
     double ajk[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ajk[e] = BOHIP_FACTOR16_ROWDPP ? row_bcast16_dpp<J>(v[e]) : row_bcast16<J>(v[e]);
+    for (int e = 0; e < 4; ++e) ajk[e] = row_bcast16_dpp<J>(v[e]);
     const bool ok = ajj > 0.0;
     bad = (!ok && bad == 0) ? J + 1 : bad;
     ajj = ok ? ajj : 1.0;
@@ -349,53 +302,9 @@ __device__ __forceinline__ void factor16_steps_nb(double (&v)[4], int r, int q, 
                                                   std::integer_sequence<int, Js...>) {
     (factor16_step_nb<Js>(v, r, q, dj, ij, bad), ...);
 }
-#ifndef BOHIP_FACTOR16_NOBRANCH
-#define BOHIP_FACTOR16_NOBRANCH 1
-#endif
-#ifndef BOHIP_FACTOR16_SWIZZLE
-#define BOHIP_FACTOR16_SWIZZLE 1   // 1 (default): the 64-lane form above; 0: the 16-lane DPP form below (round-4 experiment, same speed)
-#endif
-// Round 4: the same factorisation with ONE ROW PER LANE on 16 lanes and every broadcast a DPP move (row_newbcast: "lane J of my row of
-// 16 to the whole row", a VALU instruction, gfx90a+) instead of a trip through the LDS crossbar.  The 64-lane form above needs, per pivot,
-// a[r][J] from another 16-lane row (ds_bpermute) and row J's entries in the lane's columns (ds_swizzle): ~120 cycles of LDS-pipe
-// latency on the chain  update -> broadcast -> scale -> update, 16 times per block: 3.3 us per 16 x 16 block, a third of every panel of
-// the pivot chain (profiles/r03_chol_form1_chain_trace_N3000.txt).  With a whole row in the lane, l_r = a[r][J] / L_JJ needs nothing
-// from anybody, and the 15 - J multipliers l_k reach the lanes by DPP (two 32-bit moves each, issued back to back, the one the next
-// pivot needs first).  Same operands, same operations, same order per entry: the factor is bit-identical to the 64-lane form's
-// (tools/chol_ab.py: identical factor and alpha at N = 500 ... 10^4).  MEASURED: no faster -- 3.24 us per 16 x 16 block in the chain's
-// trace either way, refit 1.667 against 1.693 ms at N = 3000 (profiles/r04_factor16_dpp_ab.txt).  The broadcasts were never the chain:
-// a pivot step is readlane/DPP -> v_rsq_f64 -> two Newton steps (eight dependent FP64 operations at ~16 cycles each beside the trailing
-// update's waves on the same SIMDs) -> scale -> update, ~440 cycles whichever way the multipliers travel.  Kept as the alternative form.
-template <int J>
-__device__ __forceinline__ double row_bcast_dpp(double v) {   // value of lane J of this lane's row of 16 (DPP row_newbcast)
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + J, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + J, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int J>
-__device__ __forceinline__ void factor16_row_step(double (&v)[16], int r, double* dl, double* idl, int P, int* info, int row0) {
-    double ajj = row_bcast_dpp<J>(v[J]);                 // the pivot: lane J's diagonal entry
-    if (!(ajj > 0.0)) {
-        if (r == 0) atomicCAS(info, 0, row0 + P + J + 1);
-        ajj = 1.0;
-    }
-    const double inv = fast_rsqrt(ajj);
-    const double lr = v[J] * inv;                          // L[r][J] (rows r > J; row J itself: L_JJ)
-    // the multipliers of the columns right of J, nearest first (the next pivot needs column J + 1 only)
-#define BOHIP_F16_COL(K)                                                     \
-    if constexpr (K > J) {                                                   \
-        const double lk_ = row_bcast_dpp<K>(lr);                             \
-        v[K] -= lr * lk_;                                                    \
-    }
-    BOHIP_F16_COL(1) BOHIP_F16_COL(2) BOHIP_F16_COL(3) BOHIP_F16_COL(4) BOHIP_F16_COL(5) BOHIP_F16_COL(6) BOHIP_F16_COL(7) BOHIP_F16_COL(8)
-    BOHIP_F16_COL(9) BOHIP_F16_COL(10) BOHIP_F16_COL(11) BOHIP_F16_COL(12) BOHIP_F16_COL(13) BOHIP_F16_COL(14) BOHIP_F16_COL(15)
-#undef BOHIP_F16_COL
-    v[J] = lr;                                             // column J is final
-    if (r == J) { dl[P + J] = ajj * inv; idl[P + J] = inv; }
-}
+// (Round 4 also measured ONE ROW PER LANE on 16 lanes with every broadcast a DPP move: bit-identical and no faster,
+// profiles/r04_factor16_dpp_ab.txt -- the broadcasts were never the chain.)
 __device__ __forceinline__ void factor16(double* a, double* dl, double* idl, int P, int lane, int* info, int row0) {
-#if BOHIP_FACTOR16_SWIZZLE
     const int r = lane & 15, q = lane >> 4;
     double v[4];
 #pragma unroll
@@ -403,7 +312,6 @@ __device__ __forceinline__ void factor16(double* a, double* dl, double* idl, int
         const int k = 4 * q + e;
         v[e] = (k <= r) ? a[(P + r) * PF_LD + P + k] : a[(P + k) * PF_LD + P + r];   // lower triangle, mirrored into the upper
     }
-#if BOHIP_FACTOR16_NOBRANCH
     {
         double dj[16], ij[16];
         int bad = 0;
@@ -417,39 +325,11 @@ __device__ __forceinline__ void factor16(double* a, double* dl, double* idl, int
         if (lane < 16) { dl[P + lane] = dmine; idl[P + lane] = imine; }
         if (bad != 0 && lane == 0) atomicCAS(info, 0, row0 + P + bad);
     }
-#else
-    factor16_step<0>(v, r, q, dl, idl, P, lane, info, row0);   factor16_step<1>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<2>(v, r, q, dl, idl, P, lane, info, row0);   factor16_step<3>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<4>(v, r, q, dl, idl, P, lane, info, row0);   factor16_step<5>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<6>(v, r, q, dl, idl, P, lane, info, row0);   factor16_step<7>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<8>(v, r, q, dl, idl, P, lane, info, row0);   factor16_step<9>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<10>(v, r, q, dl, idl, P, lane, info, row0);  factor16_step<11>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<12>(v, r, q, dl, idl, P, lane, info, row0);  factor16_step<13>(v, r, q, dl, idl, P, lane, info, row0);
-    factor16_step<14>(v, r, q, dl, idl, P, lane, info, row0);  factor16_step<15>(v, r, q, dl, idl, P, lane, info, row0);
-#endif
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int k = 4 * q + e;
         if (k < r) a[(P + k) * PF_LD + P + r] = v[e];   // mirror
     }
-#else
-    if (lane >= 16) return;                                // (the caller's wave continues after the call: no barrier inside)
-    const int r = lane;
-    double v[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = (k <= r) ? a[(P + r) * PF_LD + P + k] : 0.0;   // row r of the lower triangle
-    factor16_row_step<0>(v, r, dl, idl, P, info, row0);   factor16_row_step<1>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<2>(v, r, dl, idl, P, info, row0);   factor16_row_step<3>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<4>(v, r, dl, idl, P, info, row0);   factor16_row_step<5>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<6>(v, r, dl, idl, P, info, row0);   factor16_row_step<7>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<8>(v, r, dl, idl, P, info, row0);   factor16_row_step<9>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<10>(v, r, dl, idl, P, info, row0);  factor16_row_step<11>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<12>(v, r, dl, idl, P, info, row0);  factor16_row_step<13>(v, r, dl, idl, P, info, row0);
-    factor16_row_step<14>(v, r, dl, idl, P, info, row0);  factor16_row_step<15>(v, r, dl, idl, P, info, row0);
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < r) a[(P + k) * PF_LD + P + r] = v[k];     // finished columns to the mirror position
-#endif
 }
 
 // Round 6: the same 16 x 16 factorisation with W16 = L16^-1 GROWN INSIDE it (the chain's pivot_block, kernels_chol.hip).  Until now the
@@ -532,7 +412,7 @@ __device__ __forceinline__ void factor16w(double* a, double* dl, double* idl, do
 }
 
 // B0 + B1 of the header above on an image whose strict upper triangle (mirror) holds L and whose idl[] holds 1 / L_ii:
-// W = L^-1 is built in the lower triangle and stored to Wblk (lower) and WTblk (upper).  Shared by k_potf2_inv and k_inv128.
+// W = L^-1 is built in the lower triangle and stored to Wblk (lower) and WTblk (upper).  Used by k_potf2_inv.
 template <bool SC1 = false>   // SC1: the result is read by kernels that are already running (agent-scope stores)
 __device__ __forceinline__ void inverse_phase(double* a, const double* idl, int tid, double* __restrict__ Wblk,
                                               double* __restrict__ WTblk, int64_t ldw) {
@@ -709,73 +589,17 @@ struct GemmNTParams {
     // ragged batches: tile (ti, tj64) of batch z exists iff  row_t0 + z row_ts + ti < total_t  and
     // col_t0 + z col_ts + tj64/2 < total_t  (all in 128-tiles); total_t <= 0 disables the check
     int row_t0, row_ts, col_t0, col_ts, total_t;
-    // dataflow gating (kernels_chol.hip): every workgroup waits until *wait_flag >= wait_val before it touches an operand,
-    // and each of its eight waves adds 1 to *signal when its part of the tile is in memory (a workgroup without a
-    // tile adds 8), so a consumer can wait for 8 x gridDim.x x gridDim.y.  abort: see flag_wait_ge.
-    const unsigned* wait_flag;
-    unsigned wait_val;
-    const unsigned* wait_flag2;   // optional second flag, same rule
-    unsigned wait_val2;
-    int wait_stride_ti, wait_stride_tj2;   // this workgroup waits on wait_flag[ti * stride_ti] and wait_flag2[(tj / 2) * stride_tj2]
-    int wait2_tj2_max;            // > 0: the second flag only exists for tj / 2 < this; beyond, the B rows are rows of the A range:
-    int wait2_rows;               //      wait2_rows = 1: wait on wait_flag[(tj / 2 - wait2_tj2_max) * wait_stride_ti], 0: no wait
-    unsigned* signal_rows;        // per row tile: waves of the column tiles tj < signal_rows_ntj count into signal_rows[ti * signal_rows_stride]
-    int signal_rows_ntj, signal_rows_stride;
-    int coalesced;                // store C through LDS as 16-byte pieces by all eight waves (plain stores) instead of from the MFMA layout
-    const unsigned* wait_flag3;   // optional third flag, the same for every workgroup (a whole earlier launch on another stream)
-    unsigned wait_val3;
-    unsigned* signal;
-    unsigned* signal_row0;        // the workgroups of the first row tile (ti == 0, scheduled first) also count here
-    unsigned* signal_col0;        // the workgroups of the first 128 columns (tj < 2) also count here
-    int first_row_col;            // dispatch order: first row tile, then the first 128 columns of the other rows, then the rest
-                                  // (the chain waits for exactly those tiles; the bulk of the launch follows)
-    unsigned* abort_flag;
-    unsigned long long spin_ticks;   // bound of the in-kernel wait (wall_clock64 ticks)
+    int coalesced;    // store C through LDS as 16-byte pieces by all eight waves instead of from the MFMA layout (no diag_skip / beta users with CT)
 };
 
 template <bool SWAVE = false>   // SWAVE: see gemm_tile_loop_glds3_ks (the throughput kernels below use it)
 __device__ __forceinline__ void gemm_nt_body(const GemmNTParams& p, const int bid, const int z, double* smem) {
     // klo_from_n: the contraction of column tile tj starts at 128 (tj/2) -> low tj = long jobs: issue them first
-    int ti = p.klo_from_n ? bid % p.mt : bid / p.nt64;
-    int tj = p.klo_from_n ? bid / p.mt : bid % p.nt64;
-    if (p.first_row_col && p.nt64 > 2) {
-        const int b = bid, edge = p.nt64 + 2 * (p.mt - 1);
-        if (b < p.nt64) { ti = 0; tj = b; }
-        else if (b < edge) { ti = 1 + (b - p.nt64) / 2; tj = (b - p.nt64) & 1; }
-        else { ti = 1 + (b - edge) / (p.nt64 - 2); tj = 2 + (b - edge) % (p.nt64 - 2); }
-    }
+    const int ti = p.klo_from_n ? bid % p.mt : bid / p.nt64;
+    const int tj = p.klo_from_n ? bid / p.mt : bid % p.nt64;
     const bool no_tile = (p.diag_skip && p.col0 + CTILE * (int64_t)tj >= p.row0 + (int64_t)TILE * (ti + 1)) ||
                          (p.total_t > 0 && (p.row_t0 + z * p.row_ts + ti >= p.total_t || p.col_t0 + z * p.col_ts + (tj >> 1) >= p.total_t));
-    if (no_tile) {
-        if (p.signal && threadIdx.x == 0) atomicAdd(p.signal, 8u);
-        if (p.signal_row0 && ti == 0 && threadIdx.x == 0) atomicAdd(p.signal_row0, 8u);
-        if (p.signal_col0 && tj < 2 && threadIdx.x == 0) atomicAdd(p.signal_col0, 8u);
-        if (p.signal_rows && tj < p.signal_rows_ntj && threadIdx.x == 0) atomicAdd(p.signal_rows + (int64_t)ti * p.signal_rows_stride, 8u);
-        return;
-    }
-    if (p.wait_flag || p.wait_flag3) {
-        if (threadIdx.x == 0) {
-            const unsigned long long t0 = wall_clock64();
-            for (;;) {
-                bool ok = !p.wait_flag ||
-                          __hip_atomic_load(p.wait_flag + (int64_t)ti * p.wait_stride_ti, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= p.wait_val;
-                if (ok && p.wait_flag2) {
-                    const int tj2 = tj >> 1;
-                    if (p.wait2_tj2_max > 0 && tj2 >= p.wait2_tj2_max)
-                        ok = !p.wait2_rows || __hip_atomic_load(p.wait_flag + (int64_t)(tj2 - p.wait2_tj2_max) * p.wait_stride_ti, __ATOMIC_RELAXED,
-                                                                __HIP_MEMORY_SCOPE_AGENT) >= p.wait_val;
-                    else
-                        ok = __hip_atomic_load(p.wait_flag2 + (int64_t)tj2 * p.wait_stride_tj2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= p.wait_val2;
-                }
-                if (ok && p.wait_flag3) ok = __hip_atomic_load(p.wait_flag3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= p.wait_val3;
-                if (ok) break;
-                if (p.abort_flag && __hip_atomic_load(p.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-                __builtin_amdgcn_s_sleep(4);
-                if (wall_clock64() - t0 > (p.spin_ticks ? p.spin_ticks : CH_SPIN_TICKS_DEFAULT)) { if (p.abort_flag) atomicCAS(p.abort_flag, 0u, 1u); break; }   // see flag_wait_ge (the FIRST waiter to give up names the cause)
-            }
-        }
-        __syncthreads();   // what the flag guards was written with agent-scope stores (kernels_chol.hip): no cache maintenance here
-    }
+    if (no_tile) return;
     int kb = 0, ke = p.kc;
     const int koff = z * p.kz;
     if (p.klo_from_m) kb = max(kb, ti * (TILE / KC) - koff);
@@ -794,10 +618,9 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNTParams& p, const int bi
                                          p.ldb, kb, ke, smem, acc);
     const int lane = threadIdx.x & 63, wave = SWAVE ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6), wr = wave >> 1, wc = wave & 1;
     double* C = p.C ? p.C + z * p.zC + (int64_t)ti * TILE * p.ldc + (int64_t)tj * CTILE : nullptr;
-    if ((p.signal || p.coalesced) && C && (!p.CT || (p.coalesced && !p.signal))) {
-        // A running kernel reads this tile: the stores are agent-scope (write-through).  Issued straight from the MFMA
-        // accumulator layout they are 8-byte pieces in 32-byte runs -- 15-25 us per tile, longer than the contraction.  So
-        // the tile takes a turn through LDS and leaves as 16-byte pieces, 1 KB contiguous per wave instruction, by all 8 waves.
+    if (p.coalesced && C) {
+        // Issued straight from the MFMA accumulator layout the stores are 8-byte pieces in 32-byte runs.  Here the tile takes a
+        // turn through LDS and leaves as 16-byte pieces, 1 KB contiguous per wave instruction, by all 8 waves.
         constexpr int TS = CTILE + 2;
         double* Tl = smem;   // [128][66]: the staging buffers are free (the loop ended on a barrier)
         if (wave < 4) {
@@ -820,35 +643,19 @@ __device__ __forceinline__ void gemm_nt_body(const GemmNTParams& p, const int bi
                 v.x += p.beta * old.x;
                 v.y += p.beta * old.y;
             }
-            if (!p.signal) {   // (coalesced only: nobody reads the tile before this kernel ends)
-                if (k1) *reinterpret_cast<d2*>(dst) = v;
-                else *dst = v.x;
-            } else if (k1) {
-                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(v) : "memory");
-            } else {
-                __hip_atomic_store(dst, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (k1) *reinterpret_cast<d2*>(dst) = v;
+            else *dst = v.x;
         }
-        if (!p.signal) {
-            if (p.CT) {   // the transpose from the same LDS tile: CT[c][r], 16-byte pieces along r (no diag_skip / beta users)
-                double* CTt = p.CT + z * p.zCT + (int64_t)tj * CTILE * p.ldct + (int64_t)ti * TILE;
+        if (p.CT) {   // the transpose from the same LDS tile: CT[c][r], 16-byte pieces along r (no diag_skip / beta users)
+            double* CTt = p.CT + z * p.zCT + (int64_t)tj * CTILE * p.ldct + (int64_t)ti * TILE;
 #pragma unroll
-                for (int u = 0; u < (TILE * CTILE / 2) / GEMM_THREADS_8; ++u) {
-                    const int piece = threadIdx.x + GEMM_THREADS_8 * u, c = piece >> 6, r = (piece & 63) * 2;
-                    d2 v;
-                    v.x = Tl[r * TS + c];
-                    v.y = Tl[(r + 1) * TS + c];
-                    *reinterpret_cast<d2*>(CTt + (int64_t)c * p.ldct + r) = v;
-                }
+            for (int u = 0; u < (TILE * CTILE / 2) / GEMM_THREADS_8; ++u) {
+                const int piece = threadIdx.x + GEMM_THREADS_8 * u, c = piece >> 6, r = (piece & 63) * 2;
+                d2 v;
+                v.x = Tl[r * TS + c];
+                v.y = Tl[(r + 1) * TS + c];
+                *reinterpret_cast<d2*>(CTt + (int64_t)c * p.ldct + r) = v;
             }
-            return;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // landed (a workgroup-scope fence emits no such wait)
-        if (lane == 0) {
-            atomicAdd(p.signal, 1u);
-            if (p.signal_row0 && ti == 0) atomicAdd(p.signal_row0, 1u);
-            if (p.signal_col0 && tj < 2) atomicAdd(p.signal_col0, 1u);
-            if (p.signal_rows && tj < p.signal_rows_ntj) atomicAdd(p.signal_rows + (int64_t)ti * p.signal_rows_stride, 1u);
         }
         return;
     }
@@ -877,30 +684,11 @@ __global__ __launch_bounds__(GEMM_THREADS_8, 2) void k_gemm_nt(GemmNTParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     gemm_nt_body(p, (int)blockIdx.x, (int)blockIdx.y, smem);
 }
-// Two launches in one grid: blocks [0, na) run `a`, the rest run `b`.  cholesky_dataflow2 puts block k's update and block k+1's
-// row solve into one launch: the solve's workgroups wait (in-kernel) for counters the update's first workgroups raise -- those
-// have lower block numbers, are dispatched first and wait for nothing in this launch -- so both are resident when the inverse
-// of the next diagonal block arrives, and ONE in-order stream carries every flagged launch.
-// (these two are compiled for FOUR waves per SIMD = 128 VGPRs = two workgroups per CU: throughput launches.  k_gemm_nt itself
-// stays at 129 VGPRs / one workgroup per CU, which suits the small launches beside the first dataflow form's chain better.)
+// The same compiled for FOUR waves per SIMD = 128 VGPRs = two workgroups per CU: throughput launches (the big levels of the triangular
+// inverse).  k_gemm_nt itself stays at one workgroup per CU, which suits the small launches of the launch chain better.
 __global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_gemm_nt_hi(GemmNTParams p) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     gemm_nt_body<true>(p, (int)blockIdx.x, (int)blockIdx.y, smem);
-}
-__global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_gemm_nt_pair(GemmNTParams a, GemmNTParams b, int na) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    if ((int)blockIdx.x < na) gemm_nt_body<true>(a, (int)blockIdx.x, 0, smem);
-    else gemm_nt_body<true>(b, (int)blockIdx.x - na, 0, smem);
-}
-// the same with four parameter sets: blocks [0, n0) run p0, [n0, n0+n1) p1, [.., +n2) p2, the rest p3
-__global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_gemm_nt_quad(GemmNTParams p0, GemmNTParams p1, GemmNTParams p2, GemmNTParams p3,
-                                                                 int n0, int n1, int n2) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int b = blockIdx.x;
-    if (b < n0) gemm_nt_body<true>(p0, b, 0, smem);
-    else if (b < n0 + n1) gemm_nt_body<true>(p1, b - n0, 0, smem);
-    else if (b < n0 + n1 + n2) gemm_nt_body<true>(p2, b - n0 - n1, 0, smem);
-    else gemm_nt_body<true>(p3, b - n0 - n1 - n2, 0, smem);
 }
 
 // dst[i][j] = src[i][j] on every 128-tile strictly below the diagonal tiles (the factorisation parks the solved

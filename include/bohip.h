@@ -254,7 +254,7 @@ int bohip_gp_get_alpha(bohip_gp *gp, double *alpha);
 #define BOHIP_INFO_CAPACITY 1     /* current observation capacity                                */
 #define BOHIP_INFO_REFITS 2       /* number of full refits so far                                */
 #define BOHIP_INFO_APPENDS 3      /* number of incremental factor extensions so far              */
-#define BOHIP_INFO_CHOL_FORM 4    /* factorisation form of the last refit: 0 launch chain, 1-3 dataflow forms, 4 executor */
+#define BOHIP_INFO_CHOL_FORM 4    /* factorisation form of the last refit: 0 launch chain, 4 executor (1-3: retired dataflow forms, never reported) */
 #define BOHIP_INFO_CHOL_FALLBACKS 5   /* refits of this handle that timed out on a dependency and were redone launch-chained */
 #define BOHIP_INFO_CHOL_ABORT_TILES 6 /* row tiles of the last factorisation that timed out (0: never)  */
 #define BOHIP_INFO_JITTER_STEPS 7 /* jitter tries the last refit needed (0: none; see bohip_gp_set_jitter) */

@@ -2,7 +2,7 @@
 
 The task records are built on the HOST (a pure function of addresses, ld and T) and executed on the device by k_chol_exec.
 Here the real builder is called through its test hook with fake base addresses, and the records are replayed with NumPy
-against a model of the persistent chain kernel (k_chol_chain in its mode2 = 100 view, with its solve_follower workgroup that
+against a model of the persistent chain kernel (k_chol_chain, with its solve_follower workgroup that
 delivers S(k+3, k)):
 
   * every queue is consumed strictly in order, a task only when all of its dependency counters have reached their value

@@ -75,8 +75,8 @@ def test_forms_are_reported_and_strict_mode_errors_instead_of_falling_back():
     assert got["1500"]["forms"] == [4] and got["4300"]["forms"] == [4]     # the executor with its inverse queues (the default from 4 row tiles on)
     assert got["1500"]["fallbacks"] == 0 and got["4300"]["abort_tiles"] == 0
     ref = got
-    got, _ = run(((1500, 3), (4300, 4)), 0, BOHIP_CHOL_INV_G="0")           # without them: the first dataflow form below 32 row tiles
-    assert got["1500"]["forms"] == [1] and got["4300"]["forms"] == [4]
+    got, _ = run(((1500, 3), (4300, 4)), 0, BOHIP_CHOL_INV_G="0")           # without them: still the executor (from 4 row tiles on)
+    assert got["1500"]["forms"] == [4] and got["4300"]["forms"] == [4]
     for N in ("1500", "4300"):
         same_factor(got[N], ref[N])
     o = subprocess.run([sys.executable, "-c", CODE % (ROOT, "((1500, 3),)", 0)], env=dict(os.environ, BOHIP_CHOL_SPIN_US="1", BOHIP_CHOL_DF_STRICT="1"),

@@ -991,10 +991,10 @@ def test_device_ascent_nlopt_stop_criteria(bohip, N):
 
 
 def test_dataflow_cholesky_matches_the_launch_chained_one(bohip, orc):
-    """csrc/kernels_chol.hip, csrc/kernels_exec.hip: the dataflow forms of the factorisation (persistent chain workgroups +
-    flags) against the launch-chained one -- form 1 (panel followers, T <= 46 by default), form 2 (flagged row solves + K = 128
-    window updates), form 2 with left-looking window updates, and the executor form (one persistent kernel pulling tile tasks;
-    the default for 47..96 row tiles), each forced at sizes the test can afford.
+    """csrc/kernels_chol.hip, csrc/kernels_exec.hip: the dataflow form of the factorisation (the persistent chain kernel + one
+    persistent executor kernel pulling tile tasks; the default for 2..96 row tiles) against the launch-chained one, with the
+    inverse queues in each of their forms and without them.  Sizes: T = 2 (no factorisation task, the inverse's rows only), T = 4
+    (the first T with a factorisation task, and the first the executor takes without the inverse queues), T = 8 and T = 24.
     Same factor to rounding, same alpha and posterior; BOHIP_CHOL_DF_STRICT turns a timed-out flag into an error instead of the
     silent fall-back.  Subprocesses because the switches are read once per process."""
     import json
@@ -1009,7 +1009,7 @@ import json, sys
 sys.path.insert(0, %r)
 import numpy as np, bohip
 out = {}
-for N, d in ((130, 2), (1000, 4), (3000, 8)):
+for N, d in ((130, 2), (500, 3), (1000, 4), (3000, 8)):
     rng = np.random.default_rng(N)
     X = rng.random((N, d)); y = np.sin(3 * X).sum(1) + 0.1 * rng.standard_normal(N)
     m = bohip.ElasticGPE(d, kernel=bohip.SEArd(np.full(d, -0.6), 0.1), logNoise=-2.0, capacity=N)
@@ -1022,17 +1022,14 @@ print("RESULT" + json.dumps(out))
 ''' % ROOT
     variants = {
         "chained": dict(BOHIP_CHOL_DATAFLOW="0"),
-        "form1": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_DF2_MIN="999", BOHIP_CHOL_EXEC="0"),
-        "form2": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_DF2_MIN="4", BOHIP_CHOL_DF2_LL="0", BOHIP_CHOL_EXEC="0"),
-        "form2-left-looking": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_DF2_MIN="4", BOHIP_CHOL_DF2_LL="1", BOHIP_CHOL_EXEC="0"),
-        # csrc/kernels_exec.hip: the chain + one persistent task-executor kernel (the default from 47 row tiles on)
-        "executor": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_EXEC="1", BOHIP_CHOL_EXEC_MIN="4"),
+        # csrc/kernels_exec.hip: the chain + one persistent task-executor kernel
+        "executor": dict(BOHIP_CHOL_DATAFLOW="2"),
         # the same without the inverse queues (W = L^-1 level by level after the factorisation), and with short pieces
-        "executor-inverse-after": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_EXEC="1", BOHIP_CHOL_EXEC_MIN="4", BOHIP_CHOL_INV_G="0"),
-        "executor-inverse-pieces-of-2": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_EXEC="1", BOHIP_CHOL_EXEC_MIN="4", BOHIP_CHOL_INV_G="2"),
+        "executor-inverse-after": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_INV_G="0"),
+        "executor-inverse-pieces-of-2": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_INV_G="2"),
         # the inverse queues in their GROUP form (the default from 28 row tiles on) forced at every size, groups of 8 and of 3 blocks
-        "executor-inverse-groups": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_EXEC="1", BOHIP_CHOL_EXEC_MIN="4", BOHIP_CHOL_INV_GRP_MIN="0"),
-        "executor-inverse-groups-of-3": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_EXEC="1", BOHIP_CHOL_EXEC_MIN="4", BOHIP_CHOL_INV_GRP_MIN="0",
+        "executor-inverse-groups": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_INV_GRP_MIN="0"),
+        "executor-inverse-groups-of-3": dict(BOHIP_CHOL_DATAFLOW="2", BOHIP_CHOL_INV_GRP_MIN="0",
                                              BOHIP_CHOL_INV_G="3"),
     }
     res = {}

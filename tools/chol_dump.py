@@ -1,4 +1,4 @@
-"""Refit N observations `reps` times with the factorisation alone (form 1 below 32 row tiles) and let the library dump the flag area on a
+"""Refit N observations `reps` times with the factorisation alone (the executor without its inverse queues) and let the library dump the flag area on a
 time-out (BOHIP_CHOL_DF_DUMP=1).  usage: BOHIP_CHOL_DF_DUMP=1 python tools/chol_dump.py N reps"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
