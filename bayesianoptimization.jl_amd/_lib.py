@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -139,6 +139,13 @@ FIT_SIGNATURES = {
     "bohip_gp_mll_grad_batch": (C.c_int, [_gp, C.c_int64, _dp, _dp, _dp, _i64p]),
 }
 
+# every symbol include/bohip_qei.h declares (greedy Monte-Carlo q-EI over joint draws that stay on the device)
+QEI_SIGNATURES = {
+    "bohip_gp_qei_batch": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_int, C.c_double, C.c_int64, _i64p, _dp,
+                                    _dp, _dp, _ip]),
+    "bohip_gp_qei_select": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_int64, _i64p, _dp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -193,7 +200,8 @@ def load():
         raise BohipError(E_NODEVICE, f"{LIB_PATH} not built (run __graft_entry__.build()); there is no CPU fallback")
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
+                              + list(QEI_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

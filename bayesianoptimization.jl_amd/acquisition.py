@@ -552,17 +552,27 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     return maxf, maxx
 
 
-_BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau"}
+_BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features"}
 _BATCH_FANTASIES = ("believer", "liar_max", "liar_min", "liar_mean")
+_BATCH_METHODS = ("fantasy", "qei")
 
 
 def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None, setparams=True):
     """q points to evaluate in parallel -- an extension: the reference's iteration is one acquire_max and `repetitions`
-    evaluations of ONE point (src/BayesianOptimization.jl:185-196).  Greedy arg-max over a candidate set under the posterior
-    conditioned on the fantasised observations of the earlier picks (model.select_batch; the model itself is not changed).
-    options: "candidates" Latin-hypercube points (default 4096) or an explicit d x R "xs"; "fantasy" in {"believer" (y_f = mu),
-    "liar_max", "liar_min", "liar_mean" (a constant taken from model.y)}; "raise_tau" (EI / PI: the incumbent follows the
-    fantasies).  Returns (values[q'], X d x q') with q' <= q: picks that could not win (no finite score left) are dropped."""
+    evaluations of ONE point (src/BayesianOptimization.jl:185-196).  options: "candidates" Latin-hypercube points (default 4096)
+    or an explicit d x R "xs"; "method":
+      "fantasy" (default)  greedy arg-max over the candidates under the posterior conditioned on the fantasised observations of
+          the earlier picks (model.select_batch; the model itself is not changed).  "fantasy" in {"believer" (y_f = mu),
+          "liar_max", "liar_min", "liar_mean" (a constant taken from model.y)}; "raise_tau" (EI / PI: the incumbent follows the
+          fantasies).  Every pick is scored by a one-point acquisition.
+      "qei"  the batch is scored as a batch: greedy Monte-Carlo q-EI, qEI(B) = E[max(max_{j in B} f_j - tau, 0)], over "draws"
+          (default 256) JOINT posterior draws that stay on the device (model.qei_batch; seed from `rng`).  The acquisition must
+          be ExpectedImprovement, and only its tau (after setparams_) is used: with q = 1 the value estimates the TEXTBOOK EI,
+          Delta Phi(z) + sigma phi(z), whereas the reference's ExpectedImprovement functor computes Delta Phi(z) + phi(z).
+          "pathwise": True takes the draws from posterior sample paths instead (model.draw_paths with "features" = M random
+          features, default 2048, evaluated over the candidates, then model.qei_select): no R x R factorisation, so "candidates"
+          may exceed one chunk.  The values returned are the picks' marginal gains; their sum is the batch's q-EI estimate.
+    Returns (values[q'], X d x q') with q' <= q: picks that could not win (no finite score / no gain left) are dropped."""
     lb = np.asarray(lowerbounds, dtype=np.float64)
     ub = np.asarray(upperbounds, dtype=np.float64)
     opts = dict(options or {})
@@ -574,13 +584,37 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
         raise ValueError(f"batch size q = {q} < 1")
     if lb.size != ub.size:
         raise ValueError("length of lowerbounds does not match length of upperbounds")
+    method = opts.get("method", "fantasy")
+    if method not in _BATCH_METHODS:
+        raise ValueError(f"batch method must be one of {_BATCH_METHODS}, got {method!r}")
+    qei = method == "qei"
+    if qei:
+        if "fantasy" in opts or "raise_tau" in opts:
+            raise ValueError("batch options 'fantasy' and 'raise_tau' belong to method 'fantasy': q-EI conditions on no fantasy, "
+                             "its draws are joint")
+        if not isinstance(a, ExpectedImprovement):
+            raise ValueError(f"batch method 'qei' is the batch form of expected improvement and takes its incumbent tau from an "
+                             f"ExpectedImprovement acquisition, got {type(a).__name__}")
+        pathwise = bool(opts.get("pathwise", False))
+        if not pathwise and "features" in opts:
+            raise ValueError("batch option 'features' needs 'pathwise': True")
+        draws = int(opts.get("draws", 256))
+        if draws < 1:
+            raise ValueError(f"options['draws'] = {draws} < 1")
+        need = ("draw_paths", "qei_select") if pathwise else ("qei_batch",)
+    else:
+        for k in ("draws", "pathwise", "features"):
+            if k in opts:
+                raise ValueError(f"batch option {k!r} needs 'method': 'qei'")
+        need = ("select_batch",)
     fantasy = opts.get("fantasy", "believer")
     if fantasy not in _BATCH_FANTASIES:
         raise ValueError(f"fantasy must be one of {_BATCH_FANTASIES}, got {fantasy!r}")
     if isinstance(a, ThompsonSamplingSimple):
         raise ValueError("acquire_batch needs a deterministic acquisition (ThompsonSamplingSimple draws its own batch: model.thompson)")
-    if not hasattr(model, "select_batch"):
-        raise NotImplementedError(f"{type(model).__name__} has no select_batch")
+    for name in need:
+        if not hasattr(model, name):
+            raise NotImplementedError(f"{type(model).__name__} has no {name}")
     if "xs" in opts and opts["xs"] is not None:
         xs = np.asarray(opts["xs"], dtype=np.float64)
         if xs.ndim != 2 or xs.shape[0] != lb.size:
@@ -596,6 +630,19 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
         raise RuntimeError("acquire_batch on an empty model")
     if setparams:
         setparams_(a, model)
+    if qei:
+        seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
+        if pathwise:
+            with model.draw_paths(draws, int(opts.get("features", 2048)), seed) as paths:
+                F, _, _ = paths.eval(xs)
+            idx, val = model.qei_select(F, a.tau, q)
+        else:
+            res = model.qei_batch(xs, q, draws, seed, tau=a.tau)
+            idx, val = res.idx, res.gain
+        keep = idx >= 0
+        if not keep.all():
+            warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a gain above zero")
+        return val[keep], np.asfortranarray(xs[:, idx[keep]])
     y = np.asarray(model.y)
     fv = {"believer": "believer", "liar_max": float(y.max()), "liar_min": float(y.min()), "liar_mean": float(y.mean())}[fantasy]
     idx, val, _, _ = model.select_batch(a.acq_id, a.params(), xs, q, fantasy=fv, raise_tau=bool(opts.get("raise_tau", False)))

@@ -201,7 +201,9 @@ class BOpt:
                  maxiterations=10 ** 4, maxduration=math.inf, acquisitionoptions=None, repetitions=1,
                  verbosity=Progress, initializer_iterations=None, initializer=None, rng=None, batchsize=1, batchoptions=None):
         # batchsize > 1 (an extension, the reference evaluates one point per iteration): an iteration proposes `batchsize` points
-        # with acquire_batch(..., batchoptions) and appends all their evaluations in ONE model update
+        # with acquire_batch(..., batchoptions) and appends all their evaluations in ONE model update.  batchoptions["method"]:
+        # "fantasy" (default; Kriging believer / constant liar) or "qei" (ExpectedImprovement only: greedy Monte-Carlo q-EI over
+        # joint posterior draws on the device)
         now = time.time()
         lowerbounds = np.asarray(lowerbounds, dtype=np.float64)
         upperbounds = np.asarray(upperbounds, dtype=np.float64)

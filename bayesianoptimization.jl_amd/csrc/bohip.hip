@@ -17,12 +17,14 @@
 #include "../../include/bohip.h"
 #include "../../include/bohip_paths.h"
 #include "../../include/bohip_fit.h"
+#include "../../include/bohip_qei.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
 #include "kernels_batch.hip"   // (after the scoring kernels: shares their functors and arg-max order)
 #include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
+#include "kernels_qei.hip"     // (after the scoring kernels: their arg-max order)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_ascent.hip"
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
@@ -179,6 +181,9 @@ struct bohip_gp {
     Best* sj_part = nullptr;
     int64_t sj_cap = 0;           // rows (a multiple of 128) the workspace holds; its leading dimension is sj_cap + 16
     size_t sjF_cap = 0, sj_part_cap = 0;
+    // greedy q-EI over the resident draws (bohip_gp_qei_batch / _qei_select): ONE block [m | partials | records | gain | idx | words]
+    char* qei_ws = nullptr;
+    size_t qei_bytes = 0;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -2386,6 +2391,7 @@ void bohip_gp_destroy(bohip_gp* g) {
         if (*p) hipFree(*p);
     if (g->sj_info) hipFree(g->sj_info);
     if (g->sj_part) hipFree(g->sj_part);
+    if (g->qei_ws) hipFree(g->qei_ws);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -2816,6 +2822,17 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
 }
 
 // ---- joint posterior draws over a candidate set (kernels_sample.hip; reference myrand(model, X::Matrix), src/models/gp.jl:7) ----
+// the S x R draws (also the matrix bohip_gp_qei_select uploads)
+static int ensure_sample_matrix(bohip_gp* g, size_t fneed) {
+    if (g->sjF_cap < fneed) {
+        if (g->sjF) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sjF)); g->sjF = nullptr; }
+        const size_t cap = std::max(fneed, g->sjF_cap + g->sjF_cap / 2);
+        g->sjF_cap = 0;
+        HIPCHK(hipMalloc(&g->sjF, cap * 8));
+        g->sjF_cap = cap;
+    }
+    return 0;
+}
 static int ensure_sample(bohip_gp* g, int64_t Rp, int64_t R, int64_t S, bool want_samples, size_t part_recs) {
     if (g->sj_cap < Rp) {
         HIPCHK(hipStreamSynchronize(g->stream));
@@ -2837,14 +2854,7 @@ static int ensure_sample(bohip_gp* g, int64_t Rp, int64_t R, int64_t S, bool wan
     }
     if (!g->sj_scal) HIPCHK(hipMalloc(&g->sj_scal, 8));
     if (!g->sj_info) HIPCHK(hipMalloc(&g->sj_info, sizeof(int)));
-    const size_t fneed = want_samples ? (size_t)S * R : 0;
-    if (g->sjF_cap < fneed) {
-        if (g->sjF) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sjF)); g->sjF = nullptr; }
-        const size_t cap = std::max(fneed, g->sjF_cap + g->sjF_cap / 2);
-        g->sjF_cap = 0;
-        HIPCHK(hipMalloc(&g->sjF, cap * 8));
-        g->sjF_cap = cap;
-    }
+    CHK(ensure_sample_matrix(g, want_samples ? (size_t)S * R : 0));
     if (g->sj_part_cap < part_recs) {
         if (g->sj_part) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sj_part)); g->sj_part = nullptr; }
         const size_t cap = std::max(part_recs, g->sj_part_cap + g->sj_part_cap / 2);
@@ -2861,17 +2871,23 @@ static int ensure_sample(bohip_gp* g, int64_t Rp, int64_t R, int64_t S, bool wan
     return 0;
 }
 
-int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel, int max_tries,
-                          double* mu, double* chol, double* samples, bohip_best* best, double* jitter_used, int* tries_used) {
-    if (!g || !Xs || R < 1 || S < 1) return fail(BOHIP_E_ARG, "sample_joint: bad arguments (R and S must be at least 1)");
-    if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return fail(BOHIP_E_ARG, "sample_joint: jitter_rel must be finite and not negative");
-    if (max_tries < 0) return fail(BOHIP_E_ARG, "sample_joint: max_tries must not be negative");
-    CHK(posterior_vv(g, Xs, R, "sample_joint"));
+// The draw itself, shared by bohip_gp_sample_joint and bohip_gp_qei_batch (`who` names the caller in messages).  keepF: the
+// draw kernels store the S x R matrix in g->sjF.  `post` enqueues what the caller wants behind the draw kernels of EVERY try --
+// before the copies and the try's one synchronisation -- so a call that needs no jitter synchronises once.
+extern "C++" {
+template <class Post>
+static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel,
+                             int max_tries, bool keepF, double* mu, double* chol, double* samples, bohip_best* best,
+                             double* jitter_used, int* tries_used, Post&& post) {
+    const std::string pre = std::string(who) + ": ";
+    if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return fail(BOHIP_E_ARG, pre + "jitter_rel must be finite and not negative");
+    if (max_tries < 0) return fail(BOHIP_E_ARG, pre + "max_tries must not be negative");
+    CHK(posterior_vv(g, Xs, R, who));
     const int64_t Rp = round_up(R, TILE);
     const int CT = (int)(Rp / TILE);
     const bool mfma = S >= g_sample_mfma_min;
     const int ntiles = (int)((R + (mfma ? SM_ROWS : SROWS) - 1) / (mfma ? SM_ROWS : SROWS));
-    CHK(ensure_sample(g, Rp, R, S, samples != nullptr, (size_t)S * ntiles));
+    CHK(ensure_sample(g, Rp, R, S, keepF, (size_t)S * ntiles));
     const int64_t ld = g->sj_cap + 16;
     const FactorWs ws{g->sjL, g->sjS, g->sjW, g->sjWT, ld, TILE, (int64_t)TILE * TILE, g->sj_info};
     const KernelHyper hp = make_hyper(g);
@@ -2905,7 +2921,7 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
         CHK(factor_launch_chain(g, ws, CT));
         t_end(g);
         t_begin(g, "sample_draw");
-        double* const dF = samples ? g->sjF : nullptr;
+        double* const dF = keepF ? g->sjF : nullptr;
         if (mfma) {
             hipLaunchKernelGGL(k_sample_mfma, dim3((unsigned)ntiles, (unsigned)((S + SM_DRAWS - 1) / SM_DRAWS)), dim3(256), 0, g->stream,
                                ws.L, ld, R, S, seed, g->dmu, dF, g->sj_part, ntiles);
@@ -2919,6 +2935,7 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
         hipLaunchKernelGGL(k_sample_best, dim3((unsigned)S), dim3(64), 0, g->stream, g->sj_part, ntiles, g->dthompson);
         HIPCHK(hipGetLastError());
         t_end(g);
+        CHK(post());
         // everything the caller asked for is copied behind the kernels, so a call that needs no jitter synchronises once
         int info = 0;
         double scale = 0.0;
@@ -2938,7 +2955,7 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
         if (tries >= max_tries || !(next > jit)) {
             g->pivot = info;
             t_collect(g);
-            return fail(BOHIP_E_NOTPD, "sample_joint: posterior covariance not positive definite at pivot " + std::to_string(info) +
+            return fail(BOHIP_E_NOTPD, pre + "posterior covariance not positive definite at pivot " + std::to_string(info) +
                                            " (jitter " + std::to_string(jit) + " after " + std::to_string(tries) + " tries)");
         }
         jit = next;
@@ -2946,6 +2963,105 @@ int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, u
     }
     if (jitter_used) *jitter_used = jit;
     if (tries_used) *tries_used = tries;
+    t_collect(g);
+    return 0;
+}
+}   // extern "C++"
+
+int bohip_gp_sample_joint(bohip_gp* g, const double* Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel, int max_tries,
+                          double* mu, double* chol, double* samples, bohip_best* best, double* jitter_used, int* tries_used) {
+    if (!g || !Xs || R < 1 || S < 1) return fail(BOHIP_E_ARG, "sample_joint: bad arguments (R and S must be at least 1)");
+    return sample_joint_core(g, "sample_joint", Xs, R, S, seed, jitter_rel, max_tries, samples != nullptr, mu, chol, samples, best,
+                             jitter_used, tries_used, [] { return 0; });
+}
+
+// ---- greedy Monte-Carlo q-EI over the resident draws (kernels_qei.hip, include/bohip_qei.h) ------------------------
+static constexpr size_t QEI_MAX_BYTES = (size_t)8 << 30;   // the S x R matrix plus the partials
+static constexpr int64_t QEI_GRID_S = (int64_t)QEI_B * 65535;   // grid.y holds the draw blocks
+static int64_t qei_max_draws(int64_t R) {
+    // S R + ceil(S / 32) R doubles <= 8 GiB  <=  S (1 + 1/32) R + R
+    const double per = 8.0 * (double)R;
+    const int64_t s = (int64_t)std::floor(((double)QEI_MAX_BYTES - per) / (per * (1.0 + 1.0 / QEI_B)));
+    return std::max<int64_t>(0, std::min(s, QEI_GRID_S));
+}
+static int qei_check(const char* who, int64_t R, int64_t S, double tau, int64_t q, const void* idx, const void* gain) {
+    const std::string pre = std::string(who) + ": ";
+    if (!idx || !gain) return fail(BOHIP_E_ARG, pre + "null argument");
+    if (R < 1 || S < 1 || q < 1) return fail(BOHIP_E_ARG, pre + "R, S and q must be at least 1");
+    if (q > R) return fail(BOHIP_E_ARG, pre + "q exceeds the number of candidates R");
+    if (!std::isfinite(tau)) return fail(BOHIP_E_ARG, pre + "tau must be finite");
+    return 0;
+}
+static int qei_check_size(const char* who, int64_t R, int64_t S) {
+    if (S > qei_max_draws(R))
+        return fail(BOHIP_E_UNSUPPORTED, std::string(who) + ": S x R draws and their partial sums exceed 8 GiB (or 65535 blocks of draws); the "
+                                             "largest S at R = " + std::to_string(R) + " is " + std::to_string(qei_max_draws(R)));
+    return 0;
+}
+static int ensure_qei(bohip_gp* g, int64_t R, int64_t S, int64_t q, QeiWs* w) {
+    const size_t NB = (size_t)((S + QEI_B - 1) / QEI_B), NT = (size_t)((R + QEI_PICK - 1) / QEI_PICK);
+    const size_t o_part = (size_t)S * 8, o_tile = o_part + NB * (size_t)R * 8, o_gain = o_tile + NT * sizeof(Best),
+                 o_idx = o_gain + (size_t)q * 8, o_words = o_idx + (size_t)q * 8, need = o_words + 16;
+    if (g->qei_bytes < need) {
+        if (g->qei_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->qei_ws)); g->qei_ws = nullptr; }
+        const size_t cap = std::max(need, g->qei_bytes + g->qei_bytes / 2);
+        g->qei_bytes = 0;
+        HIPCHK(hipMalloc(&g->qei_ws, cap));
+        g->qei_bytes = cap;
+    }
+    char* b = g->qei_ws;
+    w->m = reinterpret_cast<double*>(b);
+    w->part = reinterpret_cast<double*>(b + o_part);
+    w->tile = reinterpret_cast<Best*>(b + o_tile);
+    w->gain = reinterpret_cast<double*>(b + o_gain);
+    w->idx = reinterpret_cast<long long*>(b + o_idx);
+    w->done = reinterpret_cast<unsigned*>(b + o_words);
+    w->arrive = w->done + 1;
+    return 0;
+}
+// the q rounds over g->sjF, back to back on the handle's stream, and the two small copies behind them (no synchronisation)
+static int qei_rounds(bohip_gp* g, const QeiWs& w, int64_t R, int64_t S, double tau, int64_t q, int64_t* idx, double* gain) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "idx crosses as int64_t");
+    t_begin(g, "qei_select");
+    hipLaunchKernelGGL(k_qei_init, dim3((unsigned)((std::max(S, q) + 255) / 256)), dim3(256), 0, g->stream, w, S, tau, q);
+    const dim3 ggrid((unsigned)((R + QEI_COLS - 1) / QEI_COLS), (unsigned)((S + QEI_B - 1) / QEI_B));
+    const dim3 pgrid((unsigned)((R + QEI_PICK - 1) / QEI_PICK));
+    for (int64_t k = 0; k < q; ++k) {
+        hipLaunchKernelGGL(k_qei_gain, ggrid, dim3(QEI_COLS), 0, g->stream, g->sjF, R, S, w);
+        hipLaunchKernelGGL(k_qei_pick, pgrid, dim3(QEI_PICK), 0, g->stream, g->sjF, R, S, k, w);
+    }
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    HIPCHK(hipMemcpyAsync(idx, w.idx, (size_t)q * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(gain, w.gain, (size_t)q * 8, hipMemcpyDeviceToHost, g->stream));
+    return 0;
+}
+
+int bohip_gp_qei_batch(bohip_gp* g, const double* Xs, int64_t R, int64_t S, uint64_t seed, double jitter_rel, int max_tries, double tau,
+                       int64_t q, int64_t* idx, double* gain, double* samples, double* jitter_used, int* tries_used) {
+    if (!g || !Xs) return fail(BOHIP_E_ARG, "qei_batch: null argument");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");   // (first: the default tau, max y, does not exist then)
+    CHK(qei_check("qei_batch", R, S, tau, q, idx, gain));
+    CHK(qei_check_size("qei_batch", R, S));
+    HIPCHK(hipSetDevice(g->device));
+    QeiWs w{};
+    CHK(ensure_qei(g, R, S, q, &w));
+    return sample_joint_core(g, "qei_batch", Xs, R, S, seed, jitter_rel, max_tries, true, nullptr, nullptr, samples, nullptr, jitter_used,
+                             tries_used, [&] { return qei_rounds(g, w, R, S, tau, q, idx, gain); });
+}
+
+int bohip_gp_qei_select(bohip_gp* g, const double* samples, int64_t S, int64_t R, double tau, int64_t q, int64_t* idx, double* gain) {
+    if (!g || !samples) return fail(BOHIP_E_ARG, "qei_select: null argument");
+    CHK(qei_check("qei_select", R, S, tau, q, idx, gain));
+    CHK(qei_check_size("qei_select", R, S));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    QeiWs w{};
+    CHK(ensure_qei(g, R, S, q, &w));
+    CHK(ensure_sample_matrix(g, (size_t)S * R));
+    HIPCHK(hipMemcpyAsync(g->sjF, samples, (size_t)S * R * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(qei_rounds(g, w, R, S, tau, q, idx, gain));
+    HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;
 }

@@ -382,6 +382,21 @@ class ElasticGPE:
         the maximiser.  Only what is asked for crosses to the host.  Returns a JointSample."""
         return _sample_joint(self._lib, self._h, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
 
+    def qei_batch(self, xs, q, S=256, seed=0, tau=None, jitter=1e-12, max_tries=40, want_samples=False):
+        """Greedy Monte-Carlo q-EI batch over the columns of xs (bohip_gp_qei_batch, include/bohip_qei.h; an extension, as
+        select_batch is): sample_joint's S draws for the same (xs, S, seed, jitter rule) stay on the device and q rounds pick the
+        candidate with the largest sample-average gain E[max(max_B f - tau, 0)] over the batch so far.  tau defaults to maxy.
+        With q = 1 this estimates the TEXTBOOK EI (Delta Phi(z) + sigma phi(z)), not the reference's ExpectedImprovement functor
+        (Delta Phi(z) + phi(z)).  The model is not changed.  Returns a QEIBatch; idx = -1, gain = 0 where nothing could win."""
+        if tau is None:
+            tau = maxy(self)
+        return _qei_batch(self._lib, self._h, _cols(xs, self.dim), q, S, seed, tau, jitter, max_tries, want_samples)
+
+    def qei_select(self, samples, tau, q):
+        """The selection of qei_batch alone on the caller's S x R sample matrix (bohip_gp_qei_select): the model supplies the
+        device and the stream only.  Returns (idx[q] int64, gain[q])."""
+        return _qei_select(self._lib, self._h, samples, tau, q)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """S posterior SAMPLE PATHS (bohip_gp_paths_draw): draws that are functions, f_s(x) = beta + sum_m w_sm phi_m(x) +
         sum_j u_sj k(x, X_j) with M random features for the prior term and the exact data term (pathwise conditioning).  The result
@@ -472,6 +487,42 @@ def _sample_joint(lib, handle, xs, S, seed, jitter, max_tries, want_samples, wan
     vals = np.array([out[i].val for i in range(S)])
     idx = np.array([out[i].idx for i in range(S)], dtype=np.int64)
     return JointSample(samples, vals, idx, mu, jit.value, tries.value, factor)
+
+
+class QEIBatch:
+    """Result of qei_batch: idx[q] (int64, -1 where nothing could win), gain[q] (the sample-average gain of every pick; their sum is
+    the q-EI estimate of the batch), jitter / tries (as JointSample), samples (S x R, or None)."""
+    __slots__ = ("idx", "gain", "jitter", "tries", "samples")
+
+    def __init__(self, idx, gain, jitter, tries, samples):
+        self.idx, self.gain, self.jitter, self.tries, self.samples = idx, gain, jitter, tries, samples
+
+    def __iter__(self):
+        return iter((self.idx, self.gain, self.jitter, self.tries, self.samples))
+
+
+def _qei_batch(lib, handle, xs, q, S, seed, tau, jitter, max_tries, want_samples):
+    R, S, q = xs.shape[1], int(S), int(q)
+    idx = np.full(max(q, 1), -1, dtype=np.int64)
+    gain = np.zeros(max(q, 1))
+    samples = np.empty((S, R)) if want_samples and S > 0 else None
+    jit, tries = C.c_double(0.0), C.c_int(0)
+    check(lib.bohip_gp_qei_batch(handle, _ptr(xs), R, S, int(seed), float(jitter), int(max_tries), float(tau), q,
+                                 idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(gain),
+                                 _ptr(samples) if samples is not None else None, C.byref(jit), C.byref(tries)))
+    return QEIBatch(idx, gain, jit.value, tries.value, samples)
+
+
+def _qei_select(lib, handle, samples, tau, q):
+    F = np.ascontiguousarray(np.asarray(samples, dtype=np.float64))
+    if F.ndim != 2:
+        raise ValueError(f"samples must be S x R (one draw per row), got shape {F.shape}")
+    q = int(q)
+    idx = np.full(max(q, 1), -1, dtype=np.int64)
+    gain = np.zeros(max(q, 1))
+    check(lib.bohip_gp_qei_select(handle, _ptr(F), F.shape[0], F.shape[1], float(tau), q,
+                                  idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(gain)))
+    return idx, gain
 
 
 class PosteriorPaths:

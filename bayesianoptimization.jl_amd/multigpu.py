@@ -178,6 +178,20 @@ class MultiGPE:
         g = self._lib.bohip_mgp_handle(self._h, 0)
         return _sample_joint(self._lib, g, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
 
+    def qei_batch(self, xs, q, S=256, seed=0, tau=None, jitter=1e-12, max_tries=40, want_samples=False):
+        """ElasticGPE.qei_batch (bohip_gp_qei_batch) on the FIRST replica, as sample_joint."""
+        from .model import _qei_batch, maxy
+
+        g = self._lib.bohip_mgp_handle(self._h, 0)
+        return _qei_batch(self._lib, g, _cols(xs, self.dim), q, S, seed, maxy(self) if tau is None else tau, jitter, max_tries,
+                          want_samples)
+
+    def qei_select(self, samples, tau, q):
+        """ElasticGPE.qei_select (bohip_gp_qei_select) on the FIRST replica."""
+        from .model import _qei_select
+
+        return _qei_select(self._lib, self._lib.bohip_mgp_handle(self._h, 0), samples, tau, q)
+
     def mll_batch_dims(self):
         P, nmax = C.c_int64(), C.c_int64()
         check(self._lib.bohip_gp_mll_batch_dims(self._lib.bohip_mgp_handle(self._h, 0), C.byref(P), C.byref(nmax)))

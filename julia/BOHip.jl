@@ -346,6 +346,7 @@ function sample_joint(m::AbstractBOHipModel, X::AbstractMatrix, S::Integer; seed
 end
 include("BOHipPaths.jl")   # posterior sample paths (include/bohip_paths.h): draw_paths, paths_eval, paths_eval_grad, paths_coef
 include("BOHipFit.jl")     # batched marginal likelihood (include/bohip_fit.h): mll_batch_dims, mll_grad_batch
+include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/bohip_qei.h): qei_batch, qei_select
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
