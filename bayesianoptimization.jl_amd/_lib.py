@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("BOHIP_LIB") or os.path.join(_HERE, "csrc", "libbohip.
 
 OK, E_ARG, E_NOTPD, E_HIP, E_NODEVICE, E_STATE, E_UNSUPPORTED, E_COMM = 0, -1, -2, -3, -4, -5, -6, -7
 KERN = {"SEArd": 0, "SEIso": 1, "Mat52Ard": 2, "Mat32Ard": 3, "Mat12Ard": 4, "Mat52Iso": 5, "Mat32Iso": 6, "Mat12Iso": 7}
-ACQ = {"EI": 0, "PI": 1, "UCB": 2, "MI": 3, "MaxMean": 4, "ThompsonDraw": 5}   # (5: bohip_gp_direct_max only)
+ACQ = {"EI": 0, "PI": 1, "UCB": 2, "MI": 3, "MaxMean": 4, "ThompsonDraw": 5, "LogEI": 6}   # (5: bohip_gp_direct_max only; 6: bohip_acq.h)
 INFO_PIVOT, INFO_CAPACITY, INFO_REFITS, INFO_APPENDS = 0, 1, 2, 3
 INFO_CHOL_FORM, INFO_CHOL_FALLBACKS, INFO_CHOL_ABORT_TILES, INFO_JITTER_STEPS = 4, 5, 6, 7
 INFO_SCORE_LAUNCHES, INFO_SCORE_CHUNK, INFO_KERNEL_CLOCK_MHZ = 8, 9, 10
@@ -146,6 +146,11 @@ QEI_SIGNATURES = {
     "bohip_gp_qei_select": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_double, C.c_int64, _i64p, _dp]),
 }
 
+# every symbol include/bohip_acq.h declares (the acquisition functors and their partials on their own; the id of LogEI)
+ACQ_SIGNATURES = {
+    "bohip_acq_eval": (C.c_int, [C.c_int, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -201,12 +206,30 @@ def load():
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
-                              + list(QEI_SIGNATURES.items())):
+                              + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def acq_eval(acq, params, mu, var, partials=True):
+    """bohip_acq_eval: the functor `acq` (a key of ACQ) on the (mu, var) pairs, on the device.  -> (value, dmu, dvar), the last two
+    None without `partials`."""
+    import numpy as np
+
+    lib = load()
+    mu = np.ascontiguousarray(mu, dtype=np.float64).ravel()
+    var = np.ascontiguousarray(var, dtype=np.float64).ravel()
+    if mu.size != var.size:
+        raise ValueError("mu and var differ in length")
+    p = np.ascontiguousarray(list(params) + [0.0, 0.0], dtype=np.float64)
+    out = [np.empty(mu.size) for _ in range(3 if partials else 1)]
+    ptr = lambda a: a.ctypes.data_as(_dp)   # noqa: E731
+    check(lib.bohip_acq_eval(ACQ[acq], ptr(p), mu.size, ptr(mu), ptr(var), ptr(out[0]), ptr(out[1]) if partials else None,
+                             ptr(out[2]) if partials else None))
+    return (out[0], out[1], out[2]) if partials else (out[0], None, None)
 
 
 def check(rc):

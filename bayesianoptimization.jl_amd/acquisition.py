@@ -65,6 +65,66 @@ class ExpectedImprovement(AbstractAcquisition):               # :40-50
     params = ProbabilityOfImprovement.params
 
 
+class LogExpectedImprovement(AbstractAcquisition):
+    """The logarithm of the TEXTBOOK expected improvement, log(Delta Phi(z) + sigma phi(z)), in forms that stay finite and accurate
+    for any z = (mu - tau) / sigma (csrc/acq_log.h; Ament et al., NeurIPS 2023).  An extension: the reference has no
+    such type, and no default uses it.  Its arg-max is that of the textbook EI and its gradient never vanishes, where
+    ExpectedImprovement and its gradient are exactly 0.0 from z ~ -38 down.  `partials` returns (d/dmu, d/dsigma^2)."""
+    acq_id = "LogEI"
+    SWITCH, CF_DEPTH = -4.0, 40
+
+    def __init__(self, tau=-math.inf):
+        self.tau = float(tau)
+
+    @classmethod
+    def _parts(cls, z):
+        """(log h, Phi / h, phi / h) of h(z) = phi(z) + z Phi(z): direct above SWITCH, Mills' ratio by its continued fraction below."""
+        z = np.asarray(z, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            zz = np.where(z > cls.SWITCH, z, 0.0)
+            phi = 0.3989422804014327 * np.exp(-0.5 * (zz * zz))
+            Phi = 0.5 * _erfc(-zz / 1.4142135623730951)
+            h = phi + zz * Phi
+            t = np.where(z > cls.SWITCH, 4.0, -z)
+            r = np.zeros_like(t)
+            for k in range(cls.CF_DEPTH, 1, -1):
+                r = float(k) / (t + r)
+            tr = t + r
+            c1 = 1.0 / tr
+            tc = t + c1
+            lo = (-0.5 * (z * z) - 0.9189385332046728 + np.log(c1 / tc), tr, tc * tr)
+            hi = (np.log(h), Phi / h, phi / h)
+            return tuple(np.where(z > cls.SWITCH, a, b) for a, b in zip(hi, lo))
+
+    def __call__(self, mu, s2):
+        mu, s2 = np.asarray(mu, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            D = mu - self.tau
+            s = np.sqrt(np.where(s2 == 0, 1.0, s2))
+            v = np.where(s2 == 0, np.where(D > 0, np.log(np.where(D > 0, D, 1.0)), -math.inf), np.log(s) + self._parts(D / s)[0])
+        return float(v) if v.ndim == 0 else v
+
+    def partials(self, mu, s2):
+        mu, s2 = np.asarray(mu, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            D = mu - self.tau
+            ok = np.where(s2 == 0, 1.0, s2)
+            s = np.sqrt(ok)
+            _, a, b = self._parts(D / s)
+            dmu = np.where(s2 == 0, np.where(D > 0, 1.0 / np.where(D > 0, D, 1.0), 0.0), a / s)
+            ds2 = np.where(s2 == 0, 0.0, b / (2.0 * ok))
+        return (float(dmu), float(ds2)) if dmu.ndim == 0 else (dmu, ds2)
+
+    _setparams = ProbabilityOfImprovement._setparams          # EI's rule: tau <- max(maxy, tau)
+    params = ProbabilityOfImprovement.params
+
+
+def _erfc(x):
+    from scipy.special import erfc                             # (vectorised; math.erfc is its scalar form)
+
+    return erfc(x)
+
+
 class BrochuBetaScaling:                                      # :66-68
     def __init__(self, delta=0.1):
         self.delta = float(delta)

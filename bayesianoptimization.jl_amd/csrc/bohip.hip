@@ -18,6 +18,7 @@
 #include "../../include/bohip_paths.h"
 #include "../../include/bohip_fit.h"
 #include "../../include/bohip_qei.h"
+#include "../../include/bohip_acq.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -1694,9 +1695,14 @@ static void launch_small_pass(bohip_gp* g, const SmallCommon& sc, const SmallCom
     const bool lo = fam_low(hp);
     LAUNCH_FAM(lo, (k_small_v<DT, G, true>), (k_small_v<DT, G, false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
                g->stream, sc, sv, hp);
-    if (su)
-        LAUNCH_FAM(lo, (k_small_u<DT, G, true>), (k_small_u<DT, G, false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
-                   g->stream, scu, *su, hp);
+    if (su) {
+        if (DT == 64 && su->sv.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_small.hip k_small_u_logei64)
+            LAUNCH_FAM(lo, (k_small_u_logei64<true>), (k_small_u_logei64<false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
+                       g->stream, scu, *su, hp);
+        else
+            LAUNCH_FAM(lo, (k_small_u<DT, G, true>), (k_small_u<DT, G, false>), dim3((unsigned)sc.ntiles, (unsigned)npass), dim3(SP_THREADS), 0,
+                       g->stream, scu, *su, hp);
+    }
 }
 template <int DT>
 static void launch_small_pass_g(bohip_gp* g, int G, const SmallCommon& sc, const SmallCommon& scu, const SmallV& sv, const SmallU* su,
@@ -2697,7 +2703,7 @@ int bohip_gp_predict_dev(bohip_gp* g, const double* dXs, int64_t R, double* d_mu
 int bohip_gp_score_dev(bohip_gp* g, int acq_id, const double* acq_params, const double* dXs, int64_t R,
                        double* d_score, bohip_best* d_best) {
     if (!g || !dXs || R < 0) return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     if (R == 0) {
@@ -3339,7 +3345,7 @@ int bohip_paths_eval_grad(bohip_paths* p, const double* Xs, int64_t R, const int
 int bohip_gp_score(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* score,
                    bohip_best* best) {
     if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (R == 0) {
         if (best) { best->val = -INFINITY; best->idx = -1; }
         return 0;
@@ -3398,7 +3404,7 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
                           double fantasy_value, int flags, int64_t* idx, double* val, double* mu, double* var) {
     if (!g || !Xs || !idx || !val || R < 1) return fail(BOHIP_E_ARG, "bad arguments");
     if (acq_id == BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, "select_batch: a posterior draw has no conditioned score");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
     if (q < 1 || q > R) return fail(BOHIP_E_ARG, "select_batch: q must lie in 1..R (q = " + std::to_string(q) + ", R = " + std::to_string(R) + ")");
     if (fantasy != BOHIP_FANTASY_BELIEVER && fantasy != BOHIP_FANTASY_CONST)
@@ -3464,7 +3470,7 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     bf.mu = g->dmu; bf.var = g->dvar; bf.picked = picked; bf.rec = rec; bf.scal = scal; bf.fantasy = fantasy;
     bf.fantasy_value = fantasy_value; bf.tau0 = ap.p0;
     bf.noise = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
-    bf.raise_tau = (flags & BOHIP_BATCH_RAISE_TAU) && (acq_id == BOHIP_ACQ_EI || acq_id == BOHIP_ACQ_PI);
+    bf.raise_tau = (flags & BOHIP_BATCH_RAISE_TAU) && (acq_id == BOHIP_ACQ_EI || acq_id == BOHIP_ACQ_PI || acq_id == BOHIP_ACQ_LOGEI);
     bf.in = g->dblock_best; bf.n = nb; bf.t = 0;
     hipLaunchKernelGGL(k_batch_final, dim3(1), dim3(256), 0, g->stream, bf);
     BatchCond bc{};
@@ -3497,7 +3503,7 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
 int bohip_gp_score_grad(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* score,
                         double* grad) {
     if (!g || R < 0 || (R > 0 && (!Xs || !score || !grad))) return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (R == 0) return 0;
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
@@ -3572,7 +3578,7 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
                          const double* starts, int64_t R, int64_t maxeval, double ftol_rel, double xtol_abs, double* x_out,
                          double* f_out, bohip_best* best, double* best_x, int64_t* evals_out) {
     if (!g || !lb || !ub || R < 0 || (R > 0 && !starts)) return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
     if (evals_out) *evals_out = 0;
     if (R == 0) {
@@ -3642,6 +3648,8 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
         if (d <= 2) AW(2);
         else if (d <= 4) AW(4);
         else if (d <= 8) AW(8);
+        else if (pw.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_ascent.hip k_ascent_wg_logei16)
+            LAUNCH_FAM(lo, (k_ascent_wg_logei16<true>), (k_ascent_wg_logei16<false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
         else AW(16);
 #undef AW
         HIPCHK(hipGetLastError());
@@ -3847,7 +3855,7 @@ int bohip_gp_direct_max(bohip_gp* g, int acq_id, const double* acq_params, const
                         int64_t* device_calls) {
 #pragma clang fp contract(off)
     if (!g || !lb || !ub) return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id) && acq_id != BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     const int64_t d = g->d;
     for (int64_t i = 0; i < d; ++i)
@@ -3879,6 +3887,36 @@ int bohip_gp_direct_max(bohip_gp* g, int acq_id, const double* acq_params, const
     if (evaluations) *evaluations = s.evals;
     if (device_calls) *device_calls = calls;
     } catch (const std::exception& e) { return fail(BOHIP_E_ARG, e.what()); }   // (nothing throws across the ABI)
+    return 0;
+}
+
+// include/bohip_acq.h: the functors on their own (no model: the current device, the default stream, buffers of the call)
+int bohip_acq_eval(int acq_id, const double* acq_params, int64_t n, const double* mu, const double* var, double* value,
+                   double* dmu, double* dvar) {
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    if (n < 0 || (n > 0 && (!mu || !var || !value)) || (!dmu != !dvar)) return fail(BOHIP_E_ARG, "bad arguments");
+    if (n == 0) return 0;
+    if (n > (int64_t)1 << 31) return fail(BOHIP_E_UNSUPPORTED, "acq_eval: more than 2^31 elements");
+    if (bohip_device_count() <= 0) return fail(BOHIP_E_NODEVICE, "no HIP device visible; libbohip has no CPU fallback");
+    AcqParams ap{acq_id, 0.0, 0.0};
+    if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
+    if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
+    const int nout = dmu ? 3 : 1;
+    double* buf = nullptr;
+    HIPCHK(hipMalloc(&buf, (size_t)n * 8 * (2 + nout)));
+    double *d_mu = buf, *d_var = buf + n, *d_val = buf + 2 * n, *d_dmu = dmu ? buf + 3 * n : nullptr, *d_dvar = dmu ? buf + 4 * n : nullptr;
+    hipError_t e = hipMemcpy(d_mu, mu, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_var, var, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_acq_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)0, ap, n, d_mu, d_var, d_val, d_dmu, d_dvar);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(value, d_val, (size_t)n * 8, hipMemcpyDeviceToHost);   // (blocking: waits for the kernel)
+    if (e == hipSuccess && dmu) e = hipMemcpy(dmu, d_dmu, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && dmu) e = hipMemcpy(dvar, d_dvar, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (e != hipSuccess) return fail(BOHIP_E_HIP, std::string("acq_eval: ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -4069,7 +4107,7 @@ int bohip_debug_trigemm_pieces(int T, int64_t alpha_row, int* out, int cap) {
 // tests only (tests/test_prune_gpu.py): the pruned pass's upper bounds of the scores of R host candidates (layout of bohip_gp_score);
 // BOHIP_E_UNSUPPORTED where a value-only call of this size would not prune
 int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* ub) {
-    if (!g || R <= 0 || !Xs || !ub || acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "bad arguments");
+    if (!g || R <= 0 || !Xs || !ub || !acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "bad arguments");
     HIPCHK(hipSetDevice(g->device));
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     CHK(ensure_fresh(g));

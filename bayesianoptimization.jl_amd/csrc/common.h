@@ -20,7 +20,9 @@ __host__ __device__ inline int64_t round_up(int64_t x, int64_t m) { return (x + 
 // kernel ids / acquisition ids mirror include/bohip.h
 enum { KERN_SEARD = 0, KERN_SEISO = 1, KERN_MAT52ARD = 2, KERN_MAT32ARD = 3, KERN_MAT12ARD = 4, KERN_MAT52ISO = 5,
        KERN_MAT32ISO = 6, KERN_MAT12ISO = 7, KERN_COUNT = 8 };
-enum { ACQ_EI = 0, ACQ_PI = 1, ACQ_UCB = 2, ACQ_MI = 3, ACQ_MAXMEAN = 4 };
+enum { ACQ_EI = 0, ACQ_PI = 1, ACQ_UCB = 2, ACQ_MI = 3, ACQ_MAXMEAN = 4, ACQ_LOGEI = 6 };   // (5: BOHIP_ACQ_THOMPSON_DRAW, host only)
+// the ids a scoring entry point takes: 0-4 and 6 (include/bohip_acq.h)
+__host__ __device__ inline bool acq_id_scores(int id) { return (id >= ACQ_EI && id <= ACQ_MAXMEAN) || id == ACQ_LOGEI; }
 // What the device kernels see of the kernel: its family.  An iso kernel differs from its ARD form only in il2, which the
 // host fills with one length-scale.  FAM_M52 keeps the value 2 that the device compared the Mat52Ard id against.
 enum { FAM_SE = 0, FAM_M12 = 1, FAM_M52 = 2, FAM_M32 = 3 };

@@ -532,8 +532,8 @@ struct AscWgParams {
     unsigned long long max_ticks;       // maxtime in wall_clock64 ticks (0: none)
     int* passes;                        // [R] evaluation passes start r needed
 };
-template <int DT, bool LOW>
-__global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
+template <int DT, bool LOW, bool LOGEI>
+__device__ __forceinline__ void ascent_wg_body(const AscWgParams& p) {
 #pragma clang fp contract(off)
     __shared__ double ks[AWG_NMAX + 1], V[AWG_NMAX + 1], U[AWG_NMAX];
     __shared__ double red[AWG_WAVES][2 * DT];
@@ -695,10 +695,10 @@ __global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
                 double a = 0.0, b = 0.0;
                 for (int wv = 0; wv < AWG_WAVES; ++wv) { a += red[wv][2 * k]; b += red[wv][2 * k + 1]; }
                 double dmu, ds2;
-                acq_partials(p.ap, mu, s2, dmu, ds2);
+                acq_partials<LOGEI>(p.ap, mu, s2, dmu, ds2);
                 st.Gt[k] = dmu * a + (s2 > 0.0 ? ds2 * (-2.0 * b) : 0.0);
             }
-            if (k == 0) st.ft[0] = acq_eval(p.ap, mu, s2);
+            if (k == 0) st.ft[0] = acq_eval<LOGEI>(p.ap, mu, s2);
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0) vmcnt(0)" ::: "memory");   // (LDS state: lane 0's scalars are visible to the wave)
             // ---- the ascent's bookkeeping for this start point (same code as the batched drivers, on the LDS state)
@@ -721,6 +721,17 @@ __global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
     }
     if (tid < d) p.st.best_X[(int64_t)r * d + tid] = st.best_X[tid];
     if (tid == 0) { p.st.best_f[r] = st.best_f[0]; p.passes[r] = pass; }
+}
+// DT = 16 already spills: its LogEI calls live in k_ascent_wg_logei16, so the instantiation the other functors run keeps its registers.
+// WARNING: k_ascent_wg<16, .> answers ACQ_LOGEI with NaN (acq_eval<false>).  Its ONE launch site (bohip_gp_acquire_max) sends that id to
+// k_ascent_wg_logei16; a further launch site must make the same choice.
+template <int DT, bool LOW>
+__global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg(AscWgParams p) {
+    ascent_wg_body<DT, LOW, DT != 16>(p);
+}
+template <bool LOW>
+__global__ __launch_bounds__(AWG_THREADS) void k_ascent_wg_logei16(AscWgParams p) {
+    ascent_wg_body<16, LOW, true>(p);
 }
 
 // (value desc, index asc) over best_f; NaN never wins.  One workgroup.

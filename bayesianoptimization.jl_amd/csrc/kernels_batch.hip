@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void k_batch_cond(BatchCond bc, K
             __syncthreads();
         }
         AcqParams ap = bc.ap;
-        if (ap.acq == ACQ_EI || ap.acq == ACQ_PI) ap.p0 = sc.tau;
+        if (ap.acq == ACQ_EI || ap.acq == ACQ_PI || ap.acq == ACQ_LOGEI) ap.p0 = sc.tau;
         const double sqrtS = sqrt(sc.S), dy = sc.yf - sc.mu_s;
         const int d = hp.d;
         for (int64_t r = (int64_t)blockIdx.x * BATCH_WAVES + wave; r < bc.R; r += (int64_t)gridDim.x * BATCH_WAVES) {
@@ -132,7 +132,7 @@ struct BatchFinal {
     BatchScal* scal;
     int fantasy;        // 0 believer (y_f = mu_s), 1 constant
     double fantasy_value, noise, tau0;
-    int raise_tau;      // EI / PI: tau <- max(tau, y_f)
+    int raise_tau;      // EI / PI / LogEI: tau <- max(tau, y_f)
 };
 __global__ __launch_bounds__(256) void k_batch_final(BatchFinal bf) {
     __shared__ Best sh[4];

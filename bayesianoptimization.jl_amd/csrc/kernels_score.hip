@@ -9,6 +9,7 @@
 // src/acquisitionfunctions.jl:24-27,47-50,96,111,141 with src/utils.jl:48-49, and the arg-max of
 // acquire_max (src/acquisition.jl:54-68).
 #include "gemm_core.h"
+#include "acq_log.h"   // LogEI (ACQ_LOGEI)
 
 namespace bohip {
 
@@ -417,6 +418,9 @@ __global__ __launch_bounds__(256) void k_split_combine_u(const double* __restric
 // Acquisition functors -- verbatim operation order of the reference, contraction OFF (Julia never
 // fuses a*b+c).  normal_pdf / normal_cdf: src/utils.jl:48-49.
 // ------------------------------------------------------------------------------------------------
+// LOGEI = false compiles the LogEI call out: for the two kernel families that already spill (k_ascent_wg<16, .>, k_small_u<64, 4, .>),
+// where even the call cost 4-12 bytes of scratch more; their LogEI work runs in instantiations of its own (profiles/logei_resources.txt).
+template <bool LOGEI = true>
 __device__ __forceinline__ double acq_eval(const AcqParams& a, double mu, double s2) {
 #pragma clang fp contract(off)
     switch (a.acq) {
@@ -437,6 +441,9 @@ __device__ __forceinline__ double acq_eval(const AcqParams& a, double mu, double
             return mu + a.p0 * sqrt(s2);
         case ACQ_MI:  // :141
             return mu + a.p0 * (sqrt(s2 + a.p1) - sqrt(a.p1));
+        case ACQ_LOGEI:  // an extension (acq_log.h): log of the textbook EI, p0 = tau
+            if constexpr (LOGEI) return logei_value(mu, s2, a.p0);
+            else return NAN;   // (never launched with this id: a NaN never wins)
         default:  // MaxMean :111
             return mu;
     }
@@ -643,6 +650,10 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 //     PI  D_up >= 0: 1; else f(mu_up, s2_up) + 2^-38.
 //     UCB, MI: s2_b = s2_up for p0 >= 0, 0 for p0 < 0; slack 2^-38 (|mu_up| + |p0| (sqrt terms)) for the square roots.
 //     MaxMean: mu_up (one rounded addition: exact).
+//     LogEI (acq_log.h): log sigma + log h(z) rises in mu and, its partial phi / (2 s2 h) being positive, in sigma^2: s2_b = s2_up,
+//         which is never below the computed sigma^2 (above: no margin needed, the same fact UCB's bound rests on).  Slack
+//         2^-38 (1 + |f|): the two logarithms err by a few ulp of at most 745 + |f| each, h by <= 20 ulp at the branch switch --
+//         under 1e-12 absolute in all, ~4x head-room at f = 0 and more as |f| grows.  f = -inf (sigma^2 = 0, mu_up <= tau) stays -inf.
 // A NaN bound is never below L: such a candidate is always scored.
 struct PruneBound {
     const double* parts;     // k_kstar's partial sums [2][P][ldp]: of alpha_j K*'_j and of its absolute value, per 64 observations
@@ -698,6 +709,11 @@ __global__ __launch_bounds__(64) void k_prune_bound(PruneBound pb) {
             const double f = acq_eval(ap, mu_up, sb);
             const double roots = ap.acq == ACQ_UCB ? sqrt(sb) : sqrt(sb + fabs(ap.p1)) + sqrt(fabs(ap.p1));
             ub = f + 0x1p-38 * (fabs(mu_up) + fabs(ap.p0) * roots + 0x1p-1000);
+            break;
+        }
+        case ACQ_LOGEI: {   // rises in mu and in sigma^2 (d/ds2 > 0); -inf (sigma^2 = 0, mu_up <= tau) stays -inf, not NaN
+            const double f = acq_eval(ap, mu_up, s2);
+            ub = f == -INFINITY ? f : f + 0x1p-38 * (1.0 + fabs(f));
             break;
         }
         default:
@@ -1243,6 +1259,7 @@ __global__ __launch_bounds__(256) void k_reduce_records(const Best* __restrict__
 // this kernel finishes: one wave per candidate, lanes stride the observations, 2d butterfly sums,
 // then the chain rule through the REFERENCE's acquisition formulas (not the textbook EI).
 // ------------------------------------------------------------------------------------------------
+template <bool LOGEI = true>
 __device__ __forceinline__ void acq_partials(const AcqParams& a, double mu, double s2, double& dmu, double& ds2) {
     const double inv_sqrt_2pi = 0.3989422804014327;
     switch (a.acq) {
@@ -1263,8 +1280,21 @@ __device__ __forceinline__ void acq_partials(const AcqParams& a, double mu, doub
         }
         case ACQ_UCB: dmu = 1.0; ds2 = s2 > 0.0 ? a.p0 / (2.0 * sqrt(s2)) : 0.0; return;
         case ACQ_MI: dmu = 1.0; ds2 = a.p0 / (2.0 * sqrt(s2 + a.p1)); return;
+        case ACQ_LOGEI:
+            if constexpr (LOGEI) { const LogEIPartials g = logei_partials(mu, s2, a.p0); dmu = g.dmu; ds2 = g.ds2; }
+            else { dmu = NAN; ds2 = NAN; }
+            return;
         default: dmu = 1.0; ds2 = 0.0; return;
     }
+}
+
+// bohip_acq_eval (include/bohip_acq.h): the functor and its partials on n (mu, sigma^2) pairs, thread = element
+__global__ __launch_bounds__(256) void k_acq_eval(AcqParams ap, int64_t n, const double* __restrict__ mu, const double* __restrict__ var,
+                                                  double* __restrict__ value, double* __restrict__ dmu, double* __restrict__ dvar) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    value[i] = acq_eval(ap, mu[i], var[i]);
+    if (dmu) acq_partials(ap, mu[i], var[i], dmu[i], dvar[i]);
 }
 
 // Small batches: the posterior finish (q = sum V^2, mu, sigma^2, acquisition value: what k_small_finish does) rides on this kernel --

@@ -505,7 +505,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_small_v(SmallCommon sc, SmallV s
 // 10 us contraction, profiles/r05_small_pass_trace_*.txt.)  For the SE kernels d k*_j / d x_k = -k*_j (x_k - X_jk) / l_k^2 with k*_j taken
 // from the V pass's own K*' record (no second exponential).
 struct SmallVPair { d2 a, b; };
-template <int DT, int G, bool LOW>
+template <int DT, int G, bool LOW, bool LOGEI = true>
 __device__ __forceinline__ void small_u_body(const SmallCommon& sc, unsigned gow, const SmallU& su, const KernelHyper& hp, int tile, const SmallLds<DT>& L) {
     double* const lbuf = L.lbuf;
     double* const rt2 = lbuf;
@@ -707,12 +707,12 @@ __device__ __forceinline__ void small_u_body(const SmallCommon& sc, unsigned gow
                 const int rr = pass * 16 + small_slot_to_r(slot_);
                 if (su.sv.mu_out) su.sv.mu_out[rr] = mu;
                 if (su.sv.var_out) su.sv.var_out[rr] = s2;
-                const double fv = acq_eval(su.sv.ap, mu, s2);
+                const double fv = acq_eval<LOGEI>(su.sv.ap, mu, s2);
                 if (su.sv.score_out) su.sv.score_out[rr] = fv;
                 fold_f[rr & 15] = fv;
             } else {
                 double dmu, ds2;
-                acq_partials(su.sv.ap, mu, s2, dmu, ds2);
+                acq_partials<LOGEI>(su.sv.ap, mu, s2, dmu, ds2);
                 post_l[2 * slot_] = dmu;
                 post_l[2 * slot_ + 1] = ds2;
                 post_l[32 + slot_] = s2;
@@ -836,7 +836,15 @@ template <int DT, int G, bool LOW>
 __global__ __launch_bounds__(SP_THREADS) void k_small_u(SmallCommon sc, SmallU su, KernelHyper hp) {
     const unsigned gow = sc.go ? *sc.go : 1u;
     SMALL_LDS_DECL(DT, L);
-    small_u_body<DT, G, LOW>(sc, gow, su, hp, blockIdx.x, L);
+    // DT = 64 already spills: LogEI runs in k_small_u_logei64.  WARNING: k_small_u<64, ., .> answers ACQ_LOGEI with NaN (acq_eval<false>);
+    // its ONE launch site (launch_small_pass) sends that id to k_small_u_logei64, and a further launch site must make the same choice.
+    small_u_body<DT, G, LOW, DT != 64>(sc, gow, su, hp, blockIdx.x, L);
+}
+template <bool LOW>
+__global__ __launch_bounds__(SP_THREADS) void k_small_u_logei64(SmallCommon sc, SmallU su, KernelHyper hp) {
+    const unsigned gow = sc.go ? *sc.go : 1u;
+    SMALL_LDS_DECL(64, L);
+    small_u_body<64, 4, LOW, true>(sc, gow, su, hp, blockIdx.x, L);
 }
 
 }  // namespace bohip

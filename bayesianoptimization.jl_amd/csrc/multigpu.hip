@@ -249,7 +249,7 @@ static int mgp_exchange(bohip_mgp* m, int64_t S, Best* out) {
 }
 
 static int mgp_acq_params(int acq_id, const double* acq_params, AcqParams* ap) {
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
     (void)ap;
     return 0;
@@ -660,7 +660,7 @@ int bohip_gp_score_sharded_dev(bohip_gp* g, int acq_id, const double* acq_params
                                int64_t col_offset, int64_t R_total, double* d_score, bohip_best* best) {
     if (!g || R_local < 0 || (R_local > 0 && !dXs) || !best || col_offset < 0 || R_total < R_local)
         return fail(BOHIP_E_ARG, "bad arguments");
-    if (acq_id < 0 || acq_id > BOHIP_ACQ_MAXMEAN) return fail(BOHIP_E_ARG, "unknown acq_id");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
     if (!g->comm) return fail(BOHIP_E_STATE, "no communicator: call bohip_gp_comm_init first");
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);

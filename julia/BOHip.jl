@@ -39,7 +39,7 @@ using Dates: now
 using TimerOutputs: TimerOutput, reset_timer!, @timeit
 import Base: show
 
-export BOHipGPE, BOHipMultiGPE, DeviceBOpt
+export BOHipGPE, BOHipMultiGPE, DeviceBOpt, LogExpectedImprovement
 
 const libbohip = get(ENV, "BOHIP_LIB", "libbohip.so")
 
@@ -347,6 +347,7 @@ end
 include("BOHipPaths.jl")   # posterior sample paths (include/bohip_paths.h): draw_paths, paths_eval, paths_eval_grad, paths_coef
 include("BOHipFit.jl")     # batched marginal likelihood (include/bohip_fit.h): mll_batch_dims, mll_grad_batch
 include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/bohip_qei.h): qei_batch, qei_select
+include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_acq.h): LogExpectedImprovement, acq_eval
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 

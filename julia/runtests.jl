@@ -59,6 +59,22 @@ close_rel(a, b; rel = 1e-6, floor = 0.0) = all(abs.(a .- b) .<= rel .* abs.(b) .
         end
     end
 
+    @testset "LogEI (an extension): log of the textbook EI, same arg-max, device functor == host functor" begin
+        Random.seed!(2)
+        X = rand(3, 30); y = vec(sum(sin.(3 .* X), dims = 1)); xs = rand(3, 50)
+        dev = BOHipGPE(X, y; kernel = :SEArd, loglen = fill(log(0.5), 3), logsig = 0.0, logNoise = -2.0)
+        ac = LogExpectedImprovement(); BO.setparams!(ac, dev)
+        @test ac.τ == maximum(y)
+        μ, σ² = BO.mean_var(dev, xs)
+        v = BO.acquisitionfunction(ac, dev)(xs)
+        @test close_rel(v, ac.(μ, σ²); floor = 1e-12)
+        z = (μ .- ac.τ) ./ sqrt.(σ²)
+        ei = (μ .- ac.τ) .* (0.5 .* BOHip.erfc_.(-z ./ sqrt(2))) .+ sqrt.(σ²) .* exp.(-0.5 .* z .^ 2) ./ sqrt(2π)
+        @test argmax(v) == argmax(ei)
+        vd, dm, dv = BOHip.acq_eval(ac, μ, σ²)
+        @test vd == v && all(dm .> 0) && all(dv .> 0)
+    end
+
     @testset "warm start bookkeeping (test/warmstart.jl:9-70)" begin
         Random.seed!(7)
         ac = ExpectedImprovement()
