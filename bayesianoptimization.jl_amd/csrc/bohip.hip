@@ -236,6 +236,32 @@ static bool fam_low(const KernelHyper& h) { return h.fam == FAM_M12 || h.fam == 
 #define LAUNCH_FAM(lo, k_low, k_std, ...) \
     do { if (lo) hipLaunchKernelGGL(k_low, __VA_ARGS__); else hipLaunchKernelGGL(k_std, __VA_ARGS__); } while (0)
 
+// The kernels that loop over the coordinates are instantiated per dimension bucket DT = 2, 4, 8, 16, 32, 64 (CAP: the largest one the
+// caller's kernel is compiled for): f(std::integral_constant<int, DT>{}) for the smallest bucket that holds d.
+template <int CAP = DMAX, class F>
+static auto dispatch_dt(int d, F&& f) {
+    static_assert(CAP == 16 || CAP == 64, "a ladder ends at 16 or at DMAX = 64");
+    if (d <= 2) return f(std::integral_constant<int, 2>{});
+    if (d <= 4) return f(std::integral_constant<int, 4>{});
+    if (d <= 8) return f(std::integral_constant<int, 8>{});
+    if constexpr (CAP == 16) {
+        return f(std::integral_constant<int, 16>{});
+    } else {
+        if (d <= 16) return f(std::integral_constant<int, 16>{});
+        if (d <= 32) return f(std::integral_constant<int, 32>{});
+        return f(std::integral_constant<int, 64>{});
+    }
+}
+
+// (acq_id, acq_params) of the C ABI as the kernels take them: p0 of every acquisition but MaxMean, p1 of MI
+static int make_acq(int acq_id, const double* acq_params, AcqParams* out) {
+    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    *out = AcqParams{acq_id, 0.0, 0.0};
+    if (acq_id != BOHIP_ACQ_MAXMEAN) out->p0 = acq_params[0];
+    if (acq_id == BOHIP_ACQ_MI) out->p1 = acq_params[1];
+    return 0;
+}
+
 static KernelHyper make_hyper(const bohip_gp* g) {
     KernelHyper h;
     h.fam = kern_family(g->kern);
@@ -359,7 +385,6 @@ static const double g_asc_first_step = 0.1;   // the first step is never shorter
 static int g_asc_fold = 1;       // the free-running form's step inside k_small_u's last workgroup (BOHIP_ASC_LOCKSTEP=2: as a launch of its own, until round 6)
 static int g_asc_lockstep = 0;   // BOHIP_ASC_LOCKSTEP=1: the lock-step driver of the device ascent (five launches + a stream synchronisation per
                                  // evaluation pass) instead of the free-running one (k_asc_step)
-static int g_small_mfma = 1;   // BOHIP_SMALL_MFMA: the small-batch pass as two MFMA kernels (kernels_small.hip); 0 = round 4's five kernels
 static int g_small_m = 0;      // BOHIP_SMALL_M: 128-chunks of the contraction index per tile of those kernels; 0 = by size
 static int g_small_r = -1;  // batches up to this size (<= 256) take the row-wise path; -1: min(256, 90 + 300000 / N), the measured
                             // break-even with the MFMA path (N=500: > 256, N=3000: ~190, N=10000: ~110); BOHIP_SMALL_R overrides: below that
@@ -394,11 +419,8 @@ static int g_chol_exec_pairs = -1; // early sums and bulk updates are claimed tw
                                     // records (p tiles) per claim.  -1: 1, and 2 from 72 row tiles on (N = 10^4 14.05 -> 13.8 ms, N = 12000 23.1 -> 22.6; N = 8000 the same, N = 6000 4.0 -> 4.25)
 static int g_chol_exec_wgs = -1;  // executor workgroups (BOHIP_CHOL_EXEC_WGS); -1: by size -- ONE per free CU up to 32 row tiles, two from 45 on (see cholesky_exec)
 static int g_append_alpha_inc = 1;   // incremental alpha on append (BOHIP_APPEND_ALPHA_INC=0: recomputed as W'(W r))
-static int g_fuse_finish = 1;  // sigma^2 + acquisition + arg-max in k_trigemm_sq's epilogue (BOHIP_FUSE_FINISH=0: k_score + k_argmax_final)
 static int64_t g_chunk_rows_forced = 0;   // BOHIP_CHUNK_ROWS: candidates per K*' chunk (tools: chunk-size sweeps), 0 = the rule in chunk_rows
-static int g_halve_lo = -1, g_halve_hi = -1;   // BOHIP_TRIGEMM_HALVE (see trigemm_pieces)
 static int g_prune_m = -1;  // pruned arg-max: row tiles of the bounding prefix (BOHIP_PRUNE_M; 0: off, -1: the rule in prune_tiles)
-static int g_ks8 = 1;  // 8-wave k_trigemm_sq (contraction index split inside the workgroup); BOHIP_KS8=0 selects the 4-wave loop
 static int launch_gemm_nt(bohip_gp* g, const GemmNTParams& p, int batch = 1, hipStream_t st = nullptr, bool hi = false) {
     if (p.mt <= 0 || p.nt64 <= 0 || p.kc <= 0 || batch <= 0) return 0;
     if (hi) hipLaunchKernelGGL(k_gemm_nt_hi, dim3(p.mt * p.nt64, batch), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), st ? st : g->stream, p);
@@ -419,10 +441,10 @@ static void read_dev_knobs() {
         {"BOHIP_CHOL_EXEC_PAIRS", &g_chol_exec_pairs, -1, 64},
         {"BOHIP_CHOL_EXEC_URGENT", &g_chol_exec_urgent, 1, 1 << 20}, {"BOHIP_CHOL_NSF", &g_chol_nsf, 1, CH_NSF_MAX},
         {"BOHIP_CHOL_EXEC_PATIENCE_US", &g_chol_exec_patience_us, 0, 1 << 30}, {"BOHIP_CHOL_EXEC_FILL_INV", &g_chol_exec_fill_inv, 0, 1},
-        {"BOHIP_CHOL_EXEC_INV_PAIRS", &g_chol_exec_inv_pairs, 0, 1}, {"BOHIP_CHOL_EXEC_WGS", &g_chol_exec_wgs, 1, 1 << 20}, {"BOHIP_KS8", &g_ks8, 0, 1},
+        {"BOHIP_CHOL_EXEC_INV_PAIRS", &g_chol_exec_inv_pairs, 0, 1}, {"BOHIP_CHOL_EXEC_WGS", &g_chol_exec_wgs, 1, 1 << 20},
         {"BOHIP_CHOL_EXEC_FAST", &g_chol_exec_fast, -1, 1 << 20},
         {"BOHIP_CHOL_EXEC_SECOND", &g_chol_exec_second, 0, 1}, {"BOHIP_SMALL_ZERO_COPY", &g_small_zero_copy, 0, 1}, {"BOHIP_CHOL_EXEC_NBU", &g_chol_exec_nbu, 0, 16}, {"BOHIP_CHUNK_ROWS", &chunk_rows, 0, 1 << 30},
-        {"BOHIP_TRIGEMM_HALVE_LO", &g_halve_lo, 0, 1 << 20}, {"BOHIP_TRIGEMM_HALVE_HI", &g_halve_hi, 0, 1 << 20}, {"BOHIP_FUSE_FINISH", &g_fuse_finish, 0, 1}, {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16},
+        {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16},
         {"BOHIP_APPEND_ALPHA_INC", &g_append_alpha_inc, 0, 1}, {"BOHIP_BULK_PIECES", &g_bulk_pieces, 0, 8}, {"BOHIP_SPLIT", &g_split, 0, 1},
         {"BOHIP_SMALL_R", &g_small_r, 0, SMALL_MAX}, {"BOHIP_SMALL_M", &g_small_m, 0, 1 << 20}, {"BOHIP_CHOL_DF_DUMP", &dump, 0, 1},
     };
@@ -442,8 +464,7 @@ static int one_time_kernel_setup() {
     if (done) return 0;
     HIPCHK(hipFuncSetAttribute((const void*)k_potf2_inv, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<1>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq<2>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_rows, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
@@ -462,7 +483,6 @@ static int one_time_kernel_setup() {
     if (const char* e = getenv("BOHIP_CHOL_INV_GRP_MIN")) g_chol_inv_grp_min = std::max(0, atoi(e));
     if (const char* e = getenv("BOHIP_ASC_WG_NMAX")) g_asc_wg_nmax = std::max(0, atoi(e));
     if (const char* e = getenv("BOHIP_ASC_LOCKSTEP")) { g_asc_lockstep = atoi(e) == 1; g_asc_fold = atoi(e) != 2; }
-    if (const char* e = getenv("BOHIP_SMALL_MFMA")) g_small_mfma = atoi(e);
     if (const char* e = getenv("BOHIP_SAMPLE_MFMA_MIN")) g_sample_mfma_min = std::max(1, atoi(e));
     g_chol_df_strict = getenv("BOHIP_CHOL_DF_STRICT") != nullptr;
     read_dev_knobs();
@@ -957,7 +977,7 @@ static std::mutex g_df_mutex[64];   // per device: see refit_once
 // advisory file lock named after the device's PCI address, taken inside the host lock and released with it (the kernel drops it if the process
 // dies).  Round 5 (advisor): the lock file lives in a PER-USER directory ($XDG_RUNTIME_DIR, else /tmp/bohip-<uid> created 0700 and checked to be
 // ours), is opened O_NOFOLLOW | O_CLOEXEC with mode 0600 and never chmod'ed (a planted symlink or file cannot redirect it); the lock is taken
-// NON-blocking with a bounded retry (BOHIP_DF_FILE_LOCK_MS, 300 ms) -- a stopped or hung holder no longer blocks every refit on the GPU: the
+// NON-blocking with a bounded retry (BOHIP_DF_FILE_LOCK=n: n ms, 300 by default) -- a stopped or hung holder no longer blocks every refit on the GPU: the
 // refit then goes ahead unlocked and the flags' 200 ms time-out + launch-chain fall-back stay the safety net; the descriptor is re-opened in a
 // forked child (parent and child would share ONE open file description and not exclude each other).  No lock file (read-only directory,
 // BOHIP_DF_FILE_LOCK=0): the refit goes ahead as before.  Processes of DIFFERENT users on one device do not see each other's lock.
@@ -1243,12 +1263,11 @@ static int refit_once(bohip_gp* g, double jitter) {
     {
         const int rpb = 32;
         dim3 grid((Npad + 255) / 256, (Npad + rpb - 1) / rpb);
-        const bool lo = fam_low(hp);
-#define BC(DTV) LAUNCH_FAM(lo, (k_build_cov<DTV, true>), (k_build_cov<DTV, false>), grid, dim3(256), 0, g->stream, g->dX, N, Npad, hp, \
-                           noise, g->dL, ld, rpb)
-        if (g->d <= 2) BC(2); else if (g->d <= 4) BC(4); else if (g->d <= 8) BC(8); else if (g->d <= 16) BC(16);
-        else if (g->d <= 32) BC(32); else BC(64);
-#undef BC
+        dispatch_dt(g->d, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            LAUNCH_FAM(fam_low(hp), (k_build_cov<DT, true>), (k_build_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dX, N, Npad, hp, noise,
+                       g->dL, ld, rpb);
+        });
     }
     HIPCHK(hipGetLastError());
     t_end(g);
@@ -1576,28 +1595,17 @@ static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1,
                    g->dKsT, g->ld, rb, KstarParts{});
 }
 
-// The row pieces of k_trigemm_sq (kernels_score.hip), heaviest first: which row tiles go as two 64-row halves is a function
-// of the number of row tiles and of where the alpha row sits -- nothing else, so a candidate's score does not depend on the batch it
-// is scored in.  Default: NONE (whole tiles; only a last tile whose live rows fit its upper half runs as a half piece, as it always
-// did).  BOHIP_TRIGEMM_HALVE="lo,hi" halves the tiles lo <= rt < hi -- the round-4 experiment: tools/sim_trigemm_tail.py predicted
-// -3.7 % for the shortest third of the tiles (the launch ends evenly: idle tail 3.2 -> 0.4 % in the model), the chip gave 0.0 %
-// (profiles/r04_trigemm_halve_sweep.txt: "0,8" 609 us against 609; "0,12" 621; all halves 665): MI355X clocks to its power
-// budget, CUs that idle at the end of the launch hand their share of it to the ones still working, and a half job spends more
-// LDS reads per flop.
+// The row pieces of k_trigemm_sq (kernels_score.hip), heaviest first: whole row tiles, and a last tile whose live rows fit its
+// upper half as a half piece.  A function of the number of row tiles and of where the alpha row sits -- nothing else, so a
+// candidate's score does not depend on the batch it is scored in.  (Issuing tiles as two 64-row halves to even out the end of the
+// launch was measured in round 4 and gave nothing: profiles/r04_trigemm_halve_sweep.txt, DESIGN.md.)
 static void trigemm_pieces(int T, int64_t alpha_row, std::vector<int>& out) {
-    int lo = 0, hi = 0;
-    if (g_halve_lo >= 0) { lo = std::min(g_halve_lo, T); hi = std::min(std::max(g_halve_hi, lo), T); }
     struct P { double cost; int code; };
     std::vector<P> ps;
     for (int rt = 0; rt < T; ++rt) {
         const int64_t live = alpha_row + 1 - (int64_t)rt * TILE;   // live rows of this tile (the last one: up to the alpha row)
-        if (live <= TILE / 2) { ps.push_back({(rt + 0.5) / 2.0, rt | PIECE_UPPER_SOLO << 16}); continue; }
-        if (rt >= lo && rt < hi) {
-            ps.push_back({(rt + 0.5) / 2.0, rt | PIECE_UPPER << 16});
-            ps.push_back({(rt + 1.0) / 2.0, rt | PIECE_LOWER << 16});
-        } else {
-            ps.push_back({rt + 1.0, rt | PIECE_WHOLE << 16});
-        }
+        if (live <= TILE / 2) ps.push_back({(rt + 0.5) / 2.0, rt | PIECE_UPPER_SOLO << 16});
+        else ps.push_back({rt + 1.0, rt | PIECE_WHOLE << 16});
     }
     std::stable_sort(ps.begin(), ps.end(), [](const P& a, const P& b) { return a.cost > b.cost; });
     out.clear();
@@ -1635,12 +1643,8 @@ static int launch_trigemm(bohip_gp* g, int T, int64_t ncand, int64_t N, int64_t 
         }
         fz.clk = g->dclk;
     }
-    if (g_ks8)
-        hipLaunchKernelGGL(k_trigemm_sq<2>, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW,
-                           g->ld, g->dKsT, g->ld, g->dpieces, NP, CT, N, g->dq, Rpad, g->dmu_raw, r0, VT, g->ld, fz);
-    else
-        hipLaunchKernelGGL(k_trigemm_sq<1>, dim3(8 * n_local * NP), dim3(GEMM_THREADS), glds3_lds_bytes<4>(), g->stream, g->dW,
-                           g->ld, g->dKsT, g->ld, g->dpieces, NP, CT, N, g->dq, Rpad, g->dmu_raw, r0, VT, g->ld, fz);
+    hipLaunchKernelGGL(k_trigemm_sq, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW, g->ld,
+                       g->dKsT, g->ld, g->dpieces, NP, CT, N, g->dq, Rpad, g->dmu_raw, r0, VT, g->ld, fz);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1650,22 +1654,17 @@ template <int DT>
 static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp, const KstarParts* kp);
 static int launch_kstar_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp,
                             const KstarParts* kp = nullptr) {
-    if (g->d <= 2) launch_kstar<2>(g, dXs, r0, r1, Npad, hp, kp);
-    else if (g->d <= 4) launch_kstar<4>(g, dXs, r0, r1, Npad, hp, kp);
-    else if (g->d <= 8) launch_kstar<8>(g, dXs, r0, r1, Npad, hp, kp);
-    else if (g->d <= 16) launch_kstar<16>(g, dXs, r0, r1, Npad, hp, kp);
-    else if (g->d <= 32) launch_kstar<32>(g, dXs, r0, r1, Npad, hp, kp);
-    else launch_kstar<64>(g, dXs, r0, r1, Npad, hp, kp);
+    dispatch_dt(g->d, [&](auto dt) { launch_kstar<decltype(dt)::value>(g, dXs, r0, r1, Npad, hp, kp); });
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// Small-batch posterior (R <= SMALL_R): V' rows into dApp[0..R), q and mu_raw; optionally U' = V' W into dApp[APP_UT_ROW0..).
+// k_grad_finish with the observations split over workgroups: the splits' partial sums and the arrival counter of every candidate
 static int ensure_small_counters(bohip_gp* g) {
     if (g->dgparts) return 0;
-    HIPCHK(hipMalloc(&g->dgparts, (size_t)SMALL_MAX * 16 * (2 * DMAX + 2) * 8));
-    HIPCHK(hipMalloc(&g->dgcount, (SMALL_MAX + 1) * sizeof(unsigned)));   // [0, SMALL_MAX): k_grad_finish, [SMALL_MAX]: k_small_finish
-    HIPCHK(hipMemsetAsync(g->dgcount, 0, (SMALL_MAX + 1) * sizeof(unsigned), g->stream));
+    HIPCHK(hipMalloc(&g->dgparts, (size_t)SMALL_MAX * 16 * (2 * DMAX) * 8));
+    HIPCHK(hipMalloc(&g->dgcount, SMALL_MAX * sizeof(unsigned)));
+    HIPCHK(hipMemsetAsync(g->dgcount, 0, SMALL_MAX * sizeof(unsigned), g->stream));
     return 0;
 }
 static bool split_applicable(const bohip_gp* g);
@@ -1717,7 +1716,8 @@ static void launch_small_pass_g(bohip_gp* g, int G, const SmallCommon& sc, const
 // all R <= SMALL_MAX candidates: values (mu, sigma^2, score, arg-max record) and, with d_grad, the gradient of the score
 static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqParams& ap, double* d_mu, double* d_var, double* d_score,
                            Best* d_best, int64_t best_off, double* d_grad) {
-    const int N = (int)g->n, T = (N + TILE - 1) / TILE, P = (int)R, npass = (P + 15) / 16, DTm = g->d <= 2 ? 2 : g->d <= 4 ? 4 : g->d <= 8 ? 8 : g->d <= 16 ? 16 : g->d <= 32 ? 32 : 64;
+    const int N = (int)g->n, T = (N + TILE - 1) / TILE, P = (int)R, npass = (P + 15) / 16,
+              DTm = dispatch_dt(g->d, [](auto dt) { return decltype(dt)::value; });
     // chunks per tile: every tile's partial sums cost one 16-KiB write and one read by the block's finisher, a column block's finisher adds up
     // to ceil(T / m) of them; BOHIP_SMALL_M overrides (tools/small_batch_bench.py sweeps it)
     // (one workgroup of these kernels per CU: all tiles of a pass are resident at once when there are no more tiles than CUs)
@@ -1769,46 +1769,10 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
     scu.A = g->dW; scu.cnt = g->dsm_cnt + cnt_block;
     const int G = (std::min(P, 16) + 3) / 4;
     t_begin(g, d_grad ? "small_V+U" : "small_V");
-    switch (DTm) {
-        case 2: launch_small_pass_g<2>(g, G, sc, scu, sv, sup, hp, npass); break;
-        case 4: launch_small_pass_g<4>(g, G, sc, scu, sv, sup, hp, npass); break;
-        case 8: launch_small_pass_g<8>(g, G, sc, scu, sv, sup, hp, npass); break;
-        case 16: launch_small_pass_g<16>(g, G, sc, scu, sv, sup, hp, npass); break;
-        case 32: launch_small_pass_g<32>(g, G, sc, scu, sv, sup, hp, npass); break;
-        default: launch_small_pass_g<64>(g, G, sc, scu, sv, sup, hp, npass); break;
-    }
+    dispatch_dt(g->d, [&](auto dt) { launch_small_pass_g<decltype(dt)::value>(g, G, sc, scu, sv, sup, hp, npass); });
     HIPCHK(hipGetLastError());
     t_end(g);
     g->q_tiles = 0;
-    return 0;
-}
-
-// candidates [r0, r1), at most SMALL_MAX of them; the output pointers are indexed by the GLOBAL candidate number
-static int small_posterior(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, bool want_u, const AcqParams& ap,
-                           double* d_mu, double* d_var, double* d_score, Best* d_best, int64_t best_off = 0) {
-    if (g_small_mfma && r0 == 0 && !want_u) return small_pass_mfma(g, dXs, r1, ap, d_mu, d_var, d_score, d_best, best_off, nullptr);
-    CHK(ensure_small_counters(g));
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), ld = g->ld;
-    const int P = (int)(r1 - r0);
-    const KernelHyper hp = make_hyper(g);
-    t_begin(g, "kstar");
-    CHK(launch_kstar_any(g, dXs, r0, r1, Npad, hp));
-    t_end(g);
-    t_begin(g, "small_V");
-    // rows 0..N of W (row N carries alpha'): V'[r][j] = sum_{k<=j} W[j][k] K*'[r][k]
-    CHK(launch_rows_trimv(g, g->dW, N + 1, g->dKsT, P, g->dApp, 0));
-    hipLaunchKernelGGL(k_small_finish, dim3((unsigned)P), dim3(256), 0, g->stream, g->dApp, ld, N, P, g->dq + r0, g->dmu_raw + r0,
-                       g->dgcount + SMALL_MAX, std::exp(2.0 * g->logsig), g->beta, ap, d_mu ? d_mu + r0 : nullptr,
-                       d_var ? d_var + r0 : nullptr, d_score ? d_score + r0 : nullptr, d_best, (long long)best_off);
-    HIPCHK(hipGetLastError());
-    t_end(g);
-    g->q_tiles = 0;
-    if (want_u) {
-        t_begin(g, "small_U");
-        // U'[r][c] = sum_{k>=c} W'[c][k] V'[r][k]
-        CHK(launch_rows_trimv(g, g->dWT, N, g->dApp, P, g->dApp + (int64_t)APP_UT_ROW0 * ld, 1));
-        t_end(g);
-    }
     return 0;
 }
 
@@ -1915,16 +1879,13 @@ static int prune_tiles(int T) {
     return m < T ? m : 0;
 }
 // k_trigemm_rows's job table: the 64-row halves of the row pieces, heaviest (most chunks) first -- rt | hh << 16 | solo << 17.  The
-// weight falls with rt, so the halves of the row tiles >= t0 are the table's first rows_halves_from(t0) entries.  Empty when a
-// piece is not one k_trigemm_rows reproduces (the measurement knobs: halved tiles, the 4-wave loop).
+// weight falls with rt, so the halves of the row tiles >= t0 are the table's first rows_halves_from(t0) entries.
 static std::vector<int> rows_halves(const std::vector<int>& pieces) {
     std::vector<int> out;
-    if (!g_ks8) return out;
     for (int c : pieces) {
         const int rt = c & 0xffff, mode = c >> 16;
         if (mode == PIECE_UPPER_SOLO) out.push_back(rt | 1 << 17);
-        else if (mode == PIECE_WHOLE) { out.push_back(rt | 1 << 16); out.push_back(rt); }
-        else return {};
+        else { out.push_back(rt | 1 << 16); out.push_back(rt); }
     }
     std::stable_sort(out.begin(), out.end(), [](int a, int b) {   // chunks: 8 rt + 8 (lower half), 8 rt + 4 (upper, solo)
         return 8 * (a & 0xffff) + ((a >> 16) & 1) * 4 > 8 * (b & 0xffff) + ((b >> 16) & 1) * 4;
@@ -1956,12 +1917,8 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
     const int n_local = (CT + 7) / 8;
     if (NP <= 0 || CT <= 0) return 0;
     if (g->timing && g->dclk) fz.clk = g->dclk;
-    if (g_ks8)
-        hipLaunchKernelGGL(k_trigemm_sq<2>, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW,
-                           g->ld, KsT, g->ld, pieces, NP, CT, g->n, q, ldq, mu_raw, (int64_t)0, nullptr, g->ld, fz);
-    else
-        hipLaunchKernelGGL(k_trigemm_sq<1>, dim3(8 * n_local * NP), dim3(GEMM_THREADS), glds3_lds_bytes<4>(), g->stream, g->dW,
-                           g->ld, KsT, g->ld, pieces, NP, CT, g->n, q, ldq, mu_raw, (int64_t)0, nullptr, g->ld, fz);
+    hipLaunchKernelGGL(k_trigemm_sq, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW, g->ld, KsT,
+                       g->ld, pieces, NP, CT, g->n, q, ldq, mu_raw, (int64_t)0, nullptr, g->ld, fz);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1971,9 +1928,8 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
 // arrive finishes it (scores, merges the record; round 1 lists round 2 and, when it lists nobody, writes the result).  Round 2's
 // steady form is a fixed grid whose workgroups loop over the column groups: right for a list of any length, slow for a long one.
 // long_form (the host expects a long list: score_core) is round 2 as four launches: gathered rows + k_trigemm_sq past PRUNE_ROWS_CAP
-// candidates, k_trigemm_rows up to it, k_prune_finish.  Under the measurement knobs that change the row pieces or the loop
-// (rows_halves empty) both rounds keep k_trigemm_sq and k_prune_finish.  No host round trip: the lists and their lengths stay on
-// the device and the surplus workgroups leave at once.
+// candidates, k_trigemm_rows up to it, k_prune_finish.  No host round trip: the lists and their lengths stay on the device and the
+// surplus workgroups leave at once.
 // ub_host (tests, bohip_debug_prune_bounds): stop after the bounds and copy them out.
 static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
                        double* ub_host = nullptr, bool long_form = false) {
@@ -2007,7 +1963,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     const KstarParts kp{g->dW + N * ld, (double*)(b + o_parts), Rpad};
     unsigned* cnt = (unsigned*)(b + o_cnt);
     Best* rec = (Best*)(b + o_rec);
-    const std::vector<int> hv = rows_halves(g->hpieces);   // (after the pieces in the table; empty: the rounds keep k_trigemm_sq)
+    const std::vector<int> hv = rows_halves(g->hpieces);   // (after the pieces in the table)
     const int nh = rows_halves_from(hv, m);
     std::vector<int> both = pa;
     both.insert(both.end(), pb.begin(), pb.end());
@@ -2053,51 +2009,27 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     pf.ap = ap; pf.rec = rec;
     const int* hvd = pcs + pa.size() + pb.size();
     pf.ub = ub; pf.mark = mark; pf.R = R; pf.cnt2 = cnt + 1; pf.best_off = (long long)best_off;
-    if (nh > 0) {
-        // Round 1 finishes in its own launch: the last workgroup to arrive scores, merges and lists round 2 (the tail), and when it
-        // lists nobody it writes the call's result and the pinned word itself.
-        pf.list = l1; pf.cnt = cnt; pf.list2 = l2; pf.best_out = d_best; pf.stat = g->hprune_stat;
-        CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l1, cnt, k1, q2, Rpad, mu2, 0, &pf, cnt + PRUNE_ARRIVE));
-        const int64_t cap = R - k1;   // worst case of round 2's list
-        pf.list = l2; pf.cnt = cnt + 1; pf.list2 = nullptr;
-        if (cap > 0 && !long_form) {
-            // steady form, ONE launch for a list of any length: a fixed grid whose workgroups loop over the column groups; its last
-            // arriver finishes the round and writes the result.  An empty list: every workgroup leaves, round 1 has written it.
-            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, INT_MAX, q2, Rpad, mu2, PRUNE_R2_GROUPS, &pf, cnt + PRUNE_ARRIVE + 1));
-        } else if (cap > 0) {
-            // long form, when a long list is expected: the row-split kernel takes lists of up to PRUNE_ROWS_CAP candidates, the gathered
-            // rows and k_trigemm_sq the longer ones -- both are enqueued and the device-side count picks (cnt[2]: k_trigemm_sq's
-            // count, 0 when the list is short); the finish is a launch of its own
-            if (cap > PRUNE_ROWS_CAP) {
-                hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, (const int*)l2, (const unsigned*)(cnt + 1),
-                                   (const double*)g->dKsT, ld, Npad, ks2, PRUNE_ROWS_CAP, cnt + 2);
-                fz.live = cnt + 2;
-                CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
-            }
-            CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, (int)std::min<int64_t>(cap, PRUNE_ROWS_CAP), q2, Rpad, mu2));
-            hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
-            HIPCHK(hipGetLastError());
-        }
-        t_end(g);
-        return 0;
-    }
-    // the measurement knobs that change the row pieces or the loop (rows_halves empty): both rounds keep k_trigemm_sq on gathered rows
-    // and k_prune_finish
-    for (int round = 0; round < 2; ++round) {
-        const int* list = round == 0 ? l1 : l2;
-        const unsigned* c = cnt + round;
-        const int64_t cap = round == 0 ? k1 : R - k1;   // worst case of the list's length
-        if (cap > 0) {
-            hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, list, c, (const double*)g->dKsT, ld, Npad, ks2,
-                               -1, cnt + 2);
+    // Round 1 finishes in its own launch: the last workgroup to arrive scores, merges and lists round 2 (the tail), and when it
+    // lists nobody it writes the call's result and the pinned word itself.
+    pf.list = l1; pf.cnt = cnt; pf.list2 = l2; pf.best_out = d_best; pf.stat = g->hprune_stat;
+    CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l1, cnt, k1, q2, Rpad, mu2, 0, &pf, cnt + PRUNE_ARRIVE));
+    const int64_t cap = R - k1;   // worst case of round 2's list
+    pf.list = l2; pf.cnt = cnt + 1; pf.list2 = nullptr;
+    if (cap > 0 && !long_form) {
+        // steady form, ONE launch for a list of any length: a fixed grid whose workgroups loop over the column groups; its last
+        // arriver finishes the round and writes the result.  An empty list: every workgroup leaves, round 1 has written it.
+        CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, INT_MAX, q2, Rpad, mu2, PRUNE_R2_GROUPS, &pf, cnt + PRUNE_ARRIVE + 1));
+    } else if (cap > 0) {
+        // long form, when a long list is expected: the row-split kernel takes lists of up to PRUNE_ROWS_CAP candidates, the gathered
+        // rows and k_trigemm_sq the longer ones -- both are enqueued and the device-side count picks (cnt[2]: k_trigemm_sq's
+        // count, 0 when the list is short); the finish is a launch of its own
+        if (cap > PRUNE_ROWS_CAP) {
+            hipLaunchKernelGGL(k_prune_gather, dim3((unsigned)cap), dim3(256), 0, g->stream, (const int*)l2, (const unsigned*)(cnt + 1),
+                               (const double*)g->dKsT, ld, Npad, ks2, PRUNE_ROWS_CAP, cnt + 2);
             fz.live = cnt + 2;
             CHK(launch_trigemm_on(g, ks2, pcs + pa.size(), (int)pb.size(), (int)((cap + CTILE - 1) / CTILE), q2, Rpad, mu2, fz));
         }
-        pf.list = list; pf.cnt = c;
-        pf.best_out = round == 1 ? d_best : nullptr;
-        pf.stat = round == 1 ? g->hprune_stat : nullptr;
-        // round 1's finish goes on to list round 2 (its tail); round 2's is the same kernel without it
-        pf.list2 = round == 0 ? l2 : nullptr;
+        CHK(launch_trigemm_rows(g, g->dKsT, hvd, nh, l2, cnt + 1, (int)std::min<int64_t>(cap, PRUNE_ROWS_CAP), q2, Rpad, mu2));
         hipLaunchKernelGGL(k_prune_finish, dim3(1), dim3(256), 0, g->stream, pf);
         HIPCHK(hipGetLastError());
     }
@@ -2133,63 +2065,54 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     CHK(ensure_fresh(g));
     CHK(ensure_score_scratch(g, R));
-    AcqParams ap{acq_id, 0.0, 0.0};
-    if (acq_params) {
-        if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
-        if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
-    } else if (acq_id != BOHIP_ACQ_MAXMEAN) {
-        return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
-    }
-    if (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) {   // row-wise posterior, scoring and arg-max fused into its finish kernel
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
+    if (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) {   // small batches: scoring and arg-max ride on the pass's own kernel
         CHK(one_time_kernel_setup());
-        return small_posterior(g, dXs, 0, R, false, ap, d_mu, d_var, d_score, d_best, best_off);
+        return small_pass_mfma(g, dXs, R, ap, d_mu, d_var, d_score, d_best, best_off, nullptr);
     }
     const SplitPlan sp = split_plan(g, R);
-    if (sp.nsl > 0) {
+    if (sp.nsl > 0) {   // a few hundred candidates: split-K posterior, then scoring and arg-max as launches of their own
         CHK(split_posterior(g, dXs, R, sp, false));
-    } else if (int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
-               m > 0 && g_fuse_finish && d_best && !d_mu && !d_var && !d_score && R <= PRUNE_R_MAX && R <= g->chunk_now &&
-               g->batch_hint == 0 && prune_wanted(g, R)) {
+        const int64_t Rpad = round_up(R, TILE) + TILE;
+        const int nb = (int)((R + 255) / 256);
+        t_begin(g, "score");
+        hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, g->q_tiles, g->dmu_raw, R,
+                           std::exp(2.0 * g->logsig), g->beta, ap, d_mu, d_var, d_score, d_best ? g->dblock_best : nullptr);
+        if (d_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, g->dblock_best, nb, d_best, (long long)best_off);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        return 0;
+    }
+    if (int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
+        m > 0 && d_best && !d_mu && !d_var && !d_score && R <= PRUNE_R_MAX && R <= g->chunk_now && g->batch_hint == 0 && prune_wanted(g, R)) {
         // value-only: only the winner leaves the call -- candidates that provably cannot win are not contracted past m row tiles.
         // Not for shards of a larger set (batch_hint: the sharded entry points and bohip_gp_set_batch_hint): see DESIGN.md 6d.
         // round 2's form (either gives the same record): the long one when the last figure read or a back-off announces a long list
         const bool want_long = g->prune_retry || g->prune_seen > (unsigned)PRUNE_ROWS_CAP;
         g->prune_retry = false;
         return pruned_pass(g, dXs, R, m, ap, d_best, best_off, nullptr, g->prune_r2_form < 0 ? want_long : g->prune_r2_form == 1);
-    } else if (g_fuse_finish) {
-        // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
-        // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
-        FuseParams fz{};
-        fz.tile_cnt = g->dfz_cnt; fz.total_cnt = g->dfz_cnt + g->fz_cap; fz.tile_best = g->dfz_best;
-        fz.tiles_total = (int)((R + CTILE - 1) / CTILE); fz.R_total = R;
-        fz.sigma2 = std::exp(2.0 * g->logsig); fz.beta = g->beta; fz.ap = ap;
-        fz.mu_out = d_mu; fz.var_out = d_var; fz.score_out = d_score; fz.best_out = d_best; fz.best_off = best_off;
-        // The fused finish counts arrivals in counters its last waves leave at zero.  If an earlier call failed between two of
-        // its launches they are not: every later call would then miss its "last arrival" and write no result.  So a call that
-        // did not enqueue all of its launches marks the counters dirty, and the next one clears them first.
-        if (g->fz_dirty) HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(g->fz_cap + 1 + 16) * sizeof(unsigned), g->stream));
-        g->fz_dirty = true;
-        const int rc = posterior_pass(g, dXs, R, fz);
-        if (rc == 0) g->fz_dirty = false;
-        return rc;
-    } else {
-        CHK(posterior_pass(g, dXs, R));
     }
-    const int64_t Npad = round_up(g->n + 1, TILE), Rpad = round_up(R, TILE) + TILE;
-    const int T = (int)(Npad / TILE);
-    const int nb = (int)((R + 255) / 256);
-    t_begin(g, "score");
-    hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, g->q_tiles, g->dmu_raw, R,
-                       std::exp(2.0 * g->logsig), g->beta, ap, d_mu, d_var, d_score, d_best ? g->dblock_best : nullptr);
-    if (d_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, g->dblock_best, nb, d_best, (long long)best_off);
-    HIPCHK(hipGetLastError());
-    t_end(g);
-    return 0;
+    // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
+    // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
+    FuseParams fz{};
+    fz.tile_cnt = g->dfz_cnt; fz.total_cnt = g->dfz_cnt + g->fz_cap; fz.tile_best = g->dfz_best;
+    fz.tiles_total = (int)((R + CTILE - 1) / CTILE); fz.R_total = R;
+    fz.sigma2 = std::exp(2.0 * g->logsig); fz.beta = g->beta; fz.ap = ap;
+    fz.mu_out = d_mu; fz.var_out = d_var; fz.score_out = d_score; fz.best_out = d_best; fz.best_off = best_off;
+    // The fused finish counts arrivals in counters its last waves leave at zero.  If an earlier call failed between two of
+    // its launches they are not: every later call would then miss its "last arrival" and write no result.  So a call that
+    // did not enqueue all of its launches marks the counters dirty, and the next one clears them first.
+    if (g->fz_dirty) HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(g->fz_cap + 1 + 16) * sizeof(unsigned), g->stream));
+    g->fz_dirty = true;
+    const int rc = posterior_pass(g, dXs, R, fz);
+    if (rc == 0) g->fz_dirty = false;
+    return rc;
 }
 
 template <int DT>
 static void launch_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, const AcqParams& ap,
-                        double* d_grad, const double* UT, int S, const GradQ& gq) {
+                        double* d_grad, const double* UT, int S) {
     if constexpr (DT <= 16) {   // large batches: 4 candidates per workgroup share the observation stream
         if (r1 - r0 > SMALL_MAX) {
             LAUNCH_FAM(fam_low(hp), (k_grad_finish_tiled<DT, true>), (k_grad_finish_tiled<DT, false>), dim3((unsigned)((r1 - r0 + GC - 1) / GC)),
@@ -2198,22 +2121,17 @@ static void launch_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, 
         }
     }
     LAUNCH_FAM(fam_low(hp), (k_grad_finish<DT, true>), (k_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
-               g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad, g->dgparts, g->dgcount, gq);
+               g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad, g->dgparts, g->dgcount);
 }
 static int launch_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, const AcqParams& ap,
-                           double* d_grad, const double* UT, const GradQ& gq = GradQ{}) {
+                           double* d_grad, const double* UT) {
     // small batches: split the observations over S workgroups per candidate (see k_grad_finish)
     int S = 1;
     // (one 256-observation stride per workgroup -- (n + 255) / 256 splits -- was measured in round 4: 2 us of a 58 us pass, and the changed
     // summation order moved the ascent's end points enough to graze the SciPy check's KKT bound at N = 600: not kept)
     if (r1 - r0 <= SMALL_MAX) S = (int)std::min<int64_t>(16, std::max<int64_t>(1, g->n / 768));
     if (S > 1) CHK(ensure_small_counters(g));
-    if (g->d <= 2) launch_grad<2>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
-    else if (g->d <= 4) launch_grad<4>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
-    else if (g->d <= 8) launch_grad<8>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
-    else if (g->d <= 16) launch_grad<16>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
-    else if (g->d <= 32) launch_grad<32>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
-    else launch_grad<64>(g, dXs, r0, r1, hp, ap, d_grad, UT, S, gq);
+    dispatch_dt(g->d, [&](auto dt) { launch_grad<decltype(dt)::value>(g, dXs, r0, r1, hp, ap, d_grad, UT, S); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2226,36 +2144,14 @@ static int score_grad_core(bohip_gp* g, int acq_id, const double* acq_params, co
     CHK(ensure_fresh(g));
     CHK(ensure_score_scratch(g, R));
     CHK(one_time_kernel_setup());
-    AcqParams ap{acq_id, 0.0, 0.0};
-    if (acq_params) {
-        if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
-        if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
-    } else if (acq_id != BOHIP_ACQ_MAXMEAN) {
-        return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
-    }
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE;  // +TILE: head-room for tile-granular writes
     const int T = (int)(Npad / TILE);
     const KernelHyper hp = make_hyper(g);
     if (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) {  // the reference's default: a handful of L-BFGS restarts per call
-        // round 5: two MFMA kernels (kernels_small.hip): K*' + V' + posterior finish, U' + gradient
-        if (g_small_mfma) return small_pass_mfma(g, dXs, R, ap, g->dmu, g->dvar, d_score, nullptr, 0, d_grad);
-        // K*' -> V' = K*' W' rows (row-wise) -> U' = V' W rows -> ONE finishing kernel: q, mu, sigma^2, value and gradient
-        CHK(ensure_small_counters(g));
-        t_begin(g, "kstar");
-        CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp));
-        t_end(g);
-        t_begin(g, "small_V");
-        CHK(launch_rows_trimv(g, g->dW, N + 1, g->dKsT, (int)R, g->dApp, 0));
-        t_end(g);
-        g->q_tiles = 0;
-        t_begin(g, "small_U");
-        CHK(launch_rows_trimv(g, g->dWT, N, g->dApp, (int)R, g->dApp + (int64_t)APP_UT_ROW0 * g->ld, 1));
-        t_end(g);
-        t_begin(g, "grad");
-        GradQ gq{g->dApp, g->ld, std::exp(2.0 * g->logsig), g->beta, g->dmu, g->dvar, d_score, g->asc_go};
-        CHK(launch_grad_any(g, dXs, 0, R, hp, ap, d_grad, g->dApp + (int64_t)APP_UT_ROW0 * g->ld, gq));
-        t_end(g);
-        return 0;
+        // two MFMA kernels (kernels_small.hip): K*' + V' + posterior finish, U' + gradient
+        return small_pass_mfma(g, dXs, R, ap, g->dmu, g->dvar, d_score, nullptr, 0, d_grad);
     }
     const SplitPlan sp = split_plan(g, R);
     if (sp.nsl > 0) {
@@ -2575,12 +2471,11 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     }
     const KernelHyper hp = make_hyper(g);
     const double noise_var = std::exp(2.0 * g->lognoise);
-    const bool lo = fam_low(hp);
-#define DM(DTV) LAUNCH_FAM(lo, (k_dmll_parts<DTV, true>), (k_dmll_parts<DTV, false>), grid, dim3(256), 0, g->stream, g->dX, N, hp, \
-                           noise_var, g->dS, ld, g->dalpha, rpb, g->ddmll_parts)
-    if (g->d <= 2) DM(2); else if (g->d <= 4) DM(4); else if (g->d <= 8) DM(8); else if (g->d <= 16) DM(16);
-    else if (g->d <= 32) DM(32); else DM(64);
-#undef DM
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_dmll_parts<DT, true>), (k_dmll_parts<DT, false>), grid, dim3(256), 0, g->stream, g->dX, N, hp, noise_var,
+                   g->dS, ld, g->dalpha, rpb, g->ddmll_parts);
+    });
     const int nout = nl + 3;
     hipLaunchKernelGGL(k_dmll_final, dim3(nout), dim3(256), 0, g->stream, g->ddmll_parts, nblocks, NP, g->d, iso, g->dmll + 1);
     HIPCHK(hipGetLastError());
@@ -2671,9 +2566,7 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
         a.stamps = (trace && h0 == 0) ? d_stamps : nullptr;
         a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = g->d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
         const int64_t hc = std::min(Hc, H - h0);
-        if (g->d <= 2) CHK(fit_launch<2>(g, a, hc, lo)); else if (g->d <= 4) CHK(fit_launch<4>(g, a, hc, lo));
-        else if (g->d <= 8) CHK(fit_launch<8>(g, a, hc, lo)); else if (g->d <= 16) CHK(fit_launch<16>(g, a, hc, lo));
-        else if (g->d <= 32) CHK(fit_launch<32>(g, a, hc, lo)); else CHK(fit_launch<64>(g, a, hc, lo));
+        CHK(dispatch_dt(g->d, [&](auto dt) { return fit_launch<decltype(dt)::value>(g, a, hc, lo); }));
     }
     std::vector<long long> hpiv;
     HIPCHK(hipMemcpyAsync(mll, d_mll, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
@@ -2812,12 +2705,11 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     t_begin(g, "post_cov");
     CHK(posterior_mean(g, R));
     dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
-    const bool lo = fam_low(hp);
-#define PC(DTV) LAUNCH_FAM(lo, (k_post_cov<DTV, true>), (k_post_cov<DTV, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV, \
-                           g->cov_cap, g->dcov, R)
-    if (g->d <= 2) PC(2); else if (g->d <= 4) PC(4); else if (g->d <= 8) PC(8); else if (g->d <= 16) PC(16);
-    else if (g->d <= 32) PC(32); else PC(64);
-#undef PC
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
+                   g->cov_cap, g->dcov, R);
+    });
     HIPCHK(hipGetLastError());
     t_end(g);
     HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
@@ -2900,14 +2792,11 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
     const dim3 cgrid((unsigned)((Rp + 255) / 256), (unsigned)(Rp / 16));
     t_begin(g, "post_cov+jitter");
     CHK(posterior_mean(g, R));
-    {
-        const bool lo = fam_low(hp);
-#define SC(DTV) LAUNCH_FAM(lo, (k_sample_cov<DTV, true>), (k_sample_cov<DTV, false>), cgrid, dim3(256), 0, g->stream, g->dXs, R, Rp, hp, \
-                           g->dVV, g->cov_cap, g->dcov, g->cov_cap, ws.L, ld)
-        if (g->d <= 2) SC(2); else if (g->d <= 4) SC(4); else if (g->d <= 8) SC(8); else if (g->d <= 16) SC(16);
-        else if (g->d <= 32) SC(32); else SC(64);
-#undef SC
-    }
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_sample_cov<DT, true>), (k_sample_cov<DT, false>), cgrid, dim3(256), 0, g->stream, g->dXs, R, Rp, hp,
+                   g->dVV, g->cov_cap, g->dcov, g->cov_cap, ws.L, ld);
+    });
     hipLaunchKernelGGL(k_sample_diagmax, dim3(1), dim3(256), 0, g->stream, g->dcov, g->cov_cap, R, g->sj_scal);
     HIPCHK(hipGetLastError());
     t_end(g);
@@ -3405,7 +3294,8 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     if (!g || !Xs || !idx || !val || R < 1) return fail(BOHIP_E_ARG, "bad arguments");
     if (acq_id == BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, "select_batch: a posterior draw has no conditioned score");
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
-    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
     if (q < 1 || q > R) return fail(BOHIP_E_ARG, "select_batch: q must lie in 1..R (q = " + std::to_string(q) + ", R = " + std::to_string(R) + ")");
     if (fantasy != BOHIP_FANTASY_BELIEVER && fantasy != BOHIP_FANTASY_CONST)
         return fail(BOHIP_E_ARG, "select_batch: unknown fantasy " + std::to_string(fantasy));
@@ -3436,9 +3326,6 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     CHK(one_time_kernel_setup());
     CHK(ensure_batch(g, R, q));
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
-    AcqParams ap{acq_id, 0.0, 0.0};
-    if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
-    if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
     const int T = (int)(Npad / TILE);
     const KernelHyper hp = make_hyper(g);
@@ -3579,7 +3466,8 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
                          double* f_out, bohip_best* best, double* best_x, int64_t* evals_out) {
     if (!g || !lb || !ub || R < 0 || (R > 0 && !starts)) return fail(BOHIP_E_ARG, "bad arguments");
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
-    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
     if (evals_out) *evals_out = 0;
     if (R == 0) {
         if (best) { best->val = -INFINITY; best->idx = -1; }
@@ -3633,25 +3521,20 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
         AscWgParams pw{};
         pw.W = g->dW; pw.WT = g->dWT; pw.X = g->dX; pw.alpha = g->dalpha; pw.ld = g->ld; pw.N = g->n;
         pw.hp = make_hyper(g);
-        pw.ap = AcqParams{acq_id, 0.0, 0.0};
-        if (acq_params) {
-            if (acq_id != BOHIP_ACQ_MAXMEAN) pw.ap.p0 = acq_params[0];
-            if (acq_id == BOHIP_ACQ_MI) pw.ap.p1 = acq_params[1];
-        }
+        pw.ap = ap;
         pw.beta = g->beta; pw.st = st; pw.starts = g->asc_dio + 2 * d; pw.lb = g->asc_dio; pw.ub = g->asc_dio + d; pw.R = (int)R;
         pw.maxeval = (int)std::min<int64_t>(maxeval, 1 << 30); pw.ftol_rel = ftol_rel; pw.xtol_abs = xtol_abs; pw.first_step_scale = g_asc_first_step * span;
         pw.max_ticks = g->asc_maxtime > 0.0 ? (unsigned long long)(g->asc_maxtime * 1e8) : 0ull;
         pw.passes = st.accepted;
         t_begin(g, "ascent_wg");
         const bool lo = fam_low(pw.hp);
-#define AW(DTV) LAUNCH_FAM(lo, (k_ascent_wg<DTV, true>), (k_ascent_wg<DTV, false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw)
-        if (d <= 2) AW(2);
-        else if (d <= 4) AW(4);
-        else if (d <= 8) AW(8);
-        else if (pw.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_ascent.hip k_ascent_wg_logei16)
+        if (d > 8 && pw.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_ascent.hip k_ascent_wg_logei16)
             LAUNCH_FAM(lo, (k_ascent_wg_logei16<true>), (k_ascent_wg_logei16<false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-        else AW(16);
-#undef AW
+        else   // (use_wg: d <= 16)
+            dispatch_dt<16>(d, [&](auto dt) {
+                constexpr int DT = decltype(dt)::value;
+                LAUNCH_FAM(lo, (k_ascent_wg<DT, true>), (k_ascent_wg<DT, false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
+            });
         HIPCHK(hipGetLastError());
         t_end(g);
         // the packed result goes straight into the pinned host block (second half: the first holds the inputs): ~100 doubles written by one
@@ -3894,14 +3777,12 @@ int bohip_gp_direct_max(bohip_gp* g, int acq_id, const double* acq_params, const
 int bohip_acq_eval(int acq_id, const double* acq_params, int64_t n, const double* mu, const double* var, double* value,
                    double* dmu, double* dvar) {
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
-    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
     if (n < 0 || (n > 0 && (!mu || !var || !value)) || (!dmu != !dvar)) return fail(BOHIP_E_ARG, "bad arguments");
     if (n == 0) return 0;
     if (n > (int64_t)1 << 31) return fail(BOHIP_E_UNSUPPORTED, "acq_eval: more than 2^31 elements");
     if (bohip_device_count() <= 0) return fail(BOHIP_E_NODEVICE, "no HIP device visible; libbohip has no CPU fallback");
-    AcqParams ap{acq_id, 0.0, 0.0};
-    if (acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
-    if (acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
     const int nout = dmu ? 3 : 1;
     double* buf = nullptr;
     HIPCHK(hipMalloc(&buf, (size_t)n * 8 * (2 + nout)));
@@ -4113,9 +3994,9 @@ int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, 
     CHK(ensure_fresh(g));
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
-    AcqParams ap{acq_id, 0.0, 0.0};
-    if (acq_params && acq_id != BOHIP_ACQ_MAXMEAN) ap.p0 = acq_params[0];
-    if (acq_params && acq_id == BOHIP_ACQ_MI) ap.p1 = acq_params[1];
+    static const double no_params[2] = {0.0, 0.0};   // (a null acq_params is taken as zeros here)
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params ? acq_params : no_params, &ap));
     const int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
     if (m == 0 || R > PRUNE_R_MAX || R > g->chunk_now || (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) || split_plan(g, R).nsl > 0)
         return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
@@ -4138,7 +4019,6 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
     const int T = (int)(Npad / TILE);
     CHK(ensure_pieces(g, T, N));
     const std::vector<int> hv = rows_halves(g->hpieces);
-    if (path != 0 && hv.empty()) return fail(BOHIP_E_UNSUPPORTED, "row pieces k_trigemm_rows does not reproduce");
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     CHK(launch_kstar_any(g, g->dXs, 0, R, Npad, make_hyper(g)));
     std::vector<double> q((size_t)2 * T * Rpad), mu((size_t)Rpad);

@@ -234,19 +234,14 @@ __device__ unsigned long long g_trace[6 * 8192];   // per workgroup: wall start,
 #endif
 // ---- row pieces ------------------------------------------------------------------------------------------------------
 // A job is one ROW PIECE of W against one 64-wide candidate tile.  A piece is a whole 128-row tile (job length = its K extent:
-// rt + 1 units) or one 64-row HALF of a tile, run in the loop's half mode (both wave rows work on the 64 rows, even / odd
-// members of every contraction-index pair, partial sums added at the end): half the rows, so about half the time.
-// Why halves: with whole tiles only the launch ends raggedly -- the jobs in flight when the queue runs dry are 1 to 8 units
-// long (two co-resident workgroups: up to 160 us), CUs finish over an 80 us window and idle 5 % of the launch on average
-// (tools/trace_trigemm.py).  With the shortest third of the row tiles issued as halves the last jobs are a few units at most
-// (tools/sim_trigemm_tail.py: idle tail 3.2 % -> 0.4 % in the model).  The HOST lists the pieces heaviest-first
-// (trigemm_pieces in bohip.hip; the list depends on the number of row tiles and the position of the alpha row ONLY, never on
-// the batch: scores stay batch- and shard-independent) and the kernel reads its piece from that table.
-// Encoding: piece = rt | mode << 16;  mode 0 whole tile, 1 rows 0..63, 2 rows 64..127, 3 rows 0..63 of a tile whose rows 64..127
-// are all padding (the last tile when the alpha row sits in its upper half): no sibling piece exists.
-// q_part holds TWO partial sums per row tile (rows 0..63 and 64..127, [2 rt + h][r]); the finish adds (q[2t] + q[2t+1]) tile
-// by tile -- for a whole-tile job exactly the sum it used to store, so a list without halves reproduces the old bits.
-constexpr int PIECE_WHOLE = 0, PIECE_UPPER = 1, PIECE_LOWER = 2, PIECE_UPPER_SOLO = 3;
+// rt + 1 units) or, for a last tile whose live rows all sit in its upper half (rows 64..127 are padding), those 64 rows alone, run
+// in the loop's half mode (both wave rows work on the 64 rows, even / odd members of every contraction-index pair, partial sums
+// added at the end).  The HOST lists the pieces heaviest-first (trigemm_pieces in bohip.hip; the list depends on the number of row
+// tiles and the position of the alpha row ONLY, never on the batch: scores stay batch- and shard-independent) and the kernel reads
+// its piece from that table.  Encoding: piece = rt | mode << 16.
+// q_part holds TWO partial sums per row tile (rows 0..63 and 64..127, [2 rt + h][r]; a solo upper half writes zero for the lower
+// one); the finish adds (q[2t] + q[2t+1]) tile by tile.
+constexpr int PIECE_WHOLE = 0, PIECE_UPPER_SOLO = 3;
 
 // The sum of squares of one 64-row half of V for one candidate, shared by k_trigemm_sq and k_trigemm_rows so that the two cannot
 // differ in a bit (operand order, contraction of v * v + s): the lane of k = lane >> 4, b1 = (lane >> 3) & 1 adds the squares of
@@ -261,7 +256,6 @@ __device__ __forceinline__ double sq_tree(double s) {
 }
 
 // one job: row piece (rt, mode) of W against candidate tile ct of the chunk (all arguments wave-uniform)
-template <int KS>
 __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const double* __restrict__ W, int64_t ldw,
                                             const double* __restrict__ KsT, int64_t ldk, int NP, int64_t alpha_row,
                                             double* __restrict__ q_part, int64_t ldq, double* __restrict__ mu_raw, int64_t r_off,
@@ -272,17 +266,13 @@ __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const doub
     for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) acc[i][j] = 0.0;
-    const int h = mode == PIECE_LOWER ? 1 : 0;                 // which half the piece starts at
-    const int64_t row_base = (int64_t)rt * TILE + 64 * h;
+    const int64_t row_base = (int64_t)rt * TILE;
     // rows past alpha' are padding; a half piece has at most 64 live rows (-> the loop's half mode)
     const int active_rows = (int)min((int64_t)(mode == PIECE_WHOLE ? TILE : TILE / 2), alpha_row + 1 - row_base);
-    const int tri_kc = rt * (TILE / KC) + 4 * h;              // first chunk of the piece's triangular block
+    const int tri_kc = rt * (TILE / KC);                       // first chunk of the piece's triangular block
     const int kc_end = mode == PIECE_WHOLE ? (rt + 1) * (TILE / KC) : tri_kc + 4;
-    if constexpr (KS == 2)
-        gemm_tile_loop_glds3_ks<NJ, BOHIP_ABL, true>(W + row_base * ldw, ldw, KsT + (int64_t)ct * CW * ldk, ldk, 0,
-                                    kc_end, smem, acc, active_rows, tri_kc, tid);
-    else
-        gemm_tile_loop_glds3<NJ>(W + row_base * ldw, ldw, KsT + (int64_t)ct * CW * ldk, ldk, 0, kc_end, smem, acc, active_rows);
+    gemm_tile_loop_glds3_ks<NJ, BOHIP_ABL, true>(W + row_base * ldw, ldw, KsT + (int64_t)ct * CW * ldk, ldk, 0, kc_end, smem, acc,
+                                                 active_rows, tri_kc, tid);
     const int lane = tid & 63, wave = tid >> 6, wr = (wave & 3) >> 1, wc = wave & 1;
     __syncthreads();     // (the raw-barrier loops end on s_barrier; make the reuse of smem below explicit)
     double* red = smem;  // [2][CW]
@@ -311,9 +301,9 @@ __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const doub
     __syncthreads();
     if (tid < 2 * CW) {   // thread t < 64: the sum over the piece's first 64 rows; t >= 64: over rows 64..127 of a whole tile
         const int hh = tid >> 6, c = tid & (CW - 1);
-        double* dst = q_part + (int64_t)(2 * rt + (mode == PIECE_WHOLE ? hh : h)) * ldq + r_off + (int64_t)ct * CW + c;
+        double* dst = q_part + (int64_t)(2 * rt + (mode == PIECE_WHOLE ? hh : 0)) * ldq + r_off + (int64_t)ct * CW + c;
         if (mode == PIECE_WHOLE || hh == 0) __hip_atomic_store(dst, red[hh * CW + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else if (mode == PIECE_UPPER_SOLO) __hip_atomic_store(dst + ldq, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // no sibling: its slot is zero
+        else __hip_atomic_store(dst + ldq, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // solo upper half: the lower one's slot is zero
     }
     if (fz.tile_cnt != nullptr) {
         __shared__ int s_last;
@@ -326,13 +316,13 @@ __device__ __forceinline__ void trigemm_job(int rt, int mode, int ct, const doub
     }
 }
 
-template <int KS>  // 1: 4 waves; 2: 8 waves, contraction index halved inside the workgroup (default)
-__global__ __launch_bounds__(KS * GEMM_THREADS, 2 * KS) void k_trigemm_sq(const double* __restrict__ W, int64_t ldw,
-                                                                const double* __restrict__ KsT, int64_t ldk,
-                                                                const int* __restrict__ pieces, int NP, int CT, int64_t alpha_row,
-                                                                double* __restrict__ q_part, int64_t ldq,
-                                                                double* __restrict__ mu_raw, int64_t r_off,
-                                                                double* __restrict__ VT, int64_t ldv, FuseParams fz) {
+// 8 waves: the contraction index is halved inside the workgroup (gemm_tile_loop_glds3_ks)
+__global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_trigemm_sq(const double* __restrict__ W, int64_t ldw,
+                                                                  const double* __restrict__ KsT, int64_t ldk,
+                                                                  const int* __restrict__ pieces, int NP, int CT, int64_t alpha_row,
+                                                                  double* __restrict__ q_part, int64_t ldq,
+                                                                  double* __restrict__ mu_raw, int64_t r_off,
+                                                                  double* __restrict__ VT, int64_t ldv, FuseParams fz) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
 #if BOHIP_TRACE
     const unsigned long long t_start = wall_clock64(), c_start = clock64();
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(KS * GEMM_THREADS, 2 * KS) void k_trigemm_sq(const 
     // their ratio is the clock the chip sustained UNDER THIS KERNEL (MI355X clocks to its power budget: ~2.0 of 2.4 GHz here)
     __shared__ unsigned long long s_clk[2];
     if (fz.clk != nullptr && blockIdx.x % 33 == 0 && threadIdx.x == 0) { s_clk[0] = clock64(); s_clk[1] = wall_clock64(); }
-    trigemm_job<KS>(piece & 0xffff, piece >> 16, ct, W, ldw, KsT, ldk, NP, alpha_row, q_part, ldq, mu_raw, r_off, VT, ldv, fz, smem,
+    trigemm_job(piece & 0xffff, piece >> 16, ct, W, ldw, KsT, ldk, NP, alpha_row, q_part, ldq, mu_raw, r_off, VT, ldv, fz, smem,
                     (int)threadIdx.x);
     if (fz.clk != nullptr && blockIdx.x % 33 == 0 && threadIdx.x == 0) {
         atomicAdd(fz.clk, (unsigned long long)clock64() - s_clk[0]);
@@ -556,60 +546,6 @@ __global__ __launch_bounds__(256) void k_score(const double* __restrict__ q_part
     if (block_best) {
         block_argmax(v, idx, sh);
         if (threadIdx.x == 0) { block_best[blockIdx.x].val = idx >= 0 ? v : -INFINITY; block_best[blockIdx.x].idx = idx; }
-    }
-}
-
-// Small batches (R <= 256, row-wise posterior): one workgroup per candidate r adds q[r] = sum_j V'[r][j]^2 in a fixed
-// order and takes mu_raw[r] from the alpha row; the LAST workgroup to finish then does what k_score + k_argmax_final do
-// for a large batch (same formulas, same operation order) for all R candidates -- two launches less per call, which
-// at this size are a fifth of its latency.  The arrival counter is left at zero.
-__global__ __launch_bounds__(256) void k_small_finish(const double* __restrict__ VT, int64_t ldv, int64_t N, int R,
-                                                      double* __restrict__ q, double* __restrict__ mu_raw,
-                                                      unsigned* __restrict__ counter, double sigma2, double beta,
-                                                      AcqParams ap, double* __restrict__ mu_out,
-                                                      double* __restrict__ var_out, double* __restrict__ score_out,
-                                                      Best* __restrict__ best_out, long long idx_off) {
-#pragma clang fp contract(off)
-    __shared__ double red[256];
-    __shared__ Best sh[4];
-    __shared__ int is_last;
-    const int r = blockIdx.x;
-    const double* v = VT + (int64_t)r * ldv;
-    double s = 0.0;
-    for (int64_t j = threadIdx.x; j < N; j += 256) s += v[j] * v[j];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        // agent-scope stores + an explicit wait instead of __threadfence(): the fence is an L2 write-back on this chip (7-60 us for
-        // a device-wide hand-over, tools/ubench_gridbar.hip), the write-through stores cost nothing beside it
-        __hip_atomic_store(q + r, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mu_raw + r, v[N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        is_last = atomicAdd(counter, 1u) == (unsigned)(R - 1);
-    }
-    __syncthreads();
-    if (!is_last) return;
-    if (threadIdx.x == 0) *counter = 0u;
-    double f_best = -INFINITY;
-    long long idx = -1;
-    if ((int)threadIdx.x < R) {
-        const int c = threadIdx.x;
-        double s2 = sigma2 - __hip_atomic_load(q + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
-        const double mu = beta + __hip_atomic_load(mu_raw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (mu_out) mu_out[c] = mu;
-        if (var_out) var_out[c] = s2;
-        const double f = acq_eval(ap, mu, s2);
-        if (score_out) score_out[c] = f;
-        if (f > -INFINITY) { f_best = f; idx = c; }  // false for NaN and -Inf
-    }
-    if (best_out) {
-        block_argmax(f_best, idx, sh);
-        if (threadIdx.x == 0) { best_out->val = idx >= 0 ? f_best : -INFINITY; best_out->idx = idx >= 0 ? idx + idx_off : -1; }
     }
 }
 
@@ -961,7 +897,7 @@ __global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
 // k_trigemm_sq runs a row piece against a 64-wide candidate tile as ONE job: for round 1 (64 candidates) that is one workgroup per
 // row tile, and the job of the last tiles (K = N: ~190 chunks of 16) runs alone on one CU for ~0.2 ms.  Here a workgroup owns one
 // 64-row HALF of a row tile against RS_COLS listed candidates and walks the half's whole contraction extent, so a round spreads over
-// (halves x candidate groups) workgroups.  Every element of V comes out bit for bit as in k_trigemm_sq<2>: an element of an
+// (halves x candidate groups) workgroups.  Every element of V comes out bit for bit as in k_trigemm_sq: an element of an
 // MFMA's result depends on its own A row and B column only, so what changes is which rows and columns share an instruction, never an element's
 // chain:
 //   * v_mfma_f64_4x4x4 k-slot k of chunk kc carries contraction index 16 kc + 8 h + 2 k (the pair's even member), the next
@@ -971,8 +907,6 @@ __global__ __launch_bounds__(256) void k_prune_finish(PruneFinish pf) {
 //   * PIECE_UPPER_SOLO (the loop's half mode): kc < 8 rt + 4, chains e_h (even members) and o_h (odd), v = (e0 + e1) + (o0 + o1);
 //   * an 8-row group G of the tile skips chunk kc >= tri_kc = 8 rt when G < 2 (kc - tri_kc) + h (chunk_mma's skip);
 //   * q of the half: sq_step over the rows of a lane in k_trigemm_sq's accumulator layout, then sq_tree (shared helpers).
-// Only the product build's pieces (whole tiles, the solo last half) and the 8-wave loop are reproduced: under the measurement
-// knobs (halved tiles, BOHIP_KS8=0) the pruned pass keeps k_trigemm_sq for its rounds.
 // Sizing: a workgroup is 8 waves (h x four 16-row quarters: two waves per SIMD) against RS_COLS = 8 candidates, 2 accumulator chains
 // of 8 x 8 per wave, 4 MFMAs per wave and chunk; round 1 of 64 candidates at T = 24 is 41 halves x 8 groups = 328 workgroups, two
 // to a CU with 7 buffers of 9 KB, one with the RS_DEPTH = 8 kept (72 KB beside 12 KB of static LDS).  The operands come by LDS-DMA
@@ -1297,52 +1231,34 @@ __global__ __launch_bounds__(256) void k_acq_eval(AcqParams ap, int64_t n, const
     if (dmu) acq_partials(ap, mu[i], var[i], dmu[i], dvar[i]);
 }
 
-// Small batches: the posterior finish (q = sum V^2, mu, sigma^2, acquisition value: what k_small_finish does) rides on this kernel --
-// one launch (~7 us, whatever it does) less per value+gradient pass.  VT == nullptr: off (mu / var come from the caller).
-// q = sum_j V'[r][j]^2, sigma^2 and mu in EXACTLY the operations and order of k_small_finish (256 lane-strided sums, halving tree,
-// no contraction): the value path and the gradient path agree on the scores bit for bit (tests/test_parity_gpu.py test_score_grad_vs_oracle)
-__device__ __forceinline__ double sumsq_like_small_finish(const double* __restrict__ v, int64_t N, double* red) {
-#pragma clang fp contract(off)
-    double s = 0.0;
-    for (int64_t j = threadIdx.x; j < N; j += 256) s += v[j] * v[j];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
-}
+// The posterior of one candidate from q = sum_j V'[r][j]^2 and the alpha row's product mu_raw, without contraction: the reference's
+// clamp and formulas, shared by the small-batch kernels (kernels_small.hip) so that the value path and the gradient path agree on
+// the scores bit for bit (tests/test_parity_gpu.py test_score_grad_vs_oracle)
 __device__ __forceinline__ void posterior_like_small_finish(double sigma2, double beta, double q, double mu_raw, double& mu, double& s2) {
 #pragma clang fp contract(off)
     s2 = sigma2 - q;
     if (s2 < 0.0) s2 = 0.0;  // predict_f: max(sigma2, 0)
     mu = beta + mu_raw;
 }
-struct GradQ {
-    const double* VT;   // [R][ldv]  V' rows; entry N of a row is mu - beta
-    int64_t ldv;
-    double sigma2, beta;
-    double *mu_out, *var_out, *score_out;
-    const unsigned* go;   // not null: return at once when the word is 0 (free-running ascent, see AscentState::ticket)
-};
+// Waves per SIMD every instantiation has had, as its second launch bound: left free, the scheduler interleaves the coordinates'
+// accumulate chains of the SE / Matern 5/2 body at 22 VGPRs more (DT = 8: 118 for 96) and one wave fewer.
+constexpr int grad_finish_waves(int DT, bool LOW) { return DT <= 2 ? 8 : DT <= 4 ? 7 - LOW : DT <= 8 ? 5 - LOW : DT <= 16 ? 3 : DT <= 32 ? 2 : 1; }
 template <int DT, bool LOW>
-__global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ X, int64_t N,
+__global__ __launch_bounds__(256, grad_finish_waves(DT, LOW)) void k_grad_finish(const double* __restrict__ X, int64_t N,
                                                      const double* __restrict__ Xs, int64_t r_begin, int64_t r_end,
                                                      KernelHyper hp, const double* __restrict__ alpha,
                                                      const double* __restrict__ UT, int64_t ldu,
                                                      const double* __restrict__ mu, const double* __restrict__ var,
                                                      AcqParams ap, double* __restrict__ grad,
-                                                     double* __restrict__ parts, unsigned* __restrict__ counters, GradQ gq) {
+                                                     double* __restrict__ parts, unsigned* __restrict__ counters) {
     // workgroup (r, sp): candidate r, observations [sp len, (sp + 1) len): 256 threads stride them, 2d sums reduced in
     // a fixed order.  gridDim.y = 1 for large batches (one workgroup per candidate is plenty); for a handful of
     // candidates the observations are split over gridDim.y workgroups (a single workgroup walking N = 10^4
     // observations is latency-bound: 140 us), the LAST one to finish adds the partial sums in split order -- the
     // result depends on (N, gridDim.y) only, never on the batch -- and leaves the counter at zero for the next call.
-    __shared__ double red[4][2 * DT + 2];
+    __shared__ double red[4][2 * DT];
     __shared__ int is_last;
-    if (gq.go && *gq.go == 0u) return;
-    constexpr int PS = 2 * DT + 2;   // partial record of one split: 2 DT gradient sums + the split's part of q
+    constexpr int PS = 2 * DT;   // partial record of one split: 2 DT gradient sums
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = r_begin + blockIdx.x;
     if (r >= r_end) return;
@@ -1354,7 +1270,6 @@ __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ 
 #pragma unroll
     for (int k = 0; k < DT; ++k) { gm[k] = 0.0; gv[k] = 0.0; }
     const double* u = UT + (r - r_begin) * ldu;
-    const double* vq = gq.VT ? gq.VT + (r - r_begin) * gq.ldv : nullptr;
     for (int64_t j = j_lo + threadIdx.x; j < j_hi; j += 256) {
         double t[DT], rr = 0.0;
 #pragma unroll
@@ -1389,25 +1304,19 @@ __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ 
             if (lane == 0) { red[wave][2 * k] = a; red[wave][2 * k + 1] = b; }
         }
     __syncthreads();
-    // q = sum_j V'[r][j]^2 in k_small_finish's exact order: ONE workgroup adds it -- the only one, or split 0, which does so BEFORE it
-    // counts itself in (round 3 left it to the last arriver: a pass over the row + a tree BEHIND the counter, ~4 us of the critical path)
-    double q_all = 0.0;
-    __shared__ double redq[256];
-    if (vq && (S == 1 || sp == 0)) q_all = sumsq_like_small_finish(vq, N, redq);
     if (S > 1) {
         double* mine = parts + ((int64_t)blockIdx.x * S + sp) * PS;
         if (threadIdx.x < 2 * d)
             __hip_atomic_store(mine + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (vq && sp == 0 && threadIdx.x == 0) __hip_atomic_store(mine + 2 * DT, q_all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (agent-scope stores + this wait, not __threadfence(): see k_small_finish)
+        // agent-scope stores + an explicit wait instead of __threadfence(): the fence is an L2 write-back on this chip (7-60 us for
+        // a device-wide hand-over, tools/ubench_gridbar.hip), the write-through stores cost nothing beside it
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) is_last = atomicAdd(&counters[blockIdx.x], 1u) == (unsigned)(S - 1);
         __syncthreads();
         if (!is_last) return;
         if (threadIdx.x == 0) counters[blockIdx.x] = 0u;
-        if (vq) q_all = __hip_atomic_load(parts + (int64_t)blockIdx.x * S * PS + 2 * DT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x < d) {
         const int k = threadIdx.x;
@@ -1424,18 +1333,7 @@ __global__ __launch_bounds__(256) void k_grad_finish(const double* __restrict__ 
             b = (red[0][2 * k + 1] + red[1][2 * k + 1]) + (red[2][2 * k + 1] + red[3][2 * k + 1]);
         }
         double dmu, ds2;
-        double m, v;
-        if (vq) {   // the posterior finish of k_small_finish, per candidate: the reference's clamp and formulas
-            posterior_like_small_finish(gq.sigma2, gq.beta, q_all, vq[N], m, v);
-            if (k == 0) {
-                if (gq.mu_out) gq.mu_out[r] = m;
-                if (gq.var_out) gq.var_out[r] = v;
-                if (gq.score_out) gq.score_out[r] = acq_eval(ap, m, v);
-            }
-        } else {
-            m = mu[r];
-            v = var[r];
-        }
+        const double m = mu[r], v = var[r];
         acq_partials(ap, m, v, dmu, ds2);
         // a clamped variance (sigma^2 == 0 exactly) has zero gradient, like max(., 0) under ForwardDiff
         grad[r * d + k] = dmu * a + (v > 0.0 ? ds2 * (-2.0 * b) : 0.0);

@@ -2,8 +2,8 @@
 // acquire_max, reference src/acquisition.jl:4-6,54-68, each evaluation a value + gradient of <= 16 candidates) as TWO kernels:
 //
 //   k_small_v   K*' assembly (in the prologue of the tiles that need it)  ->  V' = K*' W'  ->  q = sum v^2, mu, sigma^2, the
-//               acquisition value and the arg-max of the batch                               (replaces k_kstar + k_trimv_stream + k_small_finish)
-//   k_small_u   U' = V' W  ->  the analytic gradient of the acquisition                     (replaces k_trimv_stream + k_grad_finish)
+//               acquisition value and the arg-max of the batch                               (round 4: k_kstar + k_trimv_stream + a finishing kernel)
+//   k_small_u   U' = V' W  ->  the analytic gradient of the acquisition                     (round 4: k_trimv_stream + k_grad_finish)
 //
 // Round 4's pass was five kernels whose dependent latency chains abutted (kstar 5 us, V' 15.4, U' 17.2, gradient 15.6 at N = 3000): each
 // triangular product was a barrier-stepped LDS-DMA ring at 0.35 of the plain read rate of W, and the gradient kernel a 15 us chain for
@@ -269,7 +269,7 @@ __device__ __forceinline__ bool small_publish_combine(const SmallCommon& sc, int
     return true;
 }
 
-// The posterior finish of one pass of 16 candidates (k_small_finish's formulas): q = sum of the column blocks' records in block order,
+// The posterior finish of one pass of 16 candidates (posterior_like_small_finish's formulas): q = sum of the column blocks' records in block order,
 // mu - beta likewise, sigma^2 = max(s_f^2 - q, 0), the acquisition value.  The records are fetched by all threads at once (one round
 // trip), then added by one thread per slot from LDS.  buf: >= 4096 doubles of LDS.  Thread `slot` (< 16) returns (f, candidate index) and
 // (mu, sigma^2); threads 64 + slot return (mu, sigma^2) too.

@@ -248,11 +248,10 @@ static int mgp_exchange(bohip_mgp* m, int64_t S, Best* out) {
     return 0;
 }
 
-static int mgp_acq_params(int acq_id, const double* acq_params, AcqParams* ap) {
+static int mgp_acq_params(int acq_id, const double* acq_params) {   // (checked before any device works; score_core unpacks them per shard)
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
-    if (acq_id != BOHIP_ACQ_MAXMEAN && !acq_params) return fail(BOHIP_E_ARG, "acq_params required for this acquisition");
-    (void)ap;
-    return 0;
+    AcqParams ap;
+    return make_acq(acq_id, acq_params, &ap);
 }
 
 // batch_hint for the duration of a sharded call, restored on every exit path (an early error return used to leave the replica --
@@ -408,7 +407,7 @@ int bohip_mgp_refit(bohip_mgp* m) {
 int bohip_mgp_score(bohip_mgp* m, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* score,
                     bohip_best* best) {
     if (!m || R < 0 || (R > 0 && !Xs) || !best) return fail(BOHIP_E_ARG, "bad arguments");
-    CHK(mgp_acq_params(acq_id, acq_params, nullptr));
+    CHK(mgp_acq_params(acq_id, acq_params));
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
     CHK(mgp_ensure_records(m, 1));
     const int64_t G = (int64_t)m->nd * m->spd;
@@ -451,7 +450,7 @@ int bohip_mgp_set_candidates(bohip_mgp* m, const double* Xs, int64_t R) {
 
 int bohip_mgp_score_resident(bohip_mgp* m, int acq_id, const double* acq_params, bohip_best* best) {
     if (!m || !best) return fail(BOHIP_E_ARG, "bad arguments");
-    CHK(mgp_acq_params(acq_id, acq_params, nullptr));
+    CHK(mgp_acq_params(acq_id, acq_params));
     const int64_t R = m->R_res;
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
     CHK(mgp_ensure_records(m, 1));
@@ -503,7 +502,7 @@ int bohip_mgp_acquire_max(bohip_mgp* m, int acq_id, const double* acq_params, co
                           double xtol_abs, double* x_out, double* f_out, bohip_best* best, double* best_x,
                           int64_t* evals_out) {
     if (!m || !lowerbounds || !upperbounds || R < 0 || (R > 0 && !starts) || !best) return fail(BOHIP_E_ARG, "bad arguments");
-    CHK(mgp_acq_params(acq_id, acq_params, nullptr));
+    CHK(mgp_acq_params(acq_id, acq_params));
     if (evals_out) *evals_out = 0;
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
     CHK(mgp_ensure_records(m, 1));

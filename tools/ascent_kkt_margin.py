@@ -1,7 +1,7 @@
 """How often does the device ascent (bohip_gp_acquire_max, free-running driver) give a start point up at a point that is NOT a KKT point of
 the oracle's objective?  The N = 600 case of tests/test_parity_gpu.py::test_device_ascent_against_scipy_lbfgsb_on_the_oracle over several
 start seeds; per seed the largest |projected gradient| / max |gradient at the starts| per acquisition and the number of start points above
-the test's 2e-4.  Run with BOHIP_SMALL_MFMA=0 for round 4's five-kernel pass."""
+the test's 2e-4."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
