@@ -9,7 +9,7 @@ from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, NoModelOptimizer, optimizemodel_,
@@ -19,7 +19,7 @@ from .utils import (ScaledSobolIterator, ScaledLHSIterator, latin_hypercube_samp
 
 GPE = ElasticGPE.from_data
 
-__all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "ProbabilityOfImprovement", "UpperConfidenceBound", "ThompsonSamplingSimple",
+__all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGradient", "ProbabilityOfImprovement", "UpperConfidenceBound", "ThompsonSamplingSimple",
            "MutualInformation", "boptimize_", "MAPGPOptimizer", "NoModelOptimizer", "Min", "Max", "BrochuBetaScaling",
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
            "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",

@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -25,6 +25,7 @@ UNIQUE_ID_BYTES = 128
 FANTASY_BELIEVER, FANTASY_CONST, BATCH_RAISE_TAU = 0, 1, 1   # bohip_gp_select_batch
 PATHS_S_MAX, PATHS_M_MAX = 4096, 16384                       # bohip_gp_paths_draw
 FIT_NMAX = 512                                               # bohip_gp_mll_grad_batch
+KG_RMAX = 8192                                               # bohip_gp_kg / bohip_kg_lines (BOHIP_KG_RMAX)
 
 
 class Best(C.Structure):
@@ -151,6 +152,13 @@ ACQ_SIGNATURES = {
     "bohip_acq_eval": (C.c_int, [C.c_int, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp]),
 }
 
+# every symbol include/bohip_kg.h declares (the knowledge gradient over a candidate set, exact, on the device)
+_i32p = C.POINTER(C.c_int32)
+KG_SIGNATURES = {
+    "bohip_gp_kg": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, _dp, _i32p, _dp, C.POINTER(Best)]),
+    "bohip_kg_lines": (C.c_int, [_gp, _dp, _dp, C.c_int64, C.c_int64, _dp, _i32p]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -206,7 +214,7 @@ def load():
     _one_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
-                              + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items())):
+                              + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

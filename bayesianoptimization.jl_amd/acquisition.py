@@ -119,6 +119,16 @@ class LogExpectedImprovement(AbstractAcquisition):
     params = ProbabilityOfImprovement.params
 
 
+class KnowledgeGradient(AbstractAcquisition):
+    """The knowledge gradient over a candidate set (include/bohip_kg.h; Frazier, Powell & Dayanik 2009): the expected
+    rise of max_j mu_j over the candidates after ONE noisy observation at the point, computed exactly on the device (model.kg).  An
+    extension: the reference has no such type, and no default uses it.  It is not a functor of one point's (mu, sigma^2) -- it ranks
+    a point by what observing it would teach about the optimum -- so it has no parameters, no gradient and no place in score /
+    ascend / DIRECT: acquisitionfunction takes a d x R candidate matrix, and acquire_max takes the arg-max over `maxeval`
+    Latin-hypercube candidates per restart (each set evaluated against itself)."""
+    acq_id = "KG"
+
+
 def _erfc(x):
     from scipy.special import erfc                             # (vectorised; math.erfc is its scalar form)
 
@@ -192,6 +202,15 @@ class MutualInformation(AbstractAcquisition):                 # :126-141
 
 def acquisitionfunction(a, model, rng=None):
     """:4-9, :108, :111.  x (vector or d x R matrix) -> score(s); batches run fused on the device."""
+    if isinstance(a, KnowledgeGradient):
+        def kg(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("KnowledgeGradient needs a candidate set, a d x R matrix: the knowledge gradient of one point "
+                                 "against itself is 0")
+            return model.kg(x).values
+
+        return kg
     if isinstance(a, ThompsonSamplingSimple):
         return lambda x: myrand(model, x, rng)
     if isinstance(a, MaxMean):
@@ -207,6 +226,8 @@ def acquisitionfunction(a, model, rng=None):
 
 # ---- src/acquisition.jl ----------------------------------------------------------------------------------
 def defaultoptions(model_type, acq_type):                    # :4-9
+    if isinstance(acq_type, type) and issubclass(acq_type, KnowledgeGradient):
+        return dict(method="LD_LBFGS", restarts=1, maxeval=1024)   # (1024: the smallest candidate chunk a model can have)
     if isinstance(acq_type, type) and issubclass(acq_type, ThompsonSamplingSimple):
         return dict(method="GN_DIRECT_L", restarts=1, maxeval=2000)
     return dict(method="LD_LBFGS", restarts=10, maxeval=2000)
@@ -502,6 +523,23 @@ def _acquire_max_pathwise(model, lb, ub, method, restarts, maxeval, maxtime, opt
     return maxf, maxx
 
 
+def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng):
+    """KnowledgeGradient: a candidate-set acquisition without a gradient.  Every restart takes `maxeval` Latin-hypercube candidates,
+    evaluates the knowledge gradient of each against the whole set in ONE model.kg call (E = R) and takes the device's arg-max.
+    The first maximum over the restarts wins (strict '>')."""
+    if not hasattr(model, "kg"):
+        raise NotImplementedError(f"{type(model).__name__} has no kg")
+    maxf, maxx = -math.inf, lb.copy()
+    for _ in range(restarts):
+        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+        res = model.kg(xs)
+        if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
+            maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
+
+
 def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
     """src/acquisition.jl:48-68: R Latin-hypercube starts (utils.jl:96-120), local search from each, keep the
     best under strict '>' (first maximum wins).  Returns (maxf, maxx).
@@ -521,6 +559,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     maxf, maxx = -math.inf, lb.copy()                             # :55-56
     if model.nobs == 0 or restarts <= 0:
         return maxf, maxx
+    if isinstance(a, KnowledgeGradient):                          # (`method` has nothing to select between: accepted, not used)
+        return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31
     if bool(opts.get("pathwise", False)):
         if not isinstance(a, ThompsonSamplingSimple):

@@ -19,6 +19,7 @@
 #include "../../include/bohip_fit.h"
 #include "../../include/bohip_qei.h"
 #include "../../include/bohip_acq.h"
+#include "../../include/bohip_kg.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -26,6 +27,7 @@
 #include "kernels_batch.hip"   // (after the scoring kernels: shares their functors and arg-max order)
 #include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
 #include "kernels_qei.hip"     // (after the scoring kernels: their arg-max order)
+#include "kernels_kg.hip"      // (after the scoring kernels: their arg-max order; acq_log.h's forms of h)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_ascent.hip"
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
@@ -185,6 +187,9 @@ struct bohip_gp {
     // greedy q-EI over the resident draws (bohip_gp_qei_batch / _qei_select): ONE block [m | partials | records | gain | idx | words]
     char* qei_ws = nullptr;
     size_t qei_bytes = 0;
+    // knowledge gradient (bohip_gp_kg / bohip_kg_lines): ONE block [kg | record | nseg | a | B], the last two for the caller's lines only
+    char* kg_ws = nullptr;
+    size_t kg_bytes = 0;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -474,6 +479,8 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_trimv_stream<TRIMV_D>, hipFuncAttributeMaxDynamicSharedMemorySize, trimv_lds_bytes(TRIMV_D)));
     HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
     HIPCHK(hipFuncSetAttribute((const void*)k_path_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_mfma_lds_bytes(DMAX)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_kg<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kg_lds_bytes(KG_RMAX)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_kg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kg_lds_bytes(KG_RMAX)));
     // The library's switches (README "Environment"): the forms of the factorisation the tests select, the bound of its
     // waits, the ascent drivers, the small-batch pass.  Everything else that used to be read here is a constant now; the
     // sweeps under tools/ that vary those constants run against csrc/abl/libbohip_dev.so (read_dev_knobs below).
@@ -2294,6 +2301,7 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->sj_info) hipFree(g->sj_info);
     if (g->sj_part) hipFree(g->sj_part);
     if (g->qei_ws) hipFree(g->qei_ws);
+    if (g->kg_ws) hipFree(g->kg_ws);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -2956,6 +2964,109 @@ int bohip_gp_qei_select(bohip_gp* g, const double* samples, int64_t S, int64_t R
     CHK(ensure_sample_matrix(g, (size_t)S * R));
     HIPCHK(hipMemcpyAsync(g->sjF, samples, (size_t)S * R * 8, hipMemcpyHostToDevice, g->stream));
     CHK(qei_rounds(g, w, R, S, tau, q, idx, gain));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+// ---- the knowledge gradient over a candidate set (kernels_kg.hip, include/bohip_kg.h) ------------------------------
+static_assert(KG_RMAX == BOHIP_KG_RMAX, "the kernel's LDS plan and the header agree");
+struct KgWs {
+    double* kg;     // [E]
+    Best* best;
+    int* nseg;      // [E]
+    double* a;      // [R]      the caller's lines only
+    double* B;      // [E][R]
+};
+static int kg_check(const char* who, const void* p0, const void* p1, const void* kg, int64_t R, int64_t E) {
+    const std::string pre = std::string(who) + ": ";
+    if (R < 1 || E < 1) return fail(BOHIP_E_ARG, pre + "R and E must be at least 1");
+    if (E > R) return fail(BOHIP_E_ARG, pre + "E exceeds the number of candidates R");
+    if (!p0 || !p1 || !kg) return fail(BOHIP_E_ARG, pre + "null argument");
+    return 0;
+}
+static int kg_check_size(const char* who, int64_t R) {
+    if (R > BOHIP_KG_RMAX)
+        return fail(BOHIP_E_UNSUPPORTED, std::string(who) + ": R exceeds BOHIP_KG_RMAX (" + std::to_string(BOHIP_KG_RMAX) +
+                                             "): a point's lines live in one workgroup's LDS");
+    return 0;
+}
+static int ensure_kg(bohip_gp* g, int64_t R, int64_t E, bool lines, KgWs* w) {
+    const size_t o_best = (size_t)E * 8, o_nseg = o_best + sizeof(Best), o_a = round_up(o_nseg + (size_t)E * 4, 16),
+                 o_B = o_a + (lines ? (size_t)R * 8 : 0), need = o_B + (lines ? (size_t)E * R * 8 : 0);
+    if (g->kg_bytes < need) {
+        if (g->kg_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->kg_ws)); g->kg_ws = nullptr; }
+        const size_t cap = std::max(need, g->kg_bytes + g->kg_bytes / 2);
+        g->kg_bytes = 0;
+        HIPCHK(hipMalloc(&g->kg_ws, cap));
+        g->kg_bytes = cap;
+    }
+    char* b = g->kg_ws;
+    w->kg = reinterpret_cast<double*>(b);
+    w->best = reinterpret_cast<Best*>(b + o_best);
+    w->nseg = reinterpret_cast<int*>(b + o_nseg);
+    w->a = reinterpret_cast<double*>(b + o_a);
+    w->B = reinterpret_cast<double*>(b + o_B);
+    return 0;
+}
+// the march of every evaluation point and the record, on the handle's stream, and the small copies behind them (no synchronisation)
+static int kg_march(bohip_gp* g, bool scale, const KgWs& w, const double* da, const double* dB, int64_t ldb, int64_t R, int64_t E, double nu,
+                    double* kg, int32_t* nseg, bohip_best* best) {
+    static_assert(sizeof(int) == sizeof(int32_t), "nseg crosses as int32_t");
+    t_begin(g, "kg");
+    const dim3 grid((unsigned)E), block(KG_THREADS);
+    if (scale) hipLaunchKernelGGL(k_kg<true>, grid, block, kg_lds_bytes(R), g->stream, da, dB, ldb, (int)R, nu, w.kg, w.nseg);
+    else hipLaunchKernelGGL(k_kg<false>, grid, block, kg_lds_bytes(R), g->stream, da, dB, ldb, (int)R, nu, w.kg, w.nseg);
+    if (best) hipLaunchKernelGGL(k_kg_best, dim3(1), dim3(256), 0, g->stream, w.kg, (int)E, w.best);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    HIPCHK(hipMemcpyAsync(kg, w.kg, (size_t)E * 8, hipMemcpyDeviceToHost, g->stream));
+    if (nseg) HIPCHK(hipMemcpyAsync(nseg, w.nseg, (size_t)E * 4, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    return 0;
+}
+
+int bohip_gp_kg(bohip_gp* g, const double* Xs, int64_t R, int64_t E, double* kg, int32_t* nseg, double* mu, bohip_best* best) {
+    CHK(kg_check("kg", g, Xs, kg, R, E));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(kg_check_size("kg", R));
+    HIPCHK(hipSetDevice(g->device));
+    KgWs w{};
+    CHK(ensure_kg(g, R, E, false, &w));
+    CHK(posterior_vv(g, Xs, R, "kg"));
+    const KernelHyper hp = make_hyper(g);
+    t_begin(g, "post_cov");
+    CHK(posterior_mean(g, R));
+    // Sigma as bohip_gp_predict_cov computes it, with the leading dimension of the buffer (a multiple of 128): every row starts on
+    // a 16-byte boundary for k_kg's loads
+    dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
+                   g->cov_cap, g->dcov, g->cov_cap);
+    });
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    const double nu = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
+    CHK(kg_march(g, true, w, g->dmu, g->dcov, g->cov_cap, R, E, nu, kg, nseg, best));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_kg_lines(bohip_gp* g, const double* a, const double* B, int64_t R, int64_t E, double* kg, int32_t* nseg) {
+    CHK(kg_check("kg_lines", a, B, kg, R, E));
+    if (!g) return fail(BOHIP_E_ARG, "kg_lines: null argument");
+    CHK(kg_check_size("kg_lines", R));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(one_time_kernel_setup());
+    KgWs w{};
+    CHK(ensure_kg(g, R, E, true, &w));
+    HIPCHK(hipMemcpyAsync(w.a, a, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.B, B, (size_t)E * R * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(kg_march(g, false, w, w.a, w.B, R, R, E, 0.0, kg, nseg, nullptr));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;

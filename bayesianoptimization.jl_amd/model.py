@@ -397,6 +397,18 @@ class ElasticGPE:
         device and the stream only.  Returns (idx[q] int64, gain[q])."""
         return _qei_select(self._lib, self._h, samples, tau, q)
 
+    def kg(self, xs, n_eval=None):
+        """The knowledge gradient of the first n_eval columns of xs (default: all) over the candidate set xs, exact, on the device
+        (bohip_gp_kg, include/bohip_kg.h; an extension): KG(e) = E[max_j mu'_j] - max_j mu_j, the expected rise of the maximum of the
+        posterior mean over the candidates after ONE noisy observation at x_e.  The posterior covariance stays on the device; the
+        model is not changed.  Returns a KGResult."""
+        return _kg(self._lib, self._h, _cols(xs, self.dim), n_eval)
+
+    def kg_lines(self, a, B):
+        """The march of kg alone on the caller's lines (bohip_kg_lines): a[R] intercepts, B E x R slopes, one evaluation point per
+        row.  The model supplies the device and the stream only.  Returns (values[E], nseg[E] int32)."""
+        return _kg_lines(self._lib, self._h, a, B)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """S posterior SAMPLE PATHS (bohip_gp_paths_draw): draws that are functions, f_s(x) = beta + sum_m w_sm phi_m(x) +
         sum_j u_sj k(x, X_j) with M random features for the prior term and the exact data term (pathwise conditioning).  The result
@@ -523,6 +535,42 @@ def _qei_select(lib, handle, samples, tau, q):
     check(lib.bohip_gp_qei_select(handle, _ptr(F), F.shape[0], F.shape[1], float(tau), q,
                                   idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(gain)))
     return idx, gain
+
+
+class KGResult:
+    """Result of kg: values[E] (the knowledge gradient of every evaluation point, >= 0), nseg[E] (int32: segments of the upper
+    envelope beyond the first), mu[R] (the latent posterior mean of the candidates), best_val / best_idx (the arg-max over the
+    evaluation points under score's rule: first maximum, NaN never wins, -Inf / -1 if nothing can win)."""
+    __slots__ = ("values", "nseg", "mu", "best_val", "best_idx")
+
+    def __init__(self, values, nseg, mu, best_val, best_idx):
+        self.values, self.nseg, self.mu, self.best_val, self.best_idx = values, nseg, mu, best_val, best_idx
+
+    def __iter__(self):
+        return iter((self.values, self.nseg, self.mu, self.best_val, self.best_idx))
+
+
+def _kg(lib, handle, xs, n_eval):
+    R = xs.shape[1]
+    E = R if n_eval is None else int(n_eval)
+    values = np.zeros(max(E, 1))
+    nseg = np.zeros(max(E, 1), dtype=np.int32)
+    mu = np.empty(R)
+    best = Best()
+    check(lib.bohip_gp_kg(handle, _ptr(xs), R, E, _ptr(values), nseg.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(mu), C.byref(best)))
+    return KGResult(values, nseg, mu, best.val, best.idx)
+
+
+def _kg_lines(lib, handle, a, B):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+    B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, dtype=np.float64)))
+    if B.ndim != 2 or B.shape[1] != a.size:
+        raise ValueError(f"B must be E x {a.size} (one evaluation point per row), got shape {B.shape}")
+    E = B.shape[0]
+    values = np.zeros(max(E, 1))
+    nseg = np.zeros(max(E, 1), dtype=np.int32)
+    check(lib.bohip_kg_lines(handle, _ptr(a), _ptr(B), a.size, E, _ptr(values), nseg.ctypes.data_as(C.POINTER(C.c_int32))))
+    return values, nseg
 
 
 class PosteriorPaths:

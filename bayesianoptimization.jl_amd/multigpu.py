@@ -192,6 +192,18 @@ class MultiGPE:
 
         return _qei_select(self._lib, self._lib.bohip_mgp_handle(self._h, 0), samples, tau, q)
 
+    def kg(self, xs, n_eval=None):
+        """ElasticGPE.kg (bohip_gp_kg) on the FIRST replica, as sample_joint: Sigma couples all candidates."""
+        from .model import _kg
+
+        return _kg(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(xs, self.dim), n_eval)
+
+    def kg_lines(self, a, B):
+        """ElasticGPE.kg_lines (bohip_kg_lines) on the FIRST replica."""
+        from .model import _kg_lines
+
+        return _kg_lines(self._lib, self._lib.bohip_mgp_handle(self._h, 0), a, B)
+
     def mll_batch_dims(self):
         P, nmax = C.c_int64(), C.c_int64()
         check(self._lib.bohip_gp_mll_batch_dims(self._lib.bohip_mgp_handle(self._h, 0), C.byref(P), C.byref(nmax)))

@@ -39,7 +39,7 @@ using Dates: now
 using TimerOutputs: TimerOutput, reset_timer!, @timeit
 import Base: show
 
-export BOHipGPE, BOHipMultiGPE, DeviceBOpt, LogExpectedImprovement
+export BOHipGPE, BOHipMultiGPE, DeviceBOpt, LogExpectedImprovement, KnowledgeGradient
 
 const libbohip = get(ENV, "BOHIP_LIB", "libbohip.so")
 
@@ -348,6 +348,7 @@ include("BOHipPaths.jl")   # posterior sample paths (include/bohip_paths.h): dra
 include("BOHipFit.jl")     # batched marginal likelihood (include/bohip_fit.h): mll_batch_dims, mll_grad_batch
 include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/bohip_qei.h): qei_batch, qei_select
 include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_acq.h): LogExpectedImprovement, acq_eval
+include("BOHipKG.jl")      # the knowledge gradient over a candidate set (include/bohip_kg.h): kg, kg_lines, KnowledgeGradient
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
