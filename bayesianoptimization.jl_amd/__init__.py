@@ -7,12 +7,12 @@ libbohip.so (HIP, gfx950).  See DESIGN.md / INTEGRATION.md.
 from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
-                    mean_var, myrand, dims, maxy, update_, PosteriorPaths)
+                    mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, Marginalised, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
-from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, NoModelOptimizer, optimizemodel_,
+from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
                    Min, Max, Silent, Timings, Progress, isdone)
 from .utils import (ScaledSobolIterator, ScaledLHSIterator, latin_hypercube_sampling, maxduration_, maxiterations_,
                     IterationCounter, DurationCounter)
@@ -24,4 +24,4 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
            "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
-           "Mat32Iso", "Mat12Ard", "Mat12Iso"]
+           "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore"]

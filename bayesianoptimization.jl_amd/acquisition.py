@@ -129,6 +129,39 @@ class KnowledgeGradient(AbstractAcquisition):
     acq_id = "KG"
 
 
+class Marginalised(AbstractAcquisition):
+    """Marginalised(a): the acquisition `a` averaged over the hyper-parameter samples that MarginalGPOptimizer left on the model
+    (model.hyper_samples = (Theta[H, P], weights)): a(x) = sum_h w_h a(x; theta_h), the integrated acquisition of Snoek, Larochelle &
+    Adams 2012 (include/bohip_ens.h).  An extension: the reference has no such type, and no default uses it.  `a` is
+    one of the functors of (mu, sigma^2): ExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, MutualInformation,
+    MaxMean, LogExpectedImprovement.  setparams_ forwards to `a` (tau = max y, UCB's beta schedule, MI's gamma-hat: all taken
+    under the model's own, highest-likelihood setting).  VALUE ONLY: there is no gradient of the average and no device ascent --
+    acquisitionfunction maps a d x R matrix to the averaged scores (model.score_ensemble), and acquire_max takes the arg-max over
+    `maxeval` Latin-hypercube candidates per restart."""
+    TAKES = ("EI", "PI", "UCB", "MI", "MaxMean", "LogEI")
+
+    def __init__(self, a):
+        if not isinstance(a, AbstractAcquisition) or a.acq_id not in self.TAKES:
+            raise ValueError(f"Marginalised takes an acquisition of (mu, sigma^2) -- {', '.join(self.TAKES)} -- not "
+                             f"{type(a).__name__}")
+        self.a = a
+        self.acq_id = a.acq_id
+
+    def _setparams(self, model):
+        return setparams_(self.a, model)
+
+    def params(self):
+        return self.a.params()
+
+
+def _hyper_samples(model):
+    hs = getattr(model, "hyper_samples", None)
+    if hs is None:
+        raise ValueError("Marginalised needs model.hyper_samples: fit the model with MarginalGPOptimizer (or set "
+                         "model.hyper_samples = (Theta, weights)) first")
+    return hs
+
+
 def _erfc(x):
     from scipy.special import erfc                             # (vectorised; math.erfc is its scalar form)
 
@@ -211,6 +244,14 @@ def acquisitionfunction(a, model, rng=None):
             return model.kg(x).values
 
         return kg
+    if isinstance(a, Marginalised):
+        def marginal(x):
+            x = np.asarray(x, dtype=np.float64)
+            Theta, w = _hyper_samples(model)
+            sc = model.score_ensemble(a.acq_id, a.params(), x, Theta, w).scores
+            return float(sc[0]) if x.ndim == 1 else sc
+
+        return marginal
     if isinstance(a, ThompsonSamplingSimple):
         return lambda x: myrand(model, x, rng)
     if isinstance(a, MaxMean):
@@ -540,6 +581,24 @@ def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng):
     return maxf, maxx
 
 
+def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng):
+    """Marginalised(a): value only, no gradient and no device ascent.  Every restart scores `maxeval` Latin-hypercube candidates
+    under all hyper-parameter samples in ONE model.score_ensemble call and takes its arg-max record.  The first maximum over the
+    restarts wins (strict '>')."""
+    Theta, w = _hyper_samples(model)
+    if not hasattr(model, "score_ensemble"):
+        raise NotImplementedError(f"{type(model).__name__} has no score_ensemble")
+    maxf, maxx = -math.inf, lb.copy()
+    for _ in range(restarts):
+        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+        res = model.score_ensemble(a.acq_id, a.params(), xs, Theta, w)
+        if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
+            maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
+
+
 def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
     """src/acquisition.jl:48-68: R Latin-hypercube starts (utils.jl:96-120), local search from each, keep the
     best under strict '>' (first maximum wins).  Returns (maxf, maxx).
@@ -561,6 +620,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return maxf, maxx
     if isinstance(a, KnowledgeGradient):                          # (`method` has nothing to select between: accepted, not used)
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, Marginalised):                               # (value only: `method` is accepted, not used)
+        return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31
     if bool(opts.get("pathwise", False)):
         if not isinstance(a, ThompsonSamplingSimple):

@@ -9,7 +9,7 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, ExpectedImprovement, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
+from .acquisition import (AbstractAcquisition, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ElasticGPE, Mat52Ard, MeanConst, update_
@@ -61,11 +61,132 @@ class MAPGPOptimizer(ModelOptimizer):
                     likbounds=None, method="LD_LBFGS", maxeval=500, restarts=1, startwidth=3.0, seed=None)
 
 
+class MarginalGPOptimizer(ModelOptimizer):
+    """Samples of the hyper-parameter posterior instead of its mode (an extension: the reference fits the MAP point only), for the
+    integrated acquisition Marginalised(a) of Snoek, Larochelle & Adams 2012.  Every ``every`` calls, ``samples`` chains of univariate
+    slice sampling (Neal 2003, shrinkage) run in lock-step over the free parameters -- every likelihood evaluation is ONE batched
+    device call for all chains (_fit_objective's dispatch, value only) -- for ``burn`` + ``thin`` sweeps; each chain's last state is
+    one sample.  The priors are flat inside the bounds (the reference's "uniform priors in an interval", src/models/gp.jl:30-33), so
+    every free parameter needs FINITE bounds: noisebounds = [lo, hi], meanbounds = [[lo], [hi]], kernbounds = [[lo...], [hi...]]
+    (length-scales then log sigma); pass noise / domean / kern = False for what stays fixed (domean=False for a MeanZero model).
+    The chains start at the current parameters and Latin-hypercube points of the box, as the multi-start MAP fit does.
+    Afterwards model.hyper_samples = (Theta[H, P], weights) in mll_grad_batch's row layout with equal weights, and the model itself is
+    set to the sample of highest likelihood and refitted, so everything that reads the model keeps working."""
+
+    def __init__(self, every=10, samples=16, burn=20, thin=1, noisebounds=None, meanbounds=None, kernbounds=None, domean=True,
+                 kern=True, noise=True, seed=None):
+        if int(samples) < 1 or int(burn) < 0 or int(thin) < 1:
+            raise ValueError("samples >= 1, burn >= 0 and thin >= 1 are required")
+        for free, name, b in ((noise, "noisebounds", noisebounds), (domean, "meanbounds", meanbounds), (kern, "kernbounds", kernbounds)):
+            if free and (b is None or not np.all(np.isfinite(np.concatenate([np.ravel(b[0]), np.ravel(b[1])]).astype(float)))):
+                raise ValueError(f"MarginalGPOptimizer: {name} must be given and finite (flat priors need a box); "
+                                 f"fix the parameter instead with {'domean' if name == 'meanbounds' else name[:-6]}=False")
+        self.i = 0
+        self.every = every
+        self.options = dict(samples=int(samples), burn=int(burn), thin=int(thin), noisebounds=noisebounds, meanbounds=meanbounds,
+                            kernbounds=kernbounds, domean=bool(domean), kern=bool(kern), noise=bool(noise), seed=seed)
+        self._rng = np.random.default_rng(seed)
+        self.options["rng"] = self._rng
+
+
+def _slice_sample_batch(logp_batch, X0, lo, hi, sweeps, rng, max_shrink=200):
+    """Univariate slice sampling with the shrinkage procedure (Neal 2003, fig. 5 and 8), H chains in lock-step.  X0[p, H]: one
+    chain per column; lo, hi: the FINITE box, a coordinate's initial bracket is its whole interval (so no stepping out).
+    logp_batch(X[p, H]) -> logp[H] is ONE evaluation of all columns; -inf (or NaN) is a rejected proposal.  The coordinates are
+    cycled; in every shrinkage round all chains that have not yet accepted propose together, the others are masked (their column
+    is evaluated at its current state and ignored).  Returns (X[p, H], logp[H], trace[sweeps, p, H])."""
+    X = np.array(X0, dtype=np.float64, order="C")
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("slice sampling over a box needs finite bounds")
+    p, H = X.shape
+    f = np.asarray(logp_batch(X), dtype=np.float64).copy()
+    trace = np.empty((int(sweeps), p, H))
+    for s in range(int(sweeps)):
+        for k in range(p):
+            logy = f - rng.exponential(size=H)                # log(u f(x)), u ~ U(0, 1)
+            L, R = np.full(H, lo[k]), np.full(H, hi[k])
+            active = np.ones(H, dtype=bool)
+            for _ in range(max_shrink):
+                prop = L + rng.random(H) * (R - L)
+                Xp = X.copy()
+                Xp[k, active] = prop[active]
+                fp = np.asarray(logp_batch(Xp), dtype=np.float64)
+                with np.errstate(invalid="ignore"):
+                    acc = active & (fp > logy) & (fp > -np.inf)
+                X[k, acc], f[acc] = prop[acc], fp[acc]
+                rej = active & ~acc
+                left = rej & (prop < X[k])
+                L[left] = prop[left]
+                right = rej & ~left
+                R[right] = prop[right]
+                active = rej
+                if not active.any():
+                    break
+        trace[s] = X
+    return X, f, trace
+
+
+def _marginal_fit(model, opt):
+    if model.nobs == 0:
+        return
+    mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
+    x0, lo, hi = [], [], []
+    if opt["noise"]:
+        x0.append(model.logNoise); lo.append(float(opt["noisebounds"][0])); hi.append(float(opt["noisebounds"][1]))
+    if mean_free:
+        x0.append(model.mean.beta); lo.append(float(np.ravel(opt["meanbounds"][0])[0])); hi.append(float(np.ravel(opt["meanbounds"][1])[0]))
+    nk = 0
+    if opt["kern"]:
+        kp = np.concatenate([model.kernel.ll, [model.kernel.lsigma]])
+        nk = kp.size
+        kb = opt["kernbounds"]
+        if np.size(kb[0]) != nk or np.size(kb[1]) != nk:
+            raise ValueError(f"kernbounds must have {nk} entries per side (length-scales, then log sigma)")
+        x0 += kp.tolist(); lo += list(np.ravel(kb[0]).astype(float)); hi += list(np.ravel(kb[1]).astype(float))
+    lo, hi = np.asarray(lo, float), np.asarray(hi, float)
+    if lo.size == 0:
+        return
+    x0 = np.clip(np.asarray(x0, float), lo, hi)
+
+    def apply(x):
+        i = 0
+        kw = {}
+        if opt["noise"]:
+            kw["logNoise"] = x[i]; i += 1
+        if mean_free:
+            kw["beta"] = x[i]; i += 1
+        if opt["kern"]:
+            kw["ll"] = x[i:i + nk - 1]; kw["lsigma"] = x[i + nk - 1]
+        model.set_params_(**kw)
+
+    H, rng = opt["samples"], opt["rng"]
+    base = np.concatenate([[model.logNoise, model.mean.beta if isinstance(model.mean, MeanConst) else 0.0], model.kernel.ll,
+                           [model.kernel.lsigma]])
+    nk_all = model.kernel.ll.size + 1
+    idx = ([0] if opt["noise"] else []) + ([1] if mean_free else []) + (list(range(2, 2 + nk_all)) if opt["kern"] else [])
+    fit_opt = dict(domean=opt["domean"], noise=opt["noise"], kern=opt["kern"])
+    fg = _fit_objective(model, fit_opt, nk, apply, x0.size, H, want_grad=False)
+    starts = np.concatenate([x0.reshape(-1, 1), latin_hypercube_sampling(lo, hi, H - 1, rng)], axis=1) if H > 1 else x0.reshape(-1, 1)
+    X, f, _ = _slice_sample_batch(lambda Z: fg(Z)[0], starts, lo, hi, opt["burn"] + opt["thin"], rng)
+    Theta = np.tile(base, (H, 1))
+    Theta[:, idx] = X.T
+    model.hyper_samples = (Theta, np.full(H, 1.0 / H))
+    f = np.where(np.isfinite(f), f, -np.inf)
+    w = int(np.argmax(f))                                     # the first of equal bests
+    apply(X[:, w] if np.isfinite(f[w]) else x0)
+    model.fit_()
+    return float(f[w]), X[:, w].copy()
+
+
 def optimizemodel_(o, model):                                 # :42-47 and NoModelOptimizer :49
     if isinstance(o, NoModelOptimizer) or o is None:
         return None
     if o.i % o.every == 0:
-        _map_fit(model, o.options)
+        if isinstance(o, MarginalGPOptimizer):
+            _marginal_fit(model, o.options)
+        else:
+            _map_fit(model, o.options)
     o.i += 1
 
 
@@ -162,10 +283,11 @@ def _fit_batched(n, H, nmax):
     return False
 
 
-def _fit_objective(model, opt, nk, apply, p, H):
+def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
     """fg_batch of _multistart_map for a model: the free parameters of the fit sit in the optimisation vector, the fixed ones are
     constants of Theta's rows.  A device model of a size the batched call takes, and wins at, evaluates all columns in one launch;
-    otherwise (or for a model without the call) every column is a set_params_ + mll_grad, at any N."""
+    otherwise (or for a model without the call) every column is a set_params_ + mll_grad, at any N.  want_grad=False (the slice
+    sampler): the same dispatch, value only -- the gradient is None, the batched call forms no inverse and the loop calls mll."""
     mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
     base = np.concatenate([[model.logNoise, model.mean.beta if isinstance(model.mean, MeanConst) else 0.0], model.kernel.ll,
                            [model.kernel.lsigma]])
@@ -176,14 +298,17 @@ def _fit_objective(model, opt, nk, apply, p, H):
     def fg_batched(X):
         Theta = np.tile(base, (X.shape[1], 1))
         Theta[:, idx] = X.T
-        mll, G, piv = model.mll_grad_batch(Theta)
-        return np.where(piv == 0, mll, -np.inf), np.ascontiguousarray(G[:, idx].T)
+        mll, G, piv = model.mll_grad_batch(Theta, want_grad)
+        return np.where(piv == 0, mll, -np.inf), np.ascontiguousarray(G[:, idx].T) if want_grad else None
 
     def fg_loop(X):
         f, G = np.full(X.shape[1], -np.inf), np.zeros(X.shape)
         for r in range(X.shape[1]):
             apply(X[:, r])
             try:
+                if not want_grad:
+                    f[r] = model.mll()
+                    continue
                 m, dn, dm, dk = model.mll_grad()
             except NotPositiveDefinite:
                 continue
@@ -191,6 +316,8 @@ def _fit_objective(model, opt, nk, apply, p, H):
             f[r], G[:, r] = m, full[idx]
         return f, G
 
+    if not want_grad:
+        return (lambda X: (fg_batched(X)[0], None)) if batched else (lambda X: (fg_loop(X)[0], None))
     return fg_batched if batched else fg_loop
 
 
@@ -222,6 +349,8 @@ class BOpt:
             raise ValueError("length of lowerbounds does not match length of upperbounds")
         if int(batchsize) != batchsize or batchsize < 1:
             raise ValueError(f"batchsize = {batchsize!r} is not a positive integer")
+        if batchsize > 1 and isinstance(acquisition, Marginalised):
+            raise ValueError("Marginalised acquisitions propose one point per iteration (batchsize = 1)")
         if batchsize == 1 and batchoptions:
             raise ValueError("batchoptions given with batchsize = 1")
         if not np.all(lowerbounds <= upperbounds):

@@ -106,6 +106,8 @@ class ElasticGPE:
     directly (src/BayesianOptimization.jl:117-119, src/acquisitionfunctions.jl:136).
     """
 
+    hyper_samples = None   # (Theta[H, P], weights) once MarginalGPOptimizer has run: what Marginalised acquisitions average over
+
     def __init__(self, d, mean=None, kernel=None, logNoise=-2.0, capacity=1024, device=0):
         self.dim = int(d)
         self.mean = mean if mean is not None else MeanZero()
@@ -250,6 +252,16 @@ class ElasticGPE:
         check(self._lib.bohip_gp_score(self._h, _lib.ACQ[acq], _ptr(p), _ptr(xs), R,
                                        _ptr(sc) if want_scores else None, C.byref(best)))
         return sc, best.val, best.idx
+
+    def score_ensemble(self, acq, params, xs, Theta, weights=None, want_each=False, want_moments=False):
+        """The acquisition `acq` averaged over the H hyper-parameter settings in the rows of Theta (row = [logNoise, mean, ll...,
+        lsigma], mll_grad_batch's layout): scores[j] = sum_h w~_h a(x_j; theta_h), the integrated acquisition of Snoek, Larochelle &
+        Adams 2012 (an extension).  weights: H numbers >= 0 (None: equal), renormalised over the settings whose factorisation
+        succeeds; a failed setting has pivot > 0 and NaN rows.  Returns an EnsembleScore; its `route` says what ran: "device"
+        (bohip_gp_score_ens, include/bohip_ens.h: all settings in one call, the model neither read beyond its observations nor
+        changed) up to mll_batch_dims()[1] observations, "host" above that (set_params_ + score / predict_f per row, the model's
+        own parameters restored afterwards), with the same averaging rule.  Value only: no gradient."""
+        return score_ensemble(self, acq, params, xs, Theta, weights, want_each, want_moments)
 
     def select_batch(self, acq, params, xs, q, fantasy="believer", raise_tau=False):
         """q candidates to evaluate in parallel (bohip_gp_select_batch; an extension, the reference proposes one point per
@@ -470,6 +482,113 @@ def _mll_grad_batch(lib, h, Theta, want_grad):
     check(lib.bohip_gp_mll_grad_batch(h, H, _ptr(Theta), _ptr(mll), _ptr(G) if want_grad else None,
                                       pivot.ctypes.data_as(C.POINTER(C.c_int64))))
     return mll, G, pivot
+
+
+class EnsembleScore:
+    """Result of score_ensemble: scores[R] (the weighted average over the surviving settings), best_val / best_idx (its arg-max
+    under score's rule: first maximum, NaN never wins, -Inf / -1 if nothing can win), pivot[H] (int64: 0, or the 1-based pivot at
+    which the setting's factorisation failed), each (H x R per-setting scores, or None), mu / var (H x R each, or None), route
+    ("device": bohip_gp_score_ens; "host": one refit per setting)."""
+    __slots__ = ("scores", "best_val", "best_idx", "pivot", "each", "mu", "var", "route")
+
+    def __init__(self, scores, best_val, best_idx, pivot, each, mu, var, route):
+        self.scores, self.best_val, self.best_idx, self.pivot = scores, best_val, best_idx, pivot
+        self.each, self.mu, self.var, self.route = each, mu, var, route
+
+    def __iter__(self):
+        return iter((self.scores, self.best_val, self.best_idx, self.pivot, self.each, self.mu, self.var))
+
+
+def ensemble_average(each, weights, pivot):
+    """The averaging rule of score_ensemble, both routes: w~ = w / (sum of w over the settings with pivot 0, ascending h), then
+    scores = sum_h w~_h each[h], added in ascending h from 0.0; failed settings and settings of weight 0 take no part."""
+    each = np.asarray(each, dtype=np.float64)
+    H, R = each.shape
+    w = np.ones(H) if weights is None else np.asarray(weights, dtype=np.float64)
+    total = 0.0
+    for h in range(H):
+        if pivot[h] == 0:
+            total += w[h]
+    scores = np.zeros(R)
+    for h in range(H):
+        wt = w[h] / total if pivot[h] == 0 else 0.0
+        if wt != 0.0:
+            scores = scores + wt * each[h]
+    return scores
+
+
+def _ens_weights(weights, H):
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).ravel())
+    if w.size != H:
+        raise ValueError(f"weights must have one entry per row of Theta ({H}), got {w.size}")
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0.0) and w.sum() > 0.0):
+        raise ValueError("weights must be finite, >= 0 and not all 0")
+    return w
+
+
+def score_ensemble(model, acq, params, xs, Theta, weights=None, want_each=False, want_moments=False):
+    """ElasticGPE.score_ensemble for any model object: the device route where the model owns a handle whose library has
+    bohip_gp_score_ens and holds at most nmax observations, else the host loop over set_params_ + score / predict_f."""
+    if acq not in _lib.ACQ or acq == "ThompsonDraw":
+        raise ValueError(f"score_ensemble takes EI, PI, UCB, MI, MaxMean and LogEI, not {acq!r}")
+    xs = _cols(xs, model.dim)
+    P = 2 + (1 if model.kernel.iso else model.dim) + 1
+    Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
+    if Theta.shape[1] != P:
+        raise ValueError(f"Theta must have {P} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
+    H, R = Theta.shape[0], xs.shape[1]
+    w = _ens_weights(weights, H)
+    p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+    if p.size < 2:
+        p = np.concatenate([p, np.zeros(2 - p.size)])
+    lib, h = getattr(model, "_lib", None), getattr(model, "_h", None)
+    if lib is not None and h and hasattr(lib, "bohip_gp_score_ens") and model.nobs <= _lib.FIT_NMAX:
+        scores = np.empty(R)
+        each = np.empty((H, R)) if want_each else None
+        mu = np.empty((H, R)) if want_moments else None
+        var = np.empty((H, R)) if want_moments else None
+        pivot = np.zeros(H, dtype=np.int64)
+        best = Best()
+        opt = lambda a: _ptr(a) if a is not None else None   # noqa: E731
+        check(lib.bohip_gp_score_ens(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), opt(w), _ptr(xs), R, _ptr(scores), opt(each), opt(mu),
+                                     opt(var), pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
+        return EnsembleScore(scores, best.val, best.idx, pivot, each, mu, var, "device")
+    # host route: one refit per setting; the model's own parameters come back whatever happens
+    saved = (model.kernel.ll.copy(), model.kernel.lsigma, model.logNoise, model.mean)
+    each = np.full((H, R), np.nan)
+    mu, var = (np.full((H, R), np.nan), np.full((H, R), np.nan)) if want_moments else (None, None)
+    pivot = np.zeros(H, dtype=np.int64)
+    nl = P - 3
+    try:
+        for k in range(H):
+            row = Theta[k]
+            if not np.all(np.isfinite(row)):
+                pivot[k] = 1
+                continue
+            try:
+                model.set_params_(ll=row[2:2 + nl], lsigma=row[2 + nl], logNoise=row[0], beta=row[1])
+                each[k] = model.score(acq, p, xs)[0]
+                if want_moments:
+                    mu[k], var[k] = model.predict_f(xs)
+            except _lib.NotPositiveDefinite:
+                piv = model.info(_lib.INFO_PIVOT) if hasattr(model, "info") else 1
+                pivot[k] = max(int(piv), 1)
+                each[k] = np.nan
+                if want_moments:
+                    mu[k], var[k] = np.nan, np.nan
+    finally:
+        model.set_params_(ll=saved[0], lsigma=saved[1], logNoise=saved[2], beta=saved[3].beta)
+        model.mean = saved[3]
+    if not np.any((pivot == 0) & ((w if w is not None else np.ones(H)) > 0.0)):
+        raise _lib.NotPositiveDefinite(_lib.E_NOTPD, "the factorisation failed at every hyper-parameter setting")
+    scores = ensemble_average(each, w, pivot)
+    best_val, best_idx = -math.inf, -1
+    for j, v in enumerate(scores):
+        if v > best_val:
+            best_val, best_idx = float(v), j
+    return EnsembleScore(scores, best_val, best_idx, pivot, each if want_each else None, mu, var, "host")
 
 
 class JointSample:
