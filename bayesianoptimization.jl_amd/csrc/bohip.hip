@@ -432,6 +432,7 @@ static int g_chol_exec_wgs = -1;  // executor workgroups (BOHIP_CHOL_EXEC_WGS); 
 static int g_append_alpha_inc = 1;   // incremental alpha on append (BOHIP_APPEND_ALPHA_INC=0: recomputed as W'(W r))
 static int64_t g_chunk_rows_forced = 0;   // BOHIP_CHUNK_ROWS: candidates per K*' chunk (tools: chunk-size sweeps), 0 = the rule in chunk_rows
 static int g_prune_m = -1;  // pruned arg-max: row tiles of the bounding prefix (BOHIP_PRUNE_M; 0: off, -1: the rule in prune_tiles)
+static int g_pa_order = 1;  // phase A's job order (BOHIP_PA_ORDER): 0 heaviest first, 1 the middle third first (phase_a_jobs): bench shape 22.1 -> 20.2 us
 static int launch_gemm_nt(bohip_gp* g, const GemmNTParams& p, int batch = 1, hipStream_t st = nullptr, bool hi = false) {
     if (p.mt <= 0 || p.nt64 <= 0 || p.kc <= 0 || batch <= 0) return 0;
     if (hi) hipLaunchKernelGGL(k_gemm_nt_hi, dim3(p.mt * p.nt64, batch), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), st ? st : g->stream, p);
@@ -455,7 +456,7 @@ static void read_dev_knobs() {
         {"BOHIP_CHOL_EXEC_INV_PAIRS", &g_chol_exec_inv_pairs, 0, 1}, {"BOHIP_CHOL_EXEC_WGS", &g_chol_exec_wgs, 1, 1 << 20},
         {"BOHIP_CHOL_EXEC_FAST", &g_chol_exec_fast, -1, 1 << 20},
         {"BOHIP_CHOL_EXEC_SECOND", &g_chol_exec_second, 0, 1}, {"BOHIP_SMALL_ZERO_COPY", &g_small_zero_copy, 0, 1}, {"BOHIP_CHOL_EXEC_NBU", &g_chol_exec_nbu, 0, 16}, {"BOHIP_CHUNK_ROWS", &chunk_rows, 0, 1 << 30},
-        {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16},
+        {"BOHIP_PRUNE_M", &g_prune_m, -1, 1 << 16}, {"BOHIP_PA_ORDER", &g_pa_order, 0, 1},
         {"BOHIP_APPEND_ALPHA_INC", &g_append_alpha_inc, 0, 1}, {"BOHIP_BULK_PIECES", &g_bulk_pieces, 0, 8}, {"BOHIP_SPLIT", &g_split, 0, 1},
         {"BOHIP_SMALL_R", &g_small_r, 0, SMALL_MAX}, {"BOHIP_SMALL_M", &g_small_m, 0, 1 << 20}, {"BOHIP_CHOL_DF_DUMP", &dump, 0, 1},
     };
@@ -476,6 +477,7 @@ static int one_time_kernel_setup() {
     HIPCHK(hipFuncSetAttribute((const void*)k_potf2_inv, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq_pa, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_rows, hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)k_batch_cond<false>, hipFuncAttributeMaxDynamicSharedMemorySize, BATCH_LDS_MAX));
@@ -1935,6 +1937,31 @@ static int launch_trigemm_on(bohip_gp* g, const double* KsT, const int* pieces, 
     HIPCHK(hipGetLastError());
     return 0;
 }
+// Phase A's job table (k_trigemm_sq_pa): the two 64-row halves of every row piece with rt < m, rt | hh << 16.  Every such piece is a
+// whole tile and none holds the alpha row (m < T: the last tile is not in the prefix).  Order: sorted heaviest first (chunks: 8 rt + 8
+// the lower half, 8 rt + 4 the upper), then the first third of the list swapped with the second.  At the bench shape all 384
+// workgroups are resident at once, two to a CU where they share one, and the workgroups dealt last land beside the ones dealt
+// first: heaviest-first pairs the lightest jobs with the heaviest and the launch lasts 24 chunks at a shared CU's pace (22.1 us);
+// with the middle third first the heaviest run alone and the lightest sit beside the middle ones (20.2 us;
+// profiles/prune_phase_a_ab.txt).  The order cannot change a result: one job writes one q row.
+static std::vector<int> phase_a_jobs(const std::vector<int>& pieces, int m) {
+    std::vector<int> out;
+    for (int c : pieces)
+        if ((c & 0xffff) < m) { out.push_back((c & 0xffff) | 1 << 16); out.push_back(c & 0xffff); }
+    std::stable_sort(out.begin(), out.end(), [](int a, int b) {
+        return 8 * (a & 0xffff) + (a >> 16) * 4 > 8 * (b & 0xffff) + (b >> 16) * 4;
+    });
+    if (g_pa_order == 1) std::rotate(out.begin(), out.begin() + out.size() / 3, out.begin() + 2 * (out.size() / 3));
+    return out;
+}
+static int launch_phase_a(bohip_gp* g, const double* KsT, const int* jobs, int NJOBS, int CT, double* q, int64_t ldq) {
+    const int n_local = (CT + 7) / 8;
+    if (NJOBS <= 0 || CT <= 0) return 0;
+    hipLaunchKernelGGL(k_trigemm_sq_pa, dim3(8 * n_local * NJOBS), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW, g->ld,
+                       KsT, g->ld, jobs, CT, q, ldq, g->timing && g->dclk ? g->dclk : nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // One chunk, value-only: K*' with the partial sums of the alpha row's product -> phase A (row tiles < m, every candidate) -> bounds ->
 // select (the 64 highest bounds) -> round 1 (row tiles >= m, exact finish: L; the finish lists round 2: every other candidate
 // whose bound is not below L) -> round 2 -> the record.  Six launches: a round is ONE k_trigemm_rows launch whose last workgroup to
@@ -1957,12 +1984,17 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     CHK(ensure_pieces(g, T, N));
     std::vector<int> pa, pb;   // the full pass's row pieces (same modes, same order), split at row tile m
     for (int c : g->hpieces) ((c & 0xffff) < m ? pa : pb).push_back(c);
+    // phase A runs 64-row jobs that write no mu: no piece of the prefix may be a solo half or hold the alpha row
+    if (m >= T) return fail(BOHIP_E_STATE, "pruned pass: the prefix holds the alpha row");
+    for (int c : pa)
+        if (c >> 16 != PIECE_WHOLE) return fail(BOHIP_E_STATE, "pruned pass: a half piece in the prefix");
+    const std::vector<int> ph = phase_a_jobs(g->hpieces, m);
     // layout (bytes, every part 256-aligned)
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
                  o_ub = o_mu2 + al((size_t)Rpad * 8), o_l1 = o_ub + al((size_t)Rpad * 8), o_l2 = o_l1 + al((size_t)PRUNE_K1 * 4),
                  o_mark = o_l2 + al((size_t)Rpad * 4), o_cnt = o_mark + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
-                 o_parts = o_rec + 256, o_pc = o_parts + al((size_t)2 * P * Rpad * 8), total = o_pc + al((3 * g->hpieces.size() + 8) * 4);
+                 o_parts = o_rec + 256, o_pc = o_parts + al((size_t)2 * P * Rpad * 8), total = o_pc + al((5 * g->hpieces.size() + 8) * 4);
     bool fresh = false;
     if (g->pr_bytes < total) {
         fresh = true;
@@ -1981,6 +2013,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     std::vector<int> both = pa;
     both.insert(both.end(), pb.begin(), pb.end());
     both.insert(both.end(), hv.begin(), hv.end());
+    both.insert(both.end(), ph.begin(), ph.end());   // (last: the other tables keep their offsets)
     if (fresh || g->hpr_pieces != both || g->pr_pieces_at != pcs) {   // (the table's offset moves with the batch)
         g->pr_pieces_at = pcs;
         g->hpr_pieces = both;   // (kept alive until the stream has consumed the copy)
@@ -2002,7 +2035,7 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     t_begin(g, "trigemm_sq");
     FuseParams fz{};
     fz.T = T;
-    CHK(launch_trigemm_on(g, g->dKsT, pcs, (int)pa.size(), (int)((R + CTILE - 1) / CTILE), g->dq, Rpad, g->dmu_raw, fz));
+    CHK(launch_phase_a(g, g->dKsT, pcs + pa.size() + pb.size() + hv.size(), (int)ph.size(), (int)((R + CTILE - 1) / CTILE), g->dq, Rpad));
     PruneBound bd{};
     bd.parts = kp.parts; bd.P = P; bd.ldp = Rpad; bd.Npad = Npad; bd.q = g->dq; bd.ldq = Rpad; bd.R = R; bd.m = m;
     bd.sigma2 = sigma2; bd.beta = g->beta; bd.ap = ap; bd.ub = ub;
@@ -4293,9 +4326,11 @@ int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, 
 }
 // tests only (tests/test_prune_rows_gpu.py): the partial sums q[2T][R] and mu_raw[R] of R host candidates from the full pass's
 // k_trigemm_sq (path 0) or from k_trigemm_rows over every row tile, the candidates listed in reverse order (path 1; path 2: the
-// same with ONE column group in the grid, every further group from the kernel's loop)
+// same with ONE column group in the grid, every further group from the kernel's loop).  Path 3: the phase-A launch exactly as
+// pruned_pass enqueues it (phase_a_jobs, launch_phase_a, m from prune_tiles): q rows 2 t + h for t < m, every other row and mu zero;
+// BOHIP_E_UNSUPPORTED where no T-tile model prunes.
 int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int path, double* q_out, double* mu_out) {
-    if (!g || R <= 0 || !Xs || !q_out || !mu_out || path < 0 || path > 2) return fail(BOHIP_E_ARG, "bad arguments");
+    if (!g || R <= 0 || !Xs || !q_out || !mu_out || path < 0 || path > 3) return fail(BOHIP_E_ARG, "bad arguments");
     HIPCHK(hipSetDevice(g->device));
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     CHK(ensure_fresh(g));
@@ -4317,6 +4352,24 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
         HIPCHK(hipStreamSynchronize(g->stream));
         for (int t = 0; t < 2 * T; ++t) std::memcpy(q_out + (size_t)t * R, q.data() + (size_t)t * Rpad, (size_t)R * 8);
         std::memcpy(mu_out, mu.data(), (size_t)R * 8);
+        return 0;
+    }
+    if (path == 3) {
+        const int m = prune_tiles(T);
+        if (m <= 0 || m >= T) return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
+        const std::vector<int> ph = phase_a_jobs(g->hpieces, m);
+        int* dj = nullptr;
+        HIPCHK(hipMalloc(&dj, ph.size() * sizeof(int)));
+        hipMemcpyAsync(dj, ph.data(), ph.size() * sizeof(int), hipMemcpyHostToDevice, g->stream);
+        hipMemsetAsync(g->dq, 0, q.size() * 8, g->stream);
+        const int rc = launch_phase_a(g, g->dKsT, dj, (int)ph.size(), (int)((R + CTILE - 1) / CTILE), g->dq, Rpad);
+        hipMemcpyAsync(q.data(), g->dq, q.size() * 8, hipMemcpyDeviceToHost, g->stream);
+        const hipError_t e = hipStreamSynchronize(g->stream);
+        hipFree(dj);
+        if (rc != 0) return rc;
+        if (e != hipSuccess) return fail(BOHIP_E_HIP, hipGetErrorString(e));
+        for (int t = 0; t < 2 * T; ++t) std::memcpy(q_out + (size_t)t * R, q.data() + (size_t)t * Rpad, (size_t)R * 8);
+        std::memset(mu_out, 0, (size_t)R * 8);
         return 0;
     }
     std::vector<int> list((size_t)R);

@@ -165,11 +165,18 @@ __device__ unsigned long long g_phase[8192 * 8 * 4];   // [block][wave]{issue+mf
 // that run beside the factorisation's chain (and the inverse's small levels) are faster that way than with two.
 // FOLD = false: leave the two partial accumulator sets as they are (a caller that runs the loop in two pieces -- with a
 // wait for the second piece's operands in between, kernels_exec.hip -- folds once, after the last piece)
-template <int NJ, int ABL = 0, bool SWAVE = false, bool FOLD = true>  // ABL: ablation switches (tools only): 1 no DMA, 2 no LDS reads, 4 no barriers
+// ROWS64 = true: the job is ONE 64-row half (row_h = 0 upper, 1 lower) of a 128-row tile, in WHOLE mode: A points at the half's first
+// row, only its 64 rows are fetched (issue_h) and only the waves with wr == 0 compute -- each exactly what the wave (khalf, wr = row_h,
+// wc) of the whole-tile job computes: same fragments, same k-slot order with both members of a pair into one accumulator, the
+// triangular skip of wave row row_h, the same khalf fold.  The waves with wr == 1 issue their share of the DMA and keep the barriers.
+// The roles are dealt so that every SIMD holds one computing wave (below).
+// (Phase A of the pruned arg-max, k_trigemm_sq_pa: twice the workgroups, half the MFMAs per SIMD and chunk.)
+template <int NJ, int ABL = 0, bool SWAVE = false, bool FOLD = true, bool ROWS64 = false>  // ABL: ablation switches (tools only): 1 no DMA, 2 no LDS reads, 4 no barriers
 __device__ __forceinline__ void gemm_tile_loop_glds3_ks(const double* __restrict__ A, int64_t lda,
                                                         const double* __restrict__ B, int64_t ldb, int kc_begin,
                                                         int kc_end, double* smem, double (&acc)[8][NJ],
-                                                        int active_rows = TILE, int tri_kc = 1 << 30, int tid_in = -1) {
+                                                        int active_rows = TILE, int tri_kc = 1 << 30, int tid_in = -1,
+                                                        int row_h = 0) {
     // tri_kc: first chunk of a 128 x 128 block of A that is LOWER-TRIANGULAR (row r has zeros at k > r): from there on
     // an 8-row group whose rows all lie above this wave's 8 contraction indices contributes nothing and is skipped
     // (47 % of that block's MFMAs).
@@ -178,7 +185,12 @@ __device__ __forceinline__ void gemm_tile_loop_glds3_ks(const double* __restrict
     // tid_in: the caller's copy of threadIdx.x (a persistent kernel passes one the compiler cannot see through, so that
     // nothing lane-dependent is hoisted out of its job loop and kept alive across the whole job)
     const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, lane = tid & 63, wave = SWAVE ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6);
-    const int khalf = wave >> 2, w4 = wave & 3, wr = w4 >> 1, wc = w4 & 1;
+    // ROWS64: the four computing roles (khalf, wc) go to waves 0..3, ONE PER SIMD (a workgroup's waves are dealt to the four SIMDs
+    // round-robin; with the whole-tile roles the computing waves would be 0, 1, 4, 5: two SIMDs with two waves each, two with
+    // none, and a chunk as long as the whole tile's -- measured, profiles/prune_phase_a_ab.txt); waves 4..7 take wr = 1.  Which wave
+    // holds a role changes no bit: the lane layout inside the wave is the role's.
+    const int w4 = wave & 3;
+    const int khalf = ROWS64 ? w4 >> 1 : wave >> 2, wr = ROWS64 ? wave >> 2 : w4 >> 1, wc = w4 & 1;
     double* As = smem;             // [3][128][16]
     double* Bs = smem + 3 * AT;    // [3][64][16]
     if (kc_begin >= kc_end) return;
@@ -208,13 +220,13 @@ __device__ __forceinline__ void gemm_tile_loop_glds3_ks(const double* __restrict
     // 64 rows idle for the whole job, both row halves of the wave grid work on rows 0..63 -- wr = 0 takes the even member of every
     // contraction-index pair, wr = 1 the odd one -- and the partial sums are added at the end.  Half the MFMAs per wave and
     // chunk: the job takes about half as long (those jobs are the LONGEST ones, K = N).
-    const bool half = active_rows <= TILE / 2;
-    const int wre = half ? 0 : wr;
+    const bool half = !ROWS64 && active_rows <= TILE / 2;
+    const int wre = half || ROWS64 ? 0 : wr;
     const int xy = __builtin_amdgcn_readfirstlane(half ? 1 + wr : 0);
     const int a_frag = (wre * 64 + r7a) * GL_ROW + oa, b_frag = (wc * 8 * NJ + r7b) * GL_ROW + ob;
-    const bool wave_active = half || wr * 64 < active_rows;
-    const int skip0 = __builtin_amdgcn_readfirstlane(khalf - 8 * wre);   // wave-uniform: keep it in an SGPR
-    if (half) {
+    const bool wave_active = ROWS64 ? wr == 0 : half || wr * 64 < active_rows;
+    const int skip0 = __builtin_amdgcn_readfirstlane(khalf - 8 * (ROWS64 ? row_h : wre));   // wave-uniform: keep it in an SGPR
+    if (half || ROWS64) {
         issue_h(kc_begin, 0);
         if (kc_begin + 1 < kc_end) {
             issue_h(kc_begin + 1, 1);
@@ -244,7 +256,7 @@ __device__ __forceinline__ void gemm_tile_loop_glds3_ks(const double* __restrict
 #endif
             const int nxt2 = cur == 0 ? 2 : cur - 1;
             const bool more2 = kc + 2 < kc_end;
-            constexpr bool HALF = decltype(xy_tag)::value != 0;
+            constexpr bool HALF = decltype(xy_tag)::value != 0 || ROWS64;   // (the DMA of 64 rows of A: two pieces per wave)
             if (more2 && !(ABL & 1)) {
                 if constexpr (HALF) issue_h(kc + 2, nxt2);
                 else issue(kc + 2, nxt2);
@@ -286,24 +298,29 @@ __device__ __forceinline__ void gemm_tile_loop_glds3_ks(const double* __restrict
         }
 #endif
     };
-    if (xy == 0) run(std::integral_constant<int, 0>{});
-    else if (xy == 1) run(std::integral_constant<int, 1>{});
-    else run(std::integral_constant<int, 2>{});
+    if constexpr (ROWS64) {
+        run(std::integral_constant<int, 0>{});
+    } else {
+        if (xy == 0) run(std::integral_constant<int, 0>{});
+        else if (xy == 1) run(std::integral_constant<int, 1>{});
+        else run(std::integral_constant<int, 2>{});
+    }
     if constexpr (!FOLD) return;
     // add the second half's partial accumulators into the first half's (through LDS: 32 doubles per lane)
     double* xch = smem;  // 256 lanes x 32 doubles = 64 KB <= staging area
-    if (khalf == 1) {
+    const bool folds = !ROWS64 || wr == 0;   // (a 64-row job's waves of wr == 1 hold nothing)
+    if (khalf == 1 && folds) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) xch[(i * NJ + j) * 256 + (tid & 255)] = acc[i][j];
+            for (int j = 0; j < NJ; ++j) xch[(i * NJ + j) * 256 + (ROWS64 ? wc * 64 + lane : (tid & 255))] = acc[i][j];
     }
     __syncthreads();
-    if (khalf == 0) {
+    if (khalf == 0 && folds) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] += xch[(i * NJ + j) * 256 + tid];
+            for (int j = 0; j < NJ; ++j) acc[i][j] += xch[(i * NJ + j) * 256 + (ROWS64 ? wc * 64 + lane : tid)];
     }
     __syncthreads();
     if (half) {   // rows 0..63: waves 2, 3 (odd members) into waves 0, 1 (even members); the lower row half ends up zero

@@ -359,6 +359,84 @@ __global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_trigemm_sq(const double* 
     }
 }
 
+// ---- phase A of the pruned arg-max as 64-row jobs ----------------------------------------------------------------------------
+// Phase A contracts the row tiles rt < m (m = 3 of 24 at N = 3000) against every candidate.  As whole-tile jobs that is 64 candidate
+// tiles x 3 pieces = 192 workgroups on 256 CUs, and the launch lasts as long as its rt = m - 1 jobs, each alone on a CU and bound by
+// the MFMA issue of two waves per SIMD.  Here every whole piece is cut into its two 64-row halves, each a workgroup of its own in
+// the loop's WHOLE mode (gemm_tile_loop_glds3_ks<.., ROWS64>): the waves of wave row 0 compute what the waves of wave row hh of the
+// whole-tile job compute -- same fragments, k-slot order, skip, khalf fold -- and sq_step / sq_tree run over the same lanes, so
+// q_part[2 rt + hh] comes out bit for bit as k_trigemm_sq's (an element of an MFMA result depends on its own A row and B column
+// only: the argument k_trigemm_rows rests on).  The upper half (hh = 0) ends at chunk 8 rt + 4: past it every row group of it is
+// skipped.  A job of the prefix never holds the alpha row (m < T, checked by the host), so no mu is written.  No fused finish.
+// jobs: rt | hh << 16 in launch order (host: phase_a_jobs); the XCD deal of k_trigemm_sq.
+__device__ __forceinline__ void trigemm_job_rows64(int rt, int hh, int ct, const double* __restrict__ W, int64_t ldw,
+                                                   const double* __restrict__ KsT, int64_t ldk, double* __restrict__ q_part,
+                                                   int64_t ldq, double* smem, int tid) {
+    constexpr int NJ = 4, CW = CTILE;
+    double acc[8][NJ];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = 0.0;
+    const int64_t row_base = (int64_t)rt * TILE + 64 * hh;
+    const int tri_kc = rt * (TILE / KC);                       // first chunk of the tile's triangular block
+    const int kc_end = tri_kc + (hh == 0 ? 4 : 8);
+    gemm_tile_loop_glds3_ks<NJ, BOHIP_ABL, true, true, true>(W + row_base * ldw, ldw, KsT + (int64_t)ct * CW * ldk, ldk, 0, kc_end, smem,
+                                                             acc, TILE / 2, tri_kc, tid, hh);
+    const int lane = tid & 63, wave = tid >> 6, wc = wave & 1;
+    __syncthreads();     // (the raw-barrier loops end on s_barrier; make the reuse of smem below explicit)
+    double* red = smem;  // [CW]
+    if (wave < 2) {      // khalf = 0, wave row 0: the half's 64 rows, folded
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) {
+            double s = 0.0;
+#pragma unroll
+            for (int mi = 0; mi < 8; ++mi) s = sq_step(s, acc[mi][nj]);
+            s = sq_tree(s);
+            if (lane < 8) red[wc * 8 * NJ + 8 * nj + lane] = s;
+        }
+    }
+    __syncthreads();
+    if (tid < CW)
+        __hip_atomic_store(q_part + (int64_t)(2 * rt + hh) * ldq + (int64_t)ct * CW + tid, red[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(GEMM_THREADS_8, 4) void k_trigemm_sq_pa(const double* __restrict__ W, int64_t ldw,
+                                                                     const double* __restrict__ KsT, int64_t ldk,
+                                                                     const int* __restrict__ jobs, int CT, double* __restrict__ q_part,
+                                                                     int64_t ldq, unsigned long long* clk) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+#if BOHIP_TRACE
+    const unsigned long long t_start = wall_clock64(), c_start = clock64();
+    struct TraceEnd {
+        unsigned long long t0, c0;
+        __device__ ~TraceEnd() {
+            if (threadIdx.x == 0) {
+                unsigned hw, xcc;
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+                unsigned long long* t = g_trace + 6 * (size_t)blockIdx.x;
+                t[0] = t0; t[1] = wall_clock64(); t[2] = hw; t[3] = xcc; t[4] = c0; t[5] = clock64();
+            }
+        }
+    } trace_end{t_start, c_start};
+#endif
+    // an XCD owns the candidate tiles ct = xcd (mod 8) and walks the jobs together, in the table's order (see k_trigemm_sq)
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int n_local = (CT + 7) >> 3;
+    const int ct = xcd + 8 * (slot % n_local);
+    if (ct >= CT) return;
+    const int job = __builtin_amdgcn_readfirstlane(jobs[slot / n_local]);   // (uniform: a scalar load)
+    // timing runs: the sampled core clock, as in k_trigemm_sq
+    __shared__ unsigned long long s_clk[2];
+    if (clk != nullptr && blockIdx.x % 33 == 0 && threadIdx.x == 0) { s_clk[0] = clock64(); s_clk[1] = wall_clock64(); }
+    trigemm_job_rows64(job & 0xffff, job >> 16, ct, W, ldw, KsT, ldk, q_part, ldq, smem, (int)threadIdx.x);
+    if (clk != nullptr && blockIdx.x % 33 == 0 && threadIdx.x == 0) {
+        atomicAdd(clk, (unsigned long long)clock64() - s_clk[0]);
+        atomicAdd(clk + 1, (unsigned long long)wall_clock64() - s_clk[1]);
+    }
+}
+
 // ---- split-K path for batches with too few candidate tiles to fill the chip (a few hundred candidates) -------------
 // With one 64-wide candidate tile column per 64 candidates the longest job (the last row tile, K = N) runs alone on one
 // CU: ~9 us per 128 of K, 215 us at N = 3000 whatever R.  Here the contraction index is cut into slices of kz chunks,
@@ -562,7 +640,7 @@ __global__ __launch_bounds__(256) void k_argmax_final(const Best* __restrict__ i
 
 // ---- pruned arg-max (value-only calls, bohip.hip pruned_pass) ---------------------------------------------------------------
 // A call that returns only the winner need not contract the rows of candidates that provably cannot win.  After the first m row
-// tiles (phase A: k_trigemm_sq over the row pieces with rt < m, all candidates) every candidate gets an UPPER BOUND of the score
+// tiles (phase A: k_trigemm_sq_pa over the 64-row halves of the row pieces with rt < m, all candidates) every candidate gets an UPPER BOUND of the score
 // the full pass would compute for it (k_prune_bound).  Round 1 scores the 64 candidates of highest bound exactly (k_prune_select:
 // the first 64 in (bound desc, index asc) -- of the candidates that share the 64th bound, the lowest indices); its best value
 // L is an exactly computed score.  Round 2 scores exactly every other candidate whose bound is not below L.  A dropped candidate
