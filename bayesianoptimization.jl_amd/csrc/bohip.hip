@@ -132,6 +132,7 @@ struct bohip_gp {
     unsigned* hprune_stat = nullptr;   // pinned: round 2's list length of the last pruned call (prune_wanted)
     unsigned prune_seen = 0;           // the last figure prune_wanted read from it
     bool prune_retry = false;          // the next pruned call is the retry after a back-off (prune_wanted cleared the word)
+    size_t pr_ks_bytes = 0;            // the packed K*' rows at the head of dpr, as the last pruned call laid them out (tests: the poison)
     int prune_r2_form = -1;            // tests (bohip_debug_prune_round2_form): -1 the rule, 0 the steady form, 1 the long form
     int prune_skip = 0;                // value-only calls left on the full pass before pruning is tried again
     // batch selection (bohip_gp_select_batch): V' of ALL candidates, and ONE block [u_i q x ldu | records | scalars | workgroup records | picked]
@@ -1982,13 +1983,10 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     const int T = (int)(Npad / TILE);
     const int64_t P = Npad / 64;   // k_kstar's partial sums: one per wave of observations
     CHK(ensure_pieces(g, T, N));
-    std::vector<int> pa, pb;   // the full pass's row pieces (same modes, same order), split at row tile m
-    for (int c : g->hpieces) ((c & 0xffff) < m ? pa : pb).push_back(c);
     // phase A runs 64-row jobs that write no mu: no piece of the prefix may be a solo half or hold the alpha row
     if (m >= T) return fail(BOHIP_E_STATE, "pruned pass: the prefix holds the alpha row");
-    for (int c : pa)
-        if (c >> 16 != PIECE_WHOLE) return fail(BOHIP_E_STATE, "pruned pass: a half piece in the prefix");
-    const std::vector<int> ph = phase_a_jobs(g->hpieces, m);
+    for (int c : g->hpieces)
+        if ((c & 0xffff) < m && c >> 16 != PIECE_WHOLE) return fail(BOHIP_E_STATE, "pruned pass: a half piece in the prefix");
     // layout (bytes, every part 256-aligned)
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
@@ -2006,8 +2004,23 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     double *ks2 = (double*)(b + o_ks), *q2 = (double*)(b + o_q2), *mu2 = (double*)(b + o_mu2), *ub = (double*)(b + o_ub);
     int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *mark = (int*)(b + o_mark), *pcs = (int*)(b + o_pc);
     const KstarParts kp{g->dW + N * ld, (double*)(b + o_parts), Rpad};
+    g->pr_ks_bytes = o_q2;
     unsigned* cnt = (unsigned*)(b + o_cnt);
     Best* rec = (Best*)(b + o_rec);
+    if (g->timing && !g->dclk) {
+        HIPCHK(hipMalloc(&g->dclk, 2 * sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
+    }
+    g->q_tiles = T;
+    g->score_launches = 1;
+    const KernelHyper hp = make_hyper(g);
+    // K*' first: it needs none of the job tables, and the device has nothing else to do while the host builds them
+    t_begin(g, "kstar");
+    CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp, &kp));
+    t_end(g);
+    std::vector<int> pa, pb;   // the full pass's row pieces (same modes, same order), split at row tile m
+    for (int c : g->hpieces) ((c & 0xffff) < m ? pa : pb).push_back(c);
+    const std::vector<int> ph = phase_a_jobs(g->hpieces, m);
     const std::vector<int> hv = rows_halves(g->hpieces);   // (after the pieces in the table)
     const int nh = rows_halves_from(hv, m);
     std::vector<int> both = pa;
@@ -2019,18 +2032,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         g->hpr_pieces = both;   // (kept alive until the stream has consumed the copy)
         HIPCHK(hipMemcpyAsync(pcs, g->hpr_pieces.data(), both.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
     }
-    if (g->timing && !g->dclk) {
-        HIPCHK(hipMalloc(&g->dclk, 2 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
-    }
-    g->q_tiles = T;
-    g->score_launches = 1;
-    const KernelHyper hp = make_hyper(g);
     const double sigma2 = std::exp(2.0 * g->logsig);
     const int k1 = (int)std::min<int64_t>(PRUNE_K1, R);
-    t_begin(g, "kstar");
-    CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp, &kp));
-    t_end(g);
     // ONE bracket from phase A to the record, under the dense pass's label: what bench.py's roofline divides by
     t_begin(g, "trigemm_sq");
     FuseParams fz{};
@@ -4404,6 +4407,16 @@ int64_t bohip_debug_prune_stat(bohip_gp* g) {
 int bohip_debug_prune_round2_form(bohip_gp* g, int form) {
     if (!g || form < -1 || form > 1) return fail(BOHIP_E_ARG, "bad arguments");
     g->prune_r2_form = form;
+    return 0;
+}
+// tests only (tests/test_prune_poison_gpu.py): the handle's K*' buffer and the pruned pass's packed rows set to all-ones bytes
+// (NaNs), so that a value-only call which reads an element that none of its own launches wrote cannot give the right record
+int bohip_debug_kstar_poison(bohip_gp* g) {
+    if (!g) return fail(BOHIP_E_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(g->device));
+    if (g->dKsT) HIPCHK(hipMemsetAsync(g->dKsT, 0xff, (size_t)(g->kst_rows + TILE) * g->ld * 8, g->stream));
+    if (g->dpr && g->pr_ks_bytes) HIPCHK(hipMemsetAsync(g->dpr, 0xff, std::min(g->pr_ks_bytes, g->pr_bytes), g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     return 0;
 }
 int bohip_debug_set_chol_inv_g(int g_new) {

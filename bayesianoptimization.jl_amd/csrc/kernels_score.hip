@@ -41,6 +41,23 @@ struct KstarParts {
     double* parts;           // [2][Npad / 64][ldp]
     int64_t ldp;
 };
+// One value of K*': k(x_j, x*) from the observation's coordinates xj and weights w (registers; zero weight for d <= k < DT) and the
+// candidate's coordinates xs (wave-uniform, in LDS); live = j < N, else the zero of the padding columns N <= j < Npad.  Every
+// k_kstar instantiation goes through here, so a value does not depend on the instantiation that wrote it.
+// (The PARTS launch stores all of K*', 100 MB a bench step, of which phase A and round 1 read 14 MB.  Storing only what is read and
+// filling the tails of listed rows in two small launches was built and measured: the store is free -- the kernel is bound by
+// VALU issue, ~85 instructions a value -- and the fills are 10 us on top.  profiles/prune_kstar_store_ab.txt)
+template <int DT, bool LOW>
+__device__ __forceinline__ double kstar_value(const double (&xj)[DT], const double (&w)[DT], const double* xs, bool live, int fam,
+                                              double sigma2) {
+    double rr = 0.0;
+#pragma unroll
+    for (int k = 0; k < DT; ++k) {
+        const double t = xj[k] - xs[k];
+        rr += w[k] * (t * t);
+    }
+    return live ? cov_from_r_fast<LOW>(fam, sigma2, rr) : 0.0;
+}
 // Sum over the wave's 64 lanes of 16 values per lane (one per candidate) by halving: a lane gives away half of what it holds and
 // adds the other lane's half of the rest.  The candidates come four at a time (one group: their `exp`s overlap, and no more than
 // a group's values are live): lane ^ 32 and ^ 16 take a group's 4 values to 1, lane ^ 8 two groups' values to 1 as soon as
@@ -114,13 +131,7 @@ __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int
                 const int c = 4 * g + i;
                 p[i] = 0.0;
                 if (c < nc) {
-                    double rr = 0.0;
-#pragma unroll
-                    for (int k = 0; k < DT; ++k) {
-                        const double t = xj[k] - xs_l[c * DT + k];
-                        rr += w[k] * (t * t);
-                    }
-                    const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
+                    const double v = kstar_value<DT, LOW>(xj, w, xs_l + c * DT, j < N, hp.fam, hp.sigma2);
                     KsT[(r0 + c - r_begin) * ldk + j] = v;
                     p[i] = aj * v;   // v exactly as stored
                 }
@@ -146,13 +157,7 @@ __global__ __launch_bounds__(256) void k_kstar(const double* __restrict__ X, int
         }
     } else {
         for (int c = 0; c < nc; ++c) {
-            double rr = 0.0;
-#pragma unroll
-            for (int k = 0; k < DT; ++k) {
-                const double t = xj[k] - xs_l[c * DT + k];
-                rr += w[k] * (t * t);
-            }
-            const double v = (j < N) ? cov_from_r_fast<LOW>(hp.fam, hp.sigma2, rr) : 0.0;
+            const double v = kstar_value<DT, LOW>(xj, w, xs_l + c * DT, j < N, hp.fam, hp.sigma2);
             KsT[(r0 + c - r_begin) * ldk + j] = v;   // plain stores: non-temporal ones evict K*' from L2/MALL and k_trigemm_sq
                                                        // then runs at 0.70 instead of 0.635 ms (measured)
         }
