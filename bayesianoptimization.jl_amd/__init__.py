@@ -7,7 +7,8 @@ libbohip.so (HIP, gfx950).  See DESIGN.md / INTEGRATION.md.
 from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
-                    mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble)
+                    mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
+                    score_ensemble_grad)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, Marginalised, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,

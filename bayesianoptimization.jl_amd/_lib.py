@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -164,6 +164,12 @@ ENS_SIGNATURES = {
     "bohip_gp_score_ens": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, _i64p, C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_ens_grad.h declares (the gradient of that average, on the device)
+ENS_GRAD_SIGNATURES = {
+    "bohip_gp_score_ens_grad": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i64p,
+                                          C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -220,7 +226,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
-                              + list(ENS_SIGNATURES.items())):
+                              + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

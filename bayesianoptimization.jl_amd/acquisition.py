@@ -135,9 +135,11 @@ class Marginalised(AbstractAcquisition):
     Adams 2012 (include/bohip_ens.h).  An extension: the reference has no such type, and no default uses it.  `a` is
     one of the functors of (mu, sigma^2): ExpectedImprovement, ProbabilityOfImprovement, UpperConfidenceBound, MutualInformation,
     MaxMean, LogExpectedImprovement.  setparams_ forwards to `a` (tau = max y, UCB's beta schedule, MI's gamma-hat: all taken
-    under the model's own, highest-likelihood setting).  VALUE ONLY: there is no gradient of the average and no device ascent --
-    acquisitionfunction maps a d x R matrix to the averaged scores (model.score_ensemble), and acquire_max takes the arg-max over
-    `maxeval` Latin-hypercube candidates per restart."""
+    under the model's own, highest-likelihood setting).  VALUE ONLY by default: acquisitionfunction maps a d x R matrix to the
+    averaged scores (model.score_ensemble), and acquire_max takes the arg-max over `maxeval` Latin-hypercube candidates per restart.
+    With the option "refine": n > 0 the n best candidates are then climbed by the batched L-BFGS ascent on the gradient of the average
+    (model.score_ensemble_grad, include/bohip_ens_grad.h).  "refine" belongs to this type alone: every other
+    acquisition accepts the key unused (BOpt shares one options record with its MaxMean search)."""
     TAKES = ("EI", "PI", "UCB", "MI", "MaxMean", "LogEI")
 
     def __init__(self, a):
@@ -500,8 +502,12 @@ def _warn_not_a_local_search(method):
 # of the posterior (model.sample_joint) instead of independent per-candidate draws (model.thompson).  Default False.
 # "pathwise" (with "features" = M, default 2048) is this package's own too: ThompsonSamplingSimple searches ONE posterior sample
 # path per restart (model.draw_paths), a function that keeps its value wherever it is evaluated again.  Default False.
+# "refine" (default 0) is this package's own as well: Marginalised climbs its n best candidates on the gradient of the average.
+# Every other acquisition accepts the key and does NOT use it -- their search is chosen by "method" (:LD_LBFGS climbs already) --
+# because BOpt hands ONE options record to the acquisition's search and to its closing MaxMean search (acquire_model_max): a
+# record written for Marginalised must pass there.
 _OPTS_USED = {"method", "restarts", "maxeval", "maxtime", "ftol_rel", "xtol_abs", "ftol_abs", "xtol_rel", "stopval", "joint",
-              "pathwise", "features"}
+              "pathwise", "features", "refine"}
 _OPTS_NLOPT_ONLY = {"initial_step", "population", "vector_storage", "seed", "local_optimizer", "default_initial_step"}
 
 
@@ -581,19 +587,53 @@ def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng):
     return maxf, maxx
 
 
-def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng):
-    """Marginalised(a): value only, no gradient and no device ascent.  Every restart scores `maxeval` Latin-hypercube candidates
-    under all hyper-parameter samples in ONE model.score_ensemble call and takes its arg-max record.  The first maximum over the
-    restarts wins (strict '>')."""
+def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts=None):
+    """Marginalised(a).  Every restart scores `maxeval` Latin-hypercube candidates under all hyper-parameter samples in ONE
+    model.score_ensemble call and takes its arg-max record.  The first maximum over the restarts wins (strict '>').
+    "refine": n > 0 (default 0: the candidate stage alone, the same calls and draws as without the option): the n highest-scoring
+    distinct candidates of all restarts then start ONE batched L-BFGS ascent inside the box, fg = one model.score_ensemble_grad call
+    per step, at most `maxeval` evaluations, the tolerances of the other acquisitions; the best ascended point replaces the candidate
+    maximum only where it is strictly better, so the result is never worse than with refine = 0."""
     Theta, w = _hyper_samples(model)
     if not hasattr(model, "score_ensemble"):
         raise NotImplementedError(f"{type(model).__name__} has no score_ensemble")
+    opts = opts or {}
+    refine = int(opts.get("refine", 0) or 0)
+    if refine > 0 and not hasattr(model, "score_ensemble_grad"):
+        raise NotImplementedError(f"{type(model).__name__} has no score_ensemble_grad")
     maxf, maxx = -math.inf, lb.copy()
+    seen_x, seen_f = [], []
     for _ in range(restarts):
         xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
         res = model.score_ensemble(a.acq_id, a.params(), xs, Theta, w)
         if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
             maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+        if refine > 0:
+            seen_x.append(xs)
+            seen_f.append(np.asarray(res.scores, dtype=np.float64))
+    if refine > 0 and np.isfinite(maxf):
+        X, f = np.concatenate(seen_x, axis=1), np.concatenate(seen_f)
+        starts, taken = [], set()
+        for j in np.argsort(-np.where(np.isnan(f), -math.inf, f), kind="stable"):
+            key = X[:, j].tobytes()
+            if np.isfinite(f[j]) and key not in taken:
+                taken.add(key)
+                starts.append(X[:, j])
+                if len(starts) == refine:
+                    break
+        p = a.params()
+
+        def fg(Z):
+            r, g = model.score_ensemble_grad(a.acq_id, p, Z, Theta, w)[:2]
+            return np.asarray(r.scores, dtype=np.float64), np.asarray(g, dtype=np.float64)
+
+        fa, Xa = _batched_lbfgs_ascent(fg, np.asfortranarray(np.stack(starts, axis=1)), lb, ub, max(2, maxeval),
+                                       ftol_rel=float(opts.get("ftol_rel", 1e-10)), xtol_abs=float(opts.get("xtol_abs", 1e-10)),
+                                       ftol_abs=float(opts.get("ftol_abs", 0.0)), xtol_rel=float(opts.get("xtol_rel", 0.0)),
+                                       stopval=float(opts.get("stopval", math.inf)))
+        j = int(np.argmax(np.where(np.isnan(fa), -math.inf, fa)))
+        if fa[j] > maxf:                                          # strict '>': never worse than the candidate maximum
+            maxf, maxx = float(fa[j]), Xa[:, j].copy()
     if not np.isfinite(maxf):
         warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
     return maxf, maxx
@@ -620,8 +660,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return maxf, maxx
     if isinstance(a, KnowledgeGradient):                          # (`method` has nothing to select between: accepted, not used)
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
-    if isinstance(a, Marginalised):                               # (value only: `method` is accepted, not used)
-        return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, Marginalised):                               # (`method` is accepted, not used; "refine" adds the ascent)
+        return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31
     if bool(opts.get("pathwise", False)):
         if not isinstance(a, ThompsonSamplingSimple):

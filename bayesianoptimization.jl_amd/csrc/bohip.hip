@@ -21,6 +21,7 @@
 #include "../../include/bohip_acq.h"
 #include "../../include/bohip_kg.h"
 #include "../../include/bohip_ens.h"
+#include "../../include/bohip_ens_grad.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -182,6 +183,15 @@ struct bohip_gp {
     // [theta | w | w~ | pivot | xs chunk | each, mu, var H x Rc | scores R | workgroup records | record]
     char* ens_io = nullptr;
     size_t ens_io_bytes = 0;
+    // its gradient (bohip_gp_score_ens_grad): alpha = W' z per setting, and what the slabs hold -- the factors of ens_theta for the
+    // observations of version ens_version, left by that symbol (ens_factor_ok) -- so that the next call with the same theta skips the factor stage
+    double* ens_alpha = nullptr;
+    size_t ens_alpha_bytes = 0;
+    bool ens_factor_ok = false;
+    std::vector<double> ens_theta;
+    std::vector<long long> ens_pivot;
+    uint64_t ens_version = 0;
+    uint64_t data_version = 0;   // raised by whatever changes X or y
     double *dVV = nullptr, *dcov = nullptr;  // [Rp][Rp] V'V (lower tiles) and the full posterior covariance
     int64_t cov_cap = 0;
     // joint sampler (bohip_gp_sample_joint): a factor workspace the model does not own -- matrix, panel scratch, the 128 x 128
@@ -2336,6 +2346,7 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->ddmll_parts) hipFree(g->ddmll_parts);
     if (g->fit_ws) hipFree(g->fit_ws);
     if (g->ens_io) hipFree(g->ens_io);
+    if (g->ens_alpha) hipFree(g->ens_alpha);
     if (g->fit_io) hipFree(g->fit_io);
     if (g->dVV) hipFree(g->dVV);
     if (g->dcov) hipFree(g->dcov);
@@ -2377,6 +2388,7 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
     int rc = 0;
     bool done = false;
     if (p > 0) {
+        ++g->data_version;
         const int64_t n_old = g->n, n_new = g->n + p;
         if (n_new > g->cap) {
             // growth: alloc_model re-uploads everything from the host mirrors, so they are extended first -- and rolled
@@ -2589,6 +2601,7 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
     size_t cap = FIT_WS_CAP_BYTES;
     if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
     const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(H, (int64_t)(cap / (slab * 8))));
+    g->ens_factor_ok = false;   // (the slabs are about to be written)
     if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {
         if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
         g->fit_ws = nullptr; g->fit_ws_bytes = 0;
@@ -2706,6 +2719,7 @@ int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_
     if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
     // (settings are the y dimension of k_ens_score's grid: at most 65535 per launch)
     const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(H, 65535), (int64_t)(cap / (slab * 8))));
+    g->ens_factor_ok = false;   // (the slabs are about to be written)
     if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {
         if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
         g->fit_ws = nullptr; g->fit_ws_bytes = 0;
@@ -2800,6 +2814,193 @@ int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_
     if (alive == 0 || !(alive_w > 0.0)) {
         best->val = -INFINITY; best->idx = -1;
         if (scores) for (int64_t j = 0; j < R; ++j) scores[j] = NAN;
+        return fail(BOHIP_E_NOTPD, alive == 0 ? "the factorisation failed at every hyper-parameter setting"
+                                              : "the factorisation failed at every hyper-parameter setting of positive weight");
+    }
+    best->val = hb.val; best->idx = hb.idx;
+    return 0;
+}
+
+// ---- its gradient (include/bohip_ens_grad.h, kernels_ens.hip: k_ens_alpha, k_ens_grad, k_ens_reduce_grad) --------------------------
+extern "C++" {
+template <int DT>
+static int ens_grad_launch(bohip_gp* g, const EnsGradArgs& a, int64_t Hc, bool lo) {
+    static bool done_dev[64] = {false};   // the > 64 KB dynamic-LDS opt-in is a per-device function attribute
+    if (!done_dev[g->device & 63]) {
+        const int s = (int)ens_grad_lds_bytes(BOHIP_FIT_NMAX, DT);
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        done_dev[g->device & 63] = true;
+    }
+    const dim3 grid((unsigned)((a.R + ENS_TC - 1) / ENS_TC), (unsigned)Hc);
+    LAUNCH_FAM(lo, (k_ens_grad<DT, true>), (k_ens_grad<DT, false>), grid, dim3(ENS_THREADS), ens_grad_lds_bytes(a.M, DT), g->stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}   // extern "C++"
+
+int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
+                            const double* xs, int64_t R, double* scores, double* grad, double* each, double* each_grad, double* mu,
+                            double* var, int64_t* pivot, bohip_best* best) {
+    if (!g || !theta || !xs || !best || !grad) return fail(BOHIP_E_ARG, "null argument");
+    if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
+    if (R < 1) return fail(BOHIP_E_ARG, "R must be >= 1");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id (Thompson draws are not averaged)");
+    AcqParams ap;
+    CHK(make_acq(acq_id, acq_params, &ap));
+    if (weights) {
+        double s = 0.0;
+        for (int64_t h = 0; h < H; ++h) {
+            if (!(weights[h] >= 0.0 && weights[h] < INFINITY)) return fail(BOHIP_E_ARG, "weights must be finite and >= 0");
+            s += weights[h];
+        }
+        if (!(s > 0.0)) return fail(BOHIP_E_ARG, "the weights sum to 0");
+    }
+    if (g->n == 0) return fail(BOHIP_E_STATE, "no observations");
+    if (g->n > BOHIP_FIT_NMAX)
+        return fail(BOHIP_E_UNSUPPORTED, "the marginalised acquisition takes at most " + std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " +
+                                             std::to_string(g->n));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    // the observations as the device holds them: the call reads dX / dy and nothing else of the model, and never refits
+    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
+    if (g->mirror_dirty) {
+        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        g->mirror_dirty = false;
+    }
+    const int iso = kern_iso(g->kern), P = 2 + (iso ? 2 : g->d + 1), d = g->d;
+    const int M = (int)round_up(g->n, FIT_NB), ld = M + 8;
+    const size_t slab = (size_t)(2 * M + 1) * ld;
+    size_t cap = FIT_WS_CAP_BYTES;
+    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
+    const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(H, 65535), (int64_t)(cap / (slab * 8))));
+    const bool resident = H <= Hc;   // every setting's factor fits the workspace at once: factor once, before the candidate chunks
+    // the slabs hold these very factors: every setting at once, left by this symbol for byte-identical theta and the same observations
+    // (M follows from the observations; the kernel and d of a handle never change)
+    const bool reuse = resident && g->ens_factor_ok && g->ens_version == g->data_version && g->ens_theta.size() == (size_t)H * P &&
+                       g->ens_pivot.size() == (size_t)H && std::memcmp(g->ens_theta.data(), theta, (size_t)H * P * 8) == 0;
+    g->ens_factor_ok = false;   // (whatever fails below: the next call factors)
+    if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {   // (never on a reuse: the same theta and M ask for the same bytes)
+        if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
+        g->fit_ws = nullptr; g->fit_ws_bytes = 0;
+        HIPCHK(hipMalloc(&g->fit_ws, (size_t)Hc * slab * 8));
+        g->fit_ws_bytes = (size_t)Hc * slab * 8;
+    }
+    if (g->ens_alpha_bytes < (size_t)Hc * M * 8) {
+        if (g->ens_alpha) HIPCHK(hipFree(g->ens_alpha));
+        g->ens_alpha = nullptr; g->ens_alpha_bytes = 0;
+        HIPCHK(hipMalloc(&g->ens_alpha, (size_t)Hc * M * 8));
+        g->ens_alpha_bytes = (size_t)Hc * M * 8;
+    }
+    // candidates per chunk: the (3 + d) H x Rc planes stay within 64 MiB (at least one tile, at most 16384 candidates)
+    const int64_t Rc = std::min<int64_t>(
+        round_up(R, ENS_TC), std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (8 * (3 + (int64_t)d) * H)) / ENS_TC * ENS_TC)));
+    int64_t nblk = 0;
+    for (int64_t r0 = 0; r0 < R; r0 += Rc) nblk += (std::min(Rc, R - r0) + 255) / 256;
+    const size_t n_dbl = (size_t)H * P + 3 * (size_t)H + (size_t)Rc * d + (3 + (size_t)d) * H * Rc + (size_t)R + (size_t)R * d;
+    const size_t io_bytes = n_dbl * 8 + (size_t)(nblk + 1) * sizeof(Best);
+    if (g->ens_io_bytes < io_bytes) {
+        if (g->ens_io) HIPCHK(hipFree(g->ens_io));
+        g->ens_io = nullptr; g->ens_io_bytes = 0;
+        HIPCHK(hipMalloc(&g->ens_io, io_bytes));
+        g->ens_io_bytes = io_bytes;
+    }
+    double* d_theta = reinterpret_cast<double*>(g->ens_io);
+    double* d_w = d_theta + (size_t)H * P;
+    double* d_wt = d_w + H;
+    long long* d_pivot = reinterpret_cast<long long*>(d_wt + H);
+    double* d_xs = d_wt + 2 * (size_t)H;
+    double* d_each = d_xs + (size_t)Rc * d;
+    double* d_mu = d_each + (size_t)H * Rc;
+    double* d_var = d_mu + (size_t)H * Rc;
+    double* d_geach = d_var + (size_t)H * Rc;
+    double* d_scores = d_geach + (size_t)H * Rc * d;
+    double* d_grad = d_scores + R;
+    Best* d_blk = reinterpret_cast<Best*>(d_grad + (size_t)R * d);
+    Best* d_best = d_blk + nblk;
+    HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
+    if (weights) HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
+    if (reuse) HIPCHK(hipMemcpyAsync(d_pivot, g->ens_pivot.data(), (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
+    const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
+    auto factor = [&](int64_t h0, int64_t hc) -> int {
+        EnsFactorArgs a{};
+        a.X = g->dX; a.y = g->dy; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0;
+        a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
+        t_begin(g, "ens_factor");
+        CHK(dispatch_dt(d, [&](auto dt) { return ens_factor_launch<decltype(dt)::value>(g, a, hc, lo); }));
+        t_end(g);
+        t_begin(g, "ens_alpha");
+        hipLaunchKernelGGL(k_ens_alpha, dim3((unsigned)hc), dim3(256), 0, g->stream, g->fit_ws, d_pivot + h0, g->ens_alpha, (long long)slab, M, ld);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        return 0;
+    };
+    if (resident && !reuse) CHK(factor(0, H));
+    int64_t blk0 = 0;
+    for (int64_t r0 = 0; r0 < R; r0 += Rc) {
+        const int64_t rc = std::min(Rc, R - r0);
+        HIPCHK(hipMemcpyAsync(d_xs, xs + (size_t)r0 * d, (size_t)rc * d * 8, hipMemcpyHostToDevice, g->stream));
+        for (int64_t h0 = 0; h0 < H; h0 += Hc) {
+            const int64_t hc = std::min(Hc, H - h0);
+            if (!resident) CHK(factor(h0, hc));
+            EnsGradArgs a{};
+            a.X = g->dX; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0; a.xs = d_xs;
+            a.each = d_each + (size_t)h0 * Rc; a.mu = d_mu + (size_t)h0 * Rc; a.var = d_var + (size_t)h0 * Rc;
+            a.slab = (long long)slab; a.ldr = Rc; a.R = rc; a.ap = ap;
+            a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
+            a.alpha = g->ens_alpha; a.geach = d_geach + (size_t)h0 * Rc * d;
+            t_begin(g, "ens_grad");
+            CHK(dispatch_dt(d, [&](auto dt) { return ens_grad_launch<decltype(dt)::value>(g, a, hc, lo); }));
+            t_end(g);
+        }
+        t_begin(g, "ens_reduce");
+        if (r0 == 0) hipLaunchKernelGGL(k_ens_weights, dim3(1), dim3(64), 0, g->stream, weights ? d_w : nullptr, d_pivot, (long long)H, d_wt);
+        const int nb256 = (int)((rc + 255) / 256);
+        hipLaunchKernelGGL(k_ens_reduce, dim3(nb256), dim3(256), 0, g->stream, d_each, (long long)Rc, d_wt, (long long)H, (long long)rc,
+                           (long long)r0, d_scores, d_blk + blk0);
+        hipLaunchKernelGGL(k_ens_reduce_grad, dim3((unsigned)((rc * d + 255) / 256)), dim3(256), 0, g->stream, d_geach, (long long)(Rc * d), d_wt,
+                           (long long)H, (long long)(rc * d), d_grad + (size_t)r0 * d);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        blk0 += nb256;
+        for (auto pr : {std::make_pair(each, d_each), std::make_pair(mu, d_mu), std::make_pair(var, d_var)})
+            if (pr.first)
+                HIPCHK(hipMemcpy2DAsync(pr.first + r0, (size_t)R * 8, pr.second, (size_t)Rc * 8, (size_t)rc * 8, (size_t)H, hipMemcpyDeviceToHost,
+                                        g->stream));
+        if (each_grad)
+            HIPCHK(hipMemcpy2DAsync(each_grad + (size_t)r0 * d, (size_t)R * d * 8, d_geach, (size_t)Rc * d * 8, (size_t)rc * d * 8, (size_t)H,
+                                    hipMemcpyDeviceToHost, g->stream));
+        if (r0 + Rc < R) HIPCHK(hipStreamSynchronize(g->stream));   // the chunk's planes and d_xs are free again
+    }
+    t_begin(g, "ens_reduce");
+    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, d_blk, (int)nblk, d_best, 0LL);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    std::vector<long long> hpiv((size_t)H);
+    Best hb{-INFINITY, -1};
+    HIPCHK(hipMemcpyAsync(hpiv.data(), d_pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&hb, d_best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    if (scores) HIPCHK(hipMemcpyAsync(scores, d_scores, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(grad, d_grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    if (resident) {   // the slabs and alpha now hold every setting's factor
+        g->ens_theta.assign(theta, theta + (size_t)H * P);
+        g->ens_pivot = hpiv;
+        g->ens_version = g->data_version;
+        g->ens_factor_ok = true;
+    }
+    if (pivot) for (int64_t h = 0; h < H; ++h) pivot[h] = hpiv[(size_t)h];
+    double alive_w = 0.0;
+    int64_t alive = 0;
+    for (int64_t h = 0; h < H; ++h)
+        if (hpiv[(size_t)h] == 0) { ++alive; alive_w += weights ? weights[h] : 1.0; }
+    if (alive == 0 || !(alive_w > 0.0)) {
+        best->val = -INFINITY; best->idx = -1;
+        if (scores) for (int64_t j = 0; j < R; ++j) scores[j] = NAN;
+        for (int64_t j = 0; j < R * d; ++j) grad[j] = NAN;
         return fail(BOHIP_E_NOTPD, alive == 0 ? "the factorisation failed at every hyper-parameter setting"
                                               : "the factorisation failed at every hyper-parameter setting of positive weight");
     }

@@ -16,6 +16,19 @@
 //                 ascending h from 0.0, settings with w~ = 0 skipped; per-workgroup arg-max records for k_argmax_final.
 // What is computed for (theta_h, x_j) depends on (model, theta_h, x_j) alone: a candidate's column of the MFMA products, its shuffles
 // and its sums see the same operations at every position of a tile, for every R, H and split into launches.
+//
+// The gradient (bohip_gp_score_ens_grad in include/bohip_ens_grad.h) adds
+//   k_ens_alpha   one workgroup per setting behind k_ens_factor: alpha = W' z, column j summed over the rows i >= j in ascending order,
+//                 into a block of its own ([settings of the launch][M]).
+//   k_ens_grad    k_ens_score instantiated with the gradient's arguments (ONE text for the K*' tile, the V stage and the finish: the
+//                 value path and the gradient path agree bit for bit; the value-only instantiation compiles to the code it had) with V
+//                 kept in a second 16 x (M + 1) LDS tile; then U = W' V on the matrix pipe (a wave owns a 16-row block J of U and
+//                 walks I >= J in ascending order, W's fragments read transposed) into the tile K*' has left; then the final stage: r and fx = 2 dk/dr
+//                 again from X, the candidates and il2 (rolled over d), fx alpha and fx U over the two tiles, and per (candidate,
+//                 coordinate) the sums  sum_j fx_j alpha_j il2_k (x_k - X_jk)  and  sum_j fx_j U_j il2_k (x_k - X_jk)  over the
+//                 observations in ascending order by ONE thread, so the order is the same at every position of a tile;
+//                 g_h = da/dmu grad mu + (sigma^2 > 0 ? da/dsigma^2 (-2 sum) : 0), k_grad_finish's rule for a clamped variance.
+//   k_ens_reduce_grad   grad[j][k] = sum_h w~_h g_h[j][k], sequentially in ascending h from 0.0, settings with w~ = 0 skipped.
 #include "gemm_core.h"   // mfma444
 
 namespace bohip {
@@ -43,12 +56,25 @@ struct EnsScoreArgs {
     long long slab, ldr, R;
     AcqParams ap;
     int N, M, ld, d, fam, iso, P;
+    static constexpr bool GRAD = false;
+};
+
+struct EnsGradArgs : EnsScoreArgs {
+    const double* alpha;   // [settings of the launch][M]  W' z (k_ens_alpha)
+    double* geach;         // [H][ldr][d] per-setting gradients
+    static constexpr bool GRAD = true;
 };
 
 // LDS of k_ens_score in doubles: [Ks 16 x (M + 1) | z M | il2 DMAX | xs tile 16 x DT, later the block sums 2 x 16 per row block]
 __host__ __device__ inline size_t ens_score_lds_bytes(int M, int DT) {
     const int a = ENS_TC * DT, b = 2 * ENS_TC * (M / FIT_NB);
     return (size_t)(ENS_TC * (M + 1) + M + DMAX + (a > b ? a : b)) * 8;
+}
+
+// LDS of k_ens_grad in doubles: [Ks, later U and fx U 16 x (M + 1) | V, later fx alpha 16 x (M + 1) | z M | alpha M | il2 DMAX |
+// xs tile 16 x DT | block sums 2 x 16 per row block | da/dmu, da/dsigma^2, sigma^2 per candidate]: 156 800 B at M = 512, DT = 64
+__host__ __device__ inline size_t ens_grad_lds_bytes(int M, int DT) {
+    return (size_t)(2 * ENS_TC * (M + 1) + 2 * M + DMAX + ENS_TC * DT + 2 * ENS_TC * (M / FIT_NB) + 3 * ENS_TC) * 8;
 }
 
 template <int DT, bool LOW>
@@ -261,8 +287,26 @@ __global__ __launch_bounds__(FIT_THREADS) void k_ens_factor(EnsFactorArgs a) {
     }
 }
 
-template <int DT, bool LOW>
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_score(EnsScoreArgs a) {
+// fx = 2 dk/dr of the final stage: k_grad_finish's expressions (common.h for the Matérn 1/2 and 3/2 families: 0 at r = 0 for 1/2)
+template <bool LOW>
+__device__ __forceinline__ double ens_fx(int fam, double sigma2, double r) {
+#pragma clang fp contract(off)
+    if constexpr (LOW) {
+        return matern_lo_fx(fam, sigma2, r);
+    } else if (fam == FAM_M52) {
+        const double s = sqrt(5.0) * sqrt(r);
+        return -(5.0 / 3.0) * sigma2 * (1.0 + s) * exp(-s);
+    } else {
+        return -(sigma2 * exp(-0.5 * r));
+    }
+}
+
+// Args = EnsScoreArgs: the value kernel, the code it has always had.  Args = EnsGradArgs: k_ens_grad (below) -- ONE text for the K*'
+// tile, the V stage and the finish, so the two give the same mu, sigma^2 and a_h bit for bit; what the gradient adds sits behind
+// `if constexpr (GRAD)`.  (The body stays in the kernel: as an inlined device function the value-only code came out different.)
+template <int DT, bool LOW, class Args = EnsScoreArgs>
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_score(Args a) {
+    constexpr bool GRAD = Args::GRAD;
     extern __shared__ double ens_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = a.N, M = a.M, ld = a.ld, d = a.d, P = a.P;
@@ -270,13 +314,19 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_score(EnsScoreArgs a) {
     const int64_t h = blockIdx.y, j0 = (int64_t)blockIdx.x * ENS_TC;
     const int nc = (int)(a.R - j0 < ENS_TC ? a.R - j0 : ENS_TC);
     double* const Ks = ens_smem;
-    double* const zs = Ks + ENS_TC * kld;
-    double* const il2s = zs + M;
+    double* const Vs = Ks + ENS_TC * kld;                    // (GRAD)
+    double* const zs = GRAD ? Vs + ENS_TC * kld : Ks + ENS_TC * kld;
+    double* const als = zs + M;                              // (GRAD)
+    double* const il2s = GRAD ? als + M : zs + M;
     double* const xt = il2s + DMAX;
-    double* const part = xt;   // (the candidates are read for the last time before the barrier behind the K*' tile)
+    // value only: the candidates are read for the last time before the barrier behind the K*' tile; the gradient's final stage reads them again
+    double* const part = GRAD ? xt + ENS_TC * DT : xt;
+    double* const pd = part + 2 * ENS_TC * nb;               // (GRAD) [da/dmu | da/dsigma^2 | sigma^2] x 16
     const int64_t o = h * a.ldr + j0;
     if (a.pivot[h] != 0) {   // the same for every thread
         if (tid < nc) { a.each[o + tid] = NAN; a.mu[o + tid] = NAN; a.var[o + tid] = NAN; }
+        if constexpr (GRAD)
+            for (int t = tid; t < nc * d; t += ENS_THREADS) a.geach[o * d + t] = NAN;
         return;
     }
     const double* th = a.theta + h * P;
@@ -290,6 +340,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_score(EnsScoreArgs a) {
         xt[t] = (c < nc && k < d) ? a.xs[(j0 + c) * d + k] : 0.0;
     }
     for (int i = tid; i < M; i += ENS_THREADS) zs[i] = A[(int64_t)M * ld + i];
+    if constexpr (GRAD)
+        for (int i = tid; i < M; i += ENS_THREADS) als[i] = a.alpha[h * M + i];
     __syncthreads();
 
     // ---- K*' tile: Ks[c][i] = k(x_i, xs_c; theta_h), 0 on the padding rows ------------------------------------------------------
@@ -363,6 +415,12 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_score(EnsScoreArgs a) {
                     part[(2 * I + 1) * ENS_TC + 8 * cb + lane] = m;
                 }
             }
+            if constexpr (GRAD) {   // V outlives its block: the lane's four entries into the second tile, candidate-major as K*'
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb) Vs[(8 * cb + bc) * kld + FIT_NB * I + 8 * rb + dr] = acc[rb][cb];
+            }
         }
     }
     __syncthreads();
@@ -379,6 +437,139 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_score(EnsScoreArgs a) {
         a.mu[o + tid] = mu;
         a.var[o + tid] = s2;
         a.each[o + tid] = acq_eval(a.ap, mu, s2);
+        if constexpr (GRAD) {
+            double dmu, ds2;
+            acq_partials(a.ap, mu, s2, dmu, ds2);
+            pd[tid] = dmu;
+            pd[ENS_TC + tid] = ds2;
+            pd[2 * ENS_TC + tid] = s2;
+        }
+    }
+    if constexpr (GRAD) {
+        double* const Us = Ks;   // (every wave has read K*' for the last time before the barrier above)
+        // ---- U = W' V: block J of U is the sum over I >= J of W_IJ' V_I, I ascending; the arrangement of the V stage with W read transposed
+        {
+#pragma clang fp contract(off)
+            const int kq = lane >> 4, bb = (lane >> 2) & 3, t = lane & 3;
+            const int ar = 4 * (bb >> 1) + t, bc = 4 * (bb & 1) + t;
+            const int dr = 4 * (bb >> 1) + (lane >> 4);
+            for (int J = wave; J < nb; J += ENS_THREADS / 64) {
+                double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+                const double* wcol0 = W + (int64_t)(4 * kq) * ld + FIT_NB * J + ar;   // A[r][m] = W[16 I + m][16 J + r], m = 4 kq + s
+                const double* vrow0 = Vs + bc * kld + 4 * kq;
+                const double* vrow1 = vrow0 + 8 * kld;
+                for (int I = J; I < nb; ++I) {
+                    double av[2][4], bv[2][4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        av[0][s] = wcol0[(int64_t)(FIT_NB * I + s) * ld];
+                        av[1][s] = wcol0[(int64_t)(FIT_NB * I + s) * ld + 8];
+                        bv[0][s] = vrow0[FIT_NB * I + s];
+                        bv[1][s] = vrow1[FIT_NB * I + s];
+                    }
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+#pragma unroll
+                        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                            for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mfma444(av[rb][s], bv[cb][s], acc[rb][cb]);
+                }
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb) Us[(8 * cb + bc) * kld + FIT_NB * J + 8 * rb + dr] = acc[rb][cb];
+            }
+        }
+        __syncthreads();
+        // ---- final stage, first half: r and fx again per (observation, candidate); the tiles become fx alpha (V's) and fx U (in place)
+        {
+#pragma clang fp contract(off)
+            for (int i = tid; i < N; i += ENS_THREADS) {
+                double r[ENS_TC];
+#pragma unroll
+                for (int c = 0; c < ENS_TC; ++c) r[c] = 0.0;
+#pragma unroll 1
+                for (int k = 0; k < d; ++k) {   // (rolled, as the K*' tile and for its reason; the same r bit for bit)
+                    const double x = a.X[(int64_t)i * d + k];
+                    const double l = il2s[k];
+#pragma unroll
+                    for (int c = 0; c < ENS_TC; ++c) {
+                        const double t = x - xt[c * DT + k];
+                        r[c] += l * (t * t);
+                    }
+                }
+                const double al = als[i];
+#pragma unroll
+                for (int c = 0; c < ENS_TC; ++c) {
+                    const double fx = ens_fx<LOW>(a.fam, sigma2, r[c]);
+                    Vs[c * kld + i] = fx * al;
+                    Us[c * kld + i] = fx * Us[c * kld + i];
+                }
+            }
+        }
+        __syncthreads();
+        // ---- final stage, second half: thread (candidate c, coordinates k = t, t + 16, ...) adds its two sums over the observations in
+        // ascending order -- the order does not depend on the candidate's slot -- and applies the chain rule
+        {
+#pragma clang fp contract(off)
+            constexpr int KPT = (DT + 15) / 16;
+            const int c = tid >> 4, t = tid & 15;
+            double gm[KPT], gv[KPT], xc[KPT], il[KPT];
+#pragma unroll
+            for (int q = 0; q < KPT; ++q) {
+                const int k = t + 16 * q;
+                gm[q] = 0.0;
+                gv[q] = 0.0;
+                xc[q] = k < d ? xt[c * DT + k] : 0.0;
+                il[q] = k < d ? il2s[k] : 0.0;
+            }
+            if (t < d) {
+                const double* pa = Vs + c * kld;
+                const double* pu = Us + c * kld;
+#pragma unroll 8
+                for (int j = 0; j < N; ++j) {
+                    const double p = pa[j], u = pu[j];
+#pragma unroll
+                    for (int q = 0; q < KPT; ++q) {
+                        const int k = t + 16 * q;
+                        const double dx = (xc[q] - (k < d ? a.X[(int64_t)j * d + k] : 0.0)) * il[q];
+                        gm[q] += p * dx;
+                        gv[q] += u * dx;
+                    }
+                }
+                if (c < nc) {
+                    const double dmu = pd[c], ds2 = pd[ENS_TC + c], s2 = pd[2 * ENS_TC + c];
+#pragma unroll
+                    for (int q = 0; q < KPT; ++q) {
+                        const int k = t + 16 * q;
+                        // a clamped variance (sigma^2 == 0 exactly) has zero gradient (k_grad_finish)
+                        if (k < d) a.geach[(o + c) * d + k] = dmu * gm[q] + (s2 > 0.0 ? ds2 * (-2.0 * gv[q]) : 0.0);
+                    }
+                }
+            }
+        }
+    }
+}
+
+
+template <int DT, bool LOW>
+constexpr auto k_ens_grad = &k_ens_score<DT, LOW, EnsGradArgs>;
+
+// alpha_h = W' z of every setting of a launch, behind k_ens_factor: one workgroup per setting, thread = column j, the rows i >= j added
+// in ascending order.  A failed setting's block is left as it is (k_ens_grad does not read it).
+__global__ __launch_bounds__(256) void k_ens_alpha(const double* __restrict__ ws, const long long* __restrict__ pivot, double* __restrict__ alpha,
+                                                   long long slab, int M, int ld) {
+#pragma clang fp contract(off)
+    const int64_t h = blockIdx.x;
+    if (pivot[h] != 0) return;   // the same for every thread
+    const double* const A = ws + h * slab;
+    const double* const W = A + (int64_t)(M + 1) * ld;
+    const double* const z = A + (int64_t)M * ld;
+    for (int j = threadIdx.x; j < M; j += 256) {
+        double s = 0.0;
+#pragma unroll 8
+        for (int i = j; i < M; ++i) s += W[(int64_t)i * ld + j] * z[i];
+        alpha[h * M + j] = s;
     }
 }
 
@@ -410,6 +601,20 @@ __global__ __launch_bounds__(256) void k_ens_reduce(const double* __restrict__ e
     }
     block_argmax(v, idx, sh);
     if (threadIdx.x == 0) { block_best[blockIdx.x].val = idx >= 0 ? v : -INFINITY; block_best[blockIdx.x].idx = idx; }
+}
+
+// grad[j][k] = sum_h w~_h geach[h][j][k] with k_ens_reduce's rule; thread = one of the n = R d entries of the chunk (rows are contiguous)
+__global__ __launch_bounds__(256) void k_ens_reduce_grad(const double* __restrict__ geach, long long plane, const double* __restrict__ wt,
+                                                         long long H, long long n, double* __restrict__ grad) {
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    double s = 0.0;
+    for (long long h = 0; h < H; ++h) {
+        const double w = wt[h];
+        if (w != 0.0) s += w * geach[h * plane + e];
+    }
+    grad[e] = s;
 }
 
 }  // namespace bohip

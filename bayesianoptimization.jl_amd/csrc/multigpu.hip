@@ -390,6 +390,7 @@ int bohip_mgp_append(bohip_mgp* m, const double* X, const double* y, int64_t p) 
                 g->n = n_old[i];
                 g->hX.resize((size_t)g->n * g->d);
                 g->hy.resize((size_t)g->n);
+                ++g->data_version;
             }
             g->stale = true;
             g->n_factored = 0;

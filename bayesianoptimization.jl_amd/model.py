@@ -263,6 +263,14 @@ class ElasticGPE:
         own parameters restored afterwards), with the same averaging rule.  Value only: no gradient."""
         return score_ensemble(self, acq, params, xs, Theta, weights, want_each, want_moments)
 
+    def score_ensemble_grad(self, acq, params, xs, Theta, weights=None, want_each=False):
+        """score_ensemble's scores together with their gradient with respect to every candidate: (EnsembleScore, grad[d, R]), and
+        each_grad[H, d, R] with want_each (NaN rows for a failed setting).  "device": bohip_gp_score_ens_grad
+        (include/bohip_ens_grad.h) -- scores, each and the arg-max are score_ensemble's bit for bit, and successive calls with the same
+        Theta and unchanged observations factor the settings once (timing() then shows no "ens_factor"); "host" above
+        mll_batch_dims()[1] observations: set_params_ + score_grad per row, the model's own parameters restored afterwards."""
+        return score_ensemble_grad(self, acq, params, xs, Theta, weights, want_each)
+
     def select_batch(self, acq, params, xs, q, fantasy="believer", raise_tau=False):
         """q candidates to evaluate in parallel (bohip_gp_select_batch; an extension, the reference proposes one point per
         iteration): greedy arg-max under the posterior conditioned on the fantasised observations of the earlier picks.
@@ -589,6 +597,73 @@ def score_ensemble(model, acq, params, xs, Theta, weights=None, want_each=False,
         if v > best_val:
             best_val, best_idx = float(v), j
     return EnsembleScore(scores, best_val, best_idx, pivot, each if want_each else None, mu, var, "host")
+
+
+def score_ensemble_grad(model, acq, params, xs, Theta, weights=None, want_each=False):
+    """ElasticGPE.score_ensemble_grad for any model object: (EnsembleScore, grad[d, R]) -- and each_grad[H, d, R] with want_each --
+    of the acquisition averaged over the rows of Theta.  The device route (bohip_gp_score_ens_grad, include/bohip_ens_grad.h) where
+    the model owns a handle whose library has the symbol and holds at most nmax observations; else the host loop over set_params_ +
+    score_grad, the model's own parameters put back whatever happens.  Both average each gradient component by ensemble_average's
+    rule; a failed setting has NaN rows and takes no part."""
+    if acq not in _lib.ACQ or acq == "ThompsonDraw":
+        raise ValueError(f"score_ensemble_grad takes EI, PI, UCB, MI, MaxMean and LogEI, not {acq!r}")
+    xs = _cols(xs, model.dim)
+    d = model.dim
+    P = 2 + (1 if model.kernel.iso else d) + 1
+    Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
+    if Theta.shape[1] != P:
+        raise ValueError(f"Theta must have {P} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
+    H, R = Theta.shape[0], xs.shape[1]
+    w = _ens_weights(weights, H)
+    p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+    if p.size < 2:
+        p = np.concatenate([p, np.zeros(2 - p.size)])
+    lib, h = getattr(model, "_lib", None), getattr(model, "_h", None)
+    if lib is not None and h and hasattr(lib, "bohip_gp_score_ens_grad") and model.nobs <= _lib.FIT_NMAX:
+        scores = np.empty(R)
+        grad = np.empty((d, R), order="F")                        # (the library's [R][d] row-major)
+        each = np.empty((H, R)) if want_each else None
+        eg = np.empty((H, R, d)) if want_each else None
+        pivot = np.zeros(H, dtype=np.int64)
+        best = Best()
+        opt = lambda a: _ptr(a) if a is not None else None   # noqa: E731
+        check(lib.bohip_gp_score_ens_grad(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), opt(w), _ptr(xs), R, _ptr(scores), _ptr(grad), opt(each),
+                                          opt(eg), None, None, pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
+        res = EnsembleScore(scores, best.val, best.idx, pivot, each, None, None, "device")
+        return (res, grad, eg.transpose(0, 2, 1)) if want_each else (res, grad)
+    # host route: one refit per setting; the model's own parameters come back whatever happens
+    saved = (model.kernel.ll.copy(), model.kernel.lsigma, model.logNoise, model.mean)
+    each = np.full((H, R), np.nan)
+    eg = np.full((H, d, R), np.nan)
+    pivot = np.zeros(H, dtype=np.int64)
+    nl = P - 3
+    try:
+        for k in range(H):
+            row = Theta[k]
+            if not np.all(np.isfinite(row)):
+                pivot[k] = 1
+                continue
+            try:
+                model.set_params_(ll=row[2:2 + nl], lsigma=row[2 + nl], logNoise=row[0], beta=row[1])
+                sc, g = model.score_grad(acq, p, xs)
+                each[k], eg[k] = sc, np.asarray(g).reshape(d, R)
+            except _lib.NotPositiveDefinite:
+                piv = model.info(_lib.INFO_PIVOT) if hasattr(model, "info") else 1
+                pivot[k] = max(int(piv), 1)
+                each[k], eg[k] = np.nan, np.nan
+    finally:
+        model.set_params_(ll=saved[0], lsigma=saved[1], logNoise=saved[2], beta=saved[3].beta)
+        model.mean = saved[3]
+    if not np.any((pivot == 0) & ((w if w is not None else np.ones(H)) > 0.0)):
+        raise _lib.NotPositiveDefinite(_lib.E_NOTPD, "the factorisation failed at every hyper-parameter setting")
+    scores = ensemble_average(each, w, pivot)
+    grad = np.asfortranarray(ensemble_average(eg.reshape(H, d * R), w, pivot).reshape(d, R))
+    best_val, best_idx = -math.inf, -1
+    for j, v in enumerate(scores):
+        if v > best_val:
+            best_val, best_idx = float(v), j
+    res = EnsembleScore(scores, best_val, best_idx, pivot, each if want_each else None, None, None, "host")
+    return (res, grad, eg) if want_each else (res, grad)
 
 
 class JointSample:

@@ -350,6 +350,7 @@ include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/b
 include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_acq.h): LogExpectedImprovement, acq_eval
 include("BOHipKG.jl")      # the knowledge gradient over a candidate set (include/bohip_kg.h): kg, kg_lines, KnowledgeGradient
 include("BOHipEns.jl")     # an acquisition averaged over hyper-parameter settings (include/bohip_ens.h): score_ensemble
+include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ensemble_grad
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
