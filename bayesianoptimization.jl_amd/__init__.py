@@ -10,7 +10,7 @@ from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
                     score_ensemble_grad)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, Marginalised, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
@@ -20,7 +20,7 @@ from .utils import (ScaledSobolIterator, ScaledLHSIterator, latin_hypercube_samp
 
 GPE = ElasticGPE.from_data
 
-__all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGradient", "ProbabilityOfImprovement", "UpperConfidenceBound", "ThompsonSamplingSimple",
+__all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGradient", "MaxValueEntropySearch", "ProbabilityOfImprovement", "UpperConfidenceBound", "ThompsonSamplingSimple",
            "MutualInformation", "boptimize_", "MAPGPOptimizer", "NoModelOptimizer", "Min", "Max", "BrochuBetaScaling",
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
            "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",

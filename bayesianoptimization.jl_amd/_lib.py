@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -26,6 +26,7 @@ FANTASY_BELIEVER, FANTASY_CONST, BATCH_RAISE_TAU = 0, 1, 1   # bohip_gp_select_b
 PATHS_S_MAX, PATHS_M_MAX = 4096, 16384                       # bohip_gp_paths_draw
 FIT_NMAX = 512                                               # bohip_gp_mll_grad_batch
 KG_RMAX = 8192                                               # bohip_gp_kg / bohip_kg_lines (BOHIP_KG_RMAX)
+MES_KMAX, MES_RMAX, MES_GUMBEL, MES_JOINT = 1024, 524288, 0, 1  # bohip_gp_mes / bohip_mes_values / bohip_mes_gumbel
 
 
 class Best(C.Structure):
@@ -170,6 +171,14 @@ ENS_GRAD_SIGNATURES = {
                                           C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_mes.h declares (max-value entropy search over a candidate set, on the device)
+MES_SIGNATURES = {
+    "bohip_gp_mes": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp,
+                               _dp, C.POINTER(Best), _dp, _ip]),
+    "bohip_mes_values": (C.c_int, [_gp, _dp, _dp, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_mes_gumbel": (C.c_int, [_gp, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, _dp, _dp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -226,7 +235,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
-                              + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items())):
+                              + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -129,6 +129,24 @@ class KnowledgeGradient(AbstractAcquisition):
     acq_id = "KG"
 
 
+class MaxValueEntropySearch(AbstractAcquisition):
+    """Max-value entropy search over a candidate set (include/bohip_mes.h; Wang & Jegelka 2017): the information the
+    observation of a point gives about the VALUE of the optimum, averaged over `samples` draws of the maximum of the posterior over
+    the candidates (model.mes).  An extension: the reference has no such type, and no default uses it.  mode "gumbel" fits a Gumbel
+    law to three quantiles of the maximum of independent candidates; "joint" takes the row maxima of joint posterior draws.  The
+    maximum is that of a SET, so acquisitionfunction takes a d x R candidate matrix, and acquire_max takes the device's arg-max over
+    `maxeval` Latin-hypercube candidates per restart; no gradient in x, no place in score / ascend / DIRECT."""
+    acq_id = "MES"
+    MODES = ("gumbel", "joint")
+
+    def __init__(self, samples=16, mode="gumbel"):
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= 1024:
+            raise ValueError(f"samples must be an integer in 1 .. 1024 (BOHIP_MES_KMAX), got {samples!r}")
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {self.MODES}, got {mode!r}")
+        self.samples, self.mode = int(samples), mode
+
+
 class Marginalised(AbstractAcquisition):
     """Marginalised(a): the acquisition `a` averaged over the hyper-parameter samples that MarginalGPOptimizer left on the model
     (model.hyper_samples = (Theta[H, P], weights)): a(x) = sum_h w_h a(x; theta_h), the integrated acquisition of Snoek, Larochelle &
@@ -246,6 +264,16 @@ def acquisitionfunction(a, model, rng=None):
             return model.kg(x).values
 
         return kg
+    if isinstance(a, MaxValueEntropySearch):
+        def mes(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("MaxValueEntropySearch needs a candidate set, a d x R matrix: the maximum it learns about is that "
+                                 "of a set")
+            seed = int((rng if rng is not None else np.random.default_rng()).integers(0, 2**63))
+            return model.mes(x, samples=a.samples, mode=a.mode, seed=seed).values
+
+        return mes
     if isinstance(a, Marginalised):
         def marginal(x):
             x = np.asarray(x, dtype=np.float64)
@@ -269,7 +297,7 @@ def acquisitionfunction(a, model, rng=None):
 
 # ---- src/acquisition.jl ----------------------------------------------------------------------------------
 def defaultoptions(model_type, acq_type):                    # :4-9
-    if isinstance(acq_type, type) and issubclass(acq_type, KnowledgeGradient):
+    if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch)):
         return dict(method="LD_LBFGS", restarts=1, maxeval=1024)   # (1024: the smallest candidate chunk a model can have)
     if isinstance(acq_type, type) and issubclass(acq_type, ThompsonSamplingSimple):
         return dict(method="GN_DIRECT_L", restarts=1, maxeval=2000)
@@ -587,6 +615,24 @@ def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng):
     return maxf, maxx
 
 
+def _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng):
+    """MaxValueEntropySearch: a candidate-set acquisition without a gradient in x.  Every restart takes `maxeval` Latin-hypercube
+    candidates and ONE model.mes call with the device's arg-max; the call's seed is drawn from `rng` after the candidates.  The
+    first maximum over the restarts wins (strict '>')."""
+    if not hasattr(model, "mes"):
+        raise NotImplementedError(f"{type(model).__name__} has no mes")
+    gen = rng if rng is not None else np.random.default_rng()
+    maxf, maxx = -math.inf, lb.copy()
+    for _ in range(restarts):
+        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+        res = model.mes(xs, samples=a.samples, mode=a.mode, seed=int(gen.integers(0, 2**63)))
+        if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
+            maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
+
+
 def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts=None):
     """Marginalised(a).  Every restart scores `maxeval` Latin-hypercube candidates under all hyper-parameter samples in ONE
     model.score_ensemble call and takes its arg-max record.  The first maximum over the restarts wins (strict '>').
@@ -660,6 +706,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return maxf, maxx
     if isinstance(a, KnowledgeGradient):                          # (`method` has nothing to select between: accepted, not used)
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, MaxValueEntropySearch):                      # (`method` is accepted, not used)
+        return _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, Marginalised):                               # (`method` is accepted, not used; "refine" adds the ascent)
         return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31

@@ -20,6 +20,7 @@
 #include "../../include/bohip_qei.h"
 #include "../../include/bohip_acq.h"
 #include "../../include/bohip_kg.h"
+#include "../../include/bohip_mes.h"
 #include "../../include/bohip_ens.h"
 #include "../../include/bohip_ens_grad.h"
 #include "kernels_linalg.hip"
@@ -30,6 +31,7 @@
 #include "kernels_sample.hip"  // (after the scoring kernels: their generator and arg-max order)
 #include "kernels_qei.hip"     // (after the scoring kernels: their arg-max order)
 #include "kernels_kg.hip"      // (after the scoring kernels: their arg-max order; acq_log.h's forms of h)
+#include "kernels_mes.hip"     // (after the scoring and sampling kernels: their generator and arg-max order; acq_log.h's continued fraction)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_ascent.hip"
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
@@ -207,6 +209,9 @@ struct bohip_gp {
     // knowledge gradient (bohip_gp_kg / bohip_kg_lines): ONE block [kg | record | nseg | a | B], the last two for the caller's lines only
     char* kg_ws = nullptr;
     size_t kg_bytes = 0;
+    // max-value entropy search (bohip_gp_mes / bohip_mes_values / bohip_mes_gumbel): ONE block, see ensure_mes
+    char* mes_ws = nullptr;
+    size_t mes_bytes = 0;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -2356,6 +2361,7 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->sj_part) hipFree(g->sj_part);
     if (g->qei_ws) hipFree(g->qei_ws);
     if (g->kg_ws) hipFree(g->kg_ws);
+    if (g->mes_ws) hipFree(g->mes_ws);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -3481,6 +3487,191 @@ int bohip_kg_lines(bohip_gp* g, const double* a, const double* B, int64_t R, int
     HIPCHK(hipMemcpyAsync(w.a, a, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(w.B, B, (size_t)E * R * 8, hipMemcpyHostToDevice, g->stream));
     CHK(kg_march(g, false, w, w.a, w.B, R, R, E, 0.0, kg, nseg, nullptr));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+// ---- max-value entropy search over a candidate set (kernels_mes.hip, include/bohip_mes.h) --------------------------
+static_assert(MES_KMAX == BOHIP_MES_KMAX && MES_RMAX == BOHIP_MES_RMAX, "the kernels' plan and the header agree");
+struct MesBufs {
+    double *mes, *dmu, *dvar;   // [R] each
+    double *maxvals;            // [K]
+    double *quant;              // [3]
+    double *mu, *var;           // [R] each: the caller's candidates (bohip_mes_values / bohip_mes_gumbel)
+    Best *blocks, *best;        // [ceil(R / 256)], [1]
+    MesWs w;
+};
+static int mes_slices(int64_t R) { return R <= MES_SLICE ? 1 : (int)((R + MES_SLICE - 1) / MES_SLICE); }
+static int mes_check_size(const char* who, int64_t R, int64_t K) {
+    const std::string pre = std::string(who) + ": ";
+    if (R < 1 || K < 1) return fail(BOHIP_E_ARG, pre + "R and K must be at least 1");
+    return 0;
+}
+static int mes_check_limits(const char* who, int64_t R, int64_t K) {
+    const std::string pre = std::string(who) + ": ";
+    if (K > BOHIP_MES_KMAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "K exceeds BOHIP_MES_KMAX (" + std::to_string(BOHIP_MES_KMAX) +
+                                             "): the max values live in a workgroup's LDS");
+    if (R > BOHIP_MES_RMAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "R exceeds BOHIP_MES_RMAX (" + std::to_string(BOHIP_MES_RMAX) +
+                                             "): the bracket of the max-value quantiles is guaranteed up to it");
+    return 0;
+}
+// ONE block: [mes | dmu | dvar | mu | var  (R each) | maxvals K | quantiles 3 (+1) | state | bracket partials | probe sums | records]
+static int ensure_mes(bohip_gp* g, int64_t R, int64_t K, MesBufs* b) {
+    const int nsl = mes_slices(R);
+    const size_t nb = (size_t)((R + 255) / 256);
+    const size_t o_max = (size_t)5 * R * 8, o_q = o_max + (size_t)K * 8, o_st = o_q + 4 * 8, o_br = o_st + (2 * MES_STATE + 4) * 8,
+                 o_part = o_br + (size_t)3 * MES_BR_MAX * 8, o_blk = o_part + (size_t)2 * MES_NQ * MES_PROBES * nsl * 8,
+                 need = o_blk + (nb + 1) * sizeof(Best);
+    if (g->mes_bytes < need) {
+        if (g->mes_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->mes_ws)); g->mes_ws = nullptr; }
+        const size_t cap = std::max(need, g->mes_bytes + g->mes_bytes / 2);
+        g->mes_bytes = 0;
+        HIPCHK(hipMalloc(&g->mes_ws, cap));
+        g->mes_bytes = cap;
+    }
+    char* p = g->mes_ws;
+    double* d = reinterpret_cast<double*>(p);
+    b->mes = d; b->dmu = d + R; b->dvar = d + 2 * R; b->mu = d + 3 * R; b->var = d + 4 * R;
+    b->maxvals = reinterpret_cast<double*>(p + o_max);
+    b->quant = reinterpret_cast<double*>(p + o_q);
+    b->w.st = reinterpret_cast<double*>(p + o_st);
+    b->w.br = reinterpret_cast<double*>(p + o_br);
+    b->w.part = reinterpret_cast<double*>(p + o_part);
+    b->w.nsl = nsl;
+    b->blocks = reinterpret_cast<Best*>(p + o_blk);
+    b->best = b->blocks + nb;
+    return 0;
+}
+// the Gumbel sampler on the device's (mu, var): bracket, 14 probe passes, the draw (no synchronisation, no copies)
+static int mes_gumbel_stages(bohip_gp* g, const MesBufs& b, const double* dmu, const double* dvar, int64_t R, int64_t K, uint64_t seed,
+                             double floor_value) {
+    const int nbr = (int)std::min<int64_t>(MES_BR_MAX, (R + 255) / 256);
+    t_begin(g, "mes_bracket");
+    hipLaunchKernelGGL(k_mes_bracket<false>, dim3(nbr), dim3(256), 0, g->stream, dmu, dvar, R, nbr, b.w);
+    hipLaunchKernelGGL(k_mes_bracket<true>, dim3(1), dim3(256), 0, g->stream, dmu, dvar, R, nbr, b.w);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    t_begin(g, "mes_probe");
+    const dim3 pgrid(MES_NQ * MES_PROBES, (unsigned)b.w.nsl);
+    for (int pass = 0; pass < MES_PASSES; ++pass)
+        hipLaunchKernelGGL(k_mes_probe, pgrid, dim3(256), 0, g->stream, dmu, dvar, R, pass, b.w);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    t_begin(g, "mes_draw");
+    hipLaunchKernelGGL(k_mes_draw, dim3(1), dim3(256), 0, g->stream, b.w, (int)K, seed, floor_value, b.quant, b.maxvals);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+// the functor over the candidates and the record, and the copies of what the caller asked for (no synchronisation)
+static int mes_value_stages(bohip_gp* g, const MesBufs& b, const double* dmu, const double* dvar, int64_t R, int64_t K, bool grad,
+                            double* mes, double* gmu, double* gvar, bohip_best* best) {
+    const int nb = (int)((R + 255) / 256);
+    t_begin(g, "mes_values");
+    if (grad)
+        hipLaunchKernelGGL(k_mes_values<true>, dim3(nb), dim3(256), 0, g->stream, dmu, dvar, R, b.maxvals, (int)K, b.mes, b.dmu, b.dvar,
+                           best ? b.blocks : (Best*)nullptr);
+    else
+        hipLaunchKernelGGL(k_mes_values<false>, dim3(nb), dim3(256), 0, g->stream, dmu, dvar, R, b.maxvals, (int)K, b.mes, (double*)nullptr,
+                           (double*)nullptr, best ? b.blocks : (Best*)nullptr);
+    if (best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, b.blocks, nb, b.best, 0ll);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    HIPCHK(hipMemcpyAsync(mes, b.mes, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (grad) {
+        HIPCHK(hipMemcpyAsync(gmu, b.dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(gvar, b.dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    }
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    return 0;
+}
+
+int bohip_gp_mes(bohip_gp* g, const double* Xs, int64_t R, int64_t K, int mode, uint64_t seed, double floor_value, double jitter_rel,
+                 int max_tries, double* mes, double* maxvals, double* quantiles, double* mu, double* var, bohip_best* best,
+                 double* jitter_used, int* tries_used) {
+    CHK(mes_check_size("mes", R, K));
+    if (mode != BOHIP_MES_GUMBEL && mode != BOHIP_MES_JOINT) return fail(BOHIP_E_ARG, "mes: unknown mode");
+    if (!g || !Xs || !mes) return fail(BOHIP_E_ARG, "mes: null argument");
+    if (floor_value != floor_value) return fail(BOHIP_E_ARG, "mes: floor_value must not be NaN");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(mes_check_limits("mes", R, K));
+    HIPCHK(hipSetDevice(g->device));
+    if (mode == BOHIP_MES_JOINT && round_up(R, 512) > chunk_cap(g))
+        return fail(BOHIP_E_UNSUPPORTED, "mes: joint mode: R exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + ")");
+    MesBufs b{};
+    CHK(ensure_mes(g, R, K, &b));
+    auto copies = [&]() -> int {
+        if (maxvals) HIPCHK(hipMemcpyAsync(maxvals, b.maxvals, (size_t)K * 8, hipMemcpyDeviceToHost, g->stream));
+        if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+        if (var) HIPCHK(hipMemcpyAsync(var, g->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+        return 0;
+    };
+    if (mode == BOHIP_MES_JOINT) {
+        if (quantiles) quantiles[0] = quantiles[1] = quantiles[2] = NAN;
+        return sample_joint_core(g, "mes", Xs, R, K, seed, jitter_rel, max_tries, true, nullptr, nullptr, nullptr, nullptr, jitter_used,
+                                 tries_used, [&]() -> int {
+                                     t_begin(g, "mes_rowmax");
+                                     hipLaunchKernelGGL(k_mes_rowmax, dim3((unsigned)K), dim3(256), 0, g->stream, g->sjF, R, floor_value,
+                                                        b.maxvals);
+                                     HIPCHK(hipGetLastError());
+                                     t_end(g);
+                                     CHK(mes_value_stages(g, b, g->dmu, g->dvar, R, K, false, mes, nullptr, nullptr, best));
+                                     return copies();
+                                 });
+    }
+    t_reset(g);
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(score_core(g, BOHIP_ACQ_MAXMEAN, nullptr, g->dXs, R, g->dmu, g->dvar, nullptr, nullptr));
+    CHK(mes_gumbel_stages(g, b, g->dmu, g->dvar, R, K, seed, floor_value));
+    CHK(mes_value_stages(g, b, g->dmu, g->dvar, R, K, false, mes, nullptr, nullptr, best));
+    CHK(copies());
+    if (quantiles) HIPCHK(hipMemcpyAsync(quantiles, b.quant, 3 * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (jitter_used) *jitter_used = 0.0;
+    if (tries_used) *tries_used = 0;
+    t_collect(g);
+    return 0;
+}
+
+int bohip_mes_values(bohip_gp* g, const double* mu, const double* var, int64_t R, const double* maxvals, int64_t K, double* mes,
+                     double* dmu, double* dvar, bohip_best* best) {
+    CHK(mes_check_size("mes_values", R, K));
+    if (!g || !mu || !var || !maxvals || !mes) return fail(BOHIP_E_ARG, "mes_values: null argument");
+    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "mes_values: dmu and dvar are given together or not at all");
+    CHK(mes_check_limits("mes_values", R, K));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    MesBufs b{};
+    CHK(ensure_mes(g, R, K, &b));
+    HIPCHK(hipMemcpyAsync(b.mu, mu, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(b.var, var, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(b.maxvals, maxvals, (size_t)K * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(mes_value_stages(g, b, b.mu, b.var, R, K, dmu != nullptr, mes, dmu, dvar, best));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_mes_gumbel(bohip_gp* g, const double* mu, const double* var, int64_t R, int64_t K, uint64_t seed, double floor_value,
+                     double* quantiles, double* maxvals) {
+    CHK(mes_check_size("mes_gumbel", R, K));
+    if (!g || !mu || !var || !quantiles || !maxvals) return fail(BOHIP_E_ARG, "mes_gumbel: null argument");
+    if (floor_value != floor_value) return fail(BOHIP_E_ARG, "mes_gumbel: floor_value must not be NaN");
+    CHK(mes_check_limits("mes_gumbel", R, K));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    MesBufs b{};
+    CHK(ensure_mes(g, R, K, &b));
+    HIPCHK(hipMemcpyAsync(b.mu, mu, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(b.var, var, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(mes_gumbel_stages(g, b, b.mu, b.var, R, K, seed, floor_value));
+    HIPCHK(hipMemcpyAsync(quantiles, b.quant, 3 * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(maxvals, b.maxvals, (size_t)K * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;

@@ -429,6 +429,25 @@ class ElasticGPE:
         row.  The model supplies the device and the stream only.  Returns (values[E], nseg[E] int32)."""
         return _kg_lines(self._lib, self._h, a, B)
 
+    def mes(self, xs, samples=16, mode="gumbel", seed=0, floor=None, jitter_rel=1e-12, max_tries=40):
+        """Max-value entropy search over the candidate set xs on the device (bohip_gp_mes, include/bohip_mes.h; an extension; Wang &
+        Jegelka 2017): MES_j = mean_k u(mu_j, s2_j, m_k) over `samples` draws m_k of the maximum of the posterior over the
+        candidates.  mode "gumbel": a Gumbel fit to three quantiles of the maximum of independent candidates (any R up to
+        _lib.MES_RMAX); "joint": the row maxima of sample_joint's draws for the same (xs, S = samples, seed, jitter rule), R
+        within one chunk.  floor (None: none) is a lower limit of every max value, e.g. the best observation.  The model is not
+        changed.  Returns a MESResult."""
+        return _mes(self._lib, self._h, _cols(xs, self.dim), samples, mode, seed, floor, jitter_rel, max_tries)
+
+    def mes_values(self, mu, var, maxvals, want_grad=False):
+        """The functor of mes alone on the caller's (mu, var, maxvals) (bohip_mes_values): the model supplies the device and the
+        stream only.  Returns (values[R], best_val, best_idx), or (values, dmu, dvar, best_val, best_idx) with want_grad."""
+        return _mes_values(self._lib, self._h, mu, var, maxvals, want_grad)
+
+    def mes_gumbel(self, mu, var, samples=16, seed=0, floor=None):
+        """The max-value sampler of mode "gumbel" alone on the caller's (mu, var) (bohip_mes_gumbel).  Returns (quantiles[3],
+        maxvals[samples])."""
+        return _mes_gumbel(self._lib, self._h, mu, var, samples, seed, floor)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """S posterior SAMPLE PATHS (bohip_gp_paths_draw): draws that are functions, f_s(x) = beta + sum_m w_sm phi_m(x) +
         sum_j u_sj k(x, X_j) with M random features for the prior term and the exact data term (pathwise conditioning).  The result
@@ -765,6 +784,62 @@ def _kg_lines(lib, handle, a, B):
     nseg = np.zeros(max(E, 1), dtype=np.int32)
     check(lib.bohip_kg_lines(handle, _ptr(a), _ptr(B), a.size, E, _ptr(values), nseg.ctypes.data_as(C.POINTER(C.c_int32))))
     return values, nseg
+
+
+class MESResult:
+    """Result of mes: values[R] (MES of every candidate), maxvals[K] (the samples of the maximum), quantiles[3] (y25, y50, y75 of
+    the Gumbel fit; NaN in joint mode), mu[R], var[R] (the posterior the values were computed from), best_val / best_idx (the
+    arg-max under score's rule: first maximum, NaN never wins, -Inf / -1 if nothing can win), jitter / tries (joint mode)."""
+    __slots__ = ("values", "maxvals", "quantiles", "mu", "var", "best_val", "best_idx", "jitter", "tries")
+
+    def __init__(self, values, maxvals, quantiles, mu, var, best_val, best_idx, jitter=0.0, tries=0):
+        self.values, self.maxvals, self.quantiles, self.mu, self.var = values, maxvals, quantiles, mu, var
+        self.best_val, self.best_idx, self.jitter, self.tries = best_val, best_idx, jitter, tries
+
+    def __iter__(self):
+        return iter((self.values, self.maxvals, self.quantiles, self.mu, self.var, self.best_val, self.best_idx))
+
+
+MES_MODES = {"gumbel": _lib.MES_GUMBEL, "joint": _lib.MES_JOINT}
+
+
+def _mes(lib, handle, xs, samples, mode, seed, floor, jitter_rel, max_tries):
+    if mode not in MES_MODES:
+        raise ValueError(f"mode must be one of {sorted(MES_MODES)}, got {mode!r}")
+    R, K = xs.shape[1], int(samples)
+    values, mu, var = np.empty(max(R, 1)), np.empty(max(R, 1)), np.empty(max(R, 1))
+    maxvals, quant = np.empty(max(K, 1)), np.empty(3)
+    best, jit, tries = Best(), C.c_double(0.0), C.c_int(0)
+    check(lib.bohip_gp_mes(handle, _ptr(xs), R, K, MES_MODES[mode], int(seed), -math.inf if floor is None else float(floor),
+                           float(jitter_rel), int(max_tries), _ptr(values), _ptr(maxvals), _ptr(quant), _ptr(mu), _ptr(var),
+                           C.byref(best), C.byref(jit), C.byref(tries)))
+    return MESResult(values, maxvals, quant, mu, var, best.val, best.idx, jit.value, tries.value)
+
+
+def _mes_values(lib, handle, mu, var, maxvals, want_grad):
+    mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).ravel())
+    var = np.ascontiguousarray(np.asarray(var, dtype=np.float64).ravel())
+    mv = np.ascontiguousarray(np.asarray(maxvals, dtype=np.float64).ravel())
+    if mu.size != var.size:
+        raise ValueError("mu and var differ in length")
+    values = np.empty(max(mu.size, 1))
+    dmu, dvar = (np.empty(max(mu.size, 1)), np.empty(max(mu.size, 1))) if want_grad else (None, None)
+    best = Best()
+    check(lib.bohip_mes_values(handle, _ptr(mu), _ptr(var), mu.size, _ptr(mv), mv.size, _ptr(values),
+                               _ptr(dmu) if want_grad else None, _ptr(dvar) if want_grad else None, C.byref(best)))
+    return (values, dmu, dvar, best.val, best.idx) if want_grad else (values, best.val, best.idx)
+
+
+def _mes_gumbel(lib, handle, mu, var, samples, seed, floor):
+    mu = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).ravel())
+    var = np.ascontiguousarray(np.asarray(var, dtype=np.float64).ravel())
+    if mu.size != var.size:
+        raise ValueError("mu and var differ in length")
+    K = int(samples)
+    quant, maxvals = np.empty(3), np.empty(max(K, 1))
+    check(lib.bohip_mes_gumbel(handle, _ptr(mu), _ptr(var), mu.size, K, int(seed), -math.inf if floor is None else float(floor),
+                               _ptr(quant), _ptr(maxvals)))
+    return quant, maxvals
 
 
 class PosteriorPaths:

@@ -204,6 +204,25 @@ class MultiGPE:
 
         return _kg_lines(self._lib, self._lib.bohip_mgp_handle(self._h, 0), a, B)
 
+    def mes(self, xs, samples=16, mode="gumbel", seed=0, floor=None, jitter_rel=1e-12, max_tries=40):
+        """ElasticGPE.mes (bohip_gp_mes) on the FIRST replica, as kg: the max values are those of the whole candidate set."""
+        from .model import _mes
+
+        return _mes(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(xs, self.dim), samples, mode, seed, floor, jitter_rel,
+                    max_tries)
+
+    def mes_values(self, mu, var, maxvals, want_grad=False):
+        """ElasticGPE.mes_values (bohip_mes_values) on the FIRST replica."""
+        from .model import _mes_values
+
+        return _mes_values(self._lib, self._lib.bohip_mgp_handle(self._h, 0), mu, var, maxvals, want_grad)
+
+    def mes_gumbel(self, mu, var, samples=16, seed=0, floor=None):
+        """ElasticGPE.mes_gumbel (bohip_mes_gumbel) on the FIRST replica."""
+        from .model import _mes_gumbel
+
+        return _mes_gumbel(self._lib, self._lib.bohip_mgp_handle(self._h, 0), mu, var, samples, seed, floor)
+
     def mll_batch_dims(self):
         P, nmax = C.c_int64(), C.c_int64()
         check(self._lib.bohip_gp_mll_batch_dims(self._lib.bohip_mgp_handle(self._h, 0), C.byref(P), C.byref(nmax)))

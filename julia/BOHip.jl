@@ -39,7 +39,7 @@ using Dates: now
 using TimerOutputs: TimerOutput, reset_timer!, @timeit
 import Base: show
 
-export BOHipGPE, BOHipMultiGPE, DeviceBOpt, LogExpectedImprovement, KnowledgeGradient
+export BOHipGPE, BOHipMultiGPE, DeviceBOpt, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch
 
 const libbohip = get(ENV, "BOHIP_LIB", "libbohip.so")
 
@@ -351,6 +351,7 @@ include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_
 include("BOHipKG.jl")      # the knowledge gradient over a candidate set (include/bohip_kg.h): kg, kg_lines, KnowledgeGradient
 include("BOHipEns.jl")     # an acquisition averaged over hyper-parameter settings (include/bohip_ens.h): score_ensemble
 include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ensemble_grad
+include("BOHipMES.jl")     # max-value entropy search over a candidate set (include/bohip_mes.h): mes, mes_values, mes_gumbel, MaxValueEntropySearch
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
