@@ -8,9 +8,9 @@ from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
-                    score_ensemble_grad)
+                    score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
@@ -25,4 +25,5 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "NoBetaScaling", "Silent", "Timings", "Progress", "ScaledSobolIterator", "ScaledLHSIterator",
            "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
-           "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore"]
+           "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
+           "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values"]

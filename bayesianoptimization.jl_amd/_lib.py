@@ -179,6 +179,16 @@ MES_SIGNATURES = {
     "bohip_mes_gumbel": (C.c_int, [_gp, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, _dp, _dp]),
 }
 
+# every symbol include/bohip_con.h declares (constrained optimisation: the posterior's Jacobians, the combine stage, the whole call)
+CON_FEASIBILITY = -1
+CON_CMAX = 16
+CON_SIGNATURES = {
+    "bohip_gp_predict_grad": (C.c_int, [_gp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "bohip_con_values": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, _dp, _ip, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_gp_score_con": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, C.POINTER(_gp), _dp, _ip, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp,
+                                     C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -235,7 +245,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
-                              + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())):
+                              + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
+                              + list(CON_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

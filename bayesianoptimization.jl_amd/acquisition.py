@@ -174,6 +174,38 @@ class Marginalised(AbstractAcquisition):
         return self.a.params()
 
 
+class Constrained(AbstractAcquisition):
+    """Constrained(a): the acquisition `a` of the objective weighted by the probability that every constraint of a ConstrainedGPE
+    holds (include/bohip_con.h; Gardner et al. 2014, Gelbart, Snoek & Adams 2014).  An extension: the reference's
+    acquisition closes over one model.  `a` is ExpectedImprovement or ProbabilityOfImprovement (a exp(L), the classic product) or
+    LogExpectedImprovement (a + L, which survives deep infeasibility); L = sum_c log P(constraint c holds).  setparams_ sets tau to
+    the best FEASIBLE observation; while there is none the call scores L alone ("Feasibility": Gelbart's rule -- look for a feasible
+    point first).  acquisitionfunction takes a d x R matrix; acquire_max takes the device's arg-max over `maxeval` Latin-hypercube
+    candidates per restart and, with the option "refine": n > 0, climbs the n best on the gradient route."""
+    TAKES = ("EI", "PI", "LogEI")
+
+    def __init__(self, a):
+        if not isinstance(a, AbstractAcquisition) or a.acq_id not in self.TAKES:
+            raise ValueError(f"Constrained takes ExpectedImprovement, ProbabilityOfImprovement or LogExpectedImprovement, not "
+                             f"{type(a).__name__}: a signed score has no product form")
+        self.a = a
+        self.feasibility_only = False
+
+    @property
+    def acq_id(self):
+        return "Feasibility" if self.feasibility_only else self.a.acq_id
+
+    def _setparams(self, model):
+        inc = model.feasible_incumbent()
+        self.feasibility_only = inc is None
+        if inc is not None:
+            self.a.tau = float(inc)
+        return self.a.tau
+
+    def params(self):
+        return [0.0] if self.feasibility_only else self.a.params()
+
+
 def _hyper_samples(model):
     hs = getattr(model, "hyper_samples", None)
     if hs is None:
@@ -274,6 +306,14 @@ def acquisitionfunction(a, model, rng=None):
             return model.mes(x, samples=a.samples, mode=a.mode, seed=seed).values
 
         return mes
+    if isinstance(a, Constrained):
+        def constrained(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("Constrained takes a d x R candidate matrix")
+            return model.score(a.acq_id, a.params(), x).scores
+
+        return constrained
     if isinstance(a, Marginalised):
         def marginal(x):
             x = np.asarray(x, dtype=np.float64)
@@ -297,7 +337,7 @@ def acquisitionfunction(a, model, rng=None):
 
 # ---- src/acquisition.jl ----------------------------------------------------------------------------------
 def defaultoptions(model_type, acq_type):                    # :4-9
-    if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch)):
+    if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch, Constrained)):
         return dict(method="LD_LBFGS", restarts=1, maxeval=1024)   # (1024: the smallest candidate chunk a model can have)
     if isinstance(acq_type, type) and issubclass(acq_type, ThompsonSamplingSimple):
         return dict(method="GN_DIRECT_L", restarts=1, maxeval=2000)
@@ -685,6 +725,51 @@ def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts=None):
     return maxf, maxx
 
 
+def _acquire_max_constrained(a, model, lb, ub, restarts, maxeval, rng, opts=None):
+    """Constrained(a) over a ConstrainedGPE.  Every restart scores `maxeval` Latin-hypercube candidates in ONE model.score call and
+    takes its arg-max record; the first maximum over the restarts wins (strict '>').  "refine": n > 0 (default 0: the candidate stage
+    alone): the n highest-scoring distinct candidates then start ONE batched L-BFGS ascent inside the box, fg = one gradient-route
+    model.score call per step; the best ascended point replaces the candidate maximum only where it is strictly better."""
+    opts = opts or {}
+    refine = int(opts.get("refine", 0) or 0)
+    acq, p = a.acq_id, a.params()
+    maxf, maxx = -math.inf, lb.copy()
+    seen_x, seen_f = [], []
+    for _ in range(restarts):
+        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+        res = model.score(acq, p, xs)
+        if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
+            maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+        if refine > 0:
+            seen_x.append(xs)
+            seen_f.append(np.asarray(res.scores, dtype=np.float64))
+    if refine > 0 and np.isfinite(maxf):
+        X, f = np.concatenate(seen_x, axis=1), np.concatenate(seen_f)
+        starts, taken = [], set()
+        for j in np.argsort(-np.where(np.isnan(f), -math.inf, f), kind="stable"):
+            key = X[:, j].tobytes()
+            if np.isfinite(f[j]) and key not in taken:
+                taken.add(key)
+                starts.append(X[:, j])
+                if len(starts) == refine:
+                    break
+
+        def fg(Z):
+            r = model.score(acq, p, Z, want_grad=True)
+            return np.asarray(r.scores, dtype=np.float64), np.asarray(r.grad, dtype=np.float64)
+
+        fa, Xa = _batched_lbfgs_ascent(fg, np.asfortranarray(np.stack(starts, axis=1)), lb, ub, max(2, maxeval),
+                                       ftol_rel=float(opts.get("ftol_rel", 1e-10)), xtol_abs=float(opts.get("xtol_abs", 1e-10)),
+                                       ftol_abs=float(opts.get("ftol_abs", 0.0)), xtol_rel=float(opts.get("xtol_rel", 0.0)),
+                                       stopval=float(opts.get("stopval", math.inf)))
+        j = int(np.argmax(np.where(np.isnan(fa), -math.inf, fa)))
+        if fa[j] > maxf:                                          # strict '>': never worse than the candidate maximum
+            maxf, maxx = float(fa[j]), Xa[:, j].copy()
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
+
+
 def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
     """src/acquisition.jl:48-68: R Latin-hypercube starts (utils.jl:96-120), local search from each, keep the
     best under strict '>' (first maximum wins).  Returns (maxf, maxx).
@@ -708,6 +793,10 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, MaxValueEntropySearch):                      # (`method` is accepted, not used)
         return _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, Constrained):                                # (`method` is accepted, not used; "refine" adds the ascent)
+        if not hasattr(model, "feasible_incumbent"):
+            raise ValueError(f"Constrained needs a ConstrainedGPE, not {type(model).__name__}")
+        return _acquire_max_constrained(a, model, lb, ub, restarts, maxeval, rng, opts)
     if isinstance(a, Marginalised):                               # (`method` is accepted, not used; "refine" adds the ascent)
         return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31

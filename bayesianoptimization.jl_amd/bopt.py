@@ -9,10 +9,10 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
+from .acquisition import (AbstractAcquisition, Constrained, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
-from .model import ElasticGPE, Mat52Ard, MeanConst, update_
+from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
 
 
@@ -183,10 +183,11 @@ def optimizemodel_(o, model):                                 # :42-47 and NoMod
     if isinstance(o, NoModelOptimizer) or o is None:
         return None
     if o.i % o.every == 0:
-        if isinstance(o, MarginalGPOptimizer):
-            _marginal_fit(model, o.options)
-        else:
-            _map_fit(model, o.options)
+        for m in (model.members if isinstance(model, ConstrainedGPE) else [model]):   # every member of a constrained model
+            if isinstance(o, MarginalGPOptimizer):
+                _marginal_fit(m, o.options)
+            else:
+                _map_fit(m, o.options)
     o.i += 1
 
 
@@ -353,12 +354,27 @@ class BOpt:
             raise ValueError("Marginalised acquisitions propose one point per iteration (batchsize = 1)")
         if batchsize == 1 and batchoptions:
             raise ValueError("batchoptions given with batchsize = 1")
+        constrained = isinstance(model, ConstrainedGPE)
+        if constrained != isinstance(acquisition, Constrained):
+            raise ValueError("a ConstrainedGPE model goes with a Constrained(a) acquisition and the other way round "
+                             f"(got {type(model).__name__} with {type(acquisition).__name__}); Marginalised over a "
+                             "ConstrainedGPE is not supported")
+        if constrained and batchsize > 1:
+            raise ValueError("a ConstrainedGPE proposes one point per iteration (batchsize = 1)")
+        if constrained and isinstance(modeloptimizer, MarginalGPOptimizer):
+            raise ValueError("MarginalGPOptimizer over a ConstrainedGPE is not supported: its samples have no constrained acquisition")
         if not np.all(lowerbounds <= upperbounds):
             raise ValueError("lowerbounds are not pointwise less than or eqal to upperbounds, they were possibly "
                              "passed in the wrong order")
         empty = model.y.size == 0
-        current_optimum = -math.inf * int(sense) if empty else int(sense) * float(np.max(model.y))   # :117
-        current_optimizer = np.zeros_like(lowerbounds) if empty else np.array(model.x[:, int(np.argmax(model.y))])
+        if constrained:                                                          # only feasible observations count
+            ok = np.zeros(0, dtype=bool) if empty else model.feasible_mask()
+            yy = np.where(ok, model.y, -math.inf) if ok.any() else None
+            current_optimum = -math.inf * int(sense) if yy is None else int(sense) * float(np.max(yy))
+            current_optimizer = np.zeros_like(lowerbounds) if yy is None else np.array(model.x[:, int(np.argmax(yy))])
+        else:
+            current_optimum = -math.inf * int(sense) if empty else int(sense) * float(np.max(model.y))   # :117
+            current_optimizer = np.zeros_like(lowerbounds) if empty else np.array(model.x[:, int(np.argmax(model.y))])
         self.func, self.sense, self.model = func, Sense(sense), model
         self.acquisition, self.acquisitionoptions, self.modeloptimizer = acquisition, acquisitionoptions, modeloptimizer
         self.lowerbounds, self.upperbounds = lowerbounds, upperbounds
@@ -401,7 +417,31 @@ class _timeit:
         rec[1] += time.perf_counter() - self.t
 
 
+def _evaluate_constrained(o, x):
+    """func(x) -> (y, g_1, ..., g_C) for a ConstrainedGPE: sense flips y only, and only a feasible observation can be the optimum."""
+    with _timeit(o, "function evaluation"):
+        out = np.atleast_1d(np.asarray(o.func(x), dtype=np.float64)).ravel()
+    C_ = len(o.model.constraints)
+    if out.size != C_ + 1:
+        raise ValueError(f"func must return (y, g_1, ..., g_C) with C = {C_} constraint values, got {out.size} numbers")
+    y, g = int(o.sense) * float(out[0]), out[1:]
+    if bool(o.model.is_feasible(g)) and y > int(o.sense) * o.observed_optimum:
+        o.observed_optimum = int(o.sense) * y
+        o.observed_optimizer = x
+    return y, g
+
+
+def _update_model(o, xs, ys):
+    """One model update with the columns xs and what _evaluate_function returned for them."""
+    if isinstance(o.model, ConstrainedGPE):
+        o.model.update_(np.stack(xs, axis=1), np.array([y for y, _ in ys]), np.stack([g for _, g in ys], axis=1))
+    else:
+        update_(o.model, np.stack(xs, axis=1), np.array(ys))
+
+
 def _evaluate_function(o, x):                                                   # :209-216
+    if isinstance(o.model, ConstrainedGPE):
+        return _evaluate_constrained(o, x)
     with _timeit(o, "function evaluation"):
         y = int(o.sense) * o.func(x)
     if y > int(o.sense) * o.observed_optimum:
@@ -418,7 +458,7 @@ def initialise_model_(o):                                                       
             xs.append(x)
     o.iterations.i = o.iterations.c = len(ys) // o.repetitions
     with _timeit(o, "model update"):
-        update_(o.model, np.stack(xs, axis=1), np.array(ys))
+        _update_model(o, xs, ys)
     with _timeit(o, "model hyperparameter optimization"):
         optimizemodel_(o.modeloptimizer, o.model)
 
@@ -469,11 +509,13 @@ def boptimize_(o):
         for _ in range(o.repetitions):
             ys.append(_evaluate_function(o, x))
         with _timeit(o, "model update"):
-            update_(o.model, np.stack([x] * o.repetitions, axis=1), np.array(ys))   # :194-196
+            _update_model(o, [x] * o.repetitions, ys)                             # :194-196
         with _timeit(o, "model hyperparameter optimization"):
             optimizemodel_(o.modeloptimizer, o.model)
     with _timeit(o, "acquisition"):
-        if o.model.nobs > 0:
+        if isinstance(o.model, ConstrainedGPE):                                   # (no unconstrained model maximum: the feasible optimum stands)
+            o.model_optimum, o.model_optimizer = int(o.sense) * o.observed_optimum, np.array(o.observed_optimizer)
+        elif o.model.nobs > 0:
             o.model_optimum, o.model_optimizer = acquire_max(MaxMean(), o.model, o.lowerbounds, o.upperbounds,
                                                              o.acquisitionoptions, o.rng)   # acquire_model_max :200
     o.duration.now = time.time()

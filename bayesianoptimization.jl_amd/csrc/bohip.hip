@@ -23,6 +23,7 @@
 #include "../../include/bohip_mes.h"
 #include "../../include/bohip_ens.h"
 #include "../../include/bohip_ens_grad.h"
+#include "../../include/bohip_con.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -33,6 +34,7 @@
 #include "kernels_kg.hip"      // (after the scoring kernels: their arg-max order; acq_log.h's forms of h)
 #include "kernels_mes.hip"     // (after the scoring and sampling kernels: their generator and arg-max order; acq_log.h's continued fraction)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
+#include "kernels_con.hip"     // (after the scoring kernels: their functors, arg-max order and k_grad_finish's launch bounds; acq_log.h's continued fraction)
 #include "kernels_ascent.hip"
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
@@ -212,6 +214,11 @@ struct bohip_gp {
     // max-value entropy search (bohip_gp_mes / bohip_mes_values / bohip_mes_gumbel): ONE block, see ensure_mes
     char* mes_ws = nullptr;
     size_t mes_bytes = 0;
+    // constrained scoring (bohip_gp_score_con / bohip_con_values / bohip_gp_predict_grad): ONE block on the objective's handle, see
+    // ensure_con; ev_con joins this handle's stream to the objective's (made on first use)
+    char* con_ws = nullptr;
+    size_t con_bytes = 0;
+    hipEvent_t ev_con = nullptr;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -2200,6 +2207,22 @@ static int launch_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r
     return 0;
 }
 
+// k_post_grad_finish (kernels_con.hip): launch_grad without the functor
+template <int DT>
+static void launch_post_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, double* d_jmu, double* d_jvar,
+                             const double* UT, int S) {
+    if constexpr (DT <= 16) {   // large batches: two candidates per workgroup share the observation stream (launch_grad's rule)
+        if (r1 - r0 > SMALL_MAX) {
+            LAUNCH_FAM(fam_low(hp), (k_post_grad_finish_tiled<DT, true>), (k_post_grad_finish_tiled<DT, false>),
+                       dim3((unsigned)((r1 - r0 + GC - 1) / GC)), dim3(256), 0, g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld,
+                       d_jmu, d_jvar);
+            return;
+        }
+    }
+    LAUNCH_FAM(fam_low(hp), (k_post_grad_finish<DT, true>), (k_post_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
+               g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, d_jmu, d_jvar, g->dgparts, g->dgcount);
+}
+
 // A8: scores + gradients for R candidates (device pointers).  Per chunk: K*' -> V' (trigemm, V stored)
 // -> U' = V' W (k_gemm) -> mu, sigma^2, score -> gradient.
 static int score_grad_core(bohip_gp* g, int acq_id, const double* acq_params, const double* dXs, int64_t R, double* d_score,
@@ -2362,6 +2385,8 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->qei_ws) hipFree(g->qei_ws);
     if (g->kg_ws) hipFree(g->kg_ws);
     if (g->mes_ws) hipFree(g->mes_ws);
+    if (g->con_ws) hipFree(g->con_ws);
+    if (g->ev_con) hipEventDestroy(g->ev_con);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -3674,6 +3699,258 @@ int bohip_mes_gumbel(bohip_gp* g, const double* mu, const double* var, int64_t R
     HIPCHK(hipMemcpyAsync(maxvals, b.maxvals, (size_t)K * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
+    return 0;
+}
+
+// ---- constrained optimisation (kernels_con.hip, include/bohip_con.h) ---------------------------------------------
+static_assert(CON_CMAX == BOHIP_CON_CMAX && CON_FEAS == BOHIP_CON_FEASIBILITY, "the kernels' plan and the header agree");
+struct ConBufs {
+    double *mu, *var, *pmu, *pvar;   // [(C + 1) R] each: the moments and the partials of the score
+    double *value, *logfeas;         // [R] each
+    double *jmu, *jvar;              // [(C + 1) R d] each: the models' Jacobians (gradient route only)
+    double *grad;                    // [R d]
+    Best *blocks, *best;             // [CON_GRID_MAX], [1]
+};
+// ONE block on the handle: [mu | var | pmu | pvar | value | logfeas | records | jmu | jvar | grad]
+static int ensure_con(bohip_gp* g, int64_t C, int64_t R, bool jac, ConBufs* b) {
+    const size_t m = (size_t)(C + 1) * R, o_rec = (4 * m + 2 * (size_t)R) * 8, o_j = o_rec + (CON_GRID_MAX + 1) * sizeof(Best),
+                 need = o_j + (jac ? (2 * m + (size_t)R) * g->d * 8 : 0);
+    if (g->con_bytes < need) {
+        if (g->con_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->con_ws)); g->con_ws = nullptr; }
+        const size_t cap = std::max(need, g->con_bytes + g->con_bytes / 2);
+        g->con_bytes = 0;
+        HIPCHK(hipMalloc(&g->con_ws, cap));
+        g->con_bytes = cap;
+    }
+    double* p = reinterpret_cast<double*>(g->con_ws);
+    b->mu = p; b->var = p + m; b->pmu = p + 2 * m; b->pvar = p + 3 * m; b->value = p + 4 * m; b->logfeas = b->value + R;
+    b->blocks = reinterpret_cast<Best*>(g->con_ws + o_rec);
+    b->best = b->blocks + CON_GRID_MAX;
+    double* j = reinterpret_cast<double*>(g->con_ws + o_j);
+    b->jmu = jac ? j : nullptr; b->jvar = jac ? j + m * g->d : nullptr; b->grad = jac ? j + 2 * m * g->d : nullptr;
+    return 0;
+}
+
+static int launch_post_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, double* d_jmu, double* d_jvar,
+                                const double* UT) {
+    int S = 1;   // launch_grad_any's observation split
+    if (r1 - r0 <= SMALL_MAX) S = (int)std::min<int64_t>(16, std::max<int64_t>(1, g->n / 768));
+    if (S > 1) CHK(ensure_small_counters(g));
+    dispatch_dt(g->d, [&](auto dt) { launch_post_grad<decltype(dt)::value>(g, dXs, r0, r1, hp, d_jmu, d_jvar, UT, S); });
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The posterior of R candidates (device pointers) on g's stream: mu, sigma^2 and, with d_jmu, the two Jacobians [r][d].  The routes of
+// score_grad_core without its fused small pass (the finish of that pass has the functor inside kernels at their register limit): the
+// split-K posterior where split_plan says so, K*' chunks otherwise.  Without d_jmu the same launches less V' / U': the moments of a
+// value call are those of a gradient call bit for bit.
+static int posterior_grad_core(bohip_gp* g, const double* dXs, int64_t R, double* d_mu, double* d_var, double* d_jmu, double* d_jvar) {
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(ensure_fresh(g));
+    CHK(ensure_score_scratch(g, R));
+    CHK(one_time_kernel_setup());
+    const bool jac = d_jmu != nullptr;
+    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE;
+    const int T = (int)(Npad / TILE);
+    const KernelHyper hp = make_hyper(g);
+    const AcqParams ap{ACQ_MAXMEAN, 0.0, 0.0};
+    const double sigma2 = std::exp(2.0 * g->logsig);
+    const SplitPlan sp = split_plan(g, R);
+    if (sp.nsl > 0) {
+        CHK(split_posterior(g, dXs, R, sp, jac));
+        t_begin(g, "con_post");
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, 0, g->dmu_raw, R, sigma2, g->beta,
+                           ap, d_mu, d_var, (double*)nullptr, (Best*)nullptr);
+        HIPCHK(hipGetLastError());
+        if (jac) CHK(launch_post_grad_any(g, dXs, 0, R, hp, d_jmu, d_jvar, g->dUT));
+        t_end(g);
+        return 0;
+    }
+    if (jac) CHK(ensure_grad_scratch(g));
+    const int64_t rc = g->chunk_now;
+    g->q_tiles = T;
+    for (int64_t r0 = 0; r0 < R; r0 += rc) {
+        const int64_t r1 = std::min(R, r0 + rc);
+        t_begin(g, "kstar");
+        CHK(launch_kstar_any(g, dXs, r0, r1, Npad, hp));
+        t_end(g);
+        t_begin(g, jac ? "trigemm_sq+V" : "trigemm_sq");
+        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, jac ? g->dVT : nullptr));
+        t_end(g);
+        if (jac) {
+            const int CT = (int)((r1 - r0 + TILE - 1) / TILE);
+            t_begin(g, "gemm_U");
+            GemmNTParams p{};  // U'[r][j] = sum_i V'[r][i] W'[j][i]   (B = W' upper-triangular: i >= j)
+            p.A = g->dVT; p.lda = g->ld; p.B = g->dWT; p.ldb = g->ld; p.C = g->dUT; p.ldc = g->ld;
+            p.mt = CT; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.klo_from_n = 1;
+            CHK(launch_gemm_nt(g, p));
+            t_end(g);
+        }
+        t_begin(g, "con_post");
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq + r0, Rpad, T, g->dmu_raw + r0,
+                           r1 - r0, sigma2, g->beta, ap, d_mu + r0, d_var + r0, (double*)nullptr, (Best*)nullptr);
+        HIPCHK(hipGetLastError());
+        if (jac) CHK(launch_post_grad_any(g, dXs, r0, r1, hp, d_jmu, d_jvar, g->dUT));
+        t_end(g);
+    }
+    return 0;
+}
+
+static int con_make_params(const char* who, int acq_id, const double* acq_params, int64_t C, const double* thresholds, const int* senses,
+                           ConParams* cp) {
+    const std::string pre = std::string(who) + ": ";
+    if (C < 0 || C > BOHIP_CON_CMAX) return fail(BOHIP_E_ARG, pre + "C must be in [0, " + std::to_string(BOHIP_CON_CMAX) + "]");
+    if (C > 0 && (!thresholds || !senses)) return fail(BOHIP_E_ARG, pre + "thresholds and senses are required");
+    if (acq_id != BOHIP_ACQ_EI && acq_id != BOHIP_ACQ_PI && acq_id != BOHIP_ACQ_LOGEI && acq_id != BOHIP_CON_FEASIBILITY)
+        return fail(BOHIP_E_ARG, pre + "acq_id must be EI, PI, LogEI or BOHIP_CON_FEASIBILITY: a signed score has no product form");
+    if (acq_id != BOHIP_CON_FEASIBILITY && !acq_params) return fail(BOHIP_E_ARG, pre + "acq_params required for this acquisition");
+    *cp = ConParams{};
+    cp->acq = acq_id; cp->C = (int)C; cp->p0 = acq_id != BOHIP_CON_FEASIBILITY ? acq_params[0] : 0.0;
+    for (int64_t c = 0; c < C; ++c) {
+        if (!std::isfinite(thresholds[c])) return fail(BOHIP_E_ARG, pre + "threshold " + std::to_string(c) + " is not finite");
+        if (senses[c] != 1 && senses[c] != -1) return fail(BOHIP_E_ARG, pre + "sense " + std::to_string(c) + " must be +1 or -1");
+        cp->thr[c] = thresholds[c]; cp->sense[c] = (double)senses[c];
+    }
+    return 0;
+}
+// the combine and the record on g's stream (no synchronisation, no copies)
+static int con_combine_stage(bohip_gp* g, const ConParams& cp, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
+    const int nb = (int)std::min<int64_t>(CON_GRID_MAX, (R + 255) / 256);
+    t_begin(g, "con_combine");
+    if (partials || jac)
+        hipLaunchKernelGGL(k_con_combine<true>, dim3(nb), dim3(256), 0, g->stream, cp, (const double*)b.mu, (const double*)b.var, R, R, b.value,
+                           b.logfeas, b.pmu, b.pvar, (const double*)b.jmu, (const double*)b.jvar, (int64_t)R * g->d, g->d,
+                           jac ? b.grad : (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
+    else
+        hipLaunchKernelGGL(k_con_combine<false>, dim3(nb), dim3(256), 0, g->stream, cp, (const double*)b.mu, (const double*)b.var, R, R, b.value,
+                           b.logfeas, (double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, g->d,
+                           (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
+    if (want_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, b.blocks, nb, b.best, 0ll);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_gp_predict_grad(bohip_gp* g, const double* Xs, int64_t R, double* mu, double* var, double* dmu, double* dvar) {
+    if (!g || R < 0 || (R > 0 && (!Xs || !mu || !var || !dmu || !dvar))) return fail(BOHIP_E_ARG, "predict_grad: bad arguments");
+    if (R == 0) return 0;
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_xs(g, R));
+    ConBufs b{};
+    CHK(ensure_con(g, 0, R, true, &b));
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(posterior_grad_core(g, g->dXs, R, b.mu, b.var, b.jmu, b.jvar));
+    HIPCHK(hipMemcpyAsync(mu, b.mu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(var, b.var, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(dmu, b.jmu, (size_t)R * g->d * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(dvar, b.jvar, (size_t)R * g->d * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_con_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t C, const double* thresholds, const int* senses,
+                     const double* mu, const double* var, int64_t R, double* value, double* logfeas, double* dmu, double* dvar,
+                     bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "con_values: null handle");
+    ConParams cp;
+    CHK(con_make_params("con_values", acq_id, acq_params, C, thresholds, senses, &cp));
+    if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "con_values: bad arguments");
+    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "con_values: dmu and dvar are given together or not at all");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    ConBufs b{};
+    CHK(ensure_con(g, C, R, false, &b));
+    const size_t m = (size_t)(C + 1) * R * 8;
+    HIPCHK(hipMemcpyAsync(b.mu, mu, m, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(b.var, var, m, hipMemcpyHostToDevice, g->stream));
+    CHK(con_combine_stage(g, cp, b, R, dmu != nullptr, false, best != nullptr));
+    HIPCHK(hipMemcpyAsync(value, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (logfeas) HIPCHK(hipMemcpyAsync(logfeas, b.logfeas, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (dmu) {
+        HIPCHK(hipMemcpyAsync(dmu, b.pmu, m, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(dvar, b.pvar, m, hipMemcpyDeviceToHost, g->stream));
+    }
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_score_con(bohip_gp* obj, int acq_id, const double* acq_params, int64_t C, bohip_gp* const* cons, const double* thresholds,
+                       const int* senses, const double* Xs, int64_t R, double* score, double* logfeas, double* grad, double* mu,
+                       double* var, bohip_best* best) {
+    if (!obj) return fail(BOHIP_E_ARG, "score_con: null objective handle");
+    ConParams cp;
+    CHK(con_make_params("score_con", acq_id, acq_params, C, thresholds, senses, &cp));
+    if (C > 0 && !cons) return fail(BOHIP_E_ARG, "score_con: cons is null");
+    for (int64_t c = 0; c < C; ++c) {
+        if (!cons[c]) return fail(BOHIP_E_ARG, "score_con: constraint handle " + std::to_string(c) + " is null");
+        if (cons[c]->d != obj->d) return fail(BOHIP_E_ARG, "score_con: constraint " + std::to_string(c) + " has another dimension");
+        if (cons[c]->device != obj->device) return fail(BOHIP_E_ARG, "score_con: constraint " + std::to_string(c) + " lives on another device");
+    }
+    if (R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_con: bad arguments");
+    const bool feas = acq_id == BOHIP_CON_FEASIBILITY;
+    if (!feas && obj->n == 0) return fail(BOHIP_E_STATE, "score_con: the objective has no observations");
+    for (int64_t c = 0; c < C; ++c)
+        if (cons[c]->n == 0) return fail(BOHIP_E_STATE, "score_con: constraint " + std::to_string(c) + " has no observations");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(obj->device));
+    const bool jac = grad != nullptr;
+    const int d = obj->d;
+    t_reset(obj);
+    CHK(ensure_xs(obj, R));
+    ConBufs b{};
+    CHK(ensure_con(obj, C, R, jac, &b));
+    HIPCHK(hipMemcpyAsync(obj->dXs, Xs, (size_t)R * d * 8, hipMemcpyHostToDevice, obj->stream));
+    auto event_of = [](bohip_gp* m) -> hipError_t {
+        return m->ev_con ? hipSuccess : hipEventCreateWithFlags(&m->ev_con, hipEventDisableTiming);
+    };
+    // the candidates are on the device once, in the objective's block: the constraints' streams wait for that copy, run their own
+    // posterior into the objective's block and are joined back before the combine -- no host wait in between
+    HIPCHK(event_of(obj));
+    if (C > 0) HIPCHK(hipEventRecord(obj->ev_con, obj->stream));
+    if (feas) {
+        HIPCHK(hipMemsetAsync(b.mu, 0xff, (size_t)R * 8, obj->stream));    // (row 0 is not computed: NaN)
+        HIPCHK(hipMemsetAsync(b.var, 0xff, (size_t)R * 8, obj->stream));
+    } else {
+        CHK(posterior_grad_core(obj, obj->dXs, R, b.mu, b.var, b.jmu, b.jvar));
+    }
+    for (int64_t c = 0; c < C; ++c) {
+        bohip_gp* m = cons[c];
+        if (m != obj) {
+            bool first = true;
+            for (int64_t e = 0; e < c; ++e) first = first && cons[e] != m;
+            if (first) { t_reset(m); HIPCHK(hipStreamWaitEvent(m->stream, obj->ev_con, 0)); }
+        }
+        const size_t o = (size_t)(c + 1) * R;
+        CHK(posterior_grad_core(m, obj->dXs, R, b.mu + o, b.var + o, jac ? b.jmu + o * d : nullptr, jac ? b.jvar + o * d : nullptr));
+        if (m != obj) { HIPCHK(event_of(m)); HIPCHK(hipEventRecord(m->ev_con, m->stream)); }
+    }
+    for (int64_t c = 0; c < C; ++c)
+        if (cons[c] != obj) HIPCHK(hipStreamWaitEvent(obj->stream, cons[c]->ev_con, 0));
+    CHK(con_combine_stage(obj, cp, b, R, false, jac, best != nullptr));
+    const size_t m_bytes = (size_t)(C + 1) * R * 8;
+    if (score) HIPCHK(hipMemcpyAsync(score, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, obj->stream));
+    if (logfeas) HIPCHK(hipMemcpyAsync(logfeas, b.logfeas, (size_t)R * 8, hipMemcpyDeviceToHost, obj->stream));
+    if (grad) HIPCHK(hipMemcpyAsync(grad, b.grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, obj->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, b.mu, m_bytes, hipMemcpyDeviceToHost, obj->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, b.var, m_bytes, hipMemcpyDeviceToHost, obj->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, obj->stream));
+    HIPCHK(hipStreamSynchronize(obj->stream));
+    t_collect(obj);
+    for (int64_t c = 0; c < C; ++c)
+        if (cons[c] != obj) t_collect(cons[c]);
     return 0;
 }
 

@@ -443,6 +443,21 @@ class ElasticGPE:
         stream only.  Returns (values[R], best_val, best_idx), or (values, dmu, dvar, best_val, best_idx) with want_grad."""
         return _mes_values(self._lib, self._h, mu, var, maxvals, want_grad)
 
+    def predict_grad(self, xs):
+        """The posterior and its own Jacobians in x (bohip_gp_predict_grad, include/bohip_con.h): (mu[R], var[R], dmu[d, R],
+        dvar[d, R]), dmu = grad mu, dvar = grad sigma^2 reported unmasked (where var == 0 the clamp is the caller's).  An extension:
+        what a score over several models (ConstrainedGPE) is differentiated through."""
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        mu, var = np.empty(max(R, 1)), np.empty(max(R, 1))
+        dmu, dvar = np.empty((self.dim, max(R, 1)), order="F"), np.empty((self.dim, max(R, 1)), order="F")
+        check(self._lib.bohip_gp_predict_grad(self._h, _ptr(xs), R, _ptr(mu), _ptr(var), _ptr(dmu), _ptr(dvar)))
+        return mu[:R], var[:R], dmu[:, :R], dvar[:, :R]
+
+    def con_values(self, acq, params, thresholds, senses, mu, var, want_grad=False):
+        """The combine stage of a constrained score alone, on the caller's moments (bohip_con_values); see con_values."""
+        return con_values(self, acq, params, thresholds, senses, mu, var, want_grad)
+
     def mes_gumbel(self, mu, var, samples=16, seed=0, floor=None):
         """The max-value sampler of mode "gumbel" alone on the caller's (mu, var) (bohip_mes_gumbel).  Returns (quantiles[3],
         maxvals[samples])."""
@@ -840,6 +855,148 @@ def _mes_gumbel(lib, handle, mu, var, samples, seed, floor):
     check(lib.bohip_mes_gumbel(handle, _ptr(mu), _ptr(var), mu.size, K, int(seed), -math.inf if floor is None else float(floor),
                                _ptr(quant), _ptr(maxvals)))
     return quant, maxvals
+
+
+# ---- constrained optimisation (include/bohip_con.h) -------------------------------------------------------------
+CON_ACQ = {"EI": _lib.ACQ["EI"], "PI": _lib.ACQ["PI"], "LogEI": _lib.ACQ["LogEI"], "Feasibility": _lib.CON_FEASIBILITY}
+_ip = C.POINTER(C.c_int)
+
+
+class ConstrainedScore:
+    """Result of ConstrainedGPE.score: scores[R], logfeas[R] (sum_c log P(constraint c holds)), grad[d, R] or None, mu and var
+    [(C + 1), R] (row 0 the objective; NaN under "Feasibility"), best_val / best_idx (first maximum, NaN never wins, -Inf / -1)."""
+    __slots__ = ("scores", "logfeas", "grad", "mu", "var", "best_val", "best_idx")
+
+    def __init__(self, scores, logfeas, grad, mu, var, best_val, best_idx):
+        self.scores, self.logfeas, self.grad, self.mu, self.var = scores, logfeas, grad, mu, var
+        self.best_val, self.best_idx = best_val, best_idx
+
+    def __iter__(self):
+        return iter((self.scores, self.logfeas, self.grad, self.mu, self.var, self.best_val, self.best_idx))
+
+
+def _con_args(acq, params, thresholds, senses):
+    if acq not in CON_ACQ:
+        raise ValueError(f"a constrained score takes one of {sorted(CON_ACQ)}, got {acq!r}: a signed score has no product form")
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)).ravel())
+    s = np.ascontiguousarray(np.atleast_1d(np.asarray(senses)).ravel().astype(np.intc))
+    if t.size != s.size:
+        raise ValueError("thresholds and senses differ in length")
+    p = np.ascontiguousarray(np.concatenate([np.atleast_1d(np.asarray(params if params is not None else [], dtype=np.float64)).ravel(),
+                                             np.zeros(2)]))
+    return CON_ACQ[acq], p, t, s
+
+
+def con_values(model, acq, params, thresholds, senses, mu, var, want_grad=False):
+    """bohip_con_values: the feasibility-weighted score of `acq` ("EI", "PI": a exp(L); "LogEI": a + L; "Feasibility": L) on the
+    moments mu, var [(C + 1), R] (row 0 the objective, the others the constraints; L = sum_c log Phi(s_c (mu_c - t_c) / sigma_c)).
+    `model` gives the device only.  -> (value[R], logfeas[R], dmu, dvar, best_val, best_idx); dmu and dvar [(C + 1), R] are the
+    partials of the score in every model's moments, None without want_grad."""
+    aid, p, t, s = _con_args(acq, params, thresholds, senses)
+    mu = np.ascontiguousarray(np.atleast_2d(np.asarray(mu, dtype=np.float64)))
+    var = np.ascontiguousarray(np.atleast_2d(np.asarray(var, dtype=np.float64)))
+    if mu.shape != var.shape or mu.shape[0] != t.size + 1:
+        raise ValueError(f"mu and var must both be (C + 1) x R = {t.size + 1} x R, got {mu.shape} and {var.shape}")
+    R = mu.shape[1]
+    value, logfeas = np.empty(max(R, 1)), np.empty(max(R, 1))
+    dmu, dvar = (np.empty((t.size + 1, max(R, 1))), np.empty((t.size + 1, max(R, 1)))) if want_grad else (None, None)
+    best = Best()
+    check(model._lib.bohip_con_values(model._h, aid, _ptr(p), t.size, _ptr(t), s.ctypes.data_as(_ip), _ptr(mu), _ptr(var), R,
+                                      _ptr(value), _ptr(logfeas), _ptr(dmu) if want_grad else None,
+                                      _ptr(dvar) if want_grad else None, C.byref(best)))
+    return value[:R], logfeas[:R], dmu, dvar, best.val, best.idx
+
+
+class ConstrainedGPE:
+    """An objective model and C constraint models scored together (include/bohip_con.h; an extension: the reference's
+    acquisition closes over one model).  Constraint c is feasible where senses[c] * (g_c(x) - thresholds[c]) >= 0.  The members are
+    ElasticGPE models of one dimension on one device, each with its own kernel, hyper-parameters and observations; one model may
+    serve two constraints (t_lo <= g <= t_hi).  `x`, `y`, `nobs` are the objective's, so the model reads like one model to BOpt."""
+
+    def __init__(self, objective, constraints, thresholds, senses):
+        self.objective, self.constraints = objective, list(constraints)
+        self.thresholds = np.atleast_1d(np.asarray(thresholds, dtype=np.float64)).ravel().copy()
+        self.senses = np.atleast_1d(np.asarray(senses)).ravel().astype(np.int64)
+        C_ = len(self.constraints)
+        if not 0 <= C_ <= _lib.CON_CMAX:
+            raise ValueError(f"0 .. {_lib.CON_CMAX} constraints are supported, got {C_}")
+        if self.thresholds.size != C_ or self.senses.size != C_:
+            raise ValueError("constraints, thresholds and senses differ in length")
+        if not np.all(np.isfinite(self.thresholds)):
+            raise ValueError("thresholds must be finite")
+        if not np.all(np.abs(self.senses) == 1):
+            raise ValueError("senses are +1 (feasible where g >= t) or -1 (feasible where g <= t)")
+        for m in self.members:
+            if type(m).__name__ == "MultiGPE":
+                raise ValueError("ConstrainedGPE members are single-device models: MultiGPE is not supported")
+            if m.dim != objective.dim:
+                raise ValueError("the members differ in dimension")
+
+    @property
+    def members(self):
+        return [self.objective] + self.constraints
+
+    dim = property(lambda self: self.objective.dim)
+    x = property(lambda self: self.objective.x)
+    y = property(lambda self: self.objective.y)
+    nobs = property(lambda self: self.objective.nobs)
+
+    def __repr__(self):
+        return f"ConstrainedGPE({self.objective!r}, {len(self.constraints)} constraints)"
+
+    def is_feasible(self, g):
+        """Whether observed constraint values g [C] or [C, n] satisfy every constraint."""
+        g = np.asarray(g, dtype=np.float64)
+        t, s = (self.thresholds, self.senses) if g.ndim == 1 else (self.thresholds[:, None], self.senses[:, None])
+        return np.all(s * (g - t) >= 0, axis=0) if g.size else np.ones(g.shape[1:], dtype=bool)
+
+    def observed_g(self):
+        """The constraints' observations [C, n]; the members' observations must be aligned (update_ keeps them so)."""
+        n = self.objective.nobs
+        if any(m.nobs != n for m in self.constraints):
+            raise ValueError("the members' observations are not aligned: feasibility of an observation needs every member's value")
+        return np.stack([np.asarray(m.y, dtype=np.float64) for m in self.constraints]) if self.constraints else np.zeros((0, n))
+
+    def feasible_mask(self):
+        return np.asarray(self.is_feasible(self.observed_g()), dtype=bool).reshape(-1)
+
+    def feasible_incumbent(self):
+        """The best observed y among the observations whose observed g satisfy every constraint, or None."""
+        if self.objective.nobs == 0:
+            return None
+        ok = self.feasible_mask()
+        return float(np.max(np.asarray(self.objective.y)[ok])) if ok.any() else None
+
+    def update_(self, x, y, g):
+        """Append observations to every member: x [d, n], y [n], g [C, n] (or [C] for one point)."""
+        y = np.atleast_1d(np.asarray(y, dtype=np.float64))
+        g = np.asarray(g, dtype=np.float64).reshape(len(self.constraints), y.size)
+        self.objective.append_(x, y)
+        for c, m in enumerate(self.constraints):
+            m.append_(x, g[c])
+        return self
+
+    def score(self, acq, params, xs, want_grad=False, want_moments=True):
+        """ONE bohip_gp_score_con call: every member's posterior on its own stream, the combine and the arg-max on the device.
+        acq: "EI" / "PI" (a exp(L)), "LogEI" (a + L) or "Feasibility" (L alone).  xs is d x R.  -> ConstrainedScore."""
+        aid, p, t, s = _con_args(acq, params, self.thresholds, self.senses)
+        obj = self.objective
+        xs = _cols(xs, obj.dim)
+        R, C_ = xs.shape[1], len(self.constraints)
+        n = max(R, 1)
+        scores, logfeas = np.empty(n), np.empty(n)
+        grad = np.empty((obj.dim, n), order="F") if want_grad else None
+        mu, var = (np.empty((C_ + 1, n)), np.empty((C_ + 1, n))) if want_moments and R > 0 else (None, None)
+        handles = (C.c_void_p * max(C_, 1))(*[m._h for m in self.constraints])
+        best = Best()
+        check(obj._lib.bohip_gp_score_con(obj._h, aid, _ptr(p), C_, handles, _ptr(t), s.ctypes.data_as(_ip), _ptr(xs), R,
+                                          _ptr(scores), _ptr(logfeas), _ptr(grad) if want_grad else None,
+                                          _ptr(mu) if mu is not None else None, _ptr(var) if var is not None else None, C.byref(best)))
+        return ConstrainedScore(scores[:R], logfeas[:R], grad[:, :R] if want_grad else None, mu, var, best.val, best.idx)
+
+    def close(self):
+        for m in self.members:
+            m.close()
 
 
 class PosteriorPaths:

@@ -352,6 +352,7 @@ include("BOHipKG.jl")      # the knowledge gradient over a candidate set (includ
 include("BOHipEns.jl")     # an acquisition averaged over hyper-parameter settings (include/bohip_ens.h): score_ensemble
 include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ensemble_grad
 include("BOHipMES.jl")     # max-value entropy search over a candidate set (include/bohip_mes.h): mes, mes_values, mes_gumbel, MaxValueEntropySearch
+include("BOHipCon.jl")     # constrained optimisation (include/bohip_con.h): predict_grad, con_values, score_constrained
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
