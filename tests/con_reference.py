@@ -29,6 +29,12 @@ EPS = np.finfo(np.float64).eps
 # d/dvar's is PI's and EI's phi z / (2 s2) at |z| ~ 12, where exp(-z^2 / 2) carries z^2 eps.  The host test bounds the twin by
 # 2 x WORST (another libm), the device test bounds the kernel by 16 x WORST.
 WORST = {"value": 2.6e-15, "dmu": 3.8e-14, "dvar": 1.8e-12}
+# The same measurement for more than 5 constraints, over crafted_near's grid (every form, C = 6, 15, 16, R = 257; tests/test_con_host.py
+# test_twin_against_mpmath_many_constraints): value 2.03e-15 (LogEI, C = 6: not larger, WORST's figure stands), d/dmu 1.47e-13 and
+# d/dvar 1.21e-11 (both EI at C = 6: the objective's (D - z) phi / sigma and phi z / (2 s2) terms at sigma ~ 1e-3 -- this grid pairs
+# other z with the small sigmas than `crafted` does; at C = 15 and 16 the figures are 3.3e-14 and 1.2e-12).  Rounded up to two digits.
+# Granted for C > 5 only: the host test bounds the twin by 2 x WORST_MANY, the device test bounds the kernel by 16 x WORST_MANY.
+WORST_MANY = {"value": 2.6e-15, "dmu": 1.5e-13, "dvar": 1.3e-11}
 PRODUCT = ("EI", "PI")
 FORMS = ("EI", "PI", "LogEI", "Feasibility")
 
@@ -297,6 +303,39 @@ def crafted(C, R, seed=0, tau=0.3):
         mu[0, 11] = np.nan                    # NaN moments: the objective's mean, a constraint's variance
         if C:
             var[C, 12] = np.nan
+    return thr, senses, mu, var
+
+
+def crafted_near(C, R, seed=0, tau=0.3):
+    """(thr[C], senses[C], mu[(C + 1), R], var[(C + 1), R]) for many constraints: `crafted` sends every constraint's z down to -40, so
+    with C = 16 the product forms are 0 at all but a few candidates.  Here z runs over [-1, 4] (both sides of 0), which keeps
+    L = sum_c log Phi(z_c) within a few units of 0, and a minority of entries in EVERY constraint row, at columns of the row's own
+    (16 c + k) mod R, are the hard ones: k = 0 the deep tail z = -40, 1 and 2 the neighbours of the switch at -4, 3 to 5
+    sigma^2 = 0 above, below and on the threshold, 6 a NaN (mean in even rows, variance in odd ones).  Neighbouring constraints
+    differ in threshold (by more than 1) and in sense; no two thresholds are equal.  The objective's z runs over [-12, 6] as in
+    `crafted`, with a clamped variance on both sides of tau and a NaN mean in the last columns.  R >= 17."""
+    assert R >= 17
+    rng = np.random.default_rng(seed)
+    thr = np.array([(-1.0) ** c * (0.5 + 0.1 * c) for c in range(C)])
+    senses = np.array([1 if c % 2 == 0 else -1 for c in range(C)], dtype=np.int64)
+    mu, var = np.empty((C + 1, R)), np.empty((C + 1, R))
+    sd0 = 10.0 ** rng.uniform(-3, 1, R)
+    z0 = rng.permutation(np.linspace(-12.0, 6.0, R))
+    mu[0], var[0] = tau + z0 * sd0, sd0 * sd0
+    var[0, R - 3], var[0, R - 2] = 0.0, 0.0
+    mu[0, R - 3:] = [tau + 0.25, tau - 0.25, np.nan]
+    for c in range(C):
+        sd = 10.0 ** rng.uniform(-3, 1, R)
+        z = rng.permutation(np.linspace(-1.0, 4.0, R))
+        k = [(16 * c + i) % R for i in range(7)]
+        z[k[:3]] = [-40.0, np.nextafter(-4.0, 0.0), np.nextafter(-4.0, -5.0)]
+        mu[c + 1], var[c + 1] = thr[c] + senses[c] * z * sd, sd * sd
+        var[c + 1, k[3:6]] = 0.0
+        mu[c + 1, k[3:6]] = [thr[c] + 0.5, thr[c] - 0.5, thr[c]]
+        if c % 2 == 0:
+            mu[c + 1, k[6]] = np.nan
+        else:
+            var[c + 1, k[6]] = np.nan
     return thr, senses, mu, var
 
 

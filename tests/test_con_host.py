@@ -3,6 +3,7 @@
 threshold -- the twin's gradient against central differences, and the plumbing of Constrained / ConstrainedGPE through setparams_,
 acquisitionfunction, acquire_max and BOpt on duck-typed members whose score is the twin."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -91,6 +92,42 @@ def test_twin_against_mpmath(acq, C_):
         assert not np.any(np.isnan(pm[:, np.isfinite(f)])) and not np.any(np.isnan(pv[:, np.isfinite(f)]))
     print(f"{acq} C={C_}: worst share of 2 x WORST {shares}")
     assert max(shares.values()) <= 1.0, shares
+
+
+@functools.lru_cache(maxsize=None)
+def many_ref(acq, C_, R=257):
+    """crafted_near's moments and the 50-digit table of one case (tests/test_limits_gpu.py shares the recipe)."""
+    thr, s, mu, var = cr.crafted_near(C_, R, seed=7 * C_ + R)
+    out = (thr, s, mu, var) + cr.mp_table(acq, [0.3], thr, s, mu, var)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def live_share(fr):
+    """The share of candidates whose 50-digit score is finite and not 0."""
+    return float(np.mean(np.isfinite(fr) & (fr != 0.0)))
+
+
+@pytest.mark.parametrize("acq", cr.FORMS)
+@pytest.mark.parametrize("C_", [6, 15, 16])
+def test_twin_against_mpmath_many_constraints(acq, C_):
+    """More than 5 constraints, on crafted_near's grid (L within a few units of 0, the hard entries in every row): the twin within
+    2 x WORST_MANY of the 50-digit evaluator -- the measurement WORST_MANY records.  Under the product forms at least half of the
+    candidates have a finite score that is not 0, so the comparison is not 0 against 0."""
+    thr, s, mu, var, fr, Lr, pmr, pvr = many_ref(acq, C_)
+    assert all(thr[c] != thr[c + 1] and s[c] != s[c + 1] for c in range(C_ - 1)) and len(set(thr.tolist())) == C_
+    f, L, pm, pv = cr.combine(acq, [0.3], thr, s, mu, var)
+    shares = {k: cr.worst_share(got, ref, 2 * cr.WORST_MANY[k]) for k, got, ref in (("value", f, fr), ("dmu", pm, pmr), ("dvar", pv, pvr))}
+    ok = np.isfinite(Lr)
+    shares["logfeas"] = cr.worst_share(L[ok], Lr[ok], 2 * cr.WORST_MANY["value"])
+    print(f"{acq} C={C_}: worst share of 2 x WORST_MANY {shares}; {live_share(fr):.2f} of the scores are finite and not 0")
+    assert max(shares.values()) <= 1.0, shares
+    assert live_share(fr) >= 0.5
+    for c in range(C_):                                                         # the hard entries sit in every row, 5 to 15 included
+        k = [(16 * c + i) % 257 for i in range(7)]
+        assert L[k[4 if s[c] > 0 else 3]] == -np.inf and np.isnan(f[k[6]]) and Lr[k[0]] < -700.0
+    assert not np.any(np.isnan(pm[:, np.isfinite(f)])) and not np.any(np.isnan(pv[:, np.isfinite(f)]))
 
 
 def test_feasibility_with_one_constraint_is_log_pi():
