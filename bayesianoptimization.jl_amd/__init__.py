@@ -8,9 +8,10 @@ from . import _lib
 from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
-                    score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values)
+                    score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values,
+                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
@@ -26,4 +27,5 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "maxduration_", "maxiterations_", "optimize", "acquire_batch", "acquire_thompson_batch",
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
            "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
-           "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values"]
+           "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values",
+           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -189,6 +189,15 @@ CON_SIGNATURES = {
                                      C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_mo.h declares (two objectives: the observed front on the host, the exact EHVI stage, the whole call)
+MO_FRONT_MAX = 1024
+MO_GROUP = 16
+MO_SIGNATURES = {
+    "bohip_mo_front": (C.c_int, [_dp, C.c_int64, _dp, _dp, C.c_int64, _i64p, _dp]),
+    "bohip_mo_ehvi_values": (C.c_int, [_gp, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_gp_score_mo": (C.c_int, [_gp, _gp, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -246,7 +255,7 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
-                              + list(CON_SIGNATURES.items())):
+                              + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

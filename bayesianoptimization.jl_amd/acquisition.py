@@ -206,6 +206,15 @@ class Constrained(AbstractAcquisition):
         return [0.0] if self.feasibility_only else self.a.params()
 
 
+class ExpectedHypervolumeImprovement(AbstractAcquisition):
+    """The exact expected hypervolume improvement of two objectives over the observed front of a MultiObjectiveGPE
+    (include/bohip_mo.h; Emmerich et al. 2016, Yang et al. 2019).  An extension: the reference optimises one objective.
+    It has no parameter of its own: the front and the reference point are the model's.  acquisitionfunction takes a d x R matrix;
+    acquire_max takes the device's arg-max over `maxeval` Latin-hypercube candidates per restart and, with the option "refine": n > 0,
+    climbs the n best on the gradient route."""
+    acq_id = "EHVI"
+
+
 def _hyper_samples(model):
     hs = getattr(model, "hyper_samples", None)
     if hs is None:
@@ -285,6 +294,11 @@ class MutualInformation(AbstractAcquisition):                 # :126-141
         return [self.sqrt_alpha, self.gamma_hat]
 
 
+def _need_mo(model):
+    if not hasattr(model, "hypervolume"):
+        raise ValueError(f"ExpectedHypervolumeImprovement needs a MultiObjectiveGPE, not {type(model).__name__}")
+
+
 def acquisitionfunction(a, model, rng=None):
     """:4-9, :108, :111.  x (vector or d x R matrix) -> score(s); batches run fused on the device."""
     if isinstance(a, KnowledgeGradient):
@@ -314,6 +328,16 @@ def acquisitionfunction(a, model, rng=None):
             return model.score(a.acq_id, a.params(), x).scores
 
         return constrained
+    if isinstance(a, ExpectedHypervolumeImprovement):
+        _need_mo(model)
+
+        def ehvi(x):
+            x = np.asarray(x, dtype=np.float64)
+            if x.ndim != 2:
+                raise ValueError("ExpectedHypervolumeImprovement takes a d x R candidate matrix")
+            return model.score(x).scores
+
+        return ehvi
     if isinstance(a, Marginalised):
         def marginal(x):
             x = np.asarray(x, dtype=np.float64)
@@ -337,7 +361,8 @@ def acquisitionfunction(a, model, rng=None):
 
 # ---- src/acquisition.jl ----------------------------------------------------------------------------------
 def defaultoptions(model_type, acq_type):                    # :4-9
-    if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch, Constrained)):
+    if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch, Constrained,
+                                                                     ExpectedHypervolumeImprovement)):
         return dict(method="LD_LBFGS", restarts=1, maxeval=1024)   # (1024: the smallest candidate chunk a model can have)
     if isinstance(acq_type, type) and issubclass(acq_type, ThompsonSamplingSimple):
         return dict(method="GN_DIRECT_L", restarts=1, maxeval=2000)
@@ -730,14 +755,28 @@ def _acquire_max_constrained(a, model, lb, ub, restarts, maxeval, rng, opts=None
     takes its arg-max record; the first maximum over the restarts wins (strict '>').  "refine": n > 0 (default 0: the candidate stage
     alone): the n highest-scoring distinct candidates then start ONE batched L-BFGS ascent inside the box, fg = one gradient-route
     model.score call per step; the best ascended point replaces the candidate maximum only where it is strictly better."""
+    acq, p = a.acq_id, a.params()
+    return _acquire_max_candidates(lambda xs, want_grad=False: model.score(acq, p, xs, want_grad=want_grad), lb, ub, restarts,
+                                   maxeval, rng, opts)
+
+
+def _acquire_max_mo(model, lb, ub, restarts, maxeval, rng, opts=None):
+    """ExpectedHypervolumeImprovement over a MultiObjectiveGPE: _acquire_max_constrained's two stages on model.score(xs), ONE
+    bohip_gp_score_mo call per restart and, with "refine": n > 0, one gradient-route call per step of the ascent."""
+    return _acquire_max_candidates(lambda xs, want_grad=False: model.score(xs, want_grad=want_grad), lb, ub, restarts, maxeval, rng,
+                                   opts)
+
+
+def _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, opts=None):
+    """The Latin-hypercube candidate route of a score over several models: score(xs, want_grad) -> a result with scores, grad [d, R],
+    best_val, best_idx (see _acquire_max_constrained)."""
     opts = opts or {}
     refine = int(opts.get("refine", 0) or 0)
-    acq, p = a.acq_id, a.params()
     maxf, maxx = -math.inf, lb.copy()
     seen_x, seen_f = [], []
     for _ in range(restarts):
         xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
-        res = model.score(acq, p, xs)
+        res = score(xs)
         if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
             maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
         if refine > 0:
@@ -755,7 +794,7 @@ def _acquire_max_constrained(a, model, lb, ub, restarts, maxeval, rng, opts=None
                     break
 
         def fg(Z):
-            r = model.score(acq, p, Z, want_grad=True)
+            r = score(Z, want_grad=True)
             return np.asarray(r.scores, dtype=np.float64), np.asarray(r.grad, dtype=np.float64)
 
         fa, Xa = _batched_lbfgs_ascent(fg, np.asfortranarray(np.stack(starts, axis=1)), lb, ub, max(2, maxeval),
@@ -797,6 +836,9 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         if not hasattr(model, "feasible_incumbent"):
             raise ValueError(f"Constrained needs a ConstrainedGPE, not {type(model).__name__}")
         return _acquire_max_constrained(a, model, lb, ub, restarts, maxeval, rng, opts)
+    if isinstance(a, ExpectedHypervolumeImprovement):             # (`method` is accepted, not used; "refine" adds the ascent)
+        _need_mo(model)
+        return _acquire_max_mo(model, lb, ub, restarts, maxeval, rng, opts)
     if isinstance(a, Marginalised):                               # (`method` is accepted, not used; "refine" adds the ascent)
         return _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts)
     derivative = len(method) > 1 and method[1] == "D" and not isinstance(a, ThompsonSamplingSimple)   # :31

@@ -9,10 +9,10 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, Constrained, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
+from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
-from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, update_
+from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
 
 
@@ -183,7 +183,8 @@ def optimizemodel_(o, model):                                 # :42-47 and NoMod
     if isinstance(o, NoModelOptimizer) or o is None:
         return None
     if o.i % o.every == 0:
-        for m in (model.members if isinstance(model, ConstrainedGPE) else [model]):   # every member of a constrained model
+        # every member of a constrained or two-objective model
+        for m in (model.members if isinstance(model, (ConstrainedGPE, MultiObjectiveGPE)) else [model]):
             if isinstance(o, MarginalGPOptimizer):
                 _marginal_fit(m, o.options)
             else:
@@ -354,6 +355,15 @@ class BOpt:
             raise ValueError("Marginalised acquisitions propose one point per iteration (batchsize = 1)")
         if batchsize == 1 and batchoptions:
             raise ValueError("batchoptions given with batchsize = 1")
+        multi = isinstance(model, MultiObjectiveGPE)
+        if multi != isinstance(acquisition, ExpectedHypervolumeImprovement):
+            raise ValueError("a MultiObjectiveGPE model goes with the ExpectedHypervolumeImprovement acquisition and the other way "
+                             f"round (got {type(model).__name__} with {type(acquisition).__name__})")
+        if multi and batchsize > 1:
+            raise ValueError("a MultiObjectiveGPE proposes one point per iteration (batchsize = 1)")
+        if multi and isinstance(modeloptimizer, MarginalGPOptimizer):
+            raise ValueError("MarginalGPOptimizer over a MultiObjectiveGPE is not supported: its samples have no two-objective "
+                             "acquisition")
         constrained = isinstance(model, ConstrainedGPE)
         if constrained != isinstance(acquisition, Constrained):
             raise ValueError("a ConstrainedGPE model goes with a Constrained(a) acquisition and the other way round "
@@ -367,7 +377,9 @@ class BOpt:
             raise ValueError("lowerbounds are not pointwise less than or eqal to upperbounds, they were possibly "
                              "passed in the wrong order")
         empty = model.y.size == 0
-        if constrained:                                                          # only feasible observations count
+        if multi:                                                                # (two objectives have a front, not an optimum)
+            current_optimum, current_optimizer = None, None
+        elif constrained:                                                        # only feasible observations count
             ok = np.zeros(0, dtype=bool) if empty else model.feasible_mask()
             yy = np.where(ok, model.y, -math.inf) if ok.any() else None
             current_optimum = -math.inf * int(sense) if yy is None else int(sense) * float(np.max(yy))
@@ -379,7 +391,7 @@ class BOpt:
         self.acquisition, self.acquisitionoptions, self.modeloptimizer = acquisition, acquisitionoptions, modeloptimizer
         self.lowerbounds, self.upperbounds = lowerbounds, upperbounds
         self.observed_optimum, self.observed_optimizer = current_optimum, current_optimizer
-        self.model_optimum, self.model_optimizer = current_optimum, current_optimizer.copy()
+        self.model_optimum, self.model_optimizer = current_optimum, None if multi else current_optimizer.copy()
         self.iterations = IterationCounter(0, 0, maxiterations)
         self.duration = DurationCounter(now, maxduration, now, now + maxduration)
         self.verbosity, self.initializer, self.repetitions = Verbosity(verbosity), initializer, repetitions
@@ -431,9 +443,20 @@ def _evaluate_constrained(o, x):
     return y, g
 
 
+def _evaluate_two(o, x):
+    """func(x) -> (y_1, y_2) for a MultiObjectiveGPE: sense flips both; there is no optimum to track."""
+    with _timeit(o, "function evaluation"):
+        out = np.atleast_1d(np.asarray(o.func(x), dtype=np.float64)).ravel()
+    if out.size != 2:
+        raise ValueError(f"func must return (y_1, y_2), the two objectives' values, got {out.size} numbers")
+    return int(o.sense) * out
+
+
 def _update_model(o, xs, ys):
     """One model update with the columns xs and what _evaluate_function returned for them."""
-    if isinstance(o.model, ConstrainedGPE):
+    if isinstance(o.model, MultiObjectiveGPE):
+        o.model.update_(np.stack(xs, axis=1), np.stack(ys, axis=1))
+    elif isinstance(o.model, ConstrainedGPE):
         o.model.update_(np.stack(xs, axis=1), np.array([y for y, _ in ys]), np.stack([g for _, g in ys], axis=1))
     else:
         update_(o.model, np.stack(xs, axis=1), np.array(ys))
@@ -442,6 +465,8 @@ def _update_model(o, xs, ys):
 def _evaluate_function(o, x):                                                   # :209-216
     if isinstance(o.model, ConstrainedGPE):
         return _evaluate_constrained(o, x)
+    if isinstance(o.model, MultiObjectiveGPE):
+        return _evaluate_two(o, x)
     with _timeit(o, "function evaluation"):
         y = int(o.sense) * o.func(x)
     if y > int(o.sense) * o.observed_optimum:
@@ -515,15 +540,32 @@ def boptimize_(o):
     with _timeit(o, "acquisition"):
         if isinstance(o.model, ConstrainedGPE):                                   # (no unconstrained model maximum: the feasible optimum stands)
             o.model_optimum, o.model_optimizer = int(o.sense) * o.observed_optimum, np.array(o.observed_optimizer)
-        elif o.model.nobs > 0:
+        elif o.model.nobs > 0 and not isinstance(o.model, MultiObjectiveGPE):     # (two objectives: no single optimum, the result carries the front)
             o.model_optimum, o.model_optimizer = acquire_max(MaxMean(), o.model, o.lowerbounds, o.upperbounds,
                                                              o.acquisitionoptions, o.rng)   # acquire_model_max :200
     o.duration.now = time.time()
     if o.verbosity >= Timings:
         for k, (n, t) in o.timeroutput.items():
             print(f"  {k:40s} calls {n:6d}  {t:10.4f} s")
+    if isinstance(o.model, MultiObjectiveGPE):
+        return _two_objective_result(o)
     return dict(observed_optimum=o.observed_optimum, observed_optimizer=o.observed_optimizer,
                 model_optimum=int(o.sense) * o.model_optimum, model_optimizer=o.model_optimizer)   # :203-206
+
+
+def _two_objective_result(o):
+    """The result of a two-objective run: the observed front as x [d, n_front] and y [2, n_front] in the caller's sense (ascending
+    in the model's first objective), the hypervolume it dominates above the model's reference point (`ref`, in the caller's sense
+    too), and None where a single-objective run reports an optimum."""
+    m = o.model
+    if m.nobs == 0:
+        front_x, front_y, hv, ref = np.zeros((m.dim, 0)), np.zeros((2, 0)), 0.0, None
+    else:
+        idx = m.front_indices()
+        front_x, front_y, hv = np.array(m.x[:, idx]), int(o.sense) * m.y[:, idx], m.hypervolume
+        ref = int(o.sense) * m.reference_point()
+    return dict(observed_optimum=None, observed_optimizer=None, model_optimum=None, model_optimizer=None,
+                observed_front=dict(x=front_x, y=front_y), hypervolume=hv, ref=ref)
 
 
 def merge_with_defaults(f, lowerbounds, upperbounds, optkwargs):                # :238-289

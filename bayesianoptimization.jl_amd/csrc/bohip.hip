@@ -24,6 +24,7 @@
 #include "../../include/bohip_ens.h"
 #include "../../include/bohip_ens_grad.h"
 #include "../../include/bohip_con.h"
+#include "../../include/bohip_mo.h"
 #include "kernels_linalg.hip"
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
@@ -35,6 +36,7 @@
 #include "kernels_mes.hip"     // (after the scoring and sampling kernels: their generator and arg-max order; acq_log.h's continued fraction)
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_con.hip"     // (after the scoring kernels: their functors, arg-max order and k_grad_finish's launch bounds; acq_log.h's continued fraction)
+#include "kernels_mo.hip"      // (after the constrained kernels: their record block; the scoring kernels' arg-max order)
 #include "kernels_ascent.hip"
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
@@ -219,6 +221,9 @@ struct bohip_gp {
     char* con_ws = nullptr;
     size_t con_bytes = 0;
     hipEvent_t ev_con = nullptr;
+    // two-objective scoring (bohip_gp_score_mo / bohip_mo_ehvi_values): the front's corners and heights, 2 BOHIP_MO_FRONT_MAX + 3
+    // doubles made on first use; everything else lives in ensure_con's block with C = 1
+    double* mo_front = nullptr;
     int64_t dmll_cap = 0;
     int64_t thompson_cap = 0;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
@@ -2387,6 +2392,7 @@ void bohip_gp_destroy(bohip_gp* g) {
     if (g->mes_ws) hipFree(g->mes_ws);
     if (g->con_ws) hipFree(g->con_ws);
     if (g->ev_con) hipEventDestroy(g->ev_con);
+    if (g->mo_front) hipFree(g->mo_front);
     if (g->dinfo) hipFree(g->dinfo);
     for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
@@ -3951,6 +3957,171 @@ int bohip_gp_score_con(bohip_gp* obj, int acq_id, const double* acq_params, int6
     t_collect(obj);
     for (int64_t c = 0; c < C; ++c)
         if (cons[c] != obj) t_collect(cons[c]);
+    return 0;
+}
+
+// ---- two-objective optimisation (kernels_mo.hip, include/bohip_mo.h) ----------------------------------------------
+static_assert(MO_FRONT_MAX == BOHIP_MO_FRONT_MAX && MO_G == BOHIP_MO_GROUP, "the kernel's plan and the header agree");
+
+// host only: the observations that strictly dominate ref and are not weakly dominated by another, ascending in f1; no device call
+int bohip_mo_front(const double* Y, int64_t n, const double* ref, double* front, int64_t cap, int64_t* n_front, double* hv) {
+    if (n < 0 || cap < 0 || !ref || (n > 0 && !Y) || (cap > 0 && !front)) return fail(BOHIP_E_ARG, "mo_front: bad arguments");
+    if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) return fail(BOHIP_E_ARG, "mo_front: the reference point is not finite");
+    std::vector<std::pair<double, double>> pts;
+    for (int64_t i = 0; i < n; ++i) {
+        const double a = Y[i], b = Y[n + i];
+        if (!std::isfinite(a) || !std::isfinite(b)) return fail(BOHIP_E_ARG, "mo_front: observation " + std::to_string(i) + " is not finite");
+        if (a > ref[0] && b > ref[1]) pts.emplace_back(a, b);
+    }
+    // descending in f1, ties descending in f2: a point stays if its f2 exceeds every f2 seen so far (of equal points the first)
+    std::sort(pts.begin(), pts.end(), [](const std::pair<double, double>& p, const std::pair<double, double>& q) {
+        return p.first > q.first || (p.first == q.first && p.second > q.second);
+    });
+    std::vector<std::pair<double, double>> keep;
+    double top = -INFINITY;
+    for (const auto& p : pts)
+        if (p.second > top) { keep.push_back(p); top = p.second; }
+    std::reverse(keep.begin(), keep.end());
+    const int64_t m = (int64_t)keep.size();
+    if (n_front) *n_front = m;
+    if (hv) {
+        double a = 0.0, prev = ref[0];
+        for (const auto& p : keep) { a += (p.first - prev) * (p.second - ref[1]); prev = p.first; }
+        *hv = a;
+    }
+    if (cap == 0) return 0;
+    if (cap < m) return fail(BOHIP_E_ARG, "mo_front: the front has " + std::to_string(m) + " points, cap is " + std::to_string(cap));
+    for (int64_t i = 0; i < m; ++i) { front[i] = keep[i].first; front[cap + i] = keep[i].second; }
+    return 0;
+}
+
+// validates the front and lays out what k_ehvi reads: c[0 .. n + 1] then b[0 .. n]
+static int mo_make_front(const char* who, const double* front, int64_t n, const double* ref, std::vector<double>* out) {
+    const std::string pre = std::string(who) + ": ";
+    if (n < 0 || !ref || (n > 0 && !front)) return fail(BOHIP_E_ARG, pre + "bad front arguments");
+    if (n > BOHIP_MO_FRONT_MAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "a front of " + std::to_string(n) + " points; at most " + std::to_string(BOHIP_MO_FRONT_MAX));
+    if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) return fail(BOHIP_E_ARG, pre + "the reference point is not finite");
+    for (int64_t i = 0; i < n; ++i) {
+        const double a = front[i], b = front[n + i];
+        if (!std::isfinite(a) || !std::isfinite(b)) return fail(BOHIP_E_ARG, pre + "front point " + std::to_string(i) + " is not finite");
+        if (!(a > ref[0]) || !(b > ref[1])) return fail(BOHIP_E_ARG, pre + "front point " + std::to_string(i) + " is not strictly above ref");
+        if (i > 0 && (!(a > front[i - 1]) || !(b < front[n + i - 1])))
+            return fail(BOHIP_E_ARG, pre + "the front must ascend strictly in f1 and descend strictly in f2 (point " + std::to_string(i) + ")");
+    }
+    out->resize((size_t)(2 * n + 3));
+    double* c = out->data();
+    double* b = c + n + 2;
+    c[0] = ref[0];
+    for (int64_t i = 0; i < n; ++i) { c[i + 1] = front[i]; b[i] = front[n + i]; }
+    c[n + 1] = INFINITY;
+    b[n] = ref[1];
+    return 0;
+}
+static int mo_upload_front(bohip_gp* g, const std::vector<double>& fr) {
+    if (!g->mo_front) HIPCHK(hipMalloc(&g->mo_front, (size_t)(2 * BOHIP_MO_FRONT_MAX + 3) * 8));
+    HIPCHK(hipMemcpyAsync(g->mo_front, fr.data(), fr.size() * 8, hipMemcpyHostToDevice, g->stream));
+    return 0;
+}
+// the EHVI and the record on g's stream (no synchronisation, no copies); b is ensure_con's block with C = 1
+static int mo_ehvi_stage(bohip_gp* g, int64_t n_front, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
+    const int nb = (int)std::min<int64_t>(MO_GRID_MAX, (R + MO_CAND - 1) / MO_CAND);
+    t_begin(g, "mo_ehvi");
+    if (partials || jac)
+        hipLaunchKernelGGL(k_ehvi<true>, dim3(nb), dim3(256), 0, g->stream, (const double*)g->mo_front, (int)n_front, (const double*)b.mu,
+                           (const double*)b.var, R, R, b.value, b.pmu, b.pvar, (const double*)b.jmu, (const double*)b.jvar,
+                           (int64_t)R * g->d, g->d, jac ? b.grad : (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
+    else
+        hipLaunchKernelGGL(k_ehvi<false>, dim3(nb), dim3(256), 0, g->stream, (const double*)g->mo_front, (int)n_front, (const double*)b.mu,
+                           (const double*)b.var, R, R, b.value, (double*)nullptr, (double*)nullptr, (const double*)nullptr,
+                           (const double*)nullptr, (int64_t)0, g->d, (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
+    if (want_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, b.blocks, nb, b.best, 0ll);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_mo_ehvi_values(bohip_gp* g, const double* front, int64_t n_front, const double* ref, const double* mu, const double* var,
+                         int64_t R, double* value, double* dmu, double* dvar, bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "mo_ehvi_values: null handle");
+    std::vector<double> fr;
+    CHK(mo_make_front("mo_ehvi_values", front, n_front, ref, &fr));
+    if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "mo_ehvi_values: bad arguments");
+    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "mo_ehvi_values: dmu and dvar are given together or not at all");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    ConBufs b{};
+    CHK(ensure_con(g, 1, R, false, &b));
+    CHK(mo_upload_front(g, fr));
+    const size_t m = (size_t)2 * R * 8;
+    HIPCHK(hipMemcpyAsync(b.mu, mu, m, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(b.var, var, m, hipMemcpyHostToDevice, g->stream));
+    CHK(mo_ehvi_stage(g, n_front, b, R, dmu != nullptr, false, best != nullptr));
+    HIPCHK(hipMemcpyAsync(value, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (dmu) {
+        HIPCHK(hipMemcpyAsync(dmu, b.pmu, m, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(dvar, b.pvar, m, hipMemcpyDeviceToHost, g->stream));
+    }
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_score_mo(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64_t n_front, const double* ref, const double* Xs,
+                      int64_t R, double* score, double* grad, double* mu, double* var, bohip_best* best) {
+    if (!obj0 || !obj1) return fail(BOHIP_E_ARG, "score_mo: null handle");
+    if (obj1->d != obj0->d) return fail(BOHIP_E_ARG, "score_mo: the objectives differ in dimension");
+    if (obj1->device != obj0->device) return fail(BOHIP_E_ARG, "score_mo: the objectives live on different devices");
+    std::vector<double> fr;
+    CHK(mo_make_front("score_mo", front, n_front, ref, &fr));
+    if (R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_mo: bad arguments");
+    if (obj0->n == 0 || obj1->n == 0) return fail(BOHIP_E_STATE, "score_mo: an objective has no observations");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(obj0->device));
+    const bool jac = grad != nullptr, two = obj1 != obj0;
+    const int d = obj0->d;
+    t_reset(obj0);
+    CHK(ensure_xs(obj0, R));
+    ConBufs b{};
+    CHK(ensure_con(obj0, 1, R, jac, &b));
+    HIPCHK(hipMemcpyAsync(obj0->dXs, Xs, (size_t)R * d * 8, hipMemcpyHostToDevice, obj0->stream));
+    auto event_of = [](bohip_gp* m) -> hipError_t {
+        return m->ev_con ? hipSuccess : hipEventCreateWithFlags(&m->ev_con, hipEventDisableTiming);
+    };
+    // the candidates are on the device once, in obj0's block: obj1's stream waits for that copy, runs its own posterior into obj0's
+    // block and is joined back before the EHVI -- no host wait in between (bohip_gp_score_con's scheme with one other model)
+    if (two) {
+        HIPCHK(event_of(obj0));
+        HIPCHK(hipEventRecord(obj0->ev_con, obj0->stream));
+        t_reset(obj1);
+        HIPCHK(hipStreamWaitEvent(obj1->stream, obj0->ev_con, 0));
+    }
+    CHK(mo_upload_front(obj0, fr));
+    CHK(posterior_grad_core(obj0, obj0->dXs, R, b.mu, b.var, b.jmu, b.jvar));
+    const size_t o = (size_t)R;
+    CHK(posterior_grad_core(obj1, obj0->dXs, R, b.mu + o, b.var + o, jac ? b.jmu + o * d : nullptr, jac ? b.jvar + o * d : nullptr));
+    if (two) {
+        HIPCHK(event_of(obj1));
+        HIPCHK(hipEventRecord(obj1->ev_con, obj1->stream));
+        HIPCHK(hipStreamWaitEvent(obj0->stream, obj1->ev_con, 0));
+    }
+    CHK(mo_ehvi_stage(obj0, n_front, b, R, false, jac, best != nullptr));
+    if (score) HIPCHK(hipMemcpyAsync(score, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, obj0->stream));
+    if (grad) HIPCHK(hipMemcpyAsync(grad, b.grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, obj0->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, b.mu, 2 * o * 8, hipMemcpyDeviceToHost, obj0->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, b.var, 2 * o * 8, hipMemcpyDeviceToHost, obj0->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, obj0->stream));
+    HIPCHK(hipStreamSynchronize(obj0->stream));
+    t_collect(obj0);
+    if (two) t_collect(obj1);
     return 0;
 }
 

@@ -999,6 +999,171 @@ class ConstrainedGPE:
             m.close()
 
 
+# ---- two-objective optimisation (include/bohip_mo.h) -----------------------------------------------------------
+class MOScore:
+    """Result of MultiObjectiveGPE.score: scores[R] (the exact EHVI), grad[d, R] or None, mu and var [2, R] (row m objective m),
+    best_value / best_index (first maximum, NaN never wins, -Inf / -1)."""
+    __slots__ = ("scores", "grad", "mu", "var", "best_value", "best_index")
+
+    def __init__(self, scores, grad, mu, var, best_value, best_index):
+        self.scores, self.grad, self.mu, self.var = scores, grad, mu, var
+        self.best_value, self.best_index = best_value, best_index
+
+    best_val = property(lambda self: self.best_value)      # (the names the candidate route of acquire_max reads)
+    best_idx = property(lambda self: self.best_index)
+
+    def __iter__(self):
+        return iter((self.scores, self.grad, self.mu, self.var, self.best_value, self.best_index))
+
+
+def _ref2(ref):
+    ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+    if ref.size != 2:
+        raise ValueError(f"the reference point has two coordinates, got {ref.size}")
+    return ref
+
+
+def mo_front(Y, ref):
+    """bohip_mo_front (host code: no device is needed): the observations Y [2, n] (both objectives MAXIMISED) that strictly dominate
+    `ref` and are not weakly dominated by another observation, ascending in f1 and descending in f2, of equal points one.
+    -> (front[2, n_front], hv), hv the hypervolume the front dominates above ref."""
+    Y = np.ascontiguousarray(np.asarray(Y, dtype=np.float64).reshape(2, -1))
+    ref = _ref2(ref)
+    n = Y.shape[1]
+    out = np.empty((2, max(n, 1)))
+    nf, hv = C.c_int64(0), C.c_double(0.0)
+    check(_lib.load().bohip_mo_front(_ptr(Y), n, _ptr(ref), _ptr(out), out.shape[1], C.byref(nf), C.byref(hv)))
+    return np.ascontiguousarray(out[:, :nf.value]), hv.value
+
+
+def ehvi_values(model, front, ref, mu, var, want_grad=False):
+    """bohip_mo_ehvi_values: the exact expected hypervolume improvement over `front` [2, n_front] (as mo_front returns it) above `ref`
+    on the moments mu, var [2, R] of two independent posteriors.  `model` gives the device only.
+    -> (value[R], dmu, dvar, best_value, best_index); dmu and dvar [2, R] are the partials in the moments, None without want_grad."""
+    front = np.ascontiguousarray(np.asarray(front, dtype=np.float64).reshape(2, -1))
+    ref = _ref2(ref)
+    mu = np.ascontiguousarray(np.atleast_2d(np.asarray(mu, dtype=np.float64)))
+    var = np.ascontiguousarray(np.atleast_2d(np.asarray(var, dtype=np.float64)))
+    if mu.shape != var.shape or mu.shape[0] != 2:
+        raise ValueError(f"mu and var must both be 2 x R, got {mu.shape} and {var.shape}")
+    R = mu.shape[1]
+    value = np.empty(max(R, 1))
+    dmu, dvar = (np.empty((2, max(R, 1))), np.empty((2, max(R, 1)))) if want_grad else (None, None)
+    best = Best()
+    check(model._lib.bohip_mo_ehvi_values(model._h, _ptr(front), front.shape[1], _ptr(ref), _ptr(mu), _ptr(var), R, _ptr(value),
+                                          _ptr(dmu) if want_grad else None, _ptr(dvar) if want_grad else None, C.byref(best)))
+    return value[:R], (dmu[:, :R] if want_grad else None), (dvar[:, :R] if want_grad else None), best.val, best.idx
+
+
+def score_mo(m0, m1, front, ref, xs, want_grad=False, want_moments=True):
+    """ONE bohip_gp_score_mo call on two ElasticGPE models (they may be the same model, and may hold different observations): the
+    exact EHVI of their posteriors at the columns of xs [d, R] over `front` [2, n_front] above `ref`.  -> MOScore."""
+    front = np.ascontiguousarray(np.asarray(front, dtype=np.float64).reshape(2, -1))
+    ref = _ref2(ref)
+    xs = _cols(xs, m0.dim)
+    R = xs.shape[1]
+    n = max(R, 1)
+    scores = np.empty(n)
+    grad = np.empty((m0.dim, n), order="F") if want_grad else None
+    mu, var = (np.empty((2, n)), np.empty((2, n))) if want_moments and R > 0 else (None, None)
+    best = Best()
+    check(m0._lib.bohip_gp_score_mo(m0._h, m1._h, _ptr(front), front.shape[1], _ptr(ref), _ptr(xs), R, _ptr(scores),
+                                    _ptr(grad) if want_grad else None, _ptr(mu) if mu is not None else None,
+                                    _ptr(var) if var is not None else None, C.byref(best)))
+    return MOScore(scores[:R], grad[:, :R] if want_grad else None, mu, var, best.val, best.idx)
+
+
+class MultiObjectiveGPE:
+    """Two objective models scored together by the exact expected hypervolume improvement (include/bohip_mo.h; an
+    extension: the reference optimises one objective).  Both objectives are MAXIMISED (BOpt's `sense` flips both).  The members are
+    ElasticGPE models of one dimension on one device, each with its own kernel, hyper-parameters and observations.  `ref` is the
+    reference point in the model's (maximised) sense; None fixes it ONCE, at the first score, per objective at
+    min y - 0.1 (max y - min y) (min y - 1 if that range is 0) of the observations held then, and keeps it in `ref`.
+    `x`, `nobs` are the first member's; `y` is [2, n]."""
+
+    def __init__(self, objectives, ref=None):
+        objectives = tuple(objectives)
+        if len(objectives) != 2:
+            raise ValueError(f"MultiObjectiveGPE takes two objectives, got {len(objectives)}")
+        for m in objectives:
+            if type(m).__name__ == "MultiGPE":
+                raise ValueError("MultiObjectiveGPE members are single-device models: MultiGPE is not supported")
+        if objectives[0].dim != objectives[1].dim:
+            raise ValueError("the members differ in dimension")
+        self.objectives = objectives
+        self.ref = None if ref is None else _ref2(ref).copy()
+        if self.ref is not None and not np.all(np.isfinite(self.ref)):
+            raise ValueError("the reference point must be finite")
+
+    members = property(lambda self: list(self.objectives))
+    dim = property(lambda self: self.objectives[0].dim)
+    x = property(lambda self: self.objectives[0].x)
+    nobs = property(lambda self: self.objectives[0].nobs)
+
+    def __repr__(self):
+        return f"MultiObjectiveGPE({self.objectives[0]!r}, {self.objectives[1]!r}, ref={self.ref})"
+
+    @property
+    def y(self):
+        """The observations [2, n]; the members' observations must be aligned (update_ keeps them so)."""
+        a, b = self.objectives
+        if a.nobs != b.nobs:
+            raise ValueError("the members' observations are not aligned: a front needs both values of every observation")
+        return np.stack([np.asarray(a.y, dtype=np.float64), np.asarray(b.y, dtype=np.float64)])
+
+    def default_ref(self):
+        """The default rule on the observations held now (not stored)."""
+        Y = self.y
+        if Y.shape[1] == 0:
+            raise ValueError("the default reference point needs observations")
+        lo, hi = Y.min(axis=1), Y.max(axis=1)
+        return np.where(hi - lo > 0.0, lo - 0.1 * (hi - lo), lo - 1.0)
+
+    def reference_point(self, fix=False):
+        """`ref`, or the default rule's point where none is fixed yet; fix=True stores it (what the first score does)."""
+        if self.ref is not None:
+            return self.ref
+        r = self.default_ref()
+        if fix:
+            self.ref = r
+        return r
+
+    def _front_hv(self):
+        return mo_front(self.y, self.reference_point())
+
+    front = property(lambda self: self._front_hv()[0])
+    hypervolume = property(lambda self: self._front_hv()[1])
+
+    def front_indices(self):
+        """The column of the first observation that equals each front point."""
+        Y, F = self.y, self.front
+        return np.array([int(np.flatnonzero((Y[0] == F[0, i]) & (Y[1] == F[1, i]))[0]) for i in range(F.shape[1])], dtype=np.int64)
+
+    def update_(self, x, y):
+        """Append observations to both members: x [d, n], y [2, n] (or [2] for one point)."""
+        y = np.asarray(y, dtype=np.float64)
+        if y.shape[0] != 2:
+            raise ValueError(f"y has one row per objective, 2 x n; got shape {y.shape}")
+        y = y.reshape(2, -1)
+        for m, row in zip(self.objectives, y):
+            m.append_(x, row)
+        return self
+
+    append_ = update_
+    append = update_
+
+    def score(self, xs, want_grad=False, want_moments=True):
+        """ONE bohip_gp_score_mo call: both members' posteriors on their own streams, the EHVI over the observed front and the
+        arg-max on the device.  xs is d x R.  -> MOScore."""
+        ref = self.reference_point(fix=True)
+        front, _ = mo_front(self.y, ref)
+        return score_mo(self.objectives[0], self.objectives[1], front, ref, xs, want_grad, want_moments)
+
+    def close(self):
+        for m in self.objectives:
+            m.close()
+
+
 class PosteriorPaths:
     """S sample paths of one model's posterior on the device (bohip_paths, include/bohip_paths.h).  Self-contained: it holds its own copy
     of the observations, hyper-parameters, frequencies and coefficients.
