@@ -42,6 +42,7 @@
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
 #include "direct_l.h"          // host bookkeeping of :GN_DIRECT_L (ask / tell)
+#include "scratch_layout.h"    // devbuf.h (who owns device memory) and the layouts of the carved scratch blocks
 
 #include <algorithm>
 #include <atomic>
@@ -60,6 +61,11 @@
 #include <vector>
 
 using namespace bohip;
+using devbuf::Grow;
+template <class T>
+using DBuf = devbuf::Buf<T>;         // device memory
+template <class T>
+using HBuf = devbuf::PinnedBuf<T>;   // pinned host memory
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -86,152 +92,158 @@ static constexpr int APP_ROWS = 2 * SMALL_MAX;
 static_assert(APPEND_PMAX <= SMALL_MAX && SMALL_R <= SMALL_MAX, "the append shares the small-batch row area");
 
 static constexpr int CHOL_DF_TCAP = 96;   // the dataflow factorisation's flag storage is sized for this many row tiles
-struct bohip_gp {
-    int device = 0, d = 0, kern = 0;
-    int64_t n = 0, cap = 0, ld = 0;
-    double *dX = nullptr, *dy = nullptr, *dL = nullptr, *dW = nullptr, *dWT = nullptr, *dS = nullptr;
-    double *dalpha = nullptr, *dr = nullptr, *dt = nullptr, *dmll = nullptr;
-    double* dApp = nullptr;  // [APP_ROWS][ld] scratch of the incremental append and of the row-wise (small-batch) posterior
-    int* dinfo = nullptr;
-    unsigned* dchol_flags = nullptr;   // dataflow factorisation (kernels_chol.hip): panel[T*8] | solved[T] | crit[T] | abort[1]
-    double* dchol_idl = nullptr;       // [T*8][16][16] published inverses of the 16 x 16 pivot blocks
-    std::vector<double> hX, hy;
-    double loglen[DMAX], logsig = 0.0, lognoise = -2.0, beta = 0.0;
-    bool stale = true;
-    int64_t n_factored = 0;  // observations covered by the current factor
+// The handle's streams and events, as a base of the handle: a base is destroyed after the members, so every buffer of bohip_gp
+// frees itself (hipFree waits for the device) before the streams and events go -- the order bohip_gp_destroy always kept.
+struct gp_streams {
+    int device = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
     hipStream_t side_stream = nullptr;            // bulk trailing updates of the factorisation run here (look-ahead)
     hipEvent_t ev_panels = nullptr, ev_bulk = nullptr;
     hipStream_t col_stream = nullptr;             // dataflow factorisation: bulk followers + column updates (high priority)
     hipEvent_t ev_inv = nullptr;
     hipEvent_t ev_gate = nullptr;                 // a diagonal-block kernel is about to start: release one piece of the pending bulk update
-    ExTask* dex_tasks = nullptr;                  // task records of the executor form (kernels_exec.hip), built once per (buffers, T)
-    size_t ex_cap = 0;
+    hipEvent_t ev_con = nullptr;                  // joins this handle's stream to the objective's (constrained scoring; made on first use)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> tpool;  // pooled event pairs of the stage timing
+    gp_streams() = default;
+    gp_streams(const gp_streams&) = delete;
+    ~gp_streams() {
+        if (ev_con) hipEventDestroy(ev_con);
+        for (auto& e : tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+        if (side_stream) { hipStreamSynchronize(side_stream); hipStreamDestroy(side_stream); }
+        if (ev_panels) hipEventDestroy(ev_panels);
+        if (ev_bulk) hipEventDestroy(ev_bulk);
+        if (col_stream) { hipStreamSynchronize(col_stream); hipStreamDestroy(col_stream); }
+        if (ev_inv) hipEventDestroy(ev_inv);
+        if (ev_gate) hipEventDestroy(ev_gate);
+        if (own_stream) hipStreamDestroy(own_stream);
+    }
+};
+extern "C" int bohip_gp_comm_destroy(bohip_gp* g);
+struct bohip_gp : gp_streams {
+    // The whole teardown (bohip_gp_destroy, and every failure path of bohip_gp_create): wait for the handle's stream, detach the
+    // communicator; then the members free themselves, then ~gp_streams.
+    ~bohip_gp() {
+        hipSetDevice(device);
+        if (own_stream) hipStreamSynchronize(own_stream);
+        if (comm) bohip_gp_comm_destroy(this);
+    }
+    int d = 0, kern = 0;
+    int64_t n = 0, cap = 0, ld = 0;
+    // Every buffer below owns its memory and knows its capacity (devbuf.h); the plain integers next to some of them are NOT
+    // capacities but what the last call derived from one (a row count, a leading dimension, the T a table was built for).
+    DBuf<double> dX, dy, dL, dW, dWT, dS;
+    DBuf<double> dalpha, dr, dt, dmll;
+    DBuf<double> dApp;  // [APP_ROWS][ld] scratch of the incremental append and of the row-wise (small-batch) posterior
+    DBuf<int> dinfo;
+    DBuf<unsigned> dchol_flags;        // dataflow factorisation (kernels_chol.hip): panel[T*8] | solved[T] | crit[T] | abort[1]
+    DBuf<double> dchol_idl;            // [T*8][16][16] published inverses of the 16 x 16 pivot blocks
+    std::vector<double> hX, hy;
+    double loglen[DMAX], logsig = 0.0, lognoise = -2.0, beta = 0.0;
+    bool stale = true;
+    int64_t n_factored = 0;  // observations covered by the current factor
+    DBuf<ExTask> dex_tasks;                       // task records of the executor form (kernels_exec.hip), built once per (buffers, T)
     bool ex_bulk4_ok = false;   // the bulk queue may be claimed two tiles at a time (exec_bulk_stride_ok)
     int ex_T = 0, ex_nsf = 0, ex_inv_g = -1, ex_grp_min = -1, ex_qbeg[EX_NQ + 1] = {0};
     bool w_done = false;       // the last factorisation also produced W = L^-1 (executor form with its inverse queue)
     // scoring scratch
-    double* dKsT = nullptr;
-    unsigned long long* dclk = nullptr;   // [2] core-clock / wall-clock ticks of sampled k_trigemm_sq workgroups (timing runs)
-    int* dpieces = nullptr;      // k_trigemm_sq's row pieces, heaviest first (trigemm_pieces)
+    DBuf<double> dKsT;
+    DBuf<unsigned long long> dclk;        // [2] core-clock / wall-clock ticks of sampled k_trigemm_sq workgroups (timing runs)
+    DBuf<int> dpieces;           // k_trigemm_sq's row pieces, heaviest first (trigemm_pieces)
     std::vector<int> hpieces;
     int n_pieces = 0, pieces_T = -1;
-    int64_t pieces_cap = 0;
     int64_t pieces_alpha = -1;
     int64_t kst_rows = 0;        // rows the K*' chunk buffer holds
     int64_t chunk_now = 0;       // candidates per K*' chunk of the current call (chunk_rows(R) <= kst_rows)
     int64_t score_launches = 0;  // k_trigemm_sq launches of the last posterior pass (BOHIP_INFO_SCORE_LAUNCHES)
-    double *dVT = nullptr, *dUT = nullptr;  // gradient path: V' and U' = V' W chunks, candidate-major
-    int64_t vt_rows = 0;
-    double *dq = nullptr, *dmu_raw = nullptr, *dXs = nullptr, *dmu = nullptr, *dvar = nullptr, *dscore = nullptr;
-    int64_t q_cap = 0, r_cap = 0, xs_cap = 0;
-    Best *dblock_best = nullptr, *dbest = nullptr;
-    int64_t bb_cap = 0;
-    unsigned* dfz_cnt = nullptr;   // fused finish of k_trigemm_sq: [tiles] arrivals per candidate tile + [1] finished tiles (kept at zero)
-    Best* dfz_best = nullptr;      // [tiles] per-tile arg-max records
-    int64_t fz_cap = 0;
+    DBuf<double> dVT, dUT;  // gradient path: V' and U' = V' W chunks, candidate-major
+    DBuf<double> dq, dmu_raw, dXs, dmu, dvar, dscore;
+    DBuf<Best> dblock_best, dbest;
+    DBuf<unsigned> dfz_cnt;        // fused finish of k_trigemm_sq: [tiles] arrivals per candidate tile + [1] finished tiles (kept at zero)
+    DBuf<Best> dfz_best;           // [tiles] per-tile arg-max records
+    int64_t fz_tiles = 0;          // the [tiles] of the two above: where the finished-tiles word sits
     bool fz_dirty = false;         // a fused call failed between its launches: clear the counters before the next one
     // pruned arg-max (pruned_pass): ONE allocation [packed K*' rows | q2 | mu2 | bounds | lists, marks | counters, record | k_kstar's partials | pieces]
-    char* dpr = nullptr;
-    size_t pr_bytes = 0;
+    DBuf<char> dpr;
     std::vector<int> hpr_pieces;
     int* pr_pieces_at = nullptr;
-    unsigned* hprune_stat = nullptr;   // pinned: round 2's list length of the last pruned call (prune_wanted)
+    HBuf<unsigned> hprune_stat;        // pinned: round 2's list length of the last pruned call (prune_wanted)
     unsigned prune_seen = 0;           // the last figure prune_wanted read from it
     bool prune_retry = false;          // the next pruned call is the retry after a back-off (prune_wanted cleared the word)
-    size_t pr_ks_bytes = 0;            // the packed K*' rows at the head of dpr, as the last pruned call laid them out (tests: the poison)
+    size_t pr_ks_len = 0;              // the packed K*' rows at the head of dpr, as the last pruned call laid them out (tests: the poison)
     int prune_r2_form = -1;            // tests (bohip_debug_prune_round2_form): -1 the rule, 0 the steady form, 1 the long form
     int prune_skip = 0;                // value-only calls left on the full pass before pruning is tried again
     // batch selection (bohip_gp_select_batch): V' of ALL candidates, and ONE block [u_i q x ldu | records | scalars | workgroup records | picked]
-    double* dBV = nullptr;
-    int64_t bv_rows = 0, bv_ld = 0;
-    char* dbatch = nullptr;
-    size_t batch_bytes = 0;
-    double* dgrad = nullptr;   // d x R gradient staging of the host-pointer entry point
+    DBuf<double> dBV;
+    DBuf<char> dbatch;
+    DBuf<double> dgrad;        // d x R gradient staging of the host-pointer entry point
     double asc_ftol_abs = 0.0, asc_xtol_rel = 0.0, asc_stopval = INFINITY;   // bohip_gp_set_ascent_stop (NLopt's ftol_abs / xtol_rel / stopval)
     double asc_maxtime = 0.0;    // bohip_gp_set_maxtime: wall-clock budget of one acquire_max call in seconds (NLopt maxtime), 0 = none
     int64_t batch_hint = 0;      // bohip_gp_set_batch_hint: choose the scoring path as if the batch had at least this many candidates
-    double* dsplit = nullptr;    // split-K partial planes (batches of a few hundred candidates)
-    int64_t split_cap = 0;
+    DBuf<double> dsplit;         // split-K partial planes (batches of a few hundred candidates)
     const SmallFold* asc_fold = nullptr;   // set around a pass of the free-running ascent: the step this pass's gradient kernel may run in its last workgroup
     bool asc_fold_done = false;            // ... and whether it took it (small_pass_mfma: one pass of <= 16 candidates, d <= 16); else k_asc_step follows
     const unsigned* asc_go = nullptr;   // set around the passes of the free-running ascent: the pass's big kernels return at once when the word is 0
-    double* dgparts = nullptr;   // [SMALL_MAX][16][2 DMAX] split partial sums of k_grad_finish (small batches)
-    unsigned* dgcount = nullptr; // per-candidate arrival counters (left at zero by the kernel)
+    DBuf<double> dgparts;        // [SMALL_MAX][16][2 DMAX] split partial sums of k_grad_finish (small batches)
+    DBuf<unsigned> dgcount;      // per-candidate arrival counters (left at zero by the kernel)
     // round 5: the small-batch pass as two MFMA kernels (kernels_small.hip): one scratch block [part | v16 | qpart | mupart | post | fstash | gpart]
-    double* dsm = nullptr;
-    size_t sm_bytes = 0;
-    unsigned* dsm_cnt = nullptr;
-    int sm_cnt_T = 0;
+    DBuf<char> dsm;
+    DBuf<unsigned> dsm_cnt;
+    int sm_cnt_T = 0;   // row tiles the counters are laid out for
     // pinned, device-visible host block the kernels of a small batch (R <= SMALL_R) write their results into: the
     // 2-3 device-to-host copies of a call cost more than its kernels (each ~8 us of API + DMA set-up)
-    double* hpin = nullptr;      // [score 32 | mu 32 | var 32 | best 2 | grad 32 DMAX | candidates of a small host call 32 DMAX]
-    double* dschur = nullptr;    // [APPEND_PMAX][APPEND_PMAX] Schur complement of an append of >= 3 rows (k_schur_dots)
+    HBuf<double> hpin;           // [score 32 | mu 32 | var 32 | best 2 | grad 32 DMAX | candidates of a small host call 32 DMAX]
+    DBuf<double> dschur;         // [APPEND_PMAX][APPEND_PMAX] Schur complement of an append of >= 3 rows (k_schur_dots)
     // lock-step L-BFGS ascent of acquire_max (kernels_ascent.hip)
     AscentState asc{};
-    double* asc_block = nullptr;   // one allocation behind all double arrays of asc
-    int* asc_ints = nullptr;       // active, accepted
-    double* asc_hio = nullptr;     // pinned staging of the one-launch ascent: [lb | ub | starts] in, the packed result out
-    double* asc_dio = nullptr;     // its device mirror
-    size_t asc_io_cap = 0;
-    int* asc_hints = nullptr;      // pinned: h_accepted, h_active
-    double* asc_bounds = nullptr;  // lb, ub, best_x (3 d doubles) + starts staging is dXs
-    Best* asc_best = nullptr;
-    int64_t asc_cap = 0;
-    int64_t grad_cap = 0;
-    Best* dthompson = nullptr; // S arg-max records
-    double* ddmll_parts = nullptr;  // per-block partial sums of the marginal-likelihood gradient
+    DBuf<char> asc_block;          // one allocation behind all double arrays of asc
+    DBuf<char> asc_ints;           // active, accepted
+    HBuf<double> asc_hio;          // pinned staging of the one-launch ascent: [lb | ub | starts] in, the packed result out
+    DBuf<double> asc_dio;          // its device mirror
+    HBuf<char> asc_hints;          // pinned: h_accepted, h_active
+    DBuf<double> asc_bounds;       // lb, ub, best_x (3 d doubles) + starts staging is dXs
+    DBuf<Best> asc_best;
+    int64_t asc_rows = 0;          // starts the pointers of asc are laid out for
+    DBuf<Best> dthompson;      // S arg-max records
+    DBuf<double> ddmll_parts;       // per-block partial sums of the marginal-likelihood gradient
     // batched marginal likelihood (bohip_gp_mll_grad_batch): the slabs of the settings of one launch, and [theta | mll | grad | pivot | stamps]
-    double* fit_ws = nullptr;
-    char* fit_io = nullptr;
-    size_t fit_ws_bytes = 0, fit_io_bytes = 0;
+    DBuf<double> fit_ws;
+    DBuf<char> fit_io;
     // marginalised acquisition (bohip_gp_score_ens): the settings' slabs are fit_ws; ONE block
     // [theta | w | w~ | pivot | xs chunk | each, mu, var H x Rc | scores R | workgroup records | record]
-    char* ens_io = nullptr;
-    size_t ens_io_bytes = 0;
+    DBuf<char> ens_io;
     // its gradient (bohip_gp_score_ens_grad): alpha = W' z per setting, and what the slabs hold -- the factors of ens_theta for the
     // observations of version ens_version, left by that symbol (ens_factor_ok) -- so that the next call with the same theta skips the factor stage
-    double* ens_alpha = nullptr;
-    size_t ens_alpha_bytes = 0;
+    DBuf<double> ens_alpha;
     bool ens_factor_ok = false;
     std::vector<double> ens_theta;
     std::vector<long long> ens_pivot;
     uint64_t ens_version = 0;
     uint64_t data_version = 0;   // raised by whatever changes X or y
-    double *dVV = nullptr, *dcov = nullptr;  // [Rp][Rp] V'V (lower tiles) and the full posterior covariance
-    int64_t cov_cap = 0;
+    DBuf<double> dVV, dcov;  // [Rp][Rp] V'V (lower tiles) and the full posterior covariance
+    int64_t cov_ld = 0;      // their leading dimension: the Rp they were made for
     // joint sampler (bohip_gp_sample_joint): a factor workspace the model does not own -- matrix, panel scratch, the 128 x 128
     // diagonal inverses -- plus [max diag | pivot word], the S x R draws (only when asked for) and the per-tile arg-max records
-    double *sjL = nullptr, *sjS = nullptr, *sjW = nullptr, *sjWT = nullptr, *sjF = nullptr, *sj_scal = nullptr;
-    int* sj_info = nullptr;
-    Best* sj_part = nullptr;
-    int64_t sj_cap = 0;           // rows (a multiple of 128) the workspace holds; its leading dimension is sj_cap + 16
-    size_t sjF_cap = 0, sj_part_cap = 0;
+    DBuf<double> sjL, sjS, sjW, sjWT, sjF, sj_scal;
+    DBuf<int> sj_info;
+    DBuf<Best> sj_part;
+    int64_t sj_rows = 0;          // rows (a multiple of 128) the workspace holds; its leading dimension is sj_rows + 16
     // greedy q-EI over the resident draws (bohip_gp_qei_batch / _qei_select): ONE block [m | partials | records | gain | idx | words]
-    char* qei_ws = nullptr;
-    size_t qei_bytes = 0;
+    DBuf<char> qei_ws;
     // knowledge gradient (bohip_gp_kg / bohip_kg_lines): ONE block [kg | record | nseg | a | B], the last two for the caller's lines only
-    char* kg_ws = nullptr;
-    size_t kg_bytes = 0;
+    DBuf<char> kg_ws;
     // max-value entropy search (bohip_gp_mes / bohip_mes_values / bohip_mes_gumbel): ONE block, see ensure_mes
-    char* mes_ws = nullptr;
-    size_t mes_bytes = 0;
+    DBuf<char> mes_ws;
     // constrained scoring (bohip_gp_score_con / bohip_con_values / bohip_gp_predict_grad): ONE block on the objective's handle, see
-    // ensure_con; ev_con joins this handle's stream to the objective's (made on first use)
-    char* con_ws = nullptr;
-    size_t con_bytes = 0;
-    hipEvent_t ev_con = nullptr;
+    // ensure_con (ev_con joins this handle's stream to the objective's)
+    DBuf<char> con_ws;
     // two-objective scoring (bohip_gp_score_mo / bohip_mo_ehvi_values): the front's corners and heights, 2 BOHIP_MO_FRONT_MAX + 3
     // doubles made on first use; everything else lives in ensure_con's block with C = 1
-    double* mo_front = nullptr;
-    int64_t dmll_cap = 0;
-    int64_t thompson_cap = 0;
+    DBuf<double> mo_front;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
     int64_t comm_exchanges = 0;        // BOHIP_INFO_COMM_EXCHANGES: all-gathers this handle has issued on its communicator
-    Best *csend = nullptr, *crecv = nullptr, *cfinal = nullptr;
-    int64_t crec_cap = 0;
+    DBuf<Best> csend, crecv, cfinal;
     // bookkeeping
     int64_t pivot = 0, refits = 0, appends = 0;
     int alpha_inc_run = 0;         // appends since alpha was last computed in full (compute_alpha); the incremental form re-synchronises every 256
@@ -251,8 +263,7 @@ struct bohip_gp {
     bool timing_dominant_only = false;   // enable_timing(2): only the dominant kernel (k_trigemm_sq) is bracketed by events
     bool timing_accumulate = false;      // enable_timing(3): as 2, and the event pairs of successive calls pile up unread until
                                          // bohip_gp_get_timing (no hipEventSynchronize / hipEventElapsedTime inside a timed loop)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tpool;  // pooled event pairs
-    size_t tused = 0;
+    size_t tused = 0;   // event pairs of tpool in use
     std::vector<const char*> tlabel;
     std::vector<std::string> tnames;
     std::vector<double> tms;
@@ -362,9 +373,8 @@ static void t_collect(bohip_gp* g, bool force = false) {
 
 // ---- allocation -----------------------------------------------------------------------------------
 static int free_model(bohip_gp* g) {
-    for (double** p : {&g->dX, &g->dy, &g->dL, &g->dW, &g->dWT, &g->dS, &g->dalpha, &g->dr, &g->dt, &g->dApp, &g->dchol_idl})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    if (g->dchol_flags) { hipFree(g->dchol_flags); g->dchol_flags = nullptr; }
+    for (DBuf<double>* b : {&g->dX, &g->dy, &g->dL, &g->dW, &g->dWT, &g->dS, &g->dalpha, &g->dr, &g->dt, &g->dApp, &g->dchol_idl}) b->release();
+    g->dchol_flags.release();
     g->ex_T = 0;   // the task records hold pointers into the buffers just freed
     return 0;
 }
@@ -373,29 +383,24 @@ static size_t chol_abort_word(int T);
 static int alloc_model(bohip_gp* g, int64_t cap) {
     free_model(g);
     // chunk buffers are sized by ld: drop them, they are re-made on demand
-    for (double** p : {&g->dKsT, &g->dVT, &g->dUT, &g->dq, &g->dBV})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    g->kst_rows = g->vt_rows = g->q_cap = g->bv_rows = 0;
+    for (DBuf<double>* b : {&g->dKsT, &g->dVT, &g->dUT, &g->dq, &g->dBV}) b->release();
+    g->kst_rows = 0;
     g->cap = cap;
     // +16 doubles: row stride is an ODD multiple of 128 B, so the 128 rows of a tile spread over the L2/HBM
     // channels instead of camping on one (a power-of-two stride sends every row of a tile to the same channel).
     g->ld = round_up(cap + 1, TILE) + 16;
-    const size_t mat = (size_t)g->ld * g->ld * sizeof(double);
-    HIPCHK(hipMalloc(&g->dX, std::max<size_t>(8, (size_t)cap * g->d * 8)));
-    HIPCHK(hipMalloc(&g->dy, std::max<size_t>(8, (size_t)cap * 8)));
-    HIPCHK(hipMalloc(&g->dL, mat));
-    HIPCHK(hipMalloc(&g->dW, mat));
-    HIPCHK(hipMalloc(&g->dWT, mat));
-    HIPCHK(hipMalloc(&g->dS, mat));
+    const size_t ld = (size_t)g->ld, mat = ld * ld * sizeof(double);
+    hipStream_t st = g->stream;   // (everything was just released: no reserve below waits for it)
+    HIPCHK(g->dX.reserve(std::max<size_t>(1, (size_t)cap * g->d), st));
+    HIPCHK(g->dy.reserve(std::max<size_t>(1, (size_t)cap), st));
+    for (DBuf<double>* b : {&g->dL, &g->dW, &g->dWT, &g->dS}) HIPCHK(b->reserve(ld * ld, st));
     // (+256: k_trimv_stream reads its right-hand sides in whole chunks of 256, masked by index)
-    HIPCHK(hipMalloc(&g->dalpha, (g->ld + 256) * 8));
-    HIPCHK(hipMalloc(&g->dr, (g->ld + 256) * 8));
-    HIPCHK(hipMalloc(&g->dt, (g->ld + 256) * 8));
-    HIPCHK(hipMalloc(&g->dApp, (size_t)APP_ROWS * g->ld * 8));
+    for (DBuf<double>* b : {&g->dalpha, &g->dr, &g->dt}) HIPCHK(b->reserve(ld + 256, st));
+    HIPCHK(g->dApp.reserve((size_t)APP_ROWS * ld, st));
     {
         const size_t Tm = (size_t)(g->ld / TILE) + 1;
-        HIPCHK(hipMalloc(&g->dchol_flags, chol_flag_words((int)std::min<size_t>(Tm, CHOL_DF_TCAP)) * sizeof(unsigned)));
-        HIPCHK(hipMalloc(&g->dchol_idl, Tm * CH_PANELS * 256 * 8));   // W16 of every pivot block
+        HIPCHK(g->dchol_flags.reserve(chol_flag_words((int)std::min<size_t>(Tm, CHOL_DF_TCAP)), st));
+        HIPCHK(g->dchol_idl.reserve(Tm * CH_PANELS * 256, st));   // W16 of every pivot block
     }
     HIPCHK(hipMemsetAsync(g->dL, 0, mat, g->stream));
     HIPCHK(hipMemsetAsync(g->dW, 0, mat, g->stream));
@@ -999,12 +1004,7 @@ static int build_exec_tasks(bohip_gp* g, int T) {
     if (g->ex_T == T && g->dex_tasks && g->ex_nsf == g_chol_nsf && g->ex_inv_g == g_chol_inv_g && g->ex_grp_min == g_chol_inv_grp_min) return 0;
     std::vector<ExTask> all;
     exec_task_list(g->dL, g->dS, g->dW, g->dWT, g->dchol_flags, g->ld, T, g_chol_nsf, g_chol_inv_g, all, g->ex_qbeg);
-    if (all.size() > g->ex_cap) {
-        if (g->dex_tasks) hipFree(g->dex_tasks);
-        g->dex_tasks = nullptr; g->ex_cap = 0;
-        HIPCHK(hipMalloc(&g->dex_tasks, all.size() * sizeof(ExTask)));
-        g->ex_cap = all.size();
-    }
+    HIPCHK(g->dex_tasks.reserve(all.size(), g->stream));
     HIPCHK(hipMemcpyAsync(g->dex_tasks, all.data(), all.size() * sizeof(ExTask), hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));   // `all` is pageable host memory that dies with this frame
     g->ex_bulk4_ok = exec_bulk_stride_ok(all, g->ex_qbeg, 4);
@@ -1385,7 +1385,7 @@ static int refit_once(bohip_gp* g, double jitter) {
                 // the chain kernel's waits leave the word address of the flag that never arrived (bit 31 set); the executor's tasks leave 1
                 char which[96] = "counters of an executor task";
                 if (aborted & 0x80000000u) {
-                    const unsigned base_w = (unsigned)(reinterpret_cast<uintptr_t>(g->dchol_flags) >> 2) | 0x80000000u;
+                    const unsigned base_w = (unsigned)(reinterpret_cast<uintptr_t>(g->dchol_flags.get()) >> 2) | 0x80000000u;
                     snprintf(which, sizeof which, "flag word %u of %zu", (aborted - base_w) & 0x7fffffffu, chol_flag_words(T));
                 }
                 fprintf(stderr, "libbohip: dataflow factorisation (form %d, %d row tiles) timed out on a dependency (%s); using the launch-chained form for a while\n",
@@ -1491,7 +1491,7 @@ static int append_incremental(bohip_gp* g, int64_t N0, int64_t p, int* defer_inf
     t_begin(g, "append_schur_chol");
     const double* schur_in = nullptr;
     if (p >= 3) {      // the Schur complement's inner products, one workgroup each (same bits as k_schur_chol's own loop, which p <= 2 keeps: one launch less)
-        if (!g->dschur) HIPCHK(hipMalloc(&g->dschur, (size_t)APPEND_PMAX * APPEND_PMAX * 8));
+        HIPCHK(g->dschur.reserve((size_t)APPEND_PMAX * APPEND_PMAX, g->stream));
         hipLaunchKernelGGL(k_schur_dots, dim3((unsigned)(p * (p + 1) / 2)), dim3(256), 0, g->stream, g->dL, ld, N0, (int)p, g->dschur);
         schur_in = g->dschur;
     }
@@ -1561,64 +1561,34 @@ static int ensure_score_scratch(bohip_gp* g, int64_t R) {
     const int64_t rc = chunk_rows(g, R);
     g->chunk_now = rc;
     const int64_t SLACK = TILE;  // head-room so tile-granular writes past the last candidate stay inside the buffers
-    if (g->kst_rows < rc || g->dKsT == nullptr) {
-        if (g->dKsT) hipFree(g->dKsT);
-        g->dKsT = nullptr;
-        HIPCHK(hipMalloc(&g->dKsT, (size_t)(rc + SLACK) * g->ld * 8));
-        g->kst_rows = rc;
-    }
-    if (g->q_cap < 2 * T * (Rpad + SLACK)) {   // two partial sums per row tile (k_trigemm_sq's row pieces)
-        if (g->dq) hipFree(g->dq);
-        g->dq = nullptr;
-        HIPCHK(hipMalloc(&g->dq, (size_t)(2 * T * (Rpad + SLACK)) * 8));
-        g->q_cap = 2 * T * (Rpad + SLACK);
-    }
-    if (g->r_cap < Rpad) {
-        for (double** p : {&g->dmu_raw, &g->dmu, &g->dvar, &g->dscore})
-            if (*p) { hipFree(*p); *p = nullptr; }
-        HIPCHK(hipMalloc(&g->dmu_raw, (Rpad + SLACK) * 8));
-        HIPCHK(hipMalloc(&g->dmu, Rpad * 8));
-        HIPCHK(hipMalloc(&g->dvar, Rpad * 8));
-        HIPCHK(hipMalloc(&g->dscore, Rpad * 8));
-        g->r_cap = Rpad;
-    }
+    const hipStream_t st = g->stream;
+    bool grew = false;
+    HIPCHK(g->dKsT.reserve((size_t)(rc + SLACK) * g->ld, st, Grow::Exact, &grew));
+    if (grew) g->kst_rows = rc;
+    HIPCHK(g->dq.reserve((size_t)(2 * T * (Rpad + SLACK)), st));   // two partial sums per row tile (k_trigemm_sq's row pieces)
+    HIPCHK(g->dmu_raw.reserve((size_t)(Rpad + SLACK), st));
+    for (DBuf<double>* b : {&g->dmu, &g->dvar, &g->dscore}) HIPCHK(b->reserve((size_t)Rpad, st));
     const int64_t tiles = Rpad / CTILE + 2;
-    if (g->fz_cap < tiles) {
-        if (g->dfz_cnt) hipFree(g->dfz_cnt);
-        if (g->dfz_best) hipFree(g->dfz_best);
-        g->dfz_cnt = nullptr; g->dfz_best = nullptr; g->fz_cap = 0;
-        HIPCHK(hipMalloc(&g->dfz_cnt, (size_t)(tiles + 1 + 16) * sizeof(unsigned)));   // + the job cursors of k_trigemm_sq_pull
-        HIPCHK(hipMalloc(&g->dfz_best, (size_t)tiles * sizeof(Best)));
-        HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(tiles + 1 + 16) * sizeof(unsigned), g->stream));
-        g->fz_cap = tiles;
+    grew = false;
+    HIPCHK(g->dfz_best.reserve((size_t)tiles, st));
+    HIPCHK(g->dfz_cnt.reserve((size_t)(tiles + 1 + 16), st, Grow::Exact, &grew));   // + the job cursors of k_trigemm_sq_pull
+    if (grew) {
+        HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(tiles + 1 + 16) * sizeof(unsigned), st));
+        g->fz_tiles = tiles;
     }
-    const int64_t nb = (R + 255) / 256 + 1;
-    if (g->bb_cap < nb) {
-        if (g->dblock_best) hipFree(g->dblock_best);
-        g->dblock_best = nullptr;
-        HIPCHK(hipMalloc(&g->dblock_best, nb * sizeof(Best)));
-        g->bb_cap = nb;
-    }
+    HIPCHK(g->dblock_best.reserve((size_t)((R + 255) / 256 + 1), st));
     return 0;
 }
 static int ensure_grad_scratch(bohip_gp* g) {
-    if (g->vt_rows >= g->kst_rows && g->dVT) return 0;
-    for (double** p : {&g->dVT, &g->dUT})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    const size_t bytes = (size_t)g->kst_rows * g->ld * 8;
-    HIPCHK(hipMalloc(&g->dVT, bytes));
-    HIPCHK(hipMalloc(&g->dUT, bytes));
-    HIPCHK(hipMemsetAsync(g->dVT, 0, bytes, g->stream));  // padding columns (>= N) must stay zero
-    g->vt_rows = g->kst_rows;
+    const size_t n = (size_t)g->kst_rows * g->ld;
+    bool grew = false;
+    HIPCHK(g->dVT.reserve(n, g->stream, Grow::Exact, &grew));
+    HIPCHK(g->dUT.reserve(n, g->stream));
+    if (grew) HIPCHK(hipMemsetAsync(g->dVT, 0, n * 8, g->stream));  // padding columns (>= N) must stay zero
     return 0;
 }
 static int ensure_xs(bohip_gp* g, int64_t R) {
-    if (g->xs_cap < R * g->d) {
-        if (g->dXs) hipFree(g->dXs);
-        g->dXs = nullptr;
-        HIPCHK(hipMalloc(&g->dXs, std::max<size_t>(8, (size_t)R * g->d * 8)));
-        g->xs_cap = R * g->d;
-    }
+    HIPCHK(g->dXs.reserve(std::max<size_t>(1, (size_t)R * g->d), g->stream));
     return 0;
 }
 
@@ -1659,11 +1629,7 @@ static int ensure_pieces(bohip_gp* g, int T, int64_t alpha_row) {
     std::vector<int> ps;
     trigemm_pieces(T, alpha_row, ps);
     if (T > 65535) return fail(BOHIP_E_UNSUPPORTED, "too many row tiles");
-    if ((int64_t)ps.size() > g->pieces_cap) {
-        if (g->dpieces) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dpieces)); g->dpieces = nullptr; }
-        g->pieces_cap = 2 * (int64_t)ps.size() + 64;
-        HIPCHK(hipMalloc(&g->dpieces, (size_t)g->pieces_cap * sizeof(int)));
-    }
+    if (ps.size() > g->dpieces.capacity()) HIPCHK(g->dpieces.reserve(2 * ps.size() + 64, g->stream));   // (a table of its own rule: twice, and some)
     // (stream-ordered: a launch of an earlier call may still be reading the old table)
     g->hpieces = ps;
     HIPCHK(hipMemcpyAsync(g->dpieces, g->hpieces.data(), ps.size() * sizeof(int), hipMemcpyHostToDevice, g->stream));
@@ -1672,6 +1638,12 @@ static int ensure_pieces(bohip_gp* g, int T, int64_t alpha_row) {
     return 0;
 }
 
+static int ensure_clk(bohip_gp* g) {
+    bool grew = false;
+    HIPCHK(g->dclk.reserve(2, g->stream, Grow::Exact, &grew));
+    if (grew) HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
+    return 0;
+}
 // V = W K* with the fused epilogue (k_trigemm_sq): one launch per K*' chunk.
 static int launch_trigemm(bohip_gp* g, int T, int64_t ncand, int64_t N, int64_t Rpad, int64_t r0, double* VT,
                           FuseParams fz = FuseParams{}) {
@@ -1680,10 +1652,7 @@ static int launch_trigemm(bohip_gp* g, int T, int64_t ncand, int64_t N, int64_t 
     const int NP = g->n_pieces;
     fz.T = T;
     if (g->timing) {   // core clock under the dominant kernel (BOHIP_INFO_KERNEL_CLOCK_MHZ)
-        if (!g->dclk) {
-            HIPCHK(hipMalloc(&g->dclk, 2 * sizeof(unsigned long long)));
-            HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
-        }
+        CHK(ensure_clk(g));
         fz.clk = g->dclk;
     }
     hipLaunchKernelGGL(k_trigemm_sq, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW, g->ld,
@@ -1704,10 +1673,10 @@ static int launch_kstar_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t 
 
 // k_grad_finish with the observations split over workgroups: the splits' partial sums and the arrival counter of every candidate
 static int ensure_small_counters(bohip_gp* g) {
-    if (g->dgparts) return 0;
-    HIPCHK(hipMalloc(&g->dgparts, (size_t)SMALL_MAX * 16 * (2 * DMAX) * 8));
-    HIPCHK(hipMalloc(&g->dgcount, SMALL_MAX * sizeof(unsigned)));
-    HIPCHK(hipMemsetAsync(g->dgcount, 0, SMALL_MAX * sizeof(unsigned), g->stream));
+    bool grew = false;
+    HIPCHK(g->dgparts.reserve((size_t)SMALL_MAX * 16 * (2 * DMAX), g->stream));
+    HIPCHK(g->dgcount.reserve(SMALL_MAX, g->stream, Grow::Exact, &grew));
+    if (grew) HIPCHK(hipMemsetAsync(g->dgcount, 0, SMALL_MAX * sizeof(unsigned), g->stream));
     return 0;
 }
 static bool split_applicable(const bohip_gp* g);
@@ -1769,24 +1738,21 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
     const int ntiles = small_ntiles(T, m);
     const size_t n_part = (size_t)npass * ntiles * 2048, n_v16 = (size_t)npass * T * 128 * 16, n_rec = (size_t)npass * T * 16,
                  n_g = (size_t)npass * ntiles * 16 * DTm, n_gm = (size_t)npass * T * 16 * DTm;
-    const size_t need = (n_part + 2 * n_v16 + 2 * n_rec + (size_t)npass * 32 + SMALL_MAX + n_g + n_gm) * 8;
-    if (need > g->sm_bytes) {
-        if (g->dsm) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dsm)); g->dsm = nullptr; g->sm_bytes = 0; }
-        HIPCHK(hipMalloc(&g->dsm, need + need / 4));
-        g->sm_bytes = need + need / 4;
-    }
-    if (!g->dsm_cnt || T > g->sm_cnt_T) {
-        if (g->dsm_cnt) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dsm_cnt)); g->dsm_cnt = nullptr; }
+    layout::SmallWs ws;
+    auto lay = [&](const void* base) { return layout::small(base, n_part, n_v16, n_rec, (size_t)npass * 32, SMALL_MAX, n_g, n_gm, &ws); };
+    HIPCHK(g->dsm.reserve(lay(nullptr), g->stream, Grow::Quarter));
+    lay(g->dsm);
+    if (!g->dsm_cnt || T > g->sm_cnt_T) {   // the counters are laid out for 16 row tiles more than the call that grows them
         const int Tc = T + 16;
         // [V counters | U counters]
         const size_t words = 2 * ((size_t)(SMALL_MAX / 16) * (Tc + 1) + 1);
-        HIPCHK(hipMalloc(&g->dsm_cnt, words * sizeof(unsigned)));
+        HIPCHK(g->dsm_cnt.reserve(words, g->stream));
         HIPCHK(hipMemsetAsync(g->dsm_cnt, 0, words * sizeof(unsigned), g->stream));
         g->sm_cnt_T = Tc;
     }
     const KernelHyper hp = make_hyper(g);
     SmallCommon sc{};
-    sc.A = g->dWT; sc.ld = g->ld; sc.N = N; sc.T = T; sc.m = m; sc.P = P; sc.part = g->dsm; sc.ntiles = ntiles; sc.cnt = g->dsm_cnt;
+    sc.A = g->dWT; sc.ld = g->ld; sc.N = N; sc.T = T; sc.m = m; sc.P = P; sc.part = ws.part; sc.ntiles = ntiles; sc.cnt = g->dsm_cnt;
     sc.X = g->dX; sc.Xs = dXs; sc.alpha = g->dalpha; sc.go = (const unsigned*)g->asc_go;
 #ifdef BOHIP_SMALL_TRACE
     if (!g_small_trace) { HIPCHK(hipMalloc(&g_small_trace, 8192 * 16 * 8)); }
@@ -1795,14 +1761,14 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
 #endif
     const size_t cnt_block = (size_t)(SMALL_MAX / 16) * (g->sm_cnt_T + 1) + 1;
     SmallV sv{};
-    sv.v16 = g->dsm + n_part; sv.qpart = sv.v16 + n_v16; sv.mupart = sv.qpart + n_rec;
-    sv.fstash = sv.mupart + n_rec + (size_t)npass * 32;
+    sv.v16 = ws.v16; sv.qpart = ws.qpart; sv.mupart = ws.mupart;
+    sv.fstash = ws.fstash;
     sv.sigma2 = std::exp(2.0 * g->logsig); sv.beta = g->beta; sv.ap = ap;
     sv.mu_out = d_mu; sv.var_out = d_var; sv.score_out = d_score; sv.best_out = d_best; sv.idx_off = (long long)best_off;
     sv.finish = d_grad ? 0 : 1;
     SmallU su{};
-    sv.ks16 = sv.fstash + SMALL_MAX;
-    su.v16 = sv.v16; su.sv = sv; su.gpart = sv.ks16 + n_v16; su.gmpart = su.gpart + n_g; su.grad = d_grad;
+    sv.ks16 = ws.ks16;
+    su.v16 = sv.v16; su.sv = sv; su.gpart = ws.gpart; su.gmpart = ws.gmpart; su.grad = d_grad;
     if (g->asc_fold && d_grad && npass == 1 && g->d <= 16 && 16 * ((g->d + 1) / 2) <= SP_THREADS - 128) {
         su.fold = *g->asc_fold;
         g->asc_fold_done = true;
@@ -1869,13 +1835,7 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), ld = g->ld, Rc = round_up(R, TILE);
     const int T = (int)(Npad / TILE);
     const KernelHyper hp = make_hyper(g);
-    const int64_t need = (int64_t)sp.nsl * Rc * ld;
-    if (g->split_cap < need) {
-        if (g->dsplit) HIPCHK(hipFree(g->dsplit));
-        g->dsplit = nullptr; g->split_cap = 0;
-        HIPCHK(hipMalloc(&g->dsplit, (size_t)need * 8));
-        g->split_cap = need;
-    }
+    HIPCHK(g->dsplit.reserve((size_t)sp.nsl * Rc * ld, g->stream));
     if (want_u) CHK(ensure_grad_scratch(g));
     t_begin(g, "kstar");
     CHK(launch_kstar_any(g, dXs, 0, R, Npad, hp));
@@ -2002,9 +1962,10 @@ static int launch_phase_a(bohip_gp* g, const double* KsT, const int* jobs, int N
 static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
                        double* ub_host = nullptr, bool long_form = false) {
     CHK(one_time_kernel_setup());
-    if (!g->hprune_stat) {
-        HIPCHK(hipHostMalloc((void**)&g->hprune_stat, 64, hipHostMallocDefault));
-        g->hprune_stat[0] = 0u;
+    {
+        bool grew = false;
+        HIPCHK(g->hprune_stat.reserve(16, g->stream, Grow::Exact, &grew));
+        if (grew) g->hprune_stat[0] = 0u;
     }
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
     const int T = (int)(Npad / TILE);
@@ -2014,30 +1975,20 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     if (m >= T) return fail(BOHIP_E_STATE, "pruned pass: the prefix holds the alpha row");
     for (int c : g->hpieces)
         if ((c & 0xffff) < m && c >> 16 != PIECE_WHOLE) return fail(BOHIP_E_STATE, "pruned pass: a half piece in the prefix");
-    // layout (bytes, every part 256-aligned)
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_ks = 0, o_q2 = o_ks + al((size_t)Rpad * ld * 8), o_mu2 = o_q2 + al((size_t)2 * T * Rpad * 8),
-                 o_ub = o_mu2 + al((size_t)Rpad * 8), o_l1 = o_ub + al((size_t)Rpad * 8), o_l2 = o_l1 + al((size_t)PRUNE_K1 * 4),
-                 o_mark = o_l2 + al((size_t)Rpad * 4), o_cnt = o_mark + al((size_t)Rpad * 4), o_rec = o_cnt + 256,
-                 o_parts = o_rec + 256, o_pc = o_parts + al((size_t)2 * P * Rpad * 8), total = o_pc + al((5 * g->hpieces.size() + 8) * 4);
+    layout::PrunedWs ws;
+    auto lay = [&](const void* base) {
+        return layout::pruned(base, (size_t)Rpad * ld, (size_t)2 * T * Rpad, (size_t)Rpad, PRUNE_K1, (size_t)2 * P * Rpad, 5 * g->hpieces.size() + 8, &ws);
+    };
     bool fresh = false;
-    if (g->pr_bytes < total) {
-        fresh = true;
-        if (g->dpr) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dpr)); g->dpr = nullptr; g->pr_bytes = 0; }
-        HIPCHK(hipMalloc(&g->dpr, total));
-        g->pr_bytes = total;
-    }
-    char* b = g->dpr;
-    double *ks2 = (double*)(b + o_ks), *q2 = (double*)(b + o_q2), *mu2 = (double*)(b + o_mu2), *ub = (double*)(b + o_ub);
-    int *l1 = (int*)(b + o_l1), *l2 = (int*)(b + o_l2), *mark = (int*)(b + o_mark), *pcs = (int*)(b + o_pc);
-    const KstarParts kp{g->dW + N * ld, (double*)(b + o_parts), Rpad};
-    g->pr_ks_bytes = o_q2;
-    unsigned* cnt = (unsigned*)(b + o_cnt);
-    Best* rec = (Best*)(b + o_rec);
-    if (g->timing && !g->dclk) {
-        HIPCHK(hipMalloc(&g->dclk, 2 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(g->dclk, 0, 2 * sizeof(unsigned long long), g->stream));
-    }
+    HIPCHK(g->dpr.reserve(lay(nullptr), g->stream, Grow::Exact, &fresh));
+    lay(g->dpr);
+    double *ks2 = ws.ks, *q2 = ws.q2, *mu2 = ws.mu2, *ub = ws.ub;
+    int *l1 = ws.l1, *l2 = ws.l2, *mark = ws.mark, *pcs = ws.pcs;
+    const KstarParts kp{g->dW + N * ld, ws.parts, Rpad};
+    g->pr_ks_len = (size_t)((char*)ws.q2 - (char*)ws.ks);
+    unsigned* cnt = ws.cnt;
+    Best* rec = static_cast<Best*>(ws.rec);
+    if (g->timing) CHK(ensure_clk(g));
     g->q_tiles = T;
     g->score_launches = 1;
     const KernelHyper hp = make_hyper(g);
@@ -2123,10 +2074,10 @@ static bool prune_wanted(bohip_gp* g, int64_t R) {
     if (g->prune_skip > 0) { --g->prune_skip; return false; }
     g->prune_seen = 0u;
     if (g->hprune_stat) {
-        const unsigned n2 = __atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
+        const unsigned n2 = __atomic_load_n(g->hprune_stat.get(), __ATOMIC_RELAXED);
         g->prune_seen = n2;
         if ((int64_t)n2 > R / 8) {
-            __atomic_store_n(g->hprune_stat, 0u, __ATOMIC_RELAXED);
+            __atomic_store_n(g->hprune_stat.get(), 0u, __ATOMIC_RELAXED);
             g->prune_skip = PRUNE_BACKOFF - 1;
             g->prune_retry = true;   // (the word no longer says why: the call after the back-off expects a long list)
             return false;
@@ -2172,14 +2123,14 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
     // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
     // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
     FuseParams fz{};
-    fz.tile_cnt = g->dfz_cnt; fz.total_cnt = g->dfz_cnt + g->fz_cap; fz.tile_best = g->dfz_best;
+    fz.tile_cnt = g->dfz_cnt; fz.total_cnt = g->dfz_cnt + g->fz_tiles; fz.tile_best = g->dfz_best;
     fz.tiles_total = (int)((R + CTILE - 1) / CTILE); fz.R_total = R;
     fz.sigma2 = std::exp(2.0 * g->logsig); fz.beta = g->beta; fz.ap = ap;
     fz.mu_out = d_mu; fz.var_out = d_var; fz.score_out = d_score; fz.best_out = d_best; fz.best_off = best_off;
     // The fused finish counts arrivals in counters its last waves leave at zero.  If an earlier call failed between two of
     // its launches they are not: every later call would then miss its "last arrival" and write no result.  So a call that
     // did not enqueue all of its launches marks the counters dirty, and the next one clears them first.
-    if (g->fz_dirty) HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(g->fz_cap + 1 + 16) * sizeof(unsigned), g->stream));
+    if (g->fz_dirty) HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(g->fz_tiles + 1 + 16) * sizeof(unsigned), g->stream));
     g->fz_dirty = true;
     const int rc = posterior_pass(g, dXs, R, fz);
     if (rc == 0) g->fz_dirty = false;
@@ -2323,14 +2274,18 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_gate, hipEventDisableTiming);
     if (e != hipSuccess) { delete g; return fail(BOHIP_E_HIP, hipGetErrorString(e)); }
     g->stream = g->own_stream;
-    if (hipHostMalloc((void**)&g->hpin, (size_t)(3 * SMALL_R + 2 + 2 * SMALL_R * DMAX) * 8, hipHostMallocDefault) != hipSuccess) g->hpin = nullptr;
-    if (hipMalloc(&g->dinfo, sizeof(int)) != hipSuccess || hipMalloc(&g->dmll, 8 * (DMAX + 4)) != hipSuccess ||
-        hipMalloc(&g->dbest, 4096 * sizeof(Best)) != hipSuccess) {
+    (void)g->hpin.reserve((size_t)(3 * SMALL_R + 2 + 2 * SMALL_R * DMAX), g->stream);   // (without it the small batches take the copies)
+    if (g->dinfo.reserve(1, g->stream) != hipSuccess || g->dmll.reserve(DMAX + 4, g->stream) != hipSuccess ||
+        g->dbest.reserve(4096, g->stream) != hipSuccess) {
         delete g;
         return fail(BOHIP_E_HIP, "hipMalloc failed");
     }
     int rc = alloc_model(g, capacity);
-    if (rc != 0) { bohip_gp_destroy(g); return rc; }
+    if (rc != 0) {
+        delete g;
+        (void)hipGetLastError();   // (the runtime keeps a failed allocation's error until it is read: not for the next call's launch check)
+        return rc;
+    }
     if (const char* e = getenv("BOHIP_JITTER")) {   // "rel[,tries]": jitter escalation for every handle of the process (default: off)
         double rel = 0.0;
         int tries = 10;
@@ -2340,70 +2295,8 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
     return 0;
 }
 
-int bohip_gp_comm_destroy(bohip_gp* g);
-void bohip_gp_destroy(bohip_gp* g) {
-    if (!g) return;
-    hipSetDevice(g->device);
-    if (g->own_stream) hipStreamSynchronize(g->own_stream);
-    if (g->comm) bohip_gp_comm_destroy(g);
-    free_model(g);
-    for (double** p : {&g->dKsT, &g->dq, &g->dmu_raw, &g->dXs, &g->dmu, &g->dvar, &g->dscore, &g->dmll, &g->dVT, &g->dUT})
-        if (*p) hipFree(*p);
-    if (g->dex_tasks) hipFree(g->dex_tasks);
-    if (g->dblock_best) hipFree(g->dblock_best);
-    if (g->dbest) hipFree(g->dbest);
-    if (g->dfz_cnt) hipFree(g->dfz_cnt);
-    if (g->dfz_best) hipFree(g->dfz_best);
-    if (g->dpr) hipFree(g->dpr);
-    if (g->hprune_stat) hipHostFree(g->hprune_stat);
-    if (g->dpieces) hipFree(g->dpieces);
-    if (g->dclk) hipFree(g->dclk);
-    if (g->dgrad) hipFree(g->dgrad);
-    if (g->dBV) hipFree(g->dBV);
-    if (g->dbatch) hipFree(g->dbatch);
-    if (g->dgparts) hipFree(g->dgparts);
-    if (g->dsplit) hipFree(g->dsplit);
-    if (g->dgcount) hipFree(g->dgcount);
-    if (g->dsm) hipFree(g->dsm);
-    if (g->dsm_cnt) hipFree(g->dsm_cnt);
-    if (g->hpin) hipHostFree(g->hpin);
-    if (g->dschur) hipFree(g->dschur);
-    if (g->asc_block) hipFree(g->asc_block);
-    if (g->asc_ints) hipFree(g->asc_ints);
-    if (g->asc_hints) hipHostFree(g->asc_hints);
-    if (g->asc_hio) hipHostFree(g->asc_hio);
-    if (g->asc_dio) hipFree(g->asc_dio);
-    if (g->asc_bounds) hipFree(g->asc_bounds);
-    if (g->asc_best) hipFree(g->asc_best);
-    if (g->dthompson) hipFree(g->dthompson);
-    if (g->ddmll_parts) hipFree(g->ddmll_parts);
-    if (g->fit_ws) hipFree(g->fit_ws);
-    if (g->ens_io) hipFree(g->ens_io);
-    if (g->ens_alpha) hipFree(g->ens_alpha);
-    if (g->fit_io) hipFree(g->fit_io);
-    if (g->dVV) hipFree(g->dVV);
-    if (g->dcov) hipFree(g->dcov);
-    for (double** p : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT, &g->sjF, &g->sj_scal})
-        if (*p) hipFree(*p);
-    if (g->sj_info) hipFree(g->sj_info);
-    if (g->sj_part) hipFree(g->sj_part);
-    if (g->qei_ws) hipFree(g->qei_ws);
-    if (g->kg_ws) hipFree(g->kg_ws);
-    if (g->mes_ws) hipFree(g->mes_ws);
-    if (g->con_ws) hipFree(g->con_ws);
-    if (g->ev_con) hipEventDestroy(g->ev_con);
-    if (g->mo_front) hipFree(g->mo_front);
-    if (g->dinfo) hipFree(g->dinfo);
-    for (auto& e : g->tpool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    if (g->side_stream) { hipStreamSynchronize(g->side_stream); hipStreamDestroy(g->side_stream); }
-    if (g->ev_panels) hipEventDestroy(g->ev_panels);
-    if (g->ev_bulk) hipEventDestroy(g->ev_bulk);
-    if (g->col_stream) { hipStreamSynchronize(g->col_stream); hipStreamDestroy(g->col_stream); }
-    if (g->ev_inv) hipEventDestroy(g->ev_inv);
-    if (g->ev_gate) hipEventDestroy(g->ev_gate);
-    if (g->own_stream) hipStreamDestroy(g->own_stream);
-    delete g;
-}
+// (the teardown is the handle's destructor: stream, communicator, every buffer, then the events and streams)
+void bohip_gp_destroy(bohip_gp* g) { delete g; }
 
 int bohip_gp_set_hyper(bohip_gp* g, const double* loglen, double logsig, double lognoise, double mean_const) {
     if (!g || !loglen) return fail(BOHIP_E_ARG, "null argument");
@@ -2563,12 +2456,7 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     const int rpb = 32;
     dim3 grid((unsigned)((N + 255) / 256), (unsigned)((N + rpb - 1) / rpb));
     const int64_t nblocks = (int64_t)grid.x * grid.y;
-    if (g->dmll_cap < nblocks * NP) {
-        if (g->ddmll_parts) HIPCHK(hipFree(g->ddmll_parts));
-        g->ddmll_parts = nullptr; g->dmll_cap = 0;
-        HIPCHK(hipMalloc(&g->ddmll_parts, (size_t)nblocks * NP * 8));
-        g->dmll_cap = nblocks * NP;
-    }
+    HIPCHK(g->ddmll_parts.reserve((size_t)nblocks * NP, g->stream));
     const KernelHyper hp = make_hyper(g);
     const double noise_var = std::exp(2.0 * g->lognoise);
     dispatch_dt(g->d, [&](auto dt) {
@@ -2591,6 +2479,45 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
 
 // ---- batched marginal likelihood (include/bohip_fit.h, kernels_fit.hip) ---------------------------------------------------------
 static constexpr size_t FIT_WS_CAP_BYTES = (size_t)1 << 30;
+// The observations as the device holds them: the batched fit and the marginalised acquisitions read dX / dy and nothing else of
+// the model, and never refit.
+static int ensure_observations_resident(bohip_gp* g) {
+    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
+    if (g->mirror_dirty) {
+        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        g->mirror_dirty = false;
+    }
+    return 0;
+}
+// The shapes of those calls: P parameters a setting, the padded order M and leading dimension ld of a setting's slab of `slab`
+// doubles, and Hc settings a launch -- what the workspace cap (BOHIP_FIT_WS_MAX_MB) and the launch itself (per_launch: H, or
+// min(H, 65535) where the settings are the y dimension of a grid) allow.
+struct FitPlan { int iso, P, M, ld; size_t slab; int64_t Hc; };
+static FitPlan fit_plan(const bohip_gp* g, int64_t per_launch) {
+    FitPlan p;
+    p.iso = kern_iso(g->kern); p.P = 2 + (p.iso ? 2 : g->d + 1);
+    p.M = (int)round_up(g->n, FIT_NB); p.ld = p.M + 8;
+    p.slab = (size_t)(2 * p.M + 1) * p.ld;
+    size_t cap = FIT_WS_CAP_BYTES;
+    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
+    p.Hc = std::max<int64_t>(1, std::min<int64_t>(per_launch, (int64_t)(cap / (p.slab * 8))));
+    return p;
+}
+static int ensure_fit_ws(bohip_gp* g, const FitPlan& p) {
+    HIPCHK(g->fit_ws.reserve((size_t)p.Hc * p.slab, g->stream));
+    return 0;
+}
+// the block of bohip_gp_score_ens and, with its two gradient members, of bohip_gp_score_ens_grad (layout::ens_io)
+static int ensure_ens_io(bohip_gp* g, int64_t H, int P, int64_t Rc, int64_t R, int64_t nblk, bool with_grad, layout::EnsIo<Best>* io) {
+    auto lay = [&](const void* base) {
+        return layout::ens_io(base, (size_t)H, (size_t)P, (size_t)Rc, (size_t)g->d, (size_t)R, (size_t)nblk, with_grad ? (size_t)g->d : 0, io);
+    };
+    HIPCHK(g->ens_io.reserve(lay(nullptr), g->stream));
+    lay(g->ens_io);
+    return 0;
+}
 extern "C++" {
 template <int DT>
 static int fit_launch(bohip_gp* g, const FitArgs& a, int64_t Hc, bool lo) {
@@ -2624,39 +2551,19 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
         return fail(BOHIP_E_UNSUPPORTED, "the batched marginal likelihood takes at most " + std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " +
                                              std::to_string(g->n) + " (bohip_gp_mll_grad has no limit)");
     HIPCHK(hipSetDevice(g->device));
-    // the observations as the device holds them: the call reads dX / dy and nothing else of the model, and never refits
-    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
-    if (g->mirror_dirty) {
-        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-        g->mirror_dirty = false;
-    }
-    const int iso = kern_iso(g->kern), P = 2 + (iso ? 2 : g->d + 1);
-    const int M = (int)round_up(g->n, FIT_NB), ld = M + 8;
-    const size_t slab = (size_t)(2 * M + 1) * ld;
-    size_t cap = FIT_WS_CAP_BYTES;
-    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
-    const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(H, (int64_t)(cap / (slab * 8))));
+    CHK(ensure_observations_resident(g));
+    const FitPlan pl = fit_plan(g, H);
+    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld;
+    const size_t slab = pl.slab;
+    const int64_t Hc = pl.Hc;
     g->ens_factor_ok = false;   // (the slabs are about to be written)
-    if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {
-        if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
-        g->fit_ws = nullptr; g->fit_ws_bytes = 0;
-        HIPCHK(hipMalloc(&g->fit_ws, (size_t)Hc * slab * 8));
-        g->fit_ws_bytes = (size_t)Hc * slab * 8;
-    }
-    const size_t io_bytes = (size_t)H * (2 * P + 2) * 8 + FIT_STAGES * 8;
-    if (g->fit_io_bytes < io_bytes) {
-        if (g->fit_io) HIPCHK(hipFree(g->fit_io));
-        g->fit_io = nullptr; g->fit_io_bytes = 0;
-        HIPCHK(hipMalloc(&g->fit_io, io_bytes));
-        g->fit_io_bytes = io_bytes;
-    }
-    double* d_theta = reinterpret_cast<double*>(g->fit_io);
-    double* d_mll = d_theta + (size_t)H * P;
-    double* d_grad = d_mll + H;
-    long long* d_pivot = reinterpret_cast<long long*>(d_grad + (size_t)H * P);
-    unsigned long long* d_stamps = reinterpret_cast<unsigned long long*>(d_pivot + H);
+    CHK(ensure_fit_ws(g, pl));
+    layout::FitIo io;
+    HIPCHK(g->fit_io.reserve(layout::fit_io(nullptr, (size_t)H, (size_t)P, FIT_STAGES, &io), g->stream));
+    layout::fit_io(g->fit_io, (size_t)H, (size_t)P, FIT_STAGES, &io);
+    double *d_theta = io.theta, *d_mll = io.mll, *d_grad = io.grad;
+    long long* d_pivot = io.pivot;
+    unsigned long long* d_stamps = io.stamps;
     const bool trace = getenv("BOHIP_FIT_TRACE") != nullptr;   // tools: the stage times of the first workgroup on stderr
     HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
     const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
@@ -2741,53 +2648,24 @@ int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_
                                              std::to_string(g->n));
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
-    // the observations as the device holds them: the call reads dX / dy and nothing else of the model, and never refits
-    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
-    if (g->mirror_dirty) {
-        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-        g->mirror_dirty = false;
-    }
-    const int iso = kern_iso(g->kern), P = 2 + (iso ? 2 : g->d + 1), d = g->d;
-    const int M = (int)round_up(g->n, FIT_NB), ld = M + 8;
-    const size_t slab = (size_t)(2 * M + 1) * ld;
-    size_t cap = FIT_WS_CAP_BYTES;
-    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
-    // (settings are the y dimension of k_ens_score's grid: at most 65535 per launch)
-    const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(H, 65535), (int64_t)(cap / (slab * 8))));
+    CHK(ensure_observations_resident(g));
+    const FitPlan pl = fit_plan(g, std::min<int64_t>(H, 65535));   // (settings are the y dimension of k_ens_score's grid)
+    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld, d = g->d;
+    const size_t slab = pl.slab;
+    const int64_t Hc = pl.Hc;
     g->ens_factor_ok = false;   // (the slabs are about to be written)
-    if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {
-        if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
-        g->fit_ws = nullptr; g->fit_ws_bytes = 0;
-        HIPCHK(hipMalloc(&g->fit_ws, (size_t)Hc * slab * 8));
-        g->fit_ws_bytes = (size_t)Hc * slab * 8;
-    }
+    CHK(ensure_fit_ws(g, pl));
     // candidates per chunk: the three H x Rc planes stay within 64 MiB (at least one tile, at most 16384 candidates)
     const int64_t Rc = std::min<int64_t>(round_up(R, ENS_TC),
                                          std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (24 * H)) / ENS_TC * ENS_TC)));
     int64_t nblk = 0;
     for (int64_t r0 = 0; r0 < R; r0 += Rc) nblk += (std::min(Rc, R - r0) + 255) / 256;
-    const size_t n_dbl = (size_t)H * P + 3 * (size_t)H + (size_t)Rc * d + 3 * (size_t)H * Rc + (size_t)R;
-    const size_t io_bytes = n_dbl * 8 + (size_t)(nblk + 1) * sizeof(Best);
-    if (g->ens_io_bytes < io_bytes) {
-        if (g->ens_io) HIPCHK(hipFree(g->ens_io));
-        g->ens_io = nullptr; g->ens_io_bytes = 0;
-        HIPCHK(hipMalloc(&g->ens_io, io_bytes));
-        g->ens_io_bytes = io_bytes;
-    }
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(Best) == 16, "pivot words, records");
-    double* d_theta = reinterpret_cast<double*>(g->ens_io);
-    double* d_w = d_theta + (size_t)H * P;
-    double* d_wt = d_w + H;
-    long long* d_pivot = reinterpret_cast<long long*>(d_wt + H);
-    double* d_xs = d_wt + 2 * (size_t)H;
-    double* d_each = d_xs + (size_t)Rc * d;
-    double* d_mu = d_each + (size_t)H * Rc;
-    double* d_var = d_mu + (size_t)H * Rc;
-    double* d_scores = d_var + (size_t)H * Rc;
-    Best* d_blk = reinterpret_cast<Best*>(d_scores + R);
-    Best* d_best = d_blk + nblk;
+    layout::EnsIo<Best> io;
+    CHK(ensure_ens_io(g, H, P, Rc, R, nblk, false, &io));
+    double *d_theta = io.theta, *d_w = io.w, *d_wt = io.wt, *d_xs = io.xs, *d_each = io.each, *d_mu = io.mu, *d_var = io.var, *d_scores = io.scores;
+    long long* d_pivot = io.pivot;
+    Best *d_blk = io.blk, *d_best = io.best;
     HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
     if (weights) HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
     const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
@@ -2899,64 +2777,30 @@ int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, i
                                              std::to_string(g->n));
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
-    // the observations as the device holds them: the call reads dX / dy and nothing else of the model, and never refits
-    if (g->dL == nullptr || g->cap < g->n) CHK(alloc_model(g, std::max<int64_t>(g->n, 1)));
-    if (g->mirror_dirty) {
-        HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-        g->mirror_dirty = false;
-    }
-    const int iso = kern_iso(g->kern), P = 2 + (iso ? 2 : g->d + 1), d = g->d;
-    const int M = (int)round_up(g->n, FIT_NB), ld = M + 8;
-    const size_t slab = (size_t)(2 * M + 1) * ld;
-    size_t cap = FIT_WS_CAP_BYTES;
-    if (const char* e = getenv("BOHIP_FIT_WS_MAX_MB")) cap = std::min(cap, (size_t)std::max(1, atoi(e)) << 20);
-    const int64_t Hc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(H, 65535), (int64_t)(cap / (slab * 8))));
+    CHK(ensure_observations_resident(g));
+    const FitPlan pl = fit_plan(g, std::min<int64_t>(H, 65535));   // (settings are the y dimension of k_ens_grad's grid)
+    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld, d = g->d;
+    const size_t slab = pl.slab;
+    const int64_t Hc = pl.Hc;
     const bool resident = H <= Hc;   // every setting's factor fits the workspace at once: factor once, before the candidate chunks
     // the slabs hold these very factors: every setting at once, left by this symbol for byte-identical theta and the same observations
     // (M follows from the observations; the kernel and d of a handle never change)
     const bool reuse = resident && g->ens_factor_ok && g->ens_version == g->data_version && g->ens_theta.size() == (size_t)H * P &&
                        g->ens_pivot.size() == (size_t)H && std::memcmp(g->ens_theta.data(), theta, (size_t)H * P * 8) == 0;
     g->ens_factor_ok = false;   // (whatever fails below: the next call factors)
-    if (g->fit_ws_bytes < (size_t)Hc * slab * 8) {   // (never on a reuse: the same theta and M ask for the same bytes)
-        if (g->fit_ws) HIPCHK(hipFree(g->fit_ws));
-        g->fit_ws = nullptr; g->fit_ws_bytes = 0;
-        HIPCHK(hipMalloc(&g->fit_ws, (size_t)Hc * slab * 8));
-        g->fit_ws_bytes = (size_t)Hc * slab * 8;
-    }
-    if (g->ens_alpha_bytes < (size_t)Hc * M * 8) {
-        if (g->ens_alpha) HIPCHK(hipFree(g->ens_alpha));
-        g->ens_alpha = nullptr; g->ens_alpha_bytes = 0;
-        HIPCHK(hipMalloc(&g->ens_alpha, (size_t)Hc * M * 8));
-        g->ens_alpha_bytes = (size_t)Hc * M * 8;
-    }
+    CHK(ensure_fit_ws(g, pl));   // (never grows on a reuse: the same theta and M ask for the same bytes)
+    HIPCHK(g->ens_alpha.reserve((size_t)Hc * M, g->stream));
     // candidates per chunk: the (3 + d) H x Rc planes stay within 64 MiB (at least one tile, at most 16384 candidates)
     const int64_t Rc = std::min<int64_t>(
         round_up(R, ENS_TC), std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (8 * (3 + (int64_t)d) * H)) / ENS_TC * ENS_TC)));
     int64_t nblk = 0;
     for (int64_t r0 = 0; r0 < R; r0 += Rc) nblk += (std::min(Rc, R - r0) + 255) / 256;
-    const size_t n_dbl = (size_t)H * P + 3 * (size_t)H + (size_t)Rc * d + (3 + (size_t)d) * H * Rc + (size_t)R + (size_t)R * d;
-    const size_t io_bytes = n_dbl * 8 + (size_t)(nblk + 1) * sizeof(Best);
-    if (g->ens_io_bytes < io_bytes) {
-        if (g->ens_io) HIPCHK(hipFree(g->ens_io));
-        g->ens_io = nullptr; g->ens_io_bytes = 0;
-        HIPCHK(hipMalloc(&g->ens_io, io_bytes));
-        g->ens_io_bytes = io_bytes;
-    }
-    double* d_theta = reinterpret_cast<double*>(g->ens_io);
-    double* d_w = d_theta + (size_t)H * P;
-    double* d_wt = d_w + H;
-    long long* d_pivot = reinterpret_cast<long long*>(d_wt + H);
-    double* d_xs = d_wt + 2 * (size_t)H;
-    double* d_each = d_xs + (size_t)Rc * d;
-    double* d_mu = d_each + (size_t)H * Rc;
-    double* d_var = d_mu + (size_t)H * Rc;
-    double* d_geach = d_var + (size_t)H * Rc;
-    double* d_scores = d_geach + (size_t)H * Rc * d;
-    double* d_grad = d_scores + R;
-    Best* d_blk = reinterpret_cast<Best*>(d_grad + (size_t)R * d);
-    Best* d_best = d_blk + nblk;
+    layout::EnsIo<Best> io;
+    CHK(ensure_ens_io(g, H, P, Rc, R, nblk, true, &io));
+    double *d_theta = io.theta, *d_w = io.w, *d_wt = io.wt, *d_xs = io.xs, *d_each = io.each, *d_mu = io.mu, *d_var = io.var;
+    double *d_geach = io.geach, *d_scores = io.scores, *d_grad = io.grad;
+    long long* d_pivot = io.pivot;
+    Best *d_blk = io.blk, *d_best = io.best;
     HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
     if (weights) HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
     if (reuse) HIPCHK(hipMemcpyAsync(d_pivot, g->ens_pivot.data(), (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
@@ -3107,7 +2951,7 @@ int bohip_gp_predict(bohip_gp* g, const double* Xs, int64_t R, double* mu, doubl
 }
 
 // Stages shared by bohip_gp_predict_cov and bohip_gp_sample_joint: K*', V' = K*'W' (stored), V'V on the MFMA engine (lower
-// 128-tiles of dVV, leading dimension cov_cap).  `who` names the caller in the message of the one-chunk limit.
+// 128-tiles of dVV, leading dimension cov_ld).  `who` names the caller in the message of the one-chunk limit.
 static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* who) {
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     HIPCHK(hipSetDevice(g->device));
@@ -3121,13 +2965,11 @@ static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* wh
     CHK(one_time_kernel_setup());
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, Rp = round_up(R, TILE);
     const int T = (int)(Npad / TILE), CT = (int)(Rp / TILE);
-    if (g->cov_cap < Rp) {
-        for (double** p : {&g->dVV, &g->dcov})
-            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-        g->cov_cap = 0;
-        HIPCHK(hipMalloc(&g->dVV, (size_t)Rp * Rp * 8));
-        HIPCHK(hipMalloc(&g->dcov, (size_t)Rp * Rp * 8));
-        g->cov_cap = Rp;
+    {
+        bool grew = false;
+        HIPCHK(g->dVV.reserve((size_t)Rp * Rp, g->stream));
+        HIPCHK(g->dcov.reserve((size_t)Rp * Rp, g->stream, Grow::Exact, &grew));
+        if (grew) g->cov_ld = Rp;   // (a smaller call keeps the leading dimension the buffers were made for)
     }
     const KernelHyper hp = make_hyper(g);
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
@@ -3140,7 +2982,7 @@ static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* wh
     t_end(g);
     t_begin(g, "gemm_VV");
     GemmNTParams p{};  // (V'V)[r][s] = sum_i V'[r][i] V'[s][i], lower 128-tiles
-    p.A = g->dVT; p.lda = g->ld; p.B = g->dVT; p.ldb = g->ld; p.C = g->dVV; p.ldc = g->cov_cap;
+    p.A = g->dVT; p.lda = g->ld; p.B = g->dVT; p.ldb = g->ld; p.C = g->dVV; p.ldc = g->cov_ld;
     p.mt = CT; p.nt64 = 2 * CT; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.diag_skip = 1;
     CHK(launch_gemm_nt(g, p));
     t_end(g);
@@ -3167,7 +3009,7 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
     dispatch_dt(g->d, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
-                   g->cov_cap, g->dcov, R);
+                   g->cov_ld, g->dcov, R);
     });
     HIPCHK(hipGetLastError());
     t_end(g);
@@ -3181,51 +3023,37 @@ int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, d
 // ---- joint posterior draws over a candidate set (kernels_sample.hip; reference myrand(model, X::Matrix), src/models/gp.jl:7) ----
 // the S x R draws (also the matrix bohip_gp_qei_select uploads)
 static int ensure_sample_matrix(bohip_gp* g, size_t fneed) {
-    if (g->sjF_cap < fneed) {
-        if (g->sjF) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sjF)); g->sjF = nullptr; }
-        const size_t cap = std::max(fneed, g->sjF_cap + g->sjF_cap / 2);
-        g->sjF_cap = 0;
-        HIPCHK(hipMalloc(&g->sjF, cap * 8));
-        g->sjF_cap = cap;
-    }
+    HIPCHK(g->sjF.reserve(fneed, g->stream, Grow::Half));
+    return 0;
+}
+static int ensure_thompson(bohip_gp* g, int64_t S) {   // S arg-max records
+    HIPCHK(g->dthompson.reserve((size_t)S, g->stream));
     return 0;
 }
 static int ensure_sample(bohip_gp* g, int64_t Rp, int64_t R, int64_t S, bool want_samples, size_t part_recs) {
-    if (g->sj_cap < Rp) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        for (double** p : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT})
-            if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-        const int64_t cap = std::max<int64_t>(Rp, round_up(g->sj_cap + g->sj_cap / 2, TILE)), ld = cap + 16;
-        g->sj_cap = 0;
-        const size_t mat = (size_t)ld * ld * 8, inv = (size_t)cap * TILE * 8;
-        HIPCHK(hipMalloc(&g->sjL, mat));
-        HIPCHK(hipMalloc(&g->sjS, mat));
-        HIPCHK(hipMalloc(&g->sjW, inv));
-        HIPCHK(hipMalloc(&g->sjWT, inv));
+    if (g->sj_rows < Rp || !g->sjWT) {   // the four grow together, by half and in whole tiles: sj_rows is also their leading dimension
+        const hipStream_t st = g->stream;
+        const int64_t rows = std::max<int64_t>(Rp, round_up(g->sj_rows + g->sj_rows / 2, TILE)), ld = rows + 16;
+        g->sj_rows = 0;
+        const size_t mat = (size_t)ld * ld, inv = (size_t)rows * TILE;
+        HIPCHK(hipStreamSynchronize(st));   // all four go before any comes back: the peak stays at one set
+        for (DBuf<double>* b : {&g->sjL, &g->sjS, &g->sjW, &g->sjWT}) b->release();
+        HIPCHK(g->sjL.reserve(mat, st));
+        HIPCHK(g->sjS.reserve(mat, st));
+        HIPCHK(g->sjW.reserve(inv, st));
+        HIPCHK(g->sjWT.reserve(inv, st));
         // tiles above the diagonal tiles of the matrix, and the far triangles of the diagonal inverses, are never written: zero once
-        HIPCHK(hipMemsetAsync(g->sjL, 0, mat, g->stream));
-        HIPCHK(hipMemsetAsync(g->sjS, 0, mat, g->stream));
-        HIPCHK(hipMemsetAsync(g->sjW, 0, inv, g->stream));
-        HIPCHK(hipMemsetAsync(g->sjWT, 0, inv, g->stream));
-        g->sj_cap = cap;
+        HIPCHK(hipMemsetAsync(g->sjL, 0, mat * 8, st));
+        HIPCHK(hipMemsetAsync(g->sjS, 0, mat * 8, st));
+        HIPCHK(hipMemsetAsync(g->sjW, 0, inv * 8, st));
+        HIPCHK(hipMemsetAsync(g->sjWT, 0, inv * 8, st));
+        g->sj_rows = rows;
     }
-    if (!g->sj_scal) HIPCHK(hipMalloc(&g->sj_scal, 8));
-    if (!g->sj_info) HIPCHK(hipMalloc(&g->sj_info, sizeof(int)));
+    HIPCHK(g->sj_scal.reserve(1, g->stream));
+    HIPCHK(g->sj_info.reserve(1, g->stream));
     CHK(ensure_sample_matrix(g, want_samples ? (size_t)S * R : 0));
-    if (g->sj_part_cap < part_recs) {
-        if (g->sj_part) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->sj_part)); g->sj_part = nullptr; }
-        const size_t cap = std::max(part_recs, g->sj_part_cap + g->sj_part_cap / 2);
-        g->sj_part_cap = 0;
-        HIPCHK(hipMalloc(&g->sj_part, cap * sizeof(Best)));
-        g->sj_part_cap = cap;
-    }
-    if (g->thompson_cap < S) {
-        if (g->dthompson) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dthompson)); }
-        g->dthompson = nullptr; g->thompson_cap = 0;
-        HIPCHK(hipMalloc(&g->dthompson, (size_t)S * sizeof(Best)));
-        g->thompson_cap = S;
-    }
-    return 0;
+    HIPCHK(g->sj_part.reserve(part_recs, g->stream, Grow::Half));
+    return ensure_thompson(g, S);
 }
 
 // The draw itself, shared by bohip_gp_sample_joint and bohip_gp_qei_batch (`who` names the caller in messages).  keepF: the
@@ -3245,7 +3073,7 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
     const bool mfma = S >= g_sample_mfma_min;
     const int ntiles = (int)((R + (mfma ? SM_ROWS : SROWS) - 1) / (mfma ? SM_ROWS : SROWS));
     CHK(ensure_sample(g, Rp, R, S, keepF, (size_t)S * ntiles));
-    const int64_t ld = g->sj_cap + 16;
+    const int64_t ld = g->sj_rows + 16;
     const FactorWs ws{g->sjL, g->sjS, g->sjW, g->sjWT, ld, TILE, (int64_t)TILE * TILE, g->sj_info};
     const KernelHyper hp = make_hyper(g);
     const dim3 cgrid((unsigned)((Rp + 255) / 256), (unsigned)(Rp / 16));
@@ -3254,9 +3082,9 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
     dispatch_dt(g->d, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         LAUNCH_FAM(fam_low(hp), (k_sample_cov<DT, true>), (k_sample_cov<DT, false>), cgrid, dim3(256), 0, g->stream, g->dXs, R, Rp, hp,
-                   g->dVV, g->cov_cap, g->dcov, g->cov_cap, ws.L, ld);
+                   g->dVV, g->cov_ld, g->dcov, g->cov_ld, ws.L, ld);
     });
-    hipLaunchKernelGGL(k_sample_diagmax, dim3(1), dim3(256), 0, g->stream, g->dcov, g->cov_cap, R, g->sj_scal);
+    hipLaunchKernelGGL(k_sample_diagmax, dim3(1), dim3(256), 0, g->stream, g->dcov, g->cov_ld, R, g->sj_scal);
     HIPCHK(hipGetLastError());
     t_end(g);
     double jit = 0.0;
@@ -3265,7 +3093,7 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
         HIPCHK(hipMemsetAsync(g->sj_info, 0, sizeof(int), g->stream));
         if (tries > 0) {   // Sigma is kept (dcov): the workspace again, with the jitter on the diagonal
             t_begin(g, "post_cov+jitter");
-            hipLaunchKernelGGL(k_sample_rejit, cgrid, dim3(256), 0, g->stream, g->dcov, g->cov_cap, R, Rp, jit, ws.L, ld);
+            hipLaunchKernelGGL(k_sample_rejit, cgrid, dim3(256), 0, g->stream, g->dcov, g->cov_ld, R, Rp, jit, ws.L, ld);
             HIPCHK(hipGetLastError());
             t_end(g);
         }
@@ -3354,23 +3182,9 @@ static int qei_check_size(const char* who, int64_t R, int64_t S) {
 }
 static int ensure_qei(bohip_gp* g, int64_t R, int64_t S, int64_t q, QeiWs* w) {
     const size_t NB = (size_t)((S + QEI_B - 1) / QEI_B), NT = (size_t)((R + QEI_PICK - 1) / QEI_PICK);
-    const size_t o_part = (size_t)S * 8, o_tile = o_part + NB * (size_t)R * 8, o_gain = o_tile + NT * sizeof(Best),
-                 o_idx = o_gain + (size_t)q * 8, o_words = o_idx + (size_t)q * 8, need = o_words + 16;
-    if (g->qei_bytes < need) {
-        if (g->qei_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->qei_ws)); g->qei_ws = nullptr; }
-        const size_t cap = std::max(need, g->qei_bytes + g->qei_bytes / 2);
-        g->qei_bytes = 0;
-        HIPCHK(hipMalloc(&g->qei_ws, cap));
-        g->qei_bytes = cap;
-    }
-    char* b = g->qei_ws;
-    w->m = reinterpret_cast<double*>(b);
-    w->part = reinterpret_cast<double*>(b + o_part);
-    w->tile = reinterpret_cast<Best*>(b + o_tile);
-    w->gain = reinterpret_cast<double*>(b + o_gain);
-    w->idx = reinterpret_cast<long long*>(b + o_idx);
-    w->done = reinterpret_cast<unsigned*>(b + o_words);
-    w->arrive = w->done + 1;
+    auto lay = [&](const void* base) { return layout::qei(base, (size_t)S, NB * (size_t)R, NT, (size_t)q, w); };
+    HIPCHK(g->qei_ws.reserve(lay(nullptr), g->stream, Grow::Half));
+    lay(g->qei_ws);
     return 0;
 }
 // the q rounds over g->sjF, back to back on the handle's stream, and the two small copies behind them (no synchronisation)
@@ -3443,21 +3257,9 @@ static int kg_check_size(const char* who, int64_t R) {
     return 0;
 }
 static int ensure_kg(bohip_gp* g, int64_t R, int64_t E, bool lines, KgWs* w) {
-    const size_t o_best = (size_t)E * 8, o_nseg = o_best + sizeof(Best), o_a = round_up(o_nseg + (size_t)E * 4, 16),
-                 o_B = o_a + (lines ? (size_t)R * 8 : 0), need = o_B + (lines ? (size_t)E * R * 8 : 0);
-    if (g->kg_bytes < need) {
-        if (g->kg_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->kg_ws)); g->kg_ws = nullptr; }
-        const size_t cap = std::max(need, g->kg_bytes + g->kg_bytes / 2);
-        g->kg_bytes = 0;
-        HIPCHK(hipMalloc(&g->kg_ws, cap));
-        g->kg_bytes = cap;
-    }
-    char* b = g->kg_ws;
-    w->kg = reinterpret_cast<double*>(b);
-    w->best = reinterpret_cast<Best*>(b + o_best);
-    w->nseg = reinterpret_cast<int*>(b + o_nseg);
-    w->a = reinterpret_cast<double*>(b + o_a);
-    w->B = reinterpret_cast<double*>(b + o_B);
+    auto lay = [&](const void* base) { return layout::kg(base, (size_t)E, lines ? (size_t)R : 0, w); };
+    HIPCHK(g->kg_ws.reserve(lay(nullptr), g->stream, Grow::Half));
+    lay(g->kg_ws);
     return 0;
 }
 // the march of every evaluation point and the record, on the handle's stream, and the small copies behind them (no synchronisation)
@@ -3494,12 +3296,12 @@ int bohip_gp_kg(bohip_gp* g, const double* Xs, int64_t R, int64_t E, double* kg,
     dispatch_dt(g->d, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
-                   g->cov_cap, g->dcov, g->cov_cap);
+                   g->cov_ld, g->dcov, g->cov_ld);
     });
     HIPCHK(hipGetLastError());
     t_end(g);
     const double nu = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
-    CHK(kg_march(g, true, w, g->dmu, g->dcov, g->cov_cap, R, E, nu, kg, nseg, best));
+    CHK(kg_march(g, true, w, g->dmu, g->dcov, g->cov_ld, R, E, nu, kg, nseg, best));
     if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
@@ -3549,31 +3351,16 @@ static int mes_check_limits(const char* who, int64_t R, int64_t K) {
                                              "): the bracket of the max-value quantiles is guaranteed up to it");
     return 0;
 }
-// ONE block: [mes | dmu | dvar | mu | var  (R each) | maxvals K | quantiles 3 (+1) | state | bracket partials | probe sums | records]
+// ONE block, see layout::mes
 static int ensure_mes(bohip_gp* g, int64_t R, int64_t K, MesBufs* b) {
     const int nsl = mes_slices(R);
-    const size_t nb = (size_t)((R + 255) / 256);
-    const size_t o_max = (size_t)5 * R * 8, o_q = o_max + (size_t)K * 8, o_st = o_q + 4 * 8, o_br = o_st + (2 * MES_STATE + 4) * 8,
-                 o_part = o_br + (size_t)3 * MES_BR_MAX * 8, o_blk = o_part + (size_t)2 * MES_NQ * MES_PROBES * nsl * 8,
-                 need = o_blk + (nb + 1) * sizeof(Best);
-    if (g->mes_bytes < need) {
-        if (g->mes_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->mes_ws)); g->mes_ws = nullptr; }
-        const size_t cap = std::max(need, g->mes_bytes + g->mes_bytes / 2);
-        g->mes_bytes = 0;
-        HIPCHK(hipMalloc(&g->mes_ws, cap));
-        g->mes_bytes = cap;
-    }
-    char* p = g->mes_ws;
-    double* d = reinterpret_cast<double*>(p);
-    b->mes = d; b->dmu = d + R; b->dvar = d + 2 * R; b->mu = d + 3 * R; b->var = d + 4 * R;
-    b->maxvals = reinterpret_cast<double*>(p + o_max);
-    b->quant = reinterpret_cast<double*>(p + o_q);
-    b->w.st = reinterpret_cast<double*>(p + o_st);
-    b->w.br = reinterpret_cast<double*>(p + o_br);
-    b->w.part = reinterpret_cast<double*>(p + o_part);
+    auto lay = [&](const void* base) {
+        return layout::mes(base, (size_t)R, (size_t)K, 2 * MES_STATE + 4, (size_t)3 * MES_BR_MAX, (size_t)2 * MES_NQ * MES_PROBES * nsl,
+                           (size_t)((R + 255) / 256), b);
+    };
+    HIPCHK(g->mes_ws.reserve(lay(nullptr), g->stream, Grow::Half));
+    lay(g->mes_ws);
     b->w.nsl = nsl;
-    b->blocks = reinterpret_cast<Best*>(p + o_blk);
-    b->best = b->blocks + nb;
     return 0;
 }
 // the Gumbel sampler on the device's (mu, var): bracket, 14 probe passes, the draw (no synchronisation, no copies)
@@ -3717,23 +3504,11 @@ struct ConBufs {
     double *grad;                    // [R d]
     Best *blocks, *best;             // [CON_GRID_MAX], [1]
 };
-// ONE block on the handle: [mu | var | pmu | pvar | value | logfeas | records | jmu | jvar | grad]
+// ONE block on the handle, see layout::con
 static int ensure_con(bohip_gp* g, int64_t C, int64_t R, bool jac, ConBufs* b) {
-    const size_t m = (size_t)(C + 1) * R, o_rec = (4 * m + 2 * (size_t)R) * 8, o_j = o_rec + (CON_GRID_MAX + 1) * sizeof(Best),
-                 need = o_j + (jac ? (2 * m + (size_t)R) * g->d * 8 : 0);
-    if (g->con_bytes < need) {
-        if (g->con_ws) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->con_ws)); g->con_ws = nullptr; }
-        const size_t cap = std::max(need, g->con_bytes + g->con_bytes / 2);
-        g->con_bytes = 0;
-        HIPCHK(hipMalloc(&g->con_ws, cap));
-        g->con_bytes = cap;
-    }
-    double* p = reinterpret_cast<double*>(g->con_ws);
-    b->mu = p; b->var = p + m; b->pmu = p + 2 * m; b->pvar = p + 3 * m; b->value = p + 4 * m; b->logfeas = b->value + R;
-    b->blocks = reinterpret_cast<Best*>(g->con_ws + o_rec);
-    b->best = b->blocks + CON_GRID_MAX;
-    double* j = reinterpret_cast<double*>(g->con_ws + o_j);
-    b->jmu = jac ? j : nullptr; b->jvar = jac ? j + m * g->d : nullptr; b->grad = jac ? j + 2 * m * g->d : nullptr;
+    auto lay = [&](const void* base) { return layout::con(base, (size_t)(C + 1) * R, (size_t)R, CON_GRID_MAX, jac ? (size_t)g->d : 0, b); };
+    HIPCHK(g->con_ws.reserve(lay(nullptr), g->stream, Grow::Half));
+    lay(g->con_ws);
     return 0;
 }
 
@@ -4019,7 +3794,7 @@ static int mo_make_front(const char* who, const double* front, int64_t n, const 
     return 0;
 }
 static int mo_upload_front(bohip_gp* g, const std::vector<double>& fr) {
-    if (!g->mo_front) HIPCHK(hipMalloc(&g->mo_front, (size_t)(2 * BOHIP_MO_FRONT_MAX + 3) * 8));
+    HIPCHK(g->mo_front.reserve((size_t)(2 * BOHIP_MO_FRONT_MAX + 3), g->stream));
     HIPCHK(hipMemcpyAsync(g->mo_front, fr.data(), fr.size() * 8, hipMemcpyHostToDevice, g->stream));
     return 0;
 }
@@ -4134,26 +3909,17 @@ struct bohip_paths {
     int d = 0, F = 0, mfma_min = 0;
     double amp = 0.0, beta = 0.0;
     KernelHyper hp;
-    double *dX = nullptr, *dOm = nullptr, *dCf = nullptr;
+    DBuf<double> dX, dOm, dCf;
     // evaluation scratch: one chunk of candidates, its S x chunk values, its tile records, the S running records, the gradient staging
-    double *dXs = nullptr, *dV = nullptr, *df = nullptr, *dg = nullptr;
-    int64_t* dpath_of = nullptr;
-    Best *dpart = nullptr, *dbest = nullptr;
-    int64_t xs_cap = 0, g_cap = 0;
-    size_t v_cap = 0, part_cap = 0;
+    DBuf<double> dXs, dV, df, dg;
+    DBuf<int64_t> dpath_of;
+    DBuf<Best> dpart, dbest;
 };
 static constexpr int64_t PATHS_CHUNK = 32768;       // candidates per launch of an evaluation (a multiple of PM_ROWS and PR_CAND)
 static constexpr int64_t PATHS_GRAD_CHUNK = 4096;   // points per launch of bohip_paths_eval_grad
 static_assert(BOHIP_PATHS_S_MAX <= 65535 && PATHS_CHUNK % PM_ROWS == 0 && PATHS_CHUNK % PR_CAND == 0, "grid.y holds the path tiles");
 
-static void paths_free(bohip_paths* p) {
-    for (double** q : {&p->dX, &p->dOm, &p->dCf, &p->dXs, &p->dV, &p->df, &p->dg})
-        if (*q) { hipFree(*q); *q = nullptr; }
-    if (p->dpath_of) hipFree(p->dpath_of);
-    if (p->dpart) hipFree(p->dpart);
-    if (p->dbest) hipFree(p->dbest);
-    delete p;
-}
+static void paths_free(bohip_paths* p) { delete p; }   // (the members free themselves)
 static PathArgs paths_args(const bohip_paths* p) {
     return PathArgs{p->dX, p->dOm, p->dCf, p->N, p->Npad, p->ldc, p->S, p->F, p->amp, p->beta};
 }
@@ -4190,16 +3956,16 @@ static int paths_draw_fill(bohip_paths* p, uint64_t seed) {
     hipStream_t st = g->stream;
     const int64_t N = p->N, S = p->S, M = p->M;
     const int d = p->d;
-    HIPCHK(hipMalloc(&p->dX, (size_t)N * d * 8));
-    HIPCHK(hipMalloc(&p->dOm, (size_t)p->F * d * 8));
-    HIPCHK(hipMalloc(&p->dCf, (size_t)S * p->ldc * 8));
-    HIPCHK(hipMalloc(&p->dbest, (size_t)S * sizeof(Best)));
+    HIPCHK(p->dX.reserve((size_t)N * d, st));
+    HIPCHK(p->dOm.reserve((size_t)p->F * d, st));
+    HIPCHK(p->dCf.reserve((size_t)S * p->ldc, st));
+    HIPCHK(p->dbest.reserve((size_t)S, st));
     // right-hand sides and the two triangular products: [S][ldr] twice (k_trimv_stream reads whole chunks of 256 columns, masked by index)
     const int64_t ldr = round_up(N, 256) + 256;
-    double *T0 = nullptr, *T1 = nullptr;
-    HIPCHK(hipMalloc(&T0, (size_t)S * ldr * 8));
-    if (hipMalloc(&T1, (size_t)S * ldr * 8) != hipSuccess) { hipFree(T0); return fail(BOHIP_E_HIP, "paths_draw: out of device memory"); }
-    int rc = [&]() -> int {
+    DBuf<double> T0, T1;   // (freed when the function leaves, however it leaves)
+    HIPCHK(T0.reserve((size_t)S * ldr, st));
+    if (T1.reserve((size_t)S * ldr, st) != hipSuccess) return fail(BOHIP_E_HIP, "paths_draw: out of device memory");
+    {
         HIPCHK(hipMemcpyAsync(p->dX, g->dX, (size_t)N * d * 8, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemsetAsync(p->dCf, 0, (size_t)S * p->ldc * 8, st));
         HIPCHK(hipMemsetAsync(T0, 0, (size_t)S * ldr * 8, st));
@@ -4237,11 +4003,8 @@ static int paths_draw_fill(bohip_paths* p, uint64_t seed) {
         HIPCHK(hipGetLastError());
         t_end(g);
         HIPCHK(hipStreamSynchronize(st));
-        return 0;
-    }();
-    hipFree(T0);
-    hipFree(T1);
-    return rc;
+    }
+    return 0;
 }
 
 int bohip_gp_paths_draw(bohip_gp* g, int64_t S, int64_t M, uint64_t seed, bohip_paths** out) {
@@ -4316,23 +4079,9 @@ int bohip_paths_eval(bohip_paths* p, const double* Xs, int64_t R, double* values
     int64_t chunk = PATHS_CHUNK;
     if (values) chunk = std::max<int64_t>(PM_ROWS, std::min<int64_t>(PATHS_CHUNK, ((int64_t)1 << 24) / p->S / PM_ROWS * PM_ROWS));
     chunk = std::min<int64_t>(chunk, round_up(R, PM_ROWS));
-    if (p->xs_cap < chunk) {
-        if (p->dXs) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dXs)); p->dXs = nullptr; p->xs_cap = 0; }
-        HIPCHK(hipMalloc(&p->dXs, (size_t)chunk * p->d * 8));
-        p->xs_cap = chunk;
-    }
-    const size_t vneed = values ? (size_t)p->S * chunk : 0;
-    if (p->v_cap < vneed) {
-        if (p->dV) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dV)); p->dV = nullptr; p->v_cap = 0; }
-        HIPCHK(hipMalloc(&p->dV, vneed * 8));
-        p->v_cap = vneed;
-    }
-    const size_t pneed = best ? (size_t)p->S * ((chunk + paths_tile(mfma) - 1) / paths_tile(mfma)) : 0;
-    if (p->part_cap < pneed) {
-        if (p->dpart) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dpart)); p->dpart = nullptr; p->part_cap = 0; }
-        HIPCHK(hipMalloc(&p->dpart, pneed * sizeof(Best)));
-        p->part_cap = pneed;
-    }
+    HIPCHK(p->dXs.reserve((size_t)chunk * p->d, st));
+    HIPCHK(p->dV.reserve(values ? (size_t)p->S * chunk : 0, st));
+    HIPCHK(p->dpart.reserve(best ? (size_t)p->S * ((chunk + paths_tile(mfma) - 1) / paths_tile(mfma)) : 0, st));
     t_reset(g);
     t_begin(g, "path_eval");
     for (int64_t j0 = 0; j0 < R; j0 += chunk) {
@@ -4359,22 +4108,10 @@ int bohip_paths_eval_grad(bohip_paths* p, const double* Xs, int64_t R, const int
     HIPCHK(hipSetDevice(g->device));
     hipStream_t st = g->stream;
     const int64_t chunk = std::min<int64_t>(PATHS_GRAD_CHUNK, R);
-    if (p->g_cap < chunk) {
-        HIPCHK(hipStreamSynchronize(st));
-        for (double** q : {&p->df, &p->dg})
-            if (*q) { HIPCHK(hipFree(*q)); *q = nullptr; }
-        if (p->dpath_of) { HIPCHK(hipFree(p->dpath_of)); p->dpath_of = nullptr; }
-        p->g_cap = 0;
-        HIPCHK(hipMalloc(&p->df, (size_t)chunk * 8));
-        HIPCHK(hipMalloc(&p->dg, (size_t)chunk * p->d * 8));
-        HIPCHK(hipMalloc(&p->dpath_of, (size_t)chunk * 8));
-        p->g_cap = chunk;
-    }
-    if (p->xs_cap < chunk) {
-        if (p->dXs) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(p->dXs)); p->dXs = nullptr; p->xs_cap = 0; }
-        HIPCHK(hipMalloc(&p->dXs, (size_t)chunk * p->d * 8));
-        p->xs_cap = chunk;
-    }
+    HIPCHK(p->df.reserve((size_t)chunk, st));
+    HIPCHK(p->dg.reserve((size_t)chunk * p->d, st));
+    HIPCHK(p->dpath_of.reserve((size_t)chunk, st));
+    HIPCHK(p->dXs.reserve((size_t)chunk * p->d, st));
     const PathArgs a = paths_args(p);
     const bool lo = fam_low(p->hp);
     t_reset(g);
@@ -4432,24 +4169,15 @@ int bohip_gp_score(bohip_gp* g, int acq_id, const double* acq_params, const doub
 // q picks from one contraction: V' of all R candidates is kept (dBV), every further pick is k_batch_cond + k_batch_final
 // (kernels_batch.hip).  All rounds are enqueued without a synchronisation; the model is not touched.
 static constexpr size_t BATCH_VT_CAP_BYTES = (size_t)8 << 30;   // V' of one call (R = 32768 at N = 10^4: 2.7 GB)
-static int ensure_batch(bohip_gp* g, int64_t R, int64_t q) {
+struct BatchWs { double* U; BatchRec* rec; BatchScal* scal; Best* wg_best; int* picked; };
+static int ensure_batch(bohip_gp* g, int64_t R, int64_t q, BatchWs* w) {
     const int64_t rows = round_up(R, TILE) + TILE;
-    if (g->dBV == nullptr || g->bv_rows < rows || g->bv_ld != g->ld) {
-        if (g->dBV) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dBV)); }
-        g->dBV = nullptr; g->bv_rows = 0;
-        const size_t bytes = (size_t)rows * g->ld * 8;
-        HIPCHK(hipMalloc(&g->dBV, bytes));
-        HIPCHK(hipMemsetAsync(g->dBV, 0, bytes, g->stream));   // padding columns (>= N) stay zero
-        g->bv_rows = rows; g->bv_ld = g->ld;
-    }
-    const size_t need = (size_t)q * rows * 8 + (size_t)q * sizeof(BatchRec) + sizeof(BatchScal) + BATCH_WG_MAX * sizeof(Best) +
-                        (size_t)rows * sizeof(int);
-    if (g->batch_bytes < need) {
-        if (g->dbatch) { HIPCHK(hipStreamSynchronize(g->stream)); HIPCHK(hipFree(g->dbatch)); }
-        g->dbatch = nullptr; g->batch_bytes = 0;
-        HIPCHK(hipMalloc(&g->dbatch, need));
-        g->batch_bytes = need;
-    }
+    bool grew = false;   // (ld never changes under a live dBV: alloc_model releases it)
+    HIPCHK(g->dBV.reserve((size_t)rows * g->ld, g->stream, Grow::Exact, &grew));
+    if (grew) HIPCHK(hipMemsetAsync(g->dBV, 0, (size_t)rows * g->ld * 8, g->stream));   // padding columns (>= N) stay zero
+    auto lay = [&](const void* base) { return layout::batch(base, (size_t)q, (size_t)rows, BATCH_WG_MAX, w); };
+    HIPCHK(g->dbatch.reserve(lay(nullptr), g->stream));
+    lay(g->dbatch);
     return 0;
 }
 
@@ -4488,16 +4216,17 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
     CHK(one_time_kernel_setup());
-    CHK(ensure_batch(g, R, q));
+    BatchWs bw;
+    CHK(ensure_batch(g, R, q, &bw));
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
     const int T = (int)(Npad / TILE);
     const KernelHyper hp = make_hyper(g);
-    double* U = reinterpret_cast<double*>(g->dbatch);
-    BatchRec* rec = reinterpret_cast<BatchRec*>(U + q * rows);
-    BatchScal* scal = reinterpret_cast<BatchScal*>(rec + q);
-    Best* wg_best = reinterpret_cast<Best*>(scal + 1);
-    int* picked = reinterpret_cast<int*>(wg_best + BATCH_WG_MAX);
+    double* U = bw.U;
+    BatchRec* rec = bw.rec;
+    BatchScal* scal = bw.scal;
+    Best* wg_best = bw.wg_best;
+    int* picked = bw.picked;
     HIPCHK(hipMemsetAsync(picked, 0, (size_t)rows * sizeof(int), g->stream));
     // round 0: the batched pass (K*' chunk -> k_trigemm_sq with V' stored), whatever R is: the other paths do not leave V' in this layout
     g->q_tiles = T;
@@ -4559,12 +4288,7 @@ int bohip_gp_score_grad(bohip_gp* g, int acq_id, const double* acq_params, const
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     CHK(ensure_xs(g, R));
-    if (g->grad_cap < R * g->d) {
-        if (g->dgrad) hipFree(g->dgrad);
-        g->dgrad = nullptr;
-        HIPCHK(hipMalloc(&g->dgrad, (size_t)R * g->d * 8));
-        g->grad_cap = R * g->d;
-    }
+    HIPCHK(g->dgrad.reserve((size_t)R * g->d, g->stream));
     double* dgrad = g->dgrad;
     const double* xin = small_candidates_in_place(g, Xs, R);
     if (!xin) HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
@@ -4595,31 +4319,24 @@ int bohip_gp_score_grad(bohip_gp* g, int acq_id, const double* acq_params, const
 }
 
 static int ensure_ascent(bohip_gp* g, int64_t R) {
-    if (g->asc_cap >= R && g->asc_block) return 0;
-    if (g->asc_block) HIPCHK(hipFree(g->asc_block));
-    if (g->asc_ints) HIPCHK(hipFree(g->asc_ints));
-    if (g->asc_hints) HIPCHK(hipHostFree(g->asc_hints));
-    g->asc_block = nullptr; g->asc_ints = nullptr; g->asc_hints = nullptr; g->asc_cap = 0;
-    const int64_t cap = std::max<int64_t>(R, 32), d = g->d, rd = cap * d;
-    HIPCHK(hipMalloc(&g->asc_block, (size_t)((9 + 2 * ASC_M) * rd + 5 * cap) * 8));
-    HIPCHK(hipMalloc(&g->asc_ints, (size_t)(4 * cap + 2 * ASC_RING + 2) * sizeof(int)));
-    HIPCHK(hipMemset(g->asc_ints, 0, (size_t)(4 * cap + 2 * ASC_RING + 2) * sizeof(int)));
-    HIPCHK(hipHostMalloc((void**)&g->asc_hints, (size_t)(2 * cap + ASC_RING) * sizeof(int), hipHostMallocDefault));
-    std::memset(g->asc_hints, 0, (size_t)(2 * cap + ASC_RING) * sizeof(int));
-    if (!g->asc_bounds) HIPCHK(hipMalloc(&g->asc_bounds, (size_t)3 * DMAX * 8));
-    if (!g->asc_best) HIPCHK(hipMalloc(&g->asc_best, sizeof(Best)));
-    double* p = g->asc_block;
+    HIPCHK(g->asc_bounds.reserve((size_t)3 * DMAX, g->stream));
+    HIPCHK(g->asc_best.reserve(1, g->stream));
+    if (g->asc_rows >= R && g->asc_block && g->asc_ints && g->asc_hints) return 0;
+    // the three blocks behind asc are laid out for `cap` starts (at least 32) and re-made together
+    const size_t cap = (size_t)std::max<int64_t>(R, 32);
     AscentState& a = g->asc;
-    a.X = p; p += rd; a.G = p; p += rd; a.Xt = p; p += rd; a.Gt = p; p += rd; a.Xn = p; p += rd; a.Gn = p; p += rd;
-    a.D = p; p += rd; a.Gp = p; p += rd; a.best_X = p; p += rd;
-    a.S = p; p += ASC_M * rd; a.Y = p; p += ASC_M * rd;
-    a.f = p; p += cap; a.ft = p; p += cap; a.fn = p; p += cap; a.step = p; p += cap; a.best_f = p; p += cap;
-    a.active = g->asc_ints; a.accepted = g->asc_ints + cap;
-    a.h_accepted = g->asc_hints; a.h_active = g->asc_hints + cap;
-    a.it = g->asc_ints + 2 * cap; a.bt = g->asc_ints + 3 * cap;
-    a.nact = reinterpret_cast<unsigned*>(g->asc_ints + 4 * cap); a.ticket = a.nact + 2 * ASC_RING;
-    a.h_cnt = g->asc_hints + 2 * cap;
-    g->asc_cap = cap;
+    g->asc_rows = 0;
+    const size_t nd = layout::ascent_doubles(nullptr, cap, (size_t)g->d, ASC_M, &a), ni = layout::ascent_words(nullptr, cap, ASC_RING, &a),
+                 nh = layout::ascent_pinned(nullptr, cap, ASC_RING, &a);
+    HIPCHK(g->asc_block.reserve(nd, g->stream));
+    HIPCHK(g->asc_ints.reserve(ni, g->stream));
+    HIPCHK(g->asc_hints.reserve(nh, g->stream));
+    HIPCHK(hipMemset(g->asc_ints, 0, ni));
+    std::memset(g->asc_hints, 0, nh);
+    layout::ascent_doubles(g->asc_block, cap, (size_t)g->d, ASC_M, &a);
+    layout::ascent_words(g->asc_ints, cap, ASC_RING, &a);
+    layout::ascent_pinned(g->asc_hints, cap, ASC_RING, &a);
+    g->asc_rows = (int64_t)cap;
     return 0;
 }
 
@@ -4656,13 +4373,9 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
     // one pinned block in ([lb | ub | starts]), one pinned block out (k_asc_final's packed result): seven pageable copies were ~0.1 ms
     // of a call that is 1.3 ms at N = 3000 since the search needs 17 passes instead of 228
     const size_t n_in = (size_t)(2 + R) * d, n_out = (size_t)2 + d + R + (size_t)R * d + R, n_io = std::max(n_in, n_out);
-    if (n_io > g->asc_io_cap) {
-        if (g->asc_hio) HIPCHK(hipHostFree(g->asc_hio));
-        if (g->asc_dio) HIPCHK(hipFree(g->asc_dio));
-        g->asc_hio = nullptr; g->asc_dio = nullptr; g->asc_io_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&g->asc_hio, n_io * 2 * 8, hipHostMallocDefault));
-        HIPCHK(hipMalloc(&g->asc_dio, n_io * 2 * 8));
-        g->asc_io_cap = n_io * 2;
+    if (n_io > g->asc_hio.capacity() || n_io > g->asc_dio.capacity()) {   // (room for twice the call that grows them)
+        HIPCHK(g->asc_hio.reserve(n_io * 2, g->stream));
+        HIPCHK(g->asc_dio.reserve(n_io * 2, g->stream));
     }
     std::memcpy(g->asc_hio, lb, (size_t)d * 8);
     std::memcpy(g->asc_hio + d, ub, (size_t)d * 8);
@@ -4948,8 +4661,8 @@ int bohip_acq_eval(int acq_id, const double* acq_params, int64_t n, const double
     if (n > (int64_t)1 << 31) return fail(BOHIP_E_UNSUPPORTED, "acq_eval: more than 2^31 elements");
     if (bohip_device_count() <= 0) return fail(BOHIP_E_NODEVICE, "no HIP device visible; libbohip has no CPU fallback");
     const int nout = dmu ? 3 : 1;
-    double* buf = nullptr;
-    HIPCHK(hipMalloc(&buf, (size_t)n * 8 * (2 + nout)));
+    DBuf<double> buf;   // (freed when the call leaves)
+    HIPCHK(buf.reserve((size_t)n * (2 + nout), (hipStream_t)0));
     double *d_mu = buf, *d_var = buf + n, *d_val = buf + 2 * n, *d_dmu = dmu ? buf + 3 * n : nullptr, *d_dvar = dmu ? buf + 4 * n : nullptr;
     hipError_t e = hipMemcpy(d_mu, mu, (size_t)n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_var, var, (size_t)n * 8, hipMemcpyHostToDevice);
@@ -4960,7 +4673,6 @@ int bohip_acq_eval(int acq_id, const double* acq_params, int64_t n, const double
     if (e == hipSuccess) e = hipMemcpy(value, d_val, (size_t)n * 8, hipMemcpyDeviceToHost);   // (blocking: waits for the kernel)
     if (e == hipSuccess && dmu) e = hipMemcpy(dmu, d_dmu, (size_t)n * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess && dmu) e = hipMemcpy(dvar, d_dvar, (size_t)n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(BOHIP_E_HIP, std::string("acq_eval: ") + hipGetErrorString(e));
     return 0;
 }
@@ -4973,12 +4685,7 @@ int bohip_gp_thompson(bohip_gp* g, const double* Xs, int64_t R, int64_t S, uint6
     CHK(ensure_score_scratch(g, R));
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     CHK(score_core(g, BOHIP_ACQ_MAXMEAN, nullptr, g->dXs, R, g->dmu, g->dvar, nullptr, nullptr));
-    if (g->thompson_cap < S) {
-        if (g->dthompson) hipFree(g->dthompson);
-        g->dthompson = nullptr;
-        HIPCHK(hipMalloc(&g->dthompson, S * sizeof(Best)));
-        g->thompson_cap = S;
-    }
+    CHK(ensure_thompson(g, S));
     Best* dout = g->dthompson;
     t_begin(g, "thompson");
     hipLaunchKernelGGL(k_thompson, dim3(S), dim3(256), 0, g->stream, g->dmu, g->dvar, R, seed, j0, dout, 0ll);
@@ -5140,6 +4847,12 @@ int64_t bohip_debug_exec_tasks(int T, int64_t ld, uint64_t base_L, uint64_t base
 }
 // tools only (tools/trace_trigemm.py): the row pieces k_trigemm_sq runs for T row tiles with the alpha row at alpha_row, in issue order
 // (piece = rt | mode << 16, see kernels_score.hip); returns their number
+// tests: the bytes the process's buffers hold (devbuf.h), kind 0 device memory, 1 pinned host memory
+int bohip_debug_live_bytes(int kind, int64_t* out) {
+    if ((kind != devbuf::DEVICE && kind != devbuf::PINNED) || !out) return fail(BOHIP_E_ARG, "bad arguments");
+    *out = devbuf::g_live_bytes[kind].load();
+    return 0;
+}
 int bohip_debug_trigemm_pieces(int T, int64_t alpha_row, int* out, int cap) {
     one_time_kernel_setup();
     std::vector<int> ps;
@@ -5241,7 +4954,7 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
 // tests only: round 2's list length of the handle's last pruned call (the pinned word prune_wanted reads; 0 after a backoff), -1: none yet
 int64_t bohip_debug_prune_stat(bohip_gp* g) {
     if (!g || !g->hprune_stat) return -1;
-    return (int64_t)__atomic_load_n(g->hprune_stat, __ATOMIC_RELAXED);
+    return (int64_t)__atomic_load_n(g->hprune_stat.get(), __ATOMIC_RELAXED);
 }
 // tests only: round 2's form in the handle's pruned calls -- -1 the library's rule, 0 the steady form (one launch), 1 the long form
 int bohip_debug_prune_round2_form(bohip_gp* g, int form) {
@@ -5255,7 +4968,7 @@ int bohip_debug_kstar_poison(bohip_gp* g) {
     if (!g) return fail(BOHIP_E_ARG, "bad arguments");
     HIPCHK(hipSetDevice(g->device));
     if (g->dKsT) HIPCHK(hipMemsetAsync(g->dKsT, 0xff, (size_t)(g->kst_rows + TILE) * g->ld * 8, g->stream));
-    if (g->dpr && g->pr_ks_bytes) HIPCHK(hipMemsetAsync(g->dpr, 0xff, std::min(g->pr_ks_bytes, g->pr_bytes), g->stream));
+    if (g->dpr && g->pr_ks_len) HIPCHK(hipMemsetAsync(g->dpr, 0xff, std::min(g->pr_ks_len, g->dpr.capacity()), g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     return 0;
 }

@@ -617,15 +617,9 @@ int bohip_comm_unique_id(void* id, int64_t nbytes) {
 }
 
 static int comm_ensure_records(bohip_gp* g, int64_t S) {
-    if (g->crec_cap >= S) return 0;
-    if (g->csend) HIPCHK(hipFree(g->csend));
-    if (g->crecv) HIPCHK(hipFree(g->crecv));
-    if (g->cfinal) HIPCHK(hipFree(g->cfinal));
-    g->csend = g->crecv = g->cfinal = nullptr; g->crec_cap = 0;
-    HIPCHK(hipMalloc(&g->csend, (size_t)S * sizeof(Best)));
-    HIPCHK(hipMalloc(&g->crecv, (size_t)g->comm_n * S * sizeof(Best)));
-    HIPCHK(hipMalloc(&g->cfinal, (size_t)S * sizeof(Best)));
-    g->crec_cap = S;
+    HIPCHK(g->csend.reserve((size_t)S, g->stream));
+    HIPCHK(g->crecv.reserve((size_t)g->comm_n * S, g->stream));
+    HIPCHK(g->cfinal.reserve((size_t)S, g->stream));
     return 0;
 }
 
@@ -650,9 +644,7 @@ int bohip_gp_comm_destroy(bohip_gp* g) {
     HIPCHK(hipStreamSynchronize(g->stream));
     if (rccl_api()) rccl_api()->CommDestroy((ncclComm_t)g->comm);
     g->comm = nullptr; g->comm_n = 0; g->comm_rank = 0;
-    for (Best** p : {&g->csend, &g->crecv, &g->cfinal})
-        if (*p) { hipFree(*p); *p = nullptr; }
-    g->crec_cap = 0;
+    for (DBuf<Best>* b : {&g->csend, &g->crecv, &g->cfinal}) b->release();
     return 0;
 }
 
