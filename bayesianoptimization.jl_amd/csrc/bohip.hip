@@ -12,6 +12,8 @@
 //   dS  [ld][ld]    scratch: solved panels during the factorisation, S' blocks during the recursive inverse,
 //                   cK^-1 for the marginal-likelihood gradient
 //   dKsT [Rc][ld]   cross-covariance chunk, candidate-major
+// A posterior pass is planned once (PassPlan, choose_route) and the plan travels by argument; every whole-K pass is chunk_pass.  The handle keeps
+// records of the last call and state that outlives a call, never the plan of a call in flight (DESIGN.md "Who owns the plan of a pass").
 // There is NO CPU fallback: every entry point that computes fails with BOHIP_E_NODEVICE / BOHIP_E_HIP
 // when the GPU is unavailable.
 #include "../../include/bohip.h"
@@ -153,7 +155,7 @@ struct bohip_gp : gp_streams {
     int n_pieces = 0, pieces_T = -1;
     int64_t pieces_alpha = -1;
     int64_t kst_rows = 0;        // rows the K*' chunk buffer holds
-    int64_t chunk_now = 0;       // candidates per K*' chunk of the current call (chunk_rows(R) <= kst_rows)
+    int64_t score_chunk = 0;     // a record (BOHIP_INFO_SCORE_CHUNK): the chunk the scratch was last sized for; a pass takes its chunk from its own PassPlan
     int64_t score_launches = 0;  // k_trigemm_sq launches of the last posterior pass (BOHIP_INFO_SCORE_LAUNCHES)
     DBuf<double> dVT, dUT;  // gradient path: V' and U' = V' W chunks, candidate-major
     DBuf<double> dq, dmu_raw, dXs, dmu, dvar, dscore;
@@ -180,9 +182,6 @@ struct bohip_gp : gp_streams {
     double asc_maxtime = 0.0;    // bohip_gp_set_maxtime: wall-clock budget of one acquire_max call in seconds (NLopt maxtime), 0 = none
     int64_t batch_hint = 0;      // bohip_gp_set_batch_hint: choose the scoring path as if the batch had at least this many candidates
     DBuf<double> dsplit;         // split-K partial planes (batches of a few hundred candidates)
-    const SmallFold* asc_fold = nullptr;   // set around a pass of the free-running ascent: the step this pass's gradient kernel may run in its last workgroup
-    bool asc_fold_done = false;            // ... and whether it took it (small_pass_mfma: one pass of <= 16 candidates, d <= 16); else k_asc_step follows
-    const unsigned* asc_go = nullptr;   // set around the passes of the free-running ascent: the pass's big kernels return at once when the word is 0
     DBuf<double> dgparts;        // [SMALL_MAX][16][2 DMAX] split partial sums of k_grad_finish (small batches)
     DBuf<unsigned> dgcount;      // per-candidate arrival counters (left at zero by the kernel)
     // round 5: the small-batch pass as two MFMA kernels (kernels_small.hip): one scratch block [part | v16 | qpart | mupart | post | fstash | gpart]
@@ -191,7 +190,8 @@ struct bohip_gp : gp_streams {
     int sm_cnt_T = 0;   // row tiles the counters are laid out for
     // pinned, device-visible host block the kernels of a small batch (R <= SMALL_R) write their results into: the
     // 2-3 device-to-host copies of a call cost more than its kernels (each ~8 us of API + DMA set-up)
-    HBuf<double> hpin;           // [score 32 | mu 32 | var 32 | best 2 | grad 32 DMAX | candidates of a small host call 32 DMAX]
+    HBuf<double> hpin;           // layout::pinned_small, made once by bohip_gp_create (null: the small batches take the copies)
+    layout::PinnedSmall pin{};   // its areas (all null without the block)
     DBuf<double> dschur;         // [APPEND_PMAX][APPEND_PMAX] Schur complement of an append of >= 3 rows (k_schur_dots)
     // lock-step L-BFGS ascent of acquire_max (kernels_ascent.hip)
     AscentState asc{};
@@ -257,7 +257,6 @@ struct bohip_gp : gp_streams {
     int jitter_tries = 0;              // 0 = report BOHIP_E_NOTPD at once (the default)
     int jitter_steps_last = 0;         // BOHIP_INFO_JITTER_STEPS: tries the last refit needed (0: none)
     double jitter_last = 0.0;          // what it added to the diagonal
-    int q_tiles = 0;  // row tiles behind dq after the last posterior pass (two partial sums each); 0: dq[r] is the finished sum (row-wise / split-K paths)
     bool timing = false;
     bool t_open = false;
     bool timing_dominant_only = false;   // enable_timing(2): only the dominant kernel (k_trigemm_sq) is bracketed by events
@@ -556,16 +555,11 @@ static int compute_alpha(bohip_gp* g) {
 }
 
 static int check_info(bohip_gp* g) {
-    int info = 0;
-    if (g->hpin) {     // through the pinned block: a plain DMA command (a pageable destination is staged by the runtime)
-        int* pw = reinterpret_cast<int*>(g->hpin + 3 * SMALL_R) + 1;
-        HIPCHK(hipMemcpyAsync(pw, g->dinfo, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-        info = *pw;
-    } else {
-        HIPCHK(hipMemcpyAsync(&info, g->dinfo, sizeof(int), hipMemcpyDeviceToHost, g->stream));
-        HIPCHK(hipStreamSynchronize(g->stream));
-    }
+    int local = 0;
+    int* const pw = g->hpin ? g->pin.words + 1 : &local;   // through the pinned block: a plain DMA command (a pageable destination is staged by the runtime)
+    HIPCHK(hipMemcpyAsync(pw, g->dinfo, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    const int info = *pw;
     if (info != 0) {
         g->pivot = info;
         g->stale = true;
@@ -1364,7 +1358,7 @@ static int refit_once(bohip_gp* g, double jitter) {
         // the abort word and the pivot word come back through the pinned block behind the kernels: ONE host round trip per refit (three before:
         // this synchronisation, a blocking copy of the abort word, check_info's copy + synchronisation -- ~25 us of a 1.5 ms refit)
         unsigned aborted = 0;
-        int* const pwords = g->hpin ? reinterpret_cast<int*>(g->hpin + 3 * SMALL_R) : nullptr;
+        int* const pwords = g->pin.words;   // (null without the pinned block)
         if (pwords) {
             HIPCHK(hipMemcpyAsync(pwords, g->dchol_flags + chol_abort_word(T), sizeof(unsigned), hipMemcpyDeviceToHost, g->stream));
             HIPCHK(hipMemcpyAsync(pwords + 1, g->dinfo, sizeof(int), hipMemcpyDeviceToHost, g->stream));
@@ -1463,7 +1457,7 @@ static int launch_rows_trimv(bohip_gp* g, const double* W, int64_t N0, const dou
     const int64_t nblk = (N0 + 7) / 8;
     const unsigned wgs = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::max(device_cus(), 1), nblk));
     hipLaunchKernelGGL(k_trimv_stream<TRIMV_D>, dim3(wgs, (unsigned)((P + 15) / 16)), dim3(TRIMV_THREADS), trimv_lds_bytes(TRIMV_D), g->stream,
-                       W, g->ld, N0, rows, g->ld, P, out, g->ld, upper, (const unsigned*)g->asc_go);
+                       W, g->ld, N0, rows, g->ld, P, out, g->ld, upper, (const unsigned*)nullptr);   // (no go word: never part of an ascent pass)
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1559,7 +1553,7 @@ static int ensure_score_scratch(bohip_gp* g, int64_t R) {
     const int64_t Rpad = round_up(std::max<int64_t>(R, 1), TILE);
     const int64_t T = g->ld / TILE;
     const int64_t rc = chunk_rows(g, R);
-    g->chunk_now = rc;
+    g->score_chunk = rc;
     const int64_t SLACK = TILE;  // head-room so tile-granular writes past the last candidate stay inside the buffers
     const hipStream_t st = g->stream;
     bool grew = false;
@@ -1591,6 +1585,26 @@ static int ensure_xs(bohip_gp* g, int64_t R) {
     HIPCHK(g->dXs.reserve(std::max<size_t>(1, (size_t)R * g->d), g->stream));
     return 0;
 }
+
+// ---- the plan of a posterior pass: values made once per pass and handed down, never left on the handle --------------------------
+// The sizes every launch of a pass is written in.  Rpad: one tile of head-room for tile-granular writes (dq's leading dimension).
+struct PassDims { int64_t N, Npad, R, Rpad, ld; int T; };
+static int row_tiles(const bohip_gp* g) { return (int)(round_up(g->n + 1, TILE) / TILE); }   // T: the observations and the alpha row
+static PassDims pass_dims(const bohip_gp* g, int64_t R) {
+    const int T = row_tiles(g);
+    return PassDims{g->n, (int64_t)T * TILE, R, round_up(R, TILE) + TILE, g->ld, T};
+}
+struct SplitPlan { int kz = 0, nsl = 0; };
+enum class Route { Small, Split, Pruned, WholeK };   // small_pass_mfma, split_posterior, pruned_pass, chunk_pass
+struct PassPlan {
+    PassDims dm{};
+    Route route = Route::WholeK;
+    SplitPlan sp;        // Route::Split
+    int prune_m = 0;     // Route::Pruned: row tiles of the bounding prefix
+    int64_t chunk = 0;   // candidates per K*' chunk (chunk_rows)
+    // row tiles behind dq once the pass has run (two partial sums each); 0: dq[r] is the finished sum -- what k_score is told
+    int dq_tiles() const { return route == Route::WholeK || route == Route::Pruned ? dm.T : 0; }
+};
 
 // kp (the pruned pass): the kernel also leaves the per-wave partial sums of alpha_j K*'_j and of its absolute value (always 16
 // candidates per block: the halving reduction is written for 16)
@@ -1645,31 +1659,61 @@ static int ensure_clk(bohip_gp* g) {
     return 0;
 }
 // V = W K* with the fused epilogue (k_trigemm_sq): one launch per K*' chunk.
-static int launch_trigemm(bohip_gp* g, int T, int64_t ncand, int64_t N, int64_t Rpad, int64_t r0, double* VT,
-                          FuseParams fz = FuseParams{}) {
+static int launch_trigemm(bohip_gp* g, const PassDims& dm, int64_t r0, int64_t ncand, double* VT, FuseParams fz) {
     const int CT = (int)((ncand + CTILE - 1) / CTILE), n_local = (CT + 7) / 8;
-    CHK(ensure_pieces(g, T, N));
+    CHK(ensure_pieces(g, dm.T, dm.N));
     const int NP = g->n_pieces;
-    fz.T = T;
+    fz.T = dm.T;
     if (g->timing) {   // core clock under the dominant kernel (BOHIP_INFO_KERNEL_CLOCK_MHZ)
         CHK(ensure_clk(g));
         fz.clk = g->dclk;
     }
     hipLaunchKernelGGL(k_trigemm_sq, dim3(8 * n_local * NP), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, g->dW, g->ld,
-                       g->dKsT, g->ld, g->dpieces, NP, CT, N, g->dq, Rpad, g->dmu_raw, r0, VT, g->ld, fz);
+                       g->dKsT, g->ld, g->dpieces, NP, CT, dm.N, g->dq, dm.Rpad, g->dmu_raw, r0, VT, g->ld, fz);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// posterior pass over all R candidates: fills dq (partials) and dmu_raw.  VT optional (chunk-local).
-template <int DT>
-static void launch_kstar(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp, const KstarParts* kp);
 static int launch_kstar_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, int64_t Npad, const KernelHyper& hp,
                             const KstarParts* kp = nullptr) {
     dispatch_dt(g->d, [&](auto dt) { launch_kstar<decltype(dt)::value>(g, dXs, r0, r1, Npad, hp, kp); });
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+static int launch_gemm_u(bohip_gp* g, const PassDims& dm, int CT) {
+    GemmNTParams p{};  // U'[r][j] = sum_i V'[r][i] W'[j][i] for the chunk's CT candidate tiles, dVT -> dUT  (B = W' upper-triangular: i >= j)
+    p.A = g->dVT; p.lda = dm.ld; p.B = g->dWT; p.ldb = dm.ld; p.C = g->dUT; p.ldc = dm.ld;
+    p.mt = CT; p.nt64 = 2 * dm.T; p.kc = dm.T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.klo_from_n = 1;
+    return launch_gemm_nt(g, p);
+}
+
+// THE chunk loop, every whole-K pass: per chunk of pl.chunk candidates K*' -> k_trigemm_sq (dq's partials, dmu_raw; fz: its fused
+// finish) [-> U' = V' W] -> finish(r0, r1).  V' is stored when v.VT is set: chunk-local (row_stride 0: dVT, which want_u needs) or for
+// all candidates (chunk r0 at VT + r0 * row_stride: select_batch).  Returns the number of chunks, or the error code (< 0).
+struct ChunkV { double* VT = nullptr; int64_t row_stride = 0; };
+template <class Finish>
+static int64_t chunk_pass(bohip_gp* g, const PassPlan& pl, const double* dXs, const KernelHyper& hp, ChunkV v, bool want_u, const FuseParams& fz, Finish&& finish) {
+    const PassDims& dm = pl.dm;
+    int64_t chunks = 0;
+    for (int64_t r0 = 0; r0 < dm.R; r0 += pl.chunk, ++chunks) {
+        const int64_t r1 = std::min(dm.R, r0 + pl.chunk);
+        t_begin(g, "kstar");
+        CHK(launch_kstar_any(g, dXs, r0, r1, dm.Npad, hp));
+        t_end(g);
+        t_begin(g, v.VT ? "trigemm_sq+V" : "trigemm_sq");
+        CHK(launch_trigemm(g, dm, r0, r1 - r0, v.VT ? v.VT + r0 * v.row_stride : nullptr, fz));
+        t_end(g);
+        if (want_u) {
+            t_begin(g, "gemm_U");
+            CHK(launch_gemm_u(g, dm, (int)((r1 - r0 + TILE - 1) / TILE)));
+            t_end(g);
+        }
+        CHK(finish(r0, r1));
+    }
+    return chunks;
+}
+static int no_finish(int64_t, int64_t) { return 0; }
 
 // k_grad_finish with the observations split over workgroups: the splits' partial sums and the arrival counter of every candidate
 static int ensure_small_counters(bohip_gp* g) {
@@ -1725,9 +1769,15 @@ static void launch_small_pass_g(bohip_gp* g, int G, const SmallCommon& sc, const
     }
     launch_small_pass<DT, 4>(g, sc, scu, sv, su, hp, npass);
 }
+// What a pass of the free-running ascent (bohip_gp_acquire_max) asks of the gradient pass it rides on; empty for everybody else.
+struct AscPass {
+    const SmallFold* fold = nullptr;   // the ascent step this pass's gradient kernel may run in its last workgroup
+    const unsigned* go = nullptr;      // the pass's big kernels return at once when the word is 0 (active start points: the adopt kernel and every step write it)
+    bool* folded = nullptr;            // out: set when the step was taken (one pass of <= 16 candidates, d <= 16); else k_asc_step follows
+};
 // all R <= SMALL_MAX candidates: values (mu, sigma^2, score, arg-max record) and, with d_grad, the gradient of the score
 static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqParams& ap, double* d_mu, double* d_var, double* d_score,
-                           Best* d_best, int64_t best_off, double* d_grad) {
+                           Best* d_best, int64_t best_off, double* d_grad, const AscPass& asc = AscPass{}) {
     const int N = (int)g->n, T = (N + TILE - 1) / TILE, P = (int)R, npass = (P + 15) / 16,
               DTm = dispatch_dt(g->d, [](auto dt) { return decltype(dt)::value; });
     // chunks per tile: every tile's partial sums cost one 16-KiB write and one read by the block's finisher, a column block's finisher adds up
@@ -1753,7 +1803,7 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
     const KernelHyper hp = make_hyper(g);
     SmallCommon sc{};
     sc.A = g->dWT; sc.ld = g->ld; sc.N = N; sc.T = T; sc.m = m; sc.P = P; sc.part = ws.part; sc.ntiles = ntiles; sc.cnt = g->dsm_cnt;
-    sc.X = g->dX; sc.Xs = dXs; sc.alpha = g->dalpha; sc.go = (const unsigned*)g->asc_go;
+    sc.X = g->dX; sc.Xs = dXs; sc.alpha = g->dalpha; sc.go = asc.go;
 #ifdef BOHIP_SMALL_TRACE
     if (!g_small_trace) { HIPCHK(hipMalloc(&g_small_trace, 8192 * 16 * 8)); }
     HIPCHK(hipMemsetAsync(g_small_trace, 0, 8192 * 16 * 8, g->stream));
@@ -1769,9 +1819,9 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
     SmallU su{};
     sv.ks16 = ws.ks16;
     su.v16 = sv.v16; su.sv = sv; su.gpart = ws.gpart; su.gmpart = ws.gmpart; su.grad = d_grad;
-    if (g->asc_fold && d_grad && npass == 1 && g->d <= 16 && 16 * ((g->d + 1) / 2) <= SP_THREADS - 128) {
-        su.fold = *g->asc_fold;
-        g->asc_fold_done = true;
+    if (asc.fold && d_grad && npass == 1 && g->d <= 16 && 16 * ((g->d + 1) / 2) <= SP_THREADS - 128) {
+        su.fold = *asc.fold;
+        if (asc.folded) *asc.folded = true;
     }
     const SmallU* sup = d_grad ? &su : nullptr;
     SmallCommon scu = sc;       // the U pass: W itself (contraction k >= c), its own partial planes and counters
@@ -1781,41 +1831,17 @@ static int small_pass_mfma(bohip_gp* g, const double* dXs, int64_t R, const AcqP
     dispatch_dt(g->d, [&](auto dt) { launch_small_pass_g<decltype(dt)::value>(g, G, sc, scu, sv, sup, hp, npass); });
     HIPCHK(hipGetLastError());
     t_end(g);
-    g->q_tiles = 0;
-    return 0;
-}
-
-static int posterior_pass(bohip_gp* g, const double* dXs, int64_t R, const FuseParams& fz = FuseParams{}) {
-    CHK(one_time_kernel_setup());
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE;  // +TILE: head-room for tile-granular writes
-    const int T = (int)(Npad / TILE);
-    g->q_tiles = T;
-    const KernelHyper hp = make_hyper(g);
-    const int64_t rc = g->chunk_now;
-    g->score_launches = 0;
-    for (int64_t r0 = 0; r0 < R; r0 += rc) {
-        const int64_t r1 = std::min(R, r0 + rc);
-        ++g->score_launches;
-        t_begin(g, "kstar");
-        CHK(launch_kstar_any(g, dXs, r0, r1, Npad, hp));
-        t_end(g);
-        t_begin(g, "trigemm_sq");
-        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, nullptr, fz));
-        t_end(g);
-    }
     return 0;
 }
 
 // ---- split-K posterior for batches too small to fill the chip with whole-K jobs (see k_split_combine_v) -----------
-struct SplitPlan { int kz = 0, nsl = 0; };
 static bool split_applicable(const bohip_gp* g) {
-    return g_split && round_up(g->n + 1, TILE) / TILE >= 8;   // short K extents gain nothing
+    return g_split && row_tiles(g) >= 8;   // short K extents gain nothing
 }
 static SplitPlan split_plan(const bohip_gp* g, int64_t R) {
     SplitPlan sp;
     if (!split_applicable(g)) return sp;
-    const int64_t Npad = round_up(g->n + 1, TILE);
-    const int T = (int)(Npad / TILE);
+    const int T = pass_dims(g, R).T;
     const int64_t CT64 = (path_R(g, R) + CTILE - 1) / CTILE;
     if (CT64 * T >= 512) return sp;                     // enough whole-K jobs for every workgroup slot
     const int units = std::max(2, (T + 7) / 8);         // 128-wide K units per slice
@@ -1830,10 +1856,11 @@ static SplitPlan split_plan(const bohip_gp* g, int64_t R) {
     sp.kz = kz; sp.nsl = nsl;
     return sp;
 }
-static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const SplitPlan& sp, bool want_u) {
+static int split_posterior(bohip_gp* g, const double* dXs, const PassPlan& pl, bool want_u) {
     CHK(one_time_kernel_setup());
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), ld = g->ld, Rc = round_up(R, TILE);
-    const int T = (int)(Npad / TILE);
+    const SplitPlan& sp = pl.sp;
+    const int64_t N = pl.dm.N, Npad = pl.dm.Npad, ld = pl.dm.ld, R = pl.dm.R, Rc = round_up(R, TILE);
+    const int T = pl.dm.T;
     const KernelHyper hp = make_hyper(g);
     HIPCHK(g->dsplit.reserve((size_t)sp.nsl * Rc * ld, g->stream));
     if (want_u) CHK(ensure_grad_scratch(g));
@@ -1851,7 +1878,6 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
                        g->dmu_raw, want_u ? g->dVT : nullptr, ld);
     HIPCHK(hipGetLastError());
     t_end(g);
-    g->q_tiles = 0;
     if (want_u) {
         t_begin(g, "split_U");
         GemmNTParams u{};   // partial U'[r][j] = sum over the slice's i of V'[r][i] W'[j][i]   (B = W' upper-triangular: i >= j)
@@ -1866,6 +1892,18 @@ static int split_posterior(bohip_gp* g, const double* dXs, int64_t R, const Spli
         t_end(g);
     }
     return 0;
+}
+
+// The posterior of a planned Split or WholeK pass (with want_u also U' in dUT), then finish(r0, r1) per chunk; split-K is one "chunk".
+template <class Finish>
+static int posterior_then(bohip_gp* g, const PassPlan& pl, const double* dXs, const KernelHyper& hp, bool want_u, Finish&& finish) {
+    if (pl.route == Route::Split) {
+        CHK(split_posterior(g, dXs, pl, want_u));
+        return finish(0, pl.dm.R);
+    }
+    if (want_u) CHK(ensure_grad_scratch(g));
+    const int64_t chunks = chunk_pass(g, pl, dXs, hp, ChunkV{want_u ? g->dVT.get() : nullptr, 0}, want_u, FuseParams{}, finish);
+    return chunks < 0 ? (int)chunks : 0;
 }
 
 // ---- pruned arg-max: value-only calls (kernels_score.hip, "pruned arg-max") ---------------------------------------------------
@@ -1959,7 +1997,7 @@ static int launch_phase_a(bohip_gp* g, const double* KsT, const int* jobs, int N
 // candidates, k_trigemm_rows up to it, k_prune_finish.  No host round trip: the lists and their lengths stay on the device and the
 // surplus workgroups leave at once.
 // ub_host (tests, bohip_debug_prune_bounds): stop after the bounds and copy them out.
-static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const AcqParams& ap, Best* d_best, int64_t best_off,
+static int pruned_pass(bohip_gp* g, const double* dXs, const PassPlan& pl, const AcqParams& ap, Best* d_best, int64_t best_off,
                        double* ub_host = nullptr, bool long_form = false) {
     CHK(one_time_kernel_setup());
     {
@@ -1967,8 +2005,8 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
         HIPCHK(g->hprune_stat.reserve(16, g->stream, Grow::Exact, &grew));
         if (grew) g->hprune_stat[0] = 0u;
     }
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
-    const int T = (int)(Npad / TILE);
+    const int64_t N = pl.dm.N, Npad = pl.dm.Npad, R = pl.dm.R, Rpad = pl.dm.Rpad, ld = pl.dm.ld;
+    const int T = pl.dm.T, m = pl.prune_m;
     const int64_t P = Npad / 64;   // k_kstar's partial sums: one per wave of observations
     CHK(ensure_pieces(g, T, N));
     // phase A runs 64-row jobs that write no mu: no piece of the prefix may be a solo half or hold the alpha row
@@ -1989,7 +2027,6 @@ static int pruned_pass(bohip_gp* g, const double* dXs, int64_t R, int m, const A
     unsigned* cnt = ws.cnt;
     Best* rec = static_cast<Best*>(ws.rec);
     if (g->timing) CHK(ensure_clk(g));
-    g->q_tiles = T;
     g->score_launches = 1;
     const KernelHyper hp = make_hyper(g);
     // K*' first: it needs none of the job tables, and the device has nothing else to do while the host builds them
@@ -2086,6 +2123,25 @@ static bool prune_wanted(bohip_gp* g, int64_t R) {
     return true;
 }
 
+// The route of a pass over R candidates, chosen ONCE.  The caller says what it can take: the small pass, the split-K posterior (neither
+// where V' must come in the chunk layout), and pruning -- Value: a call that wants the record alone; not for shards of a larger set
+// (batch_hint); prune_wanted (the back-off: side effects) is asked last.  Probe: "would this size prune?", no hint, no back-off.
+enum class Prune { No, Value, Probe };
+struct RouteWants { bool small = true, split = true; Prune prune = Prune::No; };
+static constexpr RouteWants WHOLE_K_ONLY{false, false, Prune::No};
+static PassPlan choose_route(bohip_gp* g, int64_t R, RouteWants w) {
+    PassPlan pl;
+    pl.dm = pass_dims(g, R); pl.chunk = chunk_rows(g, R);
+    if (w.small && path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) pl.route = Route::Small;
+    else if (w.split && (pl.sp = split_plan(g, R)).nsl > 0) pl.route = Route::Split;
+    else if (const int m = w.prune != Prune::No ? prune_tiles(pl.dm.T) : 0;
+             m > 0 && R <= PRUNE_R_MAX && R <= pl.chunk && (w.prune == Prune::Probe || (g->batch_hint == 0 && prune_wanted(g, R)))) {
+        pl.route = Route::Pruned;
+        pl.prune_m = m;
+    }
+    return pl;
+}
+
 // best_off: added to the winner's index (a shard of a larger candidate set reports GLOBAL columns)
 static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const double* dXs, int64_t R, double* d_mu,
                       double* d_var, double* d_score, Best* d_best, int64_t best_off = 0) {
@@ -2094,31 +2150,29 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
     CHK(ensure_score_scratch(g, R));
     AcqParams ap;
     CHK(make_acq(acq_id, acq_params, &ap));
-    if (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) {   // small batches: scoring and arg-max ride on the pass's own kernel
+    const bool record_only = d_best && !d_mu && !d_var && !d_score;
+    const PassPlan pl = choose_route(g, R, RouteWants{true, true, record_only ? Prune::Value : Prune::No});
+    if (pl.route == Route::Small) {   // small batches: scoring and arg-max ride on the pass's own kernel
         CHK(one_time_kernel_setup());
         return small_pass_mfma(g, dXs, R, ap, d_mu, d_var, d_score, d_best, best_off, nullptr);
     }
-    const SplitPlan sp = split_plan(g, R);
-    if (sp.nsl > 0) {   // a few hundred candidates: split-K posterior, then scoring and arg-max as launches of their own
-        CHK(split_posterior(g, dXs, R, sp, false));
-        const int64_t Rpad = round_up(R, TILE) + TILE;
+    if (pl.route == Route::Split) {   // a few hundred candidates: split-K posterior, then scoring and arg-max as launches of their own
+        CHK(split_posterior(g, dXs, pl, false));
         const int nb = (int)((R + 255) / 256);
         t_begin(g, "score");
-        hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, g->q_tiles, g->dmu_raw, R,
+        hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, pl.dm.Rpad, pl.dq_tiles(), g->dmu_raw, R,
                            std::exp(2.0 * g->logsig), g->beta, ap, d_mu, d_var, d_score, d_best ? g->dblock_best : nullptr);
         if (d_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, g->dblock_best, nb, d_best, (long long)best_off);
         HIPCHK(hipGetLastError());
         t_end(g);
         return 0;
     }
-    if (int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
-        m > 0 && d_best && !d_mu && !d_var && !d_score && R <= PRUNE_R_MAX && R <= g->chunk_now && g->batch_hint == 0 && prune_wanted(g, R)) {
+    if (pl.route == Route::Pruned) {
         // value-only: only the winner leaves the call -- candidates that provably cannot win are not contracted past m row tiles.
-        // Not for shards of a larger set (batch_hint: the sharded entry points and bohip_gp_set_batch_hint): see DESIGN.md 6d.
         // round 2's form (either gives the same record): the long one when the last figure read or a back-off announces a long list
         const bool want_long = g->prune_retry || g->prune_seen > (unsigned)PRUNE_ROWS_CAP;
         g->prune_retry = false;
-        return pruned_pass(g, dXs, R, m, ap, d_best, best_off, nullptr, g->prune_r2_form < 0 ? want_long : g->prune_r2_form == 1);
+        return pruned_pass(g, dXs, pl, ap, d_best, best_off, nullptr, g->prune_r2_form < 0 ? want_long : g->prune_r2_form == 1);
     }
     // whole-K jobs: scoring and arg-max ride in k_trigemm_sq's epilogue (the workgroup that completes a candidate tile
     // finishes it; the one that completes the last tile writes the record): no k_score / k_argmax_final launches
@@ -2132,9 +2186,12 @@ static int score_core(bohip_gp* g, int acq_id, const double* acq_params, const d
     // did not enqueue all of its launches marks the counters dirty, and the next one clears them first.
     if (g->fz_dirty) HIPCHK(hipMemsetAsync(g->dfz_cnt, 0, (size_t)(g->fz_tiles + 1 + 16) * sizeof(unsigned), g->stream));
     g->fz_dirty = true;
-    const int rc = posterior_pass(g, dXs, R, fz);
-    if (rc == 0) g->fz_dirty = false;
-    return rc;
+    CHK(one_time_kernel_setup());
+    const int64_t chunks = chunk_pass(g, pl, dXs, make_hyper(g), ChunkV{}, false, fz, no_finish);
+    if (chunks < 0) return (int)chunks;
+    g->score_launches = chunks;
+    g->fz_dirty = false;
+    return 0;
 }
 
 template <int DT>
@@ -2150,14 +2207,18 @@ static void launch_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, 
     LAUNCH_FAM(fam_low(hp), (k_grad_finish<DT, true>), (k_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
                g->stream, g->dX, g->n, dXs, r0, r1, hp, g->dalpha, UT, g->ld, g->dmu, g->dvar, ap, d_grad, g->dgparts, g->dgcount);
 }
+// k_grad_finish and k_post_grad_finish split the observations of a small batch over *S workgroups per candidate (S > 1: their counters)
+// (one 256-observation stride per workgroup -- (n + 255) / 256 splits -- was measured in round 4: 2 us of a 58 us pass, and the changed
+// summation order moved the ascent's end points enough to graze the SciPy check's KKT bound at N = 600: not kept)
+static int grad_obs_splits(bohip_gp* g, int64_t r0, int64_t r1, int* S) {
+    *S = r1 - r0 <= SMALL_MAX ? (int)std::min<int64_t>(16, std::max<int64_t>(1, g->n / 768)) : 1;
+    if (*S > 1) CHK(ensure_small_counters(g));
+    return 0;
+}
 static int launch_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, const AcqParams& ap,
                            double* d_grad, const double* UT) {
-    // small batches: split the observations over S workgroups per candidate (see k_grad_finish)
     int S = 1;
-    // (one 256-observation stride per workgroup -- (n + 255) / 256 splits -- was measured in round 4: 2 us of a 58 us pass, and the changed
-    // summation order moved the ascent's end points enough to graze the SciPy check's KKT bound at N = 600: not kept)
-    if (r1 - r0 <= SMALL_MAX) S = (int)std::min<int64_t>(16, std::max<int64_t>(1, g->n / 768));
-    if (S > 1) CHK(ensure_small_counters(g));
+    CHK(grad_obs_splits(g, r0, r1, &S));
     dispatch_dt(g->d, [&](auto dt) { launch_grad<decltype(dt)::value>(g, dXs, r0, r1, hp, ap, d_grad, UT, S); });
     HIPCHK(hipGetLastError());
     return 0;
@@ -2182,55 +2243,29 @@ static void launch_post_grad(bohip_gp* g, const double* dXs, int64_t r0, int64_t
 // A8: scores + gradients for R candidates (device pointers).  Per chunk: K*' -> V' (trigemm, V stored)
 // -> U' = V' W (k_gemm) -> mu, sigma^2, score -> gradient.
 static int score_grad_core(bohip_gp* g, int acq_id, const double* acq_params, const double* dXs, int64_t R, double* d_score,
-                           double* d_grad) {
+                           double* d_grad, const AscPass& asc = AscPass{}) {
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     CHK(ensure_fresh(g));
     CHK(ensure_score_scratch(g, R));
     CHK(one_time_kernel_setup());
     AcqParams ap;
     CHK(make_acq(acq_id, acq_params, &ap));
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE;  // +TILE: head-room for tile-granular writes
-    const int T = (int)(Npad / TILE);
+    const PassPlan pl = choose_route(g, R, RouteWants{});
     const KernelHyper hp = make_hyper(g);
-    if (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) {  // the reference's default: a handful of L-BFGS restarts per call
+    if (pl.route == Route::Small) {  // the reference's default: a handful of L-BFGS restarts per call
         // two MFMA kernels (kernels_small.hip): K*' + V' + posterior finish, U' + gradient
-        return small_pass_mfma(g, dXs, R, ap, g->dmu, g->dvar, d_score, nullptr, 0, d_grad);
+        return small_pass_mfma(g, dXs, R, ap, g->dmu, g->dvar, d_score, nullptr, 0, d_grad, asc);
     }
-    const SplitPlan sp = split_plan(g, R);
-    if (sp.nsl > 0) {
-        CHK(split_posterior(g, dXs, R, sp, true));
+    auto finish = [&](int64_t r0, int64_t r1) {
         t_begin(g, "score+grad");
-        hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, 0, g->dmu_raw, R,
-                           std::exp(2.0 * g->logsig), g->beta, ap, g->dmu, g->dvar, d_score, (Best*)nullptr);
-        CHK(launch_grad_any(g, dXs, 0, R, hp, ap, d_grad, g->dUT));
-        t_end(g);
-        return 0;
-    }
-    CHK(ensure_grad_scratch(g));
-    const int64_t rc = g->chunk_now;
-    for (int64_t r0 = 0; r0 < R; r0 += rc) {
-        const int64_t r1 = std::min(R, r0 + rc);
-        t_begin(g, "kstar");
-        CHK(launch_kstar_any(g, dXs, r0, r1, Npad, hp));
-        t_end(g);
-        const int CT = (int)((r1 - r0 + TILE - 1) / TILE);
-        t_begin(g, "trigemm_sq+V");
-        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, g->dVT));
-        t_end(g);
-        t_begin(g, "gemm_U");
-        GemmNTParams p{};  // U'[r][j] = sum_i V'[r][i] W'[j][i]   (B = W' upper-triangular: i >= j)
-        p.A = g->dVT; p.lda = g->ld; p.B = g->dWT; p.ldb = g->ld; p.C = g->dUT; p.ldc = g->ld;
-        p.mt = CT; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.klo_from_n = 1;
-        CHK(launch_gemm_nt(g, p));
-        t_end(g);
-        t_begin(g, "score+grad");
-        const int nb = (int)((r1 - r0 + 255) / 256);
-        hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq + r0, Rpad, T, g->dmu_raw + r0, r1 - r0,
-                           std::exp(2.0 * g->logsig), g->beta, ap, g->dmu + r0, g->dvar + r0, d_score + r0, (Best*)nullptr);
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq + r0, pl.dm.Rpad, pl.dq_tiles(),
+                           g->dmu_raw + r0, r1 - r0, std::exp(2.0 * g->logsig), g->beta, ap, g->dmu + r0, g->dvar + r0, d_score + r0,
+                           (Best*)nullptr);
         CHK(launch_grad_any(g, dXs, r0, r1, hp, ap, d_grad, g->dUT));
         t_end(g);
-    }
-    return 0;
+        return 0;
+    };
+    return posterior_then(g, pl, dXs, hp, true, finish);
 }
 
 // =====================================================================================================
@@ -2274,7 +2309,8 @@ int bohip_gp_create(int64_t d, int64_t capacity, int kernel_id, int device, bohi
     if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_gate, hipEventDisableTiming);
     if (e != hipSuccess) { delete g; return fail(BOHIP_E_HIP, hipGetErrorString(e)); }
     g->stream = g->own_stream;
-    (void)g->hpin.reserve((size_t)(3 * SMALL_R + 2 + 2 * SMALL_R * DMAX), g->stream);   // (without it the small batches take the copies)
+    if (g->hpin.reserve(layout::pinned_small(nullptr, SMALL_R, DMAX, &g->pin) / sizeof(double), g->stream) != hipSuccess) g->pin = {};
+    else layout::pinned_small(g->hpin, SMALL_R, DMAX, &g->pin);   // (without the block the small batches take the copies)
     if (g->dinfo.reserve(1, g->stream) != hipSuccess || g->dmll.reserve(DMAX + 4, g->stream) != hipSuccess ||
         g->dbest.reserve(4096, g->stream) != hipSuccess) {
         delete g;
@@ -2345,13 +2381,13 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
             const bool staged = g->hpin && p <= SMALL_R && (size_t)p * g->d <= (size_t)SMALL_R * DMAX;
             int* pinfo = nullptr;
             if (staged) {
-                double* sx = g->hpin + 3 * SMALL_R + 2;   // (the gradient area and the score area of the result block: idle during an append)
-                double* sy = g->hpin;
+                double* sx = g->pin.grad;   // (the gradient area and the score area of the result block: idle during an append)
+                double* sy = g->pin.score;
                 std::memcpy(sx, X, (size_t)p * g->d * 8);
                 std::memcpy(sy, y, (size_t)p * 8);
                 HIPCHK(hipMemcpyAsync(g->dX + n_old * g->d, sx, (size_t)p * g->d * 8, hipMemcpyHostToDevice, g->stream));
                 HIPCHK(hipMemcpyAsync(g->dy + n_old, sy, (size_t)p * 8, hipMemcpyHostToDevice, g->stream));
-                pinfo = reinterpret_cast<int*>(g->hpin + 3 * SMALL_R);
+                pinfo = g->pin.words;
                 *pinfo = 0;
             } else {
                 HIPCHK(hipMemcpyAsync(g->dX + n_old * g->d, X, (size_t)p * g->d * 8, hipMemcpyHostToDevice, g->stream));
@@ -2423,7 +2459,7 @@ int bohip_gp_mll(bohip_gp* g, double* mll) {
     CHK(ensure_fresh(g));
     hipLaunchKernelGGL(k_mll, dim3(1), dim3(256), 0, g->stream, g->dL, g->ld, g->n, g->dr, g->dalpha, g->dmll);
     HIPCHK(hipGetLastError());
-    double* const pm = g->hpin ? g->hpin : mll;     // (through the pinned block: a plain DMA command)
+    double* const pm = g->hpin ? g->pin.score : mll;     // (through the pinned block: a plain DMA command)
     HIPCHK(hipMemcpyAsync(pm, g->dmll, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = *pm;
@@ -2440,8 +2476,8 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
         return 0;
     }
     CHK(ensure_fresh(g));
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), ld = g->ld;
-    const int T = (int)(Npad / TILE), NP = g->d + 3;
+    const int64_t N = g->n, ld = g->ld;
+    const int T = row_tiles(g), NP = g->d + 3;
     hipLaunchKernelGGL(k_mll, dim3(1), dim3(256), 0, g->stream, g->dL, ld, N, g->dr, g->dalpha, g->dmll);
     t_begin(g, "kinv");
     {
@@ -2469,7 +2505,7 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     HIPCHK(hipGetLastError());
     t_end(g);
     double hbuf[DMAX + 4];
-    double* const h = g->hpin ? g->hpin + 3 * SMALL_R + 2 : hbuf;     // (the pinned block's gradient area: a plain DMA command)
+    double* const h = g->hpin ? g->pin.grad : hbuf;     // (the pinned block's gradient area: a plain DMA command)
     HIPCHK(hipMemcpyAsync(h, g->dmll, 8 * (size_t)(nout + 1), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = h[0]; *d_lognoise = h[1]; *d_mean = h[2];
@@ -2919,9 +2955,8 @@ int bohip_gp_score_dev(bohip_gp* g, int acq_id, const double* acq_params, const 
 // Every caller synchronises the stream before it returns, so the block is free again at the next call.
 static const double* small_candidates_in_place(bohip_gp* g, const double* Xs, int64_t R) {
     if (!g->hpin || R > SMALL_R || g->d > DMAX || !g_small_zero_copy) return nullptr;
-    double* sx = g->hpin + 3 * SMALL_R + 2 + SMALL_R * DMAX;
-    std::memcpy(sx, Xs, (size_t)R * g->d * 8);
-    return sx;
+    std::memcpy(g->pin.cand, Xs, (size_t)R * g->d * 8);
+    return g->pin.cand;
 }
 
 int bohip_gp_predict(bohip_gp* g, const double* Xs, int64_t R, double* mu, double* var) {
@@ -2934,7 +2969,7 @@ int bohip_gp_predict(bohip_gp* g, const double* Xs, int64_t R, double* mu, doubl
     const double* xin = small_candidates_in_place(g, Xs, R);
     if (!xin) HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     if (R <= SMALL_R && g->hpin) {   // results land in pinned host memory, no copy commands
-        double *pmu = g->hpin + SMALL_R, *pvar = g->hpin + 2 * SMALL_R;
+        double *pmu = g->pin.mu, *pvar = g->pin.var;
         CHK(score_core(g, BOHIP_ACQ_MAXMEAN, nullptr, xin ? xin : g->dXs, R, pmu, pvar, nullptr, nullptr));
         HIPCHK(hipStreamSynchronize(g->stream));
         std::memcpy(mu, pmu, (size_t)R * 8);
@@ -2952,19 +2987,20 @@ int bohip_gp_predict(bohip_gp* g, const double* Xs, int64_t R, double* mu, doubl
 
 // Stages shared by bohip_gp_predict_cov and bohip_gp_sample_joint: K*', V' = K*'W' (stored), V'V on the MFMA engine (lower
 // 128-tiles of dVV, leading dimension cov_ld).  `who` names the caller in the message of the one-chunk limit.
-static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* who) {
+static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* who, PassPlan* plan) {   // *plan: the pass that ran
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     CHK(ensure_fresh(g));
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
-    if (R > g->chunk_now)
+    const PassPlan pl = *plan = choose_route(g, R, WHOLE_K_ONLY);
+    if (R > pl.chunk)
         return fail(BOHIP_E_UNSUPPORTED, std::string(who) + ": R exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + ")");
     CHK(ensure_grad_scratch(g));
     CHK(one_time_kernel_setup());
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, Rp = round_up(R, TILE);
-    const int T = (int)(Npad / TILE), CT = (int)(Rp / TILE);
+    const int64_t Rp = round_up(R, TILE);
+    const int T = pl.dm.T, CT = (int)(Rp / TILE);
     {
         bool grew = false;
         HIPCHK(g->dVV.reserve((size_t)Rp * Rp, g->stream));
@@ -2973,13 +3009,8 @@ static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* wh
     }
     const KernelHyper hp = make_hyper(g);
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
-    g->q_tiles = T;
-    t_begin(g, "kstar");
-    CHK(launch_kstar_any(g, g->dXs, 0, R, Npad, hp));
-    t_end(g);
-    t_begin(g, "trigemm_sq+V");
-    CHK(launch_trigemm(g, T, R, N, Rpad, 0, g->dVT));
-    t_end(g);
+    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, false, FuseParams{}, no_finish);   // (one chunk)
+    if (chunks < 0) return (int)chunks;
     t_begin(g, "gemm_VV");
     GemmNTParams p{};  // (V'V)[r][s] = sum_i V'[r][i] V'[s][i], lower 128-tiles
     p.A = g->dVT; p.lda = g->ld; p.B = g->dVT; p.ldb = g->ld; p.C = g->dVV; p.ldc = g->cov_ld;
@@ -2989,11 +3020,23 @@ static int posterior_vv(bohip_gp* g, const double* Xs, int64_t R, const char* wh
     return 0;
 }
 // the latent mean of the candidates of posterior_vv -> dmu (dvar: the clamped variance, unused by the joint forms)
-static int posterior_mean(bohip_gp* g, int64_t R) {
-    const int64_t Rpad = round_up(R, TILE) + TILE;
+static int posterior_mean(bohip_gp* g, const PassPlan& pl) {
+    const int64_t R = pl.dm.R;
     AcqParams ap{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
-    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, g->q_tiles, g->dmu_raw, R,
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, pl.dm.Rpad, pl.dq_tiles(), g->dmu_raw, R,
                        std::exp(2.0 * g->logsig), g->beta, ap, g->dmu, g->dvar, (double*)nullptr, (Best*)nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Sigma = K** - V'V of the candidates of posterior_vv into dcov, with the leading dimension ldo
+static int launch_post_cov(bohip_gp* g, int64_t R, int64_t ldo) {
+    const KernelHyper hp = make_hyper(g);
+    dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
+                   g->cov_ld, g->dcov, ldo);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -3001,17 +3044,11 @@ static int posterior_mean(bohip_gp* g, int64_t R) {
 int bohip_gp_predict_cov(bohip_gp* g, const double* Xs, int64_t R, double* mu, double* cov) {
     if (!g || R < 0 || (R > 0 && (!Xs || !mu || !cov))) return fail(BOHIP_E_ARG, "bad arguments");
     if (R == 0) return 0;
-    CHK(posterior_vv(g, Xs, R, "predict_cov"));
-    const KernelHyper hp = make_hyper(g);
+    PassPlan pl;
+    CHK(posterior_vv(g, Xs, R, "predict_cov", &pl));
     t_begin(g, "post_cov");
-    CHK(posterior_mean(g, R));
-    dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
-    dispatch_dt(g->d, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
-                   g->cov_ld, g->dcov, R);
-    });
-    HIPCHK(hipGetLastError());
+    CHK(posterior_mean(g, pl));
+    CHK(launch_post_cov(g, R, R));   // (the caller's matrix: R x R, dense)
     t_end(g);
     HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipMemcpyAsync(cov, g->dcov, (size_t)R * R * 8, hipMemcpyDeviceToHost, g->stream));
@@ -3067,7 +3104,8 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
     const std::string pre = std::string(who) + ": ";
     if (!(jitter_rel >= 0.0) || !std::isfinite(jitter_rel)) return fail(BOHIP_E_ARG, pre + "jitter_rel must be finite and not negative");
     if (max_tries < 0) return fail(BOHIP_E_ARG, pre + "max_tries must not be negative");
-    CHK(posterior_vv(g, Xs, R, who));
+    PassPlan pl;
+    CHK(posterior_vv(g, Xs, R, who, &pl));
     const int64_t Rp = round_up(R, TILE);
     const int CT = (int)(Rp / TILE);
     const bool mfma = S >= g_sample_mfma_min;
@@ -3078,7 +3116,7 @@ static int sample_joint_core(bohip_gp* g, const char* who, const double* Xs, int
     const KernelHyper hp = make_hyper(g);
     const dim3 cgrid((unsigned)((Rp + 255) / 256), (unsigned)(Rp / 16));
     t_begin(g, "post_cov+jitter");
-    CHK(posterior_mean(g, R));
+    CHK(posterior_mean(g, pl));
     dispatch_dt(g->d, [&](auto dt) {
         constexpr int DT = decltype(dt)::value;
         LAUNCH_FAM(fam_low(hp), (k_sample_cov<DT, true>), (k_sample_cov<DT, false>), cgrid, dim3(256), 0, g->stream, g->dXs, R, Rp, hp,
@@ -3286,19 +3324,13 @@ int bohip_gp_kg(bohip_gp* g, const double* Xs, int64_t R, int64_t E, double* kg,
     HIPCHK(hipSetDevice(g->device));
     KgWs w{};
     CHK(ensure_kg(g, R, E, false, &w));
-    CHK(posterior_vv(g, Xs, R, "kg"));
-    const KernelHyper hp = make_hyper(g);
+    PassPlan pl;
+    CHK(posterior_vv(g, Xs, R, "kg", &pl));
     t_begin(g, "post_cov");
-    CHK(posterior_mean(g, R));
+    CHK(posterior_mean(g, pl));
     // Sigma as bohip_gp_predict_cov computes it, with the leading dimension of the buffer (a multiple of 128): every row starts on
     // a 16-byte boundary for k_kg's loads
-    dim3 grid((unsigned)((R + 255) / 256), (unsigned)((R + 15) / 16));
-    dispatch_dt(g->d, [&](auto dt) {
-        constexpr int DT = decltype(dt)::value;
-        LAUNCH_FAM(fam_low(hp), (k_post_cov<DT, true>), (k_post_cov<DT, false>), grid, dim3(256), 0, g->stream, g->dXs, R, hp, g->dVV,
-                   g->cov_ld, g->dcov, g->cov_ld);
-    });
-    HIPCHK(hipGetLastError());
+    CHK(launch_post_cov(g, R, g->cov_ld));
     t_end(g);
     const double nu = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
     CHK(kg_march(g, true, w, g->dmu, g->dcov, g->cov_ld, R, E, nu, kg, nseg, best));
@@ -3514,9 +3546,8 @@ static int ensure_con(bohip_gp* g, int64_t C, int64_t R, bool jac, ConBufs* b) {
 
 static int launch_post_grad_any(bohip_gp* g, const double* dXs, int64_t r0, int64_t r1, const KernelHyper& hp, double* d_jmu, double* d_jvar,
                                 const double* UT) {
-    int S = 1;   // launch_grad_any's observation split
-    if (r1 - r0 <= SMALL_MAX) S = (int)std::min<int64_t>(16, std::max<int64_t>(1, g->n / 768));
-    if (S > 1) CHK(ensure_small_counters(g));
+    int S = 1;
+    CHK(grad_obs_splits(g, r0, r1, &S));
     dispatch_dt(g->d, [&](auto dt) { launch_post_grad<decltype(dt)::value>(g, dXs, r0, r1, hp, d_jmu, d_jvar, UT, S); });
     HIPCHK(hipGetLastError());
     return 0;
@@ -3532,50 +3563,20 @@ static int posterior_grad_core(bohip_gp* g, const double* dXs, int64_t R, double
     CHK(ensure_score_scratch(g, R));
     CHK(one_time_kernel_setup());
     const bool jac = d_jmu != nullptr;
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE;
-    const int T = (int)(Npad / TILE);
+    const PassPlan pl = choose_route(g, R, RouteWants{false, true, Prune::No});
     const KernelHyper hp = make_hyper(g);
     const AcqParams ap{ACQ_MAXMEAN, 0.0, 0.0};
     const double sigma2 = std::exp(2.0 * g->logsig);
-    const SplitPlan sp = split_plan(g, R);
-    if (sp.nsl > 0) {
-        CHK(split_posterior(g, dXs, R, sp, jac));
+    auto finish = [&](int64_t r0, int64_t r1) {
         t_begin(g, "con_post");
-        hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, Rpad, 0, g->dmu_raw, R, sigma2, g->beta,
-                           ap, d_mu, d_var, (double*)nullptr, (Best*)nullptr);
-        HIPCHK(hipGetLastError());
-        if (jac) CHK(launch_post_grad_any(g, dXs, 0, R, hp, d_jmu, d_jvar, g->dUT));
-        t_end(g);
-        return 0;
-    }
-    if (jac) CHK(ensure_grad_scratch(g));
-    const int64_t rc = g->chunk_now;
-    g->q_tiles = T;
-    for (int64_t r0 = 0; r0 < R; r0 += rc) {
-        const int64_t r1 = std::min(R, r0 + rc);
-        t_begin(g, "kstar");
-        CHK(launch_kstar_any(g, dXs, r0, r1, Npad, hp));
-        t_end(g);
-        t_begin(g, jac ? "trigemm_sq+V" : "trigemm_sq");
-        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, jac ? g->dVT : nullptr));
-        t_end(g);
-        if (jac) {
-            const int CT = (int)((r1 - r0 + TILE - 1) / TILE);
-            t_begin(g, "gemm_U");
-            GemmNTParams p{};  // U'[r][j] = sum_i V'[r][i] W'[j][i]   (B = W' upper-triangular: i >= j)
-            p.A = g->dVT; p.lda = g->ld; p.B = g->dWT; p.ldb = g->ld; p.C = g->dUT; p.ldc = g->ld;
-            p.mt = CT; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.klo_from_n = 1;
-            CHK(launch_gemm_nt(g, p));
-            t_end(g);
-        }
-        t_begin(g, "con_post");
-        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq + r0, Rpad, T, g->dmu_raw + r0,
-                           r1 - r0, sigma2, g->beta, ap, d_mu + r0, d_var + r0, (double*)nullptr, (Best*)nullptr);
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq + r0, pl.dm.Rpad, pl.dq_tiles(),
+                           g->dmu_raw + r0, r1 - r0, sigma2, g->beta, ap, d_mu + r0, d_var + r0, (double*)nullptr, (Best*)nullptr);
         HIPCHK(hipGetLastError());
         if (jac) CHK(launch_post_grad_any(g, dXs, r0, r1, hp, d_jmu, d_jvar, g->dUT));
         t_end(g);
-    }
-    return 0;
+        return 0;
+    };
+    return posterior_then(g, pl, dXs, hp, jac, finish);
 }
 
 static int con_make_params(const char* who, int acq_id, const double* acq_params, int64_t C, const double* thresholds, const int* senses,
@@ -4147,8 +4148,8 @@ int bohip_gp_score(bohip_gp* g, int acq_id, const double* acq_params, const doub
     const double* xin = small_candidates_in_place(g, Xs, R);
     if (!xin) HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     if (R <= SMALL_R && g->hpin) {
-        double* pscore = g->hpin;
-        Best* pbest = reinterpret_cast<Best*>(g->hpin + 3 * SMALL_R);
+        double* pscore = g->pin.score;
+        Best* pbest = reinterpret_cast<Best*>(g->pin.rec);
         CHK(score_core(g, acq_id, acq_params, xin ? xin : g->dXs, R, nullptr, nullptr, score ? pscore : nullptr, best ? pbest : nullptr));
         HIPCHK(hipStreamSynchronize(g->stream));
         if (score) std::memcpy(score, pscore, (size_t)R * 8);
@@ -4219,8 +4220,9 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     BatchWs bw;
     CHK(ensure_batch(g, R, q, &bw));
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE) + TILE, ld = g->ld;
-    const int T = (int)(Npad / TILE);
+    // round 0 is the batched pass (K*' chunk -> k_trigemm_sq with V' stored), whatever R is: the other routes do not leave V' in this layout
+    const PassPlan pl = choose_route(g, R, WHOLE_K_ONLY);
+    const int64_t N = pl.dm.N, Rpad = pl.dm.Rpad, ld = pl.dm.ld;
     const KernelHyper hp = make_hyper(g);
     double* U = bw.U;
     BatchRec* rec = bw.rec;
@@ -4228,23 +4230,12 @@ int bohip_gp_select_batch(bohip_gp* g, int acq_id, const double* acq_params, con
     Best* wg_best = bw.wg_best;
     int* picked = bw.picked;
     HIPCHK(hipMemsetAsync(picked, 0, (size_t)rows * sizeof(int), g->stream));
-    // round 0: the batched pass (K*' chunk -> k_trigemm_sq with V' stored), whatever R is: the other paths do not leave V' in this layout
-    g->q_tiles = T;
-    g->score_launches = 0;
-    const int64_t rc = g->chunk_now;
-    for (int64_t r0 = 0; r0 < R; r0 += rc) {
-        const int64_t r1 = std::min(R, r0 + rc);
-        ++g->score_launches;
-        t_begin(g, "kstar");
-        CHK(launch_kstar_any(g, g->dXs, r0, r1, Npad, hp));
-        t_end(g);
-        t_begin(g, "trigemm_sq+V");
-        CHK(launch_trigemm(g, T, r1 - r0, N, Rpad, r0, g->dBV + r0 * ld));
-        t_end(g);
-    }
+    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dBV, ld}, false, FuseParams{}, no_finish);
+    if (chunks < 0) return (int)chunks;
+    g->score_launches = chunks;
     t_begin(g, "batch_rounds");
     const int nb = (int)((R + 255) / 256);
-    hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, T, g->dmu_raw, R, hp.sigma2, g->beta, ap, g->dmu, g->dvar,
+    hipLaunchKernelGGL(k_score, dim3(nb), dim3(256), 0, g->stream, g->dq, Rpad, pl.dq_tiles(), g->dmu_raw, R, hp.sigma2, g->beta, ap, g->dmu, g->dvar,
                        (double*)nullptr, g->dblock_best);
     BatchFinal bf{};
     bf.mu = g->dmu; bf.var = g->dvar; bf.picked = picked; bf.rec = rec; bf.scal = scal; bf.fantasy = fantasy;
@@ -4294,7 +4285,7 @@ int bohip_gp_score_grad(bohip_gp* g, int acq_id, const double* acq_params, const
     if (!xin) HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     int rc = ensure_score_scratch(g, R);
     if (rc == 0 && R <= SMALL_R && g->hpin) {
-        double *pscore = g->hpin, *pgrad = g->hpin + 3 * SMALL_R + 2;
+        double *pscore = g->pin.score, *pgrad = g->pin.grad;
         rc = score_grad_core(g, acq_id, acq_params, xin ? xin : g->dXs, R, pscore, pgrad);
         if (rc == 0) {
             const hipError_t e = hipStreamSynchronize(g->stream);
@@ -4342,13 +4333,177 @@ static int ensure_ascent(bohip_gp* g, int64_t R) {
 
 // acquire_max(acquisition, model, lb, ub, restarts) for the gradient-based methods (reference src/acquisition.jl:48-68 with
 // nlopt_setup :23-35): lock-step projected L-BFGS ascent from R start columns, state resident in HBM.
+// bohip_gp_acquire_max is a prologue (validation, scratch, the pinned [lb | ub | starts] block), ONE of three drivers, and an epilogue
+// (ascent_read_result).  What the prologue made and the drivers share:
+struct AscentCall {
+    int acq_id, d;
+    const double* acq_params;
+    AcqParams ap;
+    int64_t R, maxeval;
+    double ftol_rel, xtol_abs, first_step;   // first_step: g_asc_first_step x the smallest box side
+    double *dlb, *dub, *dstarts, *dbx;       // the [lb | ub | starts] block where it landed on the device; the winner's coordinates
+    double* hout;                            // pinned: k_asc_final's packed result [best 2 | best_x d | f R | x R d | passes R]
+};
+// NLopt's maxtime (reference src/acquisition.jl:24-27 forwards it): checked once per iteration
+static bool ascent_out_of_time(const bohip_gp* g, std::chrono::steady_clock::time_point t_start) {
+    return g->asc_maxtime > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= g->asc_maxtime;
+}
+// The final arg-max, and the call's ONE synchronisation.  The packed result goes straight into the pinned host block (second half: the
+// first holds the inputs): ~100 doubles written by one workgroup, no copy command behind the kernel (~10 us of a 0.2-0.4 ms call).
+static int ascent_finish(bohip_gp* g, const AscentCall& c, const int* passes) {
+    hipLaunchKernelGGL(k_asc_final, dim3(1), dim3(256), 0, g->stream, g->asc, c.d, (int)c.R, g->asc_best, c.dbx, c.hout, passes);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return 0;
+}
+static void ascent_read_result(const AscentCall& c, const double* lb, bohip_best* best, double* best_x, double* f_out, double* x_out) {
+    const double* hout = c.hout;
+    const int64_t d = c.d, R = c.R;
+    if (best) { best->val = hout[0]; best->idx = (long long)hout[1]; }
+    if (best_x) for (int k = 0; k < d; ++k) best_x[k] = hout[1] >= 0.0 ? hout[2 + k] : lb[k];   // :56  maxx = lowerbounds when nothing beat -Inf
+    if (f_out) std::memcpy(f_out, hout + 2 + d, (size_t)R * 8);
+    if (x_out) std::memcpy(x_out, hout + 2 + d + R, (size_t)R * d * 8);
+}
+
+// small models: one workgroup per start point runs its whole ascent, ONE launch (kernels_ascent.hip k_ascent_wg)
+static int ascent_one_launch(bohip_gp* g, const AscentCall& c, int64_t* evals) {
+    const AscentState& st = g->asc;
+    const int d = c.d; const int64_t R = c.R;
+    AscWgParams pw{};
+    pw.W = g->dW; pw.WT = g->dWT; pw.X = g->dX; pw.alpha = g->dalpha; pw.ld = g->ld; pw.N = g->n;
+    pw.hp = make_hyper(g); pw.ap = c.ap;
+    pw.beta = g->beta; pw.st = st; pw.starts = c.dstarts; pw.lb = c.dlb; pw.ub = c.dub; pw.R = (int)R;
+    pw.maxeval = (int)std::min<int64_t>(c.maxeval, 1 << 30); pw.ftol_rel = c.ftol_rel; pw.xtol_abs = c.xtol_abs; pw.first_step_scale = c.first_step;
+    pw.max_ticks = g->asc_maxtime > 0.0 ? (unsigned long long)(g->asc_maxtime * 1e8) : 0ull;
+    pw.passes = st.accepted;
+    t_begin(g, "ascent_wg");
+    const bool lo = fam_low(pw.hp);
+    if (d > 8 && pw.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_ascent.hip k_ascent_wg_logei16)
+        LAUNCH_FAM(lo, (k_ascent_wg_logei16<true>), (k_ascent_wg_logei16<false>), dim3((unsigned)R), dim3(AWG_THREADS), 0, g->stream, pw);
+    else   // (this driver: d <= 16)
+        dispatch_dt<16>(d, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            LAUNCH_FAM(lo, (k_ascent_wg<DT, true>), (k_ascent_wg<DT, false>), dim3((unsigned)R), dim3(AWG_THREADS), 0, g->stream, pw);
+        });
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    CHK(ascent_finish(g, c, st.accepted));
+    const double* passes = c.hout + 2 + d + R + (size_t)R * d;   // (>= 0, R >= 1)
+    *evals = (int64_t)*std::max_element(passes, passes + R);
+    return 0;
+}
+
+// FREE-RUNNING driver (k_asc_step): pass after pass is enqueued without waiting; how many start points are still active after pass e is read LAG
+// passes later from pinned memory (long written by then: no stall), so at most LAG passes run beyond convergence.  The lock-step driver's trajectories.
+static int ascent_free_running(bohip_gp* g, const AscentCall& c, int64_t* evals_out) {
+    const AscentState& st = g->asc;
+    const int d = c.d; const int64_t R = c.R; const unsigned nR = (unsigned)R;
+    const int LAG = 1;   // (2 until round 4: with 17 passes per call instead of 228 a wasted pass is 5 % of it; one queued pass keeps the device fed)
+    // (the counters of a pass clear themselves; this is for a call that was cut short -- queued before the start kernel, where the device
+    // waits for the host's copy anyway)
+    HIPCHK(hipMemsetAsync(st.nact, 0, (size_t)2 * ASC_RING * sizeof(unsigned), g->stream));
+    for (int i = 0; i < ASC_RING; ++i) st.h_cnt[i] = 0;
+    hipLaunchKernelGGL(k_asc_start, dim3(nR), dim3(64), 0, g->stream, st, d, c.dstarts, c.dlb, c.dub);
+    bool first_folded = false;   // the start points' adoption and first direction ran in the gradient kernel's last workgroup (SmallFold, on = 2)
+    SmallFold fold0{};
+    fold0.on = 2; fold0.R = (int)R; fold0.ring_slot = ASC_RING - 1; fold0.st = st; fold0.lb = c.dlb; fold0.ub = c.dub; fold0.first_step_scale = c.first_step;
+    CHK(score_grad_core(g, c.acq_id, c.acq_params, st.Xt, R, st.ft, st.Gt, AscPass{g_asc_fold ? &fold0 : nullptr, nullptr, &first_folded}));
+    if (!first_folded) {
+        // no synchronisation here: how many start points are active at all is counted by the adopt kernel into the ring slot the host reads
+        // once the first pass is queued (below)
+        hipLaunchKernelGGL(k_asc_adopt_count, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, ASC_RING - 1);
+        HIPCHK(hipGetLastError());
+    }
+    int64_t evals = 1;
+    const auto t_start = std::chrono::steady_clock::now();
+    if (!first_folded) hipLaunchKernelGGL(k_asc_direction, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, 0, 0, c.dlb, c.dub, c.first_step);
+    int64_t e = 0, converged_at = -1;
+    bool none_active = false;
+    auto read_count = [&](int64_t pass) -> int {   // active start points after `pass` (waits for it if need be)
+        volatile int* w = st.h_cnt + (pass % ASC_RING);
+        const auto t0 = std::chrono::steady_clock::now();
+        int v;
+        while ((v = *w) == 0) {
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 30.0) return -1;
+        }
+        *w = 0;
+        return v - 1;
+    };
+    for (; evals < c.maxeval && !ascent_out_of_time(g, t_start); ++e) {
+        SmallFold fold{};
+        fold.on = 1; fold.R = (int)R; fold.ring_slot = (int)(e % ASC_RING); fold.st = st; fold.lb = c.dlb; fold.ub = c.dub; fold.ftol_rel = c.ftol_rel; fold.xtol_abs = c.xtol_abs;
+        bool folded = false;
+        CHK(score_grad_core(g, c.acq_id, c.acq_params, st.Xt, R, st.ft, st.Gt, AscPass{g_asc_fold ? &fold : nullptr, st.ticket, &folded}));
+        ++evals;
+        if (!folded)   // (more than 16 start points, d > 16, or the batch took another path: the step as a launch of its own)
+            hipLaunchKernelGGL(k_asc_step, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, c.dlb, c.dub, c.first_step, c.ftol_rel, c.xtol_abs,
+                               (int)(e % ASC_RING));
+        HIPCHK(hipGetLastError());
+        if (e == 0) {   // the adopt kernel's count (the device is busy with the first pass meanwhile)
+            const int n0 = read_count(ASC_RING - 1);
+            if (n0 < 0) return fail(BOHIP_E_HIP, "device ascent: the first evaluation did not report back within 30 s");
+            if (n0 == 0) { none_active = true; ++e; break; }   // no start point with a finite value: the queued pass changes nothing
+        }
+        if (e >= LAG) {
+            const int n = read_count(e - LAG);
+            if (n < 0) return fail(BOHIP_E_HIP, "device ascent: an evaluation pass did not report back within 30 s");
+            if (n == 0) { converged_at = e - LAG; ++e; break; }
+        }
+    }
+    CHK(ascent_finish(g, c, nullptr));   // (queued behind the last pass at once; the counts of the last LAG passes are looked at after it)
+    if (converged_at < 0)   // stopped by maxeval / maxtime, or converged within the last LAG passes
+        for (int64_t p2 = std::max<int64_t>(0, e - LAG); p2 < e && converged_at < 0; ++p2)
+            if (st.h_cnt[p2 % ASC_RING] == 1) converged_at = p2;
+    if (converged_at >= 0) evals = 2 + converged_at;   // passes that were needed: the first one + passes 0 .. converged_at
+    if (none_active) evals = 1;
+    *evals_out = evals;
+    return 0;
+}
+
+// LOCK-STEP driver (BOHIP_ASC_LOCKSTEP=1): five launches and a stream synchronisation per evaluation pass, the host decides between passes
+static int ascent_lock_step(bohip_gp* g, const AscentCall& c, int64_t* evals_out) {
+    const AscentState& st = g->asc;
+    const int d = c.d; const int64_t R = c.R; const unsigned nR = (unsigned)R;
+    auto any_of = [&](const int* v, int want) { return std::any_of(v, v + R, [&](int x) { return (x != 0) == (want != 0); }); };
+    hipLaunchKernelGGL(k_asc_start, dim3(nR), dim3(64), 0, g->stream, st, d, c.dstarts, c.dlb, c.dub);
+    CHK(score_grad_core(g, c.acq_id, c.acq_params, st.Xt, R, st.ft, st.Gt));
+    hipLaunchKernelGGL(k_asc_adopt, dim3(nR), dim3(64), 0, g->stream, st, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(g->stream));
+    bool any_active = any_of(st.h_active, 1);
+    int64_t evals = 1;
+    int nh = 0, it = 0;
+    const auto t_start = std::chrono::steady_clock::now();
+    while (evals < c.maxeval && any_active && !ascent_out_of_time(g, t_start)) {
+        hipLaunchKernelGGL(k_asc_direction, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, nh, (it + ASC_M - 1) % ASC_M, c.dlb, c.dub,
+                           c.first_step);
+        for (int bt = 0; bt < ASC_MAX_BT; ++bt) {   // backtracking Armijo, all start points per device pass
+            CHK(score_grad_core(g, c.acq_id, c.acq_params, st.Xt, R, st.ft, st.Gt));
+            ++evals;
+            hipLaunchKernelGGL(k_asc_linesearch, dim3(nR), dim3(64), 0, g->stream, st, d, c.dlb, c.dub);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(g->stream));
+            if (bt == 0 && it > 0) any_active = any_of(st.h_active, 1);   // written by the previous k_asc_update
+            if (!any_of(st.h_accepted, 0) || evals >= c.maxeval || !any_active) break;
+        }
+        if (!any_active) { --evals; break; }   // the speculative evaluation of an already converged set is not counted
+        hipLaunchKernelGGL(k_asc_update, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, it % ASC_M, c.ftol_rel, c.xtol_abs);
+        nh = std::min(nh + 1, ASC_M);
+        ++it;
+    }
+    CHK(ascent_finish(g, c, nullptr));
+    *evals_out = evals;
+    return 0;
+}
+
 int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, const double* lb, const double* ub,
                          const double* starts, int64_t R, int64_t maxeval, double ftol_rel, double xtol_abs, double* x_out,
                          double* f_out, bohip_best* best, double* best_x, int64_t* evals_out) {
     if (!g || !lb || !ub || R < 0 || (R > 0 && !starts)) return fail(BOHIP_E_ARG, "bad arguments");
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id");
-    AcqParams ap;
-    CHK(make_acq(acq_id, acq_params, &ap));
+    AscentCall c{};
+    c.acq_id = acq_id; c.acq_params = acq_params; c.R = R; c.maxeval = maxeval; c.ftol_rel = ftol_rel; c.xtol_abs = xtol_abs;
+    CHK(make_acq(acq_id, acq_params, &c.ap));
     if (evals_out) *evals_out = 0;
     if (R == 0) {
         if (best) { best->val = -INFINITY; best->idx = -1; }
@@ -4357,7 +4512,7 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
-    const int d = g->d;
+    const int d = c.d = g->d;
     for (int k = 0; k < d; ++k)
         if (!(lb[k] <= ub[k])) return fail(BOHIP_E_ARG, "lowerbounds must not exceed upperbounds");
     CHK(ensure_fresh(g));
@@ -4366,10 +4521,6 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
     CHK(ensure_ascent(g, R));
     AscentState& st = g->asc;
     st.ftol_abs = g->asc_ftol_abs; st.xtol_rel = g->asc_xtol_rel; st.stopval = g->asc_stopval;
-    double* dlb = g->asc_bounds;
-    double* dub = dlb + DMAX;
-    double* dbx = dub + DMAX;
-    const bool use_wg = g_asc_wg_nmax > 0 && g->n <= std::min<int64_t>(g_asc_wg_nmax, AWG_NMAX - 1) && d <= 16 && !g_asc_lockstep;
     // one pinned block in ([lb | ub | starts]), one pinned block out (k_asc_final's packed result): seven pageable copies were ~0.1 ms
     // of a call that is 1.3 ms at N = 3000 since the search needs 17 passes instead of 228
     const size_t n_in = (size_t)(2 + R) * d, n_out = (size_t)2 + d + R + (size_t)R * d + R, n_io = std::max(n_in, n_out);
@@ -4381,183 +4532,18 @@ int bohip_gp_acquire_max(bohip_gp* g, int acq_id, const double* acq_params, cons
     std::memcpy(g->asc_hio + d, ub, (size_t)d * 8);
     std::memcpy(g->asc_hio + 2 * d, starts, (size_t)R * d * 8);
     HIPCHK(hipMemcpyAsync(g->asc_dio, g->asc_hio, n_in * 8, hipMemcpyHostToDevice, g->stream));
-    if (!use_wg) {   // (the batched kernels read the bounds and the starts where the block landed)
-        dlb = g->asc_dio;
-        dub = g->asc_dio + d;
-    }
+    c.dlb = g->asc_dio; c.dub = g->asc_dio + d; c.dstarts = g->asc_dio + 2 * d;   // (the kernels read the bounds and the starts where the block landed)
+    c.dbx = g->asc_bounds + 2 * DMAX;
+    c.hout = g->asc_hio + n_io;
     double span = INFINITY;
     for (int k = 0; k < d; ++k) span = std::min(span, ub[k] - lb[k] + 1e-300);
-    const unsigned nR = (unsigned)R;
-    auto any_of = [&](const int* v, int want) {
-        for (int64_t r = 0; r < R; ++r)
-            if ((v[r] != 0) == (want != 0)) return true;
-        return false;
-    };
-    if (use_wg) {
-        // small models: one workgroup per start point runs its whole ascent, ONE launch (kernels_ascent.hip k_ascent_wg)
-        AscWgParams pw{};
-        pw.W = g->dW; pw.WT = g->dWT; pw.X = g->dX; pw.alpha = g->dalpha; pw.ld = g->ld; pw.N = g->n;
-        pw.hp = make_hyper(g);
-        pw.ap = ap;
-        pw.beta = g->beta; pw.st = st; pw.starts = g->asc_dio + 2 * d; pw.lb = g->asc_dio; pw.ub = g->asc_dio + d; pw.R = (int)R;
-        pw.maxeval = (int)std::min<int64_t>(maxeval, 1 << 30); pw.ftol_rel = ftol_rel; pw.xtol_abs = xtol_abs; pw.first_step_scale = g_asc_first_step * span;
-        pw.max_ticks = g->asc_maxtime > 0.0 ? (unsigned long long)(g->asc_maxtime * 1e8) : 0ull;
-        pw.passes = st.accepted;
-        t_begin(g, "ascent_wg");
-        const bool lo = fam_low(pw.hp);
-        if (d > 8 && pw.ap.acq == ACQ_LOGEI)   // (the instantiation of its own: kernels_ascent.hip k_ascent_wg_logei16)
-            LAUNCH_FAM(lo, (k_ascent_wg_logei16<true>), (k_ascent_wg_logei16<false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-        else   // (use_wg: d <= 16)
-            dispatch_dt<16>(d, [&](auto dt) {
-                constexpr int DT = decltype(dt)::value;
-                LAUNCH_FAM(lo, (k_ascent_wg<DT, true>), (k_ascent_wg<DT, false>), dim3(nR), dim3(AWG_THREADS), 0, g->stream, pw);
-            });
-        HIPCHK(hipGetLastError());
-        t_end(g);
-        // the packed result goes straight into the pinned host block (second half: the first holds the inputs): ~100 doubles written by one
-        // workgroup, no copy command behind the kernel (~10 us of a 0.2-0.4 ms call)
-        double* hout = g->asc_hio + n_io;
-        hipLaunchKernelGGL(k_asc_final, dim3(1), dim3(256), 0, g->stream, st, d, (int)R, g->asc_best, dbx, hout, st.accepted);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (best) { best->val = hout[0]; best->idx = (long long)hout[1]; }
-        if (best_x) for (int k = 0; k < d; ++k) best_x[k] = hout[1] >= 0.0 ? hout[2 + k] : lb[k];   // :56  maxx = lowerbounds when nothing beat -Inf
-        if (f_out) std::memcpy(f_out, hout + 2 + d, (size_t)R * 8);
-        if (x_out) std::memcpy(x_out, hout + 2 + d + R, (size_t)R * d * 8);
-        if (evals_out) {
-            double mx = 0.0;
-            for (int64_t r = 0; r < R; ++r) mx = std::max(mx, hout[2 + d + R + (size_t)R * d + r]);
-            *evals_out = (int64_t)mx;
-        }
-        t_collect(g);
-        return 0;
-    }
-    const bool free_run = !g_asc_lockstep;
-    if (free_run) {
-        // (the counters of a pass clear themselves; this is for a call that was cut short -- queued before the start kernel, where the device
-        // waits for the host's copy anyway)
-        HIPCHK(hipMemsetAsync(st.nact, 0, (size_t)2 * ASC_RING * sizeof(unsigned), g->stream));
-        for (int i = 0; i < ASC_RING; ++i) st.h_cnt[i] = 0;
-    }
-    hipLaunchKernelGGL(k_asc_start, dim3(nR), dim3(64), 0, g->stream, st, d, g->asc_dio + 2 * d, dlb, dub);
-    bool first_folded = false;   // the start points' adoption and first direction ran in the gradient kernel's last workgroup (SmallFold, on = 2)
-    {
-        SmallFold fold{};
-        fold.on = 2; fold.R = (int)R; fold.ring_slot = ASC_RING - 1; fold.st = st; fold.lb = dlb; fold.ub = dub; fold.first_step_scale = g_asc_first_step * span;
-        g->asc_fold = (free_run && g_asc_fold) ? &fold : nullptr;
-        g->asc_fold_done = false;
-        const int rc_first = score_grad_core(g, acq_id, acq_params, st.Xt, R, st.ft, st.Gt);
-        g->asc_fold = nullptr;
-        CHK(rc_first);
-        first_folded = g->asc_fold_done;
-    }
-    bool any_active = true;
-    if (first_folded) {
-    } else if (free_run) {
-        // no synchronisation here: how many start points are active at all is counted by the adopt kernel into the ring slot the host reads
-        // once the first pass is queued (below)
-        hipLaunchKernelGGL(k_asc_adopt_count, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, ASC_RING - 1);
-        HIPCHK(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(k_asc_adopt, dim3(nR), dim3(64), 0, g->stream, st, d);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(g->stream));
-        any_active = any_of(st.h_active, 1);
-    }
-    int64_t evals = 1;
-    int nh = 0, it = 0;
-    int64_t fr_e = 0, fr_converged_at = -1;   // free-running form: what its loop leaves for after the call's one synchronisation
-    bool fr_none_active = false, fr_pending = false;
-    const auto t_start = std::chrono::steady_clock::now();
-    auto out_of_time = [&]() {   // NLopt's maxtime (reference src/acquisition.jl:24-27 forwards it): checked once per iteration
-        return g->asc_maxtime > 0.0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() >= g->asc_maxtime;
-    };
-    if (!g_asc_lockstep) {
-        // FREE-RUNNING form (k_asc_step): pass after pass is enqueued without waiting; the number of start points still active
-        // after pass e is read LAG passes later from pinned memory (by then it has long been written: no stall), so at most
-        // LAG passes run beyond convergence.  Same per-start-point trajectories as the lock-step form below.
-        const int LAG = 1;   // (2 until round 4: with 17 passes per call instead of 228 a wasted pass is 5 % of it; one queued pass keeps the device fed)
-        if (any_active) {
-            if (!first_folded) hipLaunchKernelGGL(k_asc_direction, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, 0, 0, dlb, dub, g_asc_first_step * span);
-            int64_t e = 0, converged_at = -1;
-            bool none_active = false;
-            auto read_count = [&](int64_t pass) -> int {   // active start points after `pass` (waits for it if need be)
-                volatile int* w = st.h_cnt + (pass % ASC_RING);
-                const auto t0 = std::chrono::steady_clock::now();
-                int v;
-                while ((v = *w) == 0) {
-                    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 30.0) return -1;
-                }
-                *w = 0;
-                return v - 1;
-            };
-            for (; evals < maxeval && !out_of_time(); ++e) {
-                g->asc_go = st.ticket;   // (written by the adopt kernel and by every pass's step: active start points)
-                SmallFold fold{};
-                fold.on = 1; fold.R = (int)R; fold.ring_slot = (int)(e % ASC_RING); fold.st = st; fold.lb = dlb; fold.ub = dub; fold.ftol_rel = ftol_rel; fold.xtol_abs = xtol_abs;
-                g->asc_fold = g_asc_fold ? &fold : nullptr;
-                g->asc_fold_done = false;
-                const int rc_pass = score_grad_core(g, acq_id, acq_params, st.Xt, R, st.ft, st.Gt);
-                g->asc_go = nullptr;
-                g->asc_fold = nullptr;
-                CHK(rc_pass);
-                ++evals;
-                if (!g->asc_fold_done)   // (more than 16 start points, d > 16, or the batch took another path: the step as a launch of its own)
-                    hipLaunchKernelGGL(k_asc_step, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, dlb, dub, g_asc_first_step * span, ftol_rel, xtol_abs,
-                                       (int)(e % ASC_RING));
-                HIPCHK(hipGetLastError());
-                if (e == 0) {   // the adopt kernel's count (the device is busy with the first pass meanwhile)
-                    const int n0 = read_count(ASC_RING - 1);
-                    if (n0 < 0) return fail(BOHIP_E_HIP, "device ascent: the first evaluation did not report back within 30 s");
-                    if (n0 == 0) { none_active = true; ++e; break; }   // no start point with a finite value: the queued pass changes nothing
-                }
-                if (e >= LAG) {
-                    const int n = read_count(e - LAG);
-                    if (n < 0) return fail(BOHIP_E_HIP, "device ascent: an evaluation pass did not report back within 30 s");
-                    if (n == 0) { converged_at = e - LAG; ++e; break; }
-                }
-            }
-            // (no synchronisation here: the final arg-max and the copy home are queued behind the last pass at once; the counts of the last
-            // LAG passes are looked at after the one synchronisation of the call, below)
-            fr_e = e; fr_converged_at = converged_at; fr_none_active = none_active; fr_pending = true;
-        }
-    } else {
-    while (evals < maxeval && any_active && !out_of_time()) {
-        hipLaunchKernelGGL(k_asc_direction, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, nh, (it + ASC_M - 1) % ASC_M, dlb, dub,
-                           g_asc_first_step * span);
-        for (int bt = 0; bt < ASC_MAX_BT; ++bt) {   // backtracking Armijo, all start points per device pass
-            CHK(score_grad_core(g, acq_id, acq_params, st.Xt, R, st.ft, st.Gt));
-            ++evals;
-            hipLaunchKernelGGL(k_asc_linesearch, dim3(nR), dim3(64), 0, g->stream, st, d, dlb, dub);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(g->stream));
-            if (bt == 0 && it > 0) any_active = any_of(st.h_active, 1);   // written by the previous k_asc_update
-            if (!any_of(st.h_accepted, 0) || evals >= maxeval || !any_active) break;
-        }
-        if (!any_active) { --evals; break; }   // the speculative evaluation of an already converged set is not counted
-        hipLaunchKernelGGL(k_asc_update, dim3(nR), dim3(64), 0, g->stream, st, d, (int)R, it % ASC_M, ftol_rel, xtol_abs);
-        nh = std::min(nh + 1, ASC_M);
-        ++it;
-    }
-    }
-    {
-        double* hout = g->asc_hio + n_io;   // (pinned: written by the kernel itself, see the one-launch form above)
-        hipLaunchKernelGGL(k_asc_final, dim3(1), dim3(256), 0, g->stream, st, d, (int)R, g->asc_best, dbx, hout, (const int*)nullptr);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (fr_pending) {
-            const int LAG = 1;
-            if (fr_converged_at < 0)   // stopped by maxeval / maxtime, or converged within the last LAG passes
-                for (int64_t p2 = std::max<int64_t>(0, fr_e - LAG); p2 < fr_e && fr_converged_at < 0; ++p2)
-                    if (st.h_cnt[p2 % ASC_RING] == 1) fr_converged_at = p2;
-            if (fr_converged_at >= 0) evals = 2 + fr_converged_at;   // passes that were needed: the first one + passes 0 .. converged_at
-            if (fr_none_active) evals = 1;
-        }
-        if (best) { best->val = hout[0]; best->idx = (long long)hout[1]; }
-        if (best_x) for (int k = 0; k < d; ++k) best_x[k] = hout[1] >= 0.0 ? hout[2 + k] : lb[k];   // :56  maxx = lowerbounds when nothing beat -Inf
-        if (f_out) std::memcpy(f_out, hout + 2 + d, (size_t)R * 8);
-        if (x_out) std::memcpy(x_out, hout + 2 + d + R, (size_t)R * d * 8);
-    }
+    c.first_step = g_asc_first_step * span;
+    const bool use_wg = g_asc_wg_nmax > 0 && g->n <= std::min<int64_t>(g_asc_wg_nmax, AWG_NMAX - 1) && d <= 16 && !g_asc_lockstep;
+    int64_t evals = 0;
+    if (use_wg) CHK(ascent_one_launch(g, c, &evals));
+    else if (!g_asc_lockstep) CHK(ascent_free_running(g, c, &evals));
+    else CHK(ascent_lock_step(g, c, &evals));
+    ascent_read_result(c, lb, best, best_x, f_out, x_out);
     if (evals_out) *evals_out = evals;
     t_collect(g);
     return 0;
@@ -4742,7 +4728,7 @@ int bohip_gp_info(const bohip_gp* g, int what, int64_t* value) {
         case BOHIP_INFO_CHOL_ABORT_TILES: *value = g->chol_abort_T; return 0;
         case BOHIP_INFO_JITTER_STEPS: *value = g->jitter_steps_last; return 0;
         case BOHIP_INFO_SCORE_LAUNCHES: *value = g->score_launches; return 0;
-        case BOHIP_INFO_SCORE_CHUNK: *value = g->chunk_now; return 0;
+        case BOHIP_INFO_SCORE_CHUNK: *value = g->score_chunk; return 0;
         case BOHIP_INFO_KERNEL_CLOCK_MHZ: {   // since the previous read; synchronises the handle's stream
             *value = 0;
             if (!g->dclk) return 0;
@@ -4874,11 +4860,10 @@ int bohip_debug_prune_bounds(bohip_gp* g, int acq_id, const double* acq_params, 
     static const double no_params[2] = {0.0, 0.0};   // (a null acq_params is taken as zeros here)
     AcqParams ap;
     CHK(make_acq(acq_id, acq_params ? acq_params : no_params, &ap));
-    const int m = prune_tiles((int)(round_up(g->n + 1, TILE) / TILE));
-    if (m == 0 || R > PRUNE_R_MAX || R > g->chunk_now || (path_R(g, R) <= small_limit(g) && R <= SMALL_MAX) || split_plan(g, R).nsl > 0)
-        return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
+    const PassPlan pl = choose_route(g, R, RouteWants{true, true, Prune::Probe});
+    if (pl.route != Route::Pruned) return fail(BOHIP_E_UNSUPPORTED, "no pruning at this size");
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
-    return pruned_pass(g, g->dXs, R, m, ap, nullptr, 0, ub);
+    return pruned_pass(g, g->dXs, pl, ap, nullptr, 0, ub);
 }
 // tests only (tests/test_prune_rows_gpu.py): the partial sums q[2T][R] and mu_raw[R] of R host candidates from the full pass's
 // k_trigemm_sq (path 0) or from k_trigemm_rows over every row tile, the candidates listed in reverse order (path 1; path 2: the
@@ -4892,10 +4877,11 @@ int bohip_debug_trigemm_partials(bohip_gp* g, const double* Xs, int64_t R, int p
     CHK(ensure_fresh(g));
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
-    if (R > g->chunk_now) return fail(BOHIP_E_UNSUPPORTED, "more than one K*' chunk");
+    if (R > chunk_rows(g, R)) return fail(BOHIP_E_UNSUPPORTED, "more than one K*' chunk");
     CHK(one_time_kernel_setup());
-    const int64_t N = g->n, Npad = round_up(N + 1, TILE), Rpad = round_up(R, TILE);
-    const int T = (int)(Npad / TILE);
+    const PassDims dm = pass_dims(g, R);
+    const int64_t N = dm.N, Npad = dm.Npad, Rpad = round_up(R, TILE);   // (this tool's rows of q are dense: no head-room tile, unlike dm.Rpad)
+    const int T = dm.T;
     CHK(ensure_pieces(g, T, N));
     const std::vector<int> hv = rows_halves(g->hpieces);
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
@@ -4984,7 +4970,7 @@ int bohip_debug_exec_throughput(bohip_gp* g, unsigned qmask, int hot, int wgs, d
     if (!g || !ms_out || g->n == 0) return BOHIP_E_ARG;
     hipSetDevice(g->device);
     CHK(one_time_kernel_setup());
-    const int T = (int)(round_up(g->n + 1, TILE) / TILE);
+    const int T = row_tiles(g);
     if (T <= 3) return BOHIP_E_UNSUPPORTED;
     std::vector<ExTask> all, run;
     int qb[EX_NQ + 1], qb2[EX_NQ + 1];

@@ -157,5 +157,18 @@ size_t ens_io(const void* base, size_t H, size_t P, size_t Rc, size_t d, size_t 
     w->best = w->blk + nblk;
     return c.total();
 }
+// the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
+// [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
+// Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the
+// append stages X in the gradient area, y in the score area and gets the pivot back in words[0]; mll gets its value back in score[0];
+// mll_grad gets [mll | d lognoise | d mean | d kernel ...] (<= dmax + 4 doubles) in the gradient area.  A refit: words[0], words[1].
+struct PinnedSmall { double *score, *mu, *var, *rec, *grad, *cand; int* words; };
+inline size_t pinned_small(const void* base, size_t n_small, size_t dmax, PinnedSmall* w) {
+    Carve c(base);
+    w->score = c.take<double>(n_small); w->mu = c.take<double>(n_small); w->var = c.take<double>(n_small);
+    w->words = reinterpret_cast<int*>(w->rec = c.take<double>(2));
+    w->grad = c.take<double>(n_small * dmax); w->cand = c.take<double>(n_small * dmax);
+    return c.total();
+}
 
 }   // namespace layout

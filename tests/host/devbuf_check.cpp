@@ -279,6 +279,27 @@ static void check_pruned() {
                      M(w, pcs, c[3], 256)});
     }
 }
+static void check_pinned_small() {
+    for (size_t ns : {(size_t)1, (size_t)32})
+        for (size_t dmax : {(size_t)1, (size_t)64}) {
+            layout::PinnedSmall w;
+            const size_t total = layout::pinned_small(BASE, ns, dmax, &w);
+            REQUIRE(total == (3 * ns + 2 + 2 * ns * dmax) * 8);   // the doubles the block always had ...
+            // ... at the offsets the call sites used to spell out
+            const double* b = (const double*)BASE;
+            REQUIRE(w.score == b && w.mu == b + ns && w.var == b + 2 * ns && w.rec == b + 3 * ns && w.grad == b + 3 * ns + 2 &&
+                    w.cand == b + 3 * ns + 2 + ns * dmax && (const void*)w.words == (const void*)w.rec);
+            check_block("pinned_small", B0, total,
+                        {M(w, score, ns, 8), M(w, mu, ns, 8), M(w, var, ns, 8), M(w, rec, 2, 8), M(w, grad, ns * dmax, 8), M(w, cand, ns * dmax, 8)});
+        }
+    // the deliberate aliases fit at the shipped sizes (common.h: SMALL_R = 32 candidates, DMAX = 64 coordinates): an arg-max record and
+    // the refit's two words in the record area, mll_grad's DMAX + 4 doubles and the append's SMALL_R x DMAX in the gradient area
+    const size_t SMALL_R = 32, DMAX = 64;
+    layout::PinnedSmall w;
+    layout::pinned_small(BASE, SMALL_R, DMAX, &w);
+    const size_t rec_bytes = (size_t)((const char*)w.grad - (const char*)w.rec), grad_bytes = (size_t)((const char*)w.cand - (const char*)w.grad);
+    REQUIRE(sizeof(Best) <= rec_bytes && 2 * sizeof(int) <= rec_bytes && (DMAX + 4) * 8 <= grad_bytes && SMALL_R * DMAX * 8 <= grad_bytes);
+}
 static void check_fit_and_ens() {
     for (size_t H : {(size_t)1, (size_t)5, (size_t)65535}) {
         layout::FitIo f;
@@ -318,6 +339,7 @@ int main() {
     check_ascent();
     check_small();
     check_pruned();
+    check_pinned_small();
     check_fit_and_ens();
     REQUIRE(live(devbuf::DEVICE) == 0 && live(devbuf::PINNED) == 0);   // nothing is left behind
     std::puts("devbuf_check ok");
