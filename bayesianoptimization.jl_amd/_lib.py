@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -198,6 +198,12 @@ MO_SIGNATURES = {
     "bohip_gp_score_mo": (C.c_int, [_gp, _gp, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_loo.h declares (leave-one-out predictions at the observations, their log-probability and its gradient)
+LOO_SIGNATURES = {
+    "bohip_gp_loo": (C.c_int, [_gp, _dp, _dp, _dp, _dp]),
+    "bohip_gp_loo_grad": (C.c_int, [_gp, _dp, _dp, _dp, _dp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -255,7 +261,7 @@ def load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(PATHS_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
-                              + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items())):
+                              + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -48,12 +48,18 @@ class MAPGPOptimizer(ModelOptimizer):
     ``restarts = k > 1`` (an extension: the reference runs ONE search from the current parameters) starts k searches -- the current
     parameters and k - 1 Latin-hypercube points of the bounds, a side without a finite bound replaced by current -/+ ``startwidth``
     (log-parameters) -- and advances them in lock-step, one batched device evaluation of all k per step (bohip_gp_mll_grad_batch);
-    ``maxeval`` then counts lock-step evaluations, i.e. per start.  ``seed`` seeds the starts.  The best end point wins, the first on ties."""
+    ``maxeval`` then counts lock-step evaluations, i.e. per start.  ``seed`` seeds the starts.  The best end point wins, the first on ties.
 
-    def __init__(self, every=10, **kwargs):
+    ``objective = "mll"`` (the default, the reference's) maximises the log marginal likelihood; ``"loo"`` (an extension) the
+    leave-one-out predictive log-probability (Rasmussen & Williams 5.4.2; bohip_gp_loo_grad), in the single search
+    and, with ``restarts > 1``, one set_params_ + loo_grad per start and step at any N."""
+
+    def __init__(self, every=10, objective="mll", **kwargs):
+        if objective not in ("mll", "loo"):
+            raise ValueError(f"MAPGPOptimizer: objective must be 'mll' or 'loo', got {objective!r}")
         self.i = 0
         self.every = every
-        self.options = {**self.defaultoptions(), **kwargs}
+        self.options = {**self.defaultoptions(), **kwargs, "objective": objective}
 
     @staticmethod
     def defaultoptions():                                     # :48-52
@@ -226,10 +232,12 @@ def _map_fit(model, opt):                                     # :54-77
             kw["ll"] = x[i:i + nk - 1]; kw["lsigma"] = x[i + nk - 1]
         model.set_params_(**kw)
 
+    loo = opt.get("objective", "mll") == "loo"
+
     def negmll(x):                                            # f = (x, g) -> ... gp.target, gp.dtarget  (:59-64)
         apply(x)
         try:
-            m, dn, dm, dk = model.mll_grad()
+            m, dn, dm, dk = model.loo_grad() if loo else model.mll_grad()
         except NotPositiveDefinite:                           # not positive definite for these parameters; device
             return 1e300, np.zeros_like(x)                    # failures (E_HIP, E_NODEVICE, ...) propagate
         g = []
@@ -289,13 +297,16 @@ def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
     """fg_batch of _multistart_map for a model: the free parameters of the fit sit in the optimisation vector, the fixed ones are
     constants of Theta's rows.  A device model of a size the batched call takes, and wins at, evaluates all columns in one launch;
     otherwise (or for a model without the call) every column is a set_params_ + mll_grad, at any N.  want_grad=False (the slice
-    sampler): the same dispatch, value only -- the gradient is None, the batched call forms no inverse and the loop calls mll."""
+    sampler): the same dispatch, value only -- the gradient is None, the batched call forms no inverse and the loop calls mll.
+    opt["objective"] == "loo": the leave-one-out log-probability through the loop, set_params_ + loo_grad per column (it has no
+    batched form)."""
+    loo = opt.get("objective", "mll") == "loo"
     mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
     base = np.concatenate([[model.logNoise, model.mean.beta if isinstance(model.mean, MeanConst) else 0.0], model.kernel.ll,
                            [model.kernel.lsigma]])
     idx = ([0] if opt["noise"] else []) + ([1] if mean_free else []) + (list(range(2, 2 + nk)) if opt["kern"] else [])
     assert len(idx) == p
-    batched = hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
+    batched = not loo and hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
 
     def fg_batched(X):
         Theta = np.tile(base, (X.shape[1], 1))
@@ -311,7 +322,7 @@ def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
                 if not want_grad:
                     f[r] = model.mll()
                     continue
-                m, dn, dm, dk = model.mll_grad()
+                m, dn, dm, dk = model.loo_grad() if loo else model.mll_grad()
             except NotPositiveDefinite:
                 continue
             full = np.concatenate([[dn, dm], dk])

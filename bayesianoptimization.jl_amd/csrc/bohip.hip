@@ -27,7 +27,9 @@
 #include "../../include/bohip_ens_grad.h"
 #include "../../include/bohip_con.h"
 #include "../../include/bohip_mo.h"
+#include "../../include/bohip_loo.h"
 #include "kernels_linalg.hip"
+#include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
@@ -239,6 +241,10 @@ struct bohip_gp : gp_streams {
     // two-objective scoring (bohip_gp_score_mo / bohip_mo_ehvi_values): the front's corners and heights, 2 BOHIP_MO_FRONT_MAX + 3
     // doubles made on first use; everything else lives in ensure_con's block with C = 1
     DBuf<double> mo_front;
+    // leave-one-out (bohip_gp_loo / bohip_gp_loo_grad): ONE block of vectors (layout::loo), and for the gradient one more matrix of
+    // the model's size, Z = cK^-1 diag(sqrt c); both made on first use, nothing in them outlives a call
+    DBuf<char> loo_ws;
+    DBuf<double> dZ;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
@@ -2466,6 +2472,21 @@ int bohip_gp_mll(bohip_gp* g, double* mll) {
     return 0;
 }
 
+// cK^-1 = W'W into the lower 128-tiles of dS:  (W'W)_ij = sum_{k >= max(i,j)} W'[i][k] W'[j][k]  (both gradients: the marginal
+// likelihood's and the leave-one-out log-probability's)
+static int kinv_into_scratch(bohip_gp* g) {
+    const int64_t ld = g->ld;
+    const int T = row_tiles(g);
+    t_begin(g, "kinv");
+    GemmNTParams p{};
+    p.A = g->dWT; p.lda = ld; p.B = g->dWT; p.ldb = ld; p.C = g->dS; p.ldc = ld;
+    p.mt = T; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0;
+    p.klo_from_m = 1; p.klo_from_n = 1; p.diag_skip = 1; p.row0 = 0; p.col0 = 0;
+    CHK(launch_gemm_nt(g, p));
+    t_end(g);
+    return 0;
+}
+
 int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_mean, double* d_kern) {
     if (!g || !mll || !d_lognoise || !d_mean || !d_kern) return fail(BOHIP_E_ARG, "null argument");
     HIPCHK(hipSetDevice(g->device));
@@ -2477,17 +2498,9 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     }
     CHK(ensure_fresh(g));
     const int64_t N = g->n, ld = g->ld;
-    const int T = row_tiles(g), NP = g->d + 3;
+    const int NP = g->d + 3;
     hipLaunchKernelGGL(k_mll, dim3(1), dim3(256), 0, g->stream, g->dL, ld, N, g->dr, g->dalpha, g->dmll);
-    t_begin(g, "kinv");
-    {
-        GemmNTParams p{};  // cK^-1 = W'W, lower 128-tiles only:  (W'W)_ij = sum_{k >= max(i,j)} W'[i][k] W'[j][k]
-        p.A = g->dWT; p.lda = ld; p.B = g->dWT; p.ldb = ld; p.C = g->dS; p.ldc = ld;
-        p.mt = T; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0;
-        p.klo_from_m = 1; p.klo_from_n = 1; p.diag_skip = 1; p.row0 = 0; p.col0 = 0;
-        CHK(launch_gemm_nt(g, p));
-    }
-    t_end(g);
+    CHK(kinv_into_scratch(g));
     t_begin(g, "dmll_reduce");
     const int rpb = 32;
     dim3 grid((unsigned)((N + 255) / 256), (unsigned)((N + rpb - 1) / rpb));
@@ -2509,6 +2522,104 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     HIPCHK(hipMemcpyAsync(h, g->dmll, 8 * (size_t)(nout + 1), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = h[0]; *d_lognoise = h[1]; *d_mean = h[2];
+    for (int k = 0; k <= nl; ++k) d_kern[k] = h[3 + k];
+    return 0;
+}
+
+// ---- leave-one-out cross-validation (kernels_loo.hip, include/bohip_loo.h) ----------------------------------------
+static int ensure_loo(bohip_gp* g, layout::LooWs* w) {
+    const size_t nv = (size_t)g->ld + 256;   // (as dalpha / dr / dt: k_trimv_stream reads whole chunks of 256, masked by index)
+    HIPCHK(g->loo_ws.reserve(layout::loo(nullptr, DMAX + 4, nv, w), g->stream));
+    layout::loo(g->loo_ws, DMAX + 4, nv, w);
+    return 0;
+}
+// kappa from the resident W', then every per-point value and their sum into w.out[0]: the two launches both symbols share
+static int loo_values(bohip_gp* g, const layout::LooWs& w) {
+    const int64_t N = g->n;
+    t_begin(g, "loo_kappa");
+    hipLaunchKernelGGL(k_loo_kappa, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, g->stream, g->dWT, g->ld, N, w.kappa);
+    hipLaunchKernelGGL(k_loo_finish, dim3(1), dim3(256), 0, g->stream, g->dy, g->dalpha, w.kappa, N, w.mu, w.var, w.logp, w.q, w.sc, w.out);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_gp_loo(bohip_gp* g, double* mu, double* var, double* logp, double* total) {
+    if (!g || !total) return fail(BOHIP_E_ARG, "null argument");
+    HIPCHK(hipSetDevice(g->device));
+    if (g->n == 0) { *total = 0.0; return 0; }
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    layout::LooWs w;
+    CHK(ensure_loo(g, &w));
+    CHK(loo_values(g, w));
+    const size_t nb = (size_t)g->n * 8;
+    if (mu) HIPCHK(hipMemcpyAsync(mu, w.mu, nb, hipMemcpyDeviceToHost, g->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, w.var, nb, hipMemcpyDeviceToHost, g->stream));
+    if (logp) HIPCHK(hipMemcpyAsync(logp, w.logp, nb, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(total, w.out, 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_loo_grad(bohip_gp* g, double* total, double* d_lognoise, double* d_mean, double* d_kern) {
+    if (!g || !total || !d_lognoise || !d_mean || !d_kern) return fail(BOHIP_E_ARG, "null argument");
+    HIPCHK(hipSetDevice(g->device));
+    const int iso = kern_iso(g->kern), nl = iso ? 1 : g->d;
+    if (g->n == 0) {
+        *total = 0.0; *d_lognoise = 0.0; *d_mean = 0.0;
+        for (int k = 0; k <= nl; ++k) d_kern[k] = 0.0;
+        return 0;
+    }
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    CHK(one_time_kernel_setup());
+    const int64_t N = g->n, ld = g->ld;
+    const int T = row_tiles(g), NP = g->d + 3;
+    layout::LooWs w;
+    CHK(ensure_loo(g, &w));
+    HIPCHK(g->dZ.reserve((size_t)ld * ld, g->stream));
+    CHK(loo_values(g, w));
+    t_begin(g, "loo_b");
+    CHK(launch_rows_trimv(g, g->dW, N, w.q, 1, w.t, 0));    // b = cK^-1 q = W'(W q), as alpha
+    CHK(launch_rows_trimv(g, g->dWT, N, w.t, 1, w.b, 1));
+    t_end(g);
+    CHK(kinv_into_scratch(g));
+    t_begin(g, "loo_m");
+    {
+        // Z = cK^-1 diag(sqrt c) over the whole padded square, then M = Z Z' over the full contraction range into the lower
+        // 128-tiles of dS (cK^-1 is dead once Z exists)
+        const unsigned nt = (unsigned)(T * (TILE / 64));
+        hipLaunchKernelGGL(k_loo_scale, dim3(nt, nt), dim3(256), 0, g->stream, g->dS, ld, N, w.sc, g->dZ);
+        HIPCHK(hipGetLastError());
+        GemmNTParams p{};
+        p.A = g->dZ; p.lda = ld; p.B = g->dZ; p.ldb = ld; p.C = g->dS; p.ldc = ld;
+        p.mt = T; p.nt64 = 2 * T; p.kc = T * (TILE / KC); p.alpha = 1.0; p.beta = 0.0; p.diag_skip = 1; p.row0 = 0; p.col0 = 0;
+        CHK(launch_gemm_nt(g, p));
+    }
+    t_end(g);
+    t_begin(g, "dloo_reduce");
+    const int rpb = 32;
+    dim3 grid((unsigned)((N + 255) / 256), (unsigned)((N + rpb - 1) / rpb));
+    const int64_t nblocks = (int64_t)grid.x * grid.y;
+    HIPCHK(g->ddmll_parts.reserve((size_t)nblocks * NP, g->stream));
+    const KernelHyper hp = make_hyper(g);
+    const double noise_var = std::exp(2.0 * g->lognoise);
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_dloo_parts<DT, true>), (k_dloo_parts<DT, false>), grid, dim3(256), 0, g->stream, g->dX, N, hp, noise_var,
+                   g->dS, ld, g->dalpha, w.b, rpb, g->ddmll_parts);
+    });
+    const int nout = nl + 3;
+    hipLaunchKernelGGL(k_dmll_final, dim3(nout), dim3(256), 0, g->stream, g->ddmll_parts, nblocks, NP, g->d, iso, w.out + 1);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    double h[DMAX + 4];
+    HIPCHK(hipMemcpyAsync(h, w.out, 8 * (size_t)(nout + 1), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    *total = h[0]; *d_lognoise = h[1]; *d_mean = h[2];
     for (int k = 0; k <= nl; ++k) d_kern[k] = h[3 + k];
     return 0;
 }

@@ -157,6 +157,16 @@ size_t ens_io(const void* base, size_t H, size_t P, size_t Rc, size_t d, size_t 
     w->best = w->blk + nblk;
     return c.total();
 }
+// leave-one-out: [total | gradient slots (n_out) | kappa | mu | var | logp | q | sqrt c | t = W q | b = W't], the vectors nv each
+// and 16-byte aligned (nv covers the 256-wide chunks k_trimv_stream reads its right-hand sides in)
+struct LooWs { double *out, *kappa, *mu, *var, *logp, *q, *sc, *t, *b; };
+inline size_t loo(const void* base, size_t n_out, size_t nv, LooWs* w) {
+    Carve c(base);
+    w->out = c.take<double>(n_out);
+    w->kappa = c.take<double>(nv, 16); w->mu = c.take<double>(nv, 16); w->var = c.take<double>(nv, 16); w->logp = c.take<double>(nv, 16);
+    w->q = c.take<double>(nv, 16); w->sc = c.take<double>(nv, 16); w->t = c.take<double>(nv, 16); w->b = c.take<double>(nv, 16);
+    return c.total();
+}
 // the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
 // [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
 // Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the

@@ -222,6 +222,17 @@ class ElasticGPE:
         observations) nor changed."""
         return _mll_grad_batch(self._lib, self._h, Theta, want_grad)
 
+    def loo(self):
+        """Leave-one-out cross-validation at the observations (bohip_gp_loo): LOO(mu, var, logp, total, z), the
+        prediction of every noisy y_i from all the others, its log-probability, their sum and the standardised residuals
+        z = (y - mu) / sqrt(var) of Jones, Schonlau & Welch 1998.  The model is not changed."""
+        return _loo(self._lib, self._h, self._y)
+
+    def loo_grad(self):
+        """(total, dlogNoise, dmean, dkern): the LOO predictive log-probability and its gradient, in the slots of mll_grad
+        (bohip_gp_loo_grad; Rasmussen & Williams 5.4.2)."""
+        return _loo_grad(self._lib, self._h, (1 if self.kernel.iso else self.dim) + 1)
+
     # -- predict_f / scoring ------------------------------------------------------------------------
     def predict_f(self, xs):
         xs = _cols(xs, self.dim)
@@ -524,6 +535,32 @@ def _mll_grad_batch(lib, h, Theta, want_grad):
     check(lib.bohip_gp_mll_grad_batch(h, H, _ptr(Theta), _ptr(mll), _ptr(G) if want_grad else None,
                                       pivot.ctypes.data_as(C.POINTER(C.c_int64))))
     return mll, G, pivot
+
+
+class LOO:
+    """Result of loo(): mu[n], var[n] (the leave-one-out prediction of each noisy observation from the others, mu in the sign the
+    model stores y), logp[n] (its log-probability), total (their sum) and z[n] = (y - mu) / sqrt(var), the standardised residuals."""
+    __slots__ = ("mu", "var", "logp", "total", "z")
+
+    def __init__(self, mu, var, logp, total, z):
+        self.mu, self.var, self.logp, self.total, self.z = mu, var, logp, total, z
+
+    def __iter__(self):
+        return iter((self.mu, self.var, self.logp, self.total, self.z))
+
+
+def _loo(lib, h, y):
+    n = y.size
+    mu, var, logp, total = np.empty(n), np.empty(n), np.empty(n), C.c_double()
+    check(lib.bohip_gp_loo(h, _ptr(mu), _ptr(var), _ptr(logp), C.byref(total)))
+    return LOO(mu, var, logp, total.value, (y - mu) / np.sqrt(var))
+
+
+def _loo_grad(lib, h, nk):
+    t, dn, dm = C.c_double(), C.c_double(), C.c_double()
+    dk = np.empty(nk)
+    check(lib.bohip_gp_loo_grad(h, C.byref(t), C.byref(dn), C.byref(dm), _ptr(dk)))
+    return t.value, dn.value, dm.value, dk
 
 
 class EnsembleScore:

@@ -234,6 +234,18 @@ class MultiGPE:
 
         return _mll_grad_batch(self._lib, self._lib.bohip_mgp_handle(self._h, 0), Theta, want_grad)
 
+    def loo(self):
+        """ElasticGPE.loo (bohip_gp_loo) on the FIRST replica, as mll_grad_batch: every device holds the whole model."""
+        from .model import _loo
+
+        return _loo(self._lib, self._lib.bohip_mgp_handle(self._h, 0), self._y)
+
+    def loo_grad(self):
+        """ElasticGPE.loo_grad (bohip_gp_loo_grad) on the FIRST replica."""
+        from .model import _loo_grad
+
+        return _loo_grad(self._lib, self._lib.bohip_mgp_handle(self._h, 0), (1 if self.kernel.iso else self.dim) + 1)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """Posterior sample paths (ElasticGPE.draw_paths, bohip_gp_paths_draw) on the FIRST replica, as sample_joint: the object is
         self-contained and lives on that device.  Close it before the model."""

@@ -354,6 +354,7 @@ include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ense
 include("BOHipMES.jl")     # max-value entropy search over a candidate set (include/bohip_mes.h): mes, mes_values, mes_gumbel, MaxValueEntropySearch
 include("BOHipCon.jl")     # constrained optimisation (include/bohip_con.h): predict_grad, con_values, score_constrained
 include("BOHipMO.jl")      # two objectives (include/bohip_mo.h): mo_front, ehvi_values, score_mo
+include("BOHipLOO.jl")     # leave-one-out cross-validation (include/bohip_loo.h): loo, loo_grad
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
