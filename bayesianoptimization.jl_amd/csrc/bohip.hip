@@ -287,7 +287,8 @@ static bool kern_iso(int id) { return id == KERN_SEISO || id == KERN_MAT52ISO ||
 
 // The kernels that evaluate k are instantiated twice (template argument LOW): the Matérn 1/2 and 3/2 families run their own
 // instantiation, so the SE / Matérn 5/2 one compiles to the code it had before those families existed.
-static bool fam_low(const KernelHyper& h) { return h.fam == FAM_M12 || h.fam == FAM_M32; }
+static bool fam_low(int fam) { return fam == FAM_M12 || fam == FAM_M32; }
+static bool fam_low(const KernelHyper& h) { return fam_low(h.fam); }
 #define LAUNCH_FAM(lo, k_low, k_std, ...) \
     do { if (lo) hipLaunchKernelGGL(k_low, __VA_ARGS__); else hipLaunchKernelGGL(k_std, __VA_ARGS__); } while (0)
 
@@ -505,13 +506,18 @@ static void read_dev_knobs() {
 #endif
 }
 
-static int one_time_kernel_setup() {
-    // the >64 KB dynamic-LDS opt-in is a per-device function attribute
-    static bool done_dev[64] = {false};
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    bool& done = done_dev[dev & 63];
-    if (done) return 0;
+// The per-device once-guard: the > 64 KB dynamic-LDS opt-in is a per-device function attribute, so every place that launches such a
+// kernel keeps one table of its own (a function-local static; one per instantiation of a template) and runs its set-up through this at
+// the point of first use.  A set-up that fails is tried again by the next call.
+template <class Setup>
+static int once_per_device(bool (&done)[64], int device, Setup&& setup) {
+    if (done[device & 63]) return 0;
+    CHK(setup());
+    done[device & 63] = true;
+    return 0;
+}
+
+static int kernel_setup_of_this_device() {
     HIPCHK(hipFuncSetAttribute((const void*)k_potf2_inv, hipFuncAttributeMaxDynamicSharedMemorySize, POTF2_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)k_gemm_nt, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_trigemm_sq, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
@@ -539,8 +545,13 @@ static int one_time_kernel_setup() {
     if (const char* e = getenv("BOHIP_SAMPLE_MFMA_MIN")) g_sample_mfma_min = std::max(1, atoi(e));
     g_chol_df_strict = getenv("BOHIP_CHOL_DF_STRICT") != nullptr;
     read_dev_knobs();
-    done = true;
     return 0;
+}
+static int one_time_kernel_setup() {
+    static bool done[64] = {false};
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    return once_per_device(done, dev, kernel_setup_of_this_device);
 }
 
 // ---- A1-A3: full rebuild --------------------------------------------------------------------------
@@ -2666,18 +2677,29 @@ static int ensure_ens_io(bohip_gp* g, int64_t H, int P, int64_t Rc, int64_t R, i
     return 0;
 }
 extern "C++" {
+// What every kernel over settings reads, for the settings from h0 on: the observations, the launch's rows of theta and pivot (of the
+// call's io block), the slabs and the plan's shapes -- on any of FitArgs, EnsFactorArgs, EnsScoreArgs, EnsGradArgs (y where it has one)
+template <class A, class = void>
+struct has_y : std::false_type {};
+template <class A>
+struct has_y<A, std::void_t<decltype(std::declval<A&>().y)>> : std::true_type {};
+template <class A>
+static void fill_fit_args(A& a, const bohip_gp* g, const FitPlan& pl, const double* d_theta, long long* d_pivot, int64_t h0) {
+    a.X = g->dX; a.theta = d_theta + (size_t)h0 * pl.P; a.ws = g->fit_ws; a.pivot = d_pivot + h0;
+    if constexpr (has_y<A>::value) a.y = g->dy;
+    a.slab = (long long)pl.slab; a.N = (int)g->n; a.M = pl.M; a.ld = pl.ld; a.d = g->d; a.fam = kern_family(g->kern); a.iso = pl.iso; a.P = pl.P;
+}
 template <int DT>
-static int fit_launch(bohip_gp* g, const FitArgs& a, int64_t Hc, bool lo) {
-    const size_t lds = fit_lds_bytes(a.M, DT);
-    // the > 64 KB dynamic-LDS opt-in is a per-device function attribute
-    static bool done_dev[64] = {false};
-    if (!done_dev[g->device & 63]) {
+static int fit_launch(bohip_gp* g, const FitArgs& a, int64_t Hc) {
+    static bool done[64] = {false};
+    CHK(once_per_device(done, g->device, [&]() -> int {
         const int most = (int)fit_lds_bytes(BOHIP_FIT_NMAX, DT);
         HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
         HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        done_dev[g->device & 63] = true;
-    }
-    LAUNCH_FAM(lo, (k_mll_batch<DT, true>), (k_mll_batch<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), lds, g->stream, a);
+        return 0;
+    }));
+    LAUNCH_FAM(fam_low(a.fam), (k_mll_batch<DT, true>), (k_mll_batch<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), fit_lds_bytes(a.M, DT),
+               g->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2700,8 +2722,7 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
     HIPCHK(hipSetDevice(g->device));
     CHK(ensure_observations_resident(g));
     const FitPlan pl = fit_plan(g, H);
-    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld;
-    const size_t slab = pl.slab;
+    const int P = pl.P;
     const int64_t Hc = pl.Hc;
     g->ens_factor_ok = false;   // (the slabs are about to be written)
     CHK(ensure_fit_ws(g, pl));
@@ -2713,17 +2734,15 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
     unsigned long long* d_stamps = io.stamps;
     const bool trace = getenv("BOHIP_FIT_TRACE") != nullptr;   // tools: the stage times of the first workgroup on stderr
     HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
-    const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
     for (int64_t h0 = 0; h0 < H; h0 += Hc) {
         FitArgs a{};
-        a.X = g->dX; a.y = g->dy; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.mll = d_mll + h0;
-        a.grad = grad ? d_grad + (size_t)h0 * P : nullptr; a.pivot = d_pivot + h0;
+        fill_fit_args(a, g, pl, d_theta, d_pivot, h0);
+        a.mll = d_mll + h0;
+        a.grad = grad ? d_grad + (size_t)h0 * P : nullptr;
         a.stamps = (trace && h0 == 0) ? d_stamps : nullptr;
-        a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = g->d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
         const int64_t hc = std::min(Hc, H - h0);
-        CHK(dispatch_dt(g->d, [&](auto dt) { return fit_launch<decltype(dt)::value>(g, a, hc, lo); }));
+        CHK(dispatch_dt(g->d, [&](auto dt) { return fit_launch<decltype(dt)::value>(g, a, hc); }));
     }
-    std::vector<long long> hpiv;
     HIPCHK(hipMemcpyAsync(mll, d_mll, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
     if (grad) HIPCHK(hipMemcpyAsync(grad, d_grad, (size_t)H * P * 8, hipMemcpyDeviceToHost, g->stream));
     if (pivot) {
@@ -2745,37 +2764,59 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
 extern "C++" {
 template <int DT>
 static int ens_attrs(bohip_gp* g) {
-    static bool done_dev[64] = {false};   // the > 64 KB dynamic-LDS opt-in is a per-device function attribute
-    if (done_dev[g->device & 63]) return 0;
-    const int f = (int)fit_lds_bytes(BOHIP_FIT_NMAX, DT), s = (int)ens_score_lds_bytes(BOHIP_FIT_NMAX, DT);
-    HIPCHK(hipFuncSetAttribute((const void*)k_ens_factor<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f));
-    HIPCHK(hipFuncSetAttribute((const void*)k_ens_factor<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, f));
-    HIPCHK(hipFuncSetAttribute((const void*)k_ens_score<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
-    HIPCHK(hipFuncSetAttribute((const void*)k_ens_score<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
-    done_dev[g->device & 63] = true;
-    return 0;
+    static bool done[64] = {false};
+    return once_per_device(done, g->device, [&]() -> int {
+        const int f = (int)fit_lds_bytes(BOHIP_FIT_NMAX, DT), s = (int)ens_score_lds_bytes(BOHIP_FIT_NMAX, DT);
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_factor<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, f));
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_factor<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, f));
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_score<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_score<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        return 0;
+    });
 }
 template <int DT>
-static int ens_factor_launch(bohip_gp* g, const EnsFactorArgs& a, int64_t Hc, bool lo) {
+static int ens_factor_launch(bohip_gp* g, const EnsFactorArgs& a, int64_t Hc) {
     CHK(ens_attrs<DT>(g));
-    LAUNCH_FAM(lo, (k_ens_factor<DT, true>), (k_ens_factor<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), fit_lds_bytes(a.M, DT), g->stream, a);
+    LAUNCH_FAM(fam_low(a.fam), (k_ens_factor<DT, true>), (k_ens_factor<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), fit_lds_bytes(a.M, DT),
+               g->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
 template <int DT>
-static int ens_score_launch(bohip_gp* g, const EnsScoreArgs& a, int64_t Hc, bool lo) {
+static int ens_score_launch(bohip_gp* g, const EnsScoreArgs& a, int64_t Hc) {
     CHK(ens_attrs<DT>(g));
     const dim3 grid((unsigned)((a.R + ENS_TC - 1) / ENS_TC), (unsigned)Hc);
-    LAUNCH_FAM(lo, (k_ens_score<DT, true>), (k_ens_score<DT, false>), grid, dim3(ENS_THREADS), ens_score_lds_bytes(a.M, DT), g->stream, a);
+    LAUNCH_FAM(fam_low(a.fam), (k_ens_score<DT, true>), (k_ens_score<DT, false>), grid, dim3(ENS_THREADS), ens_score_lds_bytes(a.M, DT), g->stream,
+               a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the gradient's launch (include/bohip_ens_grad.h, kernels_ens.hip: k_ens_alpha, k_ens_grad, k_ens_reduce_grad)
+template <int DT>
+static int ens_grad_launch(bohip_gp* g, const EnsGradArgs& a, int64_t Hc) {
+    static bool done[64] = {false};
+    CHK(once_per_device(done, g->device, [&]() -> int {
+        const int s = (int)ens_grad_lds_bytes(BOHIP_FIT_NMAX, DT);
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
+        return 0;
+    }));
+    const dim3 grid((unsigned)((a.R + ENS_TC - 1) / ENS_TC), (unsigned)Hc);
+    LAUNCH_FAM(fam_low(a.fam), (k_ens_grad<DT, true>), (k_ens_grad<DT, false>), grid, dim3(ENS_THREADS), ens_grad_lds_bytes(a.M, DT), g->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
 }   // extern "C++"
 
-int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
-                       const double* xs, int64_t R, double* scores, double* each, double* mu, double* var, int64_t* pivot,
-                       bohip_best* best) {
-    if (!g || !theta || !xs || !best) return fail(BOHIP_E_ARG, "null argument");
+// The one driver of bohip_gp_score_ens (with_grad false: grad and each_grad are not read) and bohip_gp_score_ens_grad: the checks, the
+// plan, the factor step, the candidate-chunk loop, the reduce tail, the copies and the alive / NOTPD epilogue.  The gradient form adds
+// ens_alpha (k_ens_alpha after every factor launch), d more planes a candidate, k_ens_grad for k_ens_score, k_ens_reduce_grad, two
+// outputs -- and the factor reuse: it alone remembers the factors it leaves (resident settings only) and skips the factor step on a
+// call with the same observations and byte-identical theta.  The value form clears that memory and never sets it.
+static int ens_drive(bohip_gp* g, bool with_grad, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
+                     const double* xs, int64_t R, double* scores, double* grad, double* each, double* each_grad, double* mu, double* var,
+                     int64_t* pivot, bohip_best* best) {
+    if (!g || !theta || !xs || !best || (with_grad && !grad)) return fail(BOHIP_E_ARG, "null argument");
     if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
     if (R < 1) return fail(BOHIP_E_ARG, "R must be >= 1");
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id (Thompson draws are not averaged)");
@@ -2796,171 +2837,41 @@ int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     CHK(ensure_observations_resident(g));
-    const FitPlan pl = fit_plan(g, std::min<int64_t>(H, 65535));   // (settings are the y dimension of k_ens_score's grid)
-    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld, d = g->d;
-    const size_t slab = pl.slab;
+    const FitPlan pl = fit_plan(g, std::min<int64_t>(H, 65535));   // (settings are the y dimension of the score kernels' grid)
+    const int P = pl.P, M = pl.M, d = g->d;
     const int64_t Hc = pl.Hc;
-    g->ens_factor_ok = false;   // (the slabs are about to be written)
-    CHK(ensure_fit_ws(g, pl));
-    // candidates per chunk: the three H x Rc planes stay within 64 MiB (at least one tile, at most 16384 candidates)
-    const int64_t Rc = std::min<int64_t>(round_up(R, ENS_TC),
-                                         std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (24 * H)) / ENS_TC * ENS_TC)));
+    const bool resident = H <= Hc;   // every setting's factor fits the workspace at once: factor once, before the candidate chunks
+    // the slabs hold these very factors: every setting at once, left by a gradient call for byte-identical theta and the same
+    // observations (M follows from the observations; the kernel and d of a handle never change)
+    const bool reuse = with_grad && resident && g->ens_factor_ok && g->ens_version == g->data_version &&
+                       g->ens_theta.size() == (size_t)H * P && g->ens_pivot.size() == (size_t)H &&
+                       std::memcmp(g->ens_theta.data(), theta, (size_t)H * P * 8) == 0;
+    g->ens_factor_ok = false;   // (the slabs are about to be written; whatever fails below: the next call factors)
+    CHK(ensure_fit_ws(g, pl));   // (never grows on a reuse: the same theta and M ask for the same bytes)
+    if (with_grad) HIPCHK(g->ens_alpha.reserve((size_t)Hc * M, g->stream));
+    // candidates per chunk: the H x Rc planes -- each, mu, var and with the gradient its d components -- stay within 64 MiB (at least
+    // one tile, at most 16384 candidates)
+    const int64_t planes = with_grad ? 3 + (int64_t)d : 3;
+    const int64_t Rc = std::min<int64_t>(
+        round_up(R, ENS_TC), std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (8 * planes * H)) / ENS_TC * ENS_TC)));
     int64_t nblk = 0;
     for (int64_t r0 = 0; r0 < R; r0 += Rc) nblk += (std::min(Rc, R - r0) + 255) / 256;
     static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(Best) == 16, "pivot words, records");
     layout::EnsIo<Best> io;
-    CHK(ensure_ens_io(g, H, P, Rc, R, nblk, false, &io));
-    double *d_theta = io.theta, *d_w = io.w, *d_wt = io.wt, *d_xs = io.xs, *d_each = io.each, *d_mu = io.mu, *d_var = io.var, *d_scores = io.scores;
-    long long* d_pivot = io.pivot;
-    Best *d_blk = io.blk, *d_best = io.best;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
-    if (weights) HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
-    const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
+    CHK(ensure_ens_io(g, H, P, Rc, R, nblk, with_grad, &io));
+    HIPCHK(hipMemcpyAsync(io.theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
+    if (weights) HIPCHK(hipMemcpyAsync(io.w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
+    if (reuse) HIPCHK(hipMemcpyAsync(io.pivot, g->ens_pivot.data(), (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
     auto factor = [&](int64_t h0, int64_t hc) -> int {
         EnsFactorArgs a{};
-        a.X = g->dX; a.y = g->dy; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0;
-        a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
+        fill_fit_args(a, g, pl, io.theta, io.pivot, h0);
         t_begin(g, "ens_factor");
-        CHK(dispatch_dt(d, [&](auto dt) { return ens_factor_launch<decltype(dt)::value>(g, a, hc, lo); }));
+        CHK(dispatch_dt(d, [&](auto dt) { return ens_factor_launch<decltype(dt)::value>(g, a, hc); }));
         t_end(g);
-        return 0;
-    };
-    const bool resident = H <= Hc;   // every setting's factor fits the workspace at once: factor once, before the candidate chunks
-    if (resident) CHK(factor(0, H));
-    int64_t blk0 = 0;
-    for (int64_t r0 = 0; r0 < R; r0 += Rc) {
-        const int64_t rc = std::min(Rc, R - r0);
-        HIPCHK(hipMemcpyAsync(d_xs, xs + (size_t)r0 * d, (size_t)rc * d * 8, hipMemcpyHostToDevice, g->stream));
-        for (int64_t h0 = 0; h0 < H; h0 += Hc) {
-            const int64_t hc = std::min(Hc, H - h0);
-            if (!resident) CHK(factor(h0, hc));
-            EnsScoreArgs a{};
-            a.X = g->dX; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0; a.xs = d_xs;
-            a.each = d_each + (size_t)h0 * Rc; a.mu = d_mu + (size_t)h0 * Rc; a.var = d_var + (size_t)h0 * Rc;
-            a.slab = (long long)slab; a.ldr = Rc; a.R = rc; a.ap = ap;
-            a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
-            t_begin(g, "ens_score");
-            CHK(dispatch_dt(d, [&](auto dt) { return ens_score_launch<decltype(dt)::value>(g, a, hc, lo); }));
-            t_end(g);
-        }
-        t_begin(g, "ens_reduce");
-        if (r0 == 0) hipLaunchKernelGGL(k_ens_weights, dim3(1), dim3(64), 0, g->stream, weights ? d_w : nullptr, d_pivot, (long long)H, d_wt);
-        const int nb256 = (int)((rc + 255) / 256);
-        hipLaunchKernelGGL(k_ens_reduce, dim3(nb256), dim3(256), 0, g->stream, d_each, (long long)Rc, d_wt, (long long)H, (long long)rc,
-                           (long long)r0, d_scores, d_blk + blk0);
-        HIPCHK(hipGetLastError());
-        t_end(g);
-        blk0 += nb256;
-        for (auto pr : {std::make_pair(each, d_each), std::make_pair(mu, d_mu), std::make_pair(var, d_var)})
-            if (pr.first)
-                HIPCHK(hipMemcpy2DAsync(pr.first + r0, (size_t)R * 8, pr.second, (size_t)Rc * 8, (size_t)rc * 8, (size_t)H, hipMemcpyDeviceToHost,
-                                        g->stream));
-        if (r0 + Rc < R) HIPCHK(hipStreamSynchronize(g->stream));   // the chunk's planes and d_xs are free again
-    }
-    t_begin(g, "ens_reduce");
-    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, d_blk, (int)nblk, d_best, 0LL);
-    HIPCHK(hipGetLastError());
-    t_end(g);
-    std::vector<long long> hpiv((size_t)H);
-    Best hb{-INFINITY, -1};
-    HIPCHK(hipMemcpyAsync(hpiv.data(), d_pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(&hb, d_best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
-    if (scores) HIPCHK(hipMemcpyAsync(scores, d_scores, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    t_collect(g);
-    if (pivot) for (int64_t h = 0; h < H; ++h) pivot[h] = hpiv[(size_t)h];
-    double alive_w = 0.0;
-    int64_t alive = 0;
-    for (int64_t h = 0; h < H; ++h)
-        if (hpiv[(size_t)h] == 0) { ++alive; alive_w += weights ? weights[h] : 1.0; }
-    if (alive == 0 || !(alive_w > 0.0)) {
-        best->val = -INFINITY; best->idx = -1;
-        if (scores) for (int64_t j = 0; j < R; ++j) scores[j] = NAN;
-        return fail(BOHIP_E_NOTPD, alive == 0 ? "the factorisation failed at every hyper-parameter setting"
-                                              : "the factorisation failed at every hyper-parameter setting of positive weight");
-    }
-    best->val = hb.val; best->idx = hb.idx;
-    return 0;
-}
-
-// ---- its gradient (include/bohip_ens_grad.h, kernels_ens.hip: k_ens_alpha, k_ens_grad, k_ens_reduce_grad) --------------------------
-extern "C++" {
-template <int DT>
-static int ens_grad_launch(bohip_gp* g, const EnsGradArgs& a, int64_t Hc, bool lo) {
-    static bool done_dev[64] = {false};   // the > 64 KB dynamic-LDS opt-in is a per-device function attribute
-    if (!done_dev[g->device & 63]) {
-        const int s = (int)ens_grad_lds_bytes(BOHIP_FIT_NMAX, DT);
-        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
-        HIPCHK(hipFuncSetAttribute((const void*)k_ens_grad<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, s));
-        done_dev[g->device & 63] = true;
-    }
-    const dim3 grid((unsigned)((a.R + ENS_TC - 1) / ENS_TC), (unsigned)Hc);
-    LAUNCH_FAM(lo, (k_ens_grad<DT, true>), (k_ens_grad<DT, false>), grid, dim3(ENS_THREADS), ens_grad_lds_bytes(a.M, DT), g->stream, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-}   // extern "C++"
-
-int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
-                            const double* xs, int64_t R, double* scores, double* grad, double* each, double* each_grad, double* mu,
-                            double* var, int64_t* pivot, bohip_best* best) {
-    if (!g || !theta || !xs || !best || !grad) return fail(BOHIP_E_ARG, "null argument");
-    if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
-    if (R < 1) return fail(BOHIP_E_ARG, "R must be >= 1");
-    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id (Thompson draws are not averaged)");
-    AcqParams ap;
-    CHK(make_acq(acq_id, acq_params, &ap));
-    if (weights) {
-        double s = 0.0;
-        for (int64_t h = 0; h < H; ++h) {
-            if (!(weights[h] >= 0.0 && weights[h] < INFINITY)) return fail(BOHIP_E_ARG, "weights must be finite and >= 0");
-            s += weights[h];
-        }
-        if (!(s > 0.0)) return fail(BOHIP_E_ARG, "the weights sum to 0");
-    }
-    if (g->n == 0) return fail(BOHIP_E_STATE, "no observations");
-    if (g->n > BOHIP_FIT_NMAX)
-        return fail(BOHIP_E_UNSUPPORTED, "the marginalised acquisition takes at most " + std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " +
-                                             std::to_string(g->n));
-    HIPCHK(hipSetDevice(g->device));
-    t_reset(g);
-    CHK(ensure_observations_resident(g));
-    const FitPlan pl = fit_plan(g, std::min<int64_t>(H, 65535));   // (settings are the y dimension of k_ens_grad's grid)
-    const int iso = pl.iso, P = pl.P, M = pl.M, ld = pl.ld, d = g->d;
-    const size_t slab = pl.slab;
-    const int64_t Hc = pl.Hc;
-    const bool resident = H <= Hc;   // every setting's factor fits the workspace at once: factor once, before the candidate chunks
-    // the slabs hold these very factors: every setting at once, left by this symbol for byte-identical theta and the same observations
-    // (M follows from the observations; the kernel and d of a handle never change)
-    const bool reuse = resident && g->ens_factor_ok && g->ens_version == g->data_version && g->ens_theta.size() == (size_t)H * P &&
-                       g->ens_pivot.size() == (size_t)H && std::memcmp(g->ens_theta.data(), theta, (size_t)H * P * 8) == 0;
-    g->ens_factor_ok = false;   // (whatever fails below: the next call factors)
-    CHK(ensure_fit_ws(g, pl));   // (never grows on a reuse: the same theta and M ask for the same bytes)
-    HIPCHK(g->ens_alpha.reserve((size_t)Hc * M, g->stream));
-    // candidates per chunk: the (3 + d) H x Rc planes stay within 64 MiB (at least one tile, at most 16384 candidates)
-    const int64_t Rc = std::min<int64_t>(
-        round_up(R, ENS_TC), std::max<int64_t>(ENS_TC, std::min<int64_t>(16384, (((int64_t)64 << 20) / (8 * (3 + (int64_t)d) * H)) / ENS_TC * ENS_TC)));
-    int64_t nblk = 0;
-    for (int64_t r0 = 0; r0 < R; r0 += Rc) nblk += (std::min(Rc, R - r0) + 255) / 256;
-    layout::EnsIo<Best> io;
-    CHK(ensure_ens_io(g, H, P, Rc, R, nblk, true, &io));
-    double *d_theta = io.theta, *d_w = io.w, *d_wt = io.wt, *d_xs = io.xs, *d_each = io.each, *d_mu = io.mu, *d_var = io.var;
-    double *d_geach = io.geach, *d_scores = io.scores, *d_grad = io.grad;
-    long long* d_pivot = io.pivot;
-    Best *d_blk = io.blk, *d_best = io.best;
-    HIPCHK(hipMemcpyAsync(d_theta, theta, (size_t)H * P * 8, hipMemcpyHostToDevice, g->stream));
-    if (weights) HIPCHK(hipMemcpyAsync(d_w, weights, (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
-    if (reuse) HIPCHK(hipMemcpyAsync(d_pivot, g->ens_pivot.data(), (size_t)H * 8, hipMemcpyHostToDevice, g->stream));
-    const bool lo = kern_family(g->kern) == FAM_M12 || kern_family(g->kern) == FAM_M32;
-    auto factor = [&](int64_t h0, int64_t hc) -> int {
-        EnsFactorArgs a{};
-        a.X = g->dX; a.y = g->dy; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0;
-        a.slab = (long long)slab; a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
-        t_begin(g, "ens_factor");
-        CHK(dispatch_dt(d, [&](auto dt) { return ens_factor_launch<decltype(dt)::value>(g, a, hc, lo); }));
-        t_end(g);
+        if (!with_grad) return 0;
         t_begin(g, "ens_alpha");
-        hipLaunchKernelGGL(k_ens_alpha, dim3((unsigned)hc), dim3(256), 0, g->stream, g->fit_ws, d_pivot + h0, g->ens_alpha, (long long)slab, M, ld);
+        hipLaunchKernelGGL(k_ens_alpha, dim3((unsigned)hc), dim3(256), 0, g->stream, g->fit_ws, io.pivot + h0, g->ens_alpha, (long long)pl.slab, M,
+                           pl.ld);
         HIPCHK(hipGetLastError());
         t_end(g);
         return 0;
@@ -2969,52 +2880,54 @@ int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, i
     int64_t blk0 = 0;
     for (int64_t r0 = 0; r0 < R; r0 += Rc) {
         const int64_t rc = std::min(Rc, R - r0);
-        HIPCHK(hipMemcpyAsync(d_xs, xs + (size_t)r0 * d, (size_t)rc * d * 8, hipMemcpyHostToDevice, g->stream));
+        HIPCHK(hipMemcpyAsync(io.xs, xs + (size_t)r0 * d, (size_t)rc * d * 8, hipMemcpyHostToDevice, g->stream));
         for (int64_t h0 = 0; h0 < H; h0 += Hc) {
             const int64_t hc = std::min(Hc, H - h0);
             if (!resident) CHK(factor(h0, hc));
-            EnsGradArgs a{};
-            a.X = g->dX; a.theta = d_theta + (size_t)h0 * P; a.ws = g->fit_ws; a.pivot = d_pivot + h0; a.xs = d_xs;
-            a.each = d_each + (size_t)h0 * Rc; a.mu = d_mu + (size_t)h0 * Rc; a.var = d_var + (size_t)h0 * Rc;
-            a.slab = (long long)slab; a.ldr = Rc; a.R = rc; a.ap = ap;
-            a.N = (int)g->n; a.M = M; a.ld = ld; a.d = d; a.fam = kern_family(g->kern); a.iso = iso; a.P = P;
-            a.alpha = g->ens_alpha; a.geach = d_geach + (size_t)h0 * Rc * d;
-            t_begin(g, "ens_grad");
-            CHK(dispatch_dt(d, [&](auto dt) { return ens_grad_launch<decltype(dt)::value>(g, a, hc, lo); }));
+            EnsGradArgs a{};   // (k_ens_score takes its EnsScoreArgs base)
+            fill_fit_args(a, g, pl, io.theta, io.pivot, h0);
+            a.xs = io.xs; a.each = io.each + (size_t)h0 * Rc; a.mu = io.mu + (size_t)h0 * Rc; a.var = io.var + (size_t)h0 * Rc;
+            a.ldr = Rc; a.R = rc; a.ap = ap;
+            if (with_grad) { a.alpha = g->ens_alpha; a.geach = io.geach + (size_t)h0 * Rc * d; }
+            t_begin(g, with_grad ? "ens_grad" : "ens_score");
+            CHK(dispatch_dt(d, [&](auto dt) {
+                return with_grad ? ens_grad_launch<decltype(dt)::value>(g, a, hc) : ens_score_launch<decltype(dt)::value>(g, a, hc);
+            }));
             t_end(g);
         }
         t_begin(g, "ens_reduce");
-        if (r0 == 0) hipLaunchKernelGGL(k_ens_weights, dim3(1), dim3(64), 0, g->stream, weights ? d_w : nullptr, d_pivot, (long long)H, d_wt);
+        if (r0 == 0) hipLaunchKernelGGL(k_ens_weights, dim3(1), dim3(64), 0, g->stream, weights ? io.w : nullptr, io.pivot, (long long)H, io.wt);
         const int nb256 = (int)((rc + 255) / 256);
-        hipLaunchKernelGGL(k_ens_reduce, dim3(nb256), dim3(256), 0, g->stream, d_each, (long long)Rc, d_wt, (long long)H, (long long)rc,
-                           (long long)r0, d_scores, d_blk + blk0);
-        hipLaunchKernelGGL(k_ens_reduce_grad, dim3((unsigned)((rc * d + 255) / 256)), dim3(256), 0, g->stream, d_geach, (long long)(Rc * d), d_wt,
-                           (long long)H, (long long)(rc * d), d_grad + (size_t)r0 * d);
+        hipLaunchKernelGGL(k_ens_reduce, dim3(nb256), dim3(256), 0, g->stream, io.each, (long long)Rc, io.wt, (long long)H, (long long)rc,
+                           (long long)r0, io.scores, io.blk + blk0);
+        if (with_grad)
+            hipLaunchKernelGGL(k_ens_reduce_grad, dim3((unsigned)((rc * d + 255) / 256)), dim3(256), 0, g->stream, io.geach, (long long)(Rc * d),
+                               io.wt, (long long)H, (long long)(rc * d), io.grad + (size_t)r0 * d);
         HIPCHK(hipGetLastError());
         t_end(g);
         blk0 += nb256;
-        for (auto pr : {std::make_pair(each, d_each), std::make_pair(mu, d_mu), std::make_pair(var, d_var)})
+        for (auto pr : {std::make_pair(each, io.each), std::make_pair(mu, io.mu), std::make_pair(var, io.var)})
             if (pr.first)
                 HIPCHK(hipMemcpy2DAsync(pr.first + r0, (size_t)R * 8, pr.second, (size_t)Rc * 8, (size_t)rc * 8, (size_t)H, hipMemcpyDeviceToHost,
                                         g->stream));
-        if (each_grad)
-            HIPCHK(hipMemcpy2DAsync(each_grad + (size_t)r0 * d, (size_t)R * d * 8, d_geach, (size_t)Rc * d * 8, (size_t)rc * d * 8, (size_t)H,
+        if (with_grad && each_grad)
+            HIPCHK(hipMemcpy2DAsync(each_grad + (size_t)r0 * d, (size_t)R * d * 8, io.geach, (size_t)Rc * d * 8, (size_t)rc * d * 8, (size_t)H,
                                     hipMemcpyDeviceToHost, g->stream));
         if (r0 + Rc < R) HIPCHK(hipStreamSynchronize(g->stream));   // the chunk's planes and d_xs are free again
     }
     t_begin(g, "ens_reduce");
-    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, d_blk, (int)nblk, d_best, 0LL);
+    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, io.blk, (int)nblk, io.best, 0LL);
     HIPCHK(hipGetLastError());
     t_end(g);
     std::vector<long long> hpiv((size_t)H);
     Best hb{-INFINITY, -1};
-    HIPCHK(hipMemcpyAsync(hpiv.data(), d_pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(&hb, d_best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
-    if (scores) HIPCHK(hipMemcpyAsync(scores, d_scores, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(grad, d_grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(hpiv.data(), io.pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(&hb, io.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    if (scores) HIPCHK(hipMemcpyAsync(scores, io.scores, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (with_grad) HIPCHK(hipMemcpyAsync(grad, io.grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
-    if (resident) {   // the slabs and alpha now hold every setting's factor
+    if (with_grad && resident) {   // the slabs and alpha now hold every setting's factor
         g->ens_theta.assign(theta, theta + (size_t)H * P);
         g->ens_pivot = hpiv;
         g->ens_version = g->data_version;
@@ -3028,12 +2941,25 @@ int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, i
     if (alive == 0 || !(alive_w > 0.0)) {
         best->val = -INFINITY; best->idx = -1;
         if (scores) for (int64_t j = 0; j < R; ++j) scores[j] = NAN;
-        for (int64_t j = 0; j < R * d; ++j) grad[j] = NAN;
+        if (with_grad) for (int64_t j = 0; j < R * d; ++j) grad[j] = NAN;
         return fail(BOHIP_E_NOTPD, alive == 0 ? "the factorisation failed at every hyper-parameter setting"
                                               : "the factorisation failed at every hyper-parameter setting of positive weight");
     }
     best->val = hb.val; best->idx = hb.idx;
     return 0;
+}
+
+int bohip_gp_score_ens(bohip_gp* g, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
+                       const double* xs, int64_t R, double* scores, double* each, double* mu, double* var, int64_t* pivot,
+                       bohip_best* best) {
+    return ens_drive(g, false, acq_id, acq_params, H, theta, weights, xs, R, scores, nullptr, each, nullptr, mu, var, pivot, best);
+}
+
+int bohip_gp_score_ens_grad(bohip_gp* g, int acq_id, const double* acq_params, int64_t H, const double* theta, const double* weights,
+                            const double* xs, int64_t R, double* scores, double* grad, double* each, double* each_grad, double* mu,
+                            double* var, int64_t* pivot, bohip_best* best) {
+    if (!grad) return fail(BOHIP_E_ARG, "null argument");
+    return ens_drive(g, true, acq_id, acq_params, H, theta, weights, xs, R, scores, grad, each, each_grad, mu, var, pivot, best);
 }
 
 int bohip_gp_predict_dev(bohip_gp* g, const double* dXs, int64_t R, double* d_mu, double* d_var) {
@@ -3707,21 +3633,96 @@ static int con_make_params(const char* who, int acq_id, const double* acq_params
     }
     return 0;
 }
-// the combine and the record on g's stream (no synchronisation, no copies)
-static int con_combine_stage(bohip_gp* g, const ConParams& cp, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
-    const int nb = (int)std::min<int64_t>(CON_GRID_MAX, (R + 255) / 256);
-    t_begin(g, "con_combine");
-    if (partials || jac)
-        hipLaunchKernelGGL(k_con_combine<true>, dim3(nb), dim3(256), 0, g->stream, cp, (const double*)b.mu, (const double*)b.var, R, R, b.value,
-                           b.logfeas, b.pmu, b.pvar, (const double*)b.jmu, (const double*)b.jvar, (int64_t)R * g->d, g->d,
-                           jac ? b.grad : (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
-    else
-        hipLaunchKernelGGL(k_con_combine<false>, dim3(nb), dim3(256), 0, g->stream, cp, (const double*)b.mu, (const double*)b.var, R, R, b.value,
-                           b.logfeas, (double*)nullptr, (double*)nullptr, (const double*)nullptr, (const double*)nullptr, (int64_t)0, g->d,
-                           (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
+// The optional half of a stage's launch (k_con_combine and k_ehvi end in the same arguments), chosen in ONE place: the GRAD
+// instantiation with the partials' and the Jacobians' planes where either is asked for, else the plain one with nulls; the gradient
+// with jac; the per-block records with want_best.
+struct StageOuts {
+    bool grad_form;
+    double *pmu, *pvar;
+    const double *jmu, *jvar;
+    int64_t jplane;
+    double* grad;
+    Best* blocks;
+};
+static StageOuts stage_outs(const bohip_gp* g, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
+    StageOuts o{};
+    o.grad_form = partials || jac;
+    if (o.grad_form) { o.pmu = b.pmu; o.pvar = b.pvar; o.jmu = b.jmu; o.jvar = b.jvar; o.jplane = R * g->d; }
+    o.grad = jac ? b.grad : nullptr;
+    o.blocks = want_best ? b.blocks : nullptr;
+    return o;
+}
+// the end of a stage opened with t_begin: the record of its nb blocks
+static int stage_end(bohip_gp* g, const ConBufs& b, int nb, bool want_best) {
     if (want_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, b.blocks, nb, b.best, 0ll);
     HIPCHK(hipGetLastError());
     t_end(g);
+    return 0;
+}
+// the combine and the record on g's stream (no synchronisation, no copies)
+static int con_combine_stage(bohip_gp* g, const ConParams& cp, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
+    const int nb = (int)std::min<int64_t>(CON_GRID_MAX, (R + 255) / 256);
+    const StageOuts o = stage_outs(g, b, R, partials, jac, want_best);
+    t_begin(g, "con_combine");
+    hipLaunchKernelGGL(o.grad_form ? k_con_combine<true> : k_con_combine<false>, dim3(nb), dim3(256), 0, g->stream, cp, (const double*)b.mu,
+                       (const double*)b.var, R, R, b.value, b.logfeas, o.pmu, o.pvar, o.jmu, o.jvar, o.jplane, g->d, o.grad, o.blocks);
+    return stage_end(g, b, nb, want_best);
+}
+
+// ---- several models at the same candidates (bohip_gp_score_con, bohip_gp_score_mo) ------------------------------------------------------
+static hipError_t event_of(bohip_gp* m) { return m->ev_con ? hipSuccess : hipEventCreateWithFlags(&m->ev_con, hipEventDisableTiming); }
+
+// Row c of b's moments (and, with jac, Jacobians) is the posterior of models[c] at the R candidates Xs (host), every model on its OWN
+// stream and with no host wait: the candidates go to the device once, into the owner's dXs on the owner's stream (whatever the caller
+// put on that stream before is ahead of them); a handle other than the owner waits for that copy -- and has its timing reset -- at its
+// first appearance only, an event is recorded after each of its passes, and the owner's stream waits for all of them before this
+// returns, so the caller's stage goes on the owner's stream.  A handle may appear more than once, the owner included.  skip_row0:
+// models[0] is not evaluated and row 0 of mu and var is filled with 0xff bytes (NaN).  The caller has ensure_con's block on the
+// owner and ends the call with multi_download.
+static int multi_posterior(bohip_gp* owner, bohip_gp* const* models, int64_t n, bool skip_row0, const double* Xs, int64_t R, bool jac,
+                           const ConBufs& b) {
+    const int d = owner->d;
+    const int64_t c0 = skip_row0 ? 1 : 0;
+    t_reset(owner);
+    CHK(ensure_xs(owner, R));
+    HIPCHK(hipMemcpyAsync(owner->dXs, Xs, (size_t)R * d * 8, hipMemcpyHostToDevice, owner->stream));
+    if (std::any_of(models + c0, models + n, [&](bohip_gp* m) { return m != owner; })) {
+        HIPCHK(event_of(owner));
+        HIPCHK(hipEventRecord(owner->ev_con, owner->stream));
+    }
+    if (skip_row0) {
+        HIPCHK(hipMemsetAsync(b.mu, 0xff, (size_t)R * 8, owner->stream));
+        HIPCHK(hipMemsetAsync(b.var, 0xff, (size_t)R * 8, owner->stream));
+    }
+    for (int64_t c = c0; c < n; ++c) {
+        bohip_gp* m = models[c];
+        if (m != owner && std::find(models + c0, models + c, m) == models + c) {
+            t_reset(m);
+            HIPCHK(hipStreamWaitEvent(m->stream, owner->ev_con, 0));
+        }
+        const size_t o = (size_t)c * R;
+        CHK(posterior_grad_core(m, owner->dXs, R, b.mu + o, b.var + o, jac ? b.jmu + o * d : nullptr, jac ? b.jvar + o * d : nullptr));
+        if (m != owner) { HIPCHK(event_of(m)); HIPCHK(hipEventRecord(m->ev_con, m->stream)); }
+    }
+    for (int64_t c = c0; c < n; ++c)
+        if (models[c] != owner) HIPCHK(hipStreamWaitEvent(owner->stream, models[c]->ev_con, 0));
+    return 0;
+}
+// ... and the end of such a call, after the stage: the value, the gradient, every row of the moments and the record where asked
+// for, the one synchronisation, and the stage times of every handle that took part (a handle other than the owner once per
+// appearance, as ever: after the first collection there is nothing left, so one that appears twice reads empty)
+static int multi_download(bohip_gp* owner, bohip_gp* const* models, int64_t n, const ConBufs& b, int64_t R, double* score, double* grad,
+                          double* mu, double* var, bohip_best* best) {
+    const size_t m_bytes = (size_t)n * R * 8;
+    if (score) HIPCHK(hipMemcpyAsync(score, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, owner->stream));
+    if (grad) HIPCHK(hipMemcpyAsync(grad, b.grad, (size_t)R * owner->d * 8, hipMemcpyDeviceToHost, owner->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, b.mu, m_bytes, hipMemcpyDeviceToHost, owner->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, b.var, m_bytes, hipMemcpyDeviceToHost, owner->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, owner->stream));
+    HIPCHK(hipStreamSynchronize(owner->stream));
+    t_collect(owner);
+    for (int64_t c = 0; c < n; ++c)
+        if (models[c] != owner) t_collect(models[c]);
     return 0;
 }
 
@@ -3745,14 +3746,13 @@ int bohip_gp_predict_grad(bohip_gp* g, const double* Xs, int64_t R, double* mu, 
     return 0;
 }
 
-int bohip_con_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t C, const double* thresholds, const int* senses,
-                     const double* mu, const double* var, int64_t R, double* value, double* logfeas, double* dmu, double* dvar,
-                     bohip_best* best) {
-    if (!g) return fail(BOHIP_E_ARG, "con_values: null handle");
-    ConParams cp;
-    CHK(con_make_params("con_values", acq_id, acq_params, C, thresholds, senses, &cp));
-    if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "con_values: bad arguments");
-    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "con_values: dmu and dvar are given together or not at all");
+// A stage on the caller's moments (bohip_con_values, bohip_mo_ehvi_values; the callers have validated): `rows` x R of mu and var up
+// into ensure_con's block, stage(b) on g's stream, then value, logfeas where asked for, the partials [rows][R] with dmu, the record
+// with best, and the one synchronisation.  R == 0 touches no device.
+extern "C++" {
+template <class Stage>
+static int moments_to_values(bohip_gp* g, int64_t rows, const double* mu, const double* var, int64_t R, Stage&& stage, double* value,
+                             double* logfeas, double* dmu, double* dvar, bohip_best* best) {
     if (R == 0) {
         if (best) { best->val = -INFINITY; best->idx = -1; }
         return 0;
@@ -3760,11 +3760,11 @@ int bohip_con_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t 
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     ConBufs b{};
-    CHK(ensure_con(g, C, R, false, &b));
-    const size_t m = (size_t)(C + 1) * R * 8;
+    CHK(ensure_con(g, rows - 1, R, false, &b));
+    const size_t m = (size_t)rows * R * 8;
     HIPCHK(hipMemcpyAsync(b.mu, mu, m, hipMemcpyHostToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(b.var, var, m, hipMemcpyHostToDevice, g->stream));
-    CHK(con_combine_stage(g, cp, b, R, dmu != nullptr, false, best != nullptr));
+    CHK(stage(b));
     HIPCHK(hipMemcpyAsync(value, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (logfeas) HIPCHK(hipMemcpyAsync(logfeas, b.logfeas, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (dmu) {
@@ -3775,6 +3775,19 @@ int bohip_con_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t 
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;
+}
+}   // extern "C++"
+
+int bohip_con_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t C, const double* thresholds, const int* senses,
+                     const double* mu, const double* var, int64_t R, double* value, double* logfeas, double* dmu, double* dvar,
+                     bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "con_values: null handle");
+    ConParams cp;
+    CHK(con_make_params("con_values", acq_id, acq_params, C, thresholds, senses, &cp));
+    if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "con_values: bad arguments");
+    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "con_values: dmu and dvar are given together or not at all");
+    auto stage = [&](const ConBufs& b) { return con_combine_stage(g, cp, b, R, dmu != nullptr, false, best != nullptr); };
+    return moments_to_values(g, C + 1, mu, var, R, stage, value, logfeas, dmu, dvar, best);
 }
 
 int bohip_gp_score_con(bohip_gp* obj, int acq_id, const double* acq_params, int64_t C, bohip_gp* const* cons, const double* thresholds,
@@ -3800,51 +3813,14 @@ int bohip_gp_score_con(bohip_gp* obj, int acq_id, const double* acq_params, int6
     }
     HIPCHK(hipSetDevice(obj->device));
     const bool jac = grad != nullptr;
-    const int d = obj->d;
-    t_reset(obj);
-    CHK(ensure_xs(obj, R));
     ConBufs b{};
     CHK(ensure_con(obj, C, R, jac, &b));
-    HIPCHK(hipMemcpyAsync(obj->dXs, Xs, (size_t)R * d * 8, hipMemcpyHostToDevice, obj->stream));
-    auto event_of = [](bohip_gp* m) -> hipError_t {
-        return m->ev_con ? hipSuccess : hipEventCreateWithFlags(&m->ev_con, hipEventDisableTiming);
-    };
-    // the candidates are on the device once, in the objective's block: the constraints' streams wait for that copy, run their own
-    // posterior into the objective's block and are joined back before the combine -- no host wait in between
-    HIPCHK(event_of(obj));
-    if (C > 0) HIPCHK(hipEventRecord(obj->ev_con, obj->stream));
-    if (feas) {
-        HIPCHK(hipMemsetAsync(b.mu, 0xff, (size_t)R * 8, obj->stream));    // (row 0 is not computed: NaN)
-        HIPCHK(hipMemsetAsync(b.var, 0xff, (size_t)R * 8, obj->stream));
-    } else {
-        CHK(posterior_grad_core(obj, obj->dXs, R, b.mu, b.var, b.jmu, b.jvar));
-    }
-    for (int64_t c = 0; c < C; ++c) {
-        bohip_gp* m = cons[c];
-        if (m != obj) {
-            bool first = true;
-            for (int64_t e = 0; e < c; ++e) first = first && cons[e] != m;
-            if (first) { t_reset(m); HIPCHK(hipStreamWaitEvent(m->stream, obj->ev_con, 0)); }
-        }
-        const size_t o = (size_t)(c + 1) * R;
-        CHK(posterior_grad_core(m, obj->dXs, R, b.mu + o, b.var + o, jac ? b.jmu + o * d : nullptr, jac ? b.jvar + o * d : nullptr));
-        if (m != obj) { HIPCHK(event_of(m)); HIPCHK(hipEventRecord(m->ev_con, m->stream)); }
-    }
-    for (int64_t c = 0; c < C; ++c)
-        if (cons[c] != obj) HIPCHK(hipStreamWaitEvent(obj->stream, cons[c]->ev_con, 0));
+    bohip_gp* models[BOHIP_CON_CMAX + 1] = {obj};   // row 0 the objective (not computed under "Feasibility"), row c + 1 constraint c
+    std::copy_n(cons, C, models + 1);
+    CHK(multi_posterior(obj, models, C + 1, feas, Xs, R, jac, b));
     CHK(con_combine_stage(obj, cp, b, R, false, jac, best != nullptr));
-    const size_t m_bytes = (size_t)(C + 1) * R * 8;
-    if (score) HIPCHK(hipMemcpyAsync(score, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, obj->stream));
     if (logfeas) HIPCHK(hipMemcpyAsync(logfeas, b.logfeas, (size_t)R * 8, hipMemcpyDeviceToHost, obj->stream));
-    if (grad) HIPCHK(hipMemcpyAsync(grad, b.grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, obj->stream));
-    if (mu) HIPCHK(hipMemcpyAsync(mu, b.mu, m_bytes, hipMemcpyDeviceToHost, obj->stream));
-    if (var) HIPCHK(hipMemcpyAsync(var, b.var, m_bytes, hipMemcpyDeviceToHost, obj->stream));
-    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, obj->stream));
-    HIPCHK(hipStreamSynchronize(obj->stream));
-    t_collect(obj);
-    for (int64_t c = 0; c < C; ++c)
-        if (cons[c] != obj) t_collect(cons[c]);
-    return 0;
+    return multi_download(obj, models, C + 1, b, R, score, grad, mu, var, best);
 }
 
 // ---- two-objective optimisation (kernels_mo.hip, include/bohip_mo.h) ----------------------------------------------
@@ -3913,19 +3889,11 @@ static int mo_upload_front(bohip_gp* g, const std::vector<double>& fr) {
 // the EHVI and the record on g's stream (no synchronisation, no copies); b is ensure_con's block with C = 1
 static int mo_ehvi_stage(bohip_gp* g, int64_t n_front, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
     const int nb = (int)std::min<int64_t>(MO_GRID_MAX, (R + MO_CAND - 1) / MO_CAND);
+    const StageOuts o = stage_outs(g, b, R, partials, jac, want_best);
     t_begin(g, "mo_ehvi");
-    if (partials || jac)
-        hipLaunchKernelGGL(k_ehvi<true>, dim3(nb), dim3(256), 0, g->stream, (const double*)g->mo_front, (int)n_front, (const double*)b.mu,
-                           (const double*)b.var, R, R, b.value, b.pmu, b.pvar, (const double*)b.jmu, (const double*)b.jvar,
-                           (int64_t)R * g->d, g->d, jac ? b.grad : (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
-    else
-        hipLaunchKernelGGL(k_ehvi<false>, dim3(nb), dim3(256), 0, g->stream, (const double*)g->mo_front, (int)n_front, (const double*)b.mu,
-                           (const double*)b.var, R, R, b.value, (double*)nullptr, (double*)nullptr, (const double*)nullptr,
-                           (const double*)nullptr, (int64_t)0, g->d, (double*)nullptr, want_best ? b.blocks : (Best*)nullptr);
-    if (want_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, b.blocks, nb, b.best, 0ll);
-    HIPCHK(hipGetLastError());
-    t_end(g);
-    return 0;
+    hipLaunchKernelGGL(o.grad_form ? k_ehvi<true> : k_ehvi<false>, dim3(nb), dim3(256), 0, g->stream, (const double*)g->mo_front, (int)n_front,
+                       (const double*)b.mu, (const double*)b.var, R, R, b.value, o.pmu, o.pvar, o.jmu, o.jvar, o.jplane, g->d, o.grad, o.blocks);
+    return stage_end(g, b, nb, want_best);
 }
 
 int bohip_mo_ehvi_values(bohip_gp* g, const double* front, int64_t n_front, const double* ref, const double* mu, const double* var,
@@ -3935,28 +3903,11 @@ int bohip_mo_ehvi_values(bohip_gp* g, const double* front, int64_t n_front, cons
     CHK(mo_make_front("mo_ehvi_values", front, n_front, ref, &fr));
     if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "mo_ehvi_values: bad arguments");
     if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "mo_ehvi_values: dmu and dvar are given together or not at all");
-    if (R == 0) {
-        if (best) { best->val = -INFINITY; best->idx = -1; }
-        return 0;
-    }
-    HIPCHK(hipSetDevice(g->device));
-    t_reset(g);
-    ConBufs b{};
-    CHK(ensure_con(g, 1, R, false, &b));
-    CHK(mo_upload_front(g, fr));
-    const size_t m = (size_t)2 * R * 8;
-    HIPCHK(hipMemcpyAsync(b.mu, mu, m, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipMemcpyAsync(b.var, var, m, hipMemcpyHostToDevice, g->stream));
-    CHK(mo_ehvi_stage(g, n_front, b, R, dmu != nullptr, false, best != nullptr));
-    HIPCHK(hipMemcpyAsync(value, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
-    if (dmu) {
-        HIPCHK(hipMemcpyAsync(dmu, b.pmu, m, hipMemcpyDeviceToHost, g->stream));
-        HIPCHK(hipMemcpyAsync(dvar, b.pvar, m, hipMemcpyDeviceToHost, g->stream));
-    }
-    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    t_collect(g);
-    return 0;
+    auto stage = [&](const ConBufs& b) -> int {
+        CHK(mo_upload_front(g, fr));
+        return mo_ehvi_stage(g, n_front, b, R, dmu != nullptr, false, best != nullptr);
+    };
+    return moments_to_values(g, 2, mu, var, R, stage, value, nullptr, dmu, dvar, best);
 }
 
 int bohip_gp_score_mo(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64_t n_front, const double* ref, const double* Xs,
@@ -3973,43 +3924,14 @@ int bohip_gp_score_mo(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64
         return 0;
     }
     HIPCHK(hipSetDevice(obj0->device));
-    const bool jac = grad != nullptr, two = obj1 != obj0;
-    const int d = obj0->d;
-    t_reset(obj0);
-    CHK(ensure_xs(obj0, R));
+    const bool jac = grad != nullptr;
     ConBufs b{};
     CHK(ensure_con(obj0, 1, R, jac, &b));
-    HIPCHK(hipMemcpyAsync(obj0->dXs, Xs, (size_t)R * d * 8, hipMemcpyHostToDevice, obj0->stream));
-    auto event_of = [](bohip_gp* m) -> hipError_t {
-        return m->ev_con ? hipSuccess : hipEventCreateWithFlags(&m->ev_con, hipEventDisableTiming);
-    };
-    // the candidates are on the device once, in obj0's block: obj1's stream waits for that copy, runs its own posterior into obj0's
-    // block and is joined back before the EHVI -- no host wait in between (bohip_gp_score_con's scheme with one other model)
-    if (two) {
-        HIPCHK(event_of(obj0));
-        HIPCHK(hipEventRecord(obj0->ev_con, obj0->stream));
-        t_reset(obj1);
-        HIPCHK(hipStreamWaitEvent(obj1->stream, obj0->ev_con, 0));
-    }
-    CHK(mo_upload_front(obj0, fr));
-    CHK(posterior_grad_core(obj0, obj0->dXs, R, b.mu, b.var, b.jmu, b.jvar));
-    const size_t o = (size_t)R;
-    CHK(posterior_grad_core(obj1, obj0->dXs, R, b.mu + o, b.var + o, jac ? b.jmu + o * d : nullptr, jac ? b.jvar + o * d : nullptr));
-    if (two) {
-        HIPCHK(event_of(obj1));
-        HIPCHK(hipEventRecord(obj1->ev_con, obj1->stream));
-        HIPCHK(hipStreamWaitEvent(obj0->stream, obj1->ev_con, 0));
-    }
+    CHK(mo_upload_front(obj0, fr));   // (on obj0's stream, ahead of its posterior)
+    bohip_gp* const models[2] = {obj0, obj1};
+    CHK(multi_posterior(obj0, models, 2, false, Xs, R, jac, b));
     CHK(mo_ehvi_stage(obj0, n_front, b, R, false, jac, best != nullptr));
-    if (score) HIPCHK(hipMemcpyAsync(score, b.value, (size_t)R * 8, hipMemcpyDeviceToHost, obj0->stream));
-    if (grad) HIPCHK(hipMemcpyAsync(grad, b.grad, (size_t)R * d * 8, hipMemcpyDeviceToHost, obj0->stream));
-    if (mu) HIPCHK(hipMemcpyAsync(mu, b.mu, 2 * o * 8, hipMemcpyDeviceToHost, obj0->stream));
-    if (var) HIPCHK(hipMemcpyAsync(var, b.var, 2 * o * 8, hipMemcpyDeviceToHost, obj0->stream));
-    if (best) HIPCHK(hipMemcpyAsync(best, b.best, sizeof(Best), hipMemcpyDeviceToHost, obj0->stream));
-    HIPCHK(hipStreamSynchronize(obj0->stream));
-    t_collect(obj0);
-    if (two) t_collect(obj1);
-    return 0;
+    return multi_download(obj0, models, 2, b, R, score, grad, mu, var, best);
 }
 
 // ---- posterior sample paths (kernels_path.hip): pathwise conditioning with a random-feature prior ----------------

@@ -607,39 +607,36 @@ def _ens_weights(weights, H):
     return w
 
 
-def score_ensemble(model, acq, params, xs, Theta, weights=None, want_each=False, want_moments=False):
-    """ElasticGPE.score_ensemble for any model object: the device route where the model owns a handle whose library has
-    bohip_gp_score_ens and holds at most nmax observations, else the host loop over set_params_ + score / predict_f."""
+def _opt(a):
+    return _ptr(a) if a is not None else None
+
+
+def _ens_prologue(model, who, symbol, acq, params, xs, Theta, weights):
+    """What score_ensemble and score_ensemble_grad (`who`; `symbol` its device route) check and shape alike
+    -> (xs[d, R], Theta[H, P], w[H] or None, p, pivot[H] of zeros, lib, h); lib is None where the host route has to run: no handle, a
+    library without the symbol, or more than nmax observations."""
     if acq not in _lib.ACQ or acq == "ThompsonDraw":
-        raise ValueError(f"score_ensemble takes EI, PI, UCB, MI, MaxMean and LogEI, not {acq!r}")
+        raise ValueError(f"{who} takes EI, PI, UCB, MI, MaxMean and LogEI, not {acq!r}")
     xs = _cols(xs, model.dim)
     P = 2 + (1 if model.kernel.iso else model.dim) + 1
     Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
     if Theta.shape[1] != P:
         raise ValueError(f"Theta must have {P} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
-    H, R = Theta.shape[0], xs.shape[1]
-    w = _ens_weights(weights, H)
+    w = _ens_weights(weights, Theta.shape[0])
     p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
     if p.size < 2:
         p = np.concatenate([p, np.zeros(2 - p.size)])
     lib, h = getattr(model, "_lib", None), getattr(model, "_h", None)
-    if lib is not None and h and hasattr(lib, "bohip_gp_score_ens") and model.nobs <= _lib.FIT_NMAX:
-        scores = np.empty(R)
-        each = np.empty((H, R)) if want_each else None
-        mu = np.empty((H, R)) if want_moments else None
-        var = np.empty((H, R)) if want_moments else None
-        pivot = np.zeros(H, dtype=np.int64)
-        best = Best()
-        opt = lambda a: _ptr(a) if a is not None else None   # noqa: E731
-        check(lib.bohip_gp_score_ens(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), opt(w), _ptr(xs), R, _ptr(scores), opt(each), opt(mu),
-                                     opt(var), pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
-        return EnsembleScore(scores, best.val, best.idx, pivot, each, mu, var, "device")
-    # host route: one refit per setting; the model's own parameters come back whatever happens
+    device = lib is not None and h and hasattr(lib, symbol) and model.nobs <= _lib.FIT_NMAX
+    return xs, Theta, w, p, np.zeros(Theta.shape[0], dtype=np.int64), (lib if device else None), h
+
+
+def _ens_host_route(model, Theta, w, pivot, planes, evaluate):
+    """The host route of both: one refit per setting, the model's own parameters put back whatever happens.  `planes` are NaN-filled
+    arrays [H, ...], planes[0] the per-setting scores; evaluate() gives one row for each of them at the model's current parameters.  A
+    setting that is not finite or whose factorisation fails keeps NaN rows and gets its pivot.  -> (scores, best_val, best_idx)."""
+    H, nl = Theta.shape[0], Theta.shape[1] - 3
     saved = (model.kernel.ll.copy(), model.kernel.lsigma, model.logNoise, model.mean)
-    each = np.full((H, R), np.nan)
-    mu, var = (np.full((H, R), np.nan), np.full((H, R), np.nan)) if want_moments else (None, None)
-    pivot = np.zeros(H, dtype=np.int64)
-    nl = P - 3
     try:
         for k in range(H):
             row = Theta[k]
@@ -648,25 +645,45 @@ def score_ensemble(model, acq, params, xs, Theta, weights=None, want_each=False,
                 continue
             try:
                 model.set_params_(ll=row[2:2 + nl], lsigma=row[2 + nl], logNoise=row[0], beta=row[1])
-                each[k] = model.score(acq, p, xs)[0]
-                if want_moments:
-                    mu[k], var[k] = model.predict_f(xs)
+                for plane, value in zip(planes, evaluate()):
+                    plane[k] = value
             except _lib.NotPositiveDefinite:
                 piv = model.info(_lib.INFO_PIVOT) if hasattr(model, "info") else 1
                 pivot[k] = max(int(piv), 1)
-                each[k] = np.nan
-                if want_moments:
-                    mu[k], var[k] = np.nan, np.nan
+                for plane in planes:
+                    plane[k] = np.nan
     finally:
         model.set_params_(ll=saved[0], lsigma=saved[1], logNoise=saved[2], beta=saved[3].beta)
         model.mean = saved[3]
     if not np.any((pivot == 0) & ((w if w is not None else np.ones(H)) > 0.0)):
         raise _lib.NotPositiveDefinite(_lib.E_NOTPD, "the factorisation failed at every hyper-parameter setting")
-    scores = ensemble_average(each, w, pivot)
+    scores = ensemble_average(planes[0], w, pivot)
     best_val, best_idx = -math.inf, -1
     for j, v in enumerate(scores):
         if v > best_val:
             best_val, best_idx = float(v), j
+    return scores, best_val, best_idx
+
+
+def score_ensemble(model, acq, params, xs, Theta, weights=None, want_each=False, want_moments=False):
+    """ElasticGPE.score_ensemble for any model object: the device route where the model owns a handle whose library has
+    bohip_gp_score_ens and holds at most nmax observations, else the host loop over set_params_ + score / predict_f."""
+    xs, Theta, w, p, pivot, lib, h = _ens_prologue(model, "score_ensemble", "bohip_gp_score_ens", acq, params, xs, Theta, weights)
+    H, R = Theta.shape[0], xs.shape[1]
+    if lib is not None:
+        scores = np.empty(R)
+        each = np.empty((H, R)) if want_each else None
+        mu = np.empty((H, R)) if want_moments else None
+        var = np.empty((H, R)) if want_moments else None
+        best = Best()
+        check(lib.bohip_gp_score_ens(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), _opt(w), _ptr(xs), R, _ptr(scores), _opt(each), _opt(mu),
+                                     _opt(var), pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
+        return EnsembleScore(scores, best.val, best.idx, pivot, each, mu, var, "device")
+    each = np.full((H, R), np.nan)
+    mu, var = (np.full((H, R), np.nan), np.full((H, R), np.nan)) if want_moments else (None, None)
+    scores, best_val, best_idx = _ens_host_route(
+        model, Theta, w, pivot, [each, mu, var] if want_moments else [each],
+        lambda: (model.score(acq, p, xs)[0],) + (tuple(model.predict_f(xs)) if want_moments else ()))
     return EnsembleScore(scores, best_val, best_idx, pivot, each if want_each else None, mu, var, "host")
 
 
@@ -676,63 +693,26 @@ def score_ensemble_grad(model, acq, params, xs, Theta, weights=None, want_each=F
     the model owns a handle whose library has the symbol and holds at most nmax observations; else the host loop over set_params_ +
     score_grad, the model's own parameters put back whatever happens.  Both average each gradient component by ensemble_average's
     rule; a failed setting has NaN rows and takes no part."""
-    if acq not in _lib.ACQ or acq == "ThompsonDraw":
-        raise ValueError(f"score_ensemble_grad takes EI, PI, UCB, MI, MaxMean and LogEI, not {acq!r}")
-    xs = _cols(xs, model.dim)
-    d = model.dim
-    P = 2 + (1 if model.kernel.iso else d) + 1
-    Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
-    if Theta.shape[1] != P:
-        raise ValueError(f"Theta must have {P} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
-    H, R = Theta.shape[0], xs.shape[1]
-    w = _ens_weights(weights, H)
-    p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
-    if p.size < 2:
-        p = np.concatenate([p, np.zeros(2 - p.size)])
-    lib, h = getattr(model, "_lib", None), getattr(model, "_h", None)
-    if lib is not None and h and hasattr(lib, "bohip_gp_score_ens_grad") and model.nobs <= _lib.FIT_NMAX:
+    xs, Theta, w, p, pivot, lib, h = _ens_prologue(model, "score_ensemble_grad", "bohip_gp_score_ens_grad", acq, params, xs, Theta, weights)
+    H, R, d = Theta.shape[0], xs.shape[1], model.dim
+    if lib is not None:
         scores = np.empty(R)
         grad = np.empty((d, R), order="F")                        # (the library's [R][d] row-major)
         each = np.empty((H, R)) if want_each else None
         eg = np.empty((H, R, d)) if want_each else None
-        pivot = np.zeros(H, dtype=np.int64)
         best = Best()
-        opt = lambda a: _ptr(a) if a is not None else None   # noqa: E731
-        check(lib.bohip_gp_score_ens_grad(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), opt(w), _ptr(xs), R, _ptr(scores), _ptr(grad), opt(each),
-                                          opt(eg), None, None, pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
+        check(lib.bohip_gp_score_ens_grad(h, _lib.ACQ[acq], _ptr(p), H, _ptr(Theta), _opt(w), _ptr(xs), R, _ptr(scores), _ptr(grad), _opt(each),
+                                          _opt(eg), None, None, pivot.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(best)))
         res = EnsembleScore(scores, best.val, best.idx, pivot, each, None, None, "device")
         return (res, grad, eg.transpose(0, 2, 1)) if want_each else (res, grad)
-    # host route: one refit per setting; the model's own parameters come back whatever happens
-    saved = (model.kernel.ll.copy(), model.kernel.lsigma, model.logNoise, model.mean)
-    each = np.full((H, R), np.nan)
-    eg = np.full((H, d, R), np.nan)
-    pivot = np.zeros(H, dtype=np.int64)
-    nl = P - 3
-    try:
-        for k in range(H):
-            row = Theta[k]
-            if not np.all(np.isfinite(row)):
-                pivot[k] = 1
-                continue
-            try:
-                model.set_params_(ll=row[2:2 + nl], lsigma=row[2 + nl], logNoise=row[0], beta=row[1])
-                sc, g = model.score_grad(acq, p, xs)
-                each[k], eg[k] = sc, np.asarray(g).reshape(d, R)
-            except _lib.NotPositiveDefinite:
-                piv = model.info(_lib.INFO_PIVOT) if hasattr(model, "info") else 1
-                pivot[k] = max(int(piv), 1)
-                each[k], eg[k] = np.nan, np.nan
-    finally:
-        model.set_params_(ll=saved[0], lsigma=saved[1], logNoise=saved[2], beta=saved[3].beta)
-        model.mean = saved[3]
-    if not np.any((pivot == 0) & ((w if w is not None else np.ones(H)) > 0.0)):
-        raise _lib.NotPositiveDefinite(_lib.E_NOTPD, "the factorisation failed at every hyper-parameter setting")
-    scores = ensemble_average(each, w, pivot)
+    each, eg = np.full((H, R), np.nan), np.full((H, d, R), np.nan)
+
+    def evaluate():
+        sc, g = model.score_grad(acq, p, xs)
+        return sc, np.asarray(g).reshape(d, R)
+
+    scores, best_val, best_idx = _ens_host_route(model, Theta, w, pivot, [each, eg], evaluate)
     grad = np.asfortranarray(ensemble_average(eg.reshape(H, d * R), w, pivot).reshape(d, R))
-    best_val, best_idx = -math.inf, -1
-    for j, v in enumerate(scores):
-        if v > best_val:
-            best_val, best_idx = float(v), j
     res = EnsembleScore(scores, best_val, best_idx, pivot, each if want_each else None, None, None, "host")
     return (res, grad, eg) if want_each else (res, grad)
 
