@@ -52,7 +52,8 @@ class MAPGPOptimizer(ModelOptimizer):
 
     ``objective = "mll"`` (the default, the reference's) maximises the log marginal likelihood; ``"loo"`` (an extension) the
     leave-one-out predictive log-probability (Rasmussen & Williams 5.4.2; bohip_gp_loo_grad), in the single search
-    and, with ``restarts > 1``, one set_params_ + loo_grad per start and step at any N."""
+    and, with ``restarts > 1``, one batched device evaluation of all starts per step up to 512 observations
+    (bohip_gp_loo_grad_batch), one set_params_ + loo_grad per start and step above."""
 
     def __init__(self, every=10, objective="mll", **kwargs):
         if objective not in ("mll", "loo"):
@@ -284,10 +285,16 @@ def _multistart_map(fg_batch, x0, lo, hi, restarts, maxeval, rng, startwidth=3.0
 _FIT_BATCH_MIN_H = ((64, 2), (128, 2), (256, 2), (512, 8))
 
 
-def _fit_batched(n, H, nmax):
+# The same for the leave-one-out objective (loo_grad_batch against set_params_ + loo_grad per column).  Measured
+# (profiles/loo_batch_ab.txt, tools/time_loo_batch.py at H = 2, 8, 32): a cell is batched where every batched run beat every loop
+# run by more than the spread; the entry is the smallest measured H from which that holds.
+_LOO_BATCH_MIN_H = ((64, 2), (128, 2), (256, 8), (512, 32))
+
+
+def _fit_batched(n, H, nmax, table=_FIT_BATCH_MIN_H):
     if n > nmax:
         return False
-    for size, hmin in _FIT_BATCH_MIN_H:
+    for size, hmin in table:
         if n <= size:
             return H >= hmin
     return False
@@ -298,20 +305,23 @@ def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
     constants of Theta's rows.  A device model of a size the batched call takes, and wins at, evaluates all columns in one launch;
     otherwise (or for a model without the call) every column is a set_params_ + mll_grad, at any N.  want_grad=False (the slice
     sampler): the same dispatch, value only -- the gradient is None, the batched call forms no inverse and the loop calls mll.
-    opt["objective"] == "loo": the leave-one-out log-probability through the loop, set_params_ + loo_grad per column (it has no
-    batched form)."""
+    opt["objective"] == "loo": the leave-one-out log-probability, all columns in one loo_grad_batch where the model has the call
+    and _LOO_BATCH_MIN_H says so, otherwise set_params_ + loo_grad (value only: loo) per column."""
     loo = opt.get("objective", "mll") == "loo"
     mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
     base = np.concatenate([[model.logNoise, model.mean.beta if isinstance(model.mean, MeanConst) else 0.0], model.kernel.ll,
                            [model.kernel.lsigma]])
     idx = ([0] if opt["noise"] else []) + ([1] if mean_free else []) + (list(range(2, 2 + nk)) if opt["kern"] else [])
     assert len(idx) == p
-    batched = not loo and hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
+    if loo:
+        batched = hasattr(model, "loo_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1], _LOO_BATCH_MIN_H)
+    else:
+        batched = hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
 
     def fg_batched(X):
         Theta = np.tile(base, (X.shape[1], 1))
         Theta[:, idx] = X.T
-        mll, G, piv = model.mll_grad_batch(Theta, want_grad)
+        mll, G, piv = (model.loo_grad_batch if loo else model.mll_grad_batch)(Theta, want_grad)
         return np.where(piv == 0, mll, -np.inf), np.ascontiguousarray(G[:, idx].T) if want_grad else None
 
     def fg_loop(X):
@@ -320,7 +330,7 @@ def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
             apply(X[:, r])
             try:
                 if not want_grad:
-                    f[r] = model.mll()
+                    f[r] = model.loo().total if loo else model.mll()
                     continue
                 m, dn, dm, dk = model.loo_grad() if loo else model.mll_grad()
             except NotPositiveDefinite:

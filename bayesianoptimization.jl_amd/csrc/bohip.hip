@@ -28,6 +28,7 @@
 #include "../../include/bohip_con.h"
 #include "../../include/bohip_mo.h"
 #include "../../include/bohip_loo.h"
+#include "../../include/bohip_loo_batch.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_chol.hip"
@@ -245,6 +246,9 @@ struct bohip_gp : gp_streams {
     // the model's size, Z = cK^-1 diag(sqrt c); both made on first use, nothing in them outlives a call
     DBuf<char> loo_ws;
     DBuf<double> dZ;
+    // batched leave-one-out (bohip_gp_loo_grad_batch): [logp H x N] (layout::loo_batch_io), made when logp is asked for; the rest
+    // of the call lives in fit_ws and fit_io
+    DBuf<char> loo_batch_io;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
@@ -2689,17 +2693,17 @@ static void fill_fit_args(A& a, const bohip_gp* g, const FitPlan& pl, const doub
     if constexpr (has_y<A>::value) a.y = g->dy;
     a.slab = (long long)pl.slab; a.N = (int)g->n; a.M = pl.M; a.ld = pl.ld; a.d = g->d; a.fam = kern_family(g->kern); a.iso = pl.iso; a.P = pl.P;
 }
-template <int DT>
+template <int DT, bool LOO>
 static int fit_launch(bohip_gp* g, const FitArgs& a, int64_t Hc) {
     static bool done[64] = {false};
     CHK(once_per_device(done, g->device, [&]() -> int {
         const int most = (int)fit_lds_bytes(BOHIP_FIT_NMAX, DT);
-        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
-        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, true, LOO>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+        HIPCHK(hipFuncSetAttribute((const void*)k_mll_batch<DT, false, LOO>, hipFuncAttributeMaxDynamicSharedMemorySize, most));
         return 0;
     }));
-    LAUNCH_FAM(fam_low(a.fam), (k_mll_batch<DT, true>), (k_mll_batch<DT, false>), dim3((unsigned)Hc), dim3(FIT_THREADS), fit_lds_bytes(a.M, DT),
-               g->stream, a);
+    LAUNCH_FAM(fam_low(a.fam), (k_mll_batch<DT, true, LOO>), (k_mll_batch<DT, false, LOO>), dim3((unsigned)Hc), dim3(FIT_THREADS),
+               fit_lds_bytes(a.M, DT), g->stream, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2712,24 +2716,32 @@ int bohip_gp_mll_batch_dims(bohip_gp* g, int64_t* P, int64_t* nmax) {
     return 0;
 }
 
-int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double* mll, double* grad, int64_t* pivot) {
-    if (!g || !theta || !mll) return fail(BOHIP_E_ARG, "null argument");
+// Both batched objectives (bohip_gp_mll_grad_batch, and with loo bohip_gp_loo_grad_batch of include/bohip_loo_batch.h): the plan, the
+// workspace, theta up, one launch per Hc settings, the rows down.  value: mll[H] or total[H]; logp: leave-one-out only.
+static int fit_batch(bohip_gp* g, bool loo, int64_t H, const double* theta, double* value, double* grad, double* logp, int64_t* pivot) {
+    if (!g || !theta || !value) return fail(BOHIP_E_ARG, "null argument");
     if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
     if (g->n == 0) return fail(BOHIP_E_STATE, "no observations");
     if (g->n > BOHIP_FIT_NMAX)
-        return fail(BOHIP_E_UNSUPPORTED, "the batched marginal likelihood takes at most " + std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " +
-                                             std::to_string(g->n) + " (bohip_gp_mll_grad has no limit)");
+        return fail(BOHIP_E_UNSUPPORTED, std::string("the batched ") + (loo ? "leave-one-out objective" : "marginal likelihood") + " takes at most " +
+                                             std::to_string(BOHIP_FIT_NMAX) + " observations, the model has " + std::to_string(g->n) + " (" +
+                                             (loo ? "bohip_gp_loo_grad" : "bohip_gp_mll_grad") + " has no limit)");
     HIPCHK(hipSetDevice(g->device));
     CHK(ensure_observations_resident(g));
     const FitPlan pl = fit_plan(g, H);
     const int P = pl.P;
-    const int64_t Hc = pl.Hc;
+    const int64_t Hc = pl.Hc, N = g->n;
     g->ens_factor_ok = false;   // (the slabs are about to be written)
     CHK(ensure_fit_ws(g, pl));
     layout::FitIo io;
     HIPCHK(g->fit_io.reserve(layout::fit_io(nullptr, (size_t)H, (size_t)P, FIT_STAGES, &io), g->stream));
     layout::fit_io(g->fit_io, (size_t)H, (size_t)P, FIT_STAGES, &io);
-    double *d_theta = io.theta, *d_mll = io.mll, *d_grad = io.grad;
+    layout::LooBatchIo lio{nullptr};
+    if (logp) {
+        HIPCHK(g->loo_batch_io.reserve(layout::loo_batch_io(nullptr, (size_t)H, (size_t)N, &lio), g->stream));
+        layout::loo_batch_io(g->loo_batch_io, (size_t)H, (size_t)N, &lio);
+    }
+    double *d_theta = io.theta, *d_value = io.mll, *d_grad = io.grad;
     long long* d_pivot = io.pivot;
     unsigned long long* d_stamps = io.stamps;
     const bool trace = getenv("BOHIP_FIT_TRACE") != nullptr;   // tools: the stage times of the first workgroup on stderr
@@ -2737,14 +2749,19 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
     for (int64_t h0 = 0; h0 < H; h0 += Hc) {
         FitArgs a{};
         fill_fit_args(a, g, pl, d_theta, d_pivot, h0);
-        a.mll = d_mll + h0;
+        a.mll = d_value + h0;
         a.grad = grad ? d_grad + (size_t)h0 * P : nullptr;
+        a.logp = logp ? lio.logp + (size_t)h0 * N : nullptr;
         a.stamps = (trace && h0 == 0) ? d_stamps : nullptr;
         const int64_t hc = std::min(Hc, H - h0);
-        CHK(dispatch_dt(g->d, [&](auto dt) { return fit_launch<decltype(dt)::value>(g, a, hc); }));
+        CHK(dispatch_dt(g->d, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            return loo ? fit_launch<DT, true>(g, a, hc) : fit_launch<DT, false>(g, a, hc);
+        }));
     }
-    HIPCHK(hipMemcpyAsync(mll, d_mll, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(value, d_value, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
     if (grad) HIPCHK(hipMemcpyAsync(grad, d_grad, (size_t)H * P * 8, hipMemcpyDeviceToHost, g->stream));
+    if (logp) HIPCHK(hipMemcpyAsync(logp, lio.logp, (size_t)H * N * 8, hipMemcpyDeviceToHost, g->stream));
     if (pivot) {
         static_assert(sizeof(long long) == sizeof(int64_t), "pivot words");
         HIPCHK(hipMemcpyAsync(pivot, d_pivot, (size_t)H * 8, hipMemcpyDeviceToHost, g->stream));
@@ -2754,10 +2771,22 @@ int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double*
     HIPCHK(hipStreamSynchronize(g->stream));
     if (trace) {   // wall_clock64 ticks at 100 MHz; a stage that did not run (value only, failed row) keeps its old stamp
         auto us = [&](int i) { return st[i] >= st[i - 1] ? (double)(st[i] - st[i - 1]) * 0.01 : 0.0; };
-        std::fprintf(stderr, "bohip fit stages N=%lld d=%d H=%lld us: build %.1f chol %.1f value %.1f inverse %.1f grad %.1f\n", (long long)g->n, g->d,
-                     (long long)H, us(1), us(2), us(3), grad ? us(4) : 0.0, grad ? us(5) : 0.0);
+        if (loo)
+            std::fprintf(stderr, "bohip loo stages N=%lld d=%d H=%lld us: build %.1f chol %.1f value %.1f inverse %.1f product %.1f grad %.1f\n",
+                         (long long)g->n, g->d, (long long)H, us(1), us(2), us(3), us(4), grad ? us(5) : 0.0, grad ? us(6) : 0.0);
+        else
+            std::fprintf(stderr, "bohip fit stages N=%lld d=%d H=%lld us: build %.1f chol %.1f value %.1f inverse %.1f grad %.1f\n", (long long)g->n,
+                         g->d, (long long)H, us(1), us(2), us(3), grad ? us(4) : 0.0, grad ? us(5) : 0.0);
     }
     return 0;
+}
+
+int bohip_gp_mll_grad_batch(bohip_gp* g, int64_t H, const double* theta, double* mll, double* grad, int64_t* pivot) {
+    return fit_batch(g, false, H, theta, mll, grad, nullptr, pivot);
+}
+
+int bohip_gp_loo_grad_batch(bohip_gp* g, int64_t H, const double* theta, double* total, double* grad, double* logp, int64_t* pivot) {
+    return fit_batch(g, true, H, theta, total, grad, logp, pivot);
 }
 
 // ---- acquisition marginalised over hyper-parameter settings (include/bohip_ens.h, kernels_ens.hip) --------------------------------

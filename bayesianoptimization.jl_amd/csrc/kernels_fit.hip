@@ -23,6 +23,19 @@
 //   grad     the single pass 1/2 sum (alpha_i alpha_j - cK^-1_ij) dcK_ij/dtheta of k_dmll_parts (same expressions per family),
 //            thread = column, row phases by wave group, then shuffles and a fixed tree over the 8 waves; output in get_params
 //            order [logNoise, mean, ll..., logsig], an iso kernel folds its d length entries into one.
+//
+// k_mll_batch<DT, LOW, true> is the leave-one-out objective at the same H settings (bohip_gp_loo_grad_batch in
+// include/bohip_loo_batch.h): the same stages up to and including the inverse (which a value-only call needs too:
+// kappa = diag cK^-1), then, with alpha in LDS, cK^-1 in the lower triangle of B and slab A dead,
+//   finish   kappa_i = B[i][i], q_i = alpha_i / kappa_i (into zs), c_i = 1/2 (1 / kappa_i + q_i^2) (sqrt c into PB[0 .. M)),
+//            logp_i = 1/2 log kappa_i - 1/2 alpha_i q_i - 1/2 log 2 pi, total = sum_{i < N} logp_i in a fixed order; the padding rows
+//            i >= N are masked by index: q_i = c_i = 0.  A value-only call ends here.
+//   b        b = cK^-1 q (into PB[M .. 2 M)): one thread per row, row i left of the diagonal then column i below it, j ascending
+//   product  Mm = cK^-1 diag(c) cK^-1, lower triangle into slab A: per 16-column block K the panel P[i][k] = cK^-1(i, 16 K + k)
+//            sqrt c_{16 K + k} (B read at (max, min)) is staged in PA and applied as a rank-16 update of every lower 16 x 16 block,
+//            the one panel as both operands
+//   grad     the gradient pass with the weight G_ij = 1/2 (b_i alpha_j + alpha_i b_j) - Mm_ij, the mean slot sum_i b_i: what
+//            k_dloo_parts (kernels_loo.hip) states for the whole chip
 #include "gemm_core.h"   // mfma444
 
 namespace bohip {
@@ -31,15 +44,17 @@ constexpr int FIT_THREADS = 512;
 constexpr int FIT_NB = 16;          // panel width = block size
 constexpr int FIT_LP = FIT_NB + 1;  // row stride of every LDS panel image (fragment reads and row writes conflict-free)
 constexpr int FIT_XROWS = 32;       // rows of X staged per chunk of the build / gradient passes
-constexpr int FIT_STAGES = 6;       // stage stamps of workgroup 0 (tools): start, build, chol, value, inverse, grad
+constexpr int FIT_STAGES = 7;       // stage stamps of workgroup 0 (tools): start, build, chol, value, inverse, grad; leave-one-out:
+                                    // ..., inverse, product (finish, b and Mm), grad
 
 struct FitArgs {
     const double* X;       // [N][d]
     const double* y;       // [N]
     const double* theta;   // [H][P]
     double* ws;            // [H][slab]
-    double* mll;           // [H]
+    double* mll;           // [H]  (leave-one-out: the total)
     double* grad;          // [H][P] or null
+    double* logp;          // [H][N] or null: leave-one-out only
     long long* pivot;      // [H]
     unsigned long long* stamps;   // [FIT_STAGES] wall-clock ticks of workgroup 0, or null
     long long slab;        // doubles per setting = (2 M + 1) ld
@@ -113,7 +128,18 @@ __device__ __forceinline__ double fit_tree8(const double* r, int stride) {
     return ((r[0] + r[stride]) + (r[2 * stride] + r[3 * stride])) + ((r[4 * stride] + r[5 * stride]) + (r[6 * stride] + r[7 * stride]));
 }
 
-template <int DT, bool LOW>
+// a row that failed: the value, the pivot, a zero gradient row and (leave-one-out) a NaN row of logp
+template <bool LOO>
+__device__ __forceinline__ void fit_fail_row(const FitArgs& a, int64_t h, int tid, long long pivot) {
+    if (tid == 0) { a.mll[h] = -INFINITY; a.pivot[h] = pivot; }
+    if (a.grad != nullptr && tid < a.P) a.grad[h * a.P + tid] = 0.0;
+    if constexpr (LOO) {
+        if (a.logp != nullptr)
+            for (int i = tid; i < a.N; i += FIT_THREADS) a.logp[h * a.N + i] = __builtin_nan("");
+    }
+}
+
+template <int DT, bool LOW, bool LOO = false>
 __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
     extern __shared__ double fit_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -143,8 +169,7 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
     bool finite = true;
     for (int k = 0; k < P; ++k) finite = finite && (fabs(th[k]) < INFINITY);   // (false for NaN too)
     if (!finite) {   // the same for every thread: nobody has met a barrier yet
-        if (tid == 0) { a.mll[h] = -INFINITY; a.pivot[h] = 1; }
-        if (want_grad && tid < P) gout[tid] = 0.0;
+        fit_fail_row<LOO>(a, h, tid, 1);
         return;
     }
     const double noise_var = exp(2.0 * th[0]);
@@ -269,8 +294,7 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
         __syncthreads();
     }
     if (bad != 0) {
-        if (tid == 0) { a.mll[h] = -INFINITY; a.pivot[h] = bad; }
-        if (want_grad && tid < P) gout[tid] = 0.0;
+        fit_fail_row<LOO>(a, h, tid, bad);
         return;
     }
     if (stamp) a.stamps[2] = wall_clock64();
@@ -282,18 +306,19 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
             const double z = A[(int64_t)M * ld + i];
             zs[i] = z;
             alpha[i] = 0.0;
-            if (i < N) s += -0.5 * z * z - log(A[(int64_t)i * ld + i]);
+            if constexpr (!LOO)
+                if (i < N) s += -0.5 * z * z - log(A[(int64_t)i * ld + i]);
         }
-        s = fit_wave_sum(s);
-        if (lane == 0) red[wave] = s;
-        __syncthreads();
-        if (tid == 0) {
-            a.mll[h] = fit_tree8(red, 1) - 0.5 * (double)N * log(2.0 * M_PI);
-            a.pivot[h] = 0;
+        if constexpr (!LOO) {
+            s = fit_wave_sum(s);
+            if (lane == 0) red[wave] = s;
+            __syncthreads();
+            if (tid == 0) a.mll[h] = fit_tree8(red, 1) - 0.5 * (double)N * log(2.0 * M_PI);
         }
+        if (tid == 0) a.pivot[h] = 0;
     }
     if (stamp) a.stamps[3] = wall_clock64();
-    if (!want_grad) return;
+    if (!LOO && !want_grad) return;
 
     // ---- W = L^-1 row block by row block, alpha and cK^-1 on the way ---------------------------------------------------------
     for (int K = 0; K < nb; ++K) {
@@ -375,7 +400,70 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
     __syncthreads();
     if (stamp) a.stamps[4] = wall_clock64();
 
-    // ---- gradient: 1/2 sum_ij (alpha_i alpha_j - cK^-1_ij) dcK_ij / dtheta over the lower triangle ---------------------------
+    [[maybe_unused]] double* const bv = PB + M;   // leave-one-out: b, M doubles behind sqrt c
+    if constexpr (LOO) {
+        double* const q = zs;    // (z is dead after the inverse)
+        double* const sc = PB;   // sqrt c, M doubles
+        // ---- finish: per point from kappa = diag cK^-1, and the total ------------------------------------------------------------
+        {
+            double s = 0.0;
+            for (int i = tid; i < M; i += FIT_THREADS) {
+                double qi = 0.0, ci = 0.0;
+                if (i < N) {   // (rows N .. M - 1 are padding: masked by index)
+                    const double kp = B[(int64_t)i * ld + i], al = alpha[i], v = 1.0 / kp;
+                    qi = al * v;
+                    ci = 0.5 * (v + qi * qi);
+                    const double lp = 0.5 * log(kp) - 0.5 * al * qi - 0.5 * log(2.0 * M_PI);
+                    if (a.logp != nullptr) a.logp[h * N + i] = lp;
+                    s += lp;
+                }
+                q[i] = qi;
+                sc[i] = sqrt(ci);
+            }
+            s = fit_wave_sum(s);
+            if (lane == 0) red[wave] = s;
+            __syncthreads();
+            if (tid == 0) a.mll[h] = fit_tree8(red, 1);
+        }
+        if (!want_grad) return;
+        // ---- b = cK^-1 q from the lower storage -----------------------------------------------------------------------------------
+        for (int i = tid; i < M; i += FIT_THREADS) {
+            double s = 0.0;
+            if (i < N) {
+                for (int j = 0; j < i; ++j) s += B[(int64_t)i * ld + j] * q[j];
+                for (int j = i; j < N; ++j) s += B[(int64_t)j * ld + i] * q[j];
+            }
+            bv[i] = s;
+        }
+        // ---- Mm = cK^-1 diag(c) cK^-1, lower triangle into A ------------------------------------------------------------------------
+        const int nlow = nb * (nb + 1) / 2;
+        for (int K = 0; K < nb; ++K) {
+            const int k0 = FIT_NB * K;
+            __syncthreads();   // (the previous panel's tasks have read PA; the first: sc is written, the inverse's tasks have read PA)
+            // rows above the block: cK^-1(i, k0 + k) = B[k0 + k][i], i fastest; rows from the block on: B[i][k0 + k], the block itself at (max, min)
+            for (int idx = tid; idx < FIT_NB * k0; idx += FIT_THREADS) {
+                const int k = idx / k0, i = idx - k * k0, c = k0 + k;
+                PA[i * FIT_LP + k] = (i < N && c < N) ? B[(int64_t)c * ld + i] * sc[c] : 0.0;
+            }
+            for (int idx = tid; idx < FIT_NB * (M - k0); idx += FIT_THREADS) {
+                const int i = k0 + idx / FIT_NB, k = idx % FIT_NB, c = k0 + k;
+                const int hi = i > c ? i : c, lo = i > c ? c : i;
+                PA[i * FIT_LP + k] = (i < N && c < N) ? B[(int64_t)hi * ld + lo] * sc[c] : 0.0;
+            }
+            __syncthreads();
+            for (int t = wave; t < nlow; t += FIT_THREADS / 64) {
+                int I, Jb;
+                fit_tri_decode(t, I, Jb);
+                fit_task16(A + (int64_t)(FIT_NB * I) * ld + FIT_NB * Jb, ld, PA + FIT_NB * I * FIT_LP, PA + FIT_NB * Jb * FIT_LP, lane, 1.0,
+                           K == 0, I == Jb, FIT_NB - 1);
+            }
+        }
+        __syncthreads();
+        if (stamp) a.stamps[5] = wall_clock64();
+    }
+
+    // ---- gradient: sum_ij G_ij dcK_ij / dtheta over the lower triangle, G = 1/2 (alpha alpha' - cK^-1), or for leave-one-out
+    //      1/2 (b alpha' + alpha b') - Mm ----------------------------------------------------------------------------------------
     double xj[DT], acc[DT], a_sig = 0.0, a_noise = 0.0, a_mean = 0.0;
 #pragma unroll
     for (int k = 0; k < DT; ++k) {
@@ -383,6 +471,8 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
         acc[k] = 0.0;
     }
     const double aj = tx < N ? alpha[tx] : 0.0;
+    double bj = 0.0;
+    if constexpr (LOO) bj = tx < N ? bv[tx] : 0.0;
     for (int i0 = 0; i0 < N; i0 += FIT_XROWS) {
         __syncthreads();
         for (int t = tid; t < FIT_XROWS * DT; t += FIT_THREADS) {
@@ -394,7 +484,14 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
             const int i = i0 + c, j = tx;
             if (i >= N || j > i) continue;   // (j <= i < N)
             const double ai = alpha[i];
-            const double G = (ai * aj - B[(int64_t)i * ld + j]) * (i == j ? 0.5 : 1.0);
+            double G, bi = 0.0;
+            if constexpr (LOO) {   // (the triangle is walked once: an off-diagonal entry counts twice)
+                bi = bv[i];
+                const double m = A[(int64_t)i * ld + j];
+                G = i == j ? ai * bi - m : (bi * aj + ai * bj) - 2.0 * m;
+            } else {
+                G = (ai * aj - B[(int64_t)i * ld + j]) * (i == j ? 0.5 : 1.0);
+            }
             double r = 0.0;
 #pragma unroll
             for (int k = 0; k < DT; ++k) {
@@ -422,7 +519,7 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
             a_sig += G * 2.0 * Kij;
             if (i == j) {
                 a_noise += G * 2.0 * noise_var;   // G carries the 1/2
-                a_mean += ai;
+                a_mean += LOO ? bi : ai;
             }
         }
     }
@@ -447,7 +544,7 @@ __global__ __launch_bounds__(FIT_THREADS) void k_mll_batch(FitArgs a) {
         else v = PB[2 + d];
         gout[tid] = v;
     }
-    if (stamp) a.stamps[5] = wall_clock64();
+    if (stamp) a.stamps[LOO ? 6 : 5] = wall_clock64();
 }
 
 }  // namespace bohip

@@ -140,6 +140,13 @@ inline size_t fit_io(const void* base, size_t H, size_t P, size_t n_stamps, FitI
     w->pivot = c.take<long long>(H); w->stamps = c.take<unsigned long long>(n_stamps);
     return c.total();
 }
+// batched leave-one-out: the per-point log-probabilities of every setting, [logp H x N]
+struct LooBatchIo { double* logp; };
+inline size_t loo_batch_io(const void* base, size_t H, size_t N, LooBatchIo* w) {
+    Carve c(base);
+    w->logp = c.take<double>(H * N);
+    return c.total();
+}
 // marginalised acquisition: [theta | w | w~ | pivot | xs chunk | each, mu, var H x Rc | d each / d x (H x Rc x d) | scores R |
 // gradient R x d | workgroup records nblk + 1], the two gradient members with dg = d only (dg = 0: null)
 template <class Rec>

@@ -233,6 +233,14 @@ class ElasticGPE:
         (bohip_gp_loo_grad; Rasmussen & Williams 5.4.2)."""
         return _loo_grad(self._lib, self._h, (1 if self.kernel.iso else self.dim) + 1)
 
+    def loo_grad_batch(self, Theta, want_grad=True, want_logp=False):
+        """The LOO predictive log-probability, and its gradient, at the H rows of Theta in ONE launch (bohip_gp_loo_grad_batch,
+        DESIGN.md 6s): rows as for mll_grad_batch.  Returns (total[H], G[H, P] or None, pivot[H]) and, with want_logp, the
+        per-point logp[H, N] as a fourth value; a row whose factorisation fails has pivot > 0, total = -inf, a zero gradient and
+        a NaN row of logp.  At most mll_batch_dims()[1] observations.  The model itself is neither read (beyond its
+        observations) nor changed."""
+        return _loo_grad_batch(self._lib, self._h, self.nobs, Theta, want_grad, want_logp)
+
     # -- predict_f / scoring ------------------------------------------------------------------------
     def predict_f(self, xs):
         xs = _cols(xs, self.dim)
@@ -561,6 +569,22 @@ def _loo_grad(lib, h, nk):
     dk = np.empty(nk)
     check(lib.bohip_gp_loo_grad(h, C.byref(t), C.byref(dn), C.byref(dm), _ptr(dk)))
     return t.value, dn.value, dm.value, dk
+
+
+def _loo_grad_batch(lib, h, n, Theta, want_grad, want_logp):
+    P, nmax = C.c_int64(), C.c_int64()
+    check(lib.bohip_gp_mll_batch_dims(h, C.byref(P), C.byref(nmax)))
+    Theta = np.ascontiguousarray(np.atleast_2d(np.asarray(Theta, dtype=np.float64)))
+    if Theta.shape[1] != P.value:
+        raise ValueError(f"Theta must have {P.value} columns [logNoise, mean, ll..., lsigma], got {Theta.shape[1]}")
+    H = Theta.shape[0]
+    total = np.empty(H)
+    G = np.empty((H, P.value)) if want_grad else None
+    logp = np.empty((H, n)) if want_logp else None
+    pivot = np.zeros(H, dtype=np.int64)
+    check(lib.bohip_gp_loo_grad_batch(h, H, _ptr(Theta), _ptr(total), _ptr(G) if want_grad else None, _ptr(logp) if want_logp else None,
+                                      pivot.ctypes.data_as(C.POINTER(C.c_int64))))
+    return (total, G, pivot, logp) if want_logp else (total, G, pivot)
 
 
 class EnsembleScore:

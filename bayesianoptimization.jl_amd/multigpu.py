@@ -246,6 +246,12 @@ class MultiGPE:
 
         return _loo_grad(self._lib, self._lib.bohip_mgp_handle(self._h, 0), (1 if self.kernel.iso else self.dim) + 1)
 
+    def loo_grad_batch(self, Theta, want_grad=True, want_logp=False):
+        """ElasticGPE.loo_grad_batch (bohip_gp_loo_grad_batch) on the FIRST replica."""
+        from .model import _loo_grad_batch
+
+        return _loo_grad_batch(self._lib, self._lib.bohip_mgp_handle(self._h, 0), self.nobs, Theta, want_grad, want_logp)
+
     def draw_paths(self, S=1, M=2048, seed=0):
         """Posterior sample paths (ElasticGPE.draw_paths, bohip_gp_paths_draw) on the FIRST replica, as sample_joint: the object is
         self-contained and lives on that device.  Close it before the model."""
