@@ -9,7 +9,7 @@ from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
                     score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values,
-                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO)
+                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
@@ -28,4 +28,4 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
            "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
            "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values",
-           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO"]
+           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO", "collapse_evaluations"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -209,6 +209,13 @@ LOO_BATCH_SIGNATURES = {
     "bohip_gp_loo_grad_batch": (C.c_int, [_gp, C.c_int64, _dp, _dp, _dp, _dp, _i64p]),
 }
 
+# every symbol include/bohip_rep.h declares (replicated sites: r evaluations at one position as one row with noise nu / r)
+REP_SIGNATURES = {
+    "bohip_gp_append_sites": (C.c_int, [_gp, _dp, _dp, _i64p, _dp, C.c_int64]),
+    "bohip_gp_sites_info": (C.c_int, [_gp, _i64p, _i64p, _dp, _dp, _ip]),
+    "bohip_gp_get_reps": (C.c_int, [_gp, _i64p]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -267,7 +274,7 @@ def load():
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
-                              + list(LOO_BATCH_SIGNATURES.items())):
+                              + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

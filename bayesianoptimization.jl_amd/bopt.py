@@ -12,7 +12,7 @@ import numpy as np
 from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
-from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, update_
+from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, refuse_weighted, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
 
 
@@ -137,6 +137,7 @@ def _slice_sample_batch(logp_batch, X0, lo, hi, sweeps, rng, max_shrink=200):
 def _marginal_fit(model, opt):
     if model.nobs == 0:
         return
+    refuse_weighted(model, "MarginalGPOptimizer (its samples feed the marginalised acquisitions)")
     mean_free = opt["domean"] and isinstance(model.mean, MeanConst)
     x0, lo, hi = [], [], []
     if opt["noise"]:
@@ -234,6 +235,8 @@ def _map_fit(model, opt):                                     # :54-77
         model.set_params_(**kw)
 
     loo = opt.get("objective", "mll") == "loo"
+    if loo:
+        refuse_weighted(model, 'MAPGPOptimizer(objective="loo") (the leave-one-out gradient)')
 
     def negmll(x):                                            # f = (x, g) -> ... gp.target, gp.dtarget  (:59-64)
         apply(x)
@@ -313,7 +316,9 @@ def _fit_objective(model, opt, nk, apply, p, H, want_grad=True):
                            [model.kernel.lsigma]])
     idx = ([0] if opt["noise"] else []) + ([1] if mean_free else []) + (list(range(2, 2 + nk)) if opt["kern"] else [])
     assert len(idx) == p
-    if loo:
+    if getattr(model, "weighted", False):                     # replicated sites: the batched kernels know no per-row noise term
+        batched = False
+    elif loo:
         batched = hasattr(model, "loo_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1], _LOO_BATCH_MIN_H)
     else:
         batched = hasattr(model, "mll_grad_batch") and _fit_batched(model.nobs, H, model.mll_batch_dims()[1])
@@ -406,8 +411,9 @@ class BOpt:
             current_optimum = -math.inf * int(sense) if yy is None else int(sense) * float(np.max(yy))
             current_optimizer = np.zeros_like(lowerbounds) if yy is None else np.array(model.x[:, int(np.argmax(yy))])
         else:
-            current_optimum = -math.inf * int(sense) if empty else int(sense) * float(np.max(model.y))   # :117
-            current_optimizer = np.zeros_like(lowerbounds) if empty else np.array(model.x[:, int(np.argmax(model.y))])
+            yraw = getattr(model, "ymax", model.y)                               # (replicated sites: the largest raw evaluation of each)
+            current_optimum = -math.inf * int(sense) if empty else int(sense) * float(np.max(yraw))   # :117
+            current_optimizer = np.zeros_like(lowerbounds) if empty else np.array(model.x[:, int(np.argmax(yraw))])
         self.func, self.sense, self.model = func, Sense(sense), model
         self.acquisition, self.acquisitionoptions, self.modeloptimizer = acquisition, acquisitionoptions, modeloptimizer
         self.lowerbounds, self.upperbounds = lowerbounds, upperbounds

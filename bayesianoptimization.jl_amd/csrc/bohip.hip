@@ -29,8 +29,10 @@
 #include "../../include/bohip_mo.h"
 #include "../../include/bohip_loo.h"
 #include "../../include/bohip_loo_batch.h"
+#include "../../include/bohip_rep.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
+#include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
 #include "kernels_chol.hip"
 #include "kernels_exec.hip"
 #include "kernels_score.hip"
@@ -143,6 +145,14 @@ struct bohip_gp : gp_streams {
     DBuf<unsigned> dchol_flags;        // dataflow factorisation (kernels_chol.hip): panel[T*8] | solved[T] | crit[T] | abort[1]
     DBuf<double> dchol_idl;            // [T*8][16][16] published inverses of the 16 x 16 pivot blocks
     std::vector<double> hX, hy;
+    // replicated sites (include/bohip_rep.h): a handle turns weighted with the first site of more than one evaluation and
+    // stays so.  Only a weighted handle holds dinvr [cap] = 1 / r_i (ones for plain rows) and its mirrors; hy then holds the site means.
+    bool weighted = false;
+    DBuf<double> dinvr;
+    std::vector<double> hinvr;
+    std::vector<int64_t> hreps;
+    int64_t n_evals_extra = 0;          // N_tot - n
+    double ss_total = 0.0, sum_log_reps = 0.0;   // sum_i s_i, sum_i log r_i
     double loglen[DMAX], logsig = 0.0, lognoise = -2.0, beta = 0.0;
     bool stale = true;
     int64_t n_factored = 0;  // observations covered by the current factor
@@ -385,11 +395,27 @@ static void t_collect(bohip_gp* g, bool force = false) {
 static int free_model(bohip_gp* g) {
     for (DBuf<double>* b : {&g->dX, &g->dy, &g->dL, &g->dW, &g->dWT, &g->dS, &g->dalpha, &g->dr, &g->dt, &g->dApp, &g->dchol_idl}) b->release();
     g->dchol_flags.release();
+    g->dinvr.release();
     g->ex_T = 0;   // the task records hold pointers into the buffers just freed
     return 0;
 }
 static size_t chol_flag_words(int T);
 static size_t chol_abort_word(int T);
+// ---- replicated sites (include/bohip_rep.h) ----------------------------------------------------------------------------------------
+// The weights of a weighted handle as the device holds them: dinvr sized like dy, filled from the host mirror (capacity growth, a
+// failed staged append, the plain rows that were there when the handle turned weighted).
+static int upload_site_weights(bohip_gp* g) {
+    HIPCHK(g->dinvr.reserve(std::max<size_t>(1, (size_t)std::max(g->cap, g->n)), g->stream));
+    if (g->n > 0) HIPCHK(hipMemcpyAsync(g->dinvr, g->hinvr.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
+    return 0;
+}
+// The entry points that build cK from dX / dy in kernels of their own (or scale the noise themselves) know no per-row noise term:
+// on a weighted handle they refuse instead of answering for a different model.
+static int refuse_weighted(const bohip_gp* g, const char* who) {
+    if (!g || !g->weighted) return 0;
+    return fail(BOHIP_E_UNSUPPORTED, std::string(who) + " does not support a model with replicated sites (bohip_gp_append_sites with reps > 1): "
+                                         "its kernels build the covariance with one noise term for every row");
+}
 static int alloc_model(bohip_gp* g, int64_t cap) {
     free_model(g);
     // chunk buffers are sized by ld: drop them, they are re-made on demand
@@ -420,6 +446,7 @@ static int alloc_model(bohip_gp* g, int64_t cap) {
         HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)g->n * g->d * 8, hipMemcpyHostToDevice, g->stream));
         HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)g->n * 8, hipMemcpyHostToDevice, g->stream));
     }
+    if (g->weighted) CHK(upload_site_weights(g));
     g->stale = true;
     return 0;
 }
@@ -1313,6 +1340,7 @@ static int refit_once(bohip_gp* g, double jitter) {
     if (g->mirror_dirty) {   // a staged append failed after the mirrors advanced: the host copies are the truth
         HIPCHK(hipMemcpyAsync(g->dX, g->hX.data(), (size_t)N * g->d * 8, hipMemcpyHostToDevice, g->stream));
         HIPCHK(hipMemcpyAsync(g->dy, g->hy.data(), (size_t)N * 8, hipMemcpyHostToDevice, g->stream));
+        if (g->weighted) CHK(upload_site_weights(g));
         HIPCHK(hipStreamSynchronize(g->stream));
         g->mirror_dirty = false;
     }
@@ -1329,6 +1357,13 @@ static int refit_once(bohip_gp* g, double jitter) {
     }
     HIPCHK(hipGetLastError());
     t_end(g);
+    if (g->weighted) {   // replicated sites: cK_w = K + noise diag(1 / r_i), the jitter of this try included
+        t_begin(g, "rep_diag");
+        hipLaunchKernelGGL(k_rep_diag, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g->stream, g->dL, ld, (int64_t)0, N, hp.sigma2, noise,
+                           g->dinvr);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+    }
     // Which form.  The executor makes progress only while the chain kernel's workgroups (9 + solve followers + 6 gated updaters) are
     // resident TOGETHER, one per CU (they fill the LDS), with CUs left over for the executor's own: on a device or partition that
     // cannot hold them the launch chain is used.  T range: from TWO row tiles on with the inverse queues -- at T = 2, 3 the executor has
@@ -1499,6 +1534,12 @@ static int append_incremental(bohip_gp* g, int64_t N0, int64_t p, int* defer_inf
                N0, N1, Npad1, hp, noise, g->dL, g->dW, g->dWT, ld);
     HIPCHK(hipGetLastError());
     t_end(g);
+    if (g->weighted) {   // replicated sites: the new rows' diagonal entries, as refit_once sets them
+        t_begin(g, "rep_diag");
+        hipLaunchKernelGGL(k_rep_diag, dim3((unsigned)((p + 255) / 256)), dim3(256), 0, g->stream, g->dL, ld, N0, N1, hp.sigma2, noise, g->dinvr);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+    }
     t_begin(g, "append_L21");
     CHK(launch_rows_trimv(g, g->dW, N0, g->dL + N0 * ld, (int)p, g->dApp, 0));
     HIPCHK(hipMemcpy2DAsync(g->dL + N0 * ld, ld * 8, g->dApp, ld * 8, N0 * 8, p, hipMemcpyDeviceToDevice, g->stream));
@@ -2368,8 +2409,30 @@ int bohip_gp_set_hyper(bohip_gp* g, const double* loglen, double logsig, double 
     return 0;
 }
 
-int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
-    if (!g || p < 0 || (p > 0 && (!X || !y))) return fail(BOHIP_E_ARG, "bad arguments");
+// The host side of a weighted handle's new rows: 1 / r_i and r_i behind the mirrors' first n_old entries, and the sums of the
+// sites' constant C (bohip_rep.h); _pop takes a failed growth back.
+static void site_mirrors_push(bohip_gp* g, int64_t n_old, const int64_t* reps, const double* ss, int64_t p) {
+    g->hinvr.resize((size_t)n_old, 1.0);
+    g->hreps.resize((size_t)n_old, 1);
+    for (int64_t i = 0; i < p; ++i) {
+        const int64_t r = reps ? reps[i] : 1;
+        g->hinvr.push_back(1.0 / (double)r);
+        g->hreps.push_back(r);
+        g->n_evals_extra += r - 1;
+        g->sum_log_reps += std::log((double)r);
+        if (ss) g->ss_total += ss[i];
+    }
+}
+struct SiteSums { int64_t extra; double ss, slr; };
+static void site_mirrors_pop(bohip_gp* g, int64_t n_old, const SiteSums& was) {
+    g->hinvr.resize((size_t)n_old);
+    g->hreps.resize((size_t)n_old);
+    g->n_evals_extra = was.extra; g->ss_total = was.ss; g->sum_log_reps = was.slr;
+}
+// What bohip_gp_append and bohip_gp_append_sites (include/bohip_rep.h) share.  reps == nullptr: plain rows, r = 1 and s = 0 each; on
+// an unweighted handle that is the whole of bohip_gp_append, launch for launch.  A weighted handle (the caller has turned it so) also
+// keeps 1 / r_i beside X and y -- mirror, staged copy, device vector -- and the three sums of the sites' constant.
+static int append_rows(bohip_gp* g, const double* X, const double* y, const int64_t* reps, const double* ss, int64_t p) {
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     int rc = 0;
@@ -2377,6 +2440,7 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
     if (p > 0) {
         ++g->data_version;
         const int64_t n_old = g->n, n_new = g->n + p;
+        const SiteSums was{g->n_evals_extra, g->ss_total, g->sum_log_reps};
         if (n_new > g->cap) {
             // growth: alloc_model re-uploads everything from the host mirrors, so they are extended first -- and rolled
             // back if the allocation fails (the handle then holds its old observations and no device buffers; the next
@@ -2384,11 +2448,13 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
             g->hX.insert(g->hX.end(), X, X + p * g->d);
             g->hy.insert(g->hy.end(), y, y + p);
             g->n = n_new;
+            if (g->weighted) site_mirrors_push(g, n_old, reps, ss, p);
             const int arc = alloc_model(g, std::max<int64_t>(2 * g->cap, n_new));
             if (arc != 0) {
                 g->hX.resize((size_t)n_old * g->d);
                 g->hy.resize((size_t)n_old);
                 g->n = n_old;
+                if (g->weighted) site_mirrors_pop(g, n_old, was);
                 free_model(g);
                 g->cap = 0;
                 g->stale = true;
@@ -2408,16 +2474,27 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
                 std::memcpy(sy, y, (size_t)p * 8);
                 HIPCHK(hipMemcpyAsync(g->dX + n_old * g->d, sx, (size_t)p * g->d * 8, hipMemcpyHostToDevice, g->stream));
                 HIPCHK(hipMemcpyAsync(g->dy + n_old, sy, (size_t)p * 8, hipMemcpyHostToDevice, g->stream));
+                if (g->weighted) {
+                    double* sw = g->pin.mu;   // (idle during an append, like the two above)
+                    for (int64_t i = 0; i < p; ++i) sw[i] = reps ? 1.0 / (double)reps[i] : 1.0;
+                    HIPCHK(hipMemcpyAsync(g->dinvr + n_old, sw, (size_t)p * 8, hipMemcpyHostToDevice, g->stream));
+                }
                 pinfo = g->pin.words;
                 *pinfo = 0;
             } else {
                 HIPCHK(hipMemcpyAsync(g->dX + n_old * g->d, X, (size_t)p * g->d * 8, hipMemcpyHostToDevice, g->stream));
                 HIPCHK(hipMemcpyAsync(g->dy + n_old, y, (size_t)p * 8, hipMemcpyHostToDevice, g->stream));
+                if (g->weighted) {
+                    std::vector<double> w((size_t)p);
+                    for (int64_t i = 0; i < p; ++i) w[i] = reps ? 1.0 / (double)reps[i] : 1.0;
+                    HIPCHK(hipMemcpy(g->dinvr + n_old, w.data(), (size_t)p * 8, hipMemcpyHostToDevice));
+                }
                 HIPCHK(hipStreamSynchronize(g->stream));  // caller's buffers are only valid during the call
             }
             g->hX.insert(g->hX.end(), X, X + p * g->d);
             g->hy.insert(g->hy.end(), y, y + p);
             g->n = n_new;
+            if (g->weighted) site_mirrors_push(g, n_old, reps, ss, p);
             if (!g->stale && g->n_factored == n_old && n_old > 0 && p <= APPEND_PMAX) {
                 rc = append_incremental(g, n_old, p, pinfo);
                 if (rc != 0) { g->stale = true; g->mirror_dirty = staged; }   // (staged: the rows' copies were only queued -- the device may not hold them)
@@ -2441,6 +2518,58 @@ int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return rc;
+}
+
+int bohip_gp_append(bohip_gp* g, const double* X, const double* y, int64_t p) {
+    if (!g || p < 0 || (p > 0 && (!X || !y))) return fail(BOHIP_E_ARG, "bad arguments");
+    return append_rows(g, X, y, nullptr, nullptr, p);
+}
+
+// ---- replicated sites (include/bohip_rep.h) ------------------------------------------------------------------------
+int bohip_gp_append_sites(bohip_gp* g, const double* X, const double* ybar, const int64_t* reps, const double* ss, int64_t p) {
+    if (!g || p < 0 || (p > 0 && (!X || !ybar || !reps || !ss))) return fail(BOHIP_E_ARG, "bad arguments");
+    bool any = false;
+    for (int64_t i = 0; i < p; ++i) {
+        if (reps[i] < 1) return fail(BOHIP_E_ARG, "site " + std::to_string(i) + ": reps must be >= 1");
+        if (!std::isfinite(ss[i]) || ss[i] < 0.0) return fail(BOHIP_E_ARG, "site " + std::to_string(i) + ": ss must be finite and >= 0");
+        if (reps[i] == 1 && ss[i] != 0.0) return fail(BOHIP_E_ARG, "site " + std::to_string(i) + ": one evaluation has no within-site sum of squares (ss must be 0)");
+        any = any || reps[i] > 1;
+    }
+    if (!g->weighted && !any) return append_rows(g, X, ybar, nullptr, nullptr, p);   // all r = 1: bohip_gp_append itself
+    if (!g->weighted) {
+        // the handle turns weighted: the rows it holds are sites of one evaluation (their diagonal entries, hence the factor, stand)
+        HIPCHK(hipSetDevice(g->device));
+        g->hinvr.assign((size_t)g->n, 1.0);
+        g->hreps.assign((size_t)g->n, 1);
+        g->n_evals_extra = 0; g->ss_total = 0.0; g->sum_log_reps = 0.0;
+        g->weighted = true;
+        g->ens_factor_ok = false;
+        const int rc = upload_site_weights(g);
+        if (rc != 0) { g->mirror_dirty = true; g->stale = true; return rc; }
+    }
+    return append_rows(g, X, ybar, reps, ss, p);
+}
+int bohip_gp_sites_info(const bohip_gp* g, int64_t* n_sites, int64_t* n_evals, double* ss_total, double* sum_log_reps, int* weighted) {
+    if (!g) return fail(BOHIP_E_ARG, "null handle");
+    if (n_sites) *n_sites = g->n;
+    if (n_evals) *n_evals = g->n + (g->weighted ? g->n_evals_extra : 0);
+    if (ss_total) *ss_total = g->weighted ? g->ss_total : 0.0;
+    if (sum_log_reps) *sum_log_reps = g->weighted ? g->sum_log_reps : 0.0;
+    if (weighted) *weighted = g->weighted ? 1 : 0;
+    return 0;
+}
+int bohip_gp_get_reps(const bohip_gp* g, int64_t* reps_out) {
+    if (!g || (g->n > 0 && !reps_out)) return fail(BOHIP_E_ARG, "null argument");
+    for (int64_t i = 0; i < g->n; ++i) reps_out[i] = g->weighted ? g->hreps[(size_t)i] : 1;
+    return 0;
+}
+// The part of the log marginal likelihood of ALL evaluations that the collapsed model does not see, and its derivative by logNoise:
+//   C = -1/2 (N_tot - n) log(2 pi nu) - 1/2 sum log r_i - (sum s_i) / (2 nu),   nu = exp(2 logNoise) + eps + jitter_last
+static void site_constant(const bohip_gp* g, double* Cval, double* dC_dlognoise) {
+    const double s2 = std::exp(2.0 * g->lognoise), nu = s2 + std::numeric_limits<double>::epsilon() + g->jitter_last;
+    const double m = (double)g->n_evals_extra;
+    *Cval = -0.5 * m * std::log(2.0 * M_PI * nu) - 0.5 * g->sum_log_reps - g->ss_total / (2.0 * nu);
+    if (dC_dlognoise) *dC_dlognoise = 2.0 * s2 * (-m / (2.0 * nu) + g->ss_total / (2.0 * nu * nu));
 }
 
 int bohip_gp_refit(bohip_gp* g) {
@@ -2484,6 +2613,11 @@ int bohip_gp_mll(bohip_gp* g, double* mll) {
     HIPCHK(hipMemcpyAsync(pm, g->dmll, 8, hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = *pm;
+    if (g->weighted) {   // replicated sites: the likelihood of every evaluation, not of the site means alone
+        double Cv;
+        site_constant(g, &Cv, nullptr);
+        *mll += Cv;
+    }
     return 0;
 }
 
@@ -2530,6 +2664,8 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     });
     const int nout = nl + 3;
     hipLaunchKernelGGL(k_dmll_final, dim3(nout), dim3(256), 0, g->stream, g->ddmll_parts, nblocks, NP, g->d, iso, g->dmll + 1);
+    if (g->weighted)   // replicated sites: slot 1 is sigma^2 sum_i (alpha_i^2 - cK_w^-1_ii) / r_i (behind k_dmll_final on the stream: its slot 1 is replaced)
+        hipLaunchKernelGGL(k_rep_noise_sum, dim3(1), dim3(256), 0, g->stream, g->dalpha, g->dS, ld, N, g->dinvr, g->dmll + 1);
     HIPCHK(hipGetLastError());
     t_end(g);
     double hbuf[DMAX + 4];
@@ -2538,6 +2674,12 @@ int bohip_gp_mll_grad(bohip_gp* g, double* mll, double* d_lognoise, double* d_me
     HIPCHK(hipStreamSynchronize(g->stream));
     *mll = h[0]; *d_lognoise = h[1]; *d_mean = h[2];
     for (int k = 0; k <= nl; ++k) d_kern[k] = h[3 + k];
+    if (g->weighted) {   // 2 sigma^2 sum_i G_ii / r_i with G_ii = 1/2 (alpha_i^2 - cK_w^-1_ii), then the sites' constant and its derivative
+        double Cv, dC;
+        site_constant(g, &Cv, &dC);
+        *mll += Cv;
+        *d_lognoise = noise_var * h[1] + dC;
+    }
     return 0;
 }
 
@@ -2580,6 +2722,7 @@ int bohip_gp_loo(bohip_gp* g, double* mu, double* var, double* logp, double* tot
 
 int bohip_gp_loo_grad(bohip_gp* g, double* total, double* d_lognoise, double* d_mean, double* d_kern) {
     if (!g || !total || !d_lognoise || !d_mean || !d_kern) return fail(BOHIP_E_ARG, "null argument");
+    CHK(refuse_weighted(g, "bohip_gp_loo_grad"));
     HIPCHK(hipSetDevice(g->device));
     const int iso = kern_iso(g->kern), nl = iso ? 1 : g->d;
     if (g->n == 0) {
@@ -2720,6 +2863,7 @@ int bohip_gp_mll_batch_dims(bohip_gp* g, int64_t* P, int64_t* nmax) {
 // workspace, theta up, one launch per Hc settings, the rows down.  value: mll[H] or total[H]; logp: leave-one-out only.
 static int fit_batch(bohip_gp* g, bool loo, int64_t H, const double* theta, double* value, double* grad, double* logp, int64_t* pivot) {
     if (!g || !theta || !value) return fail(BOHIP_E_ARG, "null argument");
+    CHK(refuse_weighted(g, loo ? "bohip_gp_loo_grad_batch" : "bohip_gp_mll_grad_batch"));
     if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
     if (g->n == 0) return fail(BOHIP_E_STATE, "no observations");
     if (g->n > BOHIP_FIT_NMAX)
@@ -2846,6 +2990,7 @@ static int ens_drive(bohip_gp* g, bool with_grad, int acq_id, const double* acq_
                      const double* xs, int64_t R, double* scores, double* grad, double* each, double* each_grad, double* mu, double* var,
                      int64_t* pivot, bohip_best* best) {
     if (!g || !theta || !xs || !best || (with_grad && !grad)) return fail(BOHIP_E_ARG, "null argument");
+    CHK(refuse_weighted(g, with_grad ? "bohip_gp_score_ens_grad" : "bohip_gp_score_ens"));
     if (H < 1) return fail(BOHIP_E_ARG, "H must be >= 1");
     if (R < 1) return fail(BOHIP_E_ARG, "R must be >= 1");
     if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, "unknown acq_id (Thompson draws are not averaged)");
@@ -4075,6 +4220,7 @@ int bohip_gp_paths_draw(bohip_gp* g, int64_t S, int64_t M, uint64_t seed, bohip_
     if (!out) return fail(BOHIP_E_ARG, "paths_draw: null output pointer");
     *out = nullptr;
     if (!g) return done(fail(BOHIP_E_ARG, "paths_draw: null handle"));
+    CHK(refuse_weighted(g, "bohip_gp_paths_draw"));
     if (S < 1) return done(fail(BOHIP_E_ARG, "paths_draw: S must be at least 1"));
     if (M < 2 || (M & 1) || M % 16 != 0) return done(fail(BOHIP_E_ARG, "paths_draw: M must be a positive multiple of 16"));
     if (S > BOHIP_PATHS_S_MAX) return done(fail(BOHIP_E_UNSUPPORTED, "paths_draw: at most " + std::to_string(BOHIP_PATHS_S_MAX) + " paths per object"));

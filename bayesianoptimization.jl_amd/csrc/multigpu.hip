@@ -176,6 +176,12 @@ static int mgp_stage_h2d(bohip_mgp* m, int i, double* dst, const double* src, si
 }
 
 // run fn(i) for every device: on the device's worker thread, or inline (BOHIP_MGP_THREADS=0 / one device)
+// A replica that was turned weighted behind the list's back (bohip_mgp_handle + bohip_gp_append_sites): the list keeps its replicas in
+// step by plain appends and roll-backs that know nothing of site weights, so every entry point refuses (include/bohip_rep.h).
+static int mgp_refuse_weighted(const bohip_mgp* m, const char* who) {
+    for (int i = 0; i < m->nd; ++i) CHK(refuse_weighted(m->h[i], who));
+    return 0;
+}
 static int mgp_for_each(bohip_mgp* m, const std::function<int(int)>& fn) {
     int rc = 0;
     if (!m->threads) {
@@ -369,12 +375,14 @@ void bohip_mgp_destroy(bohip_mgp* m) {
 
 int bohip_mgp_set_hyper(bohip_mgp* m, const double* loglen, double logsig, double lognoise, double mean_const) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_set_hyper"));
     for (int i = 0; i < m->nd; ++i) CHK(bohip_gp_set_hyper(m->h[i], loglen, logsig, lognoise, mean_const));
     return 0;
 }
 
 int bohip_mgp_append(bohip_mgp* m, const double* X, const double* y, int64_t p) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_append"));
     std::vector<int64_t> n_old((size_t)m->nd);
     for (int i = 0; i < m->nd; ++i) n_old[i] = m->h[i]->n;
     const int rc = mgp_for_each(m, [&](int i) { return bohip_gp_append(m->h[i], X, y, p); });
@@ -402,12 +410,14 @@ int bohip_mgp_append(bohip_mgp* m, const double* X, const double* y, int64_t p) 
 
 int bohip_mgp_refit(bohip_mgp* m) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_refit"));
     return mgp_for_each(m, [&](int i) { return bohip_gp_refit(m->h[i]); });
 }
 
 int bohip_mgp_score(bohip_mgp* m, int acq_id, const double* acq_params, const double* Xs, int64_t R, double* score,
                     bohip_best* best) {
     if (!m || R < 0 || (R > 0 && !Xs) || !best) return fail(BOHIP_E_ARG, "bad arguments");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_score"));
     CHK(mgp_acq_params(acq_id, acq_params));
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
     CHK(mgp_ensure_records(m, 1));
@@ -430,6 +440,7 @@ int bohip_mgp_score(bohip_mgp* m, int acq_id, const double* acq_params, const do
 
 int bohip_mgp_set_candidates(bohip_mgp* m, const double* Xs, int64_t R) {
     if (!m || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "bad arguments");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_set_candidates"));
     const int64_t G = (int64_t)m->nd * m->spd;
     CHK(mgp_for_each(m, [&](int i) -> int {
         bohip_gp* g = m->h[i];
@@ -451,6 +462,7 @@ int bohip_mgp_set_candidates(bohip_mgp* m, const double* Xs, int64_t R) {
 
 int bohip_mgp_score_resident(bohip_mgp* m, int acq_id, const double* acq_params, bohip_best* best) {
     if (!m || !best) return fail(BOHIP_E_ARG, "bad arguments");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_score_resident"));
     CHK(mgp_acq_params(acq_id, acq_params));
     const int64_t R = m->R_res;
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
@@ -470,6 +482,7 @@ int bohip_mgp_score_resident(bohip_mgp* m, int acq_id, const double* acq_params,
 
 int bohip_mgp_thompson(bohip_mgp* m, const double* Xs, int64_t R, int64_t S, uint64_t seed, bohip_best* best) {
     if (!m || R <= 0 || S <= 0 || !Xs || !best) return fail(BOHIP_E_ARG, "bad arguments");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_thompson"));
     CHK(mgp_ensure_records(m, S));
     const int64_t G = (int64_t)m->nd * m->spd;
     CHK(mgp_for_each(m, [&](int i) -> int {
@@ -503,6 +516,7 @@ int bohip_mgp_acquire_max(bohip_mgp* m, int acq_id, const double* acq_params, co
                           double xtol_abs, double* x_out, double* f_out, bohip_best* best, double* best_x,
                           int64_t* evals_out) {
     if (!m || !lowerbounds || !upperbounds || R < 0 || (R > 0 && !starts) || !best) return fail(BOHIP_E_ARG, "bad arguments");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_acquire_max"));
     CHK(mgp_acq_params(acq_id, acq_params));
     if (evals_out) *evals_out = 0;
     if (R == 0) { best->val = -INFINITY; best->idx = -1; return 0; }
@@ -547,16 +561,19 @@ int bohip_mgp_acquire_max(bohip_mgp* m, int acq_id, const double* acq_params, co
 
 int bohip_mgp_set_maxtime(bohip_mgp* m, double seconds) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_set_maxtime"));
     for (int i = 0; i < m->nd; ++i) CHK(bohip_gp_set_maxtime(m->h[i], seconds));
     return 0;
 }
 int bohip_mgp_set_ascent_stop(bohip_mgp* m, double ftol_abs, double xtol_rel, double stopval) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_set_ascent_stop"));
     for (int i = 0; i < m->nd; ++i) CHK(bohip_gp_set_ascent_stop(m->h[i], ftol_abs, xtol_rel, stopval));
     return 0;
 }
 int bohip_mgp_set_jitter(bohip_mgp* m, double rel, int max_tries) {
     if (!m) return fail(BOHIP_E_ARG, "null handle");
+    CHK(mgp_refuse_weighted(m, "bohip_mgp_set_jitter"));
     for (int i = 0; i < m->nd; ++i) CHK(bohip_gp_set_jitter(m->h[i], rel, max_tries));
     return 0;
 }

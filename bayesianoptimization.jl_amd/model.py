@@ -97,19 +97,71 @@ class Mat12Iso(_Kernel):
     iso = True
 
 
+def collapse_evaluations(x, y):
+    """Repeated evaluations as weighted sites (include/bohip_rep.h): groups the byte-identical columns of x (d x N)
+    within this call, in order of first occurrence, wherever they stand.  Returns (x_sites [d, n], ybar [n], reps [n] int64, ss [n],
+    ymax [n]): the mean of a site's evaluations, their count, the within-site sum of squares sum_j (y_j - ybar)^2 computed in a second
+    pass around the mean (exactly 0 for a single evaluation) and the largest raw value."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    x = np.asfortranarray(x)
+    y = np.ascontiguousarray(np.atleast_1d(np.asarray(y, dtype=np.float64)))
+    if x.shape[1] != y.size:
+        raise ValueError("x and y disagree on the number of observations")
+    first, members = {}, []
+    for j in range(y.size):
+        key = x[:, j].tobytes()
+        if key not in first:
+            first[key] = len(members)
+            members.append([])
+        members[first[key]].append(j)
+    n = len(members)
+    xs = np.asfortranarray(x[:, [m[0] for m in members]]) if n else np.zeros((x.shape[0], 0), order="F")
+    ybar, reps, ss, ymax = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n), np.empty(n)
+    for i, m in enumerate(members):
+        v = y[m]
+        reps[i] = v.size
+        ybar[i] = v[0] if v.size == 1 else v.sum() / v.size
+        ss[i] = 0.0 if v.size == 1 else float(np.sum((v - ybar[i]) ** 2))
+        ymax[i] = v.max()
+    return xs, ybar, reps, ss, ymax
+
+
+def refuse_weighted(model, what):
+    """ValueError for a feature that cannot take a model with replicated sites: its device kernels build the covariance themselves,
+    with one noise term for every row (include/bohip_rep.h lists the refused entry points)."""
+    if getattr(model, "weighted", False):
+        raise ValueError(f"{what} does not support a model with replicated sites (collapse=True / append_sites_ with reps > 1): "
+                         "its kernels build the covariance with one noise term for every row; use a model with collapse=False")
+
+
+def _refuse_site_member(m, owner):
+    """The member models of a constrained or two-objective model are updated column by column, one value per member and evaluation:
+    they take no replicated sites."""
+    if getattr(m, "collapse", False) or getattr(m, "weighted", False):
+        raise ValueError(f"{owner} members do not support replicated sites (collapse=True / append_sites_ with reps > 1): every "
+                         "member takes every evaluation as a row of its own; use members with collapse=False")
+
+
 class ElasticGPE:
     """Drop-in for ``ElasticGPE(d; mean, kernel, logNoise, capacity)`` (README.md:22-27).
 
     Owns a ``bohip_gp`` handle: x, y, the Cholesky factor, its inverse and alpha live in HBM and
     survive across ``boptimize_`` calls; ``append_`` extends the factor (reference ``append!``).
+    ``collapse=True`` (an extension): ``update_`` and ``from_data`` turn the repeated evaluations of one call
+    (``BOpt(..., repetitions=r)``) into one weighted site each -- the same posterior and marginal likelihood at n positions instead
+    of n r rows.  ``model.x`` / ``model.y`` are then site positions and site means, ``model.reps`` the counts, ``nobs`` the number
+    of sites and ``nevals`` of evaluations; ``maxy`` stays the largest raw evaluation.
     ``model.x`` (d x n) and ``model.y`` are host mirrors, as the reference reads those fields
     directly (src/BayesianOptimization.jl:117-119, src/acquisitionfunctions.jl:136).
     """
 
     hyper_samples = None   # (Theta[H, P], weights) once MarginalGPOptimizer has run: what Marginalised acquisitions average over
 
-    def __init__(self, d, mean=None, kernel=None, logNoise=-2.0, capacity=1024, device=0):
+    def __init__(self, d, mean=None, kernel=None, logNoise=-2.0, capacity=1024, device=0, collapse=False):
         self.dim = int(d)
+        self.collapse = bool(collapse)
         self.mean = mean if mean is not None else MeanZero()
         self.kernel = kernel if kernel is not None else SEArd(np.zeros(d), 0.0)
         self.logNoise = float(logNoise)
@@ -120,6 +172,8 @@ class ElasticGPE:
         _lib.register(self)
         self._x = np.zeros((self.dim, 0), order="F")
         self._y = np.zeros(0)
+        self._reps = np.zeros(0, dtype=np.int64)
+        self._ymax = np.zeros(0)
         self._push_hyper()
 
     def close(self):
@@ -136,6 +190,11 @@ class ElasticGPE:
         x = np.asarray(x, dtype=np.float64)
         if x.ndim == 1:
             x = x.reshape(1, -1)
+        if kw.get("collapse", False):
+            sites = collapse_evaluations(x, y)
+            m = cls(x.shape[0], mean=mean, kernel=kernel, logNoise=logNoise, capacity=max(sites[0].shape[1], 1), **kw)
+            m.append_sites_(*sites)
+            return m
         m = cls(x.shape[0], mean=mean, kernel=kernel, logNoise=logNoise, capacity=max(x.shape[1], 1), **kw)
         m.append_(x, y)
         return m
@@ -178,6 +237,37 @@ class ElasticGPE:
     def nobs(self):
         return self._y.size
 
+    @property
+    def reps(self):
+        """Evaluations behind every row (all 1 unless sites were appended)."""
+        return self._reps
+
+    @property
+    def nevals(self):
+        return int(self._reps.sum())
+
+    @property
+    def ymax(self):
+        """The largest raw evaluation of every row (= y for plain rows): what maxy reads."""
+        return self._ymax
+
+    @property
+    def weighted(self):
+        """Whether the handle holds a site of more than one evaluation (bohip_gp_sites_info)."""
+        return bool(np.any(self._reps > 1))
+
+    def sites_info(self):
+        """(n_sites, n_evals, sum s_i, sum log r_i, weighted) as the handle keeps them (bohip_gp_sites_info)."""
+        n, ne, w = C.c_int64(), C.c_int64(), C.c_int()
+        ss, slr = C.c_double(), C.c_double()
+        check(self._lib.bohip_gp_sites_info(self._h, C.byref(n), C.byref(ne), C.byref(ss), C.byref(slr), C.byref(w)))
+        return int(n.value), int(ne.value), ss.value, slr.value, int(w.value)
+
+    def get_reps(self):
+        r = np.zeros(self.nobs, dtype=np.int64)
+        check(self._lib.bohip_gp_get_reps(self._h, r.ctypes.data_as(C.POINTER(C.c_int64))))
+        return r
+
     # -- append! / fit! ----------------------------------------------------------------------------
     def append_(self, x, y):
         x = _cols(x, self.dim)
@@ -188,6 +278,28 @@ class ElasticGPE:
         if rc in (_lib.OK, _lib.E_NOTPD):  # observations are stored even when the factorisation fails
             self._x = np.asfortranarray(np.concatenate([self._x, x], axis=1))
             self._y = np.concatenate([self._y, y])
+            self._reps = np.concatenate([self._reps, np.ones(y.size, dtype=np.int64)])
+            self._ymax = np.concatenate([self._ymax, y])
+        check(rc)
+        return self
+
+    def append_sites_(self, x, ybar, reps, ss, ymax=None):
+        """Append weighted sites (bohip_gp_append_sites): column j of x with the mean ybar[j] of its reps[j] evaluations and their
+        within-site sum of squares ss[j]; ymax[j] is the largest of them (default: ybar, right for reps = 1 only), kept for maxy.
+        collapse_evaluations makes all five from raw columns.  All reps = 1 on an unweighted model is append_."""
+        x = _cols(x, self.dim)
+        ybar = np.ascontiguousarray(np.atleast_1d(np.asarray(ybar, dtype=np.float64)))
+        reps = np.ascontiguousarray(np.atleast_1d(np.asarray(reps)).astype(np.int64))
+        ss = np.ascontiguousarray(np.atleast_1d(np.asarray(ss, dtype=np.float64)))
+        ymax = ybar.copy() if ymax is None else np.ascontiguousarray(np.atleast_1d(np.asarray(ymax, dtype=np.float64)))
+        if not (x.shape[1] == ybar.size == reps.size == ss.size == ymax.size):
+            raise ValueError("x, ybar, reps, ss and ymax disagree on the number of sites")
+        rc = self._lib.bohip_gp_append_sites(self._h, _ptr(x), _ptr(ybar), reps.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(ss), ybar.size)
+        if rc in (_lib.OK, _lib.E_NOTPD):
+            self._x = np.asfortranarray(np.concatenate([self._x, x], axis=1))
+            self._y = np.concatenate([self._y, ybar])
+            self._reps = np.concatenate([self._reps, reps])
+            self._ymax = np.concatenate([self._ymax, ymax])
         check(rc)
         return self
 
@@ -280,6 +392,7 @@ class ElasticGPE:
         (bohip_gp_score_ens, include/bohip_ens.h: all settings in one call, the model neither read beyond its observations nor
         changed) up to mll_batch_dims()[1] observations, "host" above that (set_params_ + score / predict_f per row, the model's
         own parameters restored afterwards), with the same averaging rule.  Value only: no gradient."""
+        refuse_weighted(self, "score_ensemble (Marginalised acquisitions)")
         return score_ensemble(self, acq, params, xs, Theta, weights, want_each, want_moments)
 
     def score_ensemble_grad(self, acq, params, xs, Theta, weights=None, want_each=False):
@@ -288,6 +401,7 @@ class ElasticGPE:
         (include/bohip_ens_grad.h) -- scores, each and the arg-max are score_ensemble's bit for bit, and successive calls with the same
         Theta and unchanged observations factor the settings once (timing() then shows no "ens_factor"); "host" above
         mll_batch_dims()[1] observations: set_params_ + score_grad per row, the model's own parameters restored afterwards."""
+        refuse_weighted(self, "score_ensemble_grad (Marginalised acquisitions)")
         return score_ensemble_grad(self, acq, params, xs, Theta, weights, want_each)
 
     def select_batch(self, acq, params, xs, q, fantasy="believer", raise_tau=False):
@@ -487,6 +601,7 @@ class ElasticGPE:
         sum_j u_sj k(x, X_j) with M random features for the prior term and the exact data term (pathwise conditioning).  The result
         can be evaluated and differentiated anywhere afterwards and does not follow later changes of the model.  Close it (or use it
         as a context manager) before the model is closed.  Returns a PosteriorPaths."""
+        refuse_weighted(self, "draw_paths (and the \"pathwise\" options that use it)")
         p = PosteriorPaths(self._lib, self._h, self.dim, S, M, seed)
         if not hasattr(self, "_paths"):
             self._paths = weakref.WeakSet()
@@ -972,6 +1087,7 @@ class ConstrainedGPE:
                 raise ValueError("ConstrainedGPE members are single-device models: MultiGPE is not supported")
             if m.dim != objective.dim:
                 raise ValueError("the members differ in dimension")
+            _refuse_site_member(m, "ConstrainedGPE")
 
     @property
     def members(self):
@@ -1131,6 +1247,8 @@ class MultiObjectiveGPE:
                 raise ValueError("MultiObjectiveGPE members are single-device models: MultiGPE is not supported")
         if objectives[0].dim != objectives[1].dim:
             raise ValueError("the members differ in dimension")
+        for m in objectives:
+            _refuse_site_member(m, "MultiObjectiveGPE")
         self.objectives = objectives
         self.ref = None if ref is None else _ref2(ref).copy()
         if self.ref is not None and not np.all(np.isfinite(self.ref)):
@@ -1318,10 +1436,15 @@ def dims(model):
 
 
 def maxy(model):
-    """gp.jl:10."""
-    return -math.inf if model.nobs == 0 else float(np.max(model.y))
+    """gp.jl:10.  A model with replicated sites: the largest RAW evaluation (the reference's maximum(model.y)), not the largest mean."""
+    if model.nobs == 0:
+        return -math.inf
+    return float(np.max(getattr(model, "ymax", model.y)))
 
 
 def update_(model, x, y):
-    """gp.jl:11  update!(model::GPE{<:ElasticArray}, x, y) = append!(model, x, y)."""
+    """gp.jl:11  update!(model::GPE{<:ElasticArray}, x, y) = append!(model, x, y).  A model made with collapse=True takes the
+    repeated columns of the call as one weighted site each (collapse_evaluations)."""
+    if getattr(model, "collapse", False):
+        return model.append_sites_(*collapse_evaluations(x, y))
     return model.append_(x, y)

@@ -28,7 +28,10 @@ class MultiGPE:
     contiguously, winners exchanged over RCCL.  ``score`` returns the GLOBAL (value, index), bit-identical to
     ``ElasticGPE.score`` on the whole set."""
 
-    def __init__(self, d, devices=(0,), shards_per_device=1, mean=None, kernel=None, logNoise=-2.0, capacity=1024):
+    def __init__(self, d, devices=(0,), shards_per_device=1, mean=None, kernel=None, logNoise=-2.0, capacity=1024, collapse=False):
+        if collapse:
+            raise ValueError("MultiGPE does not support replicated sites (collapse=True): the device list keeps its replicas in step "
+                             "by plain appends; use ElasticGPE(collapse=True) on one device")
         self.dim = int(d)
         self.mean = mean if mean is not None else MeanZero()
         self.kernel = kernel if kernel is not None else SEArd(np.zeros(d), 0.0)
@@ -89,6 +92,10 @@ class MultiGPE:
             self._y = np.concatenate([self._y, y])
         check(rc)
         return self
+
+    def append_sites_(self, x, ybar, reps, ss, ymax=None):
+        raise ValueError("MultiGPE does not support replicated sites (append_sites_): the device list keeps its replicas in step by "
+                         "plain appends; use ElasticGPE(collapse=True) on one device")
 
     def fit_(self):
         check(self._lib.bohip_mgp_refit(self._h))

@@ -356,6 +356,7 @@ include("BOHipCon.jl")     # constrained optimisation (include/bohip_con.h): pre
 include("BOHipMO.jl")      # two objectives (include/bohip_mo.h): mo_front, ehvi_values, score_mo
 include("BOHipLOO.jl")     # leave-one-out cross-validation (include/bohip_loo.h): loo, loo_grad
 include("BOHipLOOBatch.jl") # its objective at H settings in one launch (include/bohip_loo_batch.h): loo_grad_batch
+include("BOHipRep.jl")      # replicated sites (include/bohip_rep.h): append_sites!, collapse_evaluations, sites_info, site_reps
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 

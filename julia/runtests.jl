@@ -135,6 +135,25 @@ close_rel(a, b; rel = 1e-6, floor = 0.0) = all(abs.(a .- b) .<= rel .* abs.(b) .
         @test close_rel(sd, fr; floor = 1e-12)
         @test jbest == findfirst(==(maximum(fr)), fr)                        # arg-max index: first maximum wins (src/acquisition.jl:62)
     end
+
+    @testset "replicated sites (BOHipRep.jl, an extension): 5 evaluations a position as one weighted site == the reference with every column" begin
+        Random.seed!(5)
+        d, n, r, R = 2, 40, 5, 64
+        P = rand(d, n); X = repeat(P, inner = (1, r)); y = vec(sum(sin.(3 .* X), dims = 1)) .+ 0.1 .* randn(n * r)
+        Xs = rand(d, R)
+        ref = ElasticGPE(d, mean = MeanConst(0.0), kernel = SEArd(fill(log(0.5), d), 0.0), logNoise = -2.0, capacity = n * r)
+        append!(ref, X, y)
+        dev = BOHipGPE(d; mean = 0.0, kernel = :SEArd, loglen = fill(log(0.5), d), logsig = 0.0, logNoise = -2.0, capacity = n)
+        xs, ybar, reps, ss, ymax = BOHip.collapse_evaluations(X, y)
+        @test size(xs) == (d, n) && all(reps .== r) && xs == P
+        BOHip.append_sites!(dev, xs, ybar, reps, ss, ymax)
+        @test BOHip.sites_info(dev)[1:2] == (n, n * r) && BOHip.site_reps(dev) == reps
+        @test BO.maxy(dev) == maximum(y)
+        μr, σr = BO.mean_var(ref, Xs); μd, σd = BO.mean_var(dev, Xs)
+        @test close_rel(μd, μr; floor = 64 * eps() * sum(abs, ref.alpha))
+        @test close_rel(σd, σr; floor = 64 * n * r * eps())
+        @test isapprox(BOHip.mll(dev), ref.mll; rtol = 1e-9)                  # the likelihood of ALL evaluations
+    end
 end
 
 # (3) pin the Python oracle against the real package: tests/golden/julia_inputs.txt -> tests/golden/julia_outputs.txt
