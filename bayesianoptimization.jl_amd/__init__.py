@@ -9,11 +9,11 @@ from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
                     score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values,
-                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations)
+                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations, PendingScore)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
-                          acquire_max, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
+                          acquire_max, acquire_max_pending, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
                    Min, Max, Silent, Timings, Progress, isdone)
 from .utils import (ScaledSobolIterator, ScaledLHSIterator, latin_hypercube_sampling, maxduration_, maxiterations_,
@@ -28,4 +28,5 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
            "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
            "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values",
-           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO", "collapse_evaluations"]
+           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO", "collapse_evaluations",
+           "PendingScore", "acquire_max_pending"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -216,6 +216,15 @@ REP_SIGNATURES = {
     "bohip_gp_get_reps": (C.c_int, [_gp, _i64p]),
 }
 
+# every symbol include/bohip_pend.h declares (pending evaluations: the acquisition averaged over fantasies at points out for evaluation)
+PEND_PMAX, PEND_SMAX, PEND_RAISE_TAU = 32, 1024, 1
+PEND_SIGNATURES = {
+    "bohip_gp_pending_set": (C.c_int, [_gp, _dp, C.c_int64]),
+    "bohip_gp_pending_info": (C.c_int, [_gp, _i64p, _dp, _dp, _dp]),
+    "bohip_gp_score_pending": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_pend_values": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -274,7 +283,7 @@ def load():
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
-                              + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items())):
+                              + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

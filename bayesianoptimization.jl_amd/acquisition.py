@@ -932,6 +932,46 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     return maxf, maxx
 
 
+_PENDING_REFUSED = (KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement,
+                    ThompsonSamplingSimple)
+
+
+def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
+    """acquire_max for a model with pending evaluations (model.set_pending; an extension): the acquisition is
+    averaged over fantasised outcomes at the pending points (Snoek, Larochelle & Adams 2012, section 3.2), so the proposal keeps
+    away from what is already out for evaluation.  With an empty pending set it returns acquire_max(...) itself.  Otherwise every
+    restart scores `maxeval` Latin-hypercube candidates in ONE model.score_pending call and takes its arg-max record; the call's seed
+    is drawn from `rng` after the candidates; the first maximum over the restarts wins (strict '>').  There is no gradient in x, so
+    "method" and "refine" are accepted and not used.  Options: those of acquire_max plus "fantasies" (default 16; 0: the Kriging
+    believer) and "raise_tau" (default True: the incumbent of EI / PI / LogEI follows each fantasy)."""
+    opts = dict(options if isinstance(options, dict) else vars(options))
+    fantasies = int(opts.pop("fantasies", 16))
+    raise_tau = bool(opts.pop("raise_tau", True))
+    pending = getattr(model, "pending", None)
+    if pending is None or np.shape(pending)[1] == 0:
+        return acquire_max(a, model, lowerbounds, upperbounds, opts, rng, setparams)
+    if isinstance(a, _PENDING_REFUSED):
+        raise ValueError(f"{type(a).__name__} with pending evaluations is not built")
+    if not hasattr(model, "score_pending"):
+        raise ValueError(f"{type(model).__name__} with pending evaluations is not built")
+    lb = np.asarray(lowerbounds, dtype=np.float64)
+    ub = np.asarray(upperbounds, dtype=np.float64)
+    _check_options(opts)
+    if setparams:
+        setparams_(a, model)
+    restarts = int(opts.get("restarts", 10))
+    maxeval = int(opts.get("maxeval", 2000))
+    if model.nobs == 0 or restarts <= 0:
+        return -math.inf, lb.copy()
+    gen = rng if rng is not None else np.random.default_rng()
+    acq, p = a.acq_id, a.params()
+
+    def score(xs):
+        return model.score_pending(acq, p, xs, fantasies=fantasies, seed=int(gen.integers(0, 2 ** 63 - 1)), raise_tau=raise_tau)
+
+    return _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, {**opts, "refine": 0})
+
+
 _BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features"}
 _BATCH_FANTASIES = ("believer", "liar_max", "liar_min", "liar_mean")
 _BATCH_METHODS = ("fantasy", "qei")

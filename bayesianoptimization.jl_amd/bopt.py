@@ -10,7 +10,7 @@ import warnings
 import numpy as np
 
 from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
-                          acquire_batch, acquire_max, acquire_thompson_batch, defaultoptions, setparams_)
+                          acquire_batch, acquire_max, acquire_max_pending, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, refuse_weighted, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
@@ -425,7 +425,97 @@ class BOpt:
         self.rng = rng if rng is not None else np.random.default_rng()
         self.batchsize, self.batchoptions = int(batchsize), dict(batchoptions or {})
         self.timeroutput = {}
+        self._ask_pending = np.zeros((len(lowerbounds), 0), order="F")          # ask / tell: the columns that are out for evaluation
+        self._ask_init = None                                                   # ... the initializer's iterator, made by the first ask
+        self._ask_told = 0                                                      # ... evaluations told so far
         setparams_(acquisition, model)                                          # nlopt_setup :30 (ctor :134)
+
+    # ---- ask / tell (an extension): the caller evaluates, on as many workers as it likes ---------------------------
+    def _refuse_ask_tell(self, who):
+        from .multigpu import MultiGPE
+
+        for cls in (ConstrainedGPE, MultiObjectiveGPE, MultiGPE):
+            if isinstance(self.model, cls):
+                raise ValueError(f"BOpt.{who}: a {cls.__name__} with pending evaluations is not built")
+        if self.batchsize > 1:
+            raise ValueError(f"BOpt.{who}: batchsize = {self.batchsize} with pending evaluations is not built (ask(n) proposes n points)")
+        if self.repetitions > 1:
+            raise ValueError(f"BOpt.{who}: repetitions = {self.repetitions} with pending evaluations is not built")
+        if not hasattr(self.model, "set_pending"):
+            raise ValueError(f"BOpt.{who}: {type(self.model).__name__} has no pending set (set_pending)")
+
+    def ask(self, n=1):
+        """n points to evaluate next, as a d x n array, while earlier proposals are still out.  While the initializer has points
+        left they come from it; after that each point is the maximiser of the acquisition averaged over fantasised outcomes at
+        everything that is out (acquire_max_pending with `acquisitionoptions`; its keys "fantasies" and "raise_tau" go there too) and joins the
+        model's pending set before the next one is sought, so the n points of one call see each other.  Steps the iteration
+        counter once per point.  Report the outcomes with tell, in any order."""
+        self._refuse_ask_tell("ask")
+        if int(n) != n or n < 1:
+            raise ValueError(f"ask: n = {n!r} is not a positive integer")
+        if self._ask_init is None:
+            self._ask_init = iter(self.initializer) if self.iterations.i == 0 else iter(())
+        out = []
+        for _ in range(int(n)):
+            x = next(self._ask_init, None)
+            if x is None:
+                self.model.set_pending(self._ask_pending)
+                setparams_(self.acquisition, self.model)                         # :184
+                with _timeit(self, "acquisition"):
+                    _, x = acquire_max_pending(self.acquisition, self.model, self.lowerbounds, self.upperbounds,
+                                               self.acquisitionoptions, self.rng, setparams=False)
+            x = np.array(x, dtype=np.float64)
+            step_(self.iterations)
+            self._ask_pending = np.asfortranarray(np.concatenate([self._ask_pending, x.reshape(-1, 1)], axis=1))
+            out.append(x)
+        self.model.set_pending(self._ask_pending)
+        return np.asfortranarray(np.stack(out, axis=1))
+
+    def tell(self, x, y, pending=True):
+        """The outcomes y (one per column of x, in the caller's sense) of points that ask handed out.  Each column must equal a
+        pending column bit for bit (ValueError otherwise, nothing changed); pending=False takes an unsolicited observation instead.
+        Updates the observed optimum, makes ONE model update for all columns, removes the matching pending columns and runs the
+        model optimizer at its cadence (once when the initial design is complete, then once per tell)."""
+        self._refuse_ask_tell("tell")
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(-1, 1) if x.ndim == 1 else x
+        ys = np.atleast_1d(np.asarray(y, dtype=np.float64)).ravel()
+        if x.shape[0] != len(self.lowerbounds) or x.shape[1] != ys.size:
+            raise ValueError(f"tell: x must be d x n with one y per column, got x {x.shape} and {ys.size} values")
+        keep = list(range(self._ask_pending.shape[1]))
+        if pending:
+            for j in range(x.shape[1]):
+                hit = next((k for k in keep if self._ask_pending[:, k].tobytes() == x[:, j].tobytes()), None)
+                if hit is None:
+                    raise ValueError(f"tell: column {j} of x is not a pending point (pass pending=False for an unsolicited observation)")
+                keep.remove(hit)
+        flipped = []
+        for j in range(x.shape[1]):
+            v = int(self.sense) * float(ys[j])
+            if v > int(self.sense) * self.observed_optimum:
+                self.observed_optimum, self.observed_optimizer = int(self.sense) * v, np.array(x[:, j])
+            flipped.append(v)
+        with _timeit(self, "model update"):
+            update_(self.model, np.asfortranarray(x), np.array(flipped))
+        self._ask_pending = np.asfortranarray(self._ask_pending[:, keep])
+        self.model.set_pending(self._ask_pending)
+        self._ask_told += x.shape[1]
+        if self._ask_told >= len(self.initializer):                                           # (tells of an incomplete initial design fit nothing)
+            with _timeit(self, "model hyperparameter optimization"):
+                optimizemodel_(self.modeloptimizer, self.model)
+
+    def result(self):
+        """What boptimize_ returns, for a run driven by ask / tell: the closing MaxMean search runs on the model itself (pending
+        points do not enter it)."""
+        self._refuse_ask_tell("result")
+        if self.model.nobs > 0:
+            with _timeit(self, "acquisition"):
+                opts = {k: v for k, v in self.acquisitionoptions.items() if k not in ("fantasies", "raise_tau")}
+                self.model_optimum, self.model_optimizer = acquire_max(MaxMean(), self.model, self.lowerbounds, self.upperbounds, opts,
+                                                                       self.rng)
+        self.duration.now = time.time()
+        return dict(observed_optimum=self.observed_optimum, observed_optimizer=self.observed_optimizer,
+                    model_optimum=int(self.sense) * self.model_optimum, model_optimizer=self.model_optimizer)
 
     def __repr__(self):                                                          # show :141-157
         s = f"Bayesian Optimization object\n\nmodel:\n{self.model!r}\n\nacquisition:\n{type(self.acquisition).__name__}"

@@ -30,6 +30,7 @@
 #include "../../include/bohip_loo.h"
 #include "../../include/bohip_loo_batch.h"
 #include "../../include/bohip_rep.h"
+#include "../../include/bohip_pend.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -45,6 +46,7 @@
 #include "kernels_con.hip"     // (after the scoring kernels: their functors, arg-max order and k_grad_finish's launch bounds; acq_log.h's continued fraction)
 #include "kernels_mo.hip"      // (after the constrained kernels: their record block; the scoring kernels' arg-max order)
 #include "kernels_ascent.hip"
+#include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -259,6 +261,23 @@ struct bohip_gp : gp_streams {
     // batched leave-one-out (bohip_gp_loo_grad_batch): [logp H x N] (layout::loo_batch_io), made when logp is asked for; the rest
     // of the call lives in fit_ws and fit_io
     DBuf<char> loo_batch_io;
+    // pending evaluations (include/bohip_pend.h): the set as the caller gave it (host), and what is derived from it and
+    // the model lazily -- V_p' [rows][ld] (the pending columns' V', as k_trigemm_sq stores it) and ONE block [Xp | mu_p | Sigma_p | L_p
+    // | V_p'V_p | pivot word] -- valid while pend_key equals what it was computed from; plus the block of one call (layout::pend_call)
+    std::vector<double> hpend;
+    int64_t pend_p = 0;
+    uint64_t pend_gen = 0, hyper_gen = 0;   // raised by bohip_gp_pending_set / bohip_gp_set_hyper
+    struct PendKey {
+        int64_t n = -1, ld = 0, refits = 0, appends = 0;
+        uint64_t hyper_gen = 0, pend_gen = 0;
+        double jitter = 0.0;
+        bool operator==(const PendKey& o) const {
+            return n == o.n && ld == o.ld && refits == o.refits && appends == o.appends && hyper_gen == o.hyper_gen &&
+                   pend_gen == o.pend_gen && jitter == o.jitter;
+        }
+    } pend_key;
+    DBuf<double> dPV;
+    DBuf<char> pend_state, pend_call;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
@@ -2406,6 +2425,7 @@ int bohip_gp_set_hyper(bohip_gp* g, const double* loglen, double logsig, double 
     g->lognoise = lognoise;
     g->beta = mean_const;
     g->stale = true;
+    g->hyper_gen++;
     return 0;
 }
 
@@ -4998,6 +5018,258 @@ int bohip_gp_get_timing(bohip_gp* g, const char** names, double* ms, int cap) {
         if (ms) ms[i] = g->tms[i];
     }
     return (int)g->tnames.size();
+}
+
+// ---- pending evaluations (include/bohip_pend.h; kernels_pend.hip) -----------------------------------------------------
+// An extension: the reference evaluates one point at a time (src/BayesianOptimization.jl:185-196).  The set lives on the handle as the
+// caller gave it; V_p', mu_p, Sigma_p and L_p are derived lazily and kept while the model and the set they were computed from stand.
+using PendCallWs = layout::PendCall<Best>;
+static bool pend_tau_acq(int acq_id) { return acq_id == BOHIP_ACQ_EI || acq_id == BOHIP_ACQ_PI || acq_id == BOHIP_ACQ_LOGEI; }
+static double pend_noise(const bohip_gp* g) {   // as on cK's diagonal
+    return std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;
+}
+static bohip_gp::PendKey pend_key_now(const bohip_gp* g) {
+    bohip_gp::PendKey k;
+    k.n = g->n; k.ld = g->ld; k.refits = g->refits; k.appends = g->appends; k.hyper_gen = g->hyper_gen; k.pend_gen = g->pend_gen;
+    k.jitter = g->jitter_last;
+    return k;
+}
+static constexpr size_t PEND_G_TILE = (size_t)TILE * PEND_GLD;   // the one 128 x 64 tile k_gemm_nt writes for V_p'V_p
+static size_t pend_state_layout(const bohip_gp* g, const void* base, layout::PendState* w) {
+    return layout::pend_state(base, PEND_PMAX, (size_t)g->d, PEND_G_TILE, w);
+}
+// V' of the chunk buffer (dVT alone: no U' here), as ensure_grad_scratch sizes it
+static int ensure_pend_vt(bohip_gp* g) {
+    const size_t n = (size_t)g->kst_rows * g->ld;
+    bool grew = false;
+    HIPCHK(g->dVT.reserve(n, g->stream, Grow::Exact, &grew));
+    if (grew) HIPCHK(hipMemsetAsync(g->dVT, 0, n * 8, g->stream));  // padding columns (>= N) must stay zero
+    return 0;
+}
+// The derived state up to date (the model is fresh, the set is not empty): one posterior pass over Xp that keeps V_p', mu_p from its
+// alpha row, V_p'V_p on the MFMA engine, Sigma_p and its factor in one workgroup.  A failed pivot: BOHIP_E_NOTPD, the state stays unset.
+static int ensure_pending(bohip_gp* g, layout::PendState* out) {
+    const int64_t p = g->pend_p;
+    HIPCHK(g->pend_state.reserve(pend_state_layout(g, nullptr, out), g->stream));
+    pend_state_layout(g, g->pend_state, out);
+    const bohip_gp::PendKey now = pend_key_now(g);
+    if (g->pend_key == now) return 0;
+    g->pend_key = bohip_gp::PendKey{};
+    CHK(ensure_score_scratch(g, p));
+    CHK(one_time_kernel_setup());
+    const int64_t rows = 2 * TILE;   // one tile of pending columns and a tile of head-room (tile-granular stores; the MFMA product reads 128 rows)
+    HIPCHK(g->dPV.reserve((size_t)rows * g->ld, g->stream));
+    HIPCHK(hipMemsetAsync(g->dPV, 0, (size_t)rows * g->ld * 8, g->stream));   // padding columns (>= N) and rows (>= p) start at zero
+    HIPCHK(hipMemcpyAsync(out->Xp, g->hpend.data(), (size_t)p * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const PassPlan pl = choose_route(g, p, WHOLE_K_ONLY);
+    const KernelHyper hp = make_hyper(g);
+    const int64_t chunks = chunk_pass(g, pl, out->Xp, hp, ChunkV{g->dPV, g->ld}, false, FuseParams{}, no_finish);   // (one chunk)
+    if (chunks < 0) return (int)chunks;
+    t_begin(g, "pend_state");
+    AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    hipLaunchKernelGGL(k_score, dim3(1), dim3(256), 0, g->stream, g->dq, pl.dm.Rpad, pl.dq_tiles(), g->dmu_raw, p, hp.sigma2, g->beta, mm,
+                       out->mu, (double*)nullptr, (double*)nullptr, (Best*)nullptr);
+    GemmNTParams gp{};   // (V_p'V_p)[i][j] = sum_n V_p'[i][n] V_p'[j][n]: one 128 x 64 tile, of which the lower p x p corner is read
+    gp.A = g->dPV; gp.lda = g->ld; gp.B = g->dPV; gp.ldb = g->ld; gp.C = out->G; gp.ldc = PEND_GLD;
+    gp.mt = 1; gp.nt64 = 1; gp.kc = pl.dm.T * (TILE / KC); gp.alpha = 1.0; gp.beta = 0.0;
+    CHK(launch_gemm_nt(g, gp));
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        LAUNCH_FAM(fam_low(hp), (k_pend_state<DT, true>), (k_pend_state<DT, false>), dim3(1), dim3(256), 0, g->stream, out->Xp, (int)p, hp,
+                   pend_noise(g), out->G, out->Sigma, out->L, out->info);
+    });
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    int info = 0;
+    HIPCHK(hipMemcpyAsync(&info, out->info, sizeof(int), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    if (info != 0)
+        return fail(BOHIP_E_NOTPD, "pending evaluations: the covariance of the " + std::to_string(p) + " pending points is not positive "
+                                   "definite (pivot " + std::to_string(info) + "); no jitter is added here");
+    g->pend_key = now;
+    return 0;
+}
+
+int bohip_gp_pending_set(bohip_gp* g, const double* Xp, int64_t p) {
+    if (!g) return fail(BOHIP_E_ARG, "pending_set: null handle");
+    if (p < 0 || p > BOHIP_PEND_PMAX)
+        return fail(BOHIP_E_ARG, "pending_set: p = " + std::to_string(p) + " does not lie in 0.." + std::to_string(BOHIP_PEND_PMAX) +
+                                 " (BOHIP_PEND_PMAX)");
+    if (p > 0 && !Xp) return fail(BOHIP_E_ARG, "pending_set: null Xp");
+    for (int64_t e = 0; e < p * g->d; ++e)
+        if (!std::isfinite(Xp[e])) return fail(BOHIP_E_ARG, "pending_set: coordinate " + std::to_string(e % g->d) + " of pending point " +
+                                                                std::to_string(e / g->d) + " is not finite");
+    if (p > 0) CHK(refuse_weighted(g, "bohip_gp_pending_set"));
+    g->hpend.assign(Xp, Xp + p * g->d);
+    g->pend_p = p;
+    g->pend_gen++;
+    return 0;
+}
+
+int bohip_gp_pending_info(bohip_gp* g, int64_t* p_out, double* Xp, double* mu_p, double* cov_p) {
+    if (!g) return fail(BOHIP_E_ARG, "pending_info: null handle");
+    const int64_t p = g->pend_p;
+    if (p_out) *p_out = p;
+    if (p == 0) return 0;
+    if (Xp) std::memcpy(Xp, g->hpend.data(), (size_t)p * g->d * 8);
+    if (!mu_p && !cov_p) return 0;
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(refuse_weighted(g, "bohip_gp_pending_info"));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    layout::PendState st;
+    CHK(ensure_pending(g, &st));
+    if (mu_p) HIPCHK(hipMemcpyAsync(mu_p, st.mu, (size_t)p * 8, hipMemcpyDeviceToHost, g->stream));
+    if (cov_p) HIPCHK(hipMemcpyAsync(cov_p, st.Sigma, (size_t)p * p * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+static int pend_check_acq(const char* who, int acq_id, const double* acq_params, int64_t S, int flags, AcqParams* ap) {
+    if (acq_id == BOHIP_ACQ_THOMPSON_DRAW) return fail(BOHIP_E_ARG, std::string(who) + ": a posterior draw has no score under fantasies");
+    if (!acq_id_scores(acq_id)) return fail(BOHIP_E_ARG, std::string(who) + ": unknown acq_id");
+    CHK(make_acq(acq_id, acq_params, ap));
+    if (S < 0 || S > BOHIP_PEND_SMAX)
+        return fail(BOHIP_E_ARG, std::string(who) + ": S = " + std::to_string(S) + " does not lie in 0.." + std::to_string(BOHIP_PEND_SMAX) +
+                                 " (BOHIP_PEND_SMAX)");
+    if (flags & ~BOHIP_PEND_RAISE_TAU) return fail(BOHIP_E_ARG, std::string(who) + ": unknown flags");
+    return 0;
+}
+// the averaging stage and the record: k_pend_score over R candidates, k_argmax_final when a record is wanted
+static int pend_blocks(int64_t R) { return (int)((R + PEND_SCORE_THREADS - 1) / PEND_SCORE_THREADS); }
+static int pend_score_stage(bohip_gp* g, PendScore ps, Best* blk, Best* d_best) {
+    const int nb = pend_blocks(ps.R);
+    ps.block_best = d_best ? blk : nullptr;
+    t_begin(g, "pend_score");
+    hipLaunchKernelGGL(k_pend_score, dim3(nb), dim3(PEND_SCORE_THREADS), 0, g->stream, ps);
+    if (d_best) hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, blk, nb, d_best, (long long)0);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
+                           int flags, double* score, double* mu, double* var, bohip_best* best) {
+    if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_pending: bad arguments");
+    AcqParams ap;
+    CHK(pend_check_acq("score_pending", acq_id, acq_params, S, flags, &ap));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    const int64_t p = g->pend_p;
+    if (p == 0) {   // no pending point: the call IS bohip_gp_score (and bohip_gp_predict for the moments)
+        CHK(bohip_gp_score(g, acq_id, acq_params, Xs, R, score, best));
+        if (R > 0 && (mu || var)) {
+            std::vector<double> tmp((size_t)R);
+            CHK(bohip_gp_predict(g, Xs, R, mu ? mu : tmp.data(), var ? var : tmp.data()));
+        }
+        return 0;
+    }
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    CHK(refuse_weighted(g, "bohip_gp_score_pending"));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    layout::PendState st;
+    CHK(ensure_pending(g, &st));
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    CHK(one_time_kernel_setup());
+    const PassPlan pl = choose_route(g, R, WHOLE_K_ONLY);   // the route that stores V'
+    CHK(ensure_pend_vt(g));
+    const int64_t S1 = std::max<int64_t>(S, 1), crows = round_up(std::min(R, pl.chunk), TILE);
+    // V'V_p is 128 x 64 tiles over a contraction of Npad: a chunk of 4096 candidates is 32 workgroups.  The contraction is cut into
+    // slices of kz 16-deep steps -- a function of the row tiles alone, so a candidate's value does not depend on the batch it is
+    // scored in -- whose planes k_pend_cross adds in ascending order (measured: profiles/pending_ab.txt).
+    const int kc_all = pl.dm.T * (TILE / KC), kz = std::max(8, (kc_all + 7) / 8), nsl = (kc_all + kz - 1) / kz;
+    const int64_t plane = crows * PEND_GLD;
+    const int nb = pend_blocks(R);
+    PendCallWs w;
+    auto lay = [&](const void* base) { return layout::pend_call(base, (size_t)(nsl * plane), (size_t)R, (size_t)p, (size_t)S1, 0, (size_t)nb, &w); };
+    HIPCHK(g->pend_call.reserve(lay(nullptr), g->stream));
+    lay(g->pend_call);
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const bool tau_acq = pend_tau_acq(acq_id), raise = tau_acq && (flags & BOHIP_PEND_RAISE_TAU);
+    t_begin(g, "pend_tables");
+    hipLaunchKernelGGL(k_pend_tables, dim3((unsigned)((S1 + 63) / 64)), dim3(64), 0, g->stream, st.mu, st.L, (int)p, (int)S1, S == 0 ? 1 : 0,
+                       (unsigned long long)seed, ap.p0, raise ? 1 : 0, w.Z, w.tau);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    const KernelHyper hp = make_hyper(g);
+    auto cross = [&](int64_t r0, int64_t r1) {   // per K*' chunk: C = V'V_p on the MFMA engine, then c, b = L_p^-1 c per candidate
+        t_begin(g, "pend_cross");
+        GemmNTParams gp{};
+        gp.A = g->dVT; gp.lda = g->ld; gp.B = g->dPV; gp.ldb = g->ld; gp.C = w.C; gp.ldc = PEND_GLD;
+        gp.mt = (int)((r1 - r0 + TILE - 1) / TILE); gp.nt64 = 1; gp.kc = kz; gp.alpha = 1.0; gp.beta = 0.0;
+        gp.kz = kz; gp.ktot = kc_all; gp.zA = (int64_t)kz * KC; gp.zB = (int64_t)kz * KC; gp.zC = plane;
+        CHK(launch_gemm_nt(g, gp, nsl));
+        const unsigned blocks = (unsigned)((r1 - r0 + PEND_CROSS_THREADS - 1) / PEND_CROSS_THREADS);
+        dispatch_dt(g->d, [&](auto dt) {
+            constexpr int DT = decltype(dt)::value;
+            LAUNCH_FAM(fam_low(hp), (k_pend_cross<DT, true>), (k_pend_cross<DT, false>), dim3(blocks), dim3(PEND_CROSS_THREADS), 0, g->stream,
+                       g->dXs.get(), r0, r1, hp, st.Xp, (int)p, st.L, w.C, nsl, plane, w.B);
+        });
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        return 0;
+    };
+    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, false, FuseParams{}, cross);
+    if (chunks < 0) return (int)chunks;
+    g->score_launches = chunks;
+    AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, pl.dm.Rpad, pl.dq_tiles(), g->dmu_raw, R,
+                       hp.sigma2, g->beta, mm, g->dmu.get(), g->dvar.get(), (double*)nullptr, (Best*)nullptr);
+    PendScore ps{};
+    ps.mu = g->dmu; ps.var = g->dvar; ps.B = w.B; ps.Z = w.Z; ps.tau = w.tau; ps.R = R; ps.p = (int)p; ps.S1 = (int)S1; ps.sub_bb = 1;
+    ps.tau_acq = tau_acq ? 1 : 0; ps.ap = ap; ps.score_out = score ? g->dscore.get() : nullptr; ps.var_out = g->dvar;
+    CHK(pend_score_stage(g, ps, w.blk, best ? w.best : nullptr));
+    if (score) HIPCHK(hipMemcpyAsync(score, g->dscore, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, g->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_pend_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t R, int64_t p, int64_t S, const double* mu,
+                      const double* var, const double* B, const double* Z, const double* tau_s, double* score, bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "pend_values: null handle");
+    AcqParams ap;
+    CHK(pend_check_acq("pend_values", acq_id, acq_params, S, 0, &ap));
+    if (S < 1) return fail(BOHIP_E_ARG, "pend_values: S = 0; the believer is one fantasy with z = 0 (1 <= S <= BOHIP_PEND_SMAX)");
+    if (p < 1 || p > BOHIP_PEND_PMAX)
+        return fail(BOHIP_E_ARG, "pend_values: p = " + std::to_string(p) + " does not lie in 1.." + std::to_string(BOHIP_PEND_PMAX) +
+                                 " (BOHIP_PEND_PMAX)");
+    if (R < 0 || !Z || (R > 0 && (!mu || !var || !B || !score))) return fail(BOHIP_E_ARG, "pend_values: bad arguments");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    const int nb = pend_blocks(R);
+    PendCallWs w;
+    auto lay = [&](const void* base) { return layout::pend_call(base, 0, (size_t)R, (size_t)p, (size_t)S, (size_t)R, (size_t)nb, &w); };
+    HIPCHK(g->pend_call.reserve(lay(nullptr), g->stream));
+    lay(g->pend_call);
+    HIPCHK(hipMemcpyAsync(w.mu, mu, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.var, var, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.B, B, (size_t)R * p * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.Z, Z, (size_t)S * p * 8, hipMemcpyHostToDevice, g->stream));
+    if (tau_s) HIPCHK(hipMemcpyAsync(w.tau, tau_s, (size_t)S * 8, hipMemcpyHostToDevice, g->stream));
+    PendScore ps{};
+    ps.mu = w.mu; ps.var = w.var; ps.B = w.B; ps.Z = w.Z; ps.tau = tau_s ? w.tau : nullptr; ps.R = R; ps.p = (int)p; ps.S1 = (int)S;
+    ps.sub_bb = 0; ps.tau_acq = pend_tau_acq(acq_id) ? 1 : 0; ps.ap = ap; ps.score_out = w.score; ps.var_out = nullptr;
+    CHK(pend_score_stage(g, ps, w.blk, best ? w.best : nullptr));
+    HIPCHK(hipMemcpyAsync(score, w.score, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
 }
 
 }  // extern "C"

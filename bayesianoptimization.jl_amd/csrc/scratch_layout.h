@@ -174,6 +174,31 @@ inline size_t loo(const void* base, size_t n_out, size_t nv, LooWs* w) {
     w->q = c.take<double>(nv, 16); w->sc = c.take<double>(nv, 16); w->t = c.take<double>(nv, 16); w->b = c.take<double>(nv, 16);
     return c.total();
 }
+// pending evaluations, the state derived from (model, pending set): [Xp pmax x d | mu_p | Sigma_p | L_p (pmax x pmax each) |
+// G = V_p'V_p, one MFMA tile | pivot word]
+struct PendState { double *Xp, *mu, *Sigma, *L, *G; int* info; };
+inline size_t pend_state(const void* base, size_t pmax, size_t d, size_t n_tile, PendState* w) {
+    Carve c(base);
+    w->Xp = c.take<double>(pmax * d, 16);
+    w->mu = c.take<double>(pmax); w->Sigma = c.take<double>(pmax * pmax); w->L = c.take<double>(pmax * pmax);
+    w->G = c.take<double>(n_tile, 16);
+    w->info = c.take<int>(4);
+    return c.total();
+}
+// pending evaluations, one call: [C = V'V_p of a chunk, 64 columns a row | B R x p | Z S x p | tau S | mu, var, score (R each: the
+// host-array stage only, n_io = R or 0) | workgroup records nb + 1]
+template <class Rec>
+struct PendCall { double *C, *B, *Z, *tau, *mu, *var, *score; Rec *blk, *best; };
+template <class Rec>
+size_t pend_call(const void* base, size_t n_c, size_t R, size_t p, size_t S, size_t n_io, size_t nb, PendCall<Rec>* w) {
+    Carve c(base);
+    w->C = c.take<double>(n_c, 16);
+    w->B = c.take<double>(R * p); w->Z = c.take<double>(S * p); w->tau = c.take<double>(S);
+    w->mu = c.take<double>(n_io); w->var = c.take<double>(n_io); w->score = c.take<double>(n_io);
+    w->blk = c.take<Rec>(nb + 1, REC_ALIGN);
+    w->best = w->blk + nb;
+    return c.total();
+}
 // the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
 // [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
 // Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the

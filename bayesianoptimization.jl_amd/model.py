@@ -429,6 +429,77 @@ class ElasticGPE:
                                               idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(val), _ptr(mu), _ptr(var)))
         return idx, val, mu, var
 
+    # -- pending evaluations (include/bohip_pend.h) ----------------------------------------------------------------
+    def set_pending(self, xp):
+        """The points that are out for evaluation and not back yet (d x p, p <= 32; an empty array clears the set).  Replaces the
+        model's pending set (bohip_gp_pending_set); nothing is computed until score_pending or pending_info reads it.  Every other
+        method ignores the set."""
+        if self.collapse:
+            raise ValueError("pending evaluations do not support a model with collapse=True (replicated sites)")
+        refuse_weighted(self, "set_pending (pending evaluations)")
+        xp = np.zeros((self.dim, 0), order="F") if xp is None or np.size(xp) == 0 else _cols(xp, self.dim)
+        check(self._lib.bohip_gp_pending_set(self._h, _ptr(xp) if xp.shape[1] else None, xp.shape[1]))
+        self._pending = xp.copy(order="F")
+        return self
+
+    def clear_pending(self):
+        return self.set_pending(None)
+
+    @property
+    def pending(self):
+        """A copy of the pending set, d x p."""
+        return getattr(self, "_pending", np.zeros((self.dim, 0), order="F")).copy(order="F")
+
+    def pending_info(self):
+        """(Xp [d, p], mu_p [p], Sigma_p [p, p]): the pending set with the model's predictive mean and covariance of the NOISY
+        outcomes there (bohip_gp_pending_info; nu on the diagonal).  Brings the model and the derived state up to date."""
+        p = C.c_int64()
+        check(self._lib.bohip_gp_pending_info(self._h, C.byref(p), None, None, None))
+        p = int(p.value)
+        xp, mu, cov = np.zeros((self.dim, p), order="F"), np.empty(p), np.empty((p, p))
+        if p:
+            check(self._lib.bohip_gp_pending_info(self._h, None, _ptr(xp), _ptr(mu), _ptr(cov)))
+        return xp, mu, cov
+
+    def score_pending(self, acq, params, xs, fantasies=0, seed=0, raise_tau=False, want_scores=True):
+        """The acquisition `acq` averaged over `fantasies` fantasised outcomes at the pending points (bohip_gp_score_pending; Snoek,
+        Larochelle & Adams 2012, section 3.2).  fantasies = 0: the Kriging believer (the mean stays, the variance shrinks).
+        raise_tau: the incumbent of EI / PI / LogEI follows each fantasy.  With an empty pending set it is `score`.  Returns
+        PendingScore(scores, mu, var, best_val, best_idx): mu the model's mean, var the variance conditioned on the pending points.
+        The model is not changed."""
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+        if p.size < 2:
+            p = np.concatenate([p, np.zeros(2 - p.size)])
+        sc = np.empty(R) if want_scores else None
+        mu, var = np.empty(R), np.empty(R)
+        best = Best()
+        check(self._lib.bohip_gp_score_pending(self._h, _lib.ACQ[acq], _ptr(p), _ptr(xs), R, int(fantasies), int(seed),
+                                               _lib.PEND_RAISE_TAU if raise_tau else 0, _ptr(sc) if want_scores else None, _ptr(mu),
+                                               _ptr(var), C.byref(best)))
+        return PendingScore(sc, mu, var, best.val, best.idx)
+
+    def pend_values(self, acq, params, mu, var, B, Z, tau_s=None):
+        """The averaging stage on its own, from host arrays (bohip_pend_values): mu, var [R], B [R, p], Z [S, p], tau_s [S] or None.
+        Returns (scores[R], best_val, best_idx)."""
+        mu, var = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64) for a in (mu, var))
+        B, Z = (np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for a in (B, Z))
+        R, pp, S = mu.size, Z.shape[1], Z.shape[0]
+        if var.size != R or B.shape != (R, pp):
+            raise ValueError("mu, var [R], B [R, p] and Z [S, p] disagree")
+        tau = None if tau_s is None else np.ascontiguousarray(np.atleast_1d(tau_s), dtype=np.float64)
+        if tau is not None and tau.size != S:
+            raise ValueError("tau_s must have one value per fantasy")
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+        if p.size < 2:
+            p = np.concatenate([p, np.zeros(2 - p.size)])
+        sc = np.empty(R)
+        best = Best()
+        check(self._lib.bohip_pend_values(self._h, _lib.ACQ[acq], _ptr(p), R, pp, S, _ptr(mu), _ptr(var), _ptr(B), _ptr(Z),
+                                          _ptr(tau) if tau is not None else None, _ptr(sc), C.byref(best)))
+        return sc, best.val, best.idx
+
     def score_grad(self, acq, params, xs):
         xs = _cols(xs, self.dim)
         R = xs.shape[1]
@@ -658,6 +729,18 @@ def _mll_grad_batch(lib, h, Theta, want_grad):
     check(lib.bohip_gp_mll_grad_batch(h, H, _ptr(Theta), _ptr(mll), _ptr(G) if want_grad else None,
                                       pivot.ctypes.data_as(C.POINTER(C.c_int64))))
     return mll, G, pivot
+
+
+class PendingScore:
+    """score_pending's result: scores [R] (None without want_scores), mu [R] the model's mean, var [R] the variance conditioned on
+    the pending points, and the arg-max record."""
+    __slots__ = ("scores", "mu", "var", "best_val", "best_idx")
+
+    def __init__(self, scores, mu, var, best_val, best_idx):
+        self.scores, self.mu, self.var, self.best_val, self.best_idx = scores, mu, var, float(best_val), int(best_idx)
+
+    def __iter__(self):
+        return iter((self.scores, self.mu, self.var, self.best_val, self.best_idx))
 
 
 class LOO:

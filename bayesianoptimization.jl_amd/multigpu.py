@@ -116,6 +116,11 @@ class MultiGPE:
         (DESIGN.md 10).  Use ElasticGPE.select_batch on one device."""
         raise NotImplementedError("MultiGPE.select_batch: batch selection runs on one device (ElasticGPE.select_batch)")
 
+    def set_pending(self, xp):
+        """Not implemented for a device list: the pending set and the state derived from it live on ONE handle.  Use
+        ElasticGPE.set_pending on one device."""
+        raise NotImplementedError("MultiGPE.set_pending: pending evaluations run on one device (ElasticGPE.set_pending)")
+
     def set_candidates(self, xs):
         xs = _cols(xs, self.dim)
         check(self._lib.bohip_mgp_set_candidates(self._h, _ptr(xs), xs.shape[1]))
