@@ -9,9 +9,9 @@ from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
                     score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values,
-                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations, PendingScore)
+                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations, PendingScore, NEIScore)
 from .multigpu import MultiGPE, comm_unique_id
-from .acquisition import (ExpectedImprovement, LogExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
+from .acquisition import (ExpectedImprovement, LogExpectedImprovement, NoisyExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
                           acquire_max, acquire_max_pending, acquire_batch, acquire_thompson_batch, acquire_model_max, defaultoptions)
 from .bopt import (BOpt, boptimize_, optimize, merge_with_defaults, MAPGPOptimizer, MarginalGPOptimizer, NoModelOptimizer, optimizemodel_,
@@ -29,4 +29,4 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
            "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values",
            "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO", "collapse_evaluations",
-           "PendingScore", "acquire_max_pending"]
+           "PendingScore", "acquire_max_pending", "NoisyExpectedImprovement", "NEIScore"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h, include/bohip_nei.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -225,6 +225,19 @@ PEND_SIGNATURES = {
     "bohip_pend_values": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_nei.h declares (noisy expected improvement: EI / PI / LogEI averaged over posterior draws of the noise-free
+# function values at the observed sites)
+NEI_SMAX = 1024
+NEI_INFO_REFITS, NEI_INFO_APPENDS, NEI_INFO_REBUILDS, NEI_INFO_JITTER_STEPS, NEI_INFO_BYTES, NEI_INFO_DELTA = 0, 1, 2, 3, 4, 5
+NEI_SIGNATURES = {
+    "bohip_gp_nei_prepare": (C.c_int, [_gp, C.c_double, C.c_int64, C.c_uint64]),
+    "bohip_gp_nei_fantasies": (C.c_int, [_gp, C.c_double, C.c_int64, C.c_uint64, _dp, _dp]),
+    "bohip_gp_score_nei": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_nei_values": (C.c_int, [_gp, C.c_int, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_gp_nei_info": (C.c_int, [_gp, C.c_int, _dp]),
+    "bohip_gp_nei_release": (C.c_int, [_gp]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -283,7 +296,8 @@ def load():
                               + list(QEI_SIGNATURES.items()) + list(ACQ_SIGNATURES.items()) + list(KG_SIGNATURES.items())
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
-                              + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())):
+                              + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
+                              + list(NEI_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

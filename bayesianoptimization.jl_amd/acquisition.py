@@ -147,6 +147,30 @@ class MaxValueEntropySearch(AbstractAcquisition):
         self.samples, self.mode = int(samples), mode
 
 
+class NoisyExpectedImprovement(AbstractAcquisition):
+    """Noisy expected improvement (include/bohip_nei.h; Letham, Karrer, Ottoni & Bakshy 2019, eq. 6): EI -- with
+    log=True LogEI's log of the averaged EI -- averaged over S posterior draws of the NOISE-FREE function values at the observed
+    sites.  Every draw brings its own incumbent, so the largest raw observation (the luckiest noise draw) plays no part.  S = 0:
+    the plug-in form, whose incumbent is the largest posterior mean at the sites.  An extension: the reference has no such type,
+    and no default uses it.  It has no parameter that follows the model (setparams_ does nothing) and no gradient in x:
+    acquisitionfunction takes a point or a d x R matrix, acquire_max takes the device's arg-max over `maxeval` Latin-hypercube
+    candidates per restart.  `seed` fixes the draws, so the acquisition is one deterministic function of x during a search."""
+    acq_id = "NEI"
+
+    def __init__(self, S=32, seed=0, log=False, jitter_rel=1e-8):
+        if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 0 <= S <= 1024:
+            raise ValueError(f"S must be an integer in 0 .. 1024 (BOHIP_NEI_SMAX), got {S!r}")
+        if not (jitter_rel > 0 and math.isfinite(jitter_rel)):
+            raise ValueError(f"jitter_rel must be positive and finite, got {jitter_rel!r}")
+        self.S, self.seed, self.log, self.jitter_rel = int(S), int(seed), bool(log), float(jitter_rel)
+
+    def score(self, model, xs, want_scores=True):
+        if not hasattr(model, "nei"):
+            raise NotImplementedError(f"{type(model).__name__} has no nei")
+        return model.nei(xs, S=self.S, seed=self.seed, acq="logei" if self.log else "ei", jitter_rel=self.jitter_rel,
+                         want_scores=want_scores)
+
+
 class Marginalised(AbstractAcquisition):
     """Marginalised(a): the acquisition `a` averaged over the hyper-parameter samples that MarginalGPOptimizer left on the model
     (model.hyper_samples = (Theta[H, P], weights)): a(x) = sum_h w_h a(x; theta_h), the integrated acquisition of Snoek, Larochelle &
@@ -320,6 +344,13 @@ def acquisitionfunction(a, model, rng=None):
             return model.mes(x, samples=a.samples, mode=a.mode, seed=seed).values
 
         return mes
+    if isinstance(a, NoisyExpectedImprovement):
+        def nei(x):
+            x = np.asarray(x, dtype=np.float64)
+            sc = a.score(model, x).score
+            return float(sc[0]) if x.ndim == 1 else sc
+
+        return nei
     if isinstance(a, Constrained):
         def constrained(x):
             x = np.asarray(x, dtype=np.float64)
@@ -362,7 +393,7 @@ def acquisitionfunction(a, model, rng=None):
 # ---- src/acquisition.jl ----------------------------------------------------------------------------------
 def defaultoptions(model_type, acq_type):                    # :4-9
     if isinstance(acq_type, type) and issubclass(acq_type, (KnowledgeGradient, MaxValueEntropySearch, Constrained,
-                                                                     ExpectedHypervolumeImprovement)):
+                                                                     ExpectedHypervolumeImprovement, NoisyExpectedImprovement)):
         return dict(method="LD_LBFGS", restarts=1, maxeval=1024)   # (1024: the smallest candidate chunk a model can have)
     if isinstance(acq_type, type) and issubclass(acq_type, ThompsonSamplingSimple):
         return dict(method="GN_DIRECT_L", restarts=1, maxeval=2000)
@@ -698,6 +729,21 @@ def _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng):
     return maxf, maxx
 
 
+def _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng):
+    """NoisyExpectedImprovement: no gradient in x.  Every restart scores `maxeval` Latin-hypercube candidates in ONE model.nei call
+    and takes the device's arg-max; the fantasies are built once (the seed is the acquisition's).  The first maximum over the
+    restarts wins (strict '>')."""
+    maxf, maxx = -math.inf, lb.copy()
+    for _ in range(restarts):
+        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+        val, idx = a.score(model, xs, want_scores=False).best
+        if idx >= 0 and val > maxf:                               # :62 strict '>'
+            maxf, maxx = float(val), xs[:, int(idx)].copy()
+    if not np.isfinite(maxf):
+        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
+    return maxf, maxx
+
+
 def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts=None):
     """Marginalised(a).  Every restart scores `maxeval` Latin-hypercube candidates under all hyper-parameter samples in ONE
     model.score_ensemble call and takes its arg-max record.  The first maximum over the restarts wins (strict '>').
@@ -832,6 +878,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, MaxValueEntropySearch):                      # (`method` is accepted, not used)
         return _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, NoisyExpectedImprovement):                   # (`method` is accepted, not used)
+        return _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, Constrained):                                # (`method` is accepted, not used; "refine" adds the ascent)
         if not hasattr(model, "feasible_incumbent"):
             raise ValueError(f"Constrained needs a ConstrainedGPE, not {type(model).__name__}")
@@ -933,7 +981,7 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
 
 
 _PENDING_REFUSED = (KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement,
-                    ThompsonSamplingSimple)
+                    ThompsonSamplingSimple, NoisyExpectedImprovement)
 
 
 def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):

@@ -9,7 +9,7 @@ import warnings
 
 import numpy as np
 
-from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, ThompsonSamplingSimple, _batched_lbfgs_ascent,
+from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, NoisyExpectedImprovement, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_max_pending, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
 from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, refuse_weighted, update_
@@ -508,7 +508,10 @@ class BOpt:
         """What boptimize_ returns, for a run driven by ask / tell: the closing MaxMean search runs on the model itself (pending
         points do not enter it)."""
         self._refuse_ask_tell("result")
-        if self.model.nobs > 0:
+        if self.model.nobs > 0 and isinstance(self.acquisition, NoisyExpectedImprovement):
+            with _timeit(self, "acquisition"):
+                self.model_optimum, self.model_optimizer = _best_site(self.model)
+        elif self.model.nobs > 0:
             with _timeit(self, "acquisition"):
                 opts = {k: v for k, v in self.acquisitionoptions.items() if k not in ("fantasies", "raise_tau")}
                 self.model_optimum, self.model_optimizer = acquire_max(MaxMean(), self.model, self.lowerbounds, self.upperbounds, opts,
@@ -629,6 +632,15 @@ def _batch_iteration(o):
         optimizemodel_(o.modeloptimizer, o.model)
 
 
+def _best_site(model):
+    """(mean, site): the observed site with the largest posterior mean and that mean -- what a run under NoisyExpectedImprovement
+    reports as model_optimum / model_optimizer (the first such site on a tie).  The largest raw observation (observed_optimum) is the
+    luckiest noise draw; this is the model's answer to "which of the points I tried is best"."""
+    mu, _ = model.predict_f(model.x)
+    j = int(np.argmax(mu))
+    return float(mu[j]), np.array(model.x[:, j])
+
+
 def boptimize_(o):
     """boptimize!(o) :176-207.  Re-calling resumes: init! zeroes the per-call counter but keeps the cumulative one."""
     init_(o.duration)
@@ -657,6 +669,8 @@ def boptimize_(o):
     with _timeit(o, "acquisition"):
         if isinstance(o.model, ConstrainedGPE):                                   # (no unconstrained model maximum: the feasible optimum stands)
             o.model_optimum, o.model_optimizer = int(o.sense) * o.observed_optimum, np.array(o.observed_optimizer)
+        elif o.model.nobs > 0 and isinstance(o.acquisition, NoisyExpectedImprovement):   # (noisy evaluations: the best SITE under the model)
+            o.model_optimum, o.model_optimizer = _best_site(o.model)
         elif o.model.nobs > 0 and not isinstance(o.model, MultiObjectiveGPE):     # (two objectives: no single optimum, the result carries the front)
             o.model_optimum, o.model_optimizer = acquire_max(MaxMean(), o.model, o.lowerbounds, o.upperbounds,
                                                              o.acquisitionoptions, o.rng)   # acquire_model_max :200

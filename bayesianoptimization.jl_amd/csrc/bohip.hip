@@ -31,6 +31,7 @@
 #include "../../include/bohip_loo_batch.h"
 #include "../../include/bohip_rep.h"
 #include "../../include/bohip_pend.h"
+#include "../../include/bohip_nei.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -47,6 +48,7 @@
 #include "kernels_mo.hip"      // (after the constrained kernels: their record block; the scoring kernels' arg-max order)
 #include "kernels_ascent.hip"
 #include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
+#include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -135,6 +137,7 @@ struct bohip_gp : gp_streams {
         hipSetDevice(device);
         if (own_stream) hipStreamSynchronize(own_stream);
         if (comm) bohip_gp_comm_destroy(this);
+        delete nei;
     }
     int d = 0, kern = 0;
     int64_t n = 0, cap = 0, ld = 0;
@@ -278,6 +281,25 @@ struct bohip_gp : gp_streams {
     } pend_key;
     DBuf<double> dPV;
     DBuf<char> pend_state, pend_call;
+    // noisy expected improvement (include/bohip_nei.h): the COMPANION -- a handle of its own for the same X under the same
+    // kernel parameters with delta on the diagonal, owned by this one, made at the first call of that header and kept in step lazily
+    // (nei_jrel, nei_steps: what its diagonal was set from) -- and the fantasies [F | alpha_s | work | tau_s] (layout::nei_state), valid
+    // while nei_key equals what they were computed from; plus the block of one call (layout::nei_call)
+    bohip_gp* nei = nullptr;
+    double nei_jrel = -1.0, nei_delta = 0.0;
+    int nei_steps = 0;
+    int64_t nei_rebuilds = 0, nei_ld = 0;
+    struct NeiKey {
+        int64_t n = -1, ld = 0, refits = 0, appends = 0, c_refits = 0, c_appends = 0, S = -1;
+        uint64_t hyper_gen = 0, data_version = 0, seed = 0;
+        double jitter = 0.0, delta = 0.0;
+        bool operator==(const NeiKey& o) const {
+            return n == o.n && ld == o.ld && refits == o.refits && appends == o.appends && c_refits == o.c_refits && c_appends == o.c_appends &&
+                   S == o.S && hyper_gen == o.hyper_gen && data_version == o.data_version && seed == o.seed && jitter == o.jitter &&
+                   delta == o.delta;
+        }
+    } nei_key;
+    DBuf<char> nei_ws, nei_call;
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
@@ -5269,6 +5291,351 @@ int bohip_pend_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t
     if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
+    return 0;
+}
+
+// ---- noisy expected improvement (include/bohip_nei.h; kernels_nei.hip) -----------------------------------------------
+// An extension.  The noise-free model of the same sites is a bohip_gp of its own, owned by the caller's handle: the refit plan, the
+// incremental append and the posterior pass (small, split-K, whole-K) are the model's, not copies of them.  It runs on the owner's
+// stream, is made at the first call of this header and is kept in step lazily; the fantasies live in one block on the owner.
+using NeiCallWs = layout::NeiCall<Best>;
+static int nei_kernel_setup() {
+    static bool done[64] = {false};
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    return once_per_device(done, dev, [] {
+        HIPCHK(hipFuncSetAttribute((const void*)k_nei_means, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+        return 0;
+    });
+}
+static int nei_check(const char* who, int acq_id, int64_t S, double jitter_rel, bool want_acq) {
+    if (want_acq && !pend_tau_acq(acq_id))
+        return fail(BOHIP_E_ARG, std::string(who) + ": noisy expected improvement averages an acquisition with an incumbent (EI, PI, LogEI)");
+    if (S < 0 || S > BOHIP_NEI_SMAX)
+        return fail(BOHIP_E_ARG, std::string(who) + ": S = " + std::to_string(S) + " does not lie in 0.." + std::to_string(BOHIP_NEI_SMAX) +
+                                 " (BOHIP_NEI_SMAX)");
+    if (!(jitter_rel > 0.0) || !std::isfinite(jitter_rel)) return fail(BOHIP_E_ARG, std::string(who) + ": jitter_rel must be positive and finite");
+    return 0;
+}
+// the companion's stage times behind the owner's (the owner's were collected)
+static void nei_merge_timing(bohip_gp* g) {
+    bohip_gp* c = g->nei;
+    if (!g->timing || g->timing_accumulate || !c) return;
+    g->tnames.insert(g->tnames.end(), c->tnames.begin(), c->tnames.end());   // (what an append of the companion collected itself)
+    g->tms.insert(g->tms.end(), c->tms.begin(), c->tms.end());
+    t_collect(c);
+    g->tnames.insert(g->tnames.end(), c->tnames.begin(), c->tnames.end());
+    g->tms.insert(g->tms.end(), c->tms.begin(), c->tms.end());
+    c->tnames.clear();
+    c->tms.clear();
+}
+// The companion up to date with the owner's X and kernel parameters at delta = jitter_rel sigma_f^2 (the owner is fresh).  New rows go
+// through append_rows: up to 32 of them onto a fresh factor are ONE incremental append, anything else a refit.  A failed pivot tries
+// delta x 10, up to three times.
+static int nei_companion_sync(bohip_gp* g, double jitter_rel) {
+    if (!g->nei) {
+        bohip_gp* c = nullptr;
+        CHK(bohip_gp_create(g->d, std::max<int64_t>(g->cap, 1), g->kern, g->device, &c));
+        c->jitter_rel = 0.0; c->jitter_tries = 0;   // (the steps here are the header's, not BOHIP_JITTER's)
+        g->nei = c;
+        g->nei_jrel = -1.0;
+        g->nei_key = bohip_gp::NeiKey{};
+    }
+    bohip_gp* c = g->nei;
+    c->stream = g->stream;
+    c->batch_hint = g->batch_hint;
+    c->timing = g->timing; c->timing_dominant_only = g->timing_dominant_only; c->timing_accumulate = false;
+    t_reset(c);
+    bool same = jitter_rel == g->nei_jrel && c->logsig == g->logsig;
+    for (int k = 0; k < g->d; ++k) same = same && c->loglen[k] == g->loglen[k];
+    const double eps = std::numeric_limits<double>::epsilon();
+    int rc = 0;
+    for (int step = same ? g->nei_steps : 0; step <= 3; ++step) {
+        if (!same || step != g->nei_steps) {
+            const double delta = jitter_rel * std::exp(2.0 * g->logsig) * std::pow(10.0, step);
+            for (int k = 0; k < DMAX; ++k) c->loglen[k] = g->loglen[k];
+            c->logsig = g->logsig;
+            c->lognoise = delta > 2.0 * eps ? 0.5 * std::log(delta - eps) : -400.0;
+            c->stale = true;
+            g->nei_jrel = jitter_rel;
+            g->nei_steps = step;
+            g->nei_delta = std::exp(2.0 * c->lognoise) + eps;
+        }
+        c->beta = g->beta;
+        if (c->n < g->n) {
+            const int64_t n0 = c->n;
+            rc = append_rows(c, g->hX.data() + n0 * g->d, g->hy.data() + n0, nullptr, nullptr, g->n - n0);
+        } else {
+            rc = ensure_fresh(c);
+        }
+        if (rc != BOHIP_E_NOTPD) return rc;
+        same = false;
+    }
+    return rc;
+}
+static bohip_gp::NeiKey nei_key_now(const bohip_gp* g, int64_t S, uint64_t seed) {
+    bohip_gp::NeiKey k;
+    k.n = g->n; k.ld = g->ld; k.refits = g->refits; k.appends = g->appends; k.c_refits = g->nei->refits; k.c_appends = g->nei->appends;
+    k.S = S; k.hyper_gen = g->hyper_gen; k.data_version = g->data_version; k.seed = seed; k.jitter = g->jitter_last; k.delta = g->nei_delta;
+    return k;
+}
+// out[s][i] = sum_j in[s][j] B[i][j] for the rows of the fantasy matrices and the Npad rows of a resident factor B (both K-major).
+// The factors are triangular by TILES only where their readers are (the other tiles of dW, dWT are never read by the model's passes
+// and hold whatever the factorisation parked there), so the products take the same limits: a lower factor (L, W: j <= i) is the A
+// operand with khi_from_m and the result leaves transposed; an upper one (W': j >= i) is the B operand with klo_from_n.
+static int nei_product(bohip_gp* g, const double* in, const double* B, int64_t ldb, bool lower, double* out, int64_t rows, int64_t ld,
+                       int64_t Npad) {
+    GemmNTParams p{};
+    p.kc = (int)(Npad / KC); p.alpha = 1.0; p.beta = 0.0;
+    if (lower) {
+        p.A = B; p.lda = ldb; p.B = in; p.ldb = ld; p.C = nullptr; p.CT = out; p.ldct = ld;
+        p.mt = (int)(Npad / TILE); p.nt64 = (int)(rows / CTILE); p.khi_from_m = 1;
+    } else {
+        p.A = in; p.lda = ld; p.B = B; p.ldb = ldb; p.C = out; p.ldc = ld;
+        p.mt = (int)(rows / TILE); p.nt64 = (int)(Npad / CTILE); p.klo_from_n = 1;
+    }
+    return launch_gemm_nt(g, p);
+}
+// The fantasies and alpha_s up to date (the owner and the companion are fresh): five N x N x S products on the MFMA engine between
+// the element-wise stages of kernels_nei.hip.
+static int ensure_nei_fantasies(bohip_gp* g, int64_t S, uint64_t seed, layout::NeiState* st) {
+    bohip_gp* c = g->nei;
+    const int64_t S1 = std::max<int64_t>(S, 1), rows = round_up(S1, TILE), N = g->n, Npad = (int64_t)row_tiles(g) * TILE;
+    const bohip_gp::NeiKey now = nei_key_now(g, S, seed);
+    if (g->nei_key == now && g->nei_ws) {
+        layout::nei_state(g->nei_ws, (size_t)rows, (size_t)g->nei_ld, (size_t)S1, st);
+        return 0;
+    }
+    g->nei_key = bohip_gp::NeiKey{};
+    const int64_t ld = g->ld;
+    const size_t bytes = layout::nei_state(nullptr, (size_t)rows, (size_t)ld, (size_t)S1, st);
+    HIPCHK(g->nei_ws.reserve(bytes + 128, g->stream));
+    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(g->nei_ws.get()) + 127) / 128 * 128);   // (hipMalloc aligns to more; the layout wants 128)
+    layout::nei_state(base, (size_t)rows, (size_t)ld, (size_t)S1, st);
+    g->nei_ld = ld;
+    CHK(one_time_kernel_setup());
+    t_begin(g, "nei_fantasies");
+    HIPCHK(hipMemsetAsync(base, 0, bytes, g->stream));   // rows >= S1 and columns >= N start at zero (and stay: the stages write i < N)
+    const dim3 grid_n((unsigned)((N + 255) / 256), (unsigned)S1), grid_pad((unsigned)((Npad + 255) / 256), (unsigned)S1);
+    const dim3 grid_mask((unsigned)((Npad - N + 255) / 256), (unsigned)rows);
+    const double nu = pend_noise(g);
+    const double* invr = g->weighted ? g->dinvr.get() : nullptr;
+    const int zero = S == 0 ? 1 : 0;
+    double *Z = st->w0, *G = st->w1, *RH = st->w2, *T = st->w3, *Q = st->w0, *P = st->w1, *T2 = st->w3;
+    if (S > 0) {
+        hipLaunchKernelGGL(k_nei_normals, grid_n, dim3(256), 0, g->stream, Z, ld, N, (int)S, (unsigned long long)seed);
+        CHK(nei_product(g, Z, c->dL, c->ld, true, G, rows, ld, Npad));                          // g_s = L_d z_s
+    }
+    hipLaunchKernelGGL(k_nei_resid, grid_n, dim3(256), 0, g->stream, g->dy.get(), g->beta, G, ld, N, zero, (unsigned long long)seed, nu, invr, RH);
+    CHK(nei_product(g, RH, g->dW, g->ld, true, T, rows, ld, Npad));                             // W r_s
+    hipLaunchKernelGGL(k_nei_mask, grid_mask, dim3(256), 0, g->stream, T, ld, N, Npad);   // (row N of W holds alpha)
+    CHK(nei_product(g, T, g->dWT, g->ld, false, Q, rows, ld, Npad));                             // A^-1 r_s = W'(W r_s)
+    hipLaunchKernelGGL(k_nei_fant, grid_n, dim3(256), 0, g->stream, G, Q, ld, N, g->beta, nu, invr, RH, st->F);
+    hipLaunchKernelGGL(k_nei_tau, dim3((unsigned)S1), dim3(256), 0, g->stream, st->F, ld, N, st->tau);
+    CHK(nei_product(g, RH, c->dW, c->ld, true, P, rows, ld, Npad));                             // W_d h_s
+    hipLaunchKernelGGL(k_nei_t2, grid_pad, dim3(256), 0, g->stream, P, ld, N, Npad, zero, (unsigned long long)seed, T2);
+    CHK(nei_product(g, T2, c->dWT, c->ld, false, st->alpha, rows, ld, Npad));                    // alpha_s = W_d'(z_s + W_d h_s)
+    hipLaunchKernelGGL(k_nei_mask, grid_mask, dim3(256), 0, g->stream, st->alpha, ld, N, Npad);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    g->nei_key = now;
+    g->nei_rebuilds++;
+    return 0;
+}
+// everything a call of the header needs, in order; *st: the fantasies
+static int nei_ready(bohip_gp* g, double jitter_rel, int64_t S, uint64_t seed, layout::NeiState* st) {
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    CHK(nei_companion_sync(g, jitter_rel));
+    return ensure_nei_fantasies(g, S, seed, st);
+}
+
+int bohip_gp_nei_prepare(bohip_gp* g, double jitter_rel, int64_t S, uint64_t seed) {
+    return bohip_gp_nei_fantasies(g, jitter_rel, S, seed, nullptr, nullptr);
+}
+
+int bohip_gp_nei_fantasies(bohip_gp* g, double jitter_rel, int64_t S, uint64_t seed, double* F, double* tau) {
+    if (!g) return fail(BOHIP_E_ARG, "nei_fantasies: null handle");
+    CHK(nei_check("nei_fantasies", 0, S, jitter_rel, false));
+    layout::NeiState st;
+    CHK(nei_ready(g, jitter_rel, S, seed, &st));
+    const int64_t S1 = std::max<int64_t>(S, 1);
+    if (F) HIPCHK(hipMemcpy2DAsync(F, (size_t)g->n * 8, st.F, (size_t)g->nei_ld * 8, (size_t)g->n * 8, (size_t)S1, hipMemcpyDeviceToHost, g->stream));
+    if (tau) HIPCHK(hipMemcpyAsync(tau, st.tau, (size_t)S1 * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    nei_merge_timing(g);
+    return 0;
+}
+
+// the averaging stage of the candidates [r0, r1) whose means sit in w.MT (column 0 = r0), and -- last -- the record
+static int nei_reduce_stage(bohip_gp* g, const NeiCallWs& w, const double* var, const double* tau, int64_t ldm, int nsl, int64_t plane,
+                            int64_t r0, int64_t r1, int64_t S1, int acq_id, bool want_best) {
+    NeiReduce nr{};
+    nr.MT = w.MT; nr.var = var; nr.tau = tau; nr.ldm = ldm; nr.nsl = nsl; nr.plane = plane; nr.r0 = r0; nr.r1 = r1; nr.S1 = (int)S1;
+    nr.ap = AcqParams{acq_id, 0.0, 0.0};
+    nr.score_out = w.score; nr.mu_out = w.mu; nr.block_best = want_best ? w.blk : nullptr;
+    t_begin(g, "nei_reduce");
+    hipLaunchKernelGGL(k_nei_reduce, dim3((unsigned)((r1 - r0 + NEI_RED_THREADS - 1) / NEI_RED_THREADS)), dim3(NEI_RED_THREADS), 0, g->stream, nr);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+static int nei_blocks(int64_t R) { return (int)((R + NEI_RED_THREADS - 1) / NEI_RED_THREADS); }
+static int nei_record_stage(bohip_gp* g, const NeiCallWs& w, int64_t R) {
+    hipLaunchKernelGGL(k_argmax_final, dim3(1), dim3(256), 0, g->stream, w.blk, nei_blocks(R), w.best, (long long)0);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bohip_gp_score_nei(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
+                       double jitter_rel, double* score, double* mu, double* var, bohip_best* best) {
+    (void)acq_params;   // (tau is the fantasy's own)
+    if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_nei: bad arguments");
+    CHK(nei_check("score_nei", acq_id, S, jitter_rel, true));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    layout::NeiState st;
+    CHK(nei_ready(g, jitter_rel, S, seed, &st));
+    bohip_gp* c = g->nei;
+    CHK(ensure_xs(c, R));
+    CHK(ensure_score_scratch(c, R));
+    CHK(one_time_kernel_setup());
+    CHK(nei_kernel_setup());
+    const PassPlan pl = choose_route(c, R, RouteWants{true, true, Prune::No});   // the companion's ordinary pass: the existing plan
+    const int64_t S1 = std::max<int64_t>(S, 1), Sp = round_up(S1, CTILE);
+    const int64_t crows = round_up(pl.route == Route::WholeK ? std::min(R, pl.chunk) : R, TILE);
+    // The means' contraction is cut into slices of kz 16-deep steps -- a function of the row tiles alone, so a candidate's value does
+    // not depend on the batch it is scored in -- whose planes k_nei_reduce adds in ascending order (32 workgroups over the whole
+    // contraction at R = 4096, S = 64 took 0.21 ms: profiles/nei_ab.txt).  The planes of one launch stay below 256 MB: a chunk is
+    // taken mrows candidates at a time (which changes no bit).
+    const int kc_all = (int)(pl.dm.Npad / KC), kz = std::max(8, (kc_all + 7) / 8), nsl = (kc_all + kz - 1) / kz;
+    const int64_t mrows = std::min(crows, std::max<int64_t>(TILE, ((int64_t)256 << 20) / (8 * nsl * Sp) / TILE * TILE));
+    const int64_t plane = Sp * mrows;
+    NeiCallWs w;
+    auto lay = [&](const void* base) { return layout::nei_call(base, (size_t)(nsl * plane), (size_t)R, 0, 0, (size_t)nei_blocks(R), &w); };
+    HIPCHK(g->nei_call.reserve(lay(nullptr) + 128, g->stream));
+    lay(reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(g->nei_call.get()) + 127) / 128 * 128));
+    HIPCHK(hipMemcpyAsync(c->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const KernelHyper hp = make_hyper(c);
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    // per K*' chunk (rows 0 .. r1 - r0 of the companion's chunk buffer, the one its variance contraction read): the means of every
+    // fantasy on the MFMA engine, then the average over the fantasies
+    auto finish = [&](int64_t r0, int64_t r1) {
+        for (int64_t b0 = r0; b0 < r1; b0 += mrows) {
+            const int64_t b1 = std::min(r1, b0 + mrows);
+            NeiMeans nm{};
+            nm.A = c->dKsT + (b0 - r0) * c->ld; nm.lda = c->ld; nm.B = st.alpha; nm.ldb = g->nei_ld; nm.MT = w.MT; nm.ldm = mrows; nm.plane = plane;
+            nm.mt = (int)((b1 - b0 + TILE - 1) / TILE); nm.nt = (int)(Sp / CTILE); nm.kc = kc_all; nm.kz = kz; nm.beta = g->beta;
+            t_begin(c, "nei_means");
+            hipLaunchKernelGGL(k_nei_means, dim3((unsigned)(nm.mt * nm.nt), (unsigned)nsl), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, nm);
+            HIPCHK(hipGetLastError());
+            t_end(c);
+            CHK(nei_reduce_stage(c, w, c->dvar, st.tau, mrows, nsl, plane, b0, b1, S1, acq_id, best != nullptr));
+        }
+        return 0;
+    };
+    if (pl.route == Route::Small) {
+        CHK(small_pass_mfma(c, c->dXs, R, mm, c->dmu, c->dvar, nullptr, nullptr, 0, nullptr));
+        t_begin(c, "kstar");
+        CHK(launch_kstar_any(c, c->dXs, 0, R, pl.dm.Npad, hp));   // (the small pass builds its K* in registers: the means need it in memory)
+        t_end(c);
+        CHK(finish(0, R));
+    } else if (pl.route == Route::Split) {
+        CHK(split_posterior(c, c->dXs, pl, false));
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, c->dq.get(), pl.dm.Rpad, pl.dq_tiles(),
+                           c->dmu_raw.get(), R, hp.sigma2, c->beta, mm, c->dmu.get(), c->dvar.get(), (double*)nullptr, (Best*)nullptr);
+        HIPCHK(hipGetLastError());
+        CHK(finish(0, R));
+    } else {
+        auto chunk_finish = [&](int64_t r0, int64_t r1) {
+            hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, c->dq.get() + r0, pl.dm.Rpad,
+                               pl.dq_tiles(), c->dmu_raw.get() + r0, r1 - r0, hp.sigma2, c->beta, mm, c->dmu.get() + r0, c->dvar.get() + r0,
+                               (double*)nullptr, (Best*)nullptr);
+            HIPCHK(hipGetLastError());
+            return finish(r0, r1);
+        };
+        const int64_t chunks = chunk_pass(c, pl, c->dXs, hp, ChunkV{}, false, FuseParams{}, chunk_finish);
+        if (chunks < 0) return (int)chunks;
+        c->score_launches = chunks;
+    }
+    if (best) CHK(nei_record_stage(g, w, R));
+    if (score) HIPCHK(hipMemcpyAsync(score, w.score, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, w.mu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, c->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    nei_merge_timing(g);
+    return 0;
+}
+
+int bohip_nei_values(bohip_gp* g, int acq_id, int64_t R, int64_t S, const double* mu_s, const double* var, const double* tau_s,
+                     double* score, double* mu_mean, bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "nei_values: null handle");
+    CHK(nei_check("nei_values", acq_id, S, 1.0, true));
+    if (S < 1) return fail(BOHIP_E_ARG, "nei_values: S = 0; the plug-in form is one fantasy (1 <= S <= BOHIP_NEI_SMAX)");
+    if (R < 0 || !tau_s || (R > 0 && (!mu_s || !var || !score))) return fail(BOHIP_E_ARG, "nei_values: bad arguments");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    NeiCallWs w;
+    auto lay = [&](const void* base) { return layout::nei_call(base, (size_t)(S * R), (size_t)R, (size_t)R, (size_t)S, (size_t)nei_blocks(R), &w); };
+    HIPCHK(g->nei_call.reserve(lay(nullptr) + 128, g->stream));
+    lay(reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(g->nei_call.get()) + 127) / 128 * 128));
+    std::vector<double> mt((size_t)(S * R));   // fantasy-major, as k_nei_means leaves the means
+    for (int64_t r = 0; r < R; ++r)
+        for (int64_t s = 0; s < S; ++s) mt[(size_t)(s * R + r)] = mu_s[r * S + s];
+    HIPCHK(hipMemcpyAsync(w.MT, mt.data(), (size_t)(S * R) * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.var, var, (size_t)R * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(w.tau, tau_s, (size_t)S * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(nei_reduce_stage(g, w, w.var, w.tau, R, 1, 0, 0, R, S, acq_id, best != nullptr));
+    if (best) CHK(nei_record_stage(g, w, R));
+    HIPCHK(hipMemcpyAsync(score, w.score, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (mu_mean) HIPCHK(hipMemcpyAsync(mu_mean, w.mu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));   // (mt lives until here)
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_nei_info(const bohip_gp* g, int what, double* value) {
+    if (!g || !value) return fail(BOHIP_E_ARG, "null argument");
+    const bohip_gp* c = g->nei;
+    switch (what) {
+        case BOHIP_NEI_INFO_REFITS: *value = c ? (double)c->refits : 0.0; return 0;
+        case BOHIP_NEI_INFO_APPENDS: *value = c ? (double)c->appends : 0.0; return 0;
+        case BOHIP_NEI_INFO_REBUILDS: *value = (double)g->nei_rebuilds; return 0;
+        case BOHIP_NEI_INFO_JITTER_STEPS: *value = c ? (double)g->nei_steps : 0.0; return 0;
+        case BOHIP_NEI_INFO_DELTA: *value = c ? g->nei_delta : 0.0; return 0;
+        case BOHIP_NEI_INFO_BYTES: {
+            size_t b = g->nei_ws.capacity() + g->nei_call.capacity();
+            if (c) b += 8 * (c->dL.capacity() + c->dW.capacity() + c->dWT.capacity() + c->dS.capacity() + c->dApp.capacity() + c->dKsT.capacity());
+            *value = (double)b;
+            return 0;
+        }
+        default: return fail(BOHIP_E_ARG, "unknown info id");
+    }
+}
+
+int bohip_gp_nei_release(bohip_gp* g) {
+    if (!g) return fail(BOHIP_E_ARG, "null handle");
+    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    delete g->nei;
+    g->nei = nullptr;
+    g->nei_ws.release();
+    g->nei_call.release();
+    g->nei_key = bohip_gp::NeiKey{};
+    g->nei_jrel = -1.0; g->nei_delta = 0.0; g->nei_steps = 0; g->nei_rebuilds = 0;
     return 0;
 }
 

@@ -199,6 +199,31 @@ size_t pend_call(const void* base, size_t n_c, size_t R, size_t p, size_t S, siz
     w->best = w->blk + nb;
     return c.total();
 }
+// noisy expected improvement, the fantasies derived from (model, companion, S, seed): [F | alpha | four work matrices (rows x ld each,
+// 128-byte rows for the LDS-DMA of the products) | tau S1]
+struct NeiState { double *F, *alpha, *w0, *w1, *w2, *w3, *tau; };
+inline size_t nei_state(const void* base, size_t rows, size_t ld, size_t S1, NeiState* w) {
+    Carve c(base);
+    w->F = c.take<double>(rows * ld, 128); w->alpha = c.take<double>(rows * ld, 128);
+    w->w0 = c.take<double>(rows * ld, 128); w->w1 = c.take<double>(rows * ld, 128);
+    w->w2 = c.take<double>(rows * ld, 128); w->w3 = c.take<double>(rows * ld, 128);
+    w->tau = c.take<double>(S1);
+    return c.total();
+}
+// noisy expected improvement, one call: [MT = the chunk's means, fantasy-major | score, mu R | mu_s R x S, var, tau (the host-array stage
+// only, n_io = R or 0) | workgroup records nb + 1]
+template <class Rec>
+struct NeiCall { double *MT, *score, *mu, *var, *tau; Rec *blk, *best; };
+template <class Rec>
+size_t nei_call(const void* base, size_t n_mt, size_t R, size_t n_io, size_t S, size_t nb, NeiCall<Rec>* w) {
+    Carve c(base);
+    w->MT = c.take<double>(n_mt, 128);
+    w->score = c.take<double>(R); w->mu = c.take<double>(R);
+    w->var = c.take<double>(n_io); w->tau = c.take<double>(n_io ? S : 0);
+    w->blk = c.take<Rec>(nb + 1, REC_ALIGN);
+    w->best = w->blk + nb;
+    return c.total();
+}
 // the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
 // [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
 // Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the

@@ -500,6 +500,48 @@ class ElasticGPE:
                                           _ptr(tau) if tau is not None else None, _ptr(sc), C.byref(best)))
         return sc, best.val, best.idx
 
+    # -- noisy expected improvement (include/bohip_nei.h) -------------------------------------------------------------
+    def nei(self, X, S=32, seed=0, acq="ei", jitter_rel=1e-8, want_scores=True):
+        """Noisy expected improvement at the columns of X (bohip_gp_score_nei; Letham, Karrer, Ottoni & Bakshy 2019, eq. 6): `acq`
+        ("ei", "pi" or "logei") averaged over S posterior draws of the NOISE-FREE function values at the observed sites, each with
+        its own incumbent tau_s and its own noise-free conditional mean.  S = 0: the plug-in form, the incumbent is the largest
+        posterior mean at the sites.  Returns NEIScore(score, mu, var, best, tau): mu the mean over the draws of m_s, var the shared
+        noise-free variance, best = (value, index), tau the S incumbents.  The model is not changed."""
+        return _nei(self._lib, self._h, _cols(X, self.dim), S, seed, acq, jitter_rel, want_scores)
+
+    def nei_fantasies(self, S=32, seed=0, jitter_rel=1e-8):
+        """(F [max(S, 1), n], tau [max(S, 1)]): the fantasised noise-free function values at the observed sites, row s = f_s, and
+        their maxima (bohip_gp_nei_fantasies).  Brings the model, its noise-free companion and the fantasies up to date."""
+        return _nei_fantasies(self._lib, self._h, self.nobs, S, seed, jitter_rel)
+
+    def nei_prepare(self, S=32, seed=0, jitter_rel=1e-8):
+        check(self._lib.bohip_gp_nei_prepare(self._h, float(jitter_rel), int(S), int(seed)))
+        return self
+
+    def nei_values(self, acq, mu_s, var, tau_s):
+        """The averaging stage on its own, from host arrays (bohip_nei_values): mu_s [R, S], var [R], tau_s [S].
+        Returns (scores[R], mean over s of mu_s [R], best_val, best_idx)."""
+        mu_s = np.ascontiguousarray(np.atleast_2d(mu_s), dtype=np.float64)
+        var, tau_s = (np.ascontiguousarray(np.atleast_1d(a), dtype=np.float64) for a in (var, tau_s))
+        R, S = mu_s.shape
+        if var.size != R or tau_s.size != S:
+            raise ValueError("mu_s [R, S], var [R] and tau_s [S] disagree")
+        sc, mm = np.empty(R), np.empty(R)
+        best = Best()
+        check(self._lib.bohip_nei_values(self._h, _lib.ACQ[_NEI_ACQ[str(acq).lower()]], R, S, _ptr(mu_s), _ptr(var), _ptr(tau_s), _ptr(sc),
+                                         _ptr(mm), C.byref(best)))
+        return sc, mm, best.val, best.idx
+
+    def nei_info(self, what):
+        """bohip_gp_nei_info: a _lib.NEI_INFO_* quantity (counts come back as int, the delta in force as float)."""
+        v = C.c_double()
+        check(self._lib.bohip_gp_nei_info(self._h, int(what), C.byref(v)))
+        return v.value if what == _lib.NEI_INFO_DELTA else int(v.value)
+
+    def nei_release(self):
+        check(self._lib.bohip_gp_nei_release(self._h))
+        return self
+
     def score_grad(self, acq, params, xs):
         xs = _cols(xs, self.dim)
         R = xs.shape[1]
@@ -741,6 +783,41 @@ class PendingScore:
 
     def __iter__(self):
         return iter((self.scores, self.mu, self.var, self.best_val, self.best_idx))
+
+
+_NEI_ACQ = {"ei": "EI", "pi": "PI", "logei": "LogEI"}
+
+
+class NEIScore:
+    """nei's result: score [R] (None without want_scores), mu [R] the mean over the fantasies of m_s, var [R] the noise-free variance,
+    best = (value, index) of the arg-max and tau [max(S, 1)] the fantasies' incumbents."""
+    __slots__ = ("score", "mu", "var", "best", "tau")
+
+    def __init__(self, score, mu, var, best, tau):
+        self.score, self.mu, self.var, self.best, self.tau = score, mu, var, (float(best[0]), int(best[1])), tau
+
+    def __iter__(self):
+        return iter((self.score, self.mu, self.var, self.best, self.tau))
+
+
+def _nei(lib, h, xs, S, seed, acq, jitter_rel, want_scores=True):
+    R = xs.shape[1]
+    name = _NEI_ACQ[str(acq).lower()]
+    sc = np.empty(R) if want_scores else None
+    mu, var = np.empty(R), np.empty(R)
+    best = Best()
+    tau = np.empty(max(int(S), 1))
+    check(lib.bohip_gp_nei_fantasies(h, float(jitter_rel), int(S), int(seed), None, _ptr(tau)))   # (kept: the score call rebuilds nothing)
+    check(lib.bohip_gp_score_nei(h, _lib.ACQ[name], None, _ptr(xs), R, int(S), int(seed), float(jitter_rel),
+                                 _ptr(sc) if want_scores else None, _ptr(mu), _ptr(var), C.byref(best)))
+    return NEIScore(sc, mu, var, (best.val, best.idx), tau)
+
+
+def _nei_fantasies(lib, h, n, S, seed, jitter_rel):
+    S1 = max(int(S), 1)
+    F, tau = np.empty((S1, n)), np.empty(S1)
+    check(lib.bohip_gp_nei_fantasies(h, float(jitter_rel), int(S), int(seed), _ptr(F), _ptr(tau)))
+    return F, tau
 
 
 class LOO:

@@ -190,6 +190,19 @@ class MultiGPE:
         g = self._lib.bohip_mgp_handle(self._h, 0)
         return _sample_joint(self._lib, g, _cols(xs, self.dim), S, seed, jitter, max_tries, want_samples, want_factor)
 
+    def nei(self, X, S=32, seed=0, acq="ei", jitter_rel=1e-8, want_scores=True):
+        """ElasticGPE.nei (bohip_gp_score_nei) on the FIRST replica, as sample_joint: the noise-free companion and the fantasies live
+        on ONE handle."""
+        from .model import _nei
+
+        return _nei(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(X, self.dim), S, seed, acq, jitter_rel, want_scores)
+
+    def nei_fantasies(self, S=32, seed=0, jitter_rel=1e-8):
+        """ElasticGPE.nei_fantasies (bohip_gp_nei_fantasies) on the FIRST replica."""
+        from .model import _nei_fantasies
+
+        return _nei_fantasies(self._lib, self._lib.bohip_mgp_handle(self._h, 0), self._y.size, S, seed, jitter_rel)
+
     def qei_batch(self, xs, q, S=256, seed=0, tau=None, jitter=1e-12, max_tries=40, want_samples=False):
         """ElasticGPE.qei_batch (bohip_gp_qei_batch) on the FIRST replica, as sample_joint."""
         from .model import _qei_batch, maxy

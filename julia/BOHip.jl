@@ -358,6 +358,7 @@ include("BOHipLOO.jl")     # leave-one-out cross-validation (include/bohip_loo.h
 include("BOHipLOOBatch.jl") # its objective at H settings in one launch (include/bohip_loo_batch.h): loo_grad_batch
 include("BOHipRep.jl")      # replicated sites (include/bohip_rep.h): append_sites!, collapse_evaluations, sites_info, site_reps
 include("BOHipPend.jl")     # pending evaluations (include/bohip_pend.h): pending_set!, pending_info, score_pending, acquire_max_pending
+include("BOHipNEI.jl")      # noisy expected improvement (include/bohip_nei.h): nei, nei_fantasies, nei_values, NoisyExpectedImprovement
 """
     acquire_thompson_batch(m, X, q; seed = rand(UInt64) >> 1) -> (values, 1-based columns)
 
