@@ -9,7 +9,8 @@ from ._lib import BohipError, NotPositiveDefinite
 from .model import (ElasticGPE, MeanConst, MeanZero, SEArd, SEIso, Mat52Ard, Mat52Iso, Mat32Ard, Mat32Iso, Mat12Ard, Mat12Iso,
                     mean_var, myrand, dims, maxy, update_, PosteriorPaths, EnsembleScore, score_ensemble,
                     score_ensemble_grad, ConstrainedGPE, ConstrainedScore, con_values,
-                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, LOO, collapse_evaluations, PendingScore, NEIScore)
+                    MultiObjectiveGPE, MOScore, mo_front, ehvi_values, score_mo, ManyObjectiveGPE, mom_front, mom_boxes,
+                    ehvi_values_many, score_mom, LOO, collapse_evaluations, PendingScore, NEIScore)
 from .multigpu import MultiGPE, comm_unique_id
 from .acquisition import (ExpectedImprovement, LogExpectedImprovement, NoisyExpectedImprovement, KnowledgeGradient, MaxValueEntropySearch, Marginalised, Constrained, ExpectedHypervolumeImprovement, ProbabilityOfImprovement, UpperConfidenceBound, ThompsonSamplingSimple,
                           MutualInformation, MaxMean, BrochuBetaScaling, NoBetaScaling, acquisitionfunction, setparams_,
@@ -28,5 +29,5 @@ __all__ = ["BOpt", "ExpectedImprovement", "LogExpectedImprovement", "KnowledgeGr
            "ElasticGPE", "MultiGPE", "GPE", "MeanConst", "MeanZero", "SEArd", "SEIso", "Mat52Ard", "Mat52Iso", "Mat32Ard",
            "Mat32Iso", "Mat12Ard", "Mat12Iso", "Marginalised", "MarginalGPOptimizer", "EnsembleScore",
            "Constrained", "ConstrainedGPE", "ConstrainedScore", "con_values",
-           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "LOO", "collapse_evaluations",
+           "ExpectedHypervolumeImprovement", "MultiObjectiveGPE", "MOScore", "mo_front", "ehvi_values", "score_mo", "ManyObjectiveGPE", "mom_front", "mom_boxes", "ehvi_values_many", "score_mom", "LOO", "collapse_evaluations",
            "PendingScore", "acquire_max_pending", "NoisyExpectedImprovement", "NEIScore"]

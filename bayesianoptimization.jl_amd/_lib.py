@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h, include/bohip_nei.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_mom.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h, include/bohip_nei.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -198,6 +198,16 @@ MO_SIGNATURES = {
     "bohip_gp_score_mo": (C.c_int, [_gp, _gp, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
 }
 
+# every symbol include/bohip_mom.h declares (two to four objectives: the front and its boxes on the host, the exact EHVI stage over the
+# boxes, the whole call)
+MOM_OBJ_MAX, MOM_FRONT_MAX, MOM_BOX_MAX, MOM_LANES = 4, 256, 65536, 64
+MOM_SIGNATURES = {
+    "bohip_mom_front": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp, C.c_int64, _i64p, _dp]),
+    "bohip_mom_boxes": (C.c_int, [_dp, C.c_int64, C.c_int64, _dp, _dp, _i64p, _i32p, C.c_int64, _i64p]),
+    "bohip_mom_ehvi_values": (C.c_int, [_gp, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, C.POINTER(Best)]),
+    "bohip_gp_score_mom": (C.c_int, [C.POINTER(_gp), C.c_int64, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(Best)]),
+}
+
 # every symbol include/bohip_loo.h declares (leave-one-out predictions at the observations, their log-probability and its gradient)
 LOO_SIGNATURES = {
     "bohip_gp_loo": (C.c_int, [_gp, _dp, _dp, _dp, _dp]),
@@ -297,7 +307,7 @@ def load():
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
-                              + list(NEI_SIGNATURES.items())):
+                              + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -233,7 +233,8 @@ class Constrained(AbstractAcquisition):
 class ExpectedHypervolumeImprovement(AbstractAcquisition):
     """The exact expected hypervolume improvement of two objectives over the observed front of a MultiObjectiveGPE
     (include/bohip_mo.h; Emmerich et al. 2016, Yang et al. 2019).  An extension: the reference optimises one objective.
-    It has no parameter of its own: the front and the reference point are the model's.  acquisitionfunction takes a d x R matrix;
+    It has no parameter of its own: the front and the reference point are the model's.  Over a ManyObjectiveGPE (2 to 4 objectives) it
+    is the sum over the boxes of the front (include/bohip_mom.h, DESIGN.md 6w).  acquisitionfunction takes a d x R matrix;
     acquire_max takes the device's arg-max over `maxeval` Latin-hypercube candidates per restart and, with the option "refine": n > 0,
     climbs the n best on the gradient route."""
     acq_id = "EHVI"

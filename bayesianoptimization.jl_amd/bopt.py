@@ -564,10 +564,14 @@ def _evaluate_constrained(o, x):
 
 
 def _evaluate_two(o, x):
-    """func(x) -> (y_1, y_2) for a MultiObjectiveGPE: sense flips both; there is no optimum to track."""
+    """func(x) -> (y_1, y_2) for a MultiObjectiveGPE, (y_1, .., y_M) for a ManyObjectiveGPE: sense flips all; there is no optimum to
+    track."""
     with _timeit(o, "function evaluation"):
         out = np.atleast_1d(np.asarray(o.func(x), dtype=np.float64)).ravel()
-    if out.size != 2:
+    M = len(o.model.objectives)
+    if M != 2 and out.size != M:
+        raise ValueError(f"func must return (y_1, .., y_{M}), the {M} objectives' values, got {out.size} numbers")
+    if out.size != 2 and M == 2:
         raise ValueError(f"func must return (y_1, y_2), the two objectives' values, got {out.size} numbers")
     return int(o.sense) * out
 
@@ -685,12 +689,13 @@ def boptimize_(o):
 
 
 def _two_objective_result(o):
-    """The result of a two-objective run: the observed front as x [d, n_front] and y [2, n_front] in the caller's sense (ascending
-    in the model's first objective), the hypervolume it dominates above the model's reference point (`ref`, in the caller's sense
-    too), and None where a single-objective run reports an optimum."""
+    """The result of a run with M = 2 (or, on a ManyObjectiveGPE, 2 to 4) objectives: the observed front as x [d, n_front] and y
+    [M, n_front] in the caller's sense (in the model's order: ascending in its first objective, lexicographic beyond two), the
+    hypervolume it dominates above the model's reference point (`ref`, in the caller's sense too), and None where a single-objective
+    run reports an optimum."""
     m = o.model
     if m.nobs == 0:
-        front_x, front_y, hv, ref = np.zeros((m.dim, 0)), np.zeros((2, 0)), 0.0, None
+        front_x, front_y, hv, ref = np.zeros((m.dim, 0)), np.zeros((len(m.objectives), 0)), 0.0, None
     else:
         idx = m.front_indices()
         front_x, front_y, hv = np.array(m.x[:, idx]), int(o.sense) * m.y[:, idx], m.hypervolume

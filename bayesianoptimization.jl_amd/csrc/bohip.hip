@@ -27,6 +27,7 @@
 #include "../../include/bohip_ens_grad.h"
 #include "../../include/bohip_con.h"
 #include "../../include/bohip_mo.h"
+#include "../../include/bohip_mom.h"
 #include "../../include/bohip_loo.h"
 #include "../../include/bohip_loo_batch.h"
 #include "../../include/bohip_rep.h"
@@ -46,6 +47,7 @@
 #include "kernels_path.hip"    // (after the scoring kernels: their generator, arg-max order and kernel expressions)
 #include "kernels_con.hip"     // (after the scoring kernels: their functors, arg-max order and k_grad_finish's launch bounds; acq_log.h's continued fraction)
 #include "kernels_mo.hip"      // (after the constrained kernels: their record block; the scoring kernels' arg-max order)
+#include "kernels_mom.hip"     // (after the two-objective kernel: mo_psi and its grid cap)
 #include "kernels_ascent.hip"
 #include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
 #include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
@@ -56,6 +58,7 @@
 #include "scratch_layout.h"    // devbuf.h (who owns device memory) and the layouts of the carved scratch blocks
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cerrno>
@@ -63,6 +66,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <fcntl.h>
 #include <sys/file.h>
@@ -257,6 +261,14 @@ struct bohip_gp : gp_streams {
     // two-objective scoring (bohip_gp_score_mo / bohip_mo_ehvi_values): the front's corners and heights, 2 BOHIP_MO_FRONT_MAX + 3
     // doubles made on first use; everything else lives in ensure_con's block with C = 1
     DBuf<double> mo_front;
+    // two to four objectives (bohip_gp_score_mom / bohip_mom_ehvi_values): the level arrays, BOHIP_MOM_OBJ_MAX rows of
+    // BOHIP_MOM_FRONT_MAX + 2 doubles, and the packed boxes, M words each (grows with the front's box count); everything else lives in
+    // ensure_con's block with C = M - 1
+    DBuf<double> mom_levels;
+    DBuf<unsigned> mom_boxes;
+    // ... and the host's plan of what those two buffers hold now (null: nothing valid): a call with the same front and ref -- every step
+    // of an ascent -- neither decomposes nor uploads again
+    std::shared_ptr<struct MomPlan> mom_plan;
     // leave-one-out (bohip_gp_loo / bohip_gp_loo_grad): ONE block of vectors (layout::loo), and for the gradient one more matrix of
     // the model's size, Z = cK^-1 diag(sqrt c); both made on first use, nothing in them outlives a call
     DBuf<char> loo_ws;
@@ -4148,6 +4160,302 @@ int bohip_gp_score_mo(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64
     CHK(multi_posterior(obj0, models, 2, false, Xs, R, jac, b));
     CHK(mo_ehvi_stage(obj0, n_front, b, R, false, jac, best != nullptr));
     return multi_download(obj0, models, 2, b, R, score, grad, mu, var, best);
+}
+
+// ---- two to four objectives (kernels_mom.hip, include/bohip_mom.h) -------------------------------------------------
+static_assert(MOM_OBJ_MAX == BOHIP_MOM_OBJ_MAX && MOM_FRONT_MAX == BOHIP_MOM_FRONT_MAX && MOM_BOX_MAX == BOHIP_MOM_BOX_MAX &&
+                  MOM_LANES == BOHIP_MOM_LANES && MOM_OBJ_MAX <= BOHIP_CON_CMAX + 1,
+              "the kernel's plan and the header agree; ensure_con's block holds M rows");
+using MomPt = std::array<int, BOHIP_MOM_OBJ_MAX>;   // a front point as level indices, 1 .. n_levels[m] - 2
+
+// the non-dominated subset of pts in the first `dim` coordinates (weak dominance; of equal projections one): in descending
+// lexicographic order whatever dominates a point stands before it, and dominance is transitive, so the kept ones decide
+static std::vector<MomPt> mom_filter(std::vector<MomPt> pts, int dim) {
+    auto key_gt = [dim](const MomPt& p, const MomPt& q) { return std::lexicographical_compare(q.begin(), q.begin() + dim, p.begin(), p.begin() + dim); };
+    auto key_eq = [dim](const MomPt& p, const MomPt& q) { return std::equal(p.begin(), p.begin() + dim, q.begin()); };
+    std::sort(pts.begin(), pts.end(), key_gt);
+    pts.erase(std::unique(pts.begin(), pts.end(), key_eq), pts.end());
+    std::vector<MomPt> keep;
+    for (const MomPt& p : pts) {
+        const bool dominated = std::any_of(keep.begin(), keep.end(), [&](const MomPt& k) {
+            for (int c = 0; c < dim; ++c)
+                if (k[c] < p[c]) return false;
+            return true;
+        });
+        if (!dominated) keep.push_back(p);
+    }
+    return keep;
+}
+// the slabs of P (non-dominated in `dim` coordinates) along coordinate dim - 1: z[0] = 0 (ref), the distinct levels ascending, then
+// nl - 1 (+Inf); slab j is [z[j], z[j + 1])
+static std::vector<int> mom_slabs(const std::vector<MomPt>& P, int dim, int nl) {
+    std::vector<int> z{0};
+    for (const MomPt& p : P) z.push_back(p[dim - 1]);
+    std::sort(z.begin(), z.end());
+    z.erase(std::unique(z.begin(), z.end()), z.end());
+    z.push_back(nl - 1);
+    return z;
+}
+static std::vector<MomPt> mom_above(const std::vector<MomPt>& P, int dim, int zj) {
+    std::vector<MomPt> Q;
+    for (const MomPt& p : P)
+        if (p[dim - 1] > zj) Q.push_back(p);
+    return mom_filter(std::move(Q), dim - 1);
+}
+struct MomFront {
+    int M = 0;
+    std::vector<double> levels[BOHIP_MOM_OBJ_MAX];   // L_m
+    std::vector<MomPt> pts;                          // the front in level indices
+    int64_t n_boxes = 0;
+    std::vector<int32_t> lo[BOHIP_MOM_OBJ_MAX], hi[BOHIP_MOM_OBJ_MAX];   // per box, filled up to `keep` boxes
+};
+// decomp(P, r) of bohip_mom.h, section 1: counts every box, stores the first `keep`
+static void mom_decomp(MomFront* f, const std::vector<MomPt>& P, int dim, MomPt* lo, MomPt* hi, int64_t keep) {
+    if (dim == 1) {
+        int l = 0;
+        for (const MomPt& p : P) l = std::max(l, p[0]);
+        (*lo)[0] = l;
+        (*hi)[0] = (int)f->levels[0].size() - 1;
+        if (f->n_boxes < keep)
+            for (int m = 0; m < f->M; ++m) { f->lo[m].push_back((*lo)[m]); f->hi[m].push_back((*hi)[m]); }
+        ++f->n_boxes;
+        return;
+    }
+    const std::vector<int> z = mom_slabs(P, dim, (int)f->levels[dim - 1].size());
+    for (size_t j = 0; j + 1 < z.size(); ++j) {
+        (*lo)[dim - 1] = z[j];
+        (*hi)[dim - 1] = z[j + 1];
+        mom_decomp(f, mom_above(P, dim, z[j]), dim - 1, lo, hi, keep);
+    }
+}
+// HV_dim(P) of bohip_mom.h, section 1
+static double mom_hv(const MomFront& f, const std::vector<MomPt>& P, int dim) {
+    if (dim == 1) {
+        int l = 0;
+        for (const MomPt& p : P) l = std::max(l, p[0]);
+        return f.levels[0][l] - f.levels[0][0];
+    }
+    const std::vector<int> z = mom_slabs(P, dim, (int)f.levels[dim - 1].size());
+    const std::vector<double>& L = f.levels[dim - 1];
+    double a = 0.0;
+    for (size_t j = 0; j + 2 < z.size(); ++j) a += (L[z[j + 1]] - L[z[j]]) * mom_hv(f, mom_above(P, dim, z[j]), dim - 1);
+    return a;
+}
+static int mom_check_common(const std::string& pre, int64_t M, const double* ref) {
+    if (M < 2 || M > BOHIP_MOM_OBJ_MAX)
+        return fail(BOHIP_E_ARG, pre + "M must be in [2, " + std::to_string(BOHIP_MOM_OBJ_MAX) + "], got " + std::to_string(M));
+    if (!ref) return fail(BOHIP_E_ARG, pre + "ref is null");
+    for (int64_t m = 0; m < M; ++m)
+        if (!std::isfinite(ref[m])) return fail(BOHIP_E_ARG, pre + "the reference point is not finite");
+    return 0;
+}
+// the levels and the index form of points known to be finite and strictly above ref (M x n of stride ld)
+static void mom_index(const double* pts, int64_t ld, int64_t n, int64_t M, const double* ref, MomFront* f) {
+    f->M = (int)M;
+    f->pts.assign((size_t)n, MomPt{});
+    for (int64_t m = 0; m < M; ++m) {
+        std::vector<double>& L = f->levels[m];
+        L.assign(pts + m * ld, pts + m * ld + n);
+        std::sort(L.begin(), L.end());
+        L.erase(std::unique(L.begin(), L.end()), L.end());
+        L.insert(L.begin(), ref[m]);
+        for (int64_t i = 0; i < n; ++i) f->pts[(size_t)i][m] = (int)(std::lower_bound(L.begin() + 1, L.end(), pts[m * ld + i]) - L.begin());
+        L.push_back(INFINITY);
+    }
+}
+
+// host only: the observations strictly above ref that no other weakly dominates, of equal ones one, lexicographic ascending
+int bohip_mom_front(const double* Y, int64_t M, int64_t n, const double* ref, double* front, int64_t cap, int64_t* n_front, double* hv) {
+    CHK(mom_check_common("mom_front: ", M, ref));
+    if (n < 0 || cap < 0 || (n > 0 && !Y) || (cap > 0 && !front)) return fail(BOHIP_E_ARG, "mom_front: bad arguments");
+    std::vector<double> above;   // M x k, stride n
+    above.resize((size_t)(M * std::max<int64_t>(n, 1)));
+    int64_t k = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        bool in = true;
+        for (int64_t m = 0; m < M; ++m) {
+            if (!std::isfinite(Y[m * n + i])) return fail(BOHIP_E_ARG, "mom_front: observation " + std::to_string(i) + " is not finite");
+            in = in && Y[m * n + i] > ref[m];
+        }
+        if (!in) continue;
+        for (int64_t m = 0; m < M; ++m) above[(size_t)(m * n + k)] = Y[m * n + i];
+        ++k;
+    }
+    MomFront f;
+    mom_index(above.data(), n, k, M, ref, &f);
+    std::vector<MomPt> keep = mom_filter(f.pts, (int)M);   // (index order is value order)
+    std::reverse(keep.begin(), keep.end());
+    const int64_t nf = (int64_t)keep.size();
+    if (n_front) *n_front = nf;
+    if (hv) *hv = mom_hv(f, keep, (int)M);
+    if (cap == 0) return 0;
+    if (cap < nf) return fail(BOHIP_E_ARG, "mom_front: the front has " + std::to_string(nf) + " points, cap is " + std::to_string(cap));
+    for (int64_t i = 0; i < nf; ++i)
+        for (int64_t m = 0; m < M; ++m) front[m * cap + i] = f.levels[m][(size_t)keep[(size_t)i][m]];
+    return 0;
+}
+
+// validates a front (any order) and builds its levels and, with keep > 0, its boxes
+static int mom_make_front(const char* who, int64_t M, const double* front, int64_t n, const double* ref, int64_t keep, MomFront* f) {
+    const std::string pre = std::string(who) + ": ";
+    CHK(mom_check_common(pre, M, ref));
+    if (n < 0 || (n > 0 && !front)) return fail(BOHIP_E_ARG, pre + "bad front arguments");
+    if (n > BOHIP_MOM_FRONT_MAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "a front of " + std::to_string(n) + " points; at most " + std::to_string(BOHIP_MOM_FRONT_MAX));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t m = 0; m < M; ++m) {
+            if (!std::isfinite(front[m * n + i])) return fail(BOHIP_E_ARG, pre + "front point " + std::to_string(i) + " is not finite");
+            if (!(front[m * n + i] > ref[m])) return fail(BOHIP_E_ARG, pre + "front point " + std::to_string(i) + " is not strictly above ref");
+        }
+    mom_index(front, n, n, M, ref, f);
+    if ((int64_t)mom_filter(f->pts, (int)M).size() != n)
+        return fail(BOHIP_E_ARG, pre + "the front holds a weakly dominated or a duplicated point");
+    MomPt lo{}, hi{};
+    mom_decomp(f, f->pts, (int)M, &lo, &hi, keep);
+    return 0;
+}
+
+int bohip_mom_boxes(const double* front, int64_t M, int64_t n_front, const double* ref, double* levels, int64_t* n_levels, int32_t* boxes,
+                    int64_t cap, int64_t* n_boxes) {
+    if (cap < 0 || (cap > 0 && !boxes)) return fail(BOHIP_E_ARG, "mom_boxes: bad arguments");
+    MomFront f;
+    CHK(mom_make_front("mom_boxes", M, front, n_front, ref, cap, &f));
+    if (n_boxes) *n_boxes = f.n_boxes;
+    for (int64_t m = 0; m < M; ++m) {
+        if (n_levels) n_levels[m] = (int64_t)f.levels[m].size();
+        if (levels) std::copy(f.levels[m].begin(), f.levels[m].end(), levels + m * (n_front + 2));
+    }
+    if (f.n_boxes > BOHIP_MOM_BOX_MAX)
+        return fail(BOHIP_E_UNSUPPORTED, "mom_boxes: " + std::to_string(f.n_boxes) + " boxes; at most " + std::to_string(BOHIP_MOM_BOX_MAX));
+    if (cap == 0) return 0;
+    if (cap < f.n_boxes) return fail(BOHIP_E_ARG, "mom_boxes: " + std::to_string(f.n_boxes) + " boxes, cap is " + std::to_string(cap));
+    for (int64_t m = 0; m < M; ++m) {
+        std::copy(f.lo[m].begin(), f.lo[m].end(), boxes + m * cap);
+        std::copy(f.hi[m].begin(), f.hi[m].end(), boxes + (M + m) * cap);
+    }
+    return 0;
+}
+
+// what k_ehvi_boxes reads, built on the host: the level rows and the packed boxes
+struct MomPlan {
+    int M = 0, nbox = 0;
+    MomLevels nl{};
+    std::vector<double> key;         // what the plan was made from: M, n, ref, then the front
+    std::vector<double> levels;      // [M][MOM_LEVELS]
+    std::vector<unsigned> boxes;     // [M][nbox]: lo | hi << 16
+};
+// the plan of (front, ref): the one resident on g (bit-equal arguments in the same order; *resident says so) or a new one
+static int mom_make_plan(bohip_gp* g, const char* who, int64_t M, const double* front, int64_t n, const double* ref,
+                         std::shared_ptr<MomPlan>* out, bool* resident) {
+    const std::string pre = std::string(who) + ": ";
+    CHK(mom_check_common(pre, M, ref));
+    if (n < 0 || (n > 0 && !front)) return fail(BOHIP_E_ARG, pre + "bad front arguments");
+    if (n > BOHIP_MOM_FRONT_MAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "a front of " + std::to_string(n) + " points; at most " + std::to_string(BOHIP_MOM_FRONT_MAX));
+    std::vector<double> key{(double)M, (double)n};
+    key.insert(key.end(), ref, ref + M);
+    key.insert(key.end(), front, front + M * n);
+    *resident = g->mom_plan && g->mom_plan->key.size() == key.size() && std::memcmp(g->mom_plan->key.data(), key.data(), key.size() * 8) == 0;
+    if (*resident) {
+        *out = g->mom_plan;
+        return 0;
+    }
+    MomFront f;
+    CHK(mom_make_front(who, M, front, n, ref, BOHIP_MOM_BOX_MAX, &f));
+    if (f.n_boxes > BOHIP_MOM_BOX_MAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + std::to_string(f.n_boxes) + " boxes; at most " + std::to_string(BOHIP_MOM_BOX_MAX));
+    auto p = std::make_shared<MomPlan>();
+    p->M = (int)M;
+    p->nbox = (int)f.n_boxes;
+    p->key = std::move(key);
+    p->levels.assign((size_t)(M * MOM_LEVELS), INFINITY);
+    p->boxes.resize((size_t)(M * f.n_boxes));
+    for (int64_t m = 0; m < M; ++m) {
+        p->nl.n[m] = (int)f.levels[m].size();
+        std::copy(f.levels[m].begin(), f.levels[m].end(), p->levels.begin() + m * MOM_LEVELS);
+        for (int64_t b = 0; b < f.n_boxes; ++b)
+            p->boxes[(size_t)(m * f.n_boxes + b)] = (unsigned)f.lo[m][(size_t)b] | ((unsigned)f.hi[m][(size_t)b] << 16);
+    }
+    *out = std::move(p);
+    return 0;
+}
+// on g's stream; the handle keeps the plan (and with it the host copies the transfers read) once both are queued
+static int mom_upload_plan(bohip_gp* g, const std::shared_ptr<MomPlan>& p, bool resident) {
+    if (resident) return 0;
+    g->mom_plan.reset();
+    HIPCHK(g->mom_levels.reserve((size_t)(BOHIP_MOM_OBJ_MAX * MOM_LEVELS), g->stream));
+    HIPCHK(g->mom_boxes.reserve(p->boxes.size(), g->stream, Grow::Half));
+    HIPCHK(hipMemcpyAsync(g->mom_levels, p->levels.data(), p->levels.size() * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->mom_boxes, p->boxes.data(), p->boxes.size() * 4, hipMemcpyHostToDevice, g->stream));
+    g->mom_plan = p;
+    return 0;
+}
+// the EHVI and the record on g's stream (no synchronisation, no copies); b is ensure_con's block with C = M - 1
+static int mom_ehvi_stage(bohip_gp* g, const MomPlan& p, const ConBufs& b, int64_t R, bool partials, bool jac, bool want_best) {
+    const StageOuts o = stage_outs(g, b, R, partials, jac, want_best);
+    const int W = mom_cand(o.grad_form);
+    const int nb = (int)std::min<int64_t>(MO_GRID_MAX, (R + W - 1) / W);
+    t_begin(g, "mom_ehvi");
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(64 * W), 0, g->stream, (const double*)g->mom_levels, p.nl, (const unsigned*)g->mom_boxes, p.nbox,
+                           (const double*)b.mu, (const double*)b.var, R, R, b.value, o.pmu, o.pvar, o.jmu, o.jvar, o.jplane, g->d, o.grad, o.blocks);
+    };
+    if (o.grad_form) {
+        if (p.M == 2) launch(k_ehvi_boxes<2, true>);
+        else if (p.M == 3) launch(k_ehvi_boxes<3, true>);
+        else launch(k_ehvi_boxes<4, true>);
+    } else {
+        if (p.M == 2) launch(k_ehvi_boxes<2, false>);
+        else if (p.M == 3) launch(k_ehvi_boxes<3, false>);
+        else launch(k_ehvi_boxes<4, false>);
+    }
+    return stage_end(g, b, nb, want_best);
+}
+
+int bohip_mom_ehvi_values(bohip_gp* g, int64_t M, const double* front, int64_t n_front, const double* ref, const double* mu,
+                          const double* var, int64_t R, double* value, double* dmu, double* dvar, bohip_best* best) {
+    if (!g) return fail(BOHIP_E_ARG, "mom_ehvi_values: null handle");
+    if (R < 0 || (R > 0 && (!mu || !var || !value))) return fail(BOHIP_E_ARG, "mom_ehvi_values: bad arguments");
+    if ((dmu == nullptr) != (dvar == nullptr)) return fail(BOHIP_E_ARG, "mom_ehvi_values: dmu and dvar are given together or not at all");
+    std::shared_ptr<MomPlan> p;
+    bool resident = false;
+    CHK(mom_make_plan(g, "mom_ehvi_values", M, front, n_front, ref, &p, &resident));
+    auto stage = [&](const ConBufs& b) -> int {
+        CHK(mom_upload_plan(g, p, resident));
+        return mom_ehvi_stage(g, *p, b, R, dmu != nullptr, false, best != nullptr);
+    };
+    return moments_to_values(g, M, mu, var, R, stage, value, nullptr, dmu, dvar, best);
+}
+
+int bohip_gp_score_mom(bohip_gp* const* objs, int64_t M, const double* front, int64_t n_front, const double* ref, const double* Xs,
+                       int64_t R, double* score, double* grad, double* mu, double* var, bohip_best* best) {
+    if (M < 2 || M > BOHIP_MOM_OBJ_MAX)
+        return fail(BOHIP_E_ARG, "score_mom: M must be in [2, " + std::to_string(BOHIP_MOM_OBJ_MAX) + "], got " + std::to_string(M));
+    if (!objs) return fail(BOHIP_E_ARG, "score_mom: objs is null");
+    for (int64_t m = 0; m < M; ++m) {
+        if (!objs[m]) return fail(BOHIP_E_ARG, "score_mom: handle " + std::to_string(m) + " is null");
+        if (objs[m]->d != objs[0]->d) return fail(BOHIP_E_ARG, "score_mom: objective " + std::to_string(m) + " has another dimension");
+        if (objs[m]->device != objs[0]->device) return fail(BOHIP_E_ARG, "score_mom: objective " + std::to_string(m) + " lives on another device");
+    }
+    if (R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_mom: bad arguments");
+    std::shared_ptr<MomPlan> p;
+    bool resident = false;
+    CHK(mom_make_plan(objs[0], "score_mom", M, front, n_front, ref, &p, &resident));
+    for (int64_t m = 0; m < M; ++m)
+        if (objs[m]->n == 0) return fail(BOHIP_E_STATE, "score_mom: objective " + std::to_string(m) + " has no observations");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    bohip_gp* const owner = objs[0];
+    HIPCHK(hipSetDevice(owner->device));
+    const bool jac = grad != nullptr;
+    ConBufs b{};
+    CHK(ensure_con(owner, M - 1, R, jac, &b));
+    CHK(mom_upload_plan(owner, p, resident));   // (on the owner's stream, ahead of its posterior)
+    CHK(multi_posterior(owner, objs, M, false, Xs, R, jac, b));
+    CHK(mom_ehvi_stage(owner, *p, b, R, false, jac, best != nullptr));
+    return multi_download(owner, objs, M, b, R, score, grad, mu, var, best);
 }
 
 // ---- posterior sample paths (kernels_path.hip): pathwise conditioning with a random-feature prior ----------------

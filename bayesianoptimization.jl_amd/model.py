@@ -1483,6 +1483,159 @@ class MultiObjectiveGPE:
             m.close()
 
 
+# ---- two to four objectives (include/bohip_mom.h) ----------------------------------------------------------------
+def _rows(a, what):
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or not 2 <= a.shape[0] <= _lib.MOM_OBJ_MAX:
+        raise ValueError(f"{what} has one row per objective, M x n with M in 2..{_lib.MOM_OBJ_MAX}; got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _refm(ref, M):
+    ref = np.ascontiguousarray(np.asarray(ref, dtype=np.float64).ravel())
+    if ref.size != M:
+        raise ValueError(f"the reference point has one coordinate per objective, {M}; got {ref.size}")
+    return ref
+
+
+def mom_front(Y, ref):
+    """bohip_mom_front (host code: no device is needed): the observations Y [M, n] (every objective MAXIMISED, M = 2..4) strictly
+    above `ref` in every coordinate and not weakly dominated by another observation, in lexicographic ascending order, of equal points
+    one.  -> (front[M, n_front], hv), hv the hypervolume the front dominates above ref."""
+    Y = _rows(Y, "Y")
+    M, n = Y.shape
+    ref = _refm(ref, M)
+    out = np.empty((M, max(n, 1)))
+    nf, hv = C.c_int64(0), C.c_double(0.0)
+    check(_lib.load().bohip_mom_front(_ptr(Y), M, n, _ptr(ref), _ptr(out), out.shape[1], C.byref(nf), C.byref(hv)))
+    return np.ascontiguousarray(out[:, :nf.value]), hv.value
+
+
+def mom_boxes(front, ref):
+    """bohip_mom_boxes (host code): the decomposition of the region above `ref` that no point of `front` [M, n_front] dominates.
+    -> (levels, boxes): levels a list of M arrays (ref_m, the front's distinct values ascending, +Inf); boxes Int32 [2M, n_boxes], row
+    m the lower and row M + m the upper level index of every box in objective m."""
+    front = _rows(front, "front")
+    M, n = front.shape
+    ref = _refm(ref, M)
+    lib = _lib.load()
+    levels, nl, nb = np.empty((M, n + 2)), np.zeros(M, dtype=np.int64), C.c_int64(0)
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))   # noqa: E731
+    check(lib.bohip_mom_boxes(_ptr(front), M, n, _ptr(ref), _ptr(levels), i64(nl), None, 0, C.byref(nb)))
+    boxes = np.empty((2 * M, nb.value), dtype=np.int32)
+    check(lib.bohip_mom_boxes(_ptr(front), M, n, _ptr(ref), None, None, boxes.ctypes.data_as(C.POINTER(C.c_int32)), nb.value, None))
+    return [levels[m, :nl[m]].copy() for m in range(M)], boxes
+
+
+def ehvi_values_many(model, front, ref, mu, var, want_grad=False):
+    """bohip_mom_ehvi_values: the exact expected hypervolume improvement over `front` [M, n_front] above `ref` on the moments mu, var
+    [M, R] of M independent posteriors, as a sum over the front's boxes.  `model` gives the device only.
+    -> (value[R], dmu, dvar, best_value, best_index); dmu and dvar [M, R] are the partials in the moments, None without want_grad."""
+    mu, var = _rows(np.atleast_2d(mu), "mu"), _rows(np.atleast_2d(var), "var")
+    if mu.shape != var.shape:
+        raise ValueError(f"mu and var must both be M x R, got {mu.shape} and {var.shape}")
+    M, R = mu.shape
+    front = np.ascontiguousarray(np.asarray(front, dtype=np.float64).reshape(M, -1))
+    ref = _refm(ref, M)
+    value = np.empty(max(R, 1))
+    dmu, dvar = (np.empty((M, max(R, 1))), np.empty((M, max(R, 1)))) if want_grad else (None, None)
+    best = Best()
+    check(model._lib.bohip_mom_ehvi_values(model._h, M, _ptr(front), front.shape[1], _ptr(ref), _ptr(mu), _ptr(var), R, _ptr(value),
+                                           _ptr(dmu) if want_grad else None, _ptr(dvar) if want_grad else None, C.byref(best)))
+    return (value[:R], (np.ascontiguousarray(dmu[:, :R]) if want_grad else None), (np.ascontiguousarray(dvar[:, :R]) if want_grad else None),
+            best.val, best.idx)
+
+
+def score_mom(models, front, ref, xs, want_grad=False, want_moments=True):
+    """ONE bohip_gp_score_mom call on 2 to 4 ElasticGPE models (a model may repeat, and they may hold different observations): the
+    exact EHVI of their posteriors at the columns of xs [d, R] over `front` [M, n_front] above `ref`.  -> MOScore, mu and var [M, R]."""
+    models = list(models)
+    M = len(models)
+    if not 2 <= M <= _lib.MOM_OBJ_MAX:
+        raise ValueError(f"score_mom takes 2 to {_lib.MOM_OBJ_MAX} models, got {M}")
+    front = np.ascontiguousarray(np.asarray(front, dtype=np.float64).reshape(M, -1))
+    ref = _refm(ref, M)
+    m0 = models[0]
+    xs = _cols(xs, m0.dim)
+    R = xs.shape[1]
+    n = max(R, 1)
+    scores = np.empty(n)
+    grad = np.empty((m0.dim, n), order="F") if want_grad else None
+    mu, var = (np.empty((M, n)), np.empty((M, n))) if want_moments and R > 0 else (None, None)
+    handles = (C.c_void_p * M)(*[m._h for m in models])
+    best = Best()
+    check(m0._lib.bohip_gp_score_mom(handles, M, _ptr(front), front.shape[1], _ptr(ref), _ptr(xs), R, _ptr(scores),
+                                     _ptr(grad) if want_grad else None, _ptr(mu) if mu is not None else None,
+                                     _ptr(var) if var is not None else None, C.byref(best)))
+    return MOScore(scores[:R], grad[:, :R] if want_grad else None, mu, var, best.val, best.idx)
+
+
+class ManyObjectiveGPE(MultiObjectiveGPE):
+    """Two to four objective models scored together by the exact expected hypervolume improvement as a sum over the boxes of the
+    observed front (include/bohip_mom.h; an extension).  Every objective is MAXIMISED (BOpt's `sense` flips all).  What
+    MultiObjectiveGPE says of its members, of `ref` (None: fixed once, at the first score, by the same rule per objective) and of
+    `x`, `nobs` holds here; `y` is [M, n], `front` [M, n_front] in lexicographic ascending order.  A subclass, so that whatever
+    accepts a MultiObjectiveGPE (acquire_max, BOpt) accepts this model."""
+
+    def __init__(self, objectives, ref=None):
+        objectives = tuple(objectives)
+        M = len(objectives)
+        if not 2 <= M <= _lib.MOM_OBJ_MAX:
+            raise ValueError(f"ManyObjectiveGPE takes 2 to {_lib.MOM_OBJ_MAX} objectives, got {M}")
+        for m in objectives:
+            if type(m).__name__ == "MultiGPE":
+                raise ValueError("ManyObjectiveGPE members are single-device models: MultiGPE is not supported")
+        if any(m.dim != objectives[0].dim for m in objectives):
+            raise ValueError("the members differ in dimension")
+        for m in objectives:
+            _refuse_site_member(m, "ManyObjectiveGPE")
+        self.objectives = objectives
+        self.ref = None if ref is None else _refm(ref, M).copy()
+        if self.ref is not None and not np.all(np.isfinite(self.ref)):
+            raise ValueError("the reference point must be finite")
+
+    n_objectives = property(lambda self: len(self.objectives))
+
+    def __repr__(self):
+        return f"ManyObjectiveGPE({', '.join(repr(m) for m in self.objectives)}, ref={self.ref})"
+
+    @property
+    def y(self):
+        """The observations [M, n]; the members' observations must be aligned (update_ keeps them so)."""
+        if len({m.nobs for m in self.objectives}) != 1:
+            raise ValueError("the members' observations are not aligned: a front needs every value of every observation")
+        return np.stack([np.asarray(m.y, dtype=np.float64) for m in self.objectives])
+
+    def _front_hv(self):
+        return mom_front(self.y, self.reference_point())
+
+    def front_indices(self):
+        """The column of the first observation that equals each front point."""
+        Y, F = self.y, self.front
+        return np.array([int(np.flatnonzero(np.all(Y == F[:, i:i + 1], axis=0))[0]) for i in range(F.shape[1])], dtype=np.int64)
+
+    def update_(self, x, y):
+        """Append observations to every member: x [d, n], y [M, n] (or [M] for one point)."""
+        y = np.asarray(y, dtype=np.float64)
+        M = len(self.objectives)
+        if y.ndim == 0 or y.shape[0] != M:
+            raise ValueError(f"y has one row per objective, {M} x n; got shape {y.shape}")
+        y = y.reshape(M, -1)
+        for m, row in zip(self.objectives, y):
+            m.append_(x, row)
+        return self
+
+    append_ = update_
+    append = update_
+
+    def score(self, xs, want_grad=False, want_moments=True):
+        """ONE bohip_gp_score_mom call: every member's posterior on its own stream, the EHVI over the boxes of the observed front and
+        the arg-max on the device.  xs is d x R.  -> MOScore, mu and var [M, R]."""
+        ref = self.reference_point(fix=True)
+        front, _ = mom_front(self.y, ref)
+        return score_mom(self.objectives, front, ref, xs, want_grad, want_moments)
+
+
 class PosteriorPaths:
     """S sample paths of one model's posterior on the device (bohip_paths, include/bohip_paths.h).  Self-contained: it holds its own copy
     of the observations, hyper-parameters, frequencies and coefficients.

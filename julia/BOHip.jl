@@ -354,6 +354,7 @@ include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ense
 include("BOHipMES.jl")     # max-value entropy search over a candidate set (include/bohip_mes.h): mes, mes_values, mes_gumbel, MaxValueEntropySearch
 include("BOHipCon.jl")     # constrained optimisation (include/bohip_con.h): predict_grad, con_values, score_constrained
 include("BOHipMO.jl")      # two objectives (include/bohip_mo.h): mo_front, ehvi_values, score_mo
+include("BOHipMOM.jl")     # two to four objectives (include/bohip_mom.h): mom_front, mom_boxes, ehvi_values_many, score_mom
 include("BOHipLOO.jl")     # leave-one-out cross-validation (include/bohip_loo.h): loo, loo_grad
 include("BOHipLOOBatch.jl") # its objective at H settings in one launch (include/bohip_loo_batch.h): loo_grad_batch
 include("BOHipRep.jl")      # replicated sites (include/bohip_rep.h): append_sites!, collapse_evaluations, sites_info, site_reps
