@@ -1,4 +1,4 @@
-"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_mom.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h, include/bohip_nei.h).  No CPU fallback: importing works without a
+"""ctypes binding of libbohip.so (include/bohip.h, include/bohip_paths.h, include/bohip_fit.h, include/bohip_qei.h, include/bohip_acq.h, include/bohip_kg.h, include/bohip_ens.h, include/bohip_ens_grad.h, include/bohip_mes.h, include/bohip_con.h, include/bohip_mo.h, include/bohip_mom.h, include/bohip_loo.h, include/bohip_loo_batch.h, include/bohip_rep.h, include/bohip_pend.h, include/bohip_nei.h, include/bohip_nei_grad.h).  No CPU fallback: importing works without a
 GPU (so the ABI can be inspected), but every compute entry point raises when the library or the
 device is missing."""
 from __future__ import annotations
@@ -248,6 +248,12 @@ NEI_SIGNATURES = {
     "bohip_gp_nei_release": (C.c_int, [_gp]),
 }
 
+# the symbol include/bohip_nei_grad.h declares (the gradient of noisy expected improvement in the candidate)
+NEI_GRAD_SIGNATURES = {
+    "bohip_gp_score_nei_grad": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, _dp, _dp, _dp, _dp,
+                                          C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -307,7 +313,7 @@ def load():
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
-                              + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items())):
+                              + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -152,9 +152,10 @@ class NoisyExpectedImprovement(AbstractAcquisition):
     log=True LogEI's log of the averaged EI -- averaged over S posterior draws of the NOISE-FREE function values at the observed
     sites.  Every draw brings its own incumbent, so the largest raw observation (the luckiest noise draw) plays no part.  S = 0:
     the plug-in form, whose incumbent is the largest posterior mean at the sites.  An extension: the reference has no such type,
-    and no default uses it.  It has no parameter that follows the model (setparams_ does nothing) and no gradient in x:
-    acquisitionfunction takes a point or a d x R matrix, acquire_max takes the device's arg-max over `maxeval` Latin-hypercube
-    candidates per restart.  `seed` fixes the draws, so the acquisition is one deterministic function of x during a search."""
+    and no default uses it.  It has no parameter that follows the model (setparams_ does nothing).  acquisitionfunction takes a
+    point or a d x R matrix, acquire_max takes the device's arg-max over `maxeval` Latin-hypercube candidates per restart and, with
+    the option "refine": n > 0, climbs the n best on the gradient (model.nei_grad, include/bohip_nei_grad.h).  `seed`
+    fixes the draws, so the acquisition is one deterministic function of x during a search."""
     acq_id = "NEI"
 
     def __init__(self, S=32, seed=0, log=False, jitter_rel=1e-8):
@@ -164,7 +165,12 @@ class NoisyExpectedImprovement(AbstractAcquisition):
             raise ValueError(f"jitter_rel must be positive and finite, got {jitter_rel!r}")
         self.S, self.seed, self.log, self.jitter_rel = int(S), int(seed), bool(log), float(jitter_rel)
 
-    def score(self, model, xs, want_scores=True):
+    def score(self, model, xs, want_scores=True, want_grad=False):
+        """model.nei's NEIScore at the columns of xs; with want_grad (NEIScore, grad [d, R]) from model.nei_grad."""
+        if want_grad:
+            if not hasattr(model, "nei_grad"):
+                raise NotImplementedError(f"{type(model).__name__} has no nei_grad")
+            return model.nei_grad(xs, S=self.S, seed=self.seed, acq="logei" if self.log else "ei", jitter_rel=self.jitter_rel)
         if not hasattr(model, "nei"):
             raise NotImplementedError(f"{type(model).__name__} has no nei")
         return model.nei(xs, S=self.S, seed=self.seed, acq="logei" if self.log else "ei", jitter_rel=self.jitter_rel,
@@ -730,19 +736,27 @@ def _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng):
     return maxf, maxx
 
 
-def _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng):
-    """NoisyExpectedImprovement: no gradient in x.  Every restart scores `maxeval` Latin-hypercube candidates in ONE model.nei call
-    and takes the device's arg-max; the fantasies are built once (the seed is the acquisition's).  The first maximum over the
-    restarts wins (strict '>')."""
-    maxf, maxx = -math.inf, lb.copy()
-    for _ in range(restarts):
-        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
-        val, idx = a.score(model, xs, want_scores=False).best
-        if idx >= 0 and val > maxf:                               # :62 strict '>'
-            maxf, maxx = float(val), xs[:, int(idx)].copy()
-    if not np.isfinite(maxf):
-        warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
-    return maxf, maxx
+class _NEIResult:
+    """A NEIScore (and its gradient) under the names _acquire_max_candidates reads."""
+    __slots__ = ("scores", "grad", "best_val", "best_idx")
+
+    def __init__(self, res, grad=None):
+        self.scores, self.grad, (self.best_val, self.best_idx) = res.score, grad, res.best
+
+
+def _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng, opts=None):
+    """NoisyExpectedImprovement.  Every restart scores `maxeval` Latin-hypercube candidates in ONE model.nei call and takes the
+    device's arg-max; the fantasies are built once (the seed is the acquisition's).  The first maximum over the restarts wins
+    (strict '>').  "refine": n > 0 (default 0: the candidate stage alone, the record-only calls and the draws it has always
+    issued): _acquire_max_candidates' second stage, fg = one model.nei_grad call per step of the ascent."""
+    refine = int((opts or {}).get("refine", 0) or 0)
+
+    def score(xs, want_grad=False):
+        if want_grad:
+            return _NEIResult(*a.score(model, xs, want_grad=True))
+        return _NEIResult(a.score(model, xs, want_scores=refine > 0))
+
+    return _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, opts)
 
 
 def _acquire_max_marginal(a, model, lb, ub, restarts, maxeval, rng, opts=None):
@@ -879,8 +893,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
         return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, MaxValueEntropySearch):                      # (`method` is accepted, not used)
         return _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng)
-    if isinstance(a, NoisyExpectedImprovement):                   # (`method` is accepted, not used)
-        return _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, NoisyExpectedImprovement):                   # (`method` is accepted, not used; "refine" adds the ascent)
+        return _acquire_max_nei(a, model, lb, ub, restarts, maxeval, rng, opts)
     if isinstance(a, Constrained):                                # (`method` is accepted, not used; "refine" adds the ascent)
         if not hasattr(model, "feasible_incumbent"):
             raise ValueError(f"Constrained needs a ConstrainedGPE, not {type(model).__name__}")

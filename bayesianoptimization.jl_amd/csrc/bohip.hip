@@ -33,6 +33,7 @@
 #include "../../include/bohip_rep.h"
 #include "../../include/bohip_pend.h"
 #include "../../include/bohip_nei.h"
+#include "../../include/bohip_nei_grad.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -51,6 +52,7 @@
 #include "kernels_ascent.hip"
 #include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
 #include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
+#include "kernels_nei_grad.hip"   // (after kernels_nei.hip and kernels_con.hip: NeiReduce; grad_finish_waves, GC)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -312,6 +314,7 @@ struct bohip_gp : gp_streams {
         }
     } nei_key;
     DBuf<char> nei_ws, nei_call;
+    bool nei_at = false;   // alpha' of the gradient route (layout::nei_alpha_t) matches the fantasies
     // one-process-per-device exchange (multigpu.hip): communicator attached by bohip_gp_comm_init
     void* comm = nullptr;
     int comm_rank = 0, comm_n = 0;
@@ -5715,6 +5718,7 @@ static int ensure_nei_fantasies(bohip_gp* g, int64_t S, uint64_t seed, layout::N
         return 0;
     }
     g->nei_key = bohip_gp::NeiKey{};
+    g->nei_at = false;   // (the work matrices are written again)
     const int64_t ld = g->ld;
     const size_t bytes = layout::nei_state(nullptr, (size_t)rows, (size_t)ld, (size_t)S1, st);
     HIPCHK(g->nei_ws.reserve(bytes + 128, g->stream));
@@ -5730,6 +5734,8 @@ static int ensure_nei_fantasies(bohip_gp* g, int64_t S, uint64_t seed, layout::N
     const double* invr = g->weighted ? g->dinvr.get() : nullptr;
     const int zero = S == 0 ? 1 : 0;
     double *Z = st->w0, *G = st->w1, *RH = st->w2, *T = st->w3, *Q = st->w0, *P = st->w1, *T2 = st->w3;
+    // (once the fantasies stand w0 belongs to the gradient route: alpha' lives there, layout::nei_alpha_t, valid while g->nei_at; a
+    // later stage that wants a work matrix takes w1 .. w3 or clears nei_at)
     if (S > 0) {
         hipLaunchKernelGGL(k_nei_normals, grid_n, dim3(256), 0, g->stream, Z, ld, N, (int)S, (unsigned long long)seed);
         CHK(nei_product(g, Z, c->dL, c->ld, true, G, rows, ld, Npad));                          // g_s = L_d z_s
@@ -5877,6 +5883,133 @@ int bohip_gp_score_nei(bohip_gp* g, int acq_id, const double* acq_params, const 
     if (mu) HIPCHK(hipMemcpyAsync(mu, w.mu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (var) HIPCHK(hipMemcpyAsync(var, c->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    nei_merge_timing(g);
+    return 0;
+}
+
+// ---- its gradient (include/bohip_nei_grad.h; kernels_nei_grad.hip) ----------------------------------------------------
+// k_nei_grad_finish (kernels_nei_grad.hip): launch_post_grad with one stream
+extern "C++" {
+template <int DT>
+static void launch_nei_grad_finish(bohip_gp* c, int64_t r0, int64_t r1, const KernelHyper& hp, const double* E, double* d_grad, int S) {
+    if constexpr (DT <= 16) {   // large batches: GC candidates per workgroup share the observation stream (launch_grad's rule)
+        if (r1 - r0 > SMALL_MAX) {
+            LAUNCH_FAM(fam_low(hp), (k_nei_grad_finish_tiled<DT, true>), (k_nei_grad_finish_tiled<DT, false>),
+                       dim3((unsigned)((r1 - r0 + GC - 1) / GC)), dim3(256), 0, c->stream, c->dX, c->n, c->dXs, r0, r1, hp, E, c->ld, d_grad);
+            return;
+        }
+    }
+    LAUNCH_FAM(fam_low(hp), (k_nei_grad_finish<DT, true>), (k_nei_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
+               c->stream, c->dX, c->n, c->dXs, r0, r1, hp, E, c->ld, d_grad, c->dgparts, c->dgcount);
+}
+}  // extern "C++"
+
+int bohip_gp_score_nei_grad(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
+                            double jitter_rel, double* score, double* grad, double* mu, double* var, bohip_best* best) {
+    (void)acq_params;   // (tau is the fantasy's own)
+    if (!g || R < 0 || (R > 0 && (!Xs || !grad))) return fail(BOHIP_E_ARG, "score_nei_grad: bad arguments");
+    if (!grad) return fail(BOHIP_E_ARG, "score_nei_grad: grad is required");
+    CHK(nei_check("score_nei_grad", acq_id, S, jitter_rel, true));
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    if (R == 0) {
+        if (best) { best->val = -INFINITY; best->idx = -1; }
+        return 0;
+    }
+    layout::NeiState st;
+    CHK(nei_ready(g, jitter_rel, S, seed, &st));
+    bohip_gp* c = g->nei;
+    CHK(ensure_xs(c, R));
+    CHK(ensure_score_scratch(c, R));
+    CHK(one_time_kernel_setup());
+    CHK(nei_kernel_setup());
+    {
+        static bool done[64] = {false};
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        CHK(once_per_device(done, dev, [] {
+            HIPCHK(hipFuncSetAttribute((const void*)k_nei_mix, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+            return 0;
+        }));
+    }
+    // The companion's pass on the route that stores V' and leaves U' in dUT.  The small pass forms its gradient in-kernel from ONE alpha
+    // and keeps neither K*' nor U' in memory: it is switched off, as for the posterior's Jacobians.
+    const PassPlan pl = choose_route(c, R, RouteWants{false, true, Prune::No});
+    const int64_t S1 = std::max<int64_t>(S, 1), Sp = round_up(S1, CTILE), Sk = round_up(S1, KC), srows = round_up(S1, TILE);
+    const int64_t crows = round_up(pl.route == Route::WholeK ? std::min(R, pl.chunk) : R, TILE);
+    const int kc_all = (int)(pl.dm.Npad / KC), kz = std::max(8, (kc_all + 7) / 8), nsl = (kc_all + kz - 1) / kz;   // (bohip_gp_score_nei's slices)
+    const int64_t mrows = std::min(crows, std::max<int64_t>(TILE, ((int64_t)256 << 20) / (8 * nsl * Sp) / TILE * TILE));
+    const int64_t plane = Sp * mrows;
+    layout::NeiGradCall<Best> w;
+    auto lay = [&](const void* base) {
+        return layout::nei_grad_call(base, (size_t)(nsl * plane), (size_t)R, (size_t)mrows, (size_t)Sk, (size_t)g->d, (size_t)nei_blocks(R), &w);
+    };
+    HIPCHK(g->nei_call.reserve(lay(nullptr) + 128, g->stream));
+    lay(reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(g->nei_call.get()) + 127) / 128 * 128));
+    // alpha' for the B operand of k_nei_mix: once per fantasy rebuild, in a work matrix the rebuild left dead
+    double* AT = layout::nei_alpha_t(st, (size_t)srows, (size_t)g->nei_ld, (size_t)pl.dm.Npad, (size_t)Sk);
+    if (!AT) return fail(BOHIP_E_UNSUPPORTED, "score_nei_grad: the fantasies' work matrix does not hold alpha'");
+    if (!g->nei_at) {
+        t_begin(g, "nei_transpose");
+        hipLaunchKernelGGL(k_nei_transpose, dim3((unsigned)((pl.dm.Npad + NEI_TR - 1) / NEI_TR), (unsigned)((Sk + NEI_TR - 1) / NEI_TR)), dim3(256),
+                           0, g->stream, st.alpha, g->nei_ld, pl.dm.Npad, (int)Sk, AT);
+        HIPCHK(hipGetLastError());
+        t_end(g);
+        g->nei_at = true;
+    }
+    HIPCHK(hipMemcpyAsync(c->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const KernelHyper hp = make_hyper(c);
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    // per chunk (K*' in dKsT: the V-stored pass reads it and leaves it; U' in dUT, rows 0 .. r1 - r0): mu and s^2, the means of every
+    // fantasy, the weights, E over U' in place, the contraction with dk/dx
+    auto finish = [&](int64_t r0, int64_t r1) {
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, c->dq.get() + r0, pl.dm.Rpad, pl.dq_tiles(),
+                           c->dmu_raw.get() + r0, r1 - r0, hp.sigma2, c->beta, mm, c->dmu.get() + r0, c->dvar.get() + r0, (double*)nullptr,
+                           (Best*)nullptr);
+        HIPCHK(hipGetLastError());
+        for (int64_t b0 = r0; b0 < r1; b0 += mrows) {
+            const int64_t b1 = std::min(r1, b0 + mrows);
+            const int mt = (int)((b1 - b0 + TILE - 1) / TILE);
+            NeiMeans nm{};
+            nm.A = c->dKsT + (b0 - r0) * c->ld; nm.lda = c->ld; nm.B = st.alpha; nm.ldb = g->nei_ld; nm.MT = w.v.MT; nm.ldm = mrows; nm.plane = plane;
+            nm.mt = mt; nm.nt = (int)(Sp / CTILE); nm.kc = kc_all; nm.kz = kz; nm.beta = g->beta;
+            t_begin(c, "nei_means");
+            hipLaunchKernelGGL(k_nei_means, dim3((unsigned)(nm.mt * nm.nt), (unsigned)nsl), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, nm);
+            HIPCHK(hipGetLastError());
+            t_end(c);
+            NeiWeights nw{};
+            nw.r.MT = w.v.MT; nw.r.var = c->dvar; nw.r.tau = st.tau; nw.r.ldm = mrows; nw.r.nsl = nsl; nw.r.plane = plane; nw.r.r0 = b0; nw.r.r1 = b1;
+            nw.r.S1 = (int)S1; nw.r.ap = AcqParams{acq_id, 0.0, 0.0};
+            nw.r.score_out = w.v.score; nw.r.mu_out = w.v.mu; nw.r.block_best = best ? w.v.blk : nullptr;
+            nw.omega = w.omega; nw.c = w.c; nw.ldo = Sk;
+            t_begin(c, "nei_weights");
+            hipLaunchKernelGGL(k_nei_weights, dim3((unsigned)mt), dim3(NEI_RED_THREADS), 0, g->stream, nw);
+            HIPCHK(hipGetLastError());
+            t_end(c);
+            NeiMix mx{};
+            mx.A = w.omega; mx.B = AT; mx.c = w.c; mx.E = c->dUT + (b0 - r0) * c->ld; mx.ld = Sk; mx.lde = c->ld; mx.N = c->n;
+            mx.mt = mt; mx.nt = (int)(pl.dm.Npad / CTILE); mx.kc = (int)(Sk / KC); mx.rows = (int)(b1 - b0);
+            t_begin(c, "nei_mix");
+            hipLaunchKernelGGL(k_nei_mix, dim3((unsigned)(mx.mt * mx.nt)), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, mx);
+            HIPCHK(hipGetLastError());
+            t_end(c);
+            int Sx = 1;
+            CHK(grad_obs_splits(c, b0, b1, &Sx));
+            t_begin(c, "nei_grad_finish");
+            dispatch_dt(g->d, [&](auto dt) { launch_nei_grad_finish<decltype(dt)::value>(c, b0, b1, hp, mx.E, w.grad, Sx); });
+            HIPCHK(hipGetLastError());
+            t_end(c);
+        }
+        return 0;
+    };
+    CHK(posterior_then(c, pl, c->dXs, hp, true, finish));
+    if (best) CHK(nei_record_stage(g, w.v, R));
+    if (score) HIPCHK(hipMemcpyAsync(score, w.v.score, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(grad, w.grad, (size_t)R * g->d * 8, hipMemcpyDeviceToHost, g->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, w.v.mu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, c->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.v.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     nei_merge_timing(g);

@@ -224,6 +224,27 @@ size_t nei_call(const void* base, size_t n_mt, size_t R, size_t n_io, size_t S, 
     w->best = w->blk + nb;
     return c.total();
 }
+// the gradient of noisy expected improvement, one call (bohip_gp_score_nei_grad): nei_call's members, then [omega = the chunk's weights,
+// candidate-major, 128-row tiles x Sp | c one a row | grad R x d]
+template <class Rec>
+struct NeiGradCall { NeiCall<Rec> v; double *omega, *c, *grad; };
+template <class Rec>
+size_t nei_grad_call(const void* base, size_t n_mt, size_t R, size_t rows, size_t Sp, size_t d, size_t nb, NeiGradCall<Rec>* w) {
+    Carve c(base);
+    w->v.MT = c.take<double>(n_mt, 128);
+    w->v.score = c.take<double>(R); w->v.mu = c.take<double>(R);
+    w->v.var = nullptr; w->v.tau = nullptr;
+    w->omega = c.take<double>(rows * Sp, 128); w->c = c.take<double>(rows);
+    w->grad = c.take<double>(R * d);
+    w->v.blk = c.take<Rec>(nb + 1, REC_ALIGN);
+    w->v.best = w->v.blk + nb;
+    return c.total();
+}
+// alpha' [Npad][Sp] of the gradient route lives in the first work matrix of nei_state, dead once the fantasies stand (Sp <= rows and
+// Npad <= ld: it always fits, and BOHIP_NEI_INFO_BYTES does not move); nullptr if it would not
+inline double* nei_alpha_t(const NeiState& st, size_t rows, size_t ld, size_t Npad, size_t Sp) {
+    return Npad * Sp <= rows * ld ? st.w0 : nullptr;
+}
 // the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
 // [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
 // Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the

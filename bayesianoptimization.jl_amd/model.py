@@ -509,6 +509,13 @@ class ElasticGPE:
         noise-free variance, best = (value, index), tau the S incumbents.  The model is not changed."""
         return _nei(self._lib, self._h, _cols(X, self.dim), S, seed, acq, jitter_rel, want_scores)
 
+    def nei_grad(self, X, S=32, seed=0, acq="ei", jitter_rel=1e-8):
+        """nei and its gradient in the candidates (bohip_gp_score_nei_grad, include/bohip_nei_grad.h): returns
+        (NEIScore, grad [d, R]).  With the seed fixed the score is one deterministic function of x, and grad is its derivative: what
+        an L-BFGS ascent climbs.  The score, mu and var agree with nei's to rounding (the variance pass runs the route that stores
+        V').  The model is not changed."""
+        return _nei_grad(self._lib, self._h, _cols(X, self.dim), S, seed, acq, jitter_rel)
+
     def nei_fantasies(self, S=32, seed=0, jitter_rel=1e-8):
         """(F [max(S, 1), n], tau [max(S, 1)]): the fantasised noise-free function values at the observed sites, row s = f_s, and
         their maxima (bohip_gp_nei_fantasies).  Brings the model, its noise-free companion and the fantasies up to date."""
@@ -811,6 +818,19 @@ def _nei(lib, h, xs, S, seed, acq, jitter_rel, want_scores=True):
     check(lib.bohip_gp_score_nei(h, _lib.ACQ[name], None, _ptr(xs), R, int(S), int(seed), float(jitter_rel),
                                  _ptr(sc) if want_scores else None, _ptr(mu), _ptr(var), C.byref(best)))
     return NEIScore(sc, mu, var, (best.val, best.idx), tau)
+
+
+def _nei_grad(lib, h, xs, S, seed, acq, jitter_rel):
+    d, R = xs.shape
+    name = _NEI_ACQ[str(acq).lower()]
+    sc, mu, var = np.empty(R), np.empty(R), np.empty(R)
+    grad = np.empty((d, R), order="F")
+    best = Best()
+    tau = np.empty(max(int(S), 1))
+    check(lib.bohip_gp_nei_fantasies(h, float(jitter_rel), int(S), int(seed), None, _ptr(tau)))   # (kept: the score call rebuilds nothing)
+    check(lib.bohip_gp_score_nei_grad(h, _lib.ACQ[name], None, _ptr(xs), R, int(S), int(seed), float(jitter_rel), _ptr(sc), _ptr(grad),
+                                      _ptr(mu), _ptr(var), C.byref(best)))
+    return NEIScore(sc, mu, var, (best.val, best.idx), tau), grad
 
 
 def _nei_fantasies(lib, h, n, S, seed, jitter_rel):

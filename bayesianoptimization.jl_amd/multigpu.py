@@ -197,6 +197,12 @@ class MultiGPE:
 
         return _nei(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(X, self.dim), S, seed, acq, jitter_rel, want_scores)
 
+    def nei_grad(self, X, S=32, seed=0, acq="ei", jitter_rel=1e-8):
+        """ElasticGPE.nei_grad (bohip_gp_score_nei_grad) on the FIRST replica, as nei."""
+        from .model import _nei_grad
+
+        return _nei_grad(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(X, self.dim), S, seed, acq, jitter_rel)
+
     def nei_fantasies(self, S=32, seed=0, jitter_rel=1e-8):
         """ElasticGPE.nei_fantasies (bohip_gp_nei_fantasies) on the FIRST replica."""
         from .model import _nei_fantasies
