@@ -254,6 +254,12 @@ NEI_GRAD_SIGNATURES = {
                                           C.POINTER(Best)]),
 }
 
+# the symbol include/bohip_pend_grad.h declares (the gradient of the acquisition under pending evaluations in the candidate)
+PEND_GRAD_SIGNATURES = {
+    "bohip_gp_score_pending_grad": (C.c_int, [_gp, C.c_int, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_int, _dp, _dp, _dp, _dp,
+                                              C.POINTER(Best)]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -313,7 +319,8 @@ def load():
                               + list(ENS_SIGNATURES.items()) + list(ENS_GRAD_SIGNATURES.items()) + list(MES_SIGNATURES.items())
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
-                              + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())):
+                              + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())
+                              + list(PEND_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

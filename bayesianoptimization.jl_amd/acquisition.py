@@ -999,14 +999,25 @@ _PENDING_REFUSED = (KnowledgeGradient, MaxValueEntropySearch, Marginalised, Cons
                     ThompsonSamplingSimple, NoisyExpectedImprovement)
 
 
+class _PendResult:
+    """A PendingScore and its gradient under the names _acquire_max_candidates reads."""
+    __slots__ = ("scores", "grad", "best_val", "best_idx")
+
+    def __init__(self, res, grad):
+        self.scores, self.grad, self.best_val, self.best_idx = res.scores, grad, res.best_val, res.best_idx
+
+
 def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, setparams=True):
     """acquire_max for a model with pending evaluations (model.set_pending; an extension): the acquisition is
     averaged over fantasised outcomes at the pending points (Snoek, Larochelle & Adams 2012, section 3.2), so the proposal keeps
     away from what is already out for evaluation.  With an empty pending set it returns acquire_max(...) itself.  Otherwise every
     restart scores `maxeval` Latin-hypercube candidates in ONE model.score_pending call and takes its arg-max record; the call's seed
-    is drawn from `rng` after the candidates; the first maximum over the restarts wins (strict '>').  There is no gradient in x, so
-    "method" and "refine" are accepted and not used.  Options: those of acquire_max plus "fantasies" (default 16; 0: the Kriging
-    believer) and "raise_tau" (default True: the incumbent of EI / PI / LogEI follows each fantasy)."""
+    is drawn from `rng` after the candidates; the first maximum over the restarts wins (strict '>').  "method" is accepted and not
+    used.  "refine": n > 0 (default 0: the candidate stage alone, the same calls and draws as without the option): one more seed is
+    drawn from `rng` after the last restart, and the n highest-scoring distinct candidates start ONE batched L-BFGS ascent inside the
+    box, fg = one model.score_pending_grad call per step under that seed (include/bohip_pend_grad.h); the best ascended
+    point replaces the candidate maximum only where its value is strictly higher.  Options: those of acquire_max plus "fantasies"
+    (default 16; 0: the Kriging believer) and "raise_tau" (default True: the incumbent of EI / PI / LogEI follows each fantasy)."""
     opts = dict(options if isinstance(options, dict) else vars(options))
     fantasies = int(opts.pop("fantasies", 16))
     raise_tau = bool(opts.pop("raise_tau", True))
@@ -1029,10 +1040,20 @@ def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, s
     gen = rng if rng is not None else np.random.default_rng()
     acq, p = a.acq_id, a.params()
 
-    def score(xs):
-        return model.score_pending(acq, p, xs, fantasies=fantasies, seed=int(gen.integers(0, 2 ** 63 - 1)), raise_tau=raise_tau)
+    refine = int(opts.get("refine", 0) or 0)
+    if refine > 0 and not hasattr(model, "score_pending_grad"):
+        raise NotImplementedError(f"{type(model).__name__} has no score_pending_grad")
+    climb_seed = []
 
-    return _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, {**opts, "refine": 0})
+    def score(xs, want_grad=False):
+        if not want_grad:
+            return model.score_pending(acq, p, xs, fantasies=fantasies, seed=int(gen.integers(0, 2 ** 63 - 1)), raise_tau=raise_tau)
+        if not climb_seed:                                        # (the first step of the ascent: after the last restart)
+            climb_seed.append(int(gen.integers(0, 2 ** 63 - 1)))
+        res, grad = model.score_pending_grad(acq, p, xs, fantasies=fantasies, seed=climb_seed[0], raise_tau=raise_tau)
+        return _PendResult(res, grad)
+
+    return _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, opts)
 
 
 _BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features"}

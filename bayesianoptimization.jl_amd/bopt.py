@@ -447,7 +447,7 @@ class BOpt:
     def ask(self, n=1):
         """n points to evaluate next, as a d x n array, while earlier proposals are still out.  While the initializer has points
         left they come from it; after that each point is the maximiser of the acquisition averaged over fantasised outcomes at
-        everything that is out (acquire_max_pending with `acquisitionoptions`; its keys "fantasies" and "raise_tau" go there too) and joins the
+        everything that is out (acquire_max_pending with `acquisitionoptions`; its keys "fantasies", "raise_tau" and "refine" go there too) and joins the
         model's pending set before the next one is sought, so the n points of one call see each other.  Steps the iteration
         counter once per point.  Report the outcomes with tell, in any order."""
         self._refuse_ask_tell("ask")

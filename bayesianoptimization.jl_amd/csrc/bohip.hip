@@ -34,6 +34,7 @@
 #include "../../include/bohip_pend.h"
 #include "../../include/bohip_nei.h"
 #include "../../include/bohip_nei_grad.h"
+#include "../../include/bohip_pend_grad.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -53,6 +54,7 @@
 #include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
 #include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
 #include "kernels_nei_grad.hip"   // (after kernels_nei.hip and kernels_con.hip: NeiReduce; grad_finish_waves, GC)
+#include "kernels_pend_grad.hip"  // (after kernels_pend.hip and kernels_nei_grad.hip: PEND_ZCAP; k_nei_mix and k_nei_grad_finish are launched as they stand)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -293,6 +295,10 @@ struct bohip_gp : gp_streams {
                    pend_gen == o.pend_gen && jitter == o.jitter;
         }
     } pend_key;
+    // its gradient (include/bohip_pend_grad.h): the basis [alpha | W'V_p] at the end of pend_state, pend_bt_rows rows of it
+    // (0 until a gradient call asks), valid while pend_bt_key equals pend_key
+    int64_t pend_bt_rows = 0;
+    PendKey pend_bt_key;
     DBuf<double> dPV;
     DBuf<char> pend_state, pend_call;
     // noisy expected improvement (include/bohip_nei.h): the COMPANION -- a handle of its own for the same X under the same
@@ -5368,8 +5374,12 @@ static bohip_gp::PendKey pend_key_now(const bohip_gp* g) {
     return k;
 }
 static constexpr size_t PEND_G_TILE = (size_t)TILE * PEND_GLD;   // the one 128 x 64 tile k_gemm_nt writes for V_p'V_p
-static size_t pend_state_layout(const bohip_gp* g, const void* base, layout::PendState* w) {
-    return layout::pend_state(base, PEND_PMAX, (size_t)g->d, PEND_G_TILE, w);
+static size_t pend_state_layout(const bohip_gp* g, const void* base, layout::PendState* w, double** Bt = nullptr) {
+    layout::PendGradState gs;   // (the gradient's basis follows the members; no rows of it until a gradient call has asked)
+    const size_t n = layout::pend_grad_state(base, PEND_PMAX, (size_t)g->d, PEND_G_TILE, (size_t)g->pend_bt_rows * PEND_CF, &gs);
+    *w = gs.v;
+    if (Bt) *Bt = gs.Bt;
+    return n;
 }
 // V' of the chunk buffer (dVT alone: no U' here), as ensure_grad_scratch sizes it
 static int ensure_pend_vt(bohip_gp* g) {
@@ -5383,7 +5393,9 @@ static int ensure_pend_vt(bohip_gp* g) {
 // alpha row, V_p'V_p on the MFMA engine, Sigma_p and its factor in one workgroup.  A failed pivot: BOHIP_E_NOTPD, the state stays unset.
 static int ensure_pending(bohip_gp* g, layout::PendState* out) {
     const int64_t p = g->pend_p;
-    HIPCHK(g->pend_state.reserve(pend_state_layout(g, nullptr, out), g->stream));
+    bool grew = false;
+    HIPCHK(g->pend_state.reserve(pend_state_layout(g, nullptr, out), g->stream, Grow::Exact, &grew));
+    if (grew) g->pend_key = g->pend_bt_key = bohip_gp::PendKey{};   // (the block's contents went with the old one)
     pend_state_layout(g, g->pend_state, out);
     const bohip_gp::PendKey now = pend_key_now(g);
     if (g->pend_key == now) return 0;
@@ -5483,15 +5495,40 @@ static int pend_score_stage(bohip_gp* g, PendScore ps, Best* blk, Best* d_best) 
     return 0;
 }
 
-int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
-                           int flags, double* score, double* mu, double* var, bohip_best* best) {
-    if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_pending: bad arguments");
+// What the gradient call (include/bohip_pend_grad.h; defined after the NEI gradient, whose mix and finish it launches) adds to the
+// value call: the basis once per pending state, and three stages per K*' chunk.
+struct PendGradCtx {
+    layout::PendState st;
+    double *Bt, *Cf, *gam, *Z, *tau, *B;
+    int64_t p, S1, Npad;
+    bool tau_acq;
     AcqParams ap;
-    CHK(pend_check_acq("score_pending", acq_id, acq_params, S, flags, &ap));
+};
+static int pend_grad_setup(bohip_gp* g);
+static int ensure_pending_basis(bohip_gp* g, const PassPlan& pl, double* Bt);
+static int pend_grad_chunk(bohip_gp* g, const PassPlan& pl, const KernelHyper& hp, const PendGradCtx& c, int64_t r0, int64_t r1);
+
+// bohip_gp_score_pending (grad == nullptr) and bohip_gp_score_pending_grad: ONE driver, the value call's launches in the value call's order
+static int pend_score_call(const char* who, bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S,
+                           uint64_t seed, int flags, double* score, double* grad, double* mu, double* var, bohip_best* best) {
+    const bool wg = grad != nullptr;
+    AcqParams ap;
+    CHK(pend_check_acq(who, acq_id, acq_params, S, flags, &ap));
     if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
     const int64_t p = g->pend_p;
-    if (p == 0) {   // no pending point: the call IS bohip_gp_score (and bohip_gp_predict for the moments)
+    if (p == 0 && wg) {   // no pending point: the call IS bohip_gp_score_grad (and bohip_gp_predict for the moments)
+        std::vector<double> sc((size_t)(score ? 0 : R));
+        const double* s = score ? score : sc.data();
+        CHK(bohip_gp_score_grad(g, acq_id, acq_params, Xs, R, score ? score : sc.data(), grad));
+        if (best) {   // bohip_gp_score's rule on the returned scores: the first of the largest; NaN and -Inf never win
+            best->val = -INFINITY; best->idx = -1;
+            for (int64_t r = 0; r < R; ++r)
+                if (s[r] > best->val) { best->val = s[r]; best->idx = r; }
+        }
+    } else if (p == 0) {   // no pending point: the call IS bohip_gp_score (and bohip_gp_predict for the moments)
         CHK(bohip_gp_score(g, acq_id, acq_params, Xs, R, score, best));
+    }
+    if (p == 0) {
         if (R > 0 && (mu || var)) {
             std::vector<double> tmp((size_t)R);
             CHK(bohip_gp_predict(g, Xs, R, mu ? mu : tmp.data(), var ? var : tmp.data()));
@@ -5502,17 +5539,24 @@ int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, co
         if (best) { best->val = -INFINITY; best->idx = -1; }
         return 0;
     }
-    CHK(refuse_weighted(g, "bohip_gp_score_pending"));
+    CHK(refuse_weighted(g, wg ? "bohip_gp_score_pending_grad" : "bohip_gp_score_pending"));
     HIPCHK(hipSetDevice(g->device));
     t_reset(g);
     CHK(ensure_fresh(g));
+    if (wg) g->pend_bt_rows = std::max<int64_t>(g->pend_bt_rows, (int64_t)row_tiles(g) * TILE);
     layout::PendState st;
     CHK(ensure_pending(g, &st));
     CHK(ensure_xs(g, R));
     CHK(ensure_score_scratch(g, R));
     CHK(one_time_kernel_setup());
     const PassPlan pl = choose_route(g, R, WHOLE_K_ONLY);   // the route that stores V'
-    CHK(ensure_pend_vt(g));
+    if (wg) {   // V' and U' of the chunk; the basis, if this state has none yet
+        CHK(ensure_grad_scratch(g));
+        CHK(pend_grad_setup(g));
+        HIPCHK(g->dgrad.reserve((size_t)R * g->d, g->stream));
+    } else {
+        CHK(ensure_pend_vt(g));
+    }
     const int64_t S1 = std::max<int64_t>(S, 1), crows = round_up(std::min(R, pl.chunk), TILE);
     // V'V_p is 128 x 64 tiles over a contraction of Npad: a chunk of 4096 candidates is 32 workgroups.  The contraction is cut into
     // slices of kz 16-deep steps -- a function of the row tiles alone, so a candidate's value does not depend on the batch it is
@@ -5520,10 +5564,19 @@ int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, co
     const int kc_all = pl.dm.T * (TILE / KC), kz = std::max(8, (kc_all + 7) / 8), nsl = (kc_all + kz - 1) / kz;
     const int64_t plane = crows * PEND_GLD;
     const int nb = pend_blocks(R);
-    PendCallWs w;
-    auto lay = [&](const void* base) { return layout::pend_call(base, (size_t)(nsl * plane), (size_t)R, (size_t)p, (size_t)S1, 0, (size_t)nb, &w); };
+    layout::PendGradCall<Best> gw;
+    PendCallWs& w = gw.v;
+    auto lay = [&](const void* base) {
+        if (wg) return layout::pend_grad_call(base, (size_t)(nsl * plane), (size_t)R, (size_t)p, (size_t)S1, (size_t)nb, (size_t)crows, PEND_CF, &gw);
+        return layout::pend_call(base, (size_t)(nsl * plane), (size_t)R, (size_t)p, (size_t)S1, 0, (size_t)nb, &w);
+    };
     HIPCHK(g->pend_call.reserve(lay(nullptr), g->stream));
     lay(g->pend_call);
+    PendGradCtx gc{};
+    if (wg) {
+        pend_state_layout(g, g->pend_state, &gc.st, &gc.Bt);
+        CHK(ensure_pending_basis(g, pl, gc.Bt));
+    }
     HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
     const bool tau_acq = pend_tau_acq(acq_id), raise = tau_acq && (flags & BOHIP_PEND_RAISE_TAU);
     t_begin(g, "pend_tables");
@@ -5549,7 +5602,14 @@ int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, co
         t_end(g);
         return 0;
     };
-    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, false, FuseParams{}, cross);
+    gc.Cf = gw.Cf; gc.gam = gw.gam; gc.Z = w.Z; gc.tau = w.tau; gc.B = w.B; gc.p = p; gc.S1 = S1; gc.Npad = pl.dm.Npad;
+    gc.tau_acq = tau_acq; gc.ap = ap;
+    auto cross_grad = [&](int64_t r0, int64_t r1) {   // (U' = V'W of the chunk stands in dUT)
+        CHK(cross(r0, r1));
+        return pend_grad_chunk(g, pl, hp, gc, r0, r1);
+    };
+    const int64_t chunks = wg ? chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, true, FuseParams{}, cross_grad)
+                              : chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, false, FuseParams{}, cross);
     if (chunks < 0) return (int)chunks;
     g->score_launches = chunks;
     AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
@@ -5560,12 +5620,19 @@ int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, co
     ps.tau_acq = tau_acq ? 1 : 0; ps.ap = ap; ps.score_out = score ? g->dscore.get() : nullptr; ps.var_out = g->dvar;
     CHK(pend_score_stage(g, ps, w.blk, best ? w.best : nullptr));
     if (score) HIPCHK(hipMemcpyAsync(score, g->dscore, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (wg) HIPCHK(hipMemcpyAsync(grad, g->dgrad, (size_t)R * g->d * 8, hipMemcpyDeviceToHost, g->stream));
     if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (var) HIPCHK(hipMemcpyAsync(var, g->dvar, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
     if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;
+}
+
+int bohip_gp_score_pending(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
+                           int flags, double* score, double* mu, double* var, bohip_best* best) {
+    if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_pending: bad arguments");
+    return pend_score_call("score_pending", g, acq_id, acq_params, Xs, R, S, seed, flags, score, nullptr, mu, var, best);
 }
 
 int bohip_pend_values(bohip_gp* g, int acq_id, const double* acq_params, int64_t R, int64_t p, int64_t S, const double* mu,
@@ -5905,6 +5972,15 @@ static void launch_nei_grad_finish(bohip_gp* c, int64_t r0, int64_t r1, const Ke
                c->stream, c->dX, c->n, c->dXs, r0, r1, hp, E, c->ld, d_grad, c->dgparts, c->dgcount);
 }
 }  // extern "C++"
+static int nei_mix_setup() {   // k_nei_mix's dynamic LDS, once per device
+    static bool done[64] = {false};
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    return once_per_device(done, dev, [] {
+        HIPCHK(hipFuncSetAttribute((const void*)k_nei_mix, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+        return 0;
+    });
+}
 
 int bohip_gp_score_nei_grad(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
                             double jitter_rel, double* score, double* grad, double* mu, double* var, bohip_best* best) {
@@ -5924,15 +6000,7 @@ int bohip_gp_score_nei_grad(bohip_gp* g, int acq_id, const double* acq_params, c
     CHK(ensure_score_scratch(c, R));
     CHK(one_time_kernel_setup());
     CHK(nei_kernel_setup());
-    {
-        static bool done[64] = {false};
-        int dev = 0;
-        HIPCHK(hipGetDevice(&dev));
-        CHK(once_per_device(done, dev, [] {
-            HIPCHK(hipFuncSetAttribute((const void*)k_nei_mix, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
-            return 0;
-        }));
-    }
+    CHK(nei_mix_setup());
     // The companion's pass on the route that stores V' and leaves U' in dUT.  The small pass forms its gradient in-kernel from ONE alpha
     // and keeps neither K*' nor U' in memory: it is switched off, as for the posterior's Jacobians.
     const PassPlan pl = choose_route(c, R, RouteWants{false, true, Prune::No});
@@ -6014,6 +6082,70 @@ int bohip_gp_score_nei_grad(bohip_gp* g, int acq_id, const double* acq_params, c
     t_collect(g);
     nei_merge_timing(g);
     return 0;
+}
+
+// ---- the gradient under pending evaluations (include/bohip_pend_grad.h; kernels_pend_grad.hip) -------------------------
+static int pend_grad_setup(bohip_gp* g) {
+    (void)g;
+    return nei_mix_setup();
+}
+// Bt = [alpha | A = W'V_p | 0] for the pending state in force: A' = V_p'W is the U' product over dPV (one 128-row tile into dUT, which
+// the chunk loop has not touched yet), then the transpose.  Kept while pend_key stands.
+static int ensure_pending_basis(bohip_gp* g, const PassPlan& pl, double* Bt) {
+    if (g->pend_bt_key == g->pend_key) return 0;
+    t_begin(g, "pend_state");
+    GemmNTParams u{};
+    u.A = g->dPV; u.lda = g->ld; u.B = g->dWT; u.ldb = g->ld; u.C = g->dUT; u.ldc = g->ld;
+    u.mt = 1; u.nt64 = 2 * pl.dm.T; u.kc = pl.dm.T * (TILE / KC); u.alpha = 1.0; u.beta = 0.0; u.klo_from_n = 1;
+    CHK(launch_gemm_nt(g, u));
+    hipLaunchKernelGGL(k_pend_basis, dim3((unsigned)((pl.dm.Npad * PEND_CF + 255) / 256)), dim3(256), 0, g->stream, g->dalpha.get(),
+                       g->dUT.get(), g->ld, g->n, pl.dm.Npad, (int)g->pend_p, Bt);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    g->pend_bt_key = g->pend_key;
+    return 0;
+}
+// One K*' chunk after k_pend_cross (V' in dVT, U' in dUT, b in c.B): the resident moments, the weights, E over U' in place, the
+// contraction with dk/dx and the p direct terms.  Leaves grad rows r0 .. r1 - 1 in dgrad.
+static int pend_grad_chunk(bohip_gp* g, const PassPlan& pl, const KernelHyper& hp, const PendGradCtx& c, int64_t r0, int64_t r1) {
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    const int mt = (int)((r1 - r0 + TILE - 1) / TILE);
+    t_begin(g, "pend_weights");
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq.get() + r0, pl.dm.Rpad, pl.dq_tiles(),
+                       g->dmu_raw.get() + r0, r1 - r0, hp.sigma2, g->beta, mm, g->dmu.get() + r0, g->dvar.get() + r0, (double*)nullptr,
+                       (Best*)nullptr);
+    PendWeights pw{};
+    pw.mu = g->dmu; pw.var = g->dvar; pw.B = c.B; pw.Z = c.Z; pw.tau = c.tau; pw.L = c.st.L; pw.r0 = r0; pw.r1 = r1;
+    pw.p = (int)c.p; pw.S1 = (int)c.S1; pw.tau_acq = c.tau_acq ? 1 : 0; pw.ap = c.ap; pw.Cf = c.Cf; pw.gam = c.gam;
+    hipLaunchKernelGGL(k_pend_weights, dim3((unsigned)(mt * (TILE / PEND_W_WAVES))), dim3(64 * PEND_W_WAVES), 0, g->stream, pw);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    NeiMix mx{};   // E = Cf Bt' - 2 gamma U': k_nei_mix with a contraction of PEND_CF
+    mx.A = c.Cf; mx.B = c.Bt; mx.c = c.gam; mx.E = g->dUT; mx.ld = PEND_CF; mx.lde = g->ld; mx.N = g->n;
+    mx.mt = mt; mx.nt = (int)(c.Npad / CTILE); mx.kc = PEND_CF / KC; mx.rows = (int)(r1 - r0);
+    t_begin(g, "pend_mix");
+    hipLaunchKernelGGL(k_nei_mix, dim3((unsigned)(mx.mt * mx.nt)), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(), g->stream, mx);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    int Sx = 1;
+    CHK(grad_obs_splits(g, r0, r1, &Sx));
+    t_begin(g, "pend_grad_finish");
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        launch_nei_grad_finish<DT>(g, r0, r1, hp, mx.E, g->dgrad, Sx);
+        LAUNCH_FAM(fam_low(hp), (k_pend_grad_direct<DT, true>), (k_pend_grad_direct<DT, false>), dim3((unsigned)((r1 - r0 + 63) / 64)), dim3(64), 0,
+                   g->stream, g->dXs.get(), r0, r1, hp, c.st.Xp, (int)c.p, c.Cf, g->dgrad.get());
+    });
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_gp_score_pending_grad(bohip_gp* g, int acq_id, const double* acq_params, const double* Xs, int64_t R, int64_t S, uint64_t seed,
+                                int flags, double* score, double* grad, double* mu, double* var, bohip_best* best) {
+    if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_pending_grad: bad arguments");
+    if (!grad) return fail(BOHIP_E_ARG, "score_pending_grad: grad is required");
+    return pend_score_call("score_pending_grad", g, acq_id, acq_params, Xs, R, S, seed, flags, score, grad, mu, var, best);
 }
 
 int bohip_nei_values(bohip_gp* g, int acq_id, int64_t R, int64_t S, const double* mu_s, const double* var, const double* tau_s,

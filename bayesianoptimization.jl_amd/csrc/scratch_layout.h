@@ -199,6 +199,25 @@ size_t pend_call(const void* base, size_t n_c, size_t R, size_t p, size_t S, siz
     w->best = w->blk + nb;
     return c.total();
 }
+// pending evaluations with the gradient's basis (bohip_gp_score_pending_grad): pend_state's members at pend_state's offsets, then
+// [Bt = [alpha | W'V_p | 0] n_bt doubles, 128-byte rows for the LDS-DMA of the mix]; n_bt = 0 until a gradient call asks for it
+struct PendGradState { PendState v; double* Bt; };
+inline size_t pend_grad_state(const void* base, size_t pmax, size_t d, size_t n_tile, size_t n_bt, PendGradState* w) {
+    Carve c(base);
+    c.take<char>(pend_state(base, pmax, d, n_tile, &w->v));
+    w->Bt = c.take<double>(n_bt, 128);
+    return c.total();
+}
+// its call: pend_call's members at pend_call's offsets, then [Cf = the chunk's coefficient rows, rows x kw | gamma one a row]
+template <class Rec>
+struct PendGradCall { PendCall<Rec> v; double *Cf, *gam; };
+template <class Rec>
+size_t pend_grad_call(const void* base, size_t n_c, size_t R, size_t p, size_t S, size_t nb, size_t rows, size_t kw, PendGradCall<Rec>* w) {
+    Carve c(base);
+    c.take<char>(pend_call(base, n_c, R, p, S, 0, nb, &w->v));
+    w->Cf = c.take<double>(rows * kw, 128); w->gam = c.take<double>(rows);
+    return c.total();
+}
 // noisy expected improvement, the fantasies derived from (model, companion, S, seed): [F | alpha | four work matrices (rows x ld each,
 // 128-byte rows for the LDS-DMA of the products) | tau S1]
 struct NeiState { double *F, *alpha, *w0, *w1, *w2, *w3, *tau; };

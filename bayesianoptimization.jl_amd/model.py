@@ -480,6 +480,24 @@ class ElasticGPE:
                                                _ptr(var), C.byref(best)))
         return PendingScore(sc, mu, var, best.val, best.idx)
 
+    def score_pending_grad(self, acq, params, xs, fantasies=0, seed=0, raise_tau=False):
+        """score_pending and its gradient in the candidates (bohip_gp_score_pending_grad, include/bohip_pend_grad.h):
+        returns (PendingScore, grad [d, R]).  With the seed fixed the fantasy-averaged score is one deterministic function of x, and
+        grad is its derivative: what an L-BFGS ascent climbs.  The scores, mu, var and the record are score_pending's bytes; with an
+        empty pending set the call is `score_grad`.  The model is not changed."""
+        xs = _cols(xs, self.dim)
+        R = xs.shape[1]
+        p = np.ascontiguousarray(np.atleast_1d(np.asarray(params, dtype=np.float64)))
+        if p.size < 2:
+            p = np.concatenate([p, np.zeros(2 - p.size)])
+        sc, mu, var = np.empty(R), np.empty(R), np.empty(R)
+        grad = np.empty((self.dim, R), order="F")
+        best = Best()
+        check(self._lib.bohip_gp_score_pending_grad(self._h, _lib.ACQ[acq], _ptr(p), _ptr(xs), R, int(fantasies), int(seed),
+                                                    _lib.PEND_RAISE_TAU if raise_tau else 0, _ptr(sc), _ptr(grad), _ptr(mu), _ptr(var),
+                                                    C.byref(best)))
+        return PendingScore(sc, mu, var, best.val, best.idx), grad
+
     def pend_values(self, acq, params, mu, var, B, Z, tau_s=None):
         """The averaging stage on its own, from host arrays (bohip_pend_values): mu, var [R], B [R, p], Z [S, p], tau_s [S] or None.
         Returns (scores[R], best_val, best_idx)."""

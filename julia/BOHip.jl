@@ -359,6 +359,7 @@ include("BOHipLOO.jl")     # leave-one-out cross-validation (include/bohip_loo.h
 include("BOHipLOOBatch.jl") # its objective at H settings in one launch (include/bohip_loo_batch.h): loo_grad_batch
 include("BOHipRep.jl")      # replicated sites (include/bohip_rep.h): append_sites!, collapse_evaluations, sites_info, site_reps
 include("BOHipPend.jl")     # pending evaluations (include/bohip_pend.h): pending_set!, pending_info, score_pending, acquire_max_pending
+include("BOHipPendGrad.jl") # its gradient (include/bohip_pend_grad.h): c_gp_score_pending_grad
 include("BOHipNEI.jl")      # noisy expected improvement (include/bohip_nei.h): nei, nei_fantasies, nei_values, NoisyExpectedImprovement
 include("BOHipNEIGrad.jl")  # its gradient (include/bohip_nei_grad.h): nei_grad
 """
