@@ -260,6 +260,12 @@ PEND_GRAD_SIGNATURES = {
                                               C.POINTER(Best)]),
 }
 
+# the symbol include/bohip_qei_joint.h declares (the joint q-EI of B batches of q points and its gradient)
+QEIJ_QMAX, QEIJ_SMAX = 16, 1024
+QEI_JOINT_SIGNATURES = {
+    "bohip_gp_qei_joint": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_double, _dp, _dp, _dp, _i64p]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -320,7 +326,7 @@ def load():
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
                               + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())
-                              + list(PEND_GRAD_SIGNATURES.items())):
+                              + list(PEND_GRAD_SIGNATURES.items()) + list(QEI_JOINT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

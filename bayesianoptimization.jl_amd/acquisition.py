@@ -1056,7 +1056,7 @@ def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, s
     return _acquire_max_candidates(score, lb, ub, restarts, maxeval, rng, opts)
 
 
-_BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features"}
+_BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features", "refine"}
 _BATCH_FANTASIES = ("believer", "liar_max", "liar_min", "liar_mean")
 _BATCH_METHODS = ("fantasy", "qei")
 
@@ -1076,6 +1076,12 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
           "pathwise": True takes the draws from posterior sample paths instead (model.draw_paths with "features" = M random
           features, default 2048, evaluated over the candidates, then model.qei_select): no R x R factorisation, so "candidates"
           may exceed one chunk.  The values returned are the picks' marginal gains; their sum is the batch's q-EI estimate.
+          "refine": n > 0 (default 0: the calls and draws above, nothing more) then climbs the batch OFF the candidate set: n
+          starts over the q d variables of a batch -- the greedy batch, and n - 1 batches of q distinct candidates drawn by
+          `rng` -- ascend in lock-step inside the box on the joint q-EI and its gradient (model.qei_joint, one call per step,
+          one seed drawn from `rng` for the climb; include/bohip_qei_joint.h).  A batch whose covariance does not
+          factor has the value -Inf and the ascent backtracks from it.  The end point with the largest value wins, the first on
+          ties: never below the greedy batch's value under the climb's seed.  Returns ([value], X d x q) then.
     Returns (values[q'], X d x q') with q' <= q: picks that could not win (no finite score / no gain left) are dropped."""
     lb = np.asarray(lowerbounds, dtype=np.float64)
     ub = np.asarray(upperbounds, dtype=np.float64)
@@ -1106,8 +1112,13 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
         if draws < 1:
             raise ValueError(f"options['draws'] = {draws} < 1")
         need = ("draw_paths", "qei_select") if pathwise else ("qei_batch",)
+        refine = int(opts.get("refine", 0) or 0)
+        if refine < 0:
+            raise ValueError(f"options['refine'] = {refine} < 0")
+        if refine > 0:
+            need += ("qei_joint",)
     else:
-        for k in ("draws", "pathwise", "features"):
+        for k in ("draws", "pathwise", "features", "refine"):
             if k in opts:
                 raise ValueError(f"batch option {k!r} needs 'method': 'qei'")
         need = ("select_batch",)
@@ -1146,6 +1157,10 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
         keep = idx >= 0
         if not keep.all():
             warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a gain above zero")
+        if refine > 0:
+            if not keep.all():
+                raise ValueError("batch option 'refine' needs q greedy picks to start from: this route returned fewer")
+            return _refine_batch(model, xs, idx, q, draws, a.tau, refine, lb, ub, rng or np.random.default_rng())
         return val[keep], np.asfortranarray(xs[:, idx[keep]])
     y = np.asarray(model.y)
     fv = {"believer": "believer", "liar_max": float(y.max()), "liar_min": float(y.min()), "liar_mean": float(y.mean())}[fantasy]
@@ -1154,6 +1169,27 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
     if not keep.all():
         warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a finite score")
     return val[keep], np.asfortranarray(xs[:, idx[keep]])
+
+
+_REFINE_BATCH_PASSES = 200   # device calls of one climb at the most
+
+
+def _refine_batch(model, xs, idx, q, draws, tau, refine, lb, ub, gen):
+    """acquire_batch's "refine": `refine` starts over the q d variables of a batch (column 0: the greedy picks xs[:, idx]; the others: q
+    distinct candidates each, drawn by gen) climb in lock-step on model.qei_joint under ONE seed.  Returns ([value], X d x q) of the
+    end point with the largest value, the first on ties."""
+    d = lb.size
+    starts = [np.asarray(idx)] + [gen.choice(xs.shape[1], size=q, replace=False) for _ in range(refine - 1)]
+    seed = int(gen.integers(0, 2 ** 63 - 1))
+    X0 = np.stack([xs[:, s].reshape(-1, order="F") for s in starts], axis=1)        # (q d) x refine, point j = rows j d .. j d + d - 1
+
+    def fg(X):
+        v, g, _ = model.qei_joint(X.reshape(d, -1, order="F"), q, draws, seed, tau=tau)
+        return v, g.reshape(q * d, -1, order="F")
+
+    f, X = _batched_lbfgs_ascent(fg, X0, np.tile(lb, q), np.tile(ub, q), _REFINE_BATCH_PASSES)
+    k = int(np.argmax(f))
+    return f[k:k + 1].copy(), np.asfortranarray(X[:, k].reshape(d, q, order="F"))
 
 
 def _distinct_picks(samples):

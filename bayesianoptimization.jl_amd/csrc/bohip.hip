@@ -35,6 +35,7 @@
 #include "../../include/bohip_nei.h"
 #include "../../include/bohip_nei_grad.h"
 #include "../../include/bohip_pend_grad.h"
+#include "../../include/bohip_qei_joint.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -55,6 +56,7 @@
 #include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
 #include "kernels_nei_grad.hip"   // (after kernels_nei.hip and kernels_con.hip: NeiReduce; grad_finish_waves, GC)
 #include "kernels_pend_grad.hip"  // (after kernels_pend.hip and kernels_nei_grad.hip: PEND_ZCAP; k_nei_mix and k_nei_grad_finish are launched as they stand)
+#include "kernels_qei_joint.hip"  // (after kernels_pend_grad.hip: pend_fx; the finish is k_nei_grad_finish as it stands)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -301,6 +303,8 @@ struct bohip_gp : gp_streams {
     PendKey pend_bt_key;
     DBuf<double> dPV;
     DBuf<char> pend_state, pend_call;
+    // joint q-EI (include/bohip_qei_joint.h): the block of one call (layout::qei_joint)
+    DBuf<char> qeij_ws;
     // noisy expected improvement (include/bohip_nei.h): the COMPANION -- a handle of its own for the same X under the same
     // kernel parameters with delta on the diagonal, owned by this one, made at the first call of that header and kept in step lazily
     // (nei_jrel, nei_steps: what its diagonal was set from) -- and the fantasies [F | alpha_s | work | tau_s] (layout::nei_state), valid
@@ -6146,6 +6150,93 @@ int bohip_gp_score_pending_grad(bohip_gp* g, int acq_id, const double* acq_param
     if (!g || R < 0 || (R > 0 && !Xs)) return fail(BOHIP_E_ARG, "score_pending_grad: bad arguments");
     if (!grad) return fail(BOHIP_E_ARG, "score_pending_grad: grad is required");
     return pend_score_call("score_pending_grad", g, acq_id, acq_params, Xs, R, S, seed, flags, score, grad, mu, var, best);
+}
+
+// ---- joint q-EI of B batches and its gradient (include/bohip_qei_joint.h; kernels_qei_joint.hip) -----------------------
+static size_t qeij_layout(const void* base, int64_t S, int64_t B, int64_t R, layout::QeiJoint* w) {
+    return layout::qei_joint(base, (size_t)S, (size_t)B, (size_t)R, w);
+}
+// The one K*' chunk after the pass (V' in dVT; with want_grad U' in dUT): Sigma per group, the core, and for the gradient the mix over
+// U' in place, the contraction with dk/dx and the direct terms.  The finish runs with ONE observation split whatever R is: its two
+// forms then add in the same order, so a group's bytes do not depend on B.
+static int qeij_chunk(bohip_gp* g, const PassPlan& pl, const KernelHyper& hp, const layout::QeiJoint& w, int64_t B, int q, int S, double tau,
+                      double jitter_rel, bool want_grad) {
+    const int64_t R = B * q;
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    t_begin(g, "qeij_cov");
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq.get(), pl.dm.Rpad, pl.dq_tiles(),
+                       g->dmu_raw.get(), R, hp.sigma2, g->beta, mm, g->dmu.get(), g->dvar.get(), (double*)nullptr, (Best*)nullptr);
+    LAUNCH_FAM(fam_low(hp), (k_qeij_cov<true>), (k_qeij_cov<false>), dim3((unsigned)B), dim3(256), 0, g->stream, g->dVT.get(), g->ld, g->n,
+               g->dXs.get(), q, hp, w.Sig);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    QeijCore c{};
+    c.Sig = w.Sig; c.mu = g->dmu; c.Z = w.Z; c.q = q; c.S = S; c.tau = tau; c.jitter = jitter_rel * hp.sigma2;
+    c.value = w.value; c.pivot = w.pivot; c.mubar = w.mubar; c.Sbar = w.Sbar;
+    t_begin(g, "qeij_core");
+    hipLaunchKernelGGL(k_qeij_core, dim3((unsigned)B), dim3(256), 0, g->stream, c);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    if (!want_grad) return 0;
+    t_begin(g, "qeij_mix");
+    hipLaunchKernelGGL(k_qeij_mix, dim3((unsigned)B, (unsigned)(pl.dm.Npad / 64)), dim3(256), 0, g->stream, w.Sbar, w.mubar, g->dalpha.get(),
+                       q, g->n, pl.dm.Npad, g->dUT.get(), g->ld);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    t_begin(g, "qeij_grad_finish");
+    dispatch_dt(g->d, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        launch_nei_grad_finish<DT>(g, 0, R, hp, g->dUT, g->dgrad, 1);
+        LAUNCH_FAM(fam_low(hp), (k_qeij_direct<DT, true>), (k_qeij_direct<DT, false>), dim3((unsigned)((R + 63) / 64)), dim3(64), 0, g->stream,
+                   g->dXs.get(), R, q, hp, w.Sbar, g->dgrad.get());
+    });
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    return 0;
+}
+
+int bohip_gp_qei_joint(bohip_gp* g, const double* Xs, int64_t B, int64_t q, int64_t S, uint64_t seed, double tau, double jitter_rel,
+                       double* value, double* grad, double* mu, int64_t* pivot) {
+    if (!g || !Xs || !value) return fail(BOHIP_E_ARG, "qei_joint: null argument");
+    if (B < 1 || q < 1 || q > BOHIP_QEIJ_QMAX || S < 1 || S > BOHIP_QEIJ_SMAX)
+        return fail(BOHIP_E_ARG, "qei_joint: B >= 1, 1 <= q <= " + std::to_string(BOHIP_QEIJ_QMAX) + ", 1 <= S <= " + std::to_string(BOHIP_QEIJ_SMAX));
+    if (!std::isfinite(tau) || !std::isfinite(jitter_rel) || jitter_rel < 0.0)
+        return fail(BOHIP_E_ARG, "qei_joint: tau must be finite, jitter_rel finite and >= 0");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    CHK(refuse_weighted(g, "bohip_gp_qei_joint"));
+    HIPCHK(hipSetDevice(g->device));
+    if (B > chunk_cap(g) / q)
+        return fail(BOHIP_E_UNSUPPORTED, "qei_joint: B q exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + "): the largest B at q = " +
+                                             std::to_string(q) + " is " + std::to_string(chunk_cap(g) / q));
+    const int64_t R = B * q;
+    const bool wg = grad != nullptr;
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    CHK(ensure_xs(g, R));
+    CHK(ensure_score_scratch(g, R));
+    CHK(one_time_kernel_setup());
+    const PassPlan pl = choose_route(g, R, WHOLE_K_ONLY);   // the route that stores V'
+    if (R > pl.chunk) return fail(BOHIP_E_UNSUPPORTED, "qei_joint: B q exceeds one candidate chunk (" + std::to_string(chunk_cap(g)) + ")");
+    CHK(ensure_grad_scratch(g));
+    if (wg) HIPCHK(g->dgrad.reserve((size_t)R * g->d, g->stream));
+    layout::QeiJoint w;
+    HIPCHK(g->qeij_ws.reserve(qeij_layout(nullptr, S, B, R, &w), g->stream));
+    qeij_layout(g->qeij_ws, S, B, R, &w);
+    HIPCHK(hipMemcpyAsync(g->dXs, Xs, (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const KernelHyper hp = make_hyper(g);
+    hipLaunchKernelGGL(k_qeij_normals, dim3((unsigned)((S * QEIJ_Q + 255) / 256)), dim3(256), 0, g->stream, seed, (int)S, w.Z);
+    HIPCHK(hipGetLastError());
+    auto finish = [&](int64_t, int64_t) { return qeij_chunk(g, pl, hp, w, B, (int)q, (int)S, tau, jitter_rel, wg); };
+    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, wg, FuseParams{}, finish);   // (one chunk)
+    if (chunks < 0) return (int)chunks;
+    g->score_launches = chunks;
+    HIPCHK(hipMemcpyAsync(value, w.value, (size_t)B * 8, hipMemcpyDeviceToHost, g->stream));
+    if (wg) HIPCHK(hipMemcpyAsync(grad, g->dgrad, (size_t)R * g->d * 8, hipMemcpyDeviceToHost, g->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)R * 8, hipMemcpyDeviceToHost, g->stream));
+    if (pivot) HIPCHK(hipMemcpyAsync(pivot, w.pivot, (size_t)B * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
 }
 
 int bohip_nei_values(bohip_gp* g, int acq_id, int64_t R, int64_t S, const double* mu_s, const double* var, const double* tau_s,

@@ -218,6 +218,16 @@ size_t pend_grad_call(const void* base, size_t n_c, size_t R, size_t p, size_t S
     w->Cf = c.take<double>(rows * kw, 128); w->gam = c.take<double>(rows);
     return c.total();
 }
+// joint q-EI of B groups (bohip_gp_qei_joint): [Z S x 16 | Sigma B x 256 | Sbar B x 256 | mubar R | value B | pivot B]
+struct QeiJoint { double *Z, *Sig, *Sbar, *mubar, *value; long long* pivot; };
+inline size_t qei_joint(const void* base, size_t S, size_t B, size_t R, QeiJoint* w) {
+    Carve c(base);
+    w->Z = c.take<double>(S * 16);
+    w->Sig = c.take<double>(B * 256); w->Sbar = c.take<double>(B * 256);
+    w->mubar = c.take<double>(R); w->value = c.take<double>(B);
+    w->pivot = c.take<long long>(B);
+    return c.total();
+}
 // noisy expected improvement, the fantasies derived from (model, companion, S, seed): [F | alpha | four work matrices (rows x ld each,
 // 128-byte rows for the LDS-DMA of the products) | tau S1]
 struct NeiState { double *F, *alpha, *w0, *w1, *w2, *w3, *tau; };

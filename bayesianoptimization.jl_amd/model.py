@@ -683,6 +683,25 @@ class ElasticGPE:
             tau = maxy(self)
         return _qei_batch(self._lib, self._h, _cols(xs, self.dim), q, S, seed, tau, jitter, max_tries, want_samples)
 
+    def qei_joint(self, X, q, draws=256, seed=0, tau=None, jitter_rel=1e-10, grad=True):
+        """The joint q-EI of B batches of q points and its gradient in every point (bohip_gp_qei_joint, include/bohip_qei_joint.h;
+        DESIGN.md 6z): X is d x B q, batch b = columns b q .. b q + q - 1.  Returns (value[B], grad [d, B q] or None, pivot[B]); a
+        batch whose posterior covariance has a pivot that is not positive has pivot > 0, value -Inf and a zero gradient.  With the
+        seed fixed the value is one deterministic function of the points: what an ascent over a batch climbs.  tau defaults to
+        maxy.  The model is not changed."""
+        X = _cols(X, self.dim)
+        q = int(q)
+        if q < 1 or X.shape[1] % q:
+            raise ValueError(f"X has {X.shape[1]} columns: not a multiple of q = {q}")
+        B = X.shape[1] // q
+        if tau is None:
+            tau = maxy(self)
+        value, pivot = np.empty(B), np.zeros(B, dtype=np.int64)
+        g = np.empty((self.dim, B * q), order="F") if grad else None
+        check(self._lib.bohip_gp_qei_joint(self._h, _ptr(X), B, q, int(draws), int(seed), float(tau), float(jitter_rel), _ptr(value),
+                                           _ptr(g) if grad else None, None, pivot.ctypes.data_as(C.POINTER(C.c_int64))))
+        return value, g, pivot
+
     def qei_select(self, samples, tau, q):
         """The selection of qei_batch alone on the caller's S x R sample matrix (bohip_gp_qei_select): the model supplies the
         device and the stream only.  Returns (idx[q] int64, gain[q])."""

@@ -347,6 +347,7 @@ end
 include("BOHipPaths.jl")   # posterior sample paths (include/bohip_paths.h): draw_paths, paths_eval, paths_eval_grad, paths_coef
 include("BOHipFit.jl")     # batched marginal likelihood (include/bohip_fit.h): mll_batch_dims, mll_grad_batch
 include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/bohip_qei.h): qei_batch, qei_select
+include("BOHipQEIJoint.jl") # the joint q-EI of B batches and its gradient (include/bohip_qei_joint.h): c_gp_qei_joint
 include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_acq.h): LogExpectedImprovement, acq_eval
 include("BOHipKG.jl")      # the knowledge gradient over a candidate set (include/bohip_kg.h): kg, kg_lines, KnowledgeGradient
 include("BOHipEns.jl")     # an acquisition averaged over hyper-parameter settings (include/bohip_ens.h): score_ensemble
