@@ -160,6 +160,14 @@ KG_SIGNATURES = {
     "bohip_kg_lines": (C.c_int, [_gp, _dp, _dp, C.c_int64, C.c_int64, _dp, _i32p]),
 }
 
+# every symbol include/bohip_kg_grad.h declares (the knowledge gradient at free points over a resident discretisation, and its gradient)
+KG_POINTS_R, KG_POINTS_REBUILDS, KG_POINTS_BYTES, KG_POINTS_LINES, KG_POINTS_LINE_ROWS = 0, 1, 2, 3, 4
+KG_GRAD_SIGNATURES = {
+    "bohip_gp_kg_set_points": (C.c_int, [_gp, _dp, C.c_int64]),
+    "bohip_gp_kg_points_info": (C.c_int, [_gp, C.c_int, _dp, C.c_int64]),
+    "bohip_gp_kg_grad": (C.c_int, [_gp, _dp, C.c_int64, _dp, _dp, _i32p, _dp, _dp, C.POINTER(Best)]),
+}
+
 # every symbol include/bohip_ens.h declares (one acquisition averaged over H hyper-parameter settings, on the device)
 ENS_SIGNATURES = {
     "bohip_gp_score_ens": (C.c_int, [_gp, C.c_int, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp, _i64p, C.POINTER(Best)]),
@@ -326,7 +334,8 @@ def load():
                               + list(CON_SIGNATURES.items()) + list(MO_SIGNATURES.items()) + list(LOO_SIGNATURES.items())
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
                               + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())
-                              + list(PEND_GRAD_SIGNATURES.items()) + list(QEI_JOINT_SIGNATURES.items())):
+                              + list(PEND_GRAD_SIGNATURES.items()) + list(QEI_JOINT_SIGNATURES.items())
+                              + list(KG_GRAD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -123,9 +123,11 @@ class KnowledgeGradient(AbstractAcquisition):
     """The knowledge gradient over a candidate set (include/bohip_kg.h; Frazier, Powell & Dayanik 2009): the expected
     rise of max_j mu_j over the candidates after ONE noisy observation at the point, computed exactly on the device (model.kg).  An
     extension: the reference has no such type, and no default uses it.  It is not a functor of one point's (mu, sigma^2) -- it ranks
-    a point by what observing it would teach about the optimum -- so it has no parameters, no gradient and no place in score /
-    ascend / DIRECT: acquisitionfunction takes a d x R candidate matrix, and acquire_max takes the arg-max over `maxeval`
-    Latin-hypercube candidates per restart (each set evaluated against itself)."""
+    a point by what observing it would teach about the optimum -- so it has no parameters and no place in score / ascend / DIRECT:
+    acquisitionfunction takes a d x R candidate matrix, and acquire_max takes the arg-max over `maxeval` Latin-hypercube candidates
+    per restart (each set evaluated against itself).  With the option "refine": n > 0 the restart's set becomes a discretisation
+    and the n best candidates are climbed on the gradient of the knowledge gradient at free points (model.kg_grad,
+    include/bohip_kg_grad.h)."""
     acq_id = "KG"
 
 
@@ -701,18 +703,48 @@ def _acquire_max_pathwise(model, lb, ub, method, restarts, maxeval, maxtime, opt
     return maxf, maxx
 
 
-def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng):
-    """KnowledgeGradient: a candidate-set acquisition without a gradient.  Every restart takes `maxeval` Latin-hypercube candidates,
-    evaluates the knowledge gradient of each against the whole set in ONE model.kg call (E = R) and takes the device's arg-max.
-    The first maximum over the restarts wins (strict '>')."""
+def _acquire_max_kg(model, lb, ub, restarts, maxeval, rng, opts=None):
+    """KnowledgeGradient.  Every restart takes `maxeval` Latin-hypercube candidates, evaluates the knowledge gradient of each against
+    the whole set in ONE model.kg call (E = R) and takes the device's arg-max.  The first maximum over the restarts wins (strict
+    '>').  "refine": n > 0 (default 0: the calls and draws above, nothing more): the restart's set becomes the discretisation
+    (model.kg_set_points) and its n best candidates start ONE batched L-BFGS ascent inside the box, fg = one model.kg_grad call per
+    step (include/bohip_kg_grad.h); an ascended point replaces the maximum only where it is strictly better."""
     if not hasattr(model, "kg"):
         raise NotImplementedError(f"{type(model).__name__} has no kg")
+    opts = opts or {}
+    refine = int(opts.get("refine", 0) or 0)
+    if refine > 0 and not hasattr(model, "kg_grad"):
+        raise NotImplementedError(f"{type(model).__name__} has no kg_grad")
+    from . import _lib
+
+    if refine > 0 and max(maxeval, 1) + 1 > _lib.KG_RMAX:
+        raise ValueError(f"'refine' needs maxeval + 1 <= {_lib.KG_RMAX} (BOHIP_KG_RMAX): the candidate set and the point itself are one point's lines")
     maxf, maxx = -math.inf, lb.copy()
-    for _ in range(restarts):
-        xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
-        res = model.kg(xs)
-        if res.best_idx >= 0 and res.best_val > maxf:             # :62 strict '>'
-            maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+    try:
+        for _ in range(restarts):
+            xs = latin_hypercube_sampling(lb, ub, max(maxeval, 1), rng)
+            res = model.kg(xs)
+            if res.best_idx >= 0 and res.best_val > maxf:         # :62 strict '>'
+                maxf, maxx = float(res.best_val), xs[:, int(res.best_idx)].copy()
+            if refine > 0 and res.best_idx >= 0:
+                f = np.asarray(res.values, dtype=np.float64)
+                order = [j for j in np.argsort(-np.where(np.isnan(f), -math.inf, f), kind="stable")[:refine] if np.isfinite(f[j])]
+                model.kg_set_points(xs)
+
+                def fg(Z):
+                    r, g = model.kg_grad(Z)
+                    return np.asarray(r.values, dtype=np.float64), np.asarray(g, dtype=np.float64)
+
+                fa, Xa = _batched_lbfgs_ascent(fg, np.asfortranarray(xs[:, order]), lb, ub, max(2, maxeval),
+                                               ftol_rel=float(opts.get("ftol_rel", 1e-10)), xtol_abs=float(opts.get("xtol_abs", 1e-10)),
+                                               ftol_abs=float(opts.get("ftol_abs", 0.0)), xtol_rel=float(opts.get("xtol_rel", 0.0)),
+                                               stopval=float(opts.get("stopval", math.inf)))
+                j = int(np.argmax(np.where(np.isnan(fa), -math.inf, fa)))
+                if fa[j] > maxf:                                  # strict '>': never worse than the candidate maximum
+                    maxf, maxx = float(fa[j]), Xa[:, j].copy()
+    finally:
+        if refine > 0:
+            model.kg_set_points(None)                             # (also where the ascent raised: nothing stays resident)
     if not np.isfinite(maxf):
         warnings.warn("acquisition returned no finite value; keeping the lower bounds as maximiser")
     return maxf, maxx
@@ -889,8 +921,8 @@ def acquire_max(a, model, lowerbounds, upperbounds, options, rng=None, setparams
     maxf, maxx = -math.inf, lb.copy()                             # :55-56
     if model.nobs == 0 or restarts <= 0:
         return maxf, maxx
-    if isinstance(a, KnowledgeGradient):                          # (`method` has nothing to select between: accepted, not used)
-        return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng)
+    if isinstance(a, KnowledgeGradient):                          # (`method` is accepted, not used; "refine" adds the ascent)
+        return _acquire_max_kg(model, lb, ub, restarts, maxeval, rng, opts)
     if isinstance(a, MaxValueEntropySearch):                      # (`method` is accepted, not used)
         return _acquire_max_mes(a, model, lb, ub, restarts, maxeval, rng)
     if isinstance(a, NoisyExpectedImprovement):                   # (`method` is accepted, not used; "refine" adds the ascent)

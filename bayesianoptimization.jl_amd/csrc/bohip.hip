@@ -22,6 +22,7 @@
 #include "../../include/bohip_qei.h"
 #include "../../include/bohip_acq.h"
 #include "../../include/bohip_kg.h"
+#include "../../include/bohip_kg_grad.h"
 #include "../../include/bohip_mes.h"
 #include "../../include/bohip_ens.h"
 #include "../../include/bohip_ens_grad.h"
@@ -57,6 +58,7 @@
 #include "kernels_nei_grad.hip"   // (after kernels_nei.hip and kernels_con.hip: NeiReduce; grad_finish_waves, GC)
 #include "kernels_pend_grad.hip"  // (after kernels_pend.hip and kernels_nei_grad.hip: PEND_ZCAP; k_nei_mix and k_nei_grad_finish are launched as they stand)
 #include "kernels_qei_joint.hip"  // (after kernels_pend_grad.hip: pend_fx; the finish is k_nei_grad_finish as it stands)
+#include "kernels_kg_grad.hip"    // (after kernels_kg.hip and kernels_nei_grad.hip: the march's pieces; grad_finish_waves, GC)
 #include "kernels_fit.hip"     // (after the linear algebra: cov_from_r)
 #include "kernels_ens.hip"     // (after the fit and the scoring kernels: the fit's panels and tasks, acq_eval and the arg-max order)
 #include "kernels_small.hip"   // (after the ascent: k_small_u's last workgroup runs its step, asc_step_one<true>)
@@ -259,6 +261,14 @@ struct bohip_gp : gp_streams {
     DBuf<char> qei_ws;
     // knowledge gradient (bohip_gp_kg / bohip_kg_lines): ONE block [kg | record | nseg | a | B], the last two for the caller's lines only
     DBuf<char> kg_ws;
+    // ... at free points (include/bohip_kg_grad.h): the discretisation as the caller gave it (host), what is derived from
+    // it and the model lazily -- [A | mu_A] (layout::kg_points) and V' of A, [rows][ld] as k_trigemm_sq stores it -- valid while kg_key
+    // equals what it was computed from; plus the block of one call (layout::kg_grad_call) and where its last block of line rows lies
+    std::vector<double> hkgA;
+    int64_t kg_R = 0, kg_rebuilds = 0, kg_last_rows = 0;
+    DBuf<char> kg_pts, kgg_ws;
+    DBuf<double> kg_VA;
+    const double* kg_last_C = nullptr;
     // max-value entropy search (bohip_gp_mes / bohip_mes_values / bohip_mes_gumbel): ONE block, see ensure_mes
     DBuf<char> mes_ws;
     // constrained scoring (bohip_gp_score_con / bohip_con_values / bohip_gp_predict_grad): ONE block on the objective's handle, see
@@ -303,6 +313,7 @@ struct bohip_gp : gp_streams {
     PendKey pend_bt_key;
     DBuf<double> dPV;
     DBuf<char> pend_state, pend_call;
+    PendKey kg_key;   // (the knowledge gradient's points above: the same counters, pend_gen left at 0)
     // joint q-EI (include/bohip_qei_joint.h): the block of one call (layout::qei_joint)
     DBuf<char> qeij_ws;
     // noisy expected improvement (include/bohip_nei.h): the COMPANION -- a handle of its own for the same X under the same
@@ -3633,6 +3644,209 @@ int bohip_kg_lines(bohip_gp* g, const double* a, const double* B, int64_t R, int
     HIPCHK(hipStreamSynchronize(g->stream));
     t_collect(g);
     return 0;
+}
+
+// ---- the knowledge gradient at free points and its gradient (kernels_kg_grad.hip, include/bohip_kg_grad.h) ---------
+static bohip_gp::PendKey kg_key_now(const bohip_gp* g) {
+    bohip_gp::PendKey k;
+    k.n = g->n; k.ld = g->ld; k.refits = g->refits; k.appends = g->appends; k.hyper_gen = g->hyper_gen; k.jitter = g->jitter_last;
+    return k;
+}
+static int kg_grad_setup() {   // the dynamic LDS of the march and of the cross product, once per device
+    static bool done[64] = {false};
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    return once_per_device(done, dev, [] {
+        HIPCHK(hipFuncSetAttribute((const void*)k_kg_march_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kg_lds_bytes(KG_RMAX)));
+        HIPCHK(hipFuncSetAttribute((const void*)k_kg_cross<true>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+        HIPCHK(hipFuncSetAttribute((const void*)k_kg_cross<false>, hipFuncAttributeMaxDynamicSharedMemorySize, glds3_lds_bytes<4>()));
+        return 0;
+    });
+}
+static int64_t kg_va_rows(int64_t R) { return round_up(R + 1, TILE) + TILE; }   // column R's tile, and a tile of head-room for tile-granular stores
+// The derived state up to date (the model is fresh, the set is not empty): one posterior pass over A that stores V'_A straight into its
+// resident buffer -- chunk by chunk, so R is not bound to one chunk, and without the R x R product posterior_vv would add -- and mu_A
+// from its alpha row.  Nothing runs while kg_key stands.
+static int kg_points_ready(bohip_gp* g, layout::KgPoints* out) {
+    const int64_t R = g->kg_R;
+    const size_t va = (size_t)kg_va_rows(R) * g->ld;
+    bool grew = false;
+    HIPCHK(g->kg_pts.reserve(layout::kg_points(nullptr, (size_t)R, (size_t)g->d, out), g->stream, Grow::Exact, &grew));
+    HIPCHK(g->kg_VA.reserve(va, g->stream, Grow::Exact, &grew));
+    if (grew) g->kg_key = bohip_gp::PendKey{};   // (the contents went with the old block)
+    layout::kg_points(g->kg_pts, (size_t)R, (size_t)g->d, out);
+    const bohip_gp::PendKey now = kg_key_now(g);
+    if (g->kg_key == now) return 0;
+    g->kg_key = bohip_gp::PendKey{};
+    CHK(ensure_score_scratch(g, R));
+    CHK(one_time_kernel_setup());
+    HIPCHK(hipMemsetAsync(g->kg_VA, 0, va * 8, g->stream));   // padding columns (>= N) and rows (>= R) start at zero
+    HIPCHK(hipMemcpyAsync(out->XA, g->hkgA.data(), (size_t)R * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const PassPlan pl = choose_route(g, R, WHOLE_K_ONLY);
+    const KernelHyper hp = make_hyper(g);
+    const int64_t chunks = chunk_pass(g, pl, out->XA, hp, ChunkV{g->kg_VA, g->ld}, false, FuseParams{}, no_finish);
+    if (chunks < 0) return (int)chunks;
+    t_begin(g, "kg_points");
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    hipLaunchKernelGGL(k_score, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, g->stream, g->dq, pl.dm.Rpad, pl.dq_tiles(), g->dmu_raw, R,
+                       hp.sigma2, g->beta, mm, out->muA, (double*)nullptr, (double*)nullptr, (Best*)nullptr);
+    HIPCHK(hipGetLastError());
+    t_end(g);
+    g->kg_key = now;
+    ++g->kg_rebuilds;
+    return 0;
+}
+extern "C++" {
+template <int DT>
+static void launch_kg_grad_finish(bohip_gp* g, int64_t r0, int64_t r1, const KernelHyper& hp, const KgFinish& f, int S) {
+    if constexpr (DT <= 16) {   // large batches: GC points per workgroup share the observation stream (launch_grad's rule)
+        if (r1 - r0 > SMALL_MAX) {
+            LAUNCH_FAM(fam_low(hp), (k_kg_grad_finish_tiled<DT, true>), (k_kg_grad_finish_tiled<DT, false>),
+                       dim3((unsigned)((r1 - r0 + GC - 1) / GC)), dim3(256), 0, g->stream, g->dX.get(), g->n, g->dXs.get(), r0, r1, hp, f,
+                       g->dgrad.get());
+            return;
+        }
+    }
+    LAUNCH_FAM(fam_low(hp), (k_kg_grad_finish<DT, true>), (k_kg_grad_finish<DT, false>), dim3((unsigned)(r1 - r0), (unsigned)S), dim3(256), 0,
+               g->stream, g->dX.get(), g->n, g->dXs.get(), r0, r1, hp, f, g->dgrad.get(), g->dgparts.get(), g->dgcount.get());
+}
+}  // extern "C++"
+
+int bohip_gp_kg_set_points(bohip_gp* g, const double* A, int64_t R) {
+    if (!g || R < 0 || (R > 0 && !A)) return fail(BOHIP_E_ARG, "kg_set_points: bad arguments");
+    if (R + 1 > BOHIP_KG_RMAX)
+        return fail(BOHIP_E_UNSUPPORTED, "kg_set_points: R + 1 exceeds BOHIP_KG_RMAX (" + std::to_string(BOHIP_KG_RMAX) +
+                                             "): a point's lines live in one workgroup's LDS");
+    HIPCHK(hipSetDevice(g->device));
+    g->kg_key = bohip_gp::PendKey{};
+    g->kg_last_rows = 0;
+    g->kg_last_C = nullptr;
+    g->kg_R = R;
+    if (R == 0) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        g->hkgA.clear();
+        g->kg_pts.release(); g->kgg_ws.release(); g->kg_VA.release();
+        return 0;
+    }
+    g->hkgA.assign(A, A + (size_t)R * g->d);
+    return 0;
+}
+
+int bohip_gp_kg_grad(bohip_gp* g, const double* Xe, int64_t E, double* kg, double* grad, int32_t* nseg, double* mu, double* var,
+                     bohip_best* best) {
+    if (!g || !Xe || !kg || !grad) return fail(BOHIP_E_ARG, "kg_grad: null argument");
+    if (E < 1) return fail(BOHIP_E_ARG, "kg_grad: E must be at least 1");
+    if (g->n == 0) return fail(BOHIP_E_STATE, "model has no observations");
+    if (g->kg_R == 0) return fail(BOHIP_E_STATE, "kg_grad: no points (bohip_gp_kg_set_points first)");
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    CHK(ensure_fresh(g));
+    layout::KgPoints pts;
+    CHK(kg_points_ready(g, &pts));
+    CHK(ensure_xs(g, E));
+    CHK(ensure_score_scratch(g, E));
+    CHK(one_time_kernel_setup());
+    CHK(kg_grad_setup());
+    const PassPlan pl = choose_route(g, E, WHOLE_K_ONLY);   // the route that stores V'
+    CHK(ensure_grad_scratch(g));
+    HIPCHK(g->dgrad.reserve((size_t)E * g->d, g->stream));
+    const int64_t R = g->kg_R, ldc = round_up(R + 1, 2), ld = g->ld;
+    const int64_t crows = round_up(std::min(E, pl.chunk), TILE);
+    // a chunk's points go through in blocks whose line rows and strips (20 bytes a line) stay within 256 MB
+    const int64_t brows = std::min(crows, std::max<int64_t>(TILE, ((int64_t)256 << 20) / (20 * ldc) / TILE * TILE));
+    layout::KgGradCall<Best> w;
+    auto lay = [&](const void* base) { return layout::kg_grad_call(base, (size_t)E, (size_t)brows, (size_t)ldc, (size_t)R, &w); };
+    HIPCHK(g->kgg_ws.reserve(lay(nullptr), g->stream));
+    lay(g->kgg_ws);
+    g->kg_last_rows = 0;
+    HIPCHK(hipMemcpyAsync(g->dXs, Xe, (size_t)E * g->d * 8, hipMemcpyHostToDevice, g->stream));
+    const KernelHyper hp = make_hyper(g);
+    const AcqParams mm{BOHIP_ACQ_MAXMEAN, 0.0, 0.0};
+    const double nu = std::exp(2.0 * g->lognoise) + std::numeric_limits<double>::epsilon() + g->jitter_last;   // as on cK's diagonal
+    // per K*' chunk (V' of its points in dVT, chunk-local): mu and sigma^2, then block by block the line rows, the march with the mix
+    // row over V' in place, U' = (the mix rows) W -- the pass's own product on these rows -- and the contraction with dk/dx
+    auto finish = [&](int64_t r0, int64_t r1) {
+        hipLaunchKernelGGL(k_score, dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, g->stream, g->dq.get() + r0, pl.dm.Rpad, pl.dq_tiles(),
+                           g->dmu_raw.get() + r0, r1 - r0, hp.sigma2, g->beta, mm, g->dmu.get() + r0, g->dvar.get() + r0, (double*)nullptr,
+                           (Best*)nullptr);
+        HIPCHK(hipGetLastError());
+        for (int64_t b0 = r0; b0 < r1; b0 += brows) {
+            const int64_t b1 = std::min(r1, b0 + brows), rows = b1 - b0;
+            double* VX = g->dVT + (b0 - r0) * ld;
+            KgCross kc{};
+            kc.VA = g->kg_VA; kc.VX = VX; kc.XA = pts.XA; kc.Xe = g->dXs.get() + b0 * g->d; kc.var = g->dvar.get() + b0; kc.C = w.C;
+            kc.ld = ld; kc.ldc = ldc; kc.R = (int)R; kc.rows = (int)rows;
+            kc.mt = (int)((R + 1 + TILE - 1) / TILE); kc.nt = (int)((rows + CTILE - 1) / CTILE); kc.kc = (int)(pl.dm.Npad / KC);
+            t_begin(g, "kg_cross");
+            LAUNCH_FAM(fam_low(hp), k_kg_cross<true>, k_kg_cross<false>, dim3((unsigned)(kc.mt * kc.nt)), dim3(GEMM_THREADS_8), glds3_lds_bytes<4>(),
+                       g->stream, kc, hp);
+            HIPCHK(hipGetLastError());
+            t_end(g);
+            KgMarchW mw{};
+            mw.muA = pts.muA; mw.C = w.C; mw.mu = g->dmu.get() + b0; mw.VA = g->kg_VA; mw.VX = VX; mw.kg = w.kg + b0; mw.nseg = w.nseg + b0;
+            mw.cmu = w.cmu; mw.lidx = w.lidx; mw.lw = w.lw; mw.nline = w.nline; mw.ld = ld; mw.ldc = ldc; mw.ldl = R; mw.N = g->n;
+            mw.R = (int)R; mw.nu = nu;
+            t_begin(g, "kg_march_w");
+            hipLaunchKernelGGL(k_kg_march_w, dim3((unsigned)rows), dim3(KG_THREADS), kg_lds_bytes(R + 1), g->stream, mw);
+            HIPCHK(hipGetLastError());
+            t_end(g);
+            GemmNTParams u{};   // launch_gemm_u on the block's row tiles
+            u.A = VX; u.lda = ld; u.B = g->dWT; u.ldb = ld; u.C = g->dUT + (b0 - r0) * ld; u.ldc = ld;
+            u.mt = (int)((rows + TILE - 1) / TILE); u.nt64 = 2 * pl.dm.T; u.kc = pl.dm.T * (TILE / KC); u.alpha = 1.0; u.beta = 0.0; u.klo_from_n = 1;
+            t_begin(g, "kg_mix");
+            CHK(launch_gemm_nt(g, u));
+            t_end(g);
+            KgFinish f{};
+            f.E = u.C; f.alpha = g->dalpha; f.cmu = w.cmu; f.XA = pts.XA; f.lidx = w.lidx; f.lw = w.lw; f.nline = w.nline; f.lde = ld; f.ldl = R;
+            int Sx = 1;
+            CHK(grad_obs_splits(g, b0, b1, &Sx));
+            t_begin(g, "kg_grad_finish");
+            dispatch_dt(g->d, [&](auto dt) { launch_kg_grad_finish<decltype(dt)::value>(g, b0, b1, hp, f, Sx); });
+            HIPCHK(hipGetLastError());
+            t_end(g);
+            g->kg_last_rows = rows;
+            g->kg_last_C = w.C;
+        }
+        return 0;
+    };
+    const int64_t chunks = chunk_pass(g, pl, g->dXs, hp, ChunkV{g->dVT, 0}, false, FuseParams{}, finish);
+    if (chunks < 0) return (int)chunks;
+    g->score_launches = chunks;
+    if (best) {
+        hipLaunchKernelGGL(k_kg_best, dim3(1), dim3(256), 0, g->stream, w.kg, (int)E, w.best);
+        HIPCHK(hipGetLastError());
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "nseg crosses as int32_t");
+    HIPCHK(hipMemcpyAsync(kg, w.kg, (size_t)E * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(grad, g->dgrad, (size_t)E * g->d * 8, hipMemcpyDeviceToHost, g->stream));
+    if (nseg) HIPCHK(hipMemcpyAsync(nseg, w.nseg, (size_t)E * 4, hipMemcpyDeviceToHost, g->stream));
+    if (mu) HIPCHK(hipMemcpyAsync(mu, g->dmu, (size_t)E * 8, hipMemcpyDeviceToHost, g->stream));
+    if (var) HIPCHK(hipMemcpyAsync(var, g->dvar, (size_t)E * 8, hipMemcpyDeviceToHost, g->stream));
+    if (best) HIPCHK(hipMemcpyAsync(best, w.best, sizeof(Best), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_kg_points_info(bohip_gp* g, int what, double* value, int64_t cap) {
+    if (!g || !value || cap < 1) return fail(BOHIP_E_ARG, "kg_points_info: bad arguments");
+    switch (what) {
+        case BOHIP_KG_POINTS_R: *value = (double)g->kg_R; return 0;
+        case BOHIP_KG_POINTS_REBUILDS: *value = (double)g->kg_rebuilds; return 0;
+        case BOHIP_KG_POINTS_BYTES: *value = (double)(g->kg_pts.capacity() + g->kgg_ws.capacity() + 8 * g->kg_VA.capacity()); return 0;
+        case BOHIP_KG_POINTS_LINE_ROWS: *value = (double)g->kg_last_rows; return 0;
+        case BOHIP_KG_POINTS_LINES: {
+            const int64_t R = g->kg_R, rows = g->kg_last_rows, ldc = round_up(R + 1, 2);
+            if (rows == 0 || !g->kg_last_C) return fail(BOHIP_E_STATE, "kg_points_info: no call of bohip_gp_kg_grad has left its lines");
+            if (cap < rows * (R + 1)) return fail(BOHIP_E_ARG, "kg_points_info: value holds fewer than rows x (R + 1) doubles");
+            HIPCHK(hipSetDevice(g->device));
+            HIPCHK(hipMemcpy2DAsync(value, (size_t)(R + 1) * 8, g->kg_last_C, (size_t)ldc * 8, (size_t)(R + 1) * 8, (size_t)rows,
+                                    hipMemcpyDeviceToHost, g->stream));
+            HIPCHK(hipStreamSynchronize(g->stream));
+            return 0;
+        }
+        default: return fail(BOHIP_E_ARG, "kg_points_info: unknown info id");
+    }
 }
 
 // ---- max-value entropy search over a candidate set (kernels_mes.hip, include/bohip_mes.h) --------------------------

@@ -274,6 +274,29 @@ size_t nei_grad_call(const void* base, size_t n_mt, size_t R, size_t rows, size_
 inline double* nei_alpha_t(const NeiState& st, size_t rows, size_t ld, size_t Npad, size_t Sp) {
     return Npad * Sp <= rows * ld ? st.w0 : nullptr;
 }
+// knowledge gradient at free points (include/bohip_kg_grad.h): what is derived from the discretisation and the model, [A R x d | mu_A R]
+// (V' of A is a buffer of its own: its rows are the operand of an LDS-DMA), and the block of one call: [kg E | record | nseg E |
+// C rows x ldc (16-byte rows: the march's loads) | c_mu rows | lines' weights rows x ldl | lines rows x ldl | line counts rows]
+struct KgPoints { double *XA, *muA; };
+inline size_t kg_points(const void* base, size_t R, size_t d, KgPoints* w) {
+    Carve c(base);
+    w->XA = c.take<double>(R * d);
+    w->muA = c.take<double>(R, 16);
+    return c.total();
+}
+template <class Rec>
+struct KgGradCall { double *kg, *C, *cmu, *lw; int *nseg, *lidx, *nline; Rec* best; };
+template <class Rec>
+size_t kg_grad_call(const void* base, size_t E, size_t rows, size_t ldc, size_t ldl, KgGradCall<Rec>* w) {
+    Carve c(base);
+    w->kg = c.take<double>(E);
+    w->best = c.take<Rec>(1, REC_ALIGN);
+    w->nseg = c.take<int>(E);
+    w->C = c.take<double>(rows * ldc, 16);
+    w->cmu = c.take<double>(rows); w->lw = c.take<double>(rows * ldl);
+    w->lidx = c.take<int>(rows * ldl); w->nline = c.take<int>(rows);
+    return c.total();
+}
 // the pinned, device-visible result block of a small call (up to n_small candidates of up to dmax coordinates), in doubles:
 // [score | mu | var (n_small each) | record: one arg-max record = four 32-bit words | gradient n_small x dmax | candidates n_small x dmax].
 // Every caller synchronises before it returns, so the areas are free at the next call, and three callers borrow them on purpose: the

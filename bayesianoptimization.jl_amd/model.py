@@ -719,6 +719,28 @@ class ElasticGPE:
         row.  The model supplies the device and the stream only.  Returns (values[E], nseg[E] int32)."""
         return _kg_lines(self._lib, self._h, a, B)
 
+    def kg_set_points(self, xs):
+        """The discretisation of kg_grad (bohip_gp_kg_set_points, include/bohip_kg_grad.h): the columns of xs are kept
+        on the handle; None or zero columns release them.  Nothing runs on the device until the next kg_grad."""
+        _kg_set_points(self._lib, self._h, None if xs is None else _cols(xs, self.dim))
+        return self
+
+    def kg_grad(self, xe):
+        """The knowledge gradient of the columns of xe -- points anywhere -- over the discretisation of kg_set_points and the point
+        itself, and its gradient in the point (bohip_gp_kg_grad; Scott, Frazier & Powell 2011): returns (KGResult, grad [d, E]); the
+        result's mu is the points' own posterior mean and it carries their variance as .var.  KG is a function of the point alone:
+        what an L-BFGS ascent climbs.  The model is not changed."""
+        return _kg_grad(self._lib, self._h, _cols(xe, self.dim))
+
+    def kg_points_info(self):
+        """{"R", "rebuilds", "bytes"} of the resident discretisation (bohip_gp_kg_points_info)."""
+        return _kg_points_info(self._lib, self._h)
+
+    def kg_last_lines(self):
+        """[rows, R + 1]: the rows the last kg_grad's march read (Sigma(a_j, x) for j < R, then sigma^2(x)), of its last block only.
+        A diagnostic hook for the tests (BOHIP_KG_POINTS_LINES), not stable interface."""
+        return _kg_last_lines(self._lib, self._h)
+
     def mes(self, xs, samples=16, mode="gumbel", seed=0, floor=None, jitter_rel=1e-12, max_tries=40):
         """Max-value entropy search over the candidate set xs on the device (bohip_gp_mes, include/bohip_mes.h; an extension; Wang &
         Jegelka 2017): MES_j = mean_k u(mu_j, s2_j, m_k) over `samples` draws m_k of the maximum of the posterior over the
@@ -1142,10 +1164,11 @@ class KGResult:
     """Result of kg: values[E] (the knowledge gradient of every evaluation point, >= 0), nseg[E] (int32: segments of the upper
     envelope beyond the first), mu[R] (the latent posterior mean of the candidates), best_val / best_idx (the arg-max over the
     evaluation points under score's rule: first maximum, NaN never wins, -Inf / -1 if nothing can win)."""
-    __slots__ = ("values", "nseg", "mu", "best_val", "best_idx")
+    __slots__ = ("values", "nseg", "mu", "best_val", "best_idx", "var")
 
     def __init__(self, values, nseg, mu, best_val, best_idx):
         self.values, self.nseg, self.mu, self.best_val, self.best_idx = values, nseg, mu, best_val, best_idx
+        self.var = None   # kg_grad alone: the points' own posterior variance
 
     def __iter__(self):
         return iter((self.values, self.nseg, self.mu, self.best_val, self.best_idx))
@@ -1172,6 +1195,41 @@ def _kg_lines(lib, handle, a, B):
     nseg = np.zeros(max(E, 1), dtype=np.int32)
     check(lib.bohip_kg_lines(handle, _ptr(a), _ptr(B), a.size, E, _ptr(values), nseg.ctypes.data_as(C.POINTER(C.c_int32))))
     return values, nseg
+
+
+def _kg_set_points(lib, handle, xs):
+    R = 0 if xs is None else xs.shape[1]
+    check(lib.bohip_gp_kg_set_points(handle, _ptr(xs) if R else None, R))
+
+
+def _kg_grad(lib, handle, xe):
+    E = xe.shape[1]
+    values, mu, var = np.zeros(max(E, 1)), np.empty(max(E, 1)), np.empty(max(E, 1))
+    nseg = np.zeros(max(E, 1), dtype=np.int32)
+    g = np.empty((xe.shape[0], E), order="F")
+    best = Best()
+    check(lib.bohip_gp_kg_grad(handle, _ptr(xe), E, _ptr(values), _ptr(g), nseg.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(mu), _ptr(var),
+                               C.byref(best)))
+    res = KGResult(values, nseg, mu, best.val, best.idx)
+    res.var = var
+    return res, g
+
+
+def _kg_points_info(lib, handle):
+    out = {}
+    for key, what in (("R", _lib.KG_POINTS_R), ("rebuilds", _lib.KG_POINTS_REBUILDS), ("bytes", _lib.KG_POINTS_BYTES)):
+        v = C.c_double(0.0)
+        check(lib.bohip_gp_kg_points_info(handle, what, C.byref(v), 1))
+        out[key] = int(v.value)
+    return out
+
+
+def _kg_last_lines(lib, handle):
+    R, v = _kg_points_info(lib, handle)["R"], C.c_double(0.0)
+    check(lib.bohip_gp_kg_points_info(handle, _lib.KG_POINTS_LINE_ROWS, C.byref(v), 1))
+    buf = np.empty((int(v.value), R + 1))
+    check(lib.bohip_gp_kg_points_info(handle, _lib.KG_POINTS_LINES, _ptr(buf), buf.size))
+    return buf
 
 
 class MESResult:

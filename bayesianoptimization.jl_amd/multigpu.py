@@ -229,6 +229,19 @@ class MultiGPE:
 
         return _kg(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(xs, self.dim), n_eval)
 
+    def kg_set_points(self, xs):
+        """ElasticGPE.kg_set_points (bohip_gp_kg_set_points) on the FIRST replica, as kg."""
+        from .model import _kg_set_points
+
+        _kg_set_points(self._lib, self._lib.bohip_mgp_handle(self._h, 0), None if xs is None else _cols(xs, self.dim))
+        return self
+
+    def kg_grad(self, xe):
+        """ElasticGPE.kg_grad (bohip_gp_kg_grad) on the FIRST replica, as kg."""
+        from .model import _kg_grad
+
+        return _kg_grad(self._lib, self._lib.bohip_mgp_handle(self._h, 0), _cols(xe, self.dim))
+
     def kg_lines(self, a, B):
         """ElasticGPE.kg_lines (bohip_kg_lines) on the FIRST replica."""
         from .model import _kg_lines

@@ -350,6 +350,7 @@ include("BOHipQEI.jl")     # greedy Monte-Carlo q-EI over joint draws (include/b
 include("BOHipQEIJoint.jl") # the joint q-EI of B batches and its gradient (include/bohip_qei_joint.h): c_gp_qei_joint
 include("BOHipAcq.jl")     # LogEI and the functors on their own (include/bohip_acq.h): LogExpectedImprovement, acq_eval
 include("BOHipKG.jl")      # the knowledge gradient over a candidate set (include/bohip_kg.h): kg, kg_lines, KnowledgeGradient
+include("BOHipKGGrad.jl")  # ... at free points, with its gradient (include/bohip_kg_grad.h): c_gp_kg_set_points, c_gp_kg_points_info, c_gp_kg_grad
 include("BOHipEns.jl")     # an acquisition averaged over hyper-parameter settings (include/bohip_ens.h): score_ensemble
 include("BOHipEnsGrad.jl") # its gradient (include/bohip_ens_grad.h): score_ensemble_grad
 include("BOHipMES.jl")     # max-value entropy search over a candidate set (include/bohip_mes.h): mes, mes_values, mes_gumbel, MaxValueEntropySearch
