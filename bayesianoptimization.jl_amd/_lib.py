@@ -274,6 +274,15 @@ QEI_JOINT_SIGNATURES = {
     "bohip_gp_qei_joint": (C.c_int, [_gp, _dp, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_double, _dp, _dp, _dp, _i64p]),
 }
 
+# every symbol include/bohip_qehvi.h declares (greedy Monte-Carlo q-EHVI for two objectives over joint draws that stay on the device)
+QEHVI_QMAX = 16
+QEHVI_SEED_XOR = 0x9E3779B97F4A7C15
+QEHVI_SIGNATURES = {
+    "bohip_mo_qehvi_select": (C.c_int, [_gp, _dp, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, C.c_int64, _i64p, _dp]),
+    "bohip_gp_qehvi_batch": (C.c_int, [_gp, _gp, _dp, C.c_int64, _dp, _dp, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_int, C.c_int64,
+                                       _i64p, _dp, _dp, _dp, _ip]),
+}
+
 _lib = None
 
 # Live device objects are closed at interpreter exit BEFORE the HIP / RCCL runtimes run their own static destructors:
@@ -335,7 +344,7 @@ def load():
                               + list(LOO_BATCH_SIGNATURES.items()) + list(REP_SIGNATURES.items()) + list(PEND_SIGNATURES.items())
                               + list(NEI_SIGNATURES.items()) + list(MOM_SIGNATURES.items()) + list(NEI_GRAD_SIGNATURES.items())
                               + list(PEND_GRAD_SIGNATURES.items()) + list(QEI_JOINT_SIGNATURES.items())
-                              + list(KG_GRAD_SIGNATURES.items())):
+                              + list(KG_GRAD_SIGNATURES.items()) + list(QEHVI_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -15,7 +15,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .model import ElasticGPE, dims, maxy, mean_var, myrand
+from .model import ElasticGPE, ManyObjectiveGPE, dims, maxy, mean_var, myrand
 from .utils import latin_hypercube_sampling, normal_cdf, normal_pdf
 
 
@@ -1090,7 +1090,7 @@ def acquire_max_pending(a, model, lowerbounds, upperbounds, options, rng=None, s
 
 _BATCH_OPTS = {"candidates", "xs", "fantasy", "raise_tau", "method", "draws", "pathwise", "features", "refine"}
 _BATCH_FANTASIES = ("believer", "liar_max", "liar_min", "liar_mean")
-_BATCH_METHODS = ("fantasy", "qei")
+_BATCH_METHODS = ("fantasy", "qei", "qehvi")
 
 
 def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None, setparams=True):
@@ -1114,6 +1114,11 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
           one seed drawn from `rng` for the climb; include/bohip_qei_joint.h).  A batch whose covariance does not
           factor has the value -Inf and the ascent backtracks from it.  The end point with the largest value wins, the first on
           ties: never below the greedy batch's value under the climb's seed.  Returns ([value], X d x q) then.
+      "qehvi"  two objectives: greedy Monte-Carlo q-EHVI over "draws" (default 256) joint posterior draws of each member of a
+          MultiObjectiveGPE that stay on the device (model.qehvi_batch; seed from `rng`; include/bohip_qehvi.h).  The
+          acquisition must be ExpectedHypervolumeImprovement; the front and the reference point are the model's.  It takes
+          "draws" and "candidates" or "xs" only.  The values returned are the picks' marginal gains; their sum is the batch's
+          q-EHVI estimate.
     Returns (values[q'], X d x q') with q' <= q: picks that could not win (no finite score / no gain left) are dropped."""
     lb = np.asarray(lowerbounds, dtype=np.float64)
     ub = np.asarray(upperbounds, dtype=np.float64)
@@ -1130,7 +1135,24 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
     if method not in _BATCH_METHODS:
         raise ValueError(f"batch method must be one of {_BATCH_METHODS}, got {method!r}")
     qei = method == "qei"
-    if qei:
+    qehvi = method == "qehvi"
+    if qehvi:
+        for k in ("fantasy", "raise_tau", "pathwise", "features", "refine"):
+            if k in opts:
+                raise ValueError(f"batch option {k!r} does not go with method 'qehvi': its draws are joint, come from the two "
+                                 "members' posteriors and the batch stays on the candidate set")
+        if not isinstance(a, ExpectedHypervolumeImprovement):
+            raise ValueError("batch method 'qehvi' is the batch form of the expected hypervolume improvement and needs an "
+                             f"ExpectedHypervolumeImprovement acquisition, got {type(a).__name__}")
+        _need_mo(model)
+        if len(model.objectives) != 2 or isinstance(model, ManyObjectiveGPE):
+            raise ValueError("batch method 'qehvi' is built for two objectives only: a MultiObjectiveGPE, not a "
+                             f"{type(model).__name__}")
+        draws = int(opts.get("draws", 256))
+        if draws < 1:
+            raise ValueError(f"options['draws'] = {draws} < 1")
+        need = ("qehvi_batch",)
+    elif qei:
         if "fantasy" in opts or "raise_tau" in opts:
             raise ValueError("batch options 'fantasy' and 'raise_tau' belong to method 'fantasy': q-EI conditions on no fantasy, "
                              "its draws are joint")
@@ -1177,6 +1199,13 @@ def acquire_batch(a, model, lowerbounds, upperbounds, q, options=None, rng=None,
         raise RuntimeError("acquire_batch on an empty model")
     if setparams:
         setparams_(a, model)
+    if qehvi:
+        seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
+        res = model.qehvi_batch(xs, q, draws, seed)
+        keep = res.idx >= 0
+        if not keep.all():
+            warnings.warn(f"acquire_batch: only {int(keep.sum())} of {q} picks had a gain above zero")
+        return res.gain[keep], np.asfortranarray(xs[:, res.idx[keep]])
     if qei:
         seed = int((rng or np.random.default_rng()).integers(0, 2 ** 63 - 1))
         if pathwise:

@@ -12,7 +12,7 @@ import numpy as np
 from .acquisition import (AbstractAcquisition, Constrained, ExpectedHypervolumeImprovement, ExpectedImprovement, Marginalised, MaxMean, NoisyExpectedImprovement, ThompsonSamplingSimple, _batched_lbfgs_ascent,
                           acquire_batch, acquire_max, acquire_max_pending, acquire_thompson_batch, defaultoptions, setparams_)
 from ._lib import NotPositiveDefinite
-from .model import ConstrainedGPE, ElasticGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, refuse_weighted, update_
+from .model import ConstrainedGPE, ElasticGPE, ManyObjectiveGPE, Mat52Ard, MeanConst, MultiObjectiveGPE, refuse_weighted, update_
 from .utils import (DurationCounter, IterationCounter, ScaledSobolIterator, init_, isdone as _isdone, latin_hypercube_sampling, step_)
 
 
@@ -358,7 +358,8 @@ class BOpt:
         # batchsize > 1 (an extension, the reference evaluates one point per iteration): an iteration proposes `batchsize` points
         # with acquire_batch(..., batchoptions) and appends all their evaluations in ONE model update.  batchoptions["method"]:
         # "fantasy" (default; Kriging believer / constant liar) or "qei" (ExpectedImprovement only: greedy Monte-Carlo q-EI over
-        # joint posterior draws on the device)
+        # joint posterior draws on the device) or "qehvi" (a MultiObjectiveGPE with ExpectedHypervolumeImprovement only:
+        # greedy Monte-Carlo q-EHVI over joint draws of both members; without it two objectives take batchsize = 1)
         now = time.time()
         lowerbounds = np.asarray(lowerbounds, dtype=np.float64)
         upperbounds = np.asarray(upperbounds, dtype=np.float64)
@@ -385,8 +386,11 @@ class BOpt:
         if multi != isinstance(acquisition, ExpectedHypervolumeImprovement):
             raise ValueError("a MultiObjectiveGPE model goes with the ExpectedHypervolumeImprovement acquisition and the other way "
                              f"round (got {type(model).__name__} with {type(acquisition).__name__})")
-        if multi and batchsize > 1:
+        if multi and batchsize > 1 and (batchoptions or {}).get("method") != "qehvi":   # (two objectives: greedy q-EHVI)
             raise ValueError("a MultiObjectiveGPE proposes one point per iteration (batchsize = 1)")
+        if multi and batchsize > 1 and (len(model.objectives) != 2 or isinstance(model, ManyObjectiveGPE)):
+            raise ValueError("batchsize > 1 with the method 'qehvi' is built for two objectives only: a MultiObjectiveGPE, not a "
+                             f"{type(model).__name__}")
         if multi and isinstance(modeloptimizer, MarginalGPOptimizer):
             raise ValueError("MarginalGPOptimizer over a MultiObjectiveGPE is not supported: its samples have no two-objective "
                              "acquisition")
@@ -631,7 +635,7 @@ def _batch_iteration(o):
     if not xs:                                                                   # (no candidate had a finite score: acquire_batch has warned)
         return
     with _timeit(o, "model update"):
-        update_(o.model, np.stack(xs, axis=1), np.array(ys))
+        _update_model(o, xs, ys)
     with _timeit(o, "model hyperparameter optimization"):
         optimizemodel_(o.modeloptimizer, o.model)
 

@@ -37,6 +37,7 @@
 #include "../../include/bohip_nei_grad.h"
 #include "../../include/bohip_pend_grad.h"
 #include "../../include/bohip_qei_joint.h"
+#include "../../include/bohip_qehvi.h"
 #include "kernels_linalg.hip"
 #include "kernels_loo.hip"     // (after the linear algebra: KernelHyper and the family expressions of k_dmll_parts)
 #include "kernels_rep.hip"     // (replicated sites: the weighted diagonal and the weighted logNoise sum)
@@ -52,6 +53,7 @@
 #include "kernels_con.hip"     // (after the scoring kernels: their functors, arg-max order and k_grad_finish's launch bounds; acq_log.h's continued fraction)
 #include "kernels_mo.hip"      // (after the constrained kernels: their record block; the scoring kernels' arg-max order)
 #include "kernels_mom.hip"     // (after the two-objective kernel: mo_psi and its grid cap)
+#include "kernels_qehvi.hip"   // (after the two-objective kernel: MO_FRONT_MAX; the scoring kernels' arg-max order; gemm_core.h's LDS-DMA pointer types)
 #include "kernels_ascent.hip"
 #include "kernels_pend.hip"   // (after the scoring kernels: their functors, arg-max order, generator and kernel expressions)
 #include "kernels_nei.hip"    // (after the scoring kernels: their functors, arg-max order and generator; gemm_core.h's tile loop)
@@ -316,6 +318,11 @@ struct bohip_gp : gp_streams {
     PendKey kg_key;   // (the knowledge gradient's points above: the same counters, pend_gen left at 0)
     // joint q-EI (include/bohip_qei_joint.h): the block of one call (layout::qei_joint)
     DBuf<char> qeij_ws;
+    // greedy q-EHVI (include/bohip_qehvi.h): ONE block [staircases | front | lengths | partials | records | gain | idx |
+    // words] (layout::qehvi) on obj0's handle, and the second objective's S x R draws where they are not another handle's sjF (the
+    // caller's matrix of bohip_mo_qehvi_select; obj1 == obj0 in bohip_gp_qehvi_batch)
+    DBuf<char> qehvi_ws;
+    DBuf<double> qehvi_F1;
     // noisy expected improvement (include/bohip_nei.h): the COMPANION -- a handle of its own for the same X under the same
     // kernel parameters with delta on the diagonal, owned by this one, made at the first call of that header and kept in step lazily
     // (nei_jrel, nei_steps: what its diagonal was set from) -- and the fantasies [F | alpha_s | work | tau_s] (layout::nei_state), valid
@@ -532,6 +539,9 @@ static int alloc_model(bohip_gp* g, int64_t cap) {
 static int g_bulk_pieces = 4;   // gated pieces of the side-stream bulk update per outer block (BOHIP_BULK_PIECES; 0/1: one launch)
 static int g_sample_mfma_min = 200;  // BOHIP_SAMPLE_MFMA_MIN: draws from which bohip_gp_sample_joint takes k_sample_mfma instead of k_sample_rows
                                      // (measured at R = 4096: the two cross between 192 and 256 draws, kernels_sample.hip)
+static bool g_qehvi_narrow = false;  // BOHIP_QEHVI_NARROW: k_qehvi_gain walks every strip (0) or the wave's union of contributing strips (1); the same
+                                     // bytes either way.  Measured at S = 256, R = 4096, q = 8: the full walk takes 0.72 ms against 1.13 at
+                                     // n = 64 and 4.46 against 6.89 at n = 1024 (profiles/qehvi_times.txt): 64 lanes' intervals cover most strips
 static int g_path_mfma_min = 24;     // BOHIP_PATH_MFMA_MIN: paths from which bohip_paths_eval takes k_path_mfma instead of k_path_rows (read at every
                                      // bohip_gp_paths_draw and kept by the object).  The forms cross at ~130 paths at R = 4096 and at ~15 at R = 65536
                                      // (the MFMA form is flat at 1.13 ms until its grid fills the chip, the row form is linear in S); the switch is on S
@@ -651,6 +661,7 @@ static int kernel_setup_of_this_device() {
     if (const char* e = getenv("BOHIP_ASC_WG_NMAX")) g_asc_wg_nmax = std::max(0, atoi(e));
     if (const char* e = getenv("BOHIP_ASC_LOCKSTEP")) { g_asc_lockstep = atoi(e) == 1; g_asc_fold = atoi(e) != 2; }
     if (const char* e = getenv("BOHIP_SAMPLE_MFMA_MIN")) g_sample_mfma_min = std::max(1, atoi(e));
+    if (const char* e = getenv("BOHIP_QEHVI_NARROW")) g_qehvi_narrow = atoi(e) != 0;
     g_chol_df_strict = getenv("BOHIP_CHOL_DF_STRICT") != nullptr;
     read_dev_knobs();
     return 0;
@@ -4387,6 +4398,128 @@ int bohip_gp_score_mo(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64
     CHK(multi_posterior(obj0, models, 2, false, Xs, R, jac, b));
     CHK(mo_ehvi_stage(obj0, n_front, b, R, false, jac, best != nullptr));
     return multi_download(obj0, models, 2, b, R, score, grad, mu, var, best);
+}
+
+// ---- greedy Monte-Carlo q-EHVI for two objectives (kernels_qehvi.hip, include/bohip_qehvi.h) -----------------------
+static_assert(QEHVI_QMAX == BOHIP_QEHVI_QMAX && QEHVI_B == QEI_B, "the kernel's plan and the header agree; the blocking is q-EI's");
+static constexpr size_t QEHVI_MAX_BYTES = (size_t)8 << 30;   // the two S x R matrices plus the block
+
+static size_t qehvi_layout(const void* base, int64_t R, int64_t S, int64_t n, int64_t q, QehviWs* w) {
+    const size_t NB = (size_t)((S + QEHVI_B - 1) / QEHVI_B), NT = (size_t)((R + QEHVI_PICK - 1) / QEHVI_PICK);
+    w->ST = (int)(n + q + 2);
+    return layout::qehvi(base, (size_t)S, (size_t)(n + q + 2), (size_t)n, NB * (size_t)R, NT, (size_t)q, w);
+}
+// what both calls check after the front (so n_front <= BOHIP_MO_FRONT_MAX here); nothing is allocated before it
+static int qehvi_check(const char* who, int64_t R, int64_t S, int64_t n, int64_t q, const void* idx, const void* gain) {
+    const std::string pre = std::string(who) + ": ";
+    if (!idx || !gain) return fail(BOHIP_E_ARG, pre + "null argument");
+    if (R < 1 || S < 1 || q < 1) return fail(BOHIP_E_ARG, pre + "R, S and q must be at least 1");
+    if (q > R) return fail(BOHIP_E_ARG, pre + "q exceeds the number of candidates R");
+    if (q > BOHIP_QEHVI_QMAX)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "q = " + std::to_string(q) + "; at most BOHIP_QEHVI_QMAX = " + std::to_string(BOHIP_QEHVI_QMAX));
+    if (S > QEI_GRID_S)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "more than 65535 blocks of draws; the largest S is " + std::to_string(QEI_GRID_S));
+    const double rough = 16.0 * (double)S * (double)R + 16.0 * (double)S * (double)(n + q + 2);
+    QehviWs w{};
+    if (rough > (double)QEHVI_MAX_BYTES || 16 * (size_t)S * (size_t)R + qehvi_layout(nullptr, R, S, n, q, &w) > QEHVI_MAX_BYTES)
+        return fail(BOHIP_E_UNSUPPORTED, pre + "the two S x R matrices of draws and the staircases exceed the limit of 8 GiB (S = " +
+                                             std::to_string(S) + ", R = " + std::to_string(R) + ", n_front = " + std::to_string(n) + ")");
+    return 0;
+}
+static int ensure_qehvi(bohip_gp* g, int64_t R, int64_t S, int64_t n, int64_t q, const double* ref, QehviWs* w) {
+    HIPCHK(g->qehvi_ws.reserve(qehvi_layout(nullptr, R, S, n, q, w), g->stream, Grow::Half));
+    qehvi_layout(g->qehvi_ws, R, S, n, q, w);
+    w->r1 = ref[0];
+    w->r2 = ref[1];
+    return 0;
+}
+// the front up, then the 1 + 3 q launches over F0 and F1 back to back on the handle's stream, and the two small copies behind them
+// (no synchronisation).  fr: mo_make_front's c_0 .. c_{n+1}, b_1 .. b_{n+1}.
+static int qehvi_rounds(bohip_gp* g, const QehviWs& w, const std::vector<double>& fr, const double* F0, const double* F1, int64_t R, int64_t S,
+                        int64_t n, int64_t q, int64_t* idx, double* gain) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "idx crosses as int64_t");
+    HIPCHK(hipMemcpyAsync(w.front, fr.data(), fr.size() * 8, hipMemcpyHostToDevice, g->stream));
+    t_begin(g, "qehvi_init");
+    hipLaunchKernelGGL(k_qehvi_init, dim3((unsigned)((std::max(S * w.ST, q) + 255) / 256)), dim3(256), 0, g->stream, w, S, (int)n, q);
+    t_end(g);
+    const dim3 ggrid((unsigned)((R + QEHVI_COLS - 1) / QEHVI_COLS), (unsigned)((S + QEHVI_B - 1) / QEHVI_B));
+    const dim3 pgrid((unsigned)((R + QEHVI_PICK - 1) / QEHVI_PICK));
+    const size_t glds = 2 * (size_t)qehvi_buf_doubles(w.ST) * 8, ulds = (size_t)w.ST * 16;
+    for (int64_t k = 0; k < q; ++k) {
+        t_begin(g, "qehvi_gain");
+        hipLaunchKernelGGL(g_qehvi_narrow ? k_qehvi_gain<true> : k_qehvi_gain<false>, ggrid, dim3(QEHVI_COLS), glds, g->stream, F0, F1, R, S, w);
+        t_end(g);
+        t_begin(g, "qehvi_pick");
+        hipLaunchKernelGGL(k_qehvi_pick, pgrid, dim3(QEHVI_PICK), 0, g->stream, R, S, k, w);
+        t_end(g);
+        t_begin(g, "qehvi_update");
+        hipLaunchKernelGGL(k_qehvi_update, dim3((unsigned)S), dim3(64), ulds, g->stream, F0, F1, R, k, w);
+        t_end(g);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(idx, w.idx, (size_t)q * 8, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(gain, w.gain, (size_t)q * 8, hipMemcpyDeviceToHost, g->stream));
+    return 0;
+}
+
+int bohip_mo_qehvi_select(bohip_gp* g, const double* F0, const double* F1, int64_t S, int64_t R, const double* front, int64_t n_front,
+                          const double* ref, int64_t q, int64_t* idx, double* gain) {
+    if (!g || !F0 || !F1) return fail(BOHIP_E_ARG, "qehvi_select: null argument");
+    std::vector<double> fr;
+    CHK(mo_make_front("qehvi_select", front, n_front, ref, &fr));
+    CHK(qehvi_check("qehvi_select", R, S, n_front, q, idx, gain));
+    HIPCHK(hipSetDevice(g->device));
+    t_reset(g);
+    QehviWs w{};
+    CHK(ensure_qehvi(g, R, S, n_front, q, ref, &w));
+    const size_t SR = (size_t)S * R;
+    CHK(ensure_sample_matrix(g, SR));
+    HIPCHK(g->qehvi_F1.reserve(SR, g->stream, Grow::Half));
+    HIPCHK(hipMemcpyAsync(g->sjF, F0, SR * 8, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->qehvi_F1, F1, SR * 8, hipMemcpyHostToDevice, g->stream));
+    CHK(qehvi_rounds(g, w, fr, g->sjF, g->qehvi_F1, R, S, n_front, q, idx, gain));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    t_collect(g);
+    return 0;
+}
+
+int bohip_gp_qehvi_batch(bohip_gp* obj0, bohip_gp* obj1, const double* front, int64_t n_front, const double* ref, const double* Xs, int64_t R,
+                         int64_t S, uint64_t seed, double jitter_rel, int max_tries, int64_t q, int64_t* idx, double* gain, double* samples,
+                         double* jitter_used, int* tries_used) {
+    if (!obj0 || !obj1 || !Xs) return fail(BOHIP_E_ARG, "qehvi_batch: null argument");
+    if (obj1->d != obj0->d) return fail(BOHIP_E_ARG, "qehvi_batch: the objectives differ in dimension");
+    if (obj1->device != obj0->device) return fail(BOHIP_E_ARG, "qehvi_batch: the objectives live on different devices");
+    std::vector<double> fr;
+    CHK(mo_make_front("qehvi_batch", front, n_front, ref, &fr));
+    CHK(qehvi_check("qehvi_batch", R, S, n_front, q, idx, gain));
+    if (obj0->n == 0 || obj1->n == 0) return fail(BOHIP_E_STATE, "qehvi_batch: an objective has no observations");
+    for (bohip_gp* m : {obj0, obj1})
+        if (round_up(R, 512) > chunk_cap(m))
+            return fail(BOHIP_E_UNSUPPORTED, "qehvi_batch: R exceeds one candidate chunk (" + std::to_string(chunk_cap(m)) + ")");
+    HIPCHK(hipSetDevice(obj0->device));
+    QehviWs w{};
+    CHK(ensure_qehvi(obj0, R, S, n_front, q, ref, &w));
+    const bool same = obj0 == obj1;
+    const size_t SR = (size_t)S * R;
+    if (same) HIPCHK(obj0->qehvi_F1.reserve(SR, obj0->stream, Grow::Half));
+    // the second objective first, on its own handle and stream: its draws stay in its sjF (one handle for both: they move aside, the
+    // next draw takes sjF), and an event marks them for obj0's stream
+    CHK(sample_joint_core(obj1, "qehvi_batch", Xs, R, S, seed ^ BOHIP_QEHVI_SEED_XOR, jitter_rel, max_tries, true, nullptr, nullptr,
+                          samples ? samples + SR : nullptr, nullptr, jitter_used ? jitter_used + 1 : nullptr,
+                          tries_used ? tries_used + 1 : nullptr, [&]() -> int {
+                              if (same) {
+                                  HIPCHK(hipMemcpyAsync(obj0->qehvi_F1, obj0->sjF, SR * 8, hipMemcpyDeviceToDevice, obj0->stream));
+                              } else {
+                                  HIPCHK(event_of(obj1));
+                                  HIPCHK(hipEventRecord(obj1->ev_con, obj1->stream));
+                              }
+                              return 0;
+                          }));
+    return sample_joint_core(obj0, "qehvi_batch", Xs, R, S, seed, jitter_rel, max_tries, true, nullptr, nullptr, samples, nullptr, jitter_used,
+                             tries_used, [&]() -> int {
+                                 if (!same) HIPCHK(hipStreamWaitEvent(obj0->stream, obj1->ev_con, 0));
+                                 return qehvi_rounds(obj0, w, fr, obj0->sjF, same ? obj0->qehvi_F1 : obj1->sjF, R, S, n_front, q, idx, gain);
+                             });
 }
 
 // ---- two to four objectives (kernels_mom.hip, include/bohip_mom.h) -------------------------------------------------

@@ -26,6 +26,22 @@ size_t qei(const void* base, size_t S, size_t part, size_t NT, size_t q, W* w) {
     w->arrive = w->done + 1;
     return c.total();
 }
+// greedy q-EHVI: [staircases S x ST elements of two doubles, 16-byte rows (the operand of an LDS-DMA) | front 2 n + 3 | lengths S |
+// partials NB x R | records NT | gain q | idx q | done, arrive]
+template <class W>
+size_t qehvi(const void* base, size_t S, size_t ST, size_t nfront, size_t part, size_t NT, size_t q, W* w) {
+    Carve c(base);
+    w->st = c.take<double>(S * ST * 2, 16);
+    w->front = c.take<double>(2 * nfront + 3);
+    w->len = c.take<int>(S);
+    w->part = c.take<double>(part);
+    w->tile = c.take<elem_t<decltype(w->tile)>>(NT, REC_ALIGN);
+    w->gain = c.take<double>(q);
+    w->idx = c.take<long long>(q);
+    w->done = c.take<unsigned>(4);
+    w->arrive = w->done + 1;
+    return c.total();
+}
 // knowledge gradient: [kg E | record | nseg E | a R | B E x R], the last two (nline = R or 0) for the caller's lines only
 template <class W>
 size_t kg(const void* base, size_t E, size_t nline, W* w) {

@@ -1593,6 +1593,45 @@ class MultiObjectiveGPE:
         front, _ = mo_front(self.y, ref)
         return score_mo(self.objectives[0], self.objectives[1], front, ref, xs, want_grad, want_moments)
 
+    def _qehvi_args(self, q):
+        ref = self.reference_point(fix=True)
+        front, _ = mo_front(self.y, ref)
+        q = int(q)
+        return front, ref, q, np.full(max(q, 1), -1, dtype=np.int64), np.zeros(max(q, 1))
+
+    def qehvi_batch(self, xs, q, S=256, seed=0, jitter=1e-12, max_tries=40, want_samples=False):
+        """Greedy Monte-Carlo q-EHVI batch over the columns of xs (bohip_gp_qehvi_batch, include/bohip_qehvi.h; an
+        extension): S joint posterior draws of each member (sample_joint's, the first member's with `seed`, the second's with
+        seed ^ 0x9E3779B97F4A7C15) stay on the device, and q rounds there pick the candidate whose points add the largest
+        sample-average area to the per-draw fronts, which all start as the model's own front above its ref.  The members are not
+        changed.  -> QEIBatch: idx[q] (-1 where nothing could win), gain[q] (the marginal gains; their sum is the batch's q-EHVI
+        estimate), jitter[2], tries[2], samples [2, S, R] or None."""
+        front, ref, q, idx, gain = self._qehvi_args(q)
+        xs = _cols(xs, self.dim)
+        R, S = xs.shape[1], int(S)
+        samples = np.empty((2, S, R)) if want_samples and S > 0 else None
+        jit, tries = np.zeros(2), np.zeros(2, dtype=np.int32)
+        m0, m1 = self.objectives
+        check(m0._lib.bohip_gp_qehvi_batch(m0._h, m1._h, _ptr(front), front.shape[1], _ptr(ref), _ptr(xs), R, S,
+                                           int(seed) & (2 ** 64 - 1), float(jitter), int(max_tries), q,
+                                           idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(gain),
+                                           _ptr(samples) if samples is not None else None, _ptr(jit),
+                                           tries.ctypes.data_as(C.POINTER(C.c_int))))
+        return QEIBatch(idx, gain, jit, tries, samples)
+
+    def qehvi_select(self, F0, F1, q):
+        """The selection of qehvi_batch alone on the caller's S x R draws of the two objectives (bohip_mo_qehvi_select) over the model's
+        own front and ref: the first member supplies the device and the stream only.  -> (idx[q], gain[q])."""
+        front, ref, q, idx, gain = self._qehvi_args(q)
+        F0 = np.ascontiguousarray(np.asarray(F0, dtype=np.float64))
+        F1 = np.ascontiguousarray(np.asarray(F1, dtype=np.float64))
+        if F0.ndim != 2 or F0.shape != F1.shape:
+            raise ValueError(f"F0 and F1 must both be S x R (one draw per row), got shapes {F0.shape} and {F1.shape}")
+        m0 = self.objectives[0]
+        check(m0._lib.bohip_mo_qehvi_select(m0._h, _ptr(F0), _ptr(F1), F0.shape[0], F0.shape[1], _ptr(front), front.shape[1], _ptr(ref), q,
+                                            idx.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(gain)))
+        return idx, gain
+
     def close(self):
         for m in self.objectives:
             m.close()
@@ -1749,6 +1788,9 @@ class ManyObjectiveGPE(MultiObjectiveGPE):
         ref = self.reference_point(fix=True)
         front, _ = mom_front(self.y, ref)
         return score_mom(self.objectives, front, ref, xs, want_grad, want_moments)
+
+    def _qehvi_args(self, q):
+        raise ValueError("greedy q-EHVI (qehvi_batch, qehvi_select) is built for two objectives only: use a MultiObjectiveGPE")
 
 
 class PosteriorPaths:

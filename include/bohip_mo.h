@@ -6,7 +6,7 @@
  *
  * Role: an EXTENSION -- the reference optimises one objective.  The strip form of the two-objective EHVI is that of Emmerich,
  * Yang, Deutz, Wang & Fonseca (2016) and Yang, Emmerich, Deutz & Baeck (2019); Daulton, Balandat & Bakshy (NeurIPS 2020) give the
- * context (q points, many objectives), which is out of scope here.
+ * context (q points, many objectives): q points of two objectives are bohip_qehvi.h, the rest is out of scope here.
  *
  * 1. The quantity.  Both objectives are MAXIMISED.  A reference point r = (r1, r2), finite.  The front F of n points,
  *    0 <= n <= BOHIP_MO_FRONT_MAX: the observations that strictly dominate r in both coordinates and are not weakly dominated by
